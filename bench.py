@@ -22,7 +22,9 @@ Workload (BASELINE.json `configs`):
 The tile is generated on the GPU (tiebrush_amd/synth_dev.py) before the timed region.
 
 Prints ONE JSON line (rank 0).  value = input alignment records collapsed per second, whole job, inputs resident in HBM.
-Extra objects, all measured in this run unless they say otherwise: `roofline` (dominant kernel, HIP events on the launch
+A plain run sets up, warms up, times --steps steps and prints the line; `--dump-outputs DIR` also writes what the last timed step
+computed (groups, intervals, junctions: a seeded sample of at most 2^18 rows each, float64 .npy files) so that two builds can be compared.
+`--full` adds the objects below, all measured in this run unless they say otherwise: `roofline` (dominant kernel, HIP events on the launch
 stream), `roofline_coverage` (cov_tile: median / min / max over >= 10 serialised launches), `kernel_path_host_to_host` (the same
 step with the SoA starting in pinned host memory and every result ending there: H2D + D2H inside the clock, SURVEY.md §8d —
 reported, never `value`), `end_to_end` (the `tiebrush` command line on 32 x 1M-read BAM files written to /tmp, run as a child
@@ -47,6 +49,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s measured stream copy)
+DUMP_ROWS = 1 << 18    # --dump-outputs: rows kept per family (18 float64 arrays of at most this length: 36 MB)
 
 WORKLOADS = {   # profile -> (files per GPU, reads per file, collapse options, description)
     "c2": (2, 1_000_000, {}, "default CIGAR-only"),
@@ -223,8 +226,15 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=0,
                     help="with --force-dist on one GPU: R virtual ranks in this process (loopback collectives), every one with the per-rank workload: "
                          "what the R-way cut search, pack and reduce do, without R GPUs; reported in `emulated_world`, not in `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: end-to-end legs, host -> host leg, CPU baselines, per-kernel rooflines, "
+                         "the multi-rank run's plain-path comparison, the recorded strong-scaling N = 1 reference")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs to DIR/<name>.npy (float64; a seeded sample of at most %d rows per array family)" % DUMP_ROWS)
     args = ap.parse_args()
     args.prof_steps = max(1, args.prof_steps)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` with no WORLD_SIZE in the environment starts its N ranks itself (the reference's counterpart is
     # tiewrap.py:96-126, which starts its own workers): this process never touches a GPU, it only starts and reaps the children.
@@ -238,10 +248,12 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     use_dist = world > 1 or args.force_dist
+    if args.dump_outputs and use_dist:
+        raise SystemExit("bench.py: --dump-outputs writes the single-rank path's outputs; a multi-rank run has no single set of them")
 
     # ---- end to end through the command line: a child process, finished before this process initialises the GPU ----
     e2e = None
-    if rank == 0 and not use_dist and not args.no_e2e:
+    if rank == 0 and not use_dist and args.full and not args.no_e2e:
         e2e = run_e2e_leg(args)
 
     import numpy as np
@@ -507,6 +519,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:                                 # (before anything else reuses the contexts' buffers)
+        dump_outputs(args.dump_outputs, last[(args.steps - 1) % NCTX], torch, np)
     free_b, total_b = torch.cuda.mem_get_info(dev)
     hbm_used_gb = round((total_b - free_b) / 1e9, 1)      # tile + every context's arena and outputs, after the timed region
     if use_dist:
@@ -532,25 +546,28 @@ def main():
     else:
         tot_records, tot_bases = float(n_passed), float(n_bases)
 
-    # ---- multi-rank: the same per-rank workload through the plain single-GPU path, after the timed region (every rank runs it,
-    # nothing is exchanged): what the exchange costs, on the same tile, in the same run ----
+    # ---- multi-rank: the protocol's counts of the timed steps; with --full also the same per-rank workload through the plain
+    # single-GPU path, after the timed region (every rank runs it, nothing is exchanged): what the exchange costs, on the same tile ----
     dist_extra = {}
     if use_dist:
-        ksteps = max(2, min(args.steps, 10))
-        run_plain(min(2, ksteps))
-        torch.cuda.synchronize()
-        dist.barrier()
-        t1 = time.perf_counter()
-        run_plain(ksteps)
-        torch.cuda.synchronize()
-        plain_dt = (time.perf_counter() - t1) / ksteps
-        dist.barrier()
-        pg, pc = next(x for x in last if x is not None)
         nst = max(wire["steps"], 1)
         ph = {k_: round(v / nst, 3) for k_, v in phase_ms.items()}
-        dist_extra = {
-            "plain_ms_per_step": round(plain_dt * 1e3, 4),
-            "plain_records_per_s_per_gpu": round(pg["n_passed"] / plain_dt, 1),
+        if args.full:
+            ksteps = max(2, min(args.steps, 10))
+            run_plain(min(2, ksteps))
+            torch.cuda.synchronize()
+            dist.barrier()
+            t1 = time.perf_counter()
+            run_plain(ksteps)
+            torch.cuda.synchronize()
+            plain_dt = (time.perf_counter() - t1) / ksteps
+            dist.barrier()
+            pg, pc = next(x for x in last if x is not None)
+            dist_extra = {
+                "plain_ms_per_step": round(plain_dt * 1e3, 4),
+                "plain_records_per_s_per_gpu": round(pg["n_passed"] / plain_dt, 1),
+            }
+        dist_extra.update({
             "shuffle_ms_per_step": round(sum(ph.get(k_, 0.0) for k_ in ("cuts", "pack", "exchange", "unpack", "prepare")), 3),
             "wire_bytes_per_step": int(wire["wire_bytes"] / nst),
             "wire_bytes_off_rank_per_step": int(wire["wire_bytes_off_rank"] / nst),
@@ -568,7 +585,7 @@ def main():
                          "rank's own tile, timed after the timed region; shuffle_ms_per_step: host wall time of the main thread between the "
                          "local collapse and the owner's reduce (cut search, pack, exchange, unpack) — it overlaps the worker thread's next "
                          "local collapse; wire bytes: rows x 40 B + CIGAR words, all destinations (off_rank: without the self block)" % NCTX,
-        }
+        })
 
     # ---- R virtual ranks on this one GPU (--force-dist --emulate-world R): every virtual rank holds the per-rank workload (its own files of
     # the synthetic job), the collectives are served in process.  Not a timing of R GPUs — the ranks run one after the other — but the
@@ -604,7 +621,7 @@ def main():
 
     # ---- per-kernel durations (HIP events on the launch stream) -> roofline of the dominant kernel ----
     roof = {}
-    if rank == 0:
+    if rank == 0 and args.full:
         ctx.set_profiling(True)
         acc = {}
 
@@ -702,12 +719,12 @@ def main():
     # bytes per record + the CIGAR words) in pinned memory.  Two contexts, a host thread each, take the sub-tiles in turn: the
     # link carries sub-tile i + 1 in while sub-tile i is collapsed and covered and sub-tile i - 1's results go out.
     host_path = None
-    if rank == 0 and not use_dist and not args.no_host_path:
+    if rank == 0 and not use_dist and args.full and not args.no_host_path:
         host_path = host_to_host_leg(args, torch, np, api, dtile, strat, last, n_records, n_cig_in)
 
     # ---- CPU baseline: the oracle (literal single-threaded restatement of the reference) ----
     cpu = None
-    if rank == 0 and not use_dist and not args.no_cpu_baseline:
+    if rank == 0 and not use_dist and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(args, profile, files, dtile, ctx, strat, n_records)
 
     if rank == 0:
@@ -736,7 +753,7 @@ def main():
             "tiecov": {"bases_covered_per_step": int(n_bases), "bundle_span_bases": int(span), "intervals": int(n_iv), "junctions": int(n_j)},
         }
         line.update(dist_extra)
-        if scaling == "strong" and world > 1:
+        if scaling == "strong" and world > 1 and args.full:
             # the N = 1 end of this fixed job, recorded on an MI355X (profiles/: a run of `--gpus 1 --profile c4 --scaling strong`): the
             # default N = 1 line is config 3, another workload, so a scaling efficiency has to be read against THIS figure
             refs = [os.path.join(ROOT, "profiles", "r%d_bench_%s_strong_n1.json" % (r_, profile)) for r_ in (6, 5, 4)]   # (the newest recorded)
@@ -794,6 +811,31 @@ def main():
         except Exception:
             pass
         print(json.dumps(line), flush=True)
+
+
+def dump_outputs(out_dir, step, torch, np):
+    """One step's results as a caller of api.Context.collapse / coverage receives them (the groups in output order, the intervals,
+    the junctions), written as float64 DIR/<family>_<array>.npy.  A family of more than DUMP_ROWS rows is sampled at the same seeded
+    rows in every run with the same counts (DIR/<family>_row.npy); DIR/counts.npy holds the step's counts."""
+    g, c = step
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "counts.npy"), np.array([g["n_groups"], g["n_passed"], c["n_intervals"], c["n_junctions"], c["n_bases"],
+                                                           c["span_bases"]], np.float64))
+    for fam, bufs, n, names in (("groups", g["_bufs"], g["n_groups"], ("rep", "yc", "yx", "yd", "g_start", "g_end")),
+                                ("intervals", c["_bufs"], c["n_intervals"], ("iv_tid", "iv_start", "iv_end", "iv_val")),
+                                ("junctions", c["_bufs"], c["n_junctions"], ("j_tid", "j_start", "j_end", "j_strand", "j_val"))):
+        n = int(n)
+        if n > DUMP_ROWS:
+            row = np.sort(np.random.Generator(np.random.PCG64(0x71EB)).choice(n, DUMP_ROWS, replace=False))
+        else:
+            row = np.arange(n)
+        np.save(os.path.join(out_dir, "%s_row.npy" % fam), row.astype(np.float64))
+        ti = torch.from_numpy(row).to(bufs[names[0]].device)
+        for k in names:
+            a = bufs[k][:n].index_select(0, ti).to(torch.int64 if k == "rep" else torch.float64)
+            if k == "rep":
+                a = (a & 0xFFFFFFFF).to(torch.float64)    # (uint32 record indices, held in an int32 tensor)
+            np.save(os.path.join(out_dir, "%s_%s.npy" % (fam, k)), a.cpu().numpy())
 
 
 def host_to_host_leg(args, torch, np, api, dtile, strat, last, n_records, n_cig_in):

@@ -17,7 +17,7 @@ def test_bench_two_ranks_contract():
     port = 29800 + (os.getpid() % 1000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--files-per-gpu", "2", "--reads-per-file", "30000", "--no-cpu-baseline"]
+           "--files-per-gpu", "2", "--reads-per-file", "30000", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.strip().split("\n") if l.startswith("{")]
@@ -38,9 +38,9 @@ def test_bench_two_ranks_contract():
 
 
 def test_bench_default_line_contract_small():
-    """the N = 1 line on a small shape: end_to_end and cpu_baseline (1 thread + tiewrap-style processes) are measured in the run"""
+    """the N = 1 line of --full on a small shape: end_to_end and cpu_baseline (1 thread + tiewrap-style processes) are measured in the run"""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--profile", "c3", "--files-per-gpu", "6",
-           "--reads-per-file", "40000", "--e2e-files", "3", "--e2e-reads", "20000", "--e2e-runs", "1", "--cov-prof-reps", "10"]
+           "--reads-per-file", "40000", "--e2e-files", "3", "--e2e-reads", "20000", "--e2e-runs", "1", "--cov-prof-reps", "10", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.strip().split("\n") if l.startswith("{")][-1])
@@ -70,6 +70,42 @@ def test_bench_default_line_contract_small():
     assert ce["cores"] == 1 and ce["value"] > 0 and "tb_cpu_e2e:" in ce["phases"][0] and "end_to_end_seq" in ce["beside"]
     assert ce["parallel"]["value"] > 0 and ce["parallel"]["cores"] >= 2 and "tiewrap" in ce["parallel"]["mode"]
     assert "cpu_baseline" not in es                                     # (moved under cpu_baseline, not left in the leg)
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """a plain N = 1 run measures the headline alone, and --dump-outputs writes what its last timed step computed: float64 arrays
+    within 64 MB that equal the CPU oracle on the same seeded tile (more groups and intervals than the dump keeps: the sampled rows)"""
+    import numpy as np
+    import torch
+
+    from oracle import oracle_ffi as orc
+    from tiebrush_amd import synth, synth_dev
+    files, reads = 8, 150_000
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--profile", "c3",
+           "--files-per-gpu", str(files), "--reads-per-file", str(reads), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.strip().split("\n") if l.startswith("{")][-1])
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["unit"] == "records/s" and d["higher_is_better"] is True
+    assert not {"roofline", "cpu_baseline", "end_to_end", "kernel_path_host_to_host"} & set(d)
+    dumped = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert abs(d["value"] - dumped["counts"][1] / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.02
+    assert all(a.dtype == np.float64 for a in dumped.values()) and sum(a.nbytes for a in dumped.values()) <= 64 << 20
+    tile = synth_dev.tile_to_host(synth_dev.make_tile_device(files, reads, "c3", device="cuda:0", tx=synth.make_transcriptome()))
+    torch.cuda.empty_cache()
+    want = orc.collapse(tile, strategy=2)
+    cw = orc.coverage(synth.collapsed_to_cov_input(tile, want))
+    assert list(dumped["counts"]) == [want["n_groups"], want["n_passed"], cw["n_intervals"], cw["n_junctions"], cw["n_bases"], cw["span_bases"]]
+    assert d["config"]["groups_out"] == want["n_groups"]
+    for fam, names, w in (("groups", ("rep", "yc", "yx", "yd", "g_start", "g_end"), want),
+                          ("intervals", ("iv_tid", "iv_start", "iv_end", "iv_val"), cw),
+                          ("junctions", ("j_tid", "j_start", "j_end", "j_strand", "j_val"), cw)):
+        row = dumped["%s_row" % fam].astype(np.int64)
+        assert len(row) == min(len(w[names[0]]), 1 << 18) and np.all(np.diff(row) > 0)
+        for k in names:
+            assert np.array_equal(dumped["%s_%s" % (fam, k)], np.asarray(w[k]).astype(np.float64)[row]), (fam, k)
+    assert len(dumped["groups_row"]) < want["n_groups"]
 
 
 def test_bench_starts_its_own_ranks():

@@ -6,7 +6,7 @@ O=gpurun_out/${1:-full}; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS:-} > $O/pytest.log 2>&1; rc=$?
 tail -3 $O/pytest.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python - <<P
 import json
 d=json.load(open("$O/bench.json"))

@@ -9,7 +9,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; rc=$
 tail -3 $O/pytest.log
 [ $rc -eq 0 ] || exit $rc
 fi
-COMMON="--no-cpu-baseline --no-host-path --no-e2e"
+COMMON="--full --no-cpu-baseline --no-host-path --no-e2e"
 timeout -k 10 400 python bench.py $COMMON --steps 10 > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python - <<P
 import json

@@ -18,5 +18,5 @@ rm -rf gpurun_out/e2e_prof /tmp/tbk_e2e_prof
 # the end-to-end legs as bench.py runs them (child processes), alone
 python3 tools/e2e_leg.py > $O/e2e_legs.json 2> $O/e2e_legs.err || true
 # the protocol on config 4's per-rank shape: eight emulated ranks, lists against rounds
-python3 bench.py --force-dist --profile c4 --emulate-world 8 --no-cpu-baseline --no-host-path --no-e2e > $O/bench_force_dist_emulate8.json 2> $O/bench_force_dist_emulate8.err
+python3 bench.py --full --force-dist --profile c4 --emulate-world 8 --no-cpu-baseline --no-host-path --no-e2e > $O/bench_force_dist_emulate8.json 2> $O/bench_force_dist_emulate8.err
 echo refresh c done; ls -la $O
