@@ -596,6 +596,23 @@ def test_device_writer_refusal_on_a_later_chunk_hands_over_to_the_host_writer(tm
         assert bamio.read_bam(d).n == n
 
 
+@pytest.mark.parametrize("route", ["device", "hybrid"])
+def test_a_route_that_fails_after_writing_groups_does_not_fall_through(tmp_path, route):
+    """The device writer writes the first chunk (256 groups), refuses the next one, and then the fetch of the representatives' records
+    fails (TBK_TEST_FETCH_ENOMEM).  Handing the inputs to the streaming route would write every group again behind the 256 in the file:
+    the run has to fail instead, and say how many groups were written."""
+    env = dict(os.environ, TBK_DW_CHUNK_GROUPS="256", TBK_TEST_DW_REFUSE_CHUNK="1", TBK_TEST_FETCH_ENOMEM="1")
+    if route == "device":
+        env["TBK_DEVICE_DECODE"] = "1"
+        paths = [os.path.join(GOLDEN, "t12.bam")]
+    else:
+        env["TBK_HYBRID"] = "1"
+        paths = sample_paths("t2")
+    r = subprocess.run([os.path.join(BIN, "tiebrush"), "-o", str(tmp_path / "o.bam")] + paths, capture_output=True, text=True, env=env, timeout=300)
+    assert r.returncode != 0, r.stderr[-600:]
+    assert "after 256 groups were written" in r.stderr, r.stderr[-600:]
+
+
 def test_tiebrush_ranks_four_ranks_equal_single_gpu(tmp_path):
     """ten files over four ranks (3 + 3 + 2 + 2): the multi-rank command line ends in the single-GPU run's BAM, record for record (four
     processes share the box's GPU through the gloo hook: what its process guard leaves beside the test runner)"""

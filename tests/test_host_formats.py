@@ -171,10 +171,12 @@ def test_host_write_path_of_the_ranks_tool(tmp_path):
     assert [H.tbh_is_tiebrush(p.encode()) for p in src] == [0, 1]
     parts = []
     want = []
-    for pi, p in enumerate(src):
+    # (the third part: t1s0's records over and over, more than 16384 of them — several slices, written in slice order)
+    for pi, (p, many) in enumerate([(src[0], False), (src[1], False), (src[0], True)]):
         b = bamio.read_bam(p, keep_aux=True)
-        n = min(b.n, 3000)
-        recs = [bamio.record_bytes(b, i) for i in range(n)]           # raw records without block_size
+        n = 40000 if many else min(b.n, 3000)
+        idx = [i % b.n for i in range(n)]
+        recs = [bamio.record_bytes(b, i) for i in idx]                # raw records without block_size
         blob = np.frombuffer(b"".join(recs), np.uint8).copy()
         ln = np.array([len(r) for r in recs], np.uint32)
         off = np.concatenate([[0], np.cumsum(ln)])[:-1].astype(np.uint64)
@@ -186,11 +188,11 @@ def test_host_write_path_of_the_ranks_tool(tmp_path):
         assert H.tbh_tag_deflate_part(blob.ctypes.data, off.ctypes.data, ln.ctypes.data, n, yc.ctypes.data, yx.ctypes.data, yd.ctypes.data, 6, 3,
                                       part.encode()) == 0, H.tbh_last_error()
         parts.append(part)
-        for i in range(n):
+        for i, j in enumerate(idx):
             # (an older integer-typed YC stays as it is: bam_aux_update_float refuses a non-float tag and the reference ignores
             # the return value, GSam.h:303-305 — the golden BAMs of 0.0.6 carry YC:i)
-            old = {t: ty for t, ty, _ in bamio.record_aux(b, i)}.get("YC")
-            want.append((bamio.record_identity(b, i), float(b.yc[i]) if old not in (None, "f", "d") else float(np.float32(yc[i])), int(yx[i]), int(yd[i]),
+            old = {t: ty for t, ty, _ in bamio.record_aux(b, j)}.get("YC")
+            want.append((bamio.record_identity(b, j), float(b.yc[j]) if old not in (None, "f", "d") else float(np.float32(yc[i])), int(yx[i]), int(yd[i]),
                          "f" if old in (None, "f", "d") else old))
     out = str(tmp_path / "o.bam")
     arr = lambda xs: (C.c_char_p * len(xs))(*[x.encode() for x in xs])

@@ -4,6 +4,11 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <atomic>
+#include <condition_variable>
+#include <mutex>
+#include <thread>
 #include <vector>
 
 #include "bam.h"
@@ -30,5 +35,60 @@ bool tag_and_deflate(uint32_t g0, uint32_t g1, RecOf rec, const double* yc, cons
   for (uint32_t g = g0; g < g1; ++g) append_tagged(rec(g), yc[g], yx[g], yd[g], framed, scratch);
   // BGZF members are independent deflate streams: the slice compresses itself, the writer only appends
   return bgzf_deflate_members(framed.data(), framed.size(), level, members);
+}
+
+// flushPData's tagging of the groups [0, n) (tiebrush.cpp:506-525): the groups are independent, so `threads` workers tag, frame and
+// deflate slices of them (tag_and_deflate), taking the next slice as they come free (a static split leaves the cores that drew sparse
+// regions idle).  The calling thread hands every slice's BGZF members to emit(data, size) in slice order, as soon as that slice and all
+// earlier ones are out.  Slices: one when n < 4096 or per == 0, otherwise `per` groups each.  Slice ends are member ends: the rule
+// fixes the output's bytes.  false when a deflate fails or emit returns false.
+template <class RecOf, class Emit>
+bool tag_deflate_ordered(uint32_t n, RecOf rec_of, const double* yc, const int64_t* yx, const int32_t* yd, int level, int threads, Emit emit,
+                         uint32_t per = 16384) {
+  const int nt = n < 4096 ? 1 : std::max(1, threads);
+  if (n < 4096 || per == 0) per = n ? n : 1;
+  const uint32_t nsl = n ? (n + per - 1) / per : 0;
+  std::vector<std::vector<uint8_t>> runs((size_t)nsl);
+  std::vector<std::atomic<int>> ready(nsl);  // (value-initialised: 0)
+  std::atomic<uint32_t> next_slice{0};
+  // the emitting thread sleeps until the slice it needs is out (no spinning beside fully subscribed workers); a worker that fails
+  // says so here and the calling thread reports it once every worker has stopped
+  std::mutex ready_m;
+  std::condition_variable ready_cv;
+  std::atomic<bool> failed{false};
+  auto worker = [&]() {
+    std::vector<uint8_t> o;
+    o.reserve((size_t)per * 96);
+    BamRec rr;
+    for (;;) {
+      const uint32_t sl = next_slice.fetch_add(1);
+      if (sl >= nsl) break;
+      // (after a failure: stop working, but let the emitter's wait for this slice end)
+      const uint32_t g0 = sl * per;
+      if (!failed.load() && !tag_and_deflate(g0, g0 + std::min(per, n - g0), rec_of, yc, yx, yd, level, o, rr, runs[(size_t)sl])) failed.store(true);
+      std::lock_guard<std::mutex> lk(ready_m);
+      ready[sl].store(1, std::memory_order_release);
+      ready_cv.notify_all();
+    }
+  };
+  std::vector<std::thread> th;
+  if (nt > 1)
+    for (int t = 0; t < nt; ++t) th.emplace_back(worker);
+  else
+    worker();
+  for (uint32_t sl = 0; sl < nsl; ++sl) {
+    if (!ready[sl].load(std::memory_order_acquire)) {
+      std::unique_lock<std::mutex> lk(ready_m);
+      ready_cv.wait(lk, [&] { return ready[sl].load(std::memory_order_acquire) != 0; });
+    }
+    if (failed.load()) break;
+    if (!emit(runs[(size_t)sl].data(), runs[(size_t)sl].size())) {
+      failed.store(true);
+      break;
+    }
+    std::vector<uint8_t>().swap(runs[(size_t)sl]);
+  }
+  for (auto& x : th) x.join();
+  return !failed.load();
 }
 }  // namespace tbh

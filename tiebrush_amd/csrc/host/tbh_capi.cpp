@@ -4,9 +4,7 @@
 #include <string.h>
 #include <unistd.h>
 
-#include <atomic>
 #include <string>
-#include <thread>
 #include <vector>
 
 #include "../../../include/tbh_host.h"
@@ -32,41 +30,21 @@ int tbh_tag_deflate_part(const uint8_t* blob, const uint64_t* rec_off, const uin
                          const int32_t* yd, int level, int threads, const char* out_path) {
   if (!out_path || (n && (!blob || !rec_off || !rec_len || !yc || !yx || !yd))) return fail("tbh_tag_deflate_part: null argument");
   int nt = threads > 0 ? threads : tbh::cpu_budget();
-  if (nt < 1) nt = 1;
   if (nt > 128) nt = 128;
-  if (n < 4096) nt = 1;
-  // slices of 16 K records taken by the workers as they come free; every slice deflates itself into its own run of members
-  const uint32_t per = 16384, nsl = n ? (n + per - 1) / per : 0;
-  std::vector<std::vector<uint8_t>> runs((size_t)nsl);
-  std::atomic<uint32_t> next{0};
-  std::atomic<bool> bad{false};
   auto rec = [&](uint32_t g) {
     tbh::RecView v;
     v.p = blob + rec_off[g];
     v.len = rec_len[g];
     return v;
   };
-  auto worker = [&]() {
-    std::vector<uint8_t> framed;
-    tbh::BamRec scratch;
-    for (;;) {
-      const uint32_t sl = next.fetch_add(1);
-      if (sl >= nsl || bad.load()) break;
-      const uint32_t g0 = sl * per, g1 = g0 + per < n ? g0 + per : n;
-      if (!tbh::tag_and_deflate(g0, g1, rec, yc, yx, yd, level, framed, scratch, runs[(size_t)sl])) bad.store(true);
-    }
-  };
-  std::vector<std::thread> th;
-  for (int t = 1; t < nt; ++t) th.emplace_back(worker);
-  worker();
-  for (auto& x : th) x.join();
-  if (bad.load()) return fail("tbh_tag_deflate_part: deflate failed");
   FILE* f = fopen(out_path, "wb");
   if (!f) return fail(std::string("tbh_tag_deflate_part: cannot open ") + out_path);
-  bool ok = true;
-  for (auto& r : runs) ok = ok && (r.empty() || fwrite(r.data(), 1, r.size(), f) == r.size());
-  ok = (fclose(f) == 0) && ok;
-  return ok ? 0 : fail(std::string("tbh_tag_deflate_part: write failed on ") + out_path);
+  bool wrote = true;
+  auto emit = [&](const uint8_t* p, size_t sz) { return wrote = fwrite(p, 1, sz, f) == sz; };
+  const bool ok = tbh::tag_deflate_ordered(n, rec, yc, yx, yd, level, nt, emit);
+  if (fclose(f) == 0 && ok) return 0;
+  (void)unlink(out_path);  // (no half-written part is left behind)
+  return fail(ok || !wrote ? std::string("tbh_tag_deflate_part: write failed on ") + out_path : std::string("tbh_tag_deflate_part: deflate failed"));
 }
 
 int tbh_write_bam_parts(const char* out_path, const char* version, int cmd_argc, const char* const* cmd_argv, int n_files, const char* const* files,

@@ -134,13 +134,48 @@ struct FileMap {
   }
 };
 
+using Clock = std::chrono::steady_clock::time_point;
+static Clock tnow() { return std::chrono::steady_clock::now(); }
+static double tms(Clock a, Clock b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+using RecFn = std::function<tbh::RecView(uint32_t)>;
+using PrefetchFn = std::function<void(uint32_t, int)>;
+
+static bool env_set(const char* name) { return getenv(name) != nullptr; }
+static long long env_num(const char* name, long long unset) { return getenv(name) ? atoll(getenv(name)) : unset; }
+
+// Every TBK_* variable this file reads, read once at start-up (devwriter.h reads its own tuning and test hooks).
+struct Env {
+  bool timing = env_set("TBK_TIMING");  // phase lines on stderr
+  // (TBK_TIMING=2: the calls' kernels too, through the library's HIP events — two events per launch are themselves milliseconds of a
+  // run this short, so the phase lines of TBK_TIMING=1, which the bench's end-to-end legs run under, come without them)
+  bool ktiming = env_num("TBK_TIMING", 0) > 1;
+  int device = (int)env_num("TBK_DEVICE", 0);
+  bool threads_set = env_set("TBK_THREADS");  // the host's worker threads: the CPU budget (1..128) or TBK_THREADS
+  int threads = threads_set ? std::max(1, (int)env_num("TBK_THREADS", 1)) : std::min(128, std::max(1, tbh::cpu_budget()));
+  bool host_fast_off = env_num("TBK_HOST_FAST", 1) == 0;
+  bool hybrid_off = env_num("TBK_HYBRID", 1) == 0, hybrid_on = env_num("TBK_HYBRID", 0) != 0;
+  bool hybrid_share_set = env_set("TBK_HYBRID_SHARE");  // the device's share of the hybrid decode, per cent
+  double hybrid_share = hybrid_share_set ? atof(getenv("TBK_HYBRID_SHARE")) : 0;
+  bool device_decode_set = env_set("TBK_DEVICE_DECODE"), device_decode_on = env_num("TBK_DEVICE_DECODE", 0) != 0;
+  uint64_t device_decode_max = (uint64_t)env_num("TBK_DEVICE_DECODE_MAX", (long long)6 << 30);
+  bool tile_records_set = env_set("TBK_TILE_RECORDS");  // records per streamed tile
+  size_t tile_records = (size_t)env_num("TBK_TILE_RECORDS", (long long)64 << 20);
+  bool no_warmup = env_set("TBK_NO_WARMUP");
+  bool dw_one_encoder = env_set("TBK_DW_ONE_ENCODER");    // no second context for the device writer
+  bool no_keep_results = env_set("TBK_NO_KEEP_RESULTS");  // the tags' values come back with the collapse
+  bool test_whole_enomem = env_set("TBK_TEST_WHOLE_ENOMEM");  // test hook: a whole-input collapse reports TBK_ENOMEM
+  bool test_fetch_enomem = env_set("TBK_TEST_FETCH_ENOMEM");  // test hook: the representative-record fetch reports TBK_ENOMEM
+  int exit_timing = (int)env_num("TBK_EXIT_TIMING", -1);      // diagnosis of the process exit (-1: unset)
+  std::string python = getenv("TBK_PYTHON") ? getenv("TBK_PYTHON") : "python3";  // the interpreter that runs --ranks
+};
+
 // `tiebrush --ranks N ...`: the multi-GPU form (tiebrush_amd/ranks.py: one process per GPU over torch.distributed / RCCL, the input
 // files sharded by rank, one output BAM).  The launcher, which starts the ranks, runs as a child of this process.
 static volatile pid_t g_ranks_child = 0;
 static void forward_to_ranks_child(int sig) {
   if (g_ranks_child > 0) kill(g_ranks_child, sig);
 }
-static void maybe_exec_ranks(int argc, char* argv[]) {
+static void spawn_ranks_launcher_if_asked(int argc, char* argv[], const Env& env) {
   bool want = false;
   for (int i = 1; i < argc; ++i) want = want || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
   if (!want) return;
@@ -158,7 +193,7 @@ static void maybe_exec_ranks(int argc, char* argv[]) {
   if (const char* old = getenv("PYTHONPATH")) pp += std::string(":") + old;
   setenv("PYTHONPATH", pp.c_str(), 1);
   std::vector<char*> av;
-  const char* py = getenv("TBK_PYTHON") ? getenv("TBK_PYTHON") : "python3";
+  const char* py = env.python.c_str();
   av.push_back(const_cast<char*>(py));
   av.push_back(const_cast<char*>("-m"));
   av.push_back(const_cast<char*>("tiebrush_amd.ranks"));
@@ -182,8 +217,773 @@ static void maybe_exec_ranks(int argc, char* argv[]) {
   _exit(WIFEXITED(status) ? WEXITSTATUS(status) : 128 + (WIFSIGNALED(status) ? WTERMSIG(status) : 0));
 }
 
+// The inputs as the routes see them.
+struct Inputs {
+  std::vector<std::string> paths;
+  std::vector<uint64_t> size;    // compressed bytes (0 when stat fails)
+  std::vector<uint8_t> merged;   // TieBrush-merged: their tags are updated in place
+  uint64_t total = 0;
+  bool all_bgzf = true, any_merged = false, all_sized = true;  // (SAM text inputs are decoded by the streaming reader)
+  explicit Inputs(const TInputFiles& in) {
+    for (const TSamReader* r : in.freaders) {
+      struct stat st;
+      const bool sized = stat(r->fname.c_str(), &st) == 0;
+      paths.push_back(r->fname);
+      size.push_back(sized ? (uint64_t)st.st_size : 0);
+      merged.push_back(r->tbMerged ? 1 : 0);
+      total += size.back();
+      all_bgzf = all_bgzf && tbh::bgzf_probe(r->fname);
+      any_merged = any_merged || r->tbMerged;
+      all_sized = all_sized && sized;
+    }
+  }
+};
+
+// Which routes may take the inputs.  They are tried in this order; one that gives up hands the inputs over to the next eligible one
+// (the whole-input host loader excepted: it does not run after a hybrid decode that gave up), and the streaming route takes the rest.
+//   route          inputs                                          options          environment
+//   hybrid         >= 2, all BGZF, none TieBrush-merged,           not -L, not -A   TBK_HOST_FAST != 0, TBK_HYBRID != 0, TBK_TILE_RECORDS
+//                  >= 768 MB in all unless TBK_HYBRID != 0                          unset, TBK_DEVICE_DECODE unset (any value, 0 too, turns it off)
+//   whole host     >= 1, all BGZF, within host_budget() (the       not -L, not -A   TBK_HOST_FAST != 0, TBK_DEVICE_DECODE unset or 0,
+//                  loader finds out; else it gives up)                              TBK_TILE_RECORDS unset
+//   device decode  all BGZF, 0 < total <= TBK_DEVICE_DECODE_MAX    any              TBK_DEVICE_DECODE != 0 (opt in: with libdeflate on every
+//                  (6 GiB)                                                          core the host is faster end to end)
+//   streaming      everything else
+struct Routes {
+  bool hybrid, whole_host, device_decode;
+};
+static Routes eligible_routes(const Env& e, const tbk_collapse_opts& opt, const Inputs& in) {
+  const bool host = !e.host_fast_off && !e.tile_records_set && opt.strategy != TBK_STRAT_FULL && !opt.collapse_same;
+  Routes r;
+  r.hybrid = host && in.paths.size() >= 2 && in.all_bgzf && !in.any_merged && in.all_sized && !e.hybrid_off && !e.device_decode_set &&
+             (e.hybrid_on || in.total >= ((uint64_t)768 << 20));
+  r.whole_host = host && !e.device_decode_on && in.all_bgzf && !in.paths.empty();
+  r.device_decode = e.device_decode_on && in.all_bgzf && in.total > 0 && in.total <= e.device_decode_max;
+  return r;
+}
+
+// The device's bring-up.  Binding libtbk.so (the HIP runtime comes with it) and bringing the device up take ~0.3 s: both happen on a
+// helper thread while the inputs are opened, inflated and parsed.  The thread brings the device up and then warms the context.  A caller
+// that can use the context the moment it exists — the hybrid route's device decode — says so (take_now) and gets it unwarmed: it runs
+// the warm-up itself (warm_own) when its decode is done and the cores are still busy with their share.
+class Device {
+ public:
+  TbkApi api;
+  tbk_ctx* ctx = nullptr;
+  DeviceWriter* dw = nullptr;  // (pinned staging: lives until the process ends)
+  const Clock t_start;         // the run's start
+  double ms_ready = 0;         // the context existed this long after it
+
+  Device(const Env& env, const tbk_collapse_opts& opt, bool dev_writer, Clock start) : t_start(start), env_(env), opt_(opt) {
+    thread_ = std::thread([this, dev_writer] { bring_up(dev_writer); });
+  }
+  // the context, warmed (this joins the helper thread)
+  void wait() {
+    if (joined_) return;
+    thread_.join();
+    joined_ = true;
+    check();
+  }
+  // the context as soon as it exists, unwarmed; the helper thread is NOT joined here
+  void take_now() {
+    urgent_.store(true);
+    std::unique_lock<std::mutex> lk(m_);
+    cv_.wait(lk, [&] { return created_ && !warming_; });
+    lk.unlock();
+    check();
+  }
+  // the context's own part of the warm-up (the helper thread leaves it to the caller of take_now)
+  void warm_own() {
+    if (warm_ || !api_ok_ || rc_ != 0 || env_.no_warmup) return;
+    warm_ = true;
+    (void)api.warmup(ctx);
+  }
+
+ private:
+  const Env& env_;
+  const tbk_collapse_opts opt_;
+  std::thread thread_;
+  bool joined_ = false, api_ok_ = false, warm_ = false;
+  int rc_ = 0;
+  std::mutex m_;
+  std::condition_variable cv_;
+  bool created_ = false, warming_ = false;  // (under m_)
+  std::atomic<bool> urgent_{false};
+
+  void check() {
+    if (!api_ok_) GError("Error: cannot load libtbk.so (%s); this build has no CPU collapse path\n", api.error.c_str());
+    if (rc_ != 0) GError("Error: cannot use GPU %d (%s); this build has no CPU collapse path\n", env_.device, api.strerror_(rc_));
+  }
+  void bring_up(bool dev_writer) {
+    api_ok_ = api.load();
+    if (api_ok_) rc_ = api.create(env_.device, &ctx);
+    if (api_ok_ && rc_ == 0 && dev_writer) dw = new DeviceWriter(api, tbh::cpu_budget());
+    ms_ready = tms(t_start, tnow());
+    bool warm_here;
+    {
+      std::lock_guard<std::mutex> lk(m_);
+      created_ = true;
+      warm_here = !urgent_.load();
+      warming_ = warm_here;
+    }
+    cv_.notify_all();
+    // (page-locking the writer's staging buffers: ~ 12 ms, beside the decode — and behind the hand-over: a decode that waits for the
+    // context does not wait for this)
+    if (dw) (void)dw->reserve();
+    // ... and a second context for the writer's second encode thread (its queue: ~ 10 ms to create)
+    if (dw && !env_.dw_one_encoder) {
+      tbk_ctx* c2 = nullptr;
+      if (api.create(env_.device, &c2) == 0) dw->set_second(c2);
+    }
+    const bool can_warm = api_ok_ && rc_ == 0 && !env_.no_warmup;
+    if (warm_here) {
+      if (can_warm) warm_process(ctx), warm_own();
+      {
+        std::lock_guard<std::mutex> lk(m_);
+        warming_ = false;
+      }
+      cv_.notify_all();
+    } else if (can_warm) {
+      // the context is in use already (the hybrid route's device decode): the process-wide part on a context of this thread's own,
+      // beside that decode; the decode thread does the context's part when its call has returned
+      tbk_ctx* wc = nullptr;
+      if (api.create(env_.device, &wc) == 0) {
+        warm_process(wc);
+        api.destroy(wc);
+      }
+    }
+  }
+  // What a first call pays beyond its kernels, paid ahead: (a) for the PROCESS — the library's code objects mapped onto the device by a
+  // first launch, the copy engines' first use — with one tiny collapse and tbk_warmup on whatever context `c` is; (b) for the context
+  // that will run the real call — its second queue, its list machines' first dispatch, its staging buffer: tbk_warmup(ctx), warm_own.
+  void warm_process(tbk_ctx* c) {
+    // (65 inputs of one record each: more than 64 inputs take the window path, whose kernels — the larger part of the library's
+    // device code — would otherwise be mapped by the first real collapse)
+    constexpr uint32_t WK = 65;
+    uint32_t fo[WK + 1], co[WK + 1], cg[WK];
+    uint8_t tb0[WK], mq[WK], st[WK];
+    int32_t ti[WK], po[WK], nh[WK];
+    uint16_t fl[WK];
+    for (uint32_t i = 0; i < WK; ++i) fo[i] = co[i] = i, cg[i] = 50u << 4, tb0[i] = 0, mq[i] = 60, st[i] = '.', ti[i] = 0, po[i] = 10, nh[i] = 1, fl[i] = 0;
+    fo[WK] = co[WK] = WK;
+    tbk_soa_in w;
+    memset(&w, 0, sizeof(w));
+    w.mem = TBK_MEM_HOST;
+    w.n_files = WK, w.n_records = WK, w.n_cigar_ops = WK;
+    w.file_off = fo, w.tbmerged = tb0, w.tid = ti, w.pos = po, w.flag = fl, w.mapq = mq, w.strand = st, w.nh = nh, w.cig_off = co, w.cig = cg;
+    uint32_t wrep[WK];
+    double wyc[WK];
+    int64_t wyx[WK];
+    int32_t wyd[WK];
+    tbk_groups_out wo;
+    memset(&wo, 0, sizeof(wo));
+    wo.mem = TBK_MEM_HOST;
+    wo.cap_groups = WK;
+    wo.rep = wrep, wo.yc = wyc, wo.yx = wyx, wo.yd = wyd;
+    tbk_collapse_opts wopt = opt_;
+    (void)api.collapse_tile(c, &wopt, &w, &wo);
+    if (c != ctx) (void)api.warmup(c);  // (the engines; ctx gets its own call: warm_own)
+  }
+};
+
+// The output side: the BAM file, the whole-input routes' result arrays, and what went into the file.
+class Output {
+ public:
+  // the whole-input routes' results (size_results: a value-initialising resize of 32 M entries x 24 B costs more than the collapse)
+  RawBuf<uint32_t> rep;
+  RawBuf<double> yc;
+  RawBuf<int64_t> yx;
+  RawBuf<int32_t> yd;
+  uint64_t groups = 0;                  // groups in the file
+  double ms_dev_write = 0;              // the device writer's time, its bytes of tagged records and of BGZF members
+  uint64_t dev_payload = 0, dev_z = 0;
+
+  Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env) : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env) {}
+  // (the end of the file: the EOF member)
+  void close() { file_.reset(); }
+  // whether the whole-input routes leave the tags' values on the device for the device writer (tbk_collapse_opts.keep_results)
+  bool keep_results() const { return dev_.dw && file_->level() != 0 && !env_.no_keep_results; }
+
+  // Groups [0, ng) of one collapse: rep / yc / yx / yd are host arrays in output order (yc == nullptr: the values stayed on the device,
+  // keep_results).  The device writer takes them when there is one (devwriter.h; c: its context): tags, framing and BGZF deflate as
+  // kernels, the host only gathers the records it decoded itself (rec(g) for rep[g] >= n_dev) and appends the finished members.  From
+  // the group it refuses on, the host writer goes on — after before_host(), which readies what rec() reads for it.  When that fails,
+  // write returns false; the groups before the refused one are in the file (groups says how many).
+  bool write(tbk_ctx* c, uint32_t ng, const uint32_t* rp, const double* ycp, const int64_t* yxp, const int32_t* ydp, uint32_t n_dev, const RecFn& rec,
+             const PrefetchFn& prefetch = nullptr, const std::function<bool()>& before_host = nullptr) {
+    uint32_t done = 0;
+    if (c && dev_.dw && file_->level() != 0) {
+      auto a = tnow();
+      uint64_t pb = 0, zb = 0;
+      std::string why;
+      const bool ok = dev_.dw->write(c, *file_, ng, rp, ycp, yxp, ydp, n_dev, rec, &pb, &zb, why, &done, prefetch);
+      ms_dev_write += tms(a, tnow()), dev_payload += pb, dev_z += zb;
+      groups += ok ? ng : done;
+      if (ok) return true;
+      if (env_.timing) fprintf(stderr, "device writer stopped after %u of %u groups (%s): host writer\n", done, ng, why.c_str());
+    }
+    if (before_host && !before_host()) return false;
+    if (ng <= done) return true;
+    if (!ycp) {  // (the host writer fetches the values of the groups it writes)
+      yc.resize(ng), yx.resize(ng), yd.resize(ng);
+      const int frc = dev_.api.kept_results(c, done, ng - done, nullptr, yc.data() + done, yx.data() + done, yd.data() + done);
+      if (frc != 0) GError("Error: fetching the collapse's results failed: %s (%s)\n", dev_.api.strerror_(frc), dev_.api.last_error(c));
+      ycp = yc.data(), yxp = yx.data(), ydp = yd.data();
+    }
+    // flushPData's tagging on every core (tagwrite.h); one slice when a single thread writes
+    auto from_done = [&](uint32_t g) { return rec(done + g); };
+    auto emit = [&](const uint8_t* z, size_t n) { return file_->write_members(z, n), true; };
+    if (!tbh::tag_deflate_ordered(ng - done, from_done, ycp + done, yxp + done, ydp + done, file_->level(), env_.threads, emit, env_.threads > 1 ? 16384 : 0))
+      GError("Error: deflate failed\n");
+    groups += ng - done;
+    return true;
+  }
+
+  // A route that cannot finish hands the inputs over to the next one, which writes from group 0: only while the file holds no groups.
+  void fall_through(const char* what, const std::string& why) {
+    if (groups) GError("Error: %s (%s) after %llu groups were written\n", what, why.c_str(), (unsigned long long)groups);
+    if (env_.timing) fprintf(stderr, "%s (%s): streaming host path\n", what, why.c_str());
+    rep.resize(0);  // (drops pages borrowed from the route's input tile)
+  }
+
+ private:
+  std::unique_ptr<GSamWriter> file_;
+  Device& dev_;
+  const Env& env_;
+};
+
+// What the summary lines count.
+struct Totals {
+  double ms_load = 0, ms_gpu = 0, ms_tag = 0, ms_inflate = 0;
+  uint64_t in = 0, out = 0;
+  size_t n_tiles = 0;
+};
+
+enum class Route { done, fall_through };
+
+// a whole-input route's end: one tile
+static Route account_whole(Totals& t, const tbk_groups_out& res, double ms_inflate, double ms_gpu, double ms_tag) {
+  t.ms_inflate += ms_inflate, t.ms_gpu += ms_gpu, t.ms_tag += ms_tag;
+  t.in += res.n_passed, t.out += res.n_groups;
+  t.n_tiles = 1;
+  return Route::done;
+}
+
+static std::string why_rc(Device& dev, int rc) { return std::string(dev.api.strerror_(rc)) + ": " + dev.api.last_error(dev.ctx); }
+
+// TBK_TIMING=2: the kernels of the call just made (HIP events) — what of its wall time the GPU was busy with
+static void print_kernel_times(Device& dev, const char* call, double ms_call) {
+  tbk_kernel_time kt[64];
+  const int nk = dev.api.kernel_times(dev.ctx, kt, 64);
+  std::string line = std::string(call) + " kernels ms:";
+  double sum = 0;
+  for (int i = 0; i < nk; ++i) {
+    char b[96];
+    snprintf(b, sizeof(b), " %s %.1f (%u)", kt[i].name, kt[i].ms, kt[i].launches);
+    line += b;
+    sum += kt[i].ms;
+  }
+  fprintf(stderr, "%s | sum %.1f of the call's %.1f\n", line.c_str(), sum, ms_call);
+  (void)dev.api.set_profiling(dev.ctx, 0);
+}
+
+// The results of a collapse of n records: host arrays (none when `arrays` is false: the results stay on the device) sized by the upper
+// bound, one group per record, but never initialised — the pages a call does not write are never touched.
+static void size_results(tbk_groups_out* res, size_t n, RawBuf<uint32_t>& rep, RawBuf<double>& yc, RawBuf<int64_t>& yx, RawBuf<int32_t>& yd,
+                         bool arrays = true) {
+  if (n == 0) n = 1;
+  memset(res, 0, sizeof(*res));
+  res->mem = TBK_MEM_HOST;
+  res->cap_groups = (uint32_t)n;
+  if (!arrays) return;
+  rep.resize(n), yc.resize(n), yx.resize(n), yd.resize(n);
+  res->rep = rep.data(), res->yc = yc.data(), res->yx = yx.data(), res->yd = yd.data();
+}
+
+// One collapse of a whole-input tile into out's arrays.  keep: the tags' values stay on the device for the device writer
+// (keep_results), and only `rep` comes back, once the number of groups is known — into pages that are resident already when a dead
+// array of the host's input tile (`dead`, 4 bytes a record) is long enough: a fresh block of tens of megabytes is faulted in at
+// 1-2 GB/s this late in the run.  An unsorted input is fatal; any other code is the caller's.
+static int collapse_whole(Device& dev, Output& out, const Env& env, tbk_collapse_opts opt, bool keep, tbk_soa_in* in, tbk_groups_out* res,
+                          int32_t* dead = nullptr, size_t dead_n = 0) {
+  size_results(res, in->n_records, out.rep, out.yc, out.yx, out.yd, !keep);
+  opt.keep_results = keep ? 1 : 0;
+  auto a = tnow();
+  if (env.ktiming) (void)dev.api.set_profiling(dev.ctx, 1);
+  int rc = dev.api.collapse_tile(dev.ctx, &opt, in, res);
+  if (rc == 0 && env.test_whole_enomem) rc = TBK_ENOMEM;  // test hook: exercise the fall-through
+  if (rc == 0 && keep) {
+    const uint32_t ng = res->n_groups;
+    if (dead && ng <= dead_n) out.rep.borrow((uint32_t*)dead, dead_n);
+    else out.rep.resize(ng ? ng : 1);
+    auto f0 = tnow();
+    const int frc = dev.api.kept_results(dev.ctx, 0, ng, out.rep.data(), nullptr, nullptr, nullptr);
+    if (frc != 0) GError("Error: fetching the collapse's results failed: %s (%s)\n", dev.api.strerror_(frc), dev.api.last_error(dev.ctx));
+    if (env.timing) fprintf(stderr, "representatives of %u groups fetched in %.1f ms (%s)\n", ng, tms(f0, tnow()), out.rep.borrowed ? "into the input tile's pages" : "into a new block");
+  }
+  if (env.ktiming) print_kernel_times(dev, "collapse call", tms(a, tnow()));
+  if (rc == TBK_EUNSORTED) GError("Error: an input file is not coordinate-sorted!\n");
+  return rc;
+}
+
+// The raw records of n representatives of the tile tbk_bam_decode left on the device (ids: its record indices): record i at
+// blob[roff[i] + 4, roff[i + 1]) (the block_size field first).  `guess`: bytes a record, for the first try; a blob too small
+// (TBK_E2BIG) is grown to what it takes and asked once more.
+static int fetch_device_records(Device& dev, const Env& env, const uint32_t* ids, uint32_t n, size_t guess, RawBuf<uint8_t>& blob, RawBuf<uint64_t>& roff) {
+  roff.resize((size_t)n + 1);
+  blob.resize((size_t)n * guess + 4096);
+  int rc = dev.api.bam_records(dev.ctx, ids, n, TBK_MEM_HOST, blob.data(), blob.size(), roff.data());
+  if (rc == TBK_E2BIG) {
+    blob.resize(roff[n]);
+    rc = dev.api.bam_records(dev.ctx, ids, n, TBK_MEM_HOST, blob.data(), blob.size(), roff.data());
+  }
+  if (rc == 0 && env.test_fetch_enomem) rc = TBK_ENOMEM;  // test hook: a fetch that fails behind groups already written
+  return rc;
+}
+
+// half of what the host may still use (MemAvailable, the cgroup's limit): what the whole-input loaders may fill with inflated inputs
+static size_t host_budget() {
+  size_t budget = (size_t)8 << 30;
+  if (FILE* mf = fopen("/proc/meminfo", "r")) {
+    char line[256];
+    while (fgets(line, sizeof(line), mf))
+      if (strncmp(line, "MemAvailable:", 13) == 0) budget = (size_t)atoll(line + 13) * 1024 / 2;
+    fclose(mf);
+  }
+  if (FILE* cf = fopen("/sys/fs/cgroup/memory.max", "r")) {
+    char q[64];
+    if (fscanf(cf, "%63s", q) == 1 && strcmp(q, "max") != 0) budget = std::min<size_t>(budget, (size_t)atoll(q) / 2);
+    fclose(cf);
+  }
+  return budget;
+}
+
+// ---- hybrid decode: records with SEQ / QUAL are ~ 240 inflated bytes each and the run is BGZF on the host's cores (SURVEY.md
+// §8 f1).  The GPU inflates and decodes the first files of the list (tbk_bam_decode) WHILE the cores inflate and decode the rest
+// (fastload.cpp); tbk_tile_join makes one device tile of the two, the collapse runs on it, and a representative's raw record
+// comes from wherever its file was decoded.  TBK_HYBRID=0 / 1 switches it off / on (default: inputs of 768 MB and more),
+// TBK_HYBRID_SHARE = the device's share of the compressed bytes in per cent.
+static Route run_hybrid(Device& dev, Output& out, const tbk_collapse_opts& opt, const Env& env, const Inputs& inp, Totals& tot) {
+  const size_t k = inp.paths.size();
+  // The device's share of the compressed bytes: both sides should end together.  The device starts late — the HIP runtime takes
+  // ~ 0.1 s to come up (t_ctx = 0.15: the helper thread's warm-up beside the decode and the context's own behind it cost the
+  // device's side another 0.05), the cores work alone meanwhile — and is then several times faster: with x of T bytes on the device,
+  // t_ctx + x / R_dev = (T - x) / R_host.  Rates measured on an MI355X box with a 16-core quota (round 5's end-to-end legs, tools/e2e_leg.py): the
+  // device side 4.7 GB/s of compressed BAM (upload, inflate, record index, SoA), a core 0.18 GB/s (inflate with the record index
+  // riding along, SoA).  1.8 GB of input: 54 % (17 of 32 files; measured round 6, five runs a share: 16 files 407 ms for the
+  // decode, 17 files 351-361, 18 files 374-382, 19 files 377-384); 7.1 GB: 63 %.  TBK_HYBRID_SHARE (per cent) overrides.
+  const int host_threads = env.threads_set ? env.threads : std::max(2, env.threads - 3);
+  double share;
+  if (env.hybrid_share_set) {
+    share = env.hybrid_share / 100.0;
+  } else {
+    const double T = (double)inp.total / 1e9, r_dev = 4.7, r_host = 0.18 * host_threads, t_ctx = 0.15;
+    const double x = (T / r_host - t_ctx) / (1.0 / r_dev + 1.0 / r_host);
+    share = std::min(0.9, std::max(0.2, x / T));
+  }
+  const std::vector<uint64_t>& fsz = inp.size;
+  size_t kd = 0;
+  uint64_t acc = 0;
+  while (kd + 1 < k && (double)(acc + fsz[kd]) <= share * (double)inp.total + (double)fsz[kd] / 2) acc += fsz[kd++];
+  if (kd == 0) kd = 1;
+  const size_t budget = host_budget();
+  auto t0 = tnow();
+  if (env.timing) fprintf(stderr, "hybrid decode starts at %.1f ms\n", tms(dev.t_start, t0));
+  // the device's share, on a thread of its own: read the files, wait for the context, decode
+  tbk_soa_in in_d;
+  memset(&in_d, 0, sizeof(in_d));
+  std::vector<uint32_t> fo_d(kd + 1, 0);
+  std::vector<uint8_t> tb_d(kd, 0);
+  int rc_d = -1;
+  bool read_ok = true;
+  double ms_dread = 0, ms_ddec = 0, ms_dcall = 0;
+  std::thread dth([&]() {
+    auto d0 = tnow();
+    std::vector<FileMap> comp(kd);
+    for (size_t f = 0; f < kd; ++f)
+      if (!comp[f].map(inp.paths[f]) || comp[f].n != fsz[f]) read_ok = false;
+    auto d1 = tnow();
+    ms_dread = tms(d0, d1);
+    if (!read_ok) return;
+    dev.take_now();
+    auto d2 = tnow();
+    std::vector<const uint8_t*> ptr(kd);
+    for (size_t f = 0; f < kd; ++f) ptr[f] = comp[f].p;
+    if (env.ktiming) (void)dev.api.set_profiling(dev.ctx, 1);
+    rc_d = dev.api.bam_decode(dev.ctx, (uint32_t)kd, ptr.data(), fsz.data(), tb_d.data(), 0, 0, &in_d, fo_d.data());
+    ms_dcall = tms(d2, tnow());
+    if (env.ktiming) print_kernel_times(dev, "device decode", ms_dcall);
+    for (auto& c : comp) c.unmap();
+    if (rc_d == 0 && acc > 0) {  // the arena for the joined tile, sized while the cores are still decoding their share
+      // (tbk_reserve_tile sizes for the window path AND a deferred YD stage that borrows its range of the arena: 165 bytes a record.
+      // This call defers nothing — 84 bytes a record and the CIGAR words —: six tenths of the tile's size asks for what it takes.
+      // An allocation of gigabytes is now and then 20-25 ms per GB of the driver's time)
+      const double up = (double)inp.total / (double)acc * 1.05 * 0.6;
+      (void)dev.api.reserve_tile(dev.ctx, (uint64_t)((double)in_d.n_records * up), (uint64_t)((double)in_d.n_cigar_ops * up));
+    }
+    ms_ddec = tms(d1, tnow());
+    dev.warm_own();  // (the helper thread left the context's own part to this one: take_now)
+  });
+  // the cores' share
+  tbh::FastTile& ft = *new tbh::FastTile();  // (gigabytes, needed until the last record is written: left to the process exit)
+  std::vector<std::string> ph(inp.paths.begin() + (long)kd, inp.paths.end());
+  std::vector<uint8_t> tbh_(k - kd, 0);
+  bool fits = false;
+  std::string err;
+  // (the device's side needs cores too while it runs — the HIP start-up, then the threads that feed the upload ring —, and a
+  // container's CPU quota stalls EVERY thread of the process once the sum goes over it: the loader leaves them room)
+  const bool okh = tbh::fast_load(ph, tbh_, host_threads, budget, ft, &fits, err);
+  dth.join();
+  auto t1 = tnow();
+  dev.wait();  // (the helper thread ended long ago; this only joins it)
+  if (!okh) GError("Error: reading the input failed (%s)\n", err.c_str());
+  if (!read_ok) GError("Error: reading the input failed\n");
+  if (rc_d != 0 && rc_d != TBK_ENOMEM && rc_d != TBK_E2BIG) GError("Error: decoding the input on the GPU failed: %s (%s)\n", dev.api.strerror_(rc_d), dev.api.last_error(dev.ctx));
+  int rc = 0;
+  tbk_soa_in in;
+  std::vector<uint32_t> fo(k + 1, 0);
+  std::vector<uint8_t> tbm(k, 0);
+  tbk_groups_out res;
+  memset(&res, 0, sizeof(res));
+  const uint32_t n_d = in_d.n_records;
+  auto t_join = t1, t_col = t1, t_rec = t1;
+  bool wrote = false, via_host = false, released = false;
+  auto release = [&]() {
+    auto r0 = tnow();
+    dev.api.bam_release(dev.ctx);
+    released = true;
+    if (env.timing) fprintf(stderr, "bam_release %.1f ms\n", tms(r0, tnow()));
+  };
+  if (fits && rc_d == 0) {
+    tbk_soa_in in_h = ft.view();
+    rc = dev.api.tile_join(dev.ctx, &in_d, &in_h, &in, fo.data(), tbm.data());
+    t_join = tnow();
+    const bool keep = out.keep_results();
+    if (rc == 0) rc = collapse_whole(dev, out, env, opt, keep, &in, &res, ft.tid, ft.n);  // (the host part's SoA went to the device with tbk_tile_join)
+    t_rec = t_col = tnow();  // (t_rec: the end of the fetch below, when there is one)
+    // a representative the device decoded: its raw record comes back from there (dev_slot: its place among those fetched)
+    std::vector<uint32_t> dev_slot;
+    RawBuf<uint64_t> roff;
+    RawBuf<uint8_t> blob;
+    auto rec = [&](uint32_t g) {
+      tbh::RecView v;
+      if (out.rep[g] < n_d) {
+        const uint32_t s = dev_slot[g];
+        v.p = blob.data() + roff[s] + 4;
+        v.len = (uint32_t)(roff[s + 1] - roff[s] - 4);
+      } else {
+        v.p = ft.record(out.rep[g] - n_d, &v.len);
+      }
+      return v;
+    };
+    auto fetch = [&]() {
+      via_host = true;
+      std::vector<uint32_t> dev_rep;
+      dev_slot.assign(res.n_groups, 0);
+      for (uint32_t g = 0; g < res.n_groups; ++g)
+        if (out.rep[g] < n_d) {
+          dev_slot[g] = (uint32_t)dev_rep.size();
+          dev_rep.push_back(out.rep[g]);
+        }
+      rc = fetch_device_records(dev, env, dev_rep.data(), (uint32_t)dev_rep.size(), 260, blob, roff);
+      t_rec = tnow();
+      if (rc == 0) release();
+      return rc == 0;
+    };
+    if (rc == 0)
+      wrote = out.write(dev.ctx, res.n_groups, out.rep.data(), keep ? nullptr : out.yc.data(), out.yx.data(), out.yd.data(), n_d, rec,
+                        [&](uint32_t g, int stage) { stage == 0 ? ft.prefetch_index(out.rep[g] - n_d) : ft.prefetch_record(out.rep[g] - n_d); }, fetch);
+  }
+  if (!wrote) {
+    if (rc != 0 && rc != TBK_ENOMEM && rc != TBK_E2BIG && rc != TBK_EUNSUPPORTED) GError("Error: GPU collapse failed: %s (%s)\n", dev.api.strerror_(rc), dev.api.last_error(dev.ctx));
+    if (!released) release();
+    out.fall_through("hybrid decode given up", rc_d != 0 ? dev.api.strerror_(rc_d) : (fits ? dev.api.strerror_(rc) : "the host's share does not fit"));
+    tbh::big_release_all(env.threads);
+    return Route::fall_through;
+  }
+  auto t3 = tnow();
+  if (env.timing && !via_host)  // (the device writer took every group)
+    fprintf(stderr,
+            "hybrid path ms: device %zu of %zu files (context ready at %.1f | map %.1f | decode incl. context %.1f, the call %.1f) beside host (read %.1f | inflate %.1f | index %.1f | SoA %.1f) = %.1f | "
+            "join %.1f | collapse %.1f | gather + tag + deflate (GPU) + write %.1f (%.1f MB of records -> %.1f MB)\n",
+            kd, k, dev.ms_ready, ms_dread, ms_ddec, ms_dcall, ft.ms_read, ft.ms_inflate, ft.ms_index, ft.ms_soa, tms(t0, t1), tms(t1, t_join), tms(t_join, t_col), tms(t_col, t3),
+            out.dev_payload / 1e6, out.dev_z / 1e6);
+  else if (env.timing)
+    fprintf(stderr,
+            "hybrid path ms: device %zu of %zu files (read %.1f | decode incl. context %.1f) beside host (read %.1f | inflate %.1f | index %.1f | SoA %.1f) = %.1f | "
+            "join %.1f | collapse %.1f | fetch representatives %.1f | tag+deflate+write %.1f\n",
+            kd, k, ms_dread, ms_ddec, ft.ms_read, ft.ms_inflate, ft.ms_index, ft.ms_soa, tms(t0, t1), tms(t1, t_join), tms(t_join, t_col), tms(t_col, t_rec), tms(t_rec, t3));
+  account_whole(tot, res, tms(t0, t1), tms(t1, t_rec), tms(t_rec, t3));
+  if (!released) release();
+  return Route::done;
+}
+
+// ---- whole-input host route: inputs that fit in memory are read, inflated and decoded into the tile in two parallel passes
+// (fastload.cpp) while the helper thread brings the device up; one collapse, one tagged output pass
+static Route run_whole_host(Device& dev, Output& out, const tbk_collapse_opts& opt, const Env& env, const Inputs& inp, Totals& tot) {
+  tbh::FastTile& ft = *new tbh::FastTile();  // (gigabytes, needed until the last record is written: left to the process exit)
+  bool fits = false;
+  std::string err;
+  auto t0 = tnow();
+  if (!tbh::fast_load(inp.paths, inp.merged, env.threads, host_budget(), ft, &fits, err)) GError("Error: reading the input failed (%s)\n", err.c_str());
+  if (!fits) return Route::fall_through;
+  auto t1 = tnow();
+  tbk_soa_in in = ft.view();
+  dev.wait();
+  auto t_ctxw = tnow();
+  tbk_groups_out res;
+  const bool keep = out.keep_results();
+  const int rc = collapse_whole(dev, out, env, opt, keep, &in, &res, ft.tid, ft.n);  // (the SoA went to the device with the call)
+  auto t2 = tnow();
+  if (rc == TBK_ENOMEM || rc == TBK_E2BIG) {  // one tile of everything is more than the GPU takes: the streaming route bounds it
+    out.fall_through("whole-input tile not used", why_rc(dev, rc));
+    tbh::big_release_all(env.threads);
+    return Route::fall_through;
+  }
+  if (rc != 0) GError("Error: GPU collapse failed: %s (%s)\n", dev.api.strerror_(rc), dev.api.last_error(dev.ctx));
+  out.write(
+      dev.ctx, res.n_groups, out.rep.data(), keep ? nullptr : out.yc.data(), out.yx.data(), out.yd.data(), 0,
+      [&](uint32_t g) {
+        tbh::RecView v;
+        v.p = ft.record(out.rep[g], &v.len);
+        return v;
+      },
+      [&](uint32_t g, int stage) { stage == 0 ? ft.prefetch_index(out.rep[g]) : ft.prefetch_record(out.rep[g]); });
+  auto t3 = tnow();
+  if (env.timing)
+    fprintf(stderr, "host path ms: read %.1f | inflate %.1f | index %.1f | SoA %.1f | wait for the device %.1f | collapse (PCIe incl.) %.1f | tag+deflate+write %.1f\n",
+            ft.ms_read, ft.ms_inflate, ft.ms_index, ft.ms_soa, tms(t1, t_ctxw), tms(t_ctxw, t2), tms(t2, t3));
+  return account_whole(tot, res, tms(t0, t1), tms(t1, t2), tms(t2, t3));
+}
+
+// ---- device decode: when the inputs fit, their BGZF members go to the GPU as they are — inflate, record index, aux
+// scan and SoA happen there (tbk_bam_decode), the collapse reads the tile where it lies, and only the representatives' raw records come
+// back (tbk_bam_records) to be tagged.  Anything it cannot take falls through to the streaming route.
+static Route run_device_decode(Device& dev, Output& out, const tbk_collapse_opts& opt, const Env& env, const Inputs& inp, Totals& tot) {
+  const size_t k = inp.paths.size();
+  auto t0 = tnow();
+  std::vector<FileMap> comp(k);
+  std::vector<const uint8_t*> ptr(k);
+  for (size_t f = 0; f < k; ++f) {
+    if (!comp[f].map(inp.paths[f]) || comp[f].n != inp.size[f]) GError("Error: reading the input failed\n");
+    ptr[f] = comp[f].p;
+  }
+  std::vector<uint32_t> fo(k + 1, 0);
+  auto t_read = tnow();
+  dev.wait();
+  auto t_ctxw = tnow();
+  tbk_soa_in in;
+  int rc = dev.api.bam_decode(dev.ctx, (uint32_t)k, ptr.data(), inp.size.data(), inp.merged.data(), opt.strategy == TBK_STRAT_FULL, opt.collapse_same != 0, &in,
+                              fo.data());
+  auto t1 = tnow();
+  for (auto& c : comp) c.unmap();
+  if (rc != 0) {
+    out.fall_through("device decode not used", why_rc(dev, rc));
+    dev.api.bam_release(dev.ctx);  // (whatever the failed decode left on the device goes back before the streaming route sizes its tiles)
+    return Route::fall_through;
+  }
+  tbk_groups_out res;
+  rc = collapse_whole(dev, out, env, opt, false, &in, &res);
+  auto t_col = tnow(), t_rec = t_col, t2 = t_col;
+  RawBuf<uint64_t> roff;
+  RawBuf<uint8_t> blob;
+  bool released = false;
+  auto release = [&]() {
+    t_rec = tnow();
+    dev.api.bam_release(dev.ctx);
+    released = true;
+    t2 = tnow();
+    if (env.timing)
+      fprintf(stderr, "device path ms: read files %.1f | wait for the HIP context %.1f | decode %.1f | collapse %.1f | fetch representatives %.1f | release %.1f\n",
+              tms(t0, t_read), tms(t_read, t_ctxw), tms(t_ctxw, t1), tms(t1, t_col), tms(t_col, t_rec), tms(t_rec, t2));
+  };
+  auto fetch = [&]() {
+    rc = fetch_device_records(dev, env, out.rep.data(), res.n_groups, 96, blob, roff);
+    if (rc == 0) release();
+    return rc == 0;
+  };
+  auto rec = [&](uint32_t g) {  // (the device writer asks for none: every record is on the device)
+    tbh::RecView v;
+    v.p = blob.data() + roff[g] + 4;
+    v.len = (uint32_t)(roff[g + 1] - roff[g] - 4);
+    return v;
+  };
+  if (rc == 0)  // (false only when the fetch fails: rc says why)
+    (void)out.write(dev.ctx, res.n_groups, out.rep.data(), out.yc.data(), out.yx.data(), out.yd.data(), (uint32_t)in.n_records, rec, nullptr, fetch);
+  if (rc == TBK_ENOMEM || rc == TBK_E2BIG) {  // decoded, but the whole input as one tile is more than the GPU takes:
+    out.fall_through("device decode given up", why_rc(dev, rc));  // give the device copies back and let the streaming route bound the tile
+    dev.api.bam_release(dev.ctx);
+    return Route::fall_through;
+  }
+  if (rc != 0) GError("Error: GPU collapse / fetching the representative records failed: %s (%s)\n", dev.api.strerror_(rc), dev.api.last_error(dev.ctx));
+  if (!released) release();
+  auto t3 = tnow();
+  account_whole(tot, res, tms(t0, t1), tms(t1, t2), tms(t2, t3));
+  if (env.timing) fprintf(stderr, "device decode: %zu records from %llu compressed bytes\n", (size_t)in.n_records, (unsigned long long)inp.total);
+  return Route::done;
+}
+
+// ---- streaming route: the inputs go through in tiles (TInputFiles::next_tile), and the OUTPUT side of tile i runs beside the input
+// side of tile i + 1.  The inputs stream through in tiles of about TBK_TILE_RECORDS records, cut where no read of any input reaches
+// across: exact — nothing the collapse computes crosses such a point — and host memory holds one tile's window of every input instead of
+// the inflated files (the reference holds one record per input, tmerge.cpp:331-344).  A tile's representatives are copied out of the
+// input windows right behind its collapse (the windows move on with the next tile); tags, deflate and the write of the tile then belong
+// to a writer thread with a context of its own (the device writer, or every core under --writer host), while this thread inflates,
+// decodes and collapses the next tile.  Two slots: a tile's arrays are free again once its members are in the file.
+static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt, const Env& env, TInputFiles& inRecords, Totals& tot) {
+  struct StreamSlot {
+    RawBuf<uint32_t> rep;
+    RawBuf<double> yc;
+    RawBuf<int64_t> yx;
+    RawBuf<int32_t> yd;
+    RawBuf<uint8_t> blob;   // the representatives' raw records, group after group (no block_size)
+    RawBuf<uint64_t> boff;  // [ng + 1]
+    uint32_t ng = 0;
+    bool busy = false;
+  };
+  StreamSlot slots[2];
+  std::mutex sm;
+  std::condition_variable scv;
+  std::vector<int> queue_;   // slots handed to the writer, in tile order
+  bool producer_done = false;
+  double ms_writer_busy = 0, ms_wait_slot = 0, ms_gather = 0;
+  tbk_ctx* wctx = nullptr;   // the writer's context (the collapse of the next tile keeps `ctx` busy)
+  std::thread writer_thread;
+  auto writer_main = [&]() {
+    for (;;) {
+      int si = -1;
+      {
+        std::unique_lock<std::mutex> lk(sm);
+        scv.wait(lk, [&] { return !queue_.empty() || producer_done; });
+        if (queue_.empty()) return;
+        si = queue_.front();
+        queue_.erase(queue_.begin());
+      }
+      StreamSlot& S = slots[si];
+      auto a = tnow();
+      const RecFn from_blob = [&S](uint32_t g) {
+        tbh::RecView v;
+        v.p = S.blob.data() + S.boff[g];
+        v.len = (uint32_t)(S.boff[g + 1] - S.boff[g]);
+        return v;
+      };
+      out.write(wctx, S.ng, S.rep.data(), S.yc.data(), S.yx.data(), S.yd.data(), 0, from_blob);
+      ms_writer_busy += tms(a, tnow());
+      {
+        std::lock_guard<std::mutex> lk(sm);
+        S.busy = false;
+      }
+      scv.notify_all();
+    }
+  };
+  TbkTile tile;
+  TInputFiles::TilePlan plan;
+  const int nthreads = env.threads;
+  int next_slot = 0;
+  for (;;) {
+    auto ti = tnow();
+    const bool more = inRecords.next_tile(plan, env.tile_records, nthreads);
+    tot.ms_inflate += tms(ti, tnow());
+    if (!more) break;
+    ++tot.n_tiles;
+    auto t0 = tnow();
+    inRecords.load_tile(tile, opt.strategy == TBK_STRAT_FULL, opt.collapse_same != 0, nthreads, &plan);
+    auto t1 = tnow();
+    tbk_soa_in in = tile.view();
+    size_t n = tile.n();
+    StreamSlot& S = slots[next_slot];
+    {
+      auto w0 = tnow();
+      std::unique_lock<std::mutex> lk(sm);
+      scv.wait(lk, [&] { return !S.busy; });
+      ms_wait_slot += tms(w0, tnow());
+    }
+    tbk_groups_out res;
+    size_results(&res, n, S.rep, S.yc, S.yx, S.yd);
+    dev.wait();
+    if (!writer_thread.joinable()) {
+      if (dev.dw && dev.api.create(env.device, &wctx) != 0) wctx = nullptr;  // (no second context: the host writer takes the output)
+      writer_thread = std::thread(writer_main);
+    }
+    tbk_collapse_opts copt = opt;
+    const int rc = dev.api.collapse_tile(dev.ctx, &copt, &in, &res);
+    auto t2 = tnow();
+    if (rc == TBK_EUNSORTED) GError("Error: an input file is not coordinate-sorted!\n");
+    if (rc != 0) GError("Error: GPU collapse failed: %s (%s)\n", dev.api.strerror_(rc), dev.api.last_error(dev.ctx));
+    // the representatives leave the windows: sizes per slice of groups, a prefix, the copies — every core
+    {
+      const uint32_t ng = res.n_groups;
+      S.ng = ng;
+      S.boff.resize((size_t)ng + 1);
+      const int T = ng < 8192 ? 1 : nthreads;
+      std::vector<uint64_t> part((size_t)T + 1, 0);
+      auto slice = [&](int t, uint32_t* a, uint32_t* b) {
+        *a = (uint32_t)((uint64_t)ng * (uint32_t)t / (uint32_t)T);
+        *b = (uint32_t)((uint64_t)ng * ((uint32_t)t + 1) / (uint32_t)T);
+      };
+      auto par = [&](const std::function<void(int)>& f) {
+        std::vector<std::thread> th;
+        for (int t = 1; t < T; ++t) th.emplace_back(f, t);
+        f(0);
+        for (auto& x : th) x.join();
+      };
+      par([&](int t) {
+        uint32_t a, b;
+        slice(t, &a, &b);
+        uint64_t by = 0;
+        for (uint32_t g = a; g < b; ++g) by += inRecords.record(S.rep[g]).len;
+        part[(size_t)t + 1] = by;
+      });
+      for (int t = 0; t < T; ++t) part[(size_t)t + 1] += part[(size_t)t];
+      S.blob.resize((size_t)part[(size_t)T] + 16);
+      par([&](int t) {
+        uint32_t a, b;
+        slice(t, &a, &b);
+        uint64_t o = part[(size_t)t];
+        for (uint32_t g = a; g < b; ++g) {
+          const tbh::RecView v = inRecords.record(S.rep[g]);
+          S.boff[g] = o;
+          memcpy(S.blob.data() + o, v.p, v.len);
+          o += v.len;
+        }
+      });
+      S.boff[ng] = part[(size_t)T];
+    }
+    auto t3 = tnow();
+    ms_gather += tms(t2, t3);
+    tot.in += res.n_passed;
+    tot.out += res.n_groups;
+    inRecords.release_tile(plan);
+    {
+      std::lock_guard<std::mutex> lk(sm);
+      S.busy = true;
+      queue_.push_back(next_slot);
+    }
+    scv.notify_all();
+    next_slot ^= 1;
+    tot.ms_load += tms(t0, t1);
+    tot.ms_gpu += tms(t1, t2);
+  }
+  if (writer_thread.joinable()) {
+    {
+      std::lock_guard<std::mutex> lk(sm);
+      producer_done = true;
+    }
+    scv.notify_all();
+    auto w0 = tnow();
+    writer_thread.join();
+    tot.ms_tag += tms(w0, tnow());
+    if (wctx) dev.api.destroy(wctx);
+    if (env.timing)
+      fprintf(stderr, "streamed: %zu tiles; this thread inflate+index %.1f | SoA %.1f | collapse %.1f | gather representatives %.1f | waited for a free slot %.1f | "
+                      "waited for the writer at the end %.1f; writer thread busy %.1f\n",
+              tot.n_tiles, tot.ms_inflate, tot.ms_load, tot.ms_gpu, ms_gather, ms_wait_slot, tms(w0, tnow()), ms_writer_busy);
+  }
+}
+
 int main(int argc, char* argv[]) {
-  maybe_exec_ranks(argc, argv);
+  const Env env;
+  spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
   Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;SMLPEDVho:N:Q:F:A");
@@ -244,889 +1044,47 @@ int main(int argc, char* argv[]) {
   if (opt.keep_unmapped) GError("Error: -M/--keep-unmap is not supported by the GPU build\n");
   while (const char* ifn = args.nextNonOpt()) inRecords.addFile(tbh_realpath(ifn).c_str());
 
-  const bool timing = getenv("TBK_TIMING") != nullptr;
-  // (TBK_TIMING=2: the calls' kernels too, through the library's HIP events — two events per launch are themselves milliseconds of a
-  // run this short, so the phase lines of TBK_TIMING=1, which the bench's end-to-end legs run under, come without them)
-  const bool ktiming = timing && atoi(getenv("TBK_TIMING")) > 1;
-  auto tnow = [] { return std::chrono::steady_clock::now(); };
-  auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) {
-    return std::chrono::duration<double, std::milli>(b - a).count();
-  };
-  auto t_start = tnow();
-  // binding libtbk.so (the HIP runtime comes with it) and bringing the device up take ~0.3 s: both happen on a helper thread
-  // while the inputs are opened, inflated and parsed
-  TbkApi api;
-  tbk_ctx* ctx = nullptr;
-  int dev = getenv("TBK_DEVICE") ? atoi(getenv("TBK_DEVICE")) : 0;
-  int rc = 0;
-  bool api_ok = false;
-  DeviceWriter* dw = nullptr;  // (pinned staging: lives until the process ends)
-  double ms_ctx_ready = 0;
-  // The thread brings the device up and then warms the context (below).  A caller that can use the context the moment it exists — the
-  // hybrid path's device decode — says so (ctx_urgent) and gets it unwarmed: it runs the warm-up itself when its decode is done and
-  // the cores are still busy with their share.
-  std::mutex ctx_m;
-  std::condition_variable ctx_cv;
-  bool ctx_created = false, ctx_warming = false;  // (under ctx_m)
-  std::atomic<bool> ctx_urgent{false};
-  bool ctx_warm = false;
-  // What a first call pays beyond its kernels, paid ahead: (a) for the PROCESS — the library's code objects mapped onto the device by a
-  // first launch, the copy engines' first use — with one tiny collapse and tbk_warmup on whatever context `c` is; (b) for the context
-  // that will run the real call — its second queue, its list machines' first dispatch, its staging buffer: tbk_warmup(ctx).
-  auto warm_process = [&](tbk_ctx* c) {
-    // (65 inputs of one record each: more than 64 inputs take the window path, whose kernels — the larger part of the library's
-    // device code — would otherwise be mapped by the first real collapse)
-    constexpr uint32_t WK = 65;
-    uint32_t fo[WK + 1], co[WK + 1], cg[WK];
-    uint8_t tb0[WK], mq[WK], st[WK];
-    int32_t ti[WK], po[WK], nh[WK];
-    uint16_t fl[WK];
-    for (uint32_t i = 0; i < WK; ++i) fo[i] = co[i] = i, cg[i] = 50u << 4, tb0[i] = 0, mq[i] = 60, st[i] = '.', ti[i] = 0, po[i] = 10, nh[i] = 1, fl[i] = 0;
-    fo[WK] = co[WK] = WK;
-    tbk_soa_in w;
-    memset(&w, 0, sizeof(w));
-    w.mem = TBK_MEM_HOST;
-    w.n_files = WK, w.n_records = WK, w.n_cigar_ops = WK;
-    w.file_off = fo, w.tbmerged = tb0, w.tid = ti, w.pos = po, w.flag = fl, w.mapq = mq, w.strand = st, w.nh = nh, w.cig_off = co, w.cig = cg;
-    uint32_t wrep[WK];
-    double wyc[WK];
-    int64_t wyx[WK];
-    int32_t wyd[WK];
-    tbk_groups_out wo;
-    memset(&wo, 0, sizeof(wo));
-    wo.mem = TBK_MEM_HOST;
-    wo.cap_groups = WK;
-    wo.rep = wrep, wo.yc = wyc, wo.yx = wyx, wo.yd = wyd;
-    tbk_collapse_opts wopt = opt;
-    (void)api.collapse_tile(c, &wopt, &w, &wo);
-    if (c != ctx && !getenv("TBK_NO_WARMUP2")) (void)api.warmup(c);  // (the engines; ctx gets its own call below)
-  };
-  auto warm_own = [&]() {
-    if (ctx_warm || !api_ok || rc != 0 || getenv("TBK_NO_WARMUP") || getenv("TBK_NO_WARMUP2")) return;
-    ctx_warm = true;
-    (void)api.warmup(ctx);
-  };
-  std::thread ctx_thread([&]() {
-    api_ok = api.load();
-    if (api_ok) rc = api.create(dev, &ctx);
-    if (api_ok && rc == 0 && dev_writer) dw = new DeviceWriter(api, tbh::cpu_budget());
-    ms_ctx_ready = tms(t_start, tnow());
-    bool warm_here;
-    {
-      std::lock_guard<std::mutex> lk(ctx_m);
-      ctx_created = true;
-      warm_here = !ctx_urgent.load();
-      ctx_warming = warm_here;
-    }
-    ctx_cv.notify_all();
-    // (page-locking the writer's staging buffers: ~ 12 ms, beside the decode — and behind the hand-over: a decode that waits for the
-    // context does not wait for this)
-    if (dw) (void)dw->reserve();
-    // ... and a second context for the writer's second encode thread (its queue: ~ 10 ms to create)
-    if (dw && !getenv("TBK_DW_ONE_ENCODER")) {
-      tbk_ctx* c2 = nullptr;
-      if (api.create(dev, &c2) == 0) dw->set_second(c2);
-    }
-    const bool can_warm = api_ok && rc == 0 && !getenv("TBK_NO_WARMUP");
-    if (warm_here) {
-      if (can_warm) warm_process(ctx), warm_own();
-      {
-        std::lock_guard<std::mutex> lk(ctx_m);
-        ctx_warming = false;
-      }
-      ctx_cv.notify_all();
-    } else if (can_warm) {
-      // the context is in use already (the hybrid path's device decode): the process-wide part on a context of this thread's own,
-      // beside that decode; the decode thread does the context's part when its call has returned
-      tbk_ctx* wc = nullptr;
-      if (api.create(dev, &wc) == 0) {
-        warm_process(wc);
-        api.destroy(wc);
-      }
-    }
-  });
-  bool ctx_ready = false;
-  auto check_ctx = [&]() {
-    if (!api_ok) GError("Error: cannot load libtbk.so (%s); this build has no CPU collapse path\n", api.error.c_str());
-    if (rc != 0) GError("Error: cannot use GPU %d (%s); this build has no CPU collapse path\n", dev, api.strerror_(rc));
-  };
-  auto need_ctx = [&]() {
-    if (ctx_ready) return;
-    ctx_thread.join();
-    ctx_ready = true;
-    check_ctx();
-  };
-  // (the hybrid path's decode thread: the context as soon as it exists; the thread above is NOT joined here)
-  auto need_ctx_now = [&]() {
-    ctx_urgent.store(true);
-    std::unique_lock<std::mutex> lk(ctx_m);
-    ctx_cv.wait(lk, [&] { return ctx_created && !ctx_warming; });
-    lk.unlock();
-    check_ctx();
-  };
+  Device dev(env, opt, dev_writer, tnow());
   inRecords.start();
   auto t_ctx = tnow();
-  double ms_load = 0, ms_gpu = 0, ms_tag = 0, ms_inflate = 0, ms_dev_write = 0;
-  uint64_t dev_payload = 0, dev_z = 0;
-
-  int nthreads = tbh::cpu_budget();
-  if (nthreads < 1) nthreads = 1;
-  if (nthreads > 128) nthreads = 128;
-  if (const char* e = getenv("TBK_THREADS")) nthreads = std::max(1, atoi(e));
-  // The inputs stream through in tiles of about TBK_TILE_RECORDS records, cut where no read of any input reaches across
-  // (TInputFiles::next_tile): exact — nothing the collapse computes crosses such a point — and host memory holds one tile's
-  // window of every input instead of the inflated files (the reference holds one record per input, tmerge.cpp:331-344).
-  size_t tile_records = getenv("TBK_TILE_RECORDS") ? (size_t)atoll(getenv("TBK_TILE_RECORDS")) : ((size_t)64 << 20);
-  uint64_t inCounter = 0, outCounter = 0;
-  {
-    GSamWriter outfile(outfname, inRecords.header(), GSamFile_BAM);
-    TbkTile tile;
-    // output arrays sized by the upper bound (one group per record) but never initialised: the pages a call does not write
-    // are never touched (a value-initialising resize of 32 M entries x 24 B costs more than the collapse itself)
-    RawBuf<uint32_t> rep;
-    RawBuf<double> yc;
-    RawBuf<int64_t> yx;
-    RawBuf<int32_t> yd;
-    TInputFiles::TilePlan plan;
-    size_t n_tiles = 0;
-    std::function<tbh::RecView(uint32_t)> get_record = [&](uint32_t g) { return inRecords.record(rep[g]); };
-    // flushPData tagging (tiebrush.cpp:506-525): the groups are independent, so slices of them are tagged, framed and
-    // deflated by worker threads into per-slice runs of BGZF members, which then go to the writer in order
-    // (gfirst: the groups before it are in the file already — the device writer's chunks before the one it refused, devwriter.h)
-    auto write_groups_arr = [&](uint32_t ng_all, const std::function<tbh::RecView(uint32_t)>& rec_of, const double* ycp, const int64_t* yxp, const int32_t* ydp,
-                                uint32_t gfirst) {
-      const uint32_t ng = ng_all > gfirst ? ng_all - gfirst : 0;  // groups to write
-      const int nt = ng < 4096 ? 1 : nthreads;
-      // slices of ~16 K groups, taken by the workers as they come free (a static split leaves the cores that drew sparse
-      // regions idle); the calling thread appends every slice's members to the file as soon as all earlier ones are out
-      const uint32_t per = nt == 1 ? (ng ? ng : 1) : (uint32_t)16384;
-      const uint32_t nsl = ng ? (ng + per - 1) / per : 0;
-      std::vector<std::vector<uint8_t>> runs((size_t)nsl);
-      std::unique_ptr<std::atomic<int>[]> ready(new std::atomic<int>[nsl ? nsl : 1]);
-      for (uint32_t i = 0; i < nsl; ++i) ready[i].store(0);
-      std::atomic<uint32_t> next_slice{0};
-      // the writer sleeps until the slice it needs is out (no spinning beside fully subscribed workers); a worker that fails
-      // says so here and the calling thread reports it once every worker has stopped
-      std::mutex ready_m;
-      std::condition_variable ready_cv;
-      std::atomic<bool> failed{false};
-      const int level = outfile.level();
-      auto tag_slice = [&](uint32_t sl, std::vector<uint8_t>& o, tbh::BamRec& rr) {
-        const uint32_t g0 = gfirst + sl * per, g1 = std::min(ng_all, g0 + per);
-        // flushPData's tags on every representative of the slice, then the slice deflates itself (tagwrite.h)
-        if (!tbh::tag_and_deflate(g0, g1, rec_of, ycp, yxp, ydp, level, o, rr, runs[(size_t)sl])) failed.store(true);
-        {
-          std::lock_guard<std::mutex> lk(ready_m);
-          ready[sl].store(1, std::memory_order_release);
-        }
-        ready_cv.notify_all();
-      };
-      auto worker = [&]() {
-        std::vector<uint8_t> o;
-        o.reserve((size_t)per * 96);
-        tbh::BamRec rr;
-        for (;;) {
-          const uint32_t sl = next_slice.fetch_add(1);
-          if (sl >= nsl) break;
-          if (failed.load()) {  // (stop working, but let the writer's wait for this slice end)
-            std::lock_guard<std::mutex> lk(ready_m);
-            ready[sl].store(1, std::memory_order_release);
-            ready_cv.notify_all();
-            continue;
-          }
-          tag_slice(sl, o, rr);
-        }
-      };
-      std::vector<std::thread> th;
-      if (nt > 1)
-        for (int t = 0; t < nt; ++t) th.emplace_back(worker);
-      else
-        worker();
-      for (uint32_t sl = 0; sl < nsl; ++sl) {
-        if (!ready[sl].load(std::memory_order_acquire)) {
-          std::unique_lock<std::mutex> lk(ready_m);
-          ready_cv.wait(lk, [&] { return ready[sl].load(std::memory_order_acquire) != 0; });
-        }
-        if (failed.load()) break;
-        outfile.write_members(runs[(size_t)sl].data(), runs[(size_t)sl].size());
-        std::vector<uint8_t>().swap(runs[(size_t)sl]);
-      }
-      for (auto& x : th) x.join();
-      if (failed.load()) GError("Error: deflate failed\n");
-    };
-    uint32_t dev_groups_done = 0;  // groups the device writer wrote before it refused a chunk: the host writer goes on from there
-    // the whole-input paths leave the tags' values on the device for the device writer (tbk_collapse_opts.keep_results): only `rep`
-    // comes back with the call.  When the host writer has to write after all, it fetches the values of the groups it writes.
-    bool results_kept = false;
-    auto write_groups = [&](uint32_t ng) {
-      const uint32_t gfirst = dev_groups_done;
-      dev_groups_done = 0;
-      if (results_kept && ng > gfirst) {
-        yc.resize(ng), yx.resize(ng), yd.resize(ng);
-        const int frc = api.kept_results(ctx, gfirst, ng - gfirst, nullptr, yc.data() + gfirst, yx.data() + gfirst, yd.data() + gfirst);
-        if (frc != 0) GError("Error: fetching the collapse's results failed: %s (%s)\n", api.strerror_(frc), api.last_error(ctx));
-      }
-      write_groups_arr(ng, get_record, yc.data(), yx.data(), yd.data(), gfirst);
-    };
-    const bool keep_for_writer = dev_writer && outfile.level() != 0 && !getenv("TBK_NO_KEEP_RESULTS");
-    // ... and `rep` comes back once the number of groups is known, into pages that are resident already when a dead array of the host's
-    // input tile is long enough (4 bytes per record: tid) — a fresh block of tens of megabytes is faulted in at 1-2 GB/s this late in the run
-    auto fetch_rep = [&](uint32_t ng, int32_t* dead, size_t dead_n) {
-      if (dead && ng <= dead_n) rep.borrow((uint32_t*)dead, dead_n);
-      else rep.resize(ng ? ng : 1);
-      auto f0 = tnow();
-      const int frc = api.kept_results(ctx, 0, ng, rep.data(), nullptr, nullptr, nullptr);
-      if (frc != 0) GError("Error: fetching the collapse's results failed: %s (%s)\n", api.strerror_(frc), api.last_error(ctx));
-      if (timing) fprintf(stderr, "representatives of %u groups fetched in %.1f ms (%s)\n", ng, tms(f0, tnow()), rep.borrowed ? "into the input tile's pages" : "into a new block");
-    };
-    // the same on the device (devwriter.h): tags, framing and BGZF deflate as kernels, the host only gathers the records it decoded
-    // itself and appends the finished members.  false: the host writer above takes the groups from dev_groups_done on.
-    auto write_groups_device = [&](uint32_t ng, uint32_t n_dev, const std::function<tbh::RecView(uint32_t)>& host_record,
-                                   const std::function<void(uint32_t, int)>& host_prefetch = nullptr) {
-      if (!dev_writer || outfile.level() == 0) return false;
-      need_ctx();
-      if (!dw) return false;
-      auto a = tnow();
-      uint64_t pb = 0, zb = 0;
-      std::string why;
-      uint32_t done = 0;
-      const bool ok = dw->write(ctx, outfile, ng, rep.data(), results_kept ? nullptr : yc.data(), yx.data(), yd.data(), n_dev, host_record, &pb, &zb, why, &done, host_prefetch);
-      if (!ok && timing) fprintf(stderr, "device writer stopped after %u of %u groups (%s): host writer\n", done, ng, why.c_str());
-      ms_dev_write += tms(a, tnow()), dev_payload += pb, dev_z += zb;
-      dev_groups_done = ok ? 0 : done;
-      return ok;
-    };
-    // half of what the host may still use (MemAvailable, the cgroup's limit): what the whole-input loaders may fill with inflated inputs
-    auto host_budget = []() {
-      size_t budget = (size_t)8 << 30;
-      if (FILE* mf = fopen("/proc/meminfo", "r")) {
-        char line[256];
-        while (fgets(line, sizeof(line), mf))
-          if (strncmp(line, "MemAvailable:", 13) == 0) budget = (size_t)atoll(line + 13) * 1024 / 2;
-        fclose(mf);
-      }
-      if (FILE* cf = fopen("/sys/fs/cgroup/memory.max", "r")) {
-        char q[64];
-        if (fscanf(cf, "%63s", q) == 1 && strcmp(q, "max") != 0) budget = std::min<size_t>(budget, (size_t)atoll(q) / 2);
-        fclose(cf);
-      }
-      return budget;
-    };
-    bool done_fast = false;
-    bool skip_fast = false;  // (the hybrid path below loaded a part of the inputs and gave up: the streaming path takes over)
-    tbh::FastTile& ft = *new tbh::FastTile();  // (gigabytes, needed until the last record is written: left to the process exit)
-    // ---- hybrid decode: records with SEQ / QUAL are ~ 240 inflated bytes each and the run is BGZF on the host's cores (SURVEY.md
-    // §8 f1).  The GPU inflates and decodes the first files of the list (tbk_bam_decode) WHILE the cores inflate and decode the rest
-    // (fastload.cpp); tbk_tile_join makes one device tile of the two, the collapse runs on it, and a representative's raw record
-    // comes from wherever its file was decoded.  TBK_HYBRID=0 / 1 switches it off / on (default: inputs of 768 MB and more),
-    // TBK_HYBRID_SHARE = the device's share of the compressed bytes in per cent (default 40).
-    {
-      const size_t k = inRecords.freaders.size();
-      const char* hy = getenv("TBK_HYBRID");
-      bool eligible = k >= 2 && !(getenv("TBK_HOST_FAST") && atoi(getenv("TBK_HOST_FAST")) == 0) && !getenv("TBK_DEVICE_DECODE") && !getenv("TBK_TILE_RECORDS") &&
-                      opt.strategy != TBK_STRAT_FULL && !opt.collapse_same && !(hy && atoi(hy) == 0);
-      std::vector<std::string> paths(k);
-      std::vector<uint64_t> fsz(k, 0);
-      uint64_t total = 0;
-      for (size_t f = 0; f < k && eligible; ++f) {
-        paths[f] = inRecords.freaders[f]->fname;
-        struct stat st;
-        if (inRecords.freaders[f]->tbMerged || !tbh::bgzf_probe(paths[f]) || stat(paths[f].c_str(), &st) != 0) eligible = false;
-        else fsz[f] = (uint64_t)st.st_size, total += fsz[f];
-      }
-      if (eligible && !(hy && atoi(hy) != 0) && total < ((uint64_t)768 << 20)) eligible = false;
-      if (eligible) {
-        // The device's share of the compressed bytes: both sides should end together.  The device starts late — the HIP runtime takes
-        // ~ 0.1 s to come up (t_ctx = 0.15: the helper thread's warm-up beside the decode and the context's own behind it cost the
-        // device's side another 0.05), the cores work alone meanwhile — and is then several times faster: with x of T bytes on the device,
-        // t_ctx + x / R_dev = (T - x) / R_host.  Rates measured on an MI355X box with a 16-core quota (round 5's end-to-end legs, tools/e2e_leg.py): the
-        // device side 4.7 GB/s of compressed BAM (upload, inflate, record index, SoA), a core 0.18 GB/s (inflate with the record index
-        // riding along, SoA).  1.8 GB of input: 54 % (17 of 32 files; measured round 6, five runs a share: 16 files 407 ms for the
-        // decode, 17 files 351-361, 18 files 374-382, 19 files 377-384); 7.1 GB: 63 %.  TBK_HYBRID_SHARE (per cent) overrides.
-        const int host_threads = getenv("TBK_THREADS") ? nthreads : std::max(2, nthreads - 3);
-        double share;
-        if (getenv("TBK_HYBRID_SHARE")) {
-          share = atof(getenv("TBK_HYBRID_SHARE")) / 100.0;
-        } else {
-          const double T = (double)total / 1e9, r_dev = 4.7, r_host = 0.18 * host_threads, t_ctx = 0.15;
-          const double x = (T / r_host - t_ctx) / (1.0 / r_dev + 1.0 / r_host);
-          share = std::min(0.9, std::max(0.2, x / T));
-        }
-        size_t kd = 0;
-        uint64_t acc = 0;
-        while (kd + 1 < k && (double)(acc + fsz[kd]) <= share * (double)total + (double)fsz[kd] / 2) acc += fsz[kd++];
-        if (kd == 0) kd = 1;
-        const size_t budget = host_budget();
-        auto t0 = tnow();
-        if (timing) fprintf(stderr, "hybrid decode starts at %.1f ms\n", tms(t_start, t0));
-        // the device's share, on a thread of its own: read the files, wait for the context, decode
-        tbk_soa_in in_d;
-        memset(&in_d, 0, sizeof(in_d));
-        std::vector<uint32_t> fo_d(kd + 1, 0);
-        std::vector<uint8_t> tb_d(kd, 0);
-        int rc_d = -1;
-        bool read_ok = true;
-        double ms_dread = 0, ms_ddec = 0, ms_dcall = 0;
-        std::thread dth([&]() {
-          auto d0 = tnow();
-          std::vector<FileMap> comp(kd);
-          for (size_t f = 0; f < kd; ++f)
-            if (!comp[f].map(paths[f]) || comp[f].n != fsz[f]) read_ok = false;
-          auto d1 = tnow();
-          ms_dread = tms(d0, d1);
-          if (!read_ok) return;
-          need_ctx_now();
-          auto d2 = tnow();
-          std::vector<const uint8_t*> ptr(kd);
-          for (size_t f = 0; f < kd; ++f) ptr[f] = comp[f].p;
-          if (ktiming) (void)api.set_profiling(ctx, 1);
-          rc_d = api.bam_decode(ctx, (uint32_t)kd, ptr.data(), fsz.data(), tb_d.data(), 0, 0, &in_d, fo_d.data());
-          ms_dcall = tms(d2, tnow());
-          if (ktiming) {  // the call's kernels (HIP events): what of its wall time the GPU was busy with
-            tbk_kernel_time kt[64];
-            const int nk = api.kernel_times(ctx, kt, 64);
-            std::string line = "device decode kernels ms:";
-            double sum = 0;
-            for (int i = 0; i < nk; ++i) {
-              char b[96];
-              snprintf(b, sizeof(b), " %s %.1f (%u)", kt[i].name, kt[i].ms, kt[i].launches);
-              line += b;
-              sum += kt[i].ms;
-            }
-            fprintf(stderr, "%s | sum %.1f of the call's %.1f\n", line.c_str(), sum, ms_dcall);
-            (void)api.set_profiling(ctx, 0);
-          }
-          for (auto& c : comp) c.unmap();
-          if (rc_d == 0 && acc > 0) {  // the arena for the joined tile, sized while the cores are still decoding their share
-            // (tbk_reserve_tile sizes for the window path AND a deferred YD stage that borrows its range of the arena: 165 bytes a record.
-            // This call defers nothing — 84 bytes a record and the CIGAR words —: six tenths of the tile's size asks for what it takes.
-            // An allocation of gigabytes is now and then 20-25 ms per GB of the driver's time)
-            const double up = (double)total / (double)acc * 1.05 * 0.6;
-            (void)api.reserve_tile(ctx, (uint64_t)((double)in_d.n_records * up), (uint64_t)((double)in_d.n_cigar_ops * up));
-          }
-          ms_ddec = tms(d1, tnow());
-          warm_own();  // (the helper thread left the context's own part to this one: need_ctx_now)
-        });
-        // the cores' share
-        std::vector<std::string> ph(paths.begin() + (long)kd, paths.end());
-        std::vector<uint8_t> tbh_(k - kd, 0);
-        bool fits = false;
-        std::string err;
-        // (the device's side needs cores too while it runs — the HIP start-up, then the threads that feed the upload ring —, and a
-        // container's CPU quota stalls EVERY thread of the process once the sum goes over it: the loader leaves them room)
-        const bool okh = tbh::fast_load(ph, tbh_, host_threads, budget, ft, &fits, err);
-        auto t_host = tnow();
-        dth.join();
-        auto t1 = tnow();
-        need_ctx();  // (the helper thread ended long ago; this only joins it)
-        if (!okh) GError("Error: reading the input failed (%s)\n", err.c_str());
-        if (!read_ok) GError("Error: reading the input failed\n");
-        if (rc_d != 0 && rc_d != TBK_ENOMEM && rc_d != TBK_E2BIG) GError("Error: decoding the input on the GPU failed: %s (%s)\n", api.strerror_(rc_d), api.last_error(ctx));
-        bool ok = fits && rc_d == 0;
-        tbk_soa_in in;
-        std::vector<uint32_t> fo(k + 1, 0);
-        std::vector<uint8_t> tbm(k, 0);
-        tbk_groups_out out;
-        memset(&out, 0, sizeof(out));
-        RawBuf<uint64_t> roff;
-        RawBuf<uint8_t> blob;
-        std::vector<uint32_t> dev_slot;
-        const uint32_t n_d = in_d.n_records;
-        auto t_join = t1, t_col = t1, t_rec = t1;
-        if (ok) {
-          tbk_soa_in in_h = ft.view();
-          rc = api.tile_join(ctx, &in_d, &in_h, &in, fo.data(), tbm.data());
-          t_join = tnow();
-          if (rc == 0) {
-            const size_t n = in.n_records;
-            out.mem = TBK_MEM_HOST;
-            out.cap_groups = (uint32_t)(n ? n : 1);
-            tbk_collapse_opts copt = opt;
-            copt.keep_results = keep_for_writer ? 1 : 0;
-            if (!keep_for_writer) {
-              rep.resize(n ? n : 1), yc.resize(n ? n : 1), yx.resize(n ? n : 1), yd.resize(n ? n : 1);
-              out.rep = rep.data(), out.yc = yc.data(), out.yx = yx.data(), out.yd = yd.data();
-            }
-            if (ktiming) (void)api.set_profiling(ctx, 1);
-            rc = api.collapse_tile(ctx, &copt, &in, &out);
-            if (rc == 0 && getenv("TBK_TEST_WHOLE_ENOMEM")) rc = TBK_ENOMEM;  // test hook: exercise the fall-back below
-            results_kept = rc == 0 && keep_for_writer;
-            if (results_kept) fetch_rep(out.n_groups, ft.tid, ft.n);  // (the host part's SoA went to the device with tbk_tile_join)
-            t_col = tnow();
-            if (ktiming) {
-              tbk_kernel_time kt[64];
-              const int nk = api.kernel_times(ctx, kt, 64);
-              double sum = 0;
-              for (int i = 0; i < nk; ++i) sum += kt[i].ms;
-              fprintf(stderr, "collapse call: %.1f ms, its kernels %.1f ms in %d kinds\n", tms(t_join, t_col), sum, nk);
-              (void)api.set_profiling(ctx, 0);
-            }
-            if (rc == TBK_EUNSORTED) GError("Error: an input file is not coordinate-sorted!\n");
-          }
-          bool wrote_dev = false;
-          if (rc == 0) {
-            wrote_dev = write_groups_device(
-                out.n_groups, n_d,
-                [&](uint32_t g) {
-                  tbh::RecView v;
-                  v.p = ft.record(rep[g] - n_d, &v.len);
-                  return v;
-                },
-                [&](uint32_t g, int stage) { stage == 0 ? ft.prefetch_index(rep[g] - n_d) : ft.prefetch_record(rep[g] - n_d); });
-            t_rec = tnow();
-          }
-          if (rc == 0 && !wrote_dev) {  // the representatives the device decoded: their raw records come back from there
-            std::vector<uint32_t> dev_rep;
-            dev_slot.assign(out.n_groups, 0);
-            for (uint32_t g = 0; g < out.n_groups; ++g)
-              if (rep[g] < n_d) {
-                dev_slot[g] = (uint32_t)dev_rep.size();
-                dev_rep.push_back(rep[g]);
-              }
-            roff.resize(dev_rep.size() + 1);
-            blob.resize(dev_rep.size() * 260 + 4096);
-            rc = api.bam_records(ctx, dev_rep.data(), (uint32_t)dev_rep.size(), TBK_MEM_HOST, blob.data(), blob.size(), roff.data());
-            if (rc == TBK_E2BIG) {
-              blob.resize(roff[dev_rep.size()]);
-              rc = api.bam_records(ctx, dev_rep.data(), (uint32_t)dev_rep.size(), TBK_MEM_HOST, blob.data(), blob.size(), roff.data());
-            }
-            t_rec = tnow();
-          }
-          ok = rc == 0;
-          if (!ok && rc != TBK_ENOMEM && rc != TBK_E2BIG && rc != TBK_EUNSUPPORTED)
-            GError("Error: GPU collapse failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-          if (ok && wrote_dev) {
-            auto t3 = tnow();
-            if (timing)
-              fprintf(stderr,
-                      "hybrid path ms: device %zu of %zu files (context ready at %.1f | map %.1f | decode incl. context %.1f, the call %.1f) beside host (read %.1f | inflate %.1f | index %.1f | SoA %.1f) = %.1f | "
-                      "join %.1f | collapse %.1f | gather + tag + deflate (GPU) + write %.1f (%.1f MB of records -> %.1f MB)\n",
-                      kd, k, ms_ctx_ready, ms_dread, ms_ddec, ms_dcall, ft.ms_read, ft.ms_inflate, ft.ms_index, ft.ms_soa, tms(t0, t1), tms(t1, t_join), tms(t_join, t_col), tms(t_col, t3),
-                      dev_payload / 1e6, dev_z / 1e6);
-            ms_inflate += tms(t0, t1);
-            ms_gpu += tms(t1, t_col);
-            ms_tag += tms(t_col, t3);
-            inCounter += out.n_passed;
-            outCounter += out.n_groups;
-            n_tiles = 1;
-            done_fast = true;
-          }
-        }
-        {
-          auto r0 = tnow();
-          if (ctx_ready) api.bam_release(ctx);
-          if (timing) fprintf(stderr, "bam_release %.1f ms\n", tms(r0, tnow()));
-        }
-        if (done_fast) {
-        } else if (!ok) {
-          if (timing) fprintf(stderr, "hybrid decode given up (%s): streaming host path\n", rc_d != 0 ? api.strerror_(rc_d) : (fits ? api.strerror_(rc) : "the host's share does not fit"));
-          tbh::big_release_all(nthreads);
-          skip_fast = true;
-        } else {
-          get_record = [&](uint32_t g) {
-            tbh::RecView v;
-            if (rep[g] < n_d) {
-              const uint32_t s = dev_slot[g];
-              v.p = blob.data() + roff[s] + 4;
-              v.len = (uint32_t)(roff[s + 1] - roff[s] - 4);
-            } else {
-              v.p = ft.record(rep[g] - n_d, &v.len);
-            }
-            return v;
-          };
-          write_groups(out.n_groups);
-          auto t3 = tnow();
-          if (timing)
-            fprintf(stderr,
-                    "hybrid path ms: device %zu of %zu files (read %.1f | decode incl. context %.1f) beside host (read %.1f | inflate %.1f | index %.1f | SoA %.1f) = %.1f | "
-                    "join %.1f | collapse %.1f | fetch representatives %.1f | tag+deflate+write %.1f\n",
-                    kd, k, ms_dread, ms_ddec, ft.ms_read, ft.ms_inflate, ft.ms_index, ft.ms_soa, tms(t0, t1), tms(t1, t_join), tms(t_join, t_col), tms(t_col, t_rec),
-                    tms(t_rec, t3));
-          (void)t_host;
-          ms_inflate += tms(t0, t1);
-          ms_gpu += tms(t1, t_rec);
-          ms_tag += tms(t_rec, t3);
-          inCounter += out.n_passed;
-          outCounter += out.n_groups;
-          n_tiles = 1;
-          done_fast = true;
-        }
-      }
-    }
-    // ---- whole-input host path: inputs that fit in memory are read, inflated and decoded into the tile in two parallel passes
-    // (fastload.cpp) while the helper thread brings the device up; one collapse, one tagged output pass ----
-    if (!done_fast && !skip_fast && !(getenv("TBK_HOST_FAST") && atoi(getenv("TBK_HOST_FAST")) == 0) &&
-        !(getenv("TBK_DEVICE_DECODE") && atoi(getenv("TBK_DEVICE_DECODE")) != 0) && !getenv("TBK_TILE_RECORDS") && opt.strategy != TBK_STRAT_FULL &&
-        !opt.collapse_same) {
-      const size_t k = inRecords.freaders.size();
-      bool all_bam = true;  // (SAM text inputs are converted by the streaming reader)
-      std::vector<std::string> paths(k);
-      std::vector<uint8_t> tb(k);
-      for (size_t f = 0; f < k; ++f) {
-        paths[f] = inRecords.freaders[f]->fname;
-        tb[f] = inRecords.freaders[f]->tbMerged ? 1 : 0;
-        all_bam = all_bam && tbh::bgzf_probe(paths[f]);
-      }
-      const size_t budget = host_budget();
-      bool fits = false;
-      std::string err;
-      if (all_bam && k > 0) {
-        auto t0 = tnow();
-        if (!tbh::fast_load(paths, tb, nthreads, budget, ft, &fits, err)) GError("Error: reading the input failed (%s)\n", err.c_str());
-        if (fits) {
-          auto t1 = tnow();
-          tbk_soa_in in = ft.view();
-          const size_t n = ft.n;
-          need_ctx();
-          auto t_ctxw = tnow();
-          tbk_groups_out out;
-          memset(&out, 0, sizeof(out));
-          out.mem = TBK_MEM_HOST;
-          out.cap_groups = (uint32_t)(n ? n : 1);
-          tbk_collapse_opts copt = opt;
-          copt.keep_results = keep_for_writer ? 1 : 0;
-          if (!keep_for_writer) {
-            rep.resize(n ? n : 1), yc.resize(n ? n : 1), yx.resize(n ? n : 1), yd.resize(n ? n : 1);
-            out.rep = rep.data(), out.yc = yc.data(), out.yx = yx.data(), out.yd = yd.data();
-          }
-          rc = api.collapse_tile(ctx, &copt, &in, &out);
-          if (rc == 0 && getenv("TBK_TEST_WHOLE_ENOMEM")) rc = TBK_ENOMEM;  // test hook: exercise the fall-back below
-          results_kept = rc == 0 && keep_for_writer;
-          if (results_kept) fetch_rep(out.n_groups, ft.tid, ft.n);  // (the SoA went to the device with the call)
-          auto t2 = tnow();
-          if (rc == TBK_EUNSORTED) GError("Error: an input file is not coordinate-sorted!\n");
-          if (rc == TBK_ENOMEM || rc == TBK_E2BIG) {  // one tile of everything is more than the GPU takes: the streaming path bounds it
-            if (timing) fprintf(stderr, "whole-input tile not used (%s: %s): streaming host path\n", api.strerror_(rc), api.last_error(ctx));
-            tbh::big_release_all(nthreads);
-          } else {
-            if (rc != 0) GError("Error: GPU collapse failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-            get_record = [&](uint32_t g) {
-              tbh::RecView v;
-              v.p = ft.record(rep[g], &v.len);
-              return v;
-            };
-            if (!write_groups_device(out.n_groups, 0, get_record, [&](uint32_t g, int stage) { stage == 0 ? ft.prefetch_index(rep[g]) : ft.prefetch_record(rep[g]); }))
-              write_groups(out.n_groups);
-            auto t3 = tnow();
-            if (timing)
-              fprintf(stderr, "host path ms: read %.1f | inflate %.1f | index %.1f | SoA %.1f | wait for the device %.1f | collapse (PCIe incl.) %.1f | tag+deflate+write %.1f\n",
-                      ft.ms_read, ft.ms_inflate, ft.ms_index, ft.ms_soa, tms(t1, t_ctxw), tms(t_ctxw, t2), tms(t2, t3));
-            ms_inflate += tms(t0, t1);
-            ms_gpu += tms(t1, t2);
-            ms_tag += tms(t2, t3);
-            inCounter += out.n_passed;
-            outCounter += out.n_groups;
-            n_tiles = 1;
-            done_fast = true;
-          }
-        }
-      }
-    }
-    // ---- device decode: when the inputs fit, their BGZF members go to the GPU as they are — inflate,
-    // record index, aux scan and SoA happen there (tbk_bam_decode), the collapse reads the tile where it lies, and only the
-    // representatives' raw records come back (tbk_bam_records) to be tagged.  Anything it cannot take falls through to the
-    // streaming host path below.
-    bool done_on_device = done_fast;
-    if (!done_fast) {
-      const char* e = getenv("TBK_DEVICE_DECODE");
-      const bool want = e ? atoi(e) != 0 : false;  // (opt in: with libdeflate on every core the host inflates faster than the device path end to end)
-      uint64_t total = 0;
-      const size_t k = inRecords.freaders.size();
-      std::vector<uint64_t> fsz(k, 0);
-      for (size_t f = 0; f < k; ++f) {
-        struct stat st;
-        if (stat(inRecords.freaders[f]->fname.c_str(), &st) == 0) fsz[f] = (uint64_t)st.st_size;
-        total += fsz[f];
-      }
-      const uint64_t lim = getenv("TBK_DEVICE_DECODE_MAX") ? (uint64_t)atoll(getenv("TBK_DEVICE_DECODE_MAX")) : ((uint64_t)6 << 30);
-      bool all_bam = true;  // (SAM text inputs are decoded by the host)
-      for (size_t f = 0; f < k; ++f) all_bam = all_bam && tbh::bgzf_probe(inRecords.freaders[f]->fname);
-      if (want && all_bam && total > 0 && total <= lim) {
-        auto t0 = tnow();
-        std::vector<FileMap> comp(k);
-        for (size_t f = 0; f < k; ++f)
-          if (!comp[f].map(inRecords.freaders[f]->fname) || comp[f].n != fsz[f]) GError("Error: reading the input failed\n");
-        std::vector<const uint8_t*> ptr(k);
-        std::vector<uint8_t> tb(k);
-        for (size_t f = 0; f < k; ++f) {
-          ptr[f] = comp[f].p;
-          tb[f] = inRecords.freaders[f]->tbMerged ? 1 : 0;
-        }
-        std::vector<uint32_t> fo(k + 1, 0);
-        auto t_read = tnow();
-        need_ctx();
-        auto t_ctxw = tnow();
-        tbk_soa_in in;
-        rc = api.bam_decode(ctx, (uint32_t)k, ptr.data(), fsz.data(), tb.data(), opt.strategy == TBK_STRAT_FULL, opt.collapse_same != 0, &in, fo.data());
-        auto t1 = tnow();
-        for (auto& c : comp) c.unmap();
-        if (rc == 0) {
-          const size_t n = in.n_records;
-          rep.resize(n ? n : 1);
-          yc.resize(n ? n : 1);
-          yx.resize(n ? n : 1);
-          yd.resize(n ? n : 1);
-          tbk_groups_out out;
-          memset(&out, 0, sizeof(out));
-          out.mem = TBK_MEM_HOST;
-          out.cap_groups = (uint32_t)(n ? n : 1);
-          out.rep = rep.data();
-          out.yc = yc.data();
-          out.yx = yx.data();
-          out.yd = yd.data();
-          auto t_pre = tnow();
-          rc = api.collapse_tile(ctx, &opt, &in, &out);
-          if (timing) fprintf(stderr, "device path: output arrays %.1f ms, collapse call %.1f ms\n", tms(t1, t_pre), tms(t_pre, tnow()));
-          if (rc == 0 && getenv("TBK_TEST_WHOLE_ENOMEM")) rc = TBK_ENOMEM;  // test hook: exercise the fall-back below
-          auto t_col = tnow();
-          if (rc == TBK_EUNSORTED) GError("Error: an input file is not coordinate-sorted!\n");
-          RawBuf<uint64_t> roff;
-          RawBuf<uint8_t> blob;
-          bool wrote_dev = false;
-          if (rc == 0) wrote_dev = write_groups_device(out.n_groups, (uint32_t)n, [](uint32_t) { return tbh::RecView(); });
-          if (rc == 0 && !wrote_dev) {
-            roff.resize((size_t)out.n_groups + 1);
-            blob.resize((size_t)out.n_groups * 96 + 4096);
-            rc = api.bam_records(ctx, rep.data(), out.n_groups, TBK_MEM_HOST, blob.data(), blob.size(), roff.data());
-            if (rc == TBK_E2BIG) {
-              blob.resize(roff[out.n_groups]);
-              rc = api.bam_records(ctx, rep.data(), out.n_groups, TBK_MEM_HOST, blob.data(), blob.size(), roff.data());
-            }
-          }
-          if (rc == TBK_ENOMEM || rc == TBK_E2BIG) {  // decoded, but the whole input as one tile is more than the GPU takes:
-            if (timing)                                // give the device copies back and let the streaming path bound the tile
-              fprintf(stderr, "device decode given up (%s: %s): streaming host path\n", api.strerror_(rc), api.last_error(ctx));
-            api.bam_release(ctx);
-          } else {
-            if (rc != 0) GError("Error: GPU collapse / fetching the representative records failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-            auto t_rec = tnow();
-            api.bam_release(ctx);
-            auto t2 = tnow();
-            if (timing)
-              fprintf(stderr, "device path ms: read files %.1f | wait for the HIP context %.1f | decode %.1f | collapse %.1f | fetch representatives %.1f | release %.1f\n",
-                      tms(t0, t_read), tms(t_read, t_ctxw), tms(t_ctxw, t1), tms(t1, t_col), tms(t_col, t_rec), tms(t_rec, t2));
-            get_record = [&](uint32_t g) {
-              tbh::RecView v;
-              v.p = blob.data() + roff[g] + 4;
-              v.len = (uint32_t)(roff[g + 1] - roff[g] - 4);
-              return v;
-            };
-            if (!wrote_dev) write_groups(out.n_groups);
-            auto t3 = tnow();
-            ms_inflate += tms(t0, t1);
-            ms_gpu += tms(t1, t2);
-            ms_tag += tms(t2, t3);
-            inCounter += out.n_passed;
-            outCounter += out.n_groups;
-            n_tiles = 1;
-            done_on_device = true;
-            if (timing) fprintf(stderr, "device decode: %zu records from %llu compressed bytes\n", n, (unsigned long long)total);
-          }
-        } else {
-          if (timing) fprintf(stderr, "device decode not used (%s: %s): streaming host path\n", api.strerror_(rc), api.last_error(ctx));
-          api.bam_release(ctx);  // (whatever the failed decode left on the device goes back before the streaming path sizes its tiles)
-        }
-      }
-    }
-    // ---- streaming path: the inputs go through in tiles (TInputFiles::next_tile), and the OUTPUT side of tile i runs beside the
-    // input side of tile i + 1.  A tile's representatives are copied out of the input windows right behind its collapse (the windows
-    // move on with the next tile); tags, deflate and the write of the tile then belong to a writer thread with a context of its own
-    // (the device writer, or every core under --writer host), while this thread inflates, decodes and collapses the next tile.
-    // Two slots: a tile's arrays are free again once its members are in the file.
-    struct StreamSlot {
-      RawBuf<uint32_t> rep;
-      RawBuf<double> yc;
-      RawBuf<int64_t> yx;
-      RawBuf<int32_t> yd;
-      RawBuf<uint8_t> blob;   // the representatives' raw records, group after group (no block_size)
-      RawBuf<uint64_t> boff;  // [ng + 1]
-      uint32_t ng = 0;
-      bool busy = false;
-    };
-    StreamSlot slots[2];
-    std::mutex sm;
-    std::condition_variable scv;
-    std::vector<int> queue_;   // slots handed to the writer, in tile order
-    bool producer_done = false;
-    double ms_writer_busy = 0, ms_wait_slot = 0, ms_gather = 0;
-    tbk_ctx* wctx = nullptr;   // the writer's context (the collapse of the next tile keeps `ctx` busy)
-    std::thread writer_thread;
-    auto writer_main = [&]() {
-      for (;;) {
-        int si = -1;
-        {
-          std::unique_lock<std::mutex> lk(sm);
-          scv.wait(lk, [&] { return !queue_.empty() || producer_done; });
-          if (queue_.empty()) return;
-          si = queue_.front();
-          queue_.erase(queue_.begin());
-        }
-        StreamSlot& S = slots[si];
-        auto a = tnow();
-        const std::function<tbh::RecView(uint32_t)> from_blob = [&S](uint32_t g) {
-          tbh::RecView v;
-          v.p = S.blob.data() + S.boff[g];
-          v.len = (uint32_t)(S.boff[g + 1] - S.boff[g]);
-          return v;
-        };
-        bool wrote = false;
-        uint32_t wdone = 0;
-        if (dev_writer && dw && wctx && outfile.level() != 0) {
-          uint64_t pb = 0, zb = 0;
-          std::string why;
-          wrote = dw->write(wctx, outfile, S.ng, S.rep.data(), S.yc.data(), S.yx.data(), S.yd.data(), 0, from_blob, &pb, &zb, why, &wdone);
-          dev_payload += pb, dev_z += zb;
-          if (!wrote && timing) fprintf(stderr, "device writer stopped after %u of %u groups (%s): host writer\n", wdone, S.ng, why.c_str());
-        }
-        if (!wrote) write_groups_arr(S.ng, from_blob, S.yc.data(), S.yx.data(), S.yd.data(), wdone);
-        const double ms = tms(a, tnow());
-        ms_writer_busy += ms;
-        if (wrote) ms_dev_write += ms;
-        {
-          std::lock_guard<std::mutex> lk(sm);
-          S.busy = false;
-        }
-        scv.notify_all();
-      }
-    };
-    int next_slot = 0;
-    for (; !done_on_device;) {
-      auto ti = tnow();
-      const bool more = inRecords.next_tile(plan, tile_records, nthreads);
-      ms_inflate += tms(ti, tnow());
-      if (!more) break;
-      ++n_tiles;
-      auto t0 = tnow();
-      inRecords.load_tile(tile, opt.strategy == TBK_STRAT_FULL, opt.collapse_same != 0, nthreads, &plan);
-      auto t1 = tnow();
-      tbk_soa_in in = tile.view();
-      size_t n = tile.n();
-      StreamSlot& S = slots[next_slot];
-      {
-        auto w0 = tnow();
-        std::unique_lock<std::mutex> lk(sm);
-        scv.wait(lk, [&] { return !S.busy; });
-        ms_wait_slot += tms(w0, tnow());
-      }
-      S.rep.resize(n ? n : 1);
-      S.yc.resize(n ? n : 1);
-      S.yx.resize(n ? n : 1);
-      S.yd.resize(n ? n : 1);
-      need_ctx();
-      if (!writer_thread.joinable()) {
-        if (dev_writer && api.create(dev, &wctx) != 0) wctx = nullptr;  // (no second context: the host writer takes the output)
-        writer_thread = std::thread(writer_main);
-      }
-      tbk_groups_out out;
-      memset(&out, 0, sizeof(out));
-      out.mem = TBK_MEM_HOST;
-      out.cap_groups = (uint32_t)(n ? n : 1);
-      out.rep = S.rep.data();
-      out.yc = S.yc.data();
-      out.yx = S.yx.data();
-      out.yd = S.yd.data();
-      rc = api.collapse_tile(ctx, &opt, &in, &out);
-      auto t2 = tnow();
-      if (rc == TBK_EUNSORTED) GError("Error: an input file is not coordinate-sorted!\n");
-      if (rc != 0) GError("Error: GPU collapse failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-      // the representatives leave the windows: sizes per slice of groups, a prefix, the copies — every core
-      {
-        const uint32_t ng = out.n_groups;
-        S.ng = ng;
-        S.boff.resize((size_t)ng + 1);
-        const int T = ng < 8192 ? 1 : nthreads;
-        std::vector<uint64_t> part((size_t)T + 1, 0);
-        auto slice = [&](int t, uint32_t* a, uint32_t* b) {
-          *a = (uint32_t)((uint64_t)ng * (uint32_t)t / (uint32_t)T);
-          *b = (uint32_t)((uint64_t)ng * ((uint32_t)t + 1) / (uint32_t)T);
-        };
-        auto par = [&](const std::function<void(int)>& f) {
-          std::vector<std::thread> th;
-          for (int t = 1; t < T; ++t) th.emplace_back(f, t);
-          f(0);
-          for (auto& x : th) x.join();
-        };
-        par([&](int t) {
-          uint32_t a, b;
-          slice(t, &a, &b);
-          uint64_t by = 0;
-          for (uint32_t g = a; g < b; ++g) by += inRecords.record(S.rep[g]).len;
-          part[(size_t)t + 1] = by;
-        });
-        for (int t = 0; t < T; ++t) part[(size_t)t + 1] += part[(size_t)t];
-        S.blob.resize((size_t)part[(size_t)T] + 16);
-        par([&](int t) {
-          uint32_t a, b;
-          slice(t, &a, &b);
-          uint64_t o = part[(size_t)t];
-          for (uint32_t g = a; g < b; ++g) {
-            const tbh::RecView v = inRecords.record(S.rep[g]);
-            S.boff[g] = o;
-            memcpy(S.blob.data() + o, v.p, v.len);
-            o += v.len;
-          }
-        });
-        S.boff[ng] = part[(size_t)T];
-      }
-      auto t3 = tnow();
-      ms_gather += tms(t2, t3);
-      inCounter += out.n_passed;
-      outCounter += out.n_groups;
-      inRecords.release_tile(plan);
-      {
-        std::lock_guard<std::mutex> lk(sm);
-        S.busy = true;
-        queue_.push_back(next_slot);
-      }
-      scv.notify_all();
-      next_slot ^= 1;
-      ms_load += tms(t0, t1);
-      ms_gpu += tms(t1, t2);
-    }
-    if (writer_thread.joinable()) {
-      {
-        std::lock_guard<std::mutex> lk(sm);
-        producer_done = true;
-      }
-      scv.notify_all();
-      auto w0 = tnow();
-      writer_thread.join();
-      ms_tag += tms(w0, tnow());
-      if (wctx) api.destroy(wctx);
-      if (timing)
-        fprintf(stderr, "streamed: %zu tiles; this thread inflate+index %.1f | SoA %.1f | collapse %.1f | gather representatives %.1f | waited for a free slot %.1f | "
-                        "waited for the writer at the end %.1f; writer thread busy %.1f\n",
-                n_tiles, ms_inflate, ms_load, ms_gpu, ms_gather, ms_wait_slot, tms(w0, tnow()), ms_writer_busy);
-    }
-    if (timing) fprintf(stderr, "tiles: %zu (at %.1f ms)\n", n_tiles, tms(t_start, tnow()));
-  }
+  Totals tot;
+  Output out(outfname, inRecords.header(), dev, env);
+  const Inputs inp(inRecords);
+  const Routes can = eligible_routes(env, opt, inp);
+  Route r = Route::fall_through;
+  if (can.hybrid) r = run_hybrid(dev, out, opt, env, inp, tot);
+  else if (can.whole_host) r = run_whole_host(dev, out, opt, env, inp, tot);
+  if (r == Route::fall_through && can.device_decode) r = run_device_decode(dev, out, opt, env, inp, tot);
+  if (r == Route::fall_through) run_streaming(dev, out, opt, env, inRecords, tot);
+  if (env.timing) fprintf(stderr, "tiles: %zu (at %.1f ms)\n", tot.n_tiles, tms(dev.t_start, tnow()));
+  out.close();
   auto t_closed = tnow();
-  if (timing) fprintf(stderr, "writer closed at %.1f ms\n", tms(t_start, t_closed));
-  need_ctx();
+  if (env.timing) fprintf(stderr, "writer closed at %.1f ms\n", tms(dev.t_start, t_closed));
+  dev.wait();
   // (no tbk_destroy / stop: the process ends below, the OS reclaims device and host memory faster than piecewise frees)
-  if (timing && dev_z) fprintf(stderr, "device writer: %.1f MB of tagged records -> %.1f MB of BGZF members in %.1f ms\n", dev_payload / 1e6, dev_z / 1e6, ms_dev_write);
-  if (timing)
+  if (env.timing && out.dev_z)
+    fprintf(stderr, "device writer: %.1f MB of tagged records -> %.1f MB of BGZF members in %.1f ms\n", out.dev_payload / 1e6, out.dev_z / 1e6, out.ms_dev_write);
+  if (env.timing)
     fprintf(stderr, "timing ms: open+context %.1f | inflate+index %.1f | SoA %.1f | collapse (PCIe incl.) %.1f | tag+queue %.1f | total to writer close %.1f\n",
-            tms(t_start, t_ctx), ms_inflate, ms_load, ms_gpu, ms_tag, tms(t_start, t_closed));
-  double p = 100.00 - (double)(outCounter * 100.00) / (double)inCounter;
-  GMessage("%ld input records written as %ld (%.2f%% reduction)\n", (long)inCounter, (long)outCounter, p);
+            tms(dev.t_start, t_ctx), tot.ms_inflate, tot.ms_load, tot.ms_gpu, tot.ms_tag, tms(dev.t_start, t_closed));
+  double p = 100.00 - (double)(tot.out * 100.00) / (double)tot.in;
+  GMessage("%ld input records written as %ld (%.2f%% reduction)\n", (long)tot.in, (long)tot.out, p);
   fflush(stdout);
   fflush(stderr);
-  // the gigabytes of the whole-input path go back in parallel: a process that just exits returns them in one thread while its
+  // the gigabytes of the whole-input routes go back in parallel: a process that just exits returns them in one thread while its
   // caller waits (measured: 0.17 s for 2.7 GB)
   {
     auto a = tnow();
-    if (!getenv("TBK_NO_RELEASE")) tbh::big_release_all(nthreads);  // (TBK_NO_RELEASE: diagnosis — what the exit costs without it)
-    if (timing) fprintf(stderr, "released the large buffers in %.1f ms\n", tms(a, tnow()));
+    tbh::big_release_all(env.threads);
+    if (env.timing) fprintf(stderr, "released the large buffers in %.1f ms\n", tms(a, tnow()));
   }
-  if (getenv("TBK_EXIT_TIMING")) {  // (diagnosis: what is left of the process exit)
+  if (env.exit_timing >= 0) {  // (diagnosis: what is left of the process exit)
     auto a = tnow();
-    if (atoi(getenv("TBK_EXIT_TIMING")) > 1) api.destroy(ctx);
+    if (env.exit_timing > 1) dev.api.destroy(dev.ctx);
     struct timespec ts;
     clock_gettime(CLOCK_REALTIME, &ts);
     fprintf(stderr, "exit timing: tbk_destroy %.1f ms; _exit at %.3f\n", tms(a, tnow()), (double)ts.tv_sec + ts.tv_nsec * 1e-9);
-    if (atoi(getenv("TBK_EXIT_TIMING")) > 2) return 0;  // (a plain return: what a profiler's exit handlers need to write their traces)
+    if (env.exit_timing > 2) return 0;  // (a plain return: what a profiler's exit handlers need to write their traces)
   }
-  if (const char* e = getenv("TBK_EXIT_SLEEP_MS")) usleep((useconds_t)atoi(e) * 1000);  // (diagnosis)
   _exit(0);  // the output is closed and flushed: skip the runtime's teardown of a process that is done (tens of ms of hipFree / unload)
 }
