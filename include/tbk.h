@@ -467,6 +467,38 @@ int tbk_partial_reduce(tbk_ctx* ctx, const tbk_collapse_opts* opts, const int32_
 int tbk_partial_reduce_md(tbk_ctx* ctx, const tbk_collapse_opts* opts, const int32_t* rows, uint32_t n2, const uint32_t* run_off, uint32_t n_runs,
                           const uint32_t* cig, const uint8_t* md, tbk_groups_out* out, tbk_cov_in* view);
 
+/* ---- Track text on the device (ABI version 8, appended) ---------------------------------------------------------------------------
+ * The lines tiecov writes for its three tracks, formatted by kernels from rows that tbk_coverage_tile / tbk_sample_tile produced
+ * (flushCoverage, CJunc::write, flushCoverage(pair): tiecov.cpp:91-95, :237, :289):
+ *   TBK_TRACK_COV     "%s\t%d\t%d\t%.3f\n"                 tid, start, end, val
+ *   TBK_TRACK_JUNC    "%s\t%d\t%d\tJUNC%08d\t%.3f\t%c\n"   tid, start, end, (int)(first_junc + row), val, strand
+ *   TBK_TRACK_SAMPLE  "%s\t%d\t%d\t%ld\t%f\n"              tid, start, end, count, (double)heat
+ * %s is the name of reference tid in the table of tbk_track_names.  %.3f / %f print the exact binary value rounded half to even, as
+ * glibc does, for finite values of magnitude below 2^63; a row outside that range makes the call return TBK_EUNSUPPORTED before any
+ * byte reaches the sink (the caller then formats that track on the host). */
+typedef enum tbk_track_kind { TBK_TRACK_COV = 0, TBK_TRACK_JUNC = 1, TBK_TRACK_SAMPLE = 2 } tbk_track_kind;
+typedef struct tbk_track_rows {
+  int32_t mem;           /* tbk_mem of the arrays (HOST: uploaded by the call)                                       */
+  int32_t kind;          /* tbk_track_kind                                                                          */
+  uint32_t n;            /* rows                                                                                    */
+  uint32_t reserved;
+  const int32_t* tid;
+  const int32_t* start;
+  const int32_t* end;
+  const double* val;     /* COV, JUNC                                                                               */
+  const uint8_t* strand; /* JUNC                                                                                    */
+  const int64_t* count;  /* SAMPLE                                                                                  */
+  const float* heat;     /* SAMPLE                                                                                  */
+  int64_t first_junc;    /* JUNC: the number of row 0 (1 for a whole file)                                          */
+} tbk_track_rows;
+/* receives the text in order, in slices of whole lines (the bytes are only valid during the call); nonzero stops the call (TBK_EINVAL) */
+typedef int (*tbk_track_sink)(void* user, const char* bytes, uint64_t n);
+/* The reference names as CSR (HOST): name t = bytes[off[t], off[t + 1]), no NUL.  Kept by the context until replaced or destroyed. */
+int tbk_track_names(tbk_ctx* ctx, uint32_t n_names, const uint64_t* off, const char* bytes);
+/* Format the rows and hand the text to `sink`; *out_bytes (optional) = the text's size.  The device formats slice k + 1 while the sink
+ * takes slice k (TBK_DEBUG fmt_slice=BYTES sets the slice size, default 32 MiB). */
+int tbk_format_track(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,7 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_collapse_opts_default", "tbk_collapse_tile", "tbk_collapse_finish_yd", "tbk_coverage_tile", "tbk_sample_tile",
            "tbk_groups_to_cov_in", "tbk_bgzf_inflate", "tbk_bam_decode", "tbk_bam_records", "tbk_bam_release", "tbk_shard_prepare", "tbk_shard_probe_max", "tbk_shard_probe_next",
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
-           "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md"]
+           "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track"]
 
 
 class CollapseOpts(C.Structure):
@@ -76,6 +76,17 @@ class SampleOut(C.Structure):
 class EncIn(C.Structure):
     _fields_ = [("mem", C.c_int32), ("n", C.c_uint32), ("rep", _P), ("yc", _P), ("yx", _P), ("yd", _P), ("n_dev", C.c_uint32), ("n_host", C.c_uint32),
                 ("host_blob", _P), ("host_off", _P), ("host_slot", _P), ("first", C.c_uint32), ("from_ctx", _P)]
+
+
+TRACK = {"cov": 0, "junc": 1, "sample": 2}
+
+
+class TrackRows(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("kind", C.c_int32), ("n", C.c_uint32), ("reserved", C.c_uint32), ("tid", _P), ("start", _P), ("end", _P),
+                ("val", _P), ("strand", _P), ("count", _P), ("heat", _P), ("first_junc", C.c_int64)]
+
+
+TRACK_SINK = C.CFUNCTYPE(C.c_int, _P, _P, C.c_uint64)
 
 
 class KernelTime(C.Structure):
@@ -159,6 +170,10 @@ def load():
     L.tbk_kept_results.restype = C.c_int
     L.tbk_warmup.argtypes = [_P]
     L.tbk_warmup.restype = C.c_int
+    L.tbk_track_names.argtypes = [_P, C.c_uint32, _P, _P]
+    L.tbk_track_names.restype = C.c_int
+    L.tbk_format_track.argtypes = [_P, C.POINTER(TrackRows), TRACK_SINK, _P, C.POINTER(C.c_uint64)]
+    L.tbk_format_track.restype = C.c_int
     _lib = L
     return L
 

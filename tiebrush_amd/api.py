@@ -830,6 +830,38 @@ class Context:
         a = int(o.n_intervals)
         return dict(n_sample=a, s_tid=iv[0][:a], s_start=iv[1][:a], s_end=iv[2][:a], s_count=iv[3][:a], s_heat=iv[4][:a])
 
+    # ---- track text -----------------------------------------------------------------------------
+    def track_names(self, names):
+        """The reference names (str or bytes, any length) that tid indexes in format_track's rows."""
+        raw = [n.encode() if isinstance(n, str) else bytes(n) for n in names]
+        off = np.zeros(len(raw) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(b) for b in raw], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(raw) or b"\0", dtype=np.uint8)
+        self._check(self.L.tbk_track_names(self.h, len(raw), off.ctypes.data, blob.ctypes.data), "tbk_track_names")
+
+    def format_track(self, kind, tid, start, end, val=None, strand=None, count=None, heat=None, first_junc=1):
+        """The bytes of one track as tiecov prints it (kind: "cov", "junc" or "sample"), formatted on the device from numpy rows or
+        device tensors; names from track_names().  Raises TbkError(TBK_EUNSUPPORTED) for a value outside the exact range."""
+        keep = []
+        dev = _is_torch(tid)
+        n = _numel(tid)
+        s = _lib.TrackRows(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, _lib.TRACK[kind], n, 0, _addr(tid, np.int32, keep, n),
+                           _addr(start, np.int32, keep, n), _addr(end, np.int32, keep, n), _addr(val, np.float64, keep, n),
+                           _addr(strand, np.uint8, keep, n), _addr(count, np.int64, keep, n), _addr(heat, np.float32, keep, n), int(first_junc))
+        self._order_after_torch(dev)
+        parts = []
+
+        def sink(_user, p, nb):
+            parts.append(C.string_at(p, nb))
+            return 0
+
+        cb = _lib.TRACK_SINK(sink)
+        total = C.c_uint64(0)
+        self._check(self.L.tbk_format_track(self.h, C.byref(s), cb, None, C.byref(total)), "tbk_format_track")
+        text = b"".join(parts)
+        assert len(text) == total.value
+        return text
+
 
 def to_numpy(d):
     """Bring every tensor value of a result dict back to numpy (tests / writers)."""

@@ -31,7 +31,13 @@ struct TbkApi {
   decltype(&tbk_host_free) host_free = nullptr;
   decltype(&tbk_set_profiling) set_profiling = nullptr;
   decltype(&tbk_kernel_times) kernel_times = nullptr;
+  // optional: only the track options (--cov / --junc / --samp) need them; has_tracks() says whether the library has them all
+  decltype(&tbk_coverage_tile) coverage_tile = nullptr;
+  decltype(&tbk_sample_tile) sample_tile = nullptr;
+  decltype(&tbk_track_names) track_names = nullptr;
+  decltype(&tbk_format_track) format_track = nullptr;
   std::string error;
+  bool has_tracks() const { return coverage_tile && sample_tile && track_names && format_track; }
 
   bool load() {
     std::string dir;
@@ -73,6 +79,10 @@ struct TbkApi {
     TBK_BIND(set_profiling, tbk_set_profiling)
     TBK_BIND(kernel_times, tbk_kernel_times)
 #undef TBK_BIND
+    coverage_tile = (decltype(coverage_tile))dlsym(h, "tbk_coverage_tile");
+    sample_tile = (decltype(sample_tile))dlsym(h, "tbk_sample_tile");
+    track_names = (decltype(track_names))dlsym(h, "tbk_track_names");
+    format_track = (decltype(format_track))dlsym(h, "tbk_format_track");
     if (abi_version() != TBK_ABI_VERSION) {
       error = "libtbk.so has another ABI version";
       return false;

@@ -39,6 +39,7 @@
 #include "tagwrite.h"
 #include "tbk_dl.h"
 #include "tmerge.h"
+#include "tracks.h"
 
 extern char** environ;
 
@@ -69,7 +70,12 @@ static const char* USAGE =
     "  --store-frac         YC adds 1/NH per alignment (needs --keep-secondary)\n"
     "  -V,--verbose         echo the command line\n"
     "  --ranks N            shard the input files over N GPUs of this node (one process each), one output BAM\n"
-    "  --writer WHICH       device (default): the output records are tagged and BGZF-compressed on the GPU; host: by the CPU cores\n";
+    "  --writer WHICH       device (default): the output records are tagged and BGZF-compressed on the GPU; host: by the CPU cores\n"
+    "  --cov PREFIX         also write tiecov's coverage track of the output (as tiecov -c; - or stdout: standard output)\n"
+    "  --junc PREFIX        also write tiecov's junction track of the output (as tiecov -j)\n"
+    "  --samp PREFIX        also write tiecov's sample-count track of the output (as tiecov -s; needs @CO SAMPLE: header lines)\n"
+    "  --bigwig             write the coverage track as PREFIX.bigwig (as tiecov -W; needs --cov)\n"
+    "                       (the tracks are what tiecov writes when it reads OUT.bam; not with --ranks)\n";
 
 // a buffer that is allocated, not initialised (untouched pages cost nothing), on huge pages when it is large, and not freed at
 // the end: these buffers live as long as the process, which ends with _exit — returning gigabytes page by page first only
@@ -165,6 +171,7 @@ struct Env {
   bool no_keep_results = env_set("TBK_NO_KEEP_RESULTS");  // the tags' values come back with the collapse
   bool test_whole_enomem = env_set("TBK_TEST_WHOLE_ENOMEM");  // test hook: a whole-input collapse reports TBK_ENOMEM
   bool test_fetch_enomem = env_set("TBK_TEST_FETCH_ENOMEM");  // test hook: the representative-record fetch reports TBK_ENOMEM
+  bool track_host_fmt = env_set("TBK_TRACK_HOST_FMT");        // the track text by the host formatter instead of tbk_format_track
   int exit_timing = (int)env_num("TBK_EXIT_TIMING", -1);      // diagnosis of the process exit (-1: unset)
   std::string python = getenv("TBK_PYTHON") ? getenv("TBK_PYTHON") : "python3";  // the interpreter that runs --ranks
 };
@@ -216,6 +223,91 @@ static void spawn_ranks_launcher_if_asked(int argc, char* argv[], const Env& env
   fflush(stderr);
   _exit(WIFEXITED(status) ? WEXITSTATUS(status) : 128 + (WIFSIGNALED(status) ? WTERMSIG(status) : 0));
 }
+
+// ---- tracks (--cov / --junc / --samp): what tiecov would read back from the output BAM.  Every group that goes into the file adds its
+// record here as tiecov decodes it (tiecov_main.cpp: tid, pos, flag, CIGAR, spliceStrand from XS / ts) with the YC / YX values the writer
+// put into that record.  Those are (float)yc and yx for a record that carried none of the three tags, and otherwise whatever the tag
+// update left: an integer YC of an old TieBrush input is not replaced by bam_aux_update_float (bam.cpp: update_float), and tiecov reads
+// that stale value.  The one source of the written bytes is the writer's own tagging (tagwrite.cpp), so such records are tagged again
+// here and their tags read back.  Once the routes are done the whole file's records go through tbk_coverage_tile / tbk_sample_tile in one
+// call each, as in tiecov, so the JUNC numbering and the bundles run over the whole file whatever tiles the collapse used.
+struct TrackRecs {
+  std::vector<int32_t> tid, pos;
+  std::vector<uint16_t> flag;
+  std::vector<uint32_t> cig_off{0}, cig;
+  std::vector<double> yc;
+  std::vector<int64_t> yx;
+  std::vector<uint8_t> strand;
+
+  static void written_values(const tbh::RecView& v, double gyc, int64_t gyx, int32_t gyd, double* wyc, int64_t* wyx) {
+    bool fresh = gyx >= 0 && gyx <= (int64_t)UINT32_MAX;  // (tagwrite.cpp: the tags are appended as they are)
+    for (const uint8_t* a = v.aux_begin(); fresh && a + 3 <= v.aux_end();) {
+      const size_t sz = tbh::aux_field_size(a, v.aux_end());
+      if (!sz) break;
+      if (a[0] == 'Y' && (a[1] == 'C' || a[1] == 'X' || a[1] == 'D')) fresh = false;
+      a += sz;
+    }
+    if (fresh) {
+      *wyc = (double)(float)gyc, *wyx = gyx;
+      return;
+    }
+    thread_local std::vector<uint8_t> o;
+    thread_local tbh::BamRec rr;
+    o.clear();
+    tbh::append_tagged(v, gyc, gyx, gyd, o, rr);
+    tbh::RecView w;
+    w.p = o.data() + 4;
+    w.len = (uint32_t)(o.size() - 4);
+    *wyc = 1.0, *wyx = 1;  // (tiecov.cpp:482-485 defaults)
+    if (const uint8_t* t = tbh::aux_get(w.aux_begin(), w.aux_end(), "YC")) *wyc = tbh::aux2f(t);
+    if (const uint8_t* t = tbh::aux_get(w.aux_begin(), w.aux_end(), "YX")) *wyx = tbh::aux2i(t);
+  }
+
+  // groups [0, ng) of one write, in file order: rec(g) their records, gyc / gyx / gyd the collapse's values
+  void add(uint32_t ng, const RecFn& rec, const double* gyc, const int64_t* gyx, const int32_t* gyd, int threads) {
+    const size_t b = tid.size();
+    tid.resize(b + ng), pos.resize(b + ng), flag.resize(b + ng), yc.resize(b + ng), yx.resize(b + ng), strand.resize(b + ng);
+    cig_off.resize(b + ng + 1);
+    const int T = ng < 16384 ? 1 : std::max(1, threads);
+    auto par = [&](const std::function<void(uint32_t, uint32_t)>& f) {
+      std::vector<std::thread> th;
+      for (int t = 1; t < T; ++t) th.emplace_back(f, (uint32_t)((uint64_t)ng * t / T), (uint32_t)((uint64_t)ng * (t + 1) / T));
+      f(0, (uint32_t)((uint64_t)ng / T));
+      for (auto& x : th) x.join();
+    };
+    par([&](uint32_t lo, uint32_t hi) {
+      for (uint32_t g = lo; g < hi; ++g) {
+        const tbh::RecView v = rec(g);
+        const size_t i = b + g;
+        tid[i] = v.tid(), pos[i] = v.pos(), flag[i] = v.flag();
+        cig_off[i + 1] = v.n_cigar();
+        written_values(v, gyc[g], gyx[g], gyd[g], &yc[i], &yx[i]);
+        const uint8_t *a = v.aux_begin(), *e = v.aux_end();  // spliceStrand as tiecov_main.cpp reads it
+        char xs = 0, ts = 0;
+        if (const uint8_t* t = tbh::aux_get(a, e, "XS")) xs = (*t == 'A' || *t == 'Z') ? (char)t[1] : 0;
+        if (!xs)
+          if (const uint8_t* t = tbh::aux_get(a, e, "ts")) ts = (*t == 'A' || *t == 'Z') ? (char)t[1] : 0;
+        char c = xs;
+        if (c == 0 && (ts == '+' || ts == '-')) c = (flag[i] & 0x10) ? (ts == '+' ? '-' : '+') : ts;
+        strand[i] = (uint8_t)((c == '+' || c == '-') ? c : '.');
+      }
+    });
+    uint64_t ops = cig_off[b];
+    for (size_t i = b; i < b + ng; ++i) {
+      const uint32_t k = cig_off[i + 1];
+      cig_off[i + 1] = (uint32_t)(ops += k);
+      if (ops >= (1ull << 32)) GError("Error: the output is too large for one coverage tile (--cov / --junc / --samp)\n");
+    }
+    cig.resize(ops);
+    par([&](uint32_t lo, uint32_t hi) {
+      for (uint32_t g = lo; g < hi; ++g) {
+        const tbh::RecView v = rec(g);
+        uint32_t* o = cig.data() + cig_off[b + g];
+        for (uint32_t c = 0; c < v.n_cigar(); ++c) o[c] = v.cigar(c);
+      }
+    });
+  }
+};
 
 // The inputs as the routes see them.
 struct Inputs {
@@ -274,7 +366,7 @@ class Device {
   const Clock t_start;         // the run's start
   double ms_ready = 0;         // the context existed this long after it
 
-  Device(const Env& env, const tbk_collapse_opts& opt, bool dev_writer, Clock start) : t_start(start), env_(env), opt_(opt) {
+  Device(const Env& env, const tbk_collapse_opts& opt, bool dev_writer, bool tracks, Clock start) : t_start(start), env_(env), opt_(opt), tracks_(tracks) {
     thread_ = std::thread([this, dev_writer] { bring_up(dev_writer); });
   }
   // the context, warmed (this joins the helper thread)
@@ -302,6 +394,7 @@ class Device {
  private:
   const Env& env_;
   const tbk_collapse_opts opt_;
+  const bool tracks_;
   std::thread thread_;
   bool joined_ = false, api_ok_ = false, warm_ = false;
   int rc_ = 0;
@@ -313,6 +406,7 @@ class Device {
   void check() {
     if (!api_ok_) GError("Error: cannot load libtbk.so (%s); this build has no CPU collapse path\n", api.error.c_str());
     if (rc_ != 0) GError("Error: cannot use GPU %d (%s); this build has no CPU collapse path\n", env_.device, api.strerror_(rc_));
+    if (tracks_ && !api.has_tracks()) GError("Error: --cov / --junc / --samp: libtbk.so lacks the track entry points (tbk_format_track)\n");
   }
   void bring_up(bool dev_writer) {
     api_ok_ = api.load();
@@ -398,7 +492,8 @@ class Output {
   double ms_dev_write = 0;              // the device writer's time, its bytes of tagged records and of BGZF members
   uint64_t dev_payload = 0, dev_z = 0;
 
-  Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env) : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env) {}
+  Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env, TrackRecs* tracks)
+      : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env), tracks_(tracks) {}
   // (the end of the file: the EOF member)
   void close() { file_.reset(); }
   // whether the whole-input routes leave the tags' values on the device for the device writer (tbk_collapse_opts.keep_results)
@@ -408,10 +503,12 @@ class Output {
   // keep_results).  The device writer takes them when there is one (devwriter.h; c: its context): tags, framing and BGZF deflate as
   // kernels, the host only gathers the records it decoded itself (rec(g) for rep[g] >= n_dev) and appends the finished members.  From
   // the group it refuses on, the host writer goes on — after before_host(), which readies what rec() reads for it.  When that fails,
-  // write returns false; the groups before the refused one are in the file (groups says how many).
+  // write returns false; the groups before the refused one are in the file (groups says how many).  With tracks, the groups of a write
+  // that returns true go to them (after before_host() when the device writer took every group: the tracks read the records).
   bool write(tbk_ctx* c, uint32_t ng, const uint32_t* rp, const double* ycp, const int64_t* yxp, const int32_t* ydp, uint32_t n_dev, const RecFn& rec,
              const PrefetchFn& prefetch = nullptr, const std::function<bool()>& before_host = nullptr) {
     uint32_t done = 0;
+    const bool kept = ycp == nullptr;
     if (c && dev_.dw && file_->level() != 0) {
       auto a = tnow();
       uint64_t pb = 0, zb = 0;
@@ -419,7 +516,10 @@ class Output {
       const bool ok = dev_.dw->write(c, *file_, ng, rp, ycp, yxp, ydp, n_dev, rec, &pb, &zb, why, &done, prefetch);
       ms_dev_write += tms(a, tnow()), dev_payload += pb, dev_z += zb;
       groups += ok ? ng : done;
-      if (ok) return true;
+      if (ok) {
+        if (tracks_ && before_host && !before_host()) GError("Error: fetching the representative records for the tracks failed after %llu groups were written\n", (unsigned long long)groups);
+        return add_tracks(c, ng, ycp, yxp, ydp, kept, rec);
+      }
       if (env_.timing) fprintf(stderr, "device writer stopped after %u of %u groups (%s): host writer\n", done, ng, why.c_str());
     }
     if (before_host && !before_host()) return false;
@@ -436,7 +536,7 @@ class Output {
     if (!tbh::tag_deflate_ordered(ng - done, from_done, ycp + done, yxp + done, ydp + done, file_->level(), env_.threads, emit, env_.threads > 1 ? 16384 : 0))
       GError("Error: deflate failed\n");
     groups += ng - done;
-    return true;
+    return add_tracks(c, ng, ycp, yxp, ydp, kept && done > 0, rec);
   }
 
   // A route that cannot finish hands the inputs over to the next one, which writes from group 0: only while the file holds no groups.
@@ -450,7 +550,134 @@ class Output {
   std::unique_ptr<GSamWriter> file_;
   Device& dev_;
   const Env& env_;
+  TrackRecs* tracks_;
+
+  // fetch: the values of groups [0, ng) are on the device only (keep_results)
+  bool add_tracks(tbk_ctx* c, uint32_t ng, const double* ycp, const int64_t* yxp, const int32_t* ydp, bool fetch, const RecFn& rec) {
+    if (!tracks_) return true;
+    auto a = tnow();
+    if (fetch) {
+      yc.resize(ng), yx.resize(ng), yd.resize(ng);
+      const int frc = dev_.api.kept_results(c, 0, ng, nullptr, yc.data(), yx.data(), yd.data());
+      if (frc != 0) GError("Error: fetching the collapse's results failed: %s (%s)\n", dev_.api.strerror_(frc), dev_.api.last_error(c));
+      ycp = yc.data(), yxp = yx.data(), ydp = yd.data();
+    }
+    tracks_->add(ng, rec, ycp, yxp, ydp, env_.threads);
+    if (env_.timing) fprintf(stderr, "tracks: %u records added in %.1f ms\n", ng, tms(a, tnow()));
+    return true;
+  }
 };
+
+static int fwrite_sink(void* user, const char* p, uint64_t n) { return fwrite(p, 1, n, (FILE*)user) == n ? 0 : 1; }
+
+// The tracks of the whole output, as tiecov_main.cpp computes them from its decode of the file: coverage and junctions in one
+// tbk_coverage_tile, the sample counts in tbk_sample_tile, the text by tbk_format_track (the host formatter when the device
+// formatter refuses a value, or with TBK_TRACK_HOST_FMT).
+static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, TrackRecs& T, const std::vector<std::string>& names, int num_samples) {
+  TbkApi& api = dev.api;
+  tbk_ctx* ctx = dev.ctx;
+  auto t0 = tnow();
+  const size_t n = T.tid.size(), co = T.cig.size();
+  tbk_cov_in in;
+  memset(&in, 0, sizeof(in));
+  in.mem = TBK_MEM_HOST;
+  in.n_records = (uint32_t)n;
+  in.n_cigar_ops = (uint32_t)co;
+  in.tid = T.tid.data(), in.pos = T.pos.data(), in.flag = T.flag.data(), in.cig_off = T.cig_off.data(), in.cig = T.cig.data();
+  in.yc = T.yc.data(), in.strand = T.strand.data(), in.yx = T.yx.data();
+  if (!env.track_host_fmt) {
+    std::vector<uint64_t> off(names.size() + 1, 0);
+    std::string blob;
+    for (size_t t = 0; t < names.size(); ++t) blob += names[t], off[t + 1] = blob.size();
+    const int rc = api.track_names(ctx, (uint32_t)names.size(), off.data(), blob.data());
+    if (rc != 0) GError("Error: GPU track names failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+  }
+  double ms_text = 0;
+  int host_tracks = 0;
+  // the text of one track: the device formatter, or false (then the caller's host formatter)
+  auto device_text = [&](FILE* f, tbk_track_rows r) {
+    if (env.track_host_fmt) return ++host_tracks, false;
+    const int rc = api.format_track(ctx, &r, fwrite_sink, f, nullptr);
+    if (rc == TBK_EUNSUPPORTED) return ++host_tracks, false;
+    if (rc == TBK_EINVAL && std::string(api.last_error(ctx)).find("sink") != std::string::npos) GError("Error: failed to write an output line\n");
+    if (rc != 0) GError("Error: GPU track text failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    return true;
+  };
+  auto rows = [](int kind, uint32_t nr, const int32_t* tid, const int32_t* st, const int32_t* en) {
+    tbk_track_rows r;
+    memset(&r, 0, sizeof(r));
+    r.mem = TBK_MEM_HOST, r.kind = kind, r.n = nr, r.tid = tid, r.start = st, r.end = en, r.first_junc = 1;
+    return r;
+  };
+  double ms_cov = 0, ms_samp = 0;
+  if (tf.cov || tf.cov_bw || tf.junc) {
+    size_t ci = (tf.cov || tf.cov_bw) ? 2 * co + 2 * n + 16 : 0, cj = tf.junc ? co + 16 : 0;
+    std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
+    std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
+    std::vector<uint8_t> jstr(cj ? cj : 1);
+    tbk_cov_out o;
+    memset(&o, 0, sizeof(o));
+    o.mem = TBK_MEM_HOST;
+    o.cap_intervals = (uint32_t)ci;
+    o.iv_tid = it.data(), o.iv_start = is.data(), o.iv_end = ie.data(), o.iv_val = iv.data();
+    o.cap_junctions = (uint32_t)cj;
+    o.j_tid = jt.data(), o.j_start = js.data(), o.j_end = je.data(), o.j_strand = jstr.data(), o.j_val = jv.data();
+    auto a = tnow();
+    const int rc = api.coverage_tile(ctx, &in, &o);
+    ms_cov = tms(a, tnow());
+    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+    if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    if (tf.cov) {
+      tbk_track_rows r = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
+      r.val = iv.data();
+      auto a = tnow();
+      if (!device_text(tf.cov, r)) tbh::emit_cov_lines(tf.cov, names, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
+      ms_text += tms(a, tnow());
+    }
+    if (tf.cov_bw) {
+      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
+      tf.close_bigwig();
+    }
+    if (tf.junc) {
+      tbk_track_rows r = rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
+      r.val = jv.data(), r.strand = jstr.data();
+      auto a = tnow();
+      if (!device_text(tf.junc, r)) tbh::emit_junc_lines(tf.junc, names, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
+      ms_text += tms(a, tnow());
+    }
+  }
+  if (tf.samp) {  // (sized and retried as tiecov_main.cpp does)
+    size_t cs = 2 * co + 2 * n + 16;
+    std::vector<int32_t> st, ss, se;
+    std::vector<int64_t> sc;
+    std::vector<float> sh;
+    tbk_sample_out so;
+    int rc = 0;
+    auto a = tnow();
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      st.resize(cs), ss.resize(cs), se.resize(cs), sc.resize(cs), sh.resize(cs);
+      memset(&so, 0, sizeof(so));
+      so.mem = TBK_MEM_HOST;
+      so.cap_intervals = (uint32_t)cs;
+      so.iv_tid = st.data(), so.iv_start = ss.data(), so.iv_end = se.data(), so.iv_count = sc.data(), so.iv_heat = sh.data();
+      rc = api.sample_tile(ctx, &in, num_samples, &so);
+      if (rc != TBK_E2BIG) break;
+      cs = (size_t)so.n_intervals + 16;
+    }
+    ms_samp = tms(a, tnow());
+    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+    if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    tbk_track_rows r = rows(TBK_TRACK_SAMPLE, so.n_intervals, st.data(), ss.data(), se.data());
+    r.count = sc.data(), r.heat = sh.data();
+    auto b = tnow();
+    if (!device_text(tf.samp, r)) tbh::emit_samp_lines(tf.samp, names, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());
+    ms_text += tms(b, tnow());
+  }
+  tf.close();
+  if (env.timing)
+    fprintf(stderr, "tracks ms: %zu records | coverage call %.1f | sample call %.1f | text + write %.1f (%d of the tracks by the host formatter) | total %.1f\n", n, ms_cov,
+            ms_samp, ms_text, host_tracks, tms(t0, tnow()));
+}
 
 // What the summary lines count.
 struct Totals {
@@ -981,12 +1208,26 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
   }
 }
 
+// the track options with --ranks: refused before the launcher starts (the multi-rank tracks are not built)
+static void refuse_tracks_with_ranks(int argc, char* argv[]) {
+  bool ranks = false, tracks = false;
+  for (int i = 1; i < argc; ++i) {
+    ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
+    for (const char* o : {"--cov", "--junc", "--samp", "--bigwig"}) {
+      const size_t k = strlen(o);
+      tracks = tracks || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
+    }
+  }
+  if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
+}
+
 int main(int argc, char* argv[]) {
   const Env env;
+  refuse_tracks_with_ranks(argc, argv);
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;SMLPEDVho:N:Q:F:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;SMLPEDVho:N:Q:F:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1042,13 +1283,31 @@ int main(int argc, char* argv[]) {
   }
   if (opt.flags_mask != 0) GError("Error: -F is not supported by the GPU build (its reference semantics are unpinned)\n");
   if (opt.keep_unmapped) GError("Error: -M/--keep-unmap is not supported by the GPU build\n");
+  const std::string cov_prefix = args.getOpt("cov") ? args.getOpt("cov") : "", junc_prefix = args.getOpt("junc") ? args.getOpt("junc") : "",
+                    samp_prefix = args.getOpt("samp") ? args.getOpt("samp") : "";
+  const bool bigwig = args.getOpt("bigwig") != nullptr;
+  if (bigwig && cov_prefix.empty()) GError("Error: --bigwig needs --cov\n");
+  const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty();
   while (const char* ifn = args.nextNonOpt()) inRecords.addFile(tbh_realpath(ifn).c_str());
 
-  Device dev(env, opt, dev_writer, tnow());
+  Device dev(env, opt, dev_writer, tracks, tnow());
   inRecords.start();
   auto t_ctx = tnow();
   Totals tot;
-  Output out(outfname, inRecords.header(), dev, env);
+  // the tracks: the output header's sample lines (load_sample_info, commons.h:47-71) are checked before any work, the files opened
+  std::unique_ptr<TrackRecs> trecs;
+  tbh::TrackFiles tfiles;
+  int num_samples = 0;
+  if (tracks) {
+    sam_hdr_t* h = inRecords.header();
+    if (!samp_prefix.empty()) {
+      num_samples = (int)h->co_samples().size();
+      if (num_samples == 0) GError("Error: no sample lines found in header");
+    }
+    tfiles.open(cov_prefix, junc_prefix, samp_prefix, bigwig, h->target_name, h->target_len);
+    trecs.reset(new TrackRecs());
+  }
+  Output out(outfname, inRecords.header(), dev, env, trecs.get());
   const Inputs inp(inRecords);
   const Routes can = eligible_routes(env, opt, inp);
   Route r = Route::fall_through;
@@ -1058,6 +1317,10 @@ int main(int argc, char* argv[]) {
   if (r == Route::fall_through) run_streaming(dev, out, opt, env, inRecords, tot);
   if (env.timing) fprintf(stderr, "tiles: %zu (at %.1f ms)\n", tot.n_tiles, tms(dev.t_start, tnow()));
   out.close();
+  if (trecs) {
+    dev.wait();
+    write_tracks(dev, env, tfiles, *trecs, inRecords.header()->target_name, num_samples);
+  }
   auto t_closed = tnow();
   if (env.timing) fprintf(stderr, "writer closed at %.1f ms\n", tms(dev.t_start, t_closed));
   dev.wait();

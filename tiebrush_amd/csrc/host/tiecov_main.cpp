@@ -12,8 +12,8 @@
 
 #include "../../../include/tbk.h"
 #include "GSam.h"
-#include "bigwig.h"
 #include "args.h"
+#include "tracks.h"
 
 #define VERSION "0.0.7"
 
@@ -30,46 +30,6 @@ static const char* USAGE =
     "  -s PREFIX    estimated number of samples per position as bedGraph (needs @CO SAMPLE: header lines)\n"
     "  -W           write the coverage (-c) as a bigWig file (PREFIX.bigwig) instead of a bedGraph\n"
     " At least one of -c / -j / -s is required.\n";
-
-static bool ends_with(const std::string& s, const char* suf) {
-  size_t n = strlen(suf);
-  return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
-}
-
-// Text output: the lines are independent, so slices of them are formatted by worker threads (same printf formats as the
-// reference) and written in order.
-template <class F>
-static void emit_lines(FILE* f, uint32_t n, F fmt) {
-  unsigned hw = (unsigned)tbh::cpu_budget();
-  size_t nt = n < 50000 ? 1 : std::max<size_t>(1, std::min<size_t>(hw ? hw : 4, 32));
-  std::vector<std::string> parts(nt);
-  auto work = [&](size_t t) {
-    const uint32_t lo = (uint32_t)((uint64_t)n * t / nt), hi = (uint32_t)((uint64_t)n * (t + 1) / nt);
-    std::string& o = parts[t];
-    o.reserve((size_t)(hi - lo) * 40);
-    char b[1024];
-    for (uint32_t i = lo; i < hi; ++i) {
-      int len = fmt(i, b, sizeof(b));
-      if (len < 0) len = 0;
-      if ((size_t)len >= sizeof(b)) {  // a very long reference name: format again into a buffer that fits
-        std::vector<char> big((size_t)len + 1);
-        len = fmt(i, big.data(), big.size());
-        o.append(big.data(), (size_t)len);
-      } else {
-        o.append(b, (size_t)len);
-      }
-    }
-  };
-  if (nt == 1) {
-    work(0);
-  } else {
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; ++t) th.emplace_back(work, t);
-    for (auto& x : th) x.join();
-  }
-  for (auto& o : parts)
-    if (!o.empty() && fwrite(o.data(), 1, o.size(), f) != o.size()) GError("Error: failed to write an output line\n");
-}
 
 int main(int argc, char* argv[]) {
   Args args(argc, argv, "help;verbose;version;DVWhc:s:j:");
@@ -106,44 +66,19 @@ int main(int argc, char* argv[]) {
   std::string infname = args.nextNonOpt();
   GSamReader samreader(infname.c_str(), SAM_QNAME | SAM_FLAG | SAM_RNAME | SAM_POS | SAM_CIGAR | SAM_AUX);
   sam_hdr_t* hdr = samreader.header();
-  FILE *coutf = nullptr, *joutf = nullptr, *soutf = nullptr;
-  tbh::BigWigWriter bw;
-  bool cov_bw = false;
-  if (!covfname.empty()) {
-    if (covfname == "-" || covfname == "stdout") {
-      coutf = stdout;
-    } else if (bigwig) {  // tiecov.cpp:365-402
-      if (!ends_with(covfname, ".bigwig")) covfname += ".bigwig";
-      std::vector<std::string> names;
-      std::vector<uint32_t> lens;
-      for (int t = 0; t < hdr->n_targets; ++t) {
-        names.push_back(hdr->target_name[t]);
-        lens.push_back(hdr->target_len[t]);
-      }
-      std::string err;
-      if (!bw.open(covfname, names, lens, err)) GError("Error creating file %s\n", covfname.c_str());
-      cov_bw = true;
-    } else {
-      if (!ends_with(covfname, ".bedgraph")) covfname += ".bedgraph";
-      coutf = fopen(covfname.c_str(), "w");
-      if (!coutf) GError("Error creating file %s\n", covfname.c_str());
-      fprintf(coutf, "track type=bedGraph\n");
+  // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
+  tbh::TrackFiles tf;
+  {
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens;
+    for (int t = 0; t < hdr->n_targets; ++t) {
+      names.push_back(hdr->target_name[t]);
+      lens.push_back(hdr->target_len[t]);
     }
+    tf.open(covfname, jfname, sfname, bigwig, names, lens);
   }
-  if (!jfname.empty()) {
-    if (!ends_with(jfname, ".bed")) jfname += ".bed";
-    joutf = fopen(jfname.c_str(), "w");
-    if (!joutf) GError("Error creating file %s\n", jfname.c_str());
-    fprintf(joutf, "track name=junctions\n");
-  }
-  if (!sfname.empty()) {
-    if (!ends_with(sfname, ".bedgraph")) sfname += ".bedgraph";
-    soutf = fopen(sfname.c_str(), "w");
-    if (!soutf) GError("Error creating file %s\n", sfname.c_str());
-    fprintf(soutf,
-            "track type=bedGraph name=\"Sample Count Heatmap\" description=\"Sample Count Heatmap\" visibility=full "
-            "graphType=\"heatmap\" color=200,100,0 altColor=0,100,200\n");
-  }
+  FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
+  const bool cov_bw = tf.cov_bw;
   int num_samples = 0;
   if (soutf) {  // load_sample_info (commons.h:47-71)
     num_samples = (int)hdr->co_samples().size();
@@ -156,6 +91,10 @@ int main(int argc, char* argv[]) {
   std::thread ctx_thread([&]() { rc = tbk_create(dev, &ctx); });
   // ---- decode to SoA (tiecov.cpp:482-485 defaults: YC absent -> 1.0, YX absent -> 1)
   tbh::BamFile* bf = samreader.file();
+  {  // (the reader opened the header only: its records are inflated on demand, and this decode takes the whole file)
+    std::string err;
+    if (!bf->load(infname, err, std::max(1, tbh::cpu_budget()))) GError("Error: could not read %s (%s)\n", infname.c_str(), err.c_str());
+  }
   size_t n = bf->n();
   std::vector<int32_t> tid(n), pos(n);
   std::vector<uint16_t> flag(n);
@@ -240,20 +179,13 @@ int main(int argc, char* argv[]) {
     rc = tbk_coverage_tile(ctx, &in, &o);
     if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
     if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-    if (coutf)  // flushCoverage, tiecov.cpp:237
-      emit_lines(coutf, o.n_intervals, [&](uint32_t i, char* b, size_t cap) {
-        return snprintf(b, cap, "%s\t%d\t%d\t%.3f\n", hdr->target_name[it[i]].c_str(), is[i], ie[i], iv[i]);
-      });
+    if (coutf) tbh::emit_cov_lines(coutf, hdr->target_name, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());  // flushCoverage, tiecov.cpp:237
     if (cov_bw) {  // flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the same intervals, the value as a float
-      for (uint32_t i = 0; i < o.n_intervals; ++i) bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
-      std::string err;
-      if (!bw.close(err)) GError("Error: writing %s failed (%s)\n", covfname.c_str(), err.c_str());
+      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
+      tf.close_bigwig();
     }
     if (joutf)  // CJunc::write, tiecov.cpp:91-95
-      emit_lines(joutf, o.n_junctions, [&](uint32_t i, char* b, size_t cap) {
-        return snprintf(b, cap, "%s\t%d\t%d\tJUNC%08d\t%.3f\t%c\n", hdr->target_name[jt[i]].c_str(), js[i], je[i], (int)i + 1, jv[i],
-                        (char)jstr[i]);
-      });
+      tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
   }
   if (soutf) {
     // the value of the track changes only where an M segment starts or ends: at most 2 intervals per CIGAR operation + 2 per
@@ -284,13 +216,9 @@ int main(int argc, char* argv[]) {
     }
     if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
     if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-    emit_lines(soutf, so.n_intervals, [&](uint32_t i, char* b, size_t cap) {  // flushCoverage(pair), tiecov.cpp:289
-      return snprintf(b, cap, "%s\t%d\t%d\t%ld\t%f\n", hdr->target_name[st[i]].c_str(), ss[i], se[i], (long)sc[i], sh[i]);
-    });
+    tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
   }
-  if (coutf && coutf != stdout) fclose(coutf);
-  if (joutf) fclose(joutf);
-  if (soutf) fclose(soutf);
+  tf.close();
   tbk_destroy(ctx);
   return 0;
 }

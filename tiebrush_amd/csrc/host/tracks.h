@@ -1,0 +1,84 @@
+// tracks.h — tiecov's three track files, shared by the tiecov command line and by `tiebrush --cov / --junc / --samp`: file names and
+// header lines (tiecov.cpp:365-402 and the openings around them), and the host formatter of the lines (flushCoverage :237,
+// CJunc::write :91-95, flushCoverage(pair) :289).  The host formatter is what tiecov prints with, the reference the device formatter
+// (tbk_format_track) is tested against, and the command line's fallback when the device formatter refuses a track.
+#pragma once
+#include <stdint.h>
+#include <stdio.h>
+
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "bigwig.h"
+#include "bgzf.h"
+
+namespace tbh {
+
+// The open track files.  An empty prefix: that track is not written.  Coverage goes to stdout for "-" / "stdout", to PREFIX.bigwig
+// with `bigwig`, else to PREFIX.bedgraph; junctions to PREFIX.bed; the sample counts to PREFIX.bedgraph.  Errors are fatal (GError).
+struct TrackFiles {
+  FILE *cov = nullptr, *junc = nullptr, *samp = nullptr;
+  BigWigWriter bw;
+  bool cov_bw = false;
+  std::string cov_name;
+  void open(std::string cov_prefix, std::string junc_prefix, std::string samp_prefix, bool bigwig, const std::vector<std::string>& names,
+            const std::vector<uint32_t>& lens);
+  void close_bigwig();  // (after every interval went to bw)
+  void close();
+};
+
+// Text output: the lines are independent, so slices of them are formatted by worker threads and written in order.
+// fmt(i, buf, cap) is snprintf-like: it returns the line's length even when that is more than cap.
+template <class F>
+void emit_lines(FILE* f, uint32_t n, F fmt);
+
+// the three formats, as the reference prints them
+int fmt_cov_line(char* b, size_t cap, const char* name, int32_t start, int32_t end, double val);
+int fmt_junc_line(char* b, size_t cap, const char* name, int32_t start, int32_t end, int number, double val, char strand);
+int fmt_samp_line(char* b, size_t cap, const char* name, int32_t start, int32_t end, int64_t count, float heat);
+
+// whole tracks from row arrays (first_junc: the JUNC number of row 0)
+void emit_cov_lines(FILE* f, const std::vector<std::string>& names, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end,
+                    const double* val);
+void emit_junc_lines(FILE* f, const std::vector<std::string>& names, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end,
+                     const double* val, const uint8_t* strand, int64_t first_junc);
+void emit_samp_lines(FILE* f, const std::vector<std::string>& names, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end,
+                     const int64_t* count, const float* heat);
+
+void GErrorWrite();  // [[noreturn]]: "failed to write an output line"
+
+template <class F>
+void emit_lines(FILE* f, uint32_t n, F fmt) {
+  unsigned hw = (unsigned)cpu_budget();
+  size_t nt = n < 50000 ? 1 : std::max<size_t>(1, std::min<size_t>(hw ? hw : 4, 32));
+  std::vector<std::string> parts(nt);
+  auto work = [&](size_t t) {
+    const uint32_t lo = (uint32_t)((uint64_t)n * t / nt), hi = (uint32_t)((uint64_t)n * (t + 1) / nt);
+    std::string& o = parts[t];
+    o.reserve((size_t)(hi - lo) * 40);
+    char b[1024];
+    for (uint32_t i = lo; i < hi; ++i) {
+      int len = fmt(i, b, sizeof(b));
+      if (len < 0) len = 0;
+      if ((size_t)len >= sizeof(b)) {  // a very long reference name: format again into a buffer that fits
+        std::vector<char> big((size_t)len + 1);
+        len = fmt(i, big.data(), big.size());
+        o.append(big.data(), (size_t)len);
+      } else {
+        o.append(b, (size_t)len);
+      }
+    }
+  };
+  if (nt == 1) {
+    work(0);
+  } else {
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; ++t) th.emplace_back(work, t);
+    for (auto& x : th) x.join();
+  }
+  for (auto& o : parts)
+    if (!o.empty() && fwrite(o.data(), 1, o.size(), f) != o.size()) GErrorWrite();
+}
+
+}  // namespace tbh

@@ -525,6 +525,7 @@ void tbk_debug_parse(const char* spec, TbkDebug* out) {
     else if (k == "no_register") out->no_register = on;
     else if (k == "phases") out->phases = on;
     else if (k == "no_bounce") out->no_bounce = on;
+    else if (k == "fmt_slice") out->fmt_slice = u;
   }
 }
 
@@ -611,6 +612,10 @@ void tbk_destroy(tbk_ctx* ctx) {
   if (ctx->d_view) (void)hipFree(ctx->d_view);
   if (ctx->d_unpack) (void)hipFree(ctx->d_unpack);
   if (ctx->kept) (void)hipFree(ctx->kept);
+  if (ctx->d_names) (void)hipFree(ctx->d_names);
+  if (ctx->d_name_off) (void)hipFree(ctx->d_name_off);
+  for (void* p : ctx->fmt_pin)
+    if (p) (void)hipHostFree(p);
   if (ctx->bounce) (void)hipHostFree(ctx->bounce);
   tbk_enc_free(ctx);
   tbk_stager_free(ctx);
@@ -1002,6 +1007,48 @@ int tbk_sample_tile(tbk_ctx* ctx, const tbk_cov_in* in, int32_t num_samples, tbk
       TBK_HIP(hipStreamSynchronize(ctx->stream));
     }
   }
+  tbk_prof_end_call(ctx);
+  return rc;
+}
+
+int tbk_track_names(tbk_ctx* ctx, uint32_t n_names, const uint64_t* off, const char* bytes) {
+  if (!ctx || !off || (off[n_names] && !bytes)) return TBK_EINVAL;
+  for (uint32_t t = 0; t < n_names; ++t)
+    if (off[t + 1] < off[t]) return TBK_EINVAL;
+  TBK_HIP(hipSetDevice(ctx->device));
+  return tbk_names_upload(ctx, n_names, off, bytes);
+}
+
+int tbk_format_track(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes) {
+  if (!ctx || !rows || !sink || rows->n == UINT32_MAX) return TBK_EINVAL;
+  if (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE) return TBK_EINVAL;
+  const bool cov = rows->kind == TBK_TRACK_COV, junc = rows->kind == TBK_TRACK_JUNC, samp = rows->kind == TBK_TRACK_SAMPLE;
+  if (!cov && !junc && !samp) return TBK_EINVAL;
+  const size_t n = rows->n;
+  if (n && (!rows->tid || !rows->start || !rows->end || ((cov || junc) && !rows->val) || (junc && !rows->strand) ||
+            (samp && (!rows->count || !rows->heat))))
+    return TBK_EINVAL;
+  if (n && !ctx->d_name_off) {
+    ctx->last_error = "tbk_format_track: no reference names (tbk_track_names)";
+    return TBK_EINVAL;
+  }
+  TBK_HIP(hipSetDevice(ctx->device));
+  tbk_prof_begin_call(ctx);
+  // (rows, lengths and offsets, two slices of at most 32 MiB by default)
+  TBK_TRY(ws_begin_call(ctx, n * 64 + ((size_t)80 << 20)));
+  RegGuard reg_guard{ctx};
+  tbk_track_rows d = *rows;
+  if (rows->mem == TBK_MEM_HOST) {
+    d.mem = TBK_MEM_DEVICE;
+    TBK_TRY(h2d(ctx, rows->tid, n, &d.tid));
+    TBK_TRY(h2d(ctx, rows->start, n, &d.start));
+    TBK_TRY(h2d(ctx, rows->end, n, &d.end));
+    if (!samp) TBK_TRY(h2d(ctx, rows->val, n, &d.val));
+    if (junc) TBK_TRY(h2d(ctx, rows->strand, n, &d.strand));
+    if (samp) TBK_TRY(h2d(ctx, rows->count, n, &d.count));
+    if (samp) TBK_TRY(h2d(ctx, rows->heat, n, &d.heat));
+  }
+  const int rc = tbk_format_device(ctx, &d, sink, user, out_bytes);
   tbk_prof_end_call(ctx);
   return rc;
 }

@@ -104,6 +104,7 @@ struct TbkDebug {
   bool no_register = false;   // no_register=1: large host buffers are not page-locked for a call's copies
   bool no_bounce = false;     // no_bounce=1: results of moderate size are copied straight into the caller's (registered) arrays
   bool phases = false;        // phases=1: tbk_collapse_tile prints where its wall time went (copies in, grouping, YD stage, results) to stderr
+  uint64_t fmt_slice = 0;     // fmt_slice=N: bytes of a tbk_format_track slice (0: 32 MiB)
 };
 void tbk_debug_parse(const char* spec, TbkDebug* out);
 
@@ -178,6 +179,12 @@ struct tbk_ctx {
   double* kept_yc = nullptr;
   int64_t* kept_yx = nullptr;
   int32_t* kept_yd = nullptr;
+  // tbk_track_names: the reference names as CSR; tbk_format_track's two pinned slice buffers (fmt_pin_cap bytes each)
+  char* d_names = nullptr;
+  uint64_t* d_name_off = nullptr;
+  uint32_t n_names = 0;
+  void* fmt_pin[2] = {nullptr, nullptr};
+  size_t fmt_pin_cap = 0;
 };
 void tbk_stager_free(tbk_ctx* ctx);
 void tbk_enc_free(tbk_ctx* ctx);
@@ -286,3 +293,6 @@ int tbk_cov_view_build(tbk_ctx* ctx, const int32_t* r_tid, const int32_t* r_pos,
                        const uint32_t* r_cig, const uint32_t* g_rep, const double* g_yc, const int64_t* g_yx, uint32_t ng, tbk_cov_in* view,
                        const uint64_t* g_key = nullptr);
 int tbk_sample_device(tbk_ctx* ctx, const tbk_cov_in* in, int32_t num_samples, tbk_sample_out* out);
+// fmt.hip: tbk_format_track's body (rows in device memory; the arena must be reserved by the caller) and tbk_track_names'
+int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes);
+int tbk_names_upload(tbk_ctx* ctx, uint32_t n_names, const uint64_t* off, const char* bytes);
