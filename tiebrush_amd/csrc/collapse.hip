@@ -534,7 +534,7 @@ __device__ __forceinline__ YsAgg ys_chain_cells(const YsCells& P, uint32_t c, Ys
 }
 __global__ __launch_bounds__(YS_NT) void yd_lcount_k(YsIn S, const uint4* __restrict__ gpk /* YdGroups::pk */, uint32_t ntiles,
                                                      uint32_t* __restrict__ table /* [YS_NL][ntiles] */, uint4* __restrict__ agg /* [YS_NL][ntiles] */,
-                                                     uint64_t* __restrict__ gfiles /* [2 ng]: the files of output group o, its strand code */) {
+                                                     uint64_t* __restrict__ gwb /* [ntiles][YS_NT / 64][YS_NL]: the columns, for yd_lscatter_k */) {
   __shared__ uint64_t wb[YS_NT / 64][YS_NL];
   __shared__ uint32_t g_tid[YS_NT];
   __shared__ int32_t g_e1[YS_NT];
@@ -553,16 +553,21 @@ __global__ __launch_bounds__(YS_NT) void yd_lcount_k(YsIn S, const uint4* __rest
         files = S.gfmask[sg];
       else
         for (uint32_t i = 0; i < n; ++i) files |= 1ull << S.pfile[p0 + i];
-      gfiles[2 * (size_t)o] = files;
-      gfiles[2 * (size_t)o + 1] = c;
       ys_mask_from_files(files, c, &lo, &hi);
       const uint4 g = gpk[o];
       g_tid[threadIdx.x] = g.x;
       g_e1[threadIdx.x] = (int32_t)g.z + 1;
     }
   }
-  wb[threadIdx.x >> 6][lane_id()] = wave_bit_transpose(lo);  // lane c: the groups of this wave in lists c and 64 + c
-  wb[threadIdx.x >> 6][64u + lane_id()] = wave_bit_transpose(hi);
+  {
+    const uint32_t x = threadIdx.x >> 6, l = lane_id();
+    const uint64_t a = wave_bit_transpose(lo), b = wave_bit_transpose(hi);  // lane c: the groups of this wave in lists c and 64 + c
+    wb[x][l] = a;
+    wb[x][64u + l] = b;
+    uint64_t* out = gwb + (size_t)blockIdx.x * (YS_NT / 64) * YS_NL + x * YS_NL;  // (groups past ng: empty rows, zero bits)
+    out[l] = a;
+    out[64u + l] = b;
+  }
   __syncthreads();
   for (uint32_t q = threadIdx.x; q < (YS_NT / 64) * YS_NL; q += YS_NT) {
     const uint32_t x = q / YS_NL, c = q % YS_NL;
@@ -577,8 +582,11 @@ __global__ __launch_bounds__(YS_NT) void yd_lcount_k(YsIn S, const uint4* __rest
   if (threadIdx.x < YS_NL) {
     const uint32_t c = threadIdx.x;
     uint32_t n = 0;
-    for (uint32_t x = 0; x < YS_NT / 64; ++x) n += (uint32_t)__builtin_popcountll(wb[x][c]);
-    const YsAgg A = ys_chain_cells(P, c, YsAgg{0u, 0u, INT32_MIN, 1u});
+    YsAgg A{0u, 0u, INT32_MIN, 1u};
+    for (uint32_t x = 0; x < YS_NT / 64; ++x) {
+      n += (uint32_t)__builtin_popcountll(wb[x][c]);
+      A = ys_combine(A, P.get(x, c));
+    }
     table[(size_t)c * ntiles + blockIdx.x] = n;
     agg[(size_t)c * ntiles + blockIdx.x] = make_uint4(A.first_tid, A.last_tid, (uint32_t)A.mx, A.whole);
   }
@@ -784,125 +792,99 @@ struct YdEmit {
   }
 };
 
-// the second pass: every item dropped at its place in its list (the same record YdEmit leaves behind the radix split).  The items of
-// the tile are walked list by list — thread k takes the k-th, k + 256-th, ... item of that order, finds its list by a bisection in
-// the tile's per-list prefix and its group by selecting the r-th set bit of the list's 256-bit column — so that consecutive
-// threads write consecutive positions of one list.
-__device__ __forceinline__ uint32_t ys_select(uint64_t v, uint32_t r) {  // position of the r-th (0-based) set bit of v
-  // (the half first, then five 32-bit steps of bit-field extract + count: the placement loop is bound by its vector instructions)
-  const uint32_t lo = (uint32_t)v, cl = (uint32_t)__builtin_popcount(lo);
-  const bool up = r >= cl;
-  const uint32_t w = up ? (uint32_t)(v >> 32) : lo;
-  r = up ? r - cl : r;
-  uint32_t pos = 0;
-#pragma unroll
-  for (uint32_t st = 16; st >= 1; st >>= 1) {
-    const uint32_t c = (uint32_t)__builtin_popcount((w >> pos) & ((1u << st) - 1u));
-    const bool go = r >= c;
-    r = go ? r - c : r;
-    pos = go ? pos + st : pos;
-  }
-  return pos + (up ? 32u : 0u);
-}
-__global__ __launch_bounds__(YS_NT) void yd_lscatter_k(YsIn S, uint32_t ntiles, const uint32_t* __restrict__ table, const uint64_t* __restrict__ totals,
-                                                       const uint4* __restrict__ agg, const uint64_t* __restrict__ gfiles, YdGroups Q, YdItems Y,
-                                                       uint32_t* __restrict__ item) {
-  __shared__ uint32_t base[YS_NL];            // first position of this tile's items of list c
-  __shared__ uint32_t pre[YS_NL + 1];         // the tile's items in lists before c
-  __shared__ uint64_t wb[YS_NT / 64][YS_NL];  // column c of wave w's bit matrix
-  __shared__ uint64_t hb[YS_NT / 64][YS_NL];  // ... and which of those items open a chain
-  __shared__ uint32_t ltot[YS_NL];            // items of list c in the whole call
-  __shared__ uint32_t lsum[YS_NL];            // ... and in this tile
-  __shared__ uint4 grec[YS_NT];
-  __shared__ uint32_t gnex[YS_NT];
-  __shared__ uint32_t pa[YS_NT / 64][YS_NL], pb[YS_NT / 64][YS_NL];
-  __shared__ int32_t pm[YS_NT / 64][YS_NL];
-  const YsCells P{pa, pb, pm};
-  const uint32_t t = threadIdx.x, w = t >> 6;
-  if (t < YS_NL) ltot[t] = (uint32_t)totals[t];
+// the second pass: every item dropped at its place in its list (the same record YdEmit leaves behind the radix split, lean form).
+// Consecutive threads must write consecutive positions of one list, but the walk that flags the heads visits a tile's items cell by
+// cell.  So the walk — one per (wave, list) cell, in the cell's order, from the aggregate of the list's items before the cell — drops
+// each item's compact entry (group in the tile, list, head bit) into LDS at its tile-local list-major index, pre[c] + pa[x][c] + k,
+// and a copy-out loop reads the entries in that order (thread i: entry i) and writes the items.  No item is searched for: round 6
+// found every item again by a bisection over the lists, one over the waves and a select of the r-th set bit — 275 wave instructions
+// per 64 items, against three scattered stores per item if the walk wrote the items itself.  A tile holds up to
+// 1024 x 128 items (every group in all 128 lists); the entries of one round fill YS_CAP slots, and a denser tile takes rounds over
+// index ranges, each walk writing only the entries of the current round.
+constexpr uint32_t YS_CAP = 15360;  // staging slots (60 KB: two workgroups per CU): config 3's tiles average 7.3 k items
+constexpr uint32_t YS_NC = (YS_NT / 64) * YS_NL;  // (wave, list) cells of a tile: two per thread
+static_assert(YS_NC == 2 * YS_NT && YS_CAP >= 4 * YS_NC, "the staging array holds the cells' aggregates and counts first");
+__global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t ntiles, const uint32_t* __restrict__ table,
+                                                       const uint64_t* __restrict__ totals, const uint4* __restrict__ agg,
+                                                       const uint64_t* __restrict__ gwb /* yd_lcount_k's columns */, YdGroups Q,
+                                                       YdItems Y, uint32_t* __restrict__ item) {
+  __shared__ uint32_t off[YS_NL];      // first position of this tile's items of list c, less pre[c]
+  __shared__ uint32_t pre[YS_NL + 1];  // the tile's items in lists before c
+  __shared__ uint32_t lsum[YS_NL];     // items of list c in this tile
+  __shared__ uint32_t lbase[YS_NL];    // items of list c in the whole call, then of the lists before c
+  __shared__ uint4 grec[YS_NT];        // (tid + 1, start, end, exon word) of the tile's groups
+  __shared__ uint32_t stage[YS_CAP];   // entries: group | list << 10 | head << 17 — first the cells' aggregates and counts
+  const YsCells P{reinterpret_cast<uint32_t(*)[YS_NL]>(stage), reinterpret_cast<uint32_t(*)[YS_NL]>(stage + YS_NC),
+                  reinterpret_cast<int32_t(*)[YS_NL]>(stage + 2 * YS_NC)};
+  uint32_t(*pa)[YS_NL] = reinterpret_cast<uint32_t(*)[YS_NL]>(stage + 3 * YS_NC);  // the cell's items, then the list's before it
+  const uint32_t t = threadIdx.x, c = t % YS_NL, x0 = t / YS_NL, x1 = x0 + YS_NT / YS_NL;  // this thread's cells: (x0, c), (x1, c)
+  const uint64_t* col = gwb + (size_t)blockIdx.x * YS_NC;
+  const uint64_t m0 = col[t], m1 = col[YS_NT + t];
+  if (t < YS_NL) lbase[t] = (uint32_t)totals[t];
   const uint32_t o = blockIdx.x * YS_NT + t;
-  uint64_t lo = 0, hi = 0;
-  if (o < S.ng) ys_mask_from_files(gfiles[2 * (size_t)o], (uint32_t)gfiles[2 * (size_t)o + 1], &lo, &hi);
-  wb[w][lane_id()] = wave_bit_transpose(lo);
-  wb[w][64u + lane_id()] = wave_bit_transpose(hi);
-  if (o < S.ng) {
-    const uint4 g = Q.pk[o];
-    grec[t] = make_uint4(g.x, g.y, g.z, Q.xoff[o]);
-    gnex[t] = g.w;
-  }
+  if (o < ng) grec[t] = Q.pk[o];
   __syncthreads();
-  for (uint32_t q = t; q < (YS_NT / 64) * YS_NL; q += YS_NT) {  // every cell folds its items
-    const uint32_t x = q / YS_NL, c = q % YS_NL;
+  auto fold = [&](uint64_t m, uint32_t x) {  // the cell's items -> one aggregate
+    pa[x][c] = (uint32_t)__builtin_popcountll(m);
     YsAgg A{0u, 0u, INT32_MIN, 1u};
-    for (uint64_t m = wb[x][c]; m; m &= m - 1) {
+    for (; m; m &= m - 1) {
       const uint4 g = grec[x * 64u + (uint32_t)__builtin_ctzll(m)];
       A = ys_combine(A, YsAgg{g.x, g.x, (int32_t)g.z + 1, 1u});
     }
     P.put(x, c, A);
-  }
+  };
+  fold(m0, x0);
+  fold(m1, x1);
   __syncthreads();
-  if (t < YS_NL) {
-    uint32_t b = 0;  // list base: the totals of the lists before it (128 values: a serial sum per thread is cheap enough)
-    for (uint32_t c = 0; c < t; ++c) b += ltot[c];
-    base[t] = b + table[(size_t)t * ntiles + blockIdx.x];
-    uint32_t n = 0;
-    for (uint32_t x = 0; x < YS_NT / 64; ++x) n += (uint32_t)__builtin_popcountll(wb[x][t]);
-    lsum[t] = n;
-    // every cell of the list learns the aggregate of the list's items before it, those of the tiles before included
+  if (t < YS_NL) {  // every cell of list t learns the aggregate of the list's items before it (the tiles before included) ...
     const uint4 av = agg[(size_t)t * ntiles + blockIdx.x];
     (void)ys_chain_cells(P, t, YsAgg{av.x, av.y, (int32_t)av.z, av.w});
-  }
-  __syncthreads();
-  for (uint32_t q = t; q < (YS_NT / 64) * YS_NL; q += YS_NT) {  // ... and flags its heads
-    const uint32_t x = q / YS_NL, c = q % YS_NL;
-    YsAgg A = P.get(x, c);
-    uint64_t heads = 0;
-    for (uint64_t m = wb[x][c]; m; m &= m - 1) {
-      const uint32_t bit = (uint32_t)__builtin_ctzll(m);
-      const uint4 g = grec[x * 64u + bit];
-      if (A.last_tid == 0u || g.x != A.last_tid || (int32_t)g.y > A.mx) heads |= 1ull << bit;
-      A = ys_combine(A, YsAgg{g.x, g.x, (int32_t)g.z + 1, 1u});
+    uint32_t run = 0;  // ... and how many of them are in the tile
+    for (uint32_t x = 0; x < YS_NT / 64; ++x) {
+      const uint32_t n = pa[x][t];
+      pa[x][t] = run;
+      run += n;
     }
-    hb[x][c] = heads;
+    lsum[t] = run;
   }
   __syncthreads();
-  if (t < 64) {  // exclusive prefix of the 128 per-list counts: one wave, two lists per lane
-    const uint32_t a = lsum[2 * t], b = lsum[2 * t + 1];
-    const uint32_t inc = wave_incl_sum(a + b);
+  if (t < 64) {  // exclusive prefixes over the 128 lists: one wave, two lists per lane
+    const uint32_t a = lsum[2 * t], b = lsum[2 * t + 1], inc = wave_incl_sum(a + b);
+    const uint32_t ta = lbase[2 * t], tb = lbase[2 * t + 1], tinc = wave_incl_sum(ta + tb);
     pre[2 * t] = inc - a - b;
     pre[2 * t + 1] = inc - b;
     if (t == 63) pre[YS_NL] = inc;
-  } else if (t < 64 + YS_NL) {  // ... and of every list's items wave by wave (the cells' aggregates are dead: pa holds it)
-    const uint32_t c = t - 64;
-    uint32_t run = 0;
-    for (uint32_t x = 0; x < YS_NT / 64; ++x) {
-      pa[x][c] = run;
-      run += (uint32_t)__builtin_popcountll(wb[x][c]);
-    }
+    off[2 * t] = tinc - ta - tb + table[(size_t)(2 * t) * ntiles + blockIdx.x] - (inc - a - b);
+    off[2 * t + 1] = tinc - tb + table[(size_t)(2 * t + 1) * ntiles + blockIdx.x] - (inc - b);
   }
   __syncthreads();
-  const uint32_t T = pre[YS_NL];
-  for (uint32_t idx = t; idx < T; idx += YS_NT) {
-    uint32_t c = 0;  // last list with pre[c] <= idx
-#pragma unroll
-    for (uint32_t st = 64; st >= 1; st >>= 1) c = pre[c + st] <= idx ? c + st : c;
-    uint32_t r = idx - pre[c];
-    const uint32_t rank = r;
-    // the wave whose column holds the r-th group: the last one with at most r of the list's items before it (it holds an item:
-    // r < the list's count).  A walk over the columns ran as long as the slowest lane of the wave: sixteen rounds, not eight.
-    uint32_t x = 0;
-#pragma unroll
-    for (uint32_t st = YS_NT / 128; st >= 1; st >>= 1) x = pa[x + st][c] <= r ? x + st : x;
-    r -= pa[x][c];
-    const uint32_t bit = ys_select(wb[x][c], r);
-    const uint32_t g = x * 64u + bit;
-    const uint32_t pos = base[c] + rank;
-    if (Y.se)
-      Y.se[pos] = make_uint2(grec[g].y, grec[g].z);
-    else
-      Y.pk[pos] = grec[g];
-    Y.nex[pos] = gnex[g] | ((uint32_t)((hb[x][c] >> bit) & 1ull) << 31);  // (bit 31: the item opens a chain — read by yd_number)
-    item[pos] = blockIdx.x * YS_NT + g;
+  const YsAgg A0 = P.get(x0, c), A1 = P.get(x1, c);
+  const uint32_t s0 = pre[c] + pa[x0][c], s1 = pre[c] + pa[x1][c], T = pre[YS_NL];
+  for (uint32_t r0 = 0; r0 < T; r0 += YS_CAP) {
+    __syncthreads();  // (the cells' words, then the round before: read)
+    const uint32_t r1 = r0 + YS_CAP;
+    auto walk = [&](uint64_t m, uint32_t x, YsAgg A, uint32_t i) {  // item i of the tile's list-major order: slot i - r0
+      if (i >= r1 || i + (uint32_t)__builtin_popcountll(m) <= r0) return;
+      for (; m && i < r1; m &= m - 1, ++i) {
+        const uint32_t g = x * 64u + (uint32_t)__builtin_ctzll(m);
+        const uint4 v = grec[g];
+        const bool head = A.last_tid == 0u || v.x != A.last_tid || (int32_t)v.y > A.mx;
+        A = ys_combine(A, YsAgg{v.x, v.x, (int32_t)v.z + 1, 1u});
+        if (i >= r0) stage[i - r0] = g | (c << 10) | ((uint32_t)head << 17);
+      }
+    };
+    walk(m0, x0, A0, s0);
+    walk(m1, x1, A1, s1);
+    __syncthreads();
+    const uint32_t n = T - r0 < YS_CAP ? T - r0 : YS_CAP;
+    for (uint32_t i = t; i < n; i += YS_NT) {
+      const uint32_t e = stage[i], g = e & (YS_NT - 1u), l = (e >> 10) & (YS_NL - 1u);
+      const uint4 v = grec[g];
+      const uint32_t pos = off[l] + r0 + i;
+      Y.se[pos] = make_uint2(v.y, v.z);
+      Y.nex[pos] = v.w | ((e >> 17) << 31);  // (bit 31: the item opens a chain — read by yd_number)
+      item[pos] = blockIdx.x * YS_NT + g;
+    }
   }
 }
 
@@ -1952,7 +1934,7 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
     uint32_t* ys_table = nullptr;
     uint4* ys_agg = nullptr;
     uint64_t* ys_totals = nullptr;
-    uint64_t* ys_files = nullptr;
+    uint64_t* ys_wb = nullptr;  // the tiles' bit columns (yd_lcount_k -> yd_lscatter_k)
     uint32_t *yd_d = nullptr, *ys_item = nullptr;
     YdGroups Q{};
     if (by_list) {  // the groups' coordinates first (the first pass folds them); then items and aggregates per (list, tile of groups)
@@ -1962,11 +1944,11 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
       ys_table = ws_alloc<uint32_t>(ctx, (size_t)YS_NL * ys_tiles);
       ys_agg = ws_alloc<uint4>(ctx, (size_t)YS_NL * ys_tiles);
       ys_totals = ws_alloc<uint64_t>(ctx, YS_NL + 1);
-      ys_files = ws_alloc<uint64_t>(ctx, 2 * (size_t)ng);
-      if (!Q.xoff || !ys_table || !ys_agg || !ys_totals || !ys_files) return TBK_ENOMEM;
+      ys_wb = ws_alloc<uint64_t>(ctx, (size_t)ys_tiles * YS_NC);
+      if (!Q.xoff || !ys_table || !ys_agg || !ys_totals || !ys_wb) return TBK_ENOMEM;
       TBK_LAUNCH(ctx, "yd_groups", yd_groups_k, cdiv(ng, B), B, 0, I, ng, J.gperm, J.G, J.shi, J.slo, Q);
       TBK_TRY(tbk_exscan_u32(ctx, Q.nex, Q.xoff, ng, sc + 5));
-      TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k, ys_tiles, YS_NT, 0, S, Q.pk, ys_tiles, ys_table, ys_agg, ys_files);
+      TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k, ys_tiles, YS_NT, 0, S, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
       TBK_LAUNCH(ctx, "yd_lscan", yd_lscan_k, YS_NL, 1024, 0, ys_table, ys_tiles, ys_totals, (unsigned long long*)(sc + 2));
       TBK_LAUNCH(ctx, "yd_lscan", yd_lagg_scan_k, YS_NL, 256, 0, ys_agg, ys_tiles);
     } else if (J.win) {  // items per output group straight from the per-group sample counts
@@ -2029,7 +2011,7 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
         TBK_TRY(tbk_exscan_u32(ctx, Q.nex, Q.xoff, ng, sc + 5));
       }
       if (by_list) {
-        TBK_LAUNCH(ctx, "yd_scatter", yd_lscatter_k, ys_tiles, YS_NT, 0, S, ys_tiles, ys_table, ys_totals, ys_agg, ys_files, Q, Y, io);
+        TBK_LAUNCH(ctx, "yd_scatter", yd_lscatter_k, ys_tiles, YS_NT, 0, ng, ys_tiles, ys_table, ys_totals, ys_agg, ys_wb, Q, Y, io);
       } else {  // stable split by list id (file * 2 + strand list); group order is already in place.  The id range is known:
         uint32_t bits = 1;  // no scan for the varying bits
         while ((1ull << bits) < 2ull * I.k) ++bits;
