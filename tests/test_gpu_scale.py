@@ -1,8 +1,10 @@
 """GPU parity at BASELINE.json sizes.
   * config 2 at full size (2 x 1M reads) and a config-3 shaped tile (64 files, --clip): bit-exact vs the oracle;
-  * a 32 x 1M tile (and, with TBK_FULL_SCALE=1, config 3 at its full 64 x 5M) through size-independent properties:
-    count conservation, output order, rec_group consistency, idempotence of re-collapsing the output, and for
-    tiecov the checksum  sum((end-start)*value) == sum(YC * M bases)."""
+  * a 32 x 1M tile, config 3 at its full 64 x 5M, configs 4 and 5 per rank and as one job through size-independent
+    properties: count conservation, output order, rec_group consistency, idempotence of re-collapsing the output, and
+    for tiecov the checksum  sum((end-start)*value) == sum(YC * M bases);
+  * the same tiles array for array against the oracle (`test_exact_*`, `tests/scale_helpers.py`): the seven group
+    arrays, the nine coverage arrays and the four counters, bit for bit, on the production path."""
 import os
 
 import numpy as np
@@ -234,6 +236,69 @@ def test_properties_config5_1024_files_one_job(ctx):
     assert 0 < g < tile.n_records
     del tile
     torch.cuda.empty_cache()
+
+
+# ---- the same tiles, every output array against the oracle (scale_helpers.exact_at_scale) --------------------------------
+
+# Longest YD chain of the 64 x 5M config-3 tile under --clip, measured with the oracle (scale_helpers.chain_stats): see the
+# docstring of test_exact_config3_full_64x5M.  The tests assert half of it.
+LONGEST_CHAIN_64x5M = 17_971
+# The other tiles: chains of 24 items and more go to yd_wave_k, shorter ones to yd_lane_k — each tile must hold a
+# chain of several times that bound, or the wave kernel's runs and batches are not met at all.
+MIN_CHAIN = 8 * 24
+
+
+def _exact_at_scale(ctx, make, desc, min_chain=MIN_CHAIN, too_large="skip", **kw):
+    import scale_helpers as sh
+    try:
+        host, want, cov, info = sh.exact_at_scale(ctx, make, desc, too_large="raise" if too_large == "skip" else too_large, **kw)
+    except sh.TileTooLarge as e:
+        pytest.skip("%s: the exact comparison needs %d bytes of host memory, %d are available" % (desc, e.need, e.avail))
+    st = sh.content_checks(host, want, min_chain, device="cuda:0")
+    print("exact %s: %d YD items in %d chains, the longest %d; YD max %d" % (desc, st["items"], st["chains"], st["longest"],
+                                                                          int(want["yd"].max())))
+    return info, st
+
+
+def test_exact_32x1M(ctx):
+    from tiebrush_amd import synth
+    _exact_at_scale(ctx, lambda: synth.make_tile(32, 1_000_000, "c3"), 'synth.make_tile(32, 1_000_000, "c3")', strategy="clip")
+
+
+def test_exact_config3_full_64x5M(ctx):
+    """The tile every benchmark line is quoted on (320 M records), array for array.  Its longest YD chain under --clip, by the
+    oracle's result on the CPU: 17,971 items (177,891,981 items in 3,322,613 chains over 25,086,541 groups, YD up to 1359); the test
+    asserts half of that, so that a generator change that flattens the tile fails here instead of emptying the test."""
+    from tiebrush_amd import synth_dev
+    _exact_at_scale(ctx, lambda: synth_dev.make_tile_device(64, 5_000_000, "c3", device="cuda:0"),
+                    'synth_dev.make_tile_device(64, 5_000_000, "c3")', min_chain=LONGEST_CHAIN_64x5M // 2, strategy="clip")
+
+
+@pytest.mark.parametrize("files,reads,profile,kw", [
+    (32, 2_000_000, "c2", {}),
+    (128, 1_000_000, "c5", dict(strategy="exon", max_nh=5, min_qual=1)),
+])
+def test_exact_per_rank_shapes_config4_config5(ctx, files, reads, profile, kw):
+    from tiebrush_amd import synth_dev
+    _exact_at_scale(ctx, lambda: synth_dev.make_tile_device(files, reads, profile, device="cuda:0"),
+                    'synth_dev.make_tile_device(%d, %d, "%s")' % (files, reads, profile), **kw)
+
+
+def test_exact_config4_full_256x2M_one_gpu(ctx):
+    """512 M records, 256 files (incidence lists, radix-split YD items).  A host that cannot hold the comparison compares the
+    largest prefix of the first reference that fits, collapsed on the GPU as a tile of its own (the byte counts are printed)."""
+    from tiebrush_amd import synth_dev
+    info, st = _exact_at_scale(ctx, lambda: synth_dev.make_tile_device(256, 2_000_000, "c2", device="cuda:0"),
+                               'synth_dev.make_tile_device(256, 2_000_000, "c2")', too_large="window")
+    if info["window"] is not None:
+        print("config 4 as one job ran windowed %r: the whole tile needs %d bytes, %d are available"
+              % (info["window"], info["full_need"], info["budget"]))
+
+
+def test_exact_config5_1024_files_one_job(ctx):
+    from tiebrush_amd import synth_dev
+    _exact_at_scale(ctx, lambda: synth_dev.make_tile_device(1024, 250_000, "c5", device="cuda:0"),
+                    'synth_dev.make_tile_device(1024, 250_000, "c5")', strategy="exon", max_nh=5, min_qual=1)
 
 
 def test_device_generator_matches_host_model(ctx):
