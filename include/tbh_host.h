@@ -40,6 +40,13 @@ int tbh_write_bam_parts(const char* out_path, const char* version, int cmd_argc,
  * -1 when the header cannot be read. */
 int tbh_is_tiebrush(const char* path);
 
+/* The BAM index (BAI, SAM specification 5.2) of the coordinate-sorted BAM at bam_path, by the host builder behind `tiebrush --index`
+ * (csrc/host/bai.h; the contract is DESIGN.md 4d), written to bai_path (NULL: bam_path + ".bai").  0 on success, -1 otherwise
+ * (tbh_last_error: a reference longer than 2^29 is named). */
+int tbh_bai_index_file(const char* bam_path, const char* bai_path);
+/* reg2bin of the half-open interval [beg, end) (SAM specification 5.3) */
+uint32_t tbh_bai_reg2bin(int64_t beg, int64_t end);
+
 #ifdef __cplusplus
 }
 #endif

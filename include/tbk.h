@@ -322,6 +322,46 @@ typedef struct tbk_enc_in {
  * *out_bytes set) when out_cap is too small; TBK_EUNSUPPORTED when a record is nearly as long as a member (the caller's host
  * writer takes such an output); TBK_EINVAL for a malformed record. */
 int tbk_bam_encode(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes);
+/* ---- BAM index of an encoded run (appended; no existing struct or entry changes) ------------------------------------------------
+ * What `samtools index` (htslib hts_idx_push / hts_idx_finish, BAI: SAM specification 5.2) makes of a second pass over the file,
+ * built from what the encoder holds anyway: the records' payload offsets, the member cuts and the members' compressed sizes.
+ * Virtual offsets are RELATIVE to the first byte of `out` (coffset 0 at the call's first member): a writer that puts the run at file
+ * offset `base` adds base << 16.  The contract: beg = pos, end = pos + reference length of the CIGAR (M D N = X; pos + 1
+ * when that is 0), bin = reg2bin(beg, end); a record's vbeg = its member's offset << 16 | its offset in the member's payload, its vend
+ * = the next record's vbeg (the last record's: *out_bytes << 16).  The records must come with nondecreasing refID. */
+typedef struct tbk_ix_opts {
+  uint32_t n_ref;           /* references in the output header                                                        */
+  uint32_t reserved;
+  const uint32_t* ref_len;  /* HOST [n_ref]: their lengths (the layout of the linear table)                            */
+  uint64_t* rec_vbeg;       /* optional HOST [n + 1]: every record's vbeg, then the run's end                          */
+} tbk_ix_opts;
+typedef struct tbk_ix_chunk {
+  int32_t tid;
+  uint32_t bin;
+  uint64_t beg, end;        /* virtual offsets                                                                        */
+} tbk_ix_chunk;
+typedef struct tbk_ix_ref {
+  int32_t tid;
+  uint32_t reserved;
+  uint64_t n_records;
+  uint64_t first, last;     /* vbeg of the reference's first record in the run, vend of its last                      */
+} tbk_ix_ref;
+/* The arrays are HOST memory owned by the context, valid until its next tbk_bam_encode / tbk_bam_encode_indexed or tbk_destroy. */
+typedef struct tbk_ix_part {
+  uint32_t n_chunks;           /* runs of consecutive records with equal (tid, bin), one chunk (first vbeg, last vend) each, sorted by
+                                  (tid, bin, beg); neighbours of one bin merged when earlier.end >> 16 >= later.beg >> 16 */
+  uint32_t n_refs;             /* references with records in the run, ascending tid                                   */
+  uint64_t n_lin;
+  uint64_t lin_first;          /* lin[i] belongs to flat window lin_first + i; flat = (sum of ceil(ref_len / 16384) over the references
+                                  before tid) + window: from window 0 of the run's first reference to the last window its last reaches */
+  const tbk_ix_chunk* chunks;
+  const uint64_t* lin;         /* the smallest vbeg among the run's records of that reference with end > window << 14; UINT64_MAX: none */
+  const tbk_ix_ref* refs;
+} tbk_ix_part;
+/* tbk_bam_encode, and the index part of the run it wrote.  TBK_EINVAL (nothing faults) for a refID outside [0, n_ref), a negative pos,
+ * an end beyond 2^29 (BAI cannot address it), or refIDs that decrease. */
+int tbk_bam_encode_indexed(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes,
+                           const tbk_ix_opts* ix, tbk_ix_part* part);
 /* (ABI version 8) Groups [first, first + n) of the results kept by the last tbk_collapse_tile with keep_results, into HOST arrays (any
  * of them may be NULL) — what a caller whose device writer refused a chunk needs for its host writer (flushPData's tag values,
  * tiebrush.cpp:506-525).  TBK_EINVAL when nothing is kept or the range ends behind the kept groups. */

@@ -27,7 +27,7 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_collapse_opts_default", "tbk_collapse_tile", "tbk_collapse_finish_yd", "tbk_coverage_tile", "tbk_sample_tile",
            "tbk_groups_to_cov_in", "tbk_bgzf_inflate", "tbk_bam_decode", "tbk_bam_records", "tbk_bam_release", "tbk_shard_prepare", "tbk_shard_probe_max", "tbk_shard_probe_next",
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
-           "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track"]
+           "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed"]
 
 
 class CollapseOpts(C.Structure):
@@ -76,6 +76,22 @@ class SampleOut(C.Structure):
 class EncIn(C.Structure):
     _fields_ = [("mem", C.c_int32), ("n", C.c_uint32), ("rep", _P), ("yc", _P), ("yx", _P), ("yd", _P), ("n_dev", C.c_uint32), ("n_host", C.c_uint32),
                 ("host_blob", _P), ("host_off", _P), ("host_slot", _P), ("first", C.c_uint32), ("from_ctx", _P)]
+
+
+class IxOpts(C.Structure):
+    _fields_ = [("n_ref", C.c_uint32), ("reserved", C.c_uint32), ("ref_len", _P), ("rec_vbeg", _P)]
+
+
+class IxChunk(C.Structure):
+    _fields_ = [("tid", C.c_int32), ("bin", C.c_uint32), ("beg", C.c_uint64), ("end", C.c_uint64)]
+
+
+class IxRef(C.Structure):
+    _fields_ = [("tid", C.c_int32), ("reserved", C.c_uint32), ("n_records", C.c_uint64), ("first", C.c_uint64), ("last", C.c_uint64)]
+
+
+class IxPart(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint32), ("n_refs", C.c_uint32), ("n_lin", C.c_uint64), ("lin_first", C.c_uint64), ("chunks", _P), ("lin", _P), ("refs", _P)]
 
 
 TRACK = {"cov": 0, "junc": 1, "sample": 2}
@@ -166,6 +182,8 @@ def load():
     L.tbk_bgzf_deflate.restype = C.c_int
     L.tbk_bam_encode.argtypes = [_P, C.POINTER(EncIn), _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.tbk_bam_encode.restype = C.c_int
+    L.tbk_bam_encode_indexed.argtypes = [_P, C.POINTER(EncIn), _P, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(IxOpts), C.POINTER(IxPart)]
+    L.tbk_bam_encode_indexed.restype = C.c_int
     L.tbk_kept_results.argtypes = [_P, C.c_uint32, C.c_uint32, _P, _P, _P, _P]
     L.tbk_kept_results.restype = C.c_int
     L.tbk_warmup.argtypes = [_P]
@@ -180,7 +198,7 @@ def load():
 
 # (TBK_HOST_LIB: the sanitizer builds of tools/san_check.sh)
 HOST_LIB_PATH = os.environ.get("TBK_HOST_LIB") or os.path.join(_HERE, "_build", "libtbh.so")
-HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush"]   # include/tbh_host.h
+HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin"]   # include/tbh_host.h
 _host = None
 
 
@@ -201,6 +219,10 @@ def load_host():
     H.tbh_write_bam_parts.restype = C.c_int
     H.tbh_is_tiebrush.argtypes = [C.c_char_p]
     H.tbh_is_tiebrush.restype = C.c_int
+    H.tbh_bai_index_file.argtypes = [C.c_char_p, C.c_char_p]
+    H.tbh_bai_index_file.restype = C.c_int
+    H.tbh_bai_reg2bin.argtypes = [C.c_int64, C.c_int64]
+    H.tbh_bai_reg2bin.restype = C.c_uint32
     _host = H
     return H
 

@@ -377,6 +377,15 @@ class Context:
         bam_decode left on this context; the others come from host_records = {group index: raw record bytes WITHOUT block_size}.
         kept_first: the len(rep) groups from that index on of the results the context kept (keep_results): rep / yc / yx / yd are not handed over;
         from_ctx: the Context that holds them (and the decoded tile), when it is not this one"""
+        return self._bam_encode(rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, None)
+
+    def bam_encode_indexed(self, rep, yc, yx, yd, ref_len, n_dev=0, host_records=None, kept_first=None, from_ctx=None):
+        """tbk_bam_encode_indexed: bam_encode's (run, payload bytes) and the run's index part (BAI) as a dict of numpy arrays:
+        chunks (structured: tid, bin, beg, end), lin (uint64, UINT64_MAX = no record) with lin_first, refs (structured: tid, n_records, first,
+        last), rec_vbeg (uint64 [n + 1]).  Virtual offsets are relative to the run's first byte.  ref_len: the header's reference lengths"""
+        return self._bam_encode(rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, np.ascontiguousarray(ref_len, dtype=np.uint32))
+
+    def _bam_encode(self, rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, ref_len):
         rep = np.ascontiguousarray(rep, dtype=np.uint32)
         n = len(rep)
         e = _lib.EncIn()
@@ -404,13 +413,31 @@ class Context:
             e.n_host, e.host_blob, e.host_off, e.host_slot = len(blobs), blob.ctypes.data, offa.ctypes.data, slot.ctypes.data
         need, pay = C.c_uint64(0), C.c_uint64(0)
         out = np.empty(max(1 << 16, 64 * n), dtype=np.uint8)
-        rc = self.L.tbk_bam_encode(self.h, C.byref(e), out.ctypes.data, out.size, C.byref(need), C.byref(pay))
+        if ref_len is None:
+            call = lambda: self.L.tbk_bam_encode(self.h, C.byref(e), out.ctypes.data, out.size, C.byref(need), C.byref(pay))
+        else:
+            vb = np.zeros(n + 1, dtype=np.uint64)
+            io, part = _lib.IxOpts(), _lib.IxPart()
+            io.n_ref, io.ref_len, io.rec_vbeg = len(ref_len), ref_len.ctypes.data, vb.ctypes.data
+            call = lambda: self.L.tbk_bam_encode_indexed(self.h, C.byref(e), out.ctypes.data, out.size, C.byref(need), C.byref(pay), C.byref(io), C.byref(part))
+        rc = call()
         if rc == -4:
             out = np.empty(int(need.value), dtype=np.uint8)
-            rc = self.L.tbk_bam_encode(self.h, C.byref(e), out.ctypes.data, out.size, C.byref(need), C.byref(pay))
-        self._check(rc, "tbk_bam_encode")
+            rc = call()
+        self._check(rc, "tbk_bam_encode" if ref_len is None else "tbk_bam_encode_indexed")
         del keep
-        return out[:int(need.value)].tobytes(), int(pay.value)
+        run = out[:int(need.value)].tobytes()
+        if ref_len is None:
+            return run, int(pay.value)
+
+        def arr(ptr, count, dt):  # (the part's arrays are the context's: copied out before its next call)
+            if not count:
+                return np.zeros(0, dtype=dt)
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dt).itemsize), dtype=dt).copy()
+        chunk_dt = np.dtype([("tid", "<i4"), ("bin", "<u4"), ("beg", "<u8"), ("end", "<u8")])
+        ref_dt = np.dtype([("tid", "<i4"), ("reserved", "<u4"), ("n_records", "<u8"), ("first", "<u8"), ("last", "<u8")])
+        return run, int(pay.value), {"chunks": arr(part.chunks, part.n_chunks, chunk_dt), "lin": arr(part.lin, part.n_lin, np.dtype("<u8")),
+                                     "lin_first": int(part.lin_first), "refs": arr(part.refs, part.n_refs, ref_dt), "rec_vbeg": vb}
 
     def bam_decode(self, files, tbmerged=None, want_md=False, want_names=False):
         """tbk_bam_decode: list of whole BAM files (bytes) -> (SoaIn struct describing the device-resident tile, file_off).

@@ -969,7 +969,8 @@ int deflate_grid(tbk_ctx* ctx) {
 }
 
 // payload run (device) + member table (device) -> packed members in *d_out (device, EB_PACKED) and their total size
-int deflate_members(tbk_ctx* ctx, const uint8_t* d_src, const DfMember* d_mem, uint32_t nmem, uint8_t** d_out, uint64_t* total) {
+int deflate_members(tbk_ctx* ctx, const uint8_t* d_src, const DfMember* d_mem, uint32_t nmem, uint8_t** d_out, uint64_t* total,
+                    const uint64_t** d_moff = nullptr) {
   *total = 0;
   *d_out = nullptr;
   if (nmem == 0) return 0;
@@ -998,6 +999,7 @@ int deflate_members(tbk_ctx* ctx, const uint8_t* d_src, const DfMember* d_mem, u
   TBK_TRY(enc_buf(ctx, EB_PACKED, (size_t)*total + 16, (void**)&packed));
   TBK_LAUNCH(ctx, "bgz_gather", bgz_gather_k, nmem, 256, 0, nmem, slots, msize, moff, packed);
   *d_out = packed;
+  if (d_moff) *d_moff = moff;
   return 0;
 }
 
@@ -1069,11 +1071,18 @@ extern "C" int tbk_bgzf_deflate(tbk_ctx* ctx, const uint8_t* src, uint64_t n, in
   return tbk_check_launch(ctx, "bgzf_deflate");
 }
 
-extern "C" int tbk_bam_encode(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes) {
+namespace {
+// tbk_bam_encode; with `ix`, the run's index part too (tbk_bam_encode_indexed: baix.hip) — nothing else differs
+int bam_encode_run(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes, const tbk_ix_opts* ix,
+                   tbk_ix_part* part) {
   if (!ctx || !in || !out_bytes) return TBK_EINVAL;
   *out_bytes = 0;
   if (payload_bytes) *payload_bytes = 0;
   const uint32_t n = in->n;
+  if (ix) {
+    memset(part, 0, sizeof(*part));
+    TBK_TRY(tbk_ix_check_opts(ctx, ix));
+  }
   if (n == 0) return 0;
   const bool kept = in->mem == TBK_MEM_KEPT;  // the columns of a context's last collapse (tbk_collapse_opts.keep_results), read where they lie
   tbk_ctx* const src = in->from ? in->from : ctx;  // whose kept results / decoded tile (read only; the same device)
@@ -1170,10 +1179,25 @@ extern "C" int tbk_bam_encode(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, 
   TBK_LAUNCH(ctx, "enc_members", enc_members_k, cdiv(nmem, 256), 256, 0, nmem, d_cut, d_mem);
   uint8_t* packed;
   uint64_t ztotal;
-  TBK_TRY(deflate_members(ctx, pay, d_mem, nmem, &packed, &ztotal));
+  const uint64_t* d_moff = nullptr;
+  TBK_TRY(deflate_members(ctx, pay, d_mem, nmem, &packed, &ztotal, &d_moff));
   *out_bytes = ztotal;
   if (ztotal > out_cap || (ztotal && !out)) return TBK_E2BIG;
   TBK_HIP(hipMemcpyAsync(out, packed, ztotal, hipMemcpyDeviceToHost, st));
+  if (ix) {  // the index kernels run under the members' download; their own (small) download follows it on the stream
+    TbkIxIn I{n, pay, d_ooff, nmem, d_cut, d_moff, ztotal};
+    return tbk_ix_build(ctx, I, ix, part);
+  }
   TBK_HIP(hipStreamSynchronize(st));
   return tbk_check_launch(ctx, "bam_encode");
+}
+}  // namespace
+
+extern "C" int tbk_bam_encode(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes) {
+  return bam_encode_run(ctx, in, out, out_cap, out_bytes, payload_bytes, nullptr, nullptr);
+}
+extern "C" int tbk_bam_encode_indexed(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes,
+                                      const tbk_ix_opts* ix, tbk_ix_part* part) {
+  if (!ix || !part) return TBK_EINVAL;
+  return bam_encode_run(ctx, in, out, out_cap, out_bytes, payload_bytes, ix, part);
 }

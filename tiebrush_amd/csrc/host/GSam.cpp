@@ -171,6 +171,12 @@ void GSamWriter::write_members(const uint8_t* z, size_t n) {
   if (!w_.write_members(z, n)) GError("Error: failed to write alignment records\n");
 }
 
+uint64_t GSamWriter::tell() {
+  const long long t = w_.tell();
+  if (t < 0) GError("Error: failed to write alignment records\n");
+  return (uint64_t)t;
+}
+
 void GSamWriter::write(GSamRecord* brec) {
   if (brec) write_raw(*brec->get_b());
 }

@@ -164,4 +164,6 @@ class GSamWriter {
   // the same run already deflated into BGZF members by the caller's worker threads (tbh::bgzf_deflate_members)
   void write_members(const uint8_t* z, size_t n);
   int level() const { return w_.level(); }
+  // the file offset of the next write_members (the output's index: bai.h)
+  uint64_t tell();
 };

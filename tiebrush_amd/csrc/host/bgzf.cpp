@@ -310,6 +310,11 @@ bool BgzfWriter::write_members(const uint8_t* z, size_t n) {
   return true;
 }
 
+long long BgzfWriter::tell() {
+  if (!f_ || !flush_chunk() || !wait_bg()) return -1;
+  return (long long)ftello(f_);
+}
+
 bool BgzfWriter::wait_bg() {
   if (bg_) {
     bg_->join();

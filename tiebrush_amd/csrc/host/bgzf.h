@@ -45,6 +45,9 @@ class BgzfWriter {
   // already deflated members (bgzf_deflate_members), e.g. produced by worker threads: written as they are, in call order
   bool write_members(const uint8_t* z, size_t n);
   int level() const { return level_; }
+  // the file offset the next write_members lands at: what was written uncompressed so far goes out first, as write_members itself
+  // would send it (the member sequence does not change); -1 on failure
+  long long tell();
   bool close();  // flushes and appends the 28-byte EOF block
   const std::string& error() const { return err_; }
 

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "GSam.h"
+#include "bai.h"
 #include "bam.h"
 #include "tbk_dl.h"
 
@@ -65,10 +66,11 @@ class DeviceWriter {
   // output — TBK_EUNSUPPORTED (a record too long for a BGZF member of its own: bgzdef.hip) or TBK_ENOMEM / no pinned memory, on ANY
   // chunk: the chunks before the refused one are written in full and *groups_done says how many groups that was, so the caller's host
   // writer takes the groups from there on (a long read far into the output does not cost the run).  Any other failure is fatal
-  // (GError).  *payload / *zbytes: bytes of tagged records / of BGZF members written.
+  // (GError).  *payload / *zbytes: bytes of tagged records / of BGZF members written.  With `bai` (tiebrush --index) every chunk goes
+  // through tbk_bam_encode_indexed and the write stage, which knows where the chunk's members land in the file, hands its index part on.
   bool write(tbk_ctx* ctx, GSamWriter& out, uint32_t ng, const uint32_t* rep, const double* yc, const int64_t* yx, const int32_t* yd, uint32_t n_dev,
              const std::function<tbh::RecView(uint32_t)>& host_record, uint64_t* payload, uint64_t* zbytes, std::string& why, uint32_t* groups_done,
-             const std::function<void(uint32_t, int)>& host_prefetch = nullptr) {
+             const std::function<void(uint32_t, int)>& host_prefetch = nullptr, tbh::BaiIndex* bai = nullptr) {
     *payload = *zbytes = 0;
     *groups_done = 0;
     if (ng == 0) return true;
@@ -147,6 +149,11 @@ class DeviceWriter {
     const char* force_refuse = getenv("TBK_TEST_DW_REFUSE_CHUNK");  // test hook: chunk k answers TBK_EUNSUPPORTED
     std::vector<uint64_t> zsz(nchunk, 0), psz(nchunk, 0);
     std::vector<uint32_t> nhost(nchunk, 0);
+    std::vector<tbh::BaiPart> ixpart(bai ? nchunk : 0);  // (a chunk's part: copied out of its context before that encodes again)
+    tbk_ix_opts ixo;
+    memset(&ixo, 0, sizeof(ixo));
+    if (bai) ixo.n_ref = (uint32_t)bai->ref_len().size(), ixo.ref_len = bai->ref_len().data();
+    tbk_ix_part ixp[2];
     auto tnow = [] { return std::chrono::steady_clock::now(); };
     auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     double busy_gather = 0, busy_encode = 0, busy_write = 0, busy_pass1 = 0;  // what each stage spent working (TBK_TIMING: which one paces the pipeline)
@@ -174,10 +181,22 @@ class DeviceWriter {
         in.host_blob = s.blob, in.host_off = s.off.data(), in.host_slot = s.slot.data();
         uint64_t zb = 0, pb = 0;
         const auto e0 = tnow();
-        int rc = (force_refuse && (uint32_t)atol(force_refuse) == k) ? TBK_EUNSUPPORTED : api_.bam_encode(ectx, &in, s.z, s.z_cap, &zb, &pb);
+        auto encode = [&]() {
+          return bai ? api_.bam_encode_indexed(ectx, &in, s.z, s.z_cap, &zb, &pb, &ixo, &ixp[e]) : api_.bam_encode(ectx, &in, s.z, s.z_cap, &zb, &pb);
+        };
+        int rc = (force_refuse && (uint32_t)atol(force_refuse) == k) ? TBK_EUNSUPPORTED : encode();
         if (rc == TBK_E2BIG && zb > s.z_cap) {  // (the members of this chunk need a larger buffer: the call said how large)
           if (!grow(s.z, s.z_cap, zb + zb / 8)) rc = TBK_ENOMEM;
-          else rc = api_.bam_encode(ectx, &in, s.z, s.z_cap, &zb, &pb);
+          else rc = encode();
+        }
+        if (rc == 0 && bai) {
+          tbh::BaiPart& P = ixpart[k];
+          const tbk_ix_part& q = ixp[e];
+          static_assert(sizeof(tbh::BaiChunk) == sizeof(tbk_ix_chunk) && sizeof(tbh::BaiRef) == sizeof(tbk_ix_ref), "bai.h mirrors tbk.h");
+          P.chunks.assign((const tbh::BaiChunk*)q.chunks, (const tbh::BaiChunk*)q.chunks + q.n_chunks);
+          P.lin.assign(q.lin, q.lin + q.n_lin);
+          P.lin_first = q.lin_first;
+          P.refs.assign((const tbh::BaiRef*)q.refs, (const tbh::BaiRef*)q.refs + q.n_refs);
         }
         if (rc != 0) {
           set_fail(k, (rc == TBK_EUNSUPPORTED || rc == TBK_ENOMEM) ? 1 : 2, std::string(api_.strerror_(rc)) + " (" + api_.last_error(ectx) + ")");
@@ -199,6 +218,10 @@ class DeviceWriter {
         if (!wait_state(k, 2)) return;
         Slot& s = slot_[k % (uint32_t)nslots_];
         const auto w0 = tnow();
+        if (bai) {
+          bai->add(out.tell(), ixpart[k]);
+          ixpart[k] = tbh::BaiPart();
+        }
         out.write_members(s.z, (size_t)zsz[k]);
         busy_write += tms(w0, tnow());
         set_state(k, 3);

@@ -9,6 +9,7 @@
 
 #include "../../../include/tbh_host.h"
 #include "GSam.h"
+#include "bai.h"
 #include "bgzf.h"
 #include "tagwrite.h"
 #include "tmerge.h"
@@ -97,5 +98,13 @@ int tbh_is_tiebrush(const char* path) {
   }
   return bf.hdr.is_tiebrush() ? 1 : 0;
 }
+
+int tbh_bai_index_file(const char* bam_path, const char* bai_path) {
+  if (!bam_path) return fail("tbh_bai_index_file: null argument");
+  std::string err;
+  if (!tbh::bai_index_file(bam_path, bai_path ? std::string(bai_path) : std::string(bam_path) + ".bai", err)) return fail("tbh_bai_index_file: " + err);
+  return 0;
+}
+uint32_t tbh_bai_reg2bin(int64_t beg, int64_t end) { return tbh::bai_reg2bin(beg, end); }
 
 }  // extern "C"

@@ -37,6 +37,7 @@
 #include "devwriter.h"
 #include "fastload.h"
 #include "tagwrite.h"
+#include "bai.h"
 #include "tbk_dl.h"
 #include "tmerge.h"
 #include "tracks.h"
@@ -75,7 +76,9 @@ static const char* USAGE =
     "  --junc PREFIX        also write tiecov's junction track of the output (as tiecov -j)\n"
     "  --samp PREFIX        also write tiecov's sample-count track of the output (as tiecov -s; needs @CO SAMPLE: header lines)\n"
     "  --bigwig             write the coverage track as PREFIX.bigwig (as tiecov -W; needs --cov)\n"
-    "                       (the tracks are what tiecov writes when it reads OUT.bam; not with --ranks)\n";
+    "                       (the tracks are what tiecov writes when it reads OUT.bam; not with --ranks)\n"
+    "  --index              also write the output's BAM index OUT.bam.bai (what samtools index makes of OUT.bam; not with --ranks,\n"
+    "                       not when the output goes to standard output)\n";
 
 // a buffer that is allocated, not initialised (untouched pages cost nothing), on huge pages when it is large, and not freed at
 // the end: these buffers live as long as the process, which ends with _exit — returning gigabytes page by page first only
@@ -492,10 +495,17 @@ class Output {
   double ms_dev_write = 0;              // the device writer's time, its bytes of tagged records and of BGZF members
   uint64_t dev_payload = 0, dev_z = 0;
 
-  Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env, TrackRecs* tracks)
-      : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env), tracks_(tracks) {}
-  // (the end of the file: the EOF member)
-  void close() { file_.reset(); }
+  Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env, TrackRecs* tracks, tbh::BaiIndex* bai = nullptr)
+      : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env), tracks_(tracks), bai_(bai), bai_path_(std::string(fname) + ".bai") {}
+  // (the end of the file: the EOF member; the index goes out once that is on disk)
+  void close() {
+    file_.reset();
+    if (!bai_) return;
+    auto a = tnow();
+    std::string err;
+    if (!bai_->write(bai_path_, err)) GError("Error: writing the index failed: %s\n", err.c_str());
+    if (env_.timing) fprintf(stderr, "index: %s written in %.1f ms\n", bai_path_.c_str(), tms(a, tnow()));
+  }
   // whether the whole-input routes leave the tags' values on the device for the device writer (tbk_collapse_opts.keep_results)
   bool keep_results() const { return dev_.dw && file_->level() != 0 && !env_.no_keep_results; }
 
@@ -513,7 +523,7 @@ class Output {
       auto a = tnow();
       uint64_t pb = 0, zb = 0;
       std::string why;
-      const bool ok = dev_.dw->write(c, *file_, ng, rp, ycp, yxp, ydp, n_dev, rec, &pb, &zb, why, &done, prefetch);
+      const bool ok = dev_.dw->write(c, *file_, ng, rp, ycp, yxp, ydp, n_dev, rec, &pb, &zb, why, &done, prefetch, bai_);
       ms_dev_write += tms(a, tnow()), dev_payload += pb, dev_z += zb;
       groups += ok ? ng : done;
       if (ok) {
@@ -532,8 +542,21 @@ class Output {
     }
     // flushPData's tagging on every core (tagwrite.h); one slice when a single thread writes
     auto from_done = [&](uint32_t g) { return rec(done + g); };
-    auto emit = [&](const uint8_t* z, size_t n) { return file_->write_members(z, n), true; };
-    if (!tbh::tag_deflate_ordered(ng - done, from_done, ycp + done, yxp + done, ydp + done, file_->level(), env_.threads, emit, env_.threads > 1 ? 16384 : 0))
+    // (--index: a slice's records come with its members; the slice's index part is the host builder's, bai.h)
+    std::vector<std::vector<tbh::BaiRec>> slice_recs;
+    size_t slice = 0;
+    auto emit = [&](const uint8_t* z, size_t n) {
+      if (bai_) {
+        const std::vector<tbh::BaiRec>& sr = slice_recs[slice++];
+        tbh::BaiPart part;
+        std::string err;
+        if (!tbh::bai_build_part(sr.data(), sr.size(), (uint64_t)n << 16, bai_->ref_len(), part, err)) GError("Error: indexing the output failed: %s\n", err.c_str());
+        bai_->add(file_->tell(), part);
+      }
+      return file_->write_members(z, n), true;
+    };
+    if (!tbh::tag_deflate_ordered(ng - done, from_done, ycp + done, yxp + done, ydp + done, file_->level(), env_.threads, emit, env_.threads > 1 ? 16384 : 0,
+                                  bai_ ? &slice_recs : nullptr))
       GError("Error: deflate failed\n");
     groups += ng - done;
     return add_tracks(c, ng, ycp, yxp, ydp, kept && done > 0, rec);
@@ -551,6 +574,8 @@ class Output {
   Device& dev_;
   const Env& env_;
   TrackRecs* tracks_;
+  tbh::BaiIndex* bai_;  // --index: the parts of everything that goes into the file, in file order
+  std::string bai_path_;
 
   // fetch: the values of groups [0, ng) are on the device only (keep_results)
   bool add_tracks(tbk_ctx* c, uint32_t ng, const double* ycp, const int64_t* yxp, const int32_t* ydp, bool fetch, const RecFn& rec) {
@@ -1208,17 +1233,19 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
   }
 }
 
-// the track options with --ranks: refused before the launcher starts (the multi-rank tracks are not built)
+// the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
-  bool ranks = false, tracks = false;
+  bool ranks = false, tracks = false, index = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
+    index = index || strcmp(argv[i], "--index") == 0;
     for (const char* o : {"--cov", "--junc", "--samp", "--bigwig"}) {
       const size_t k = strlen(o);
       tracks = tracks || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
     }
   }
   if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
+  if (ranks && index) GError("Error: --index is not available with --ranks (index the output afterwards)\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -1227,7 +1254,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;SMLPEDVho:N:Q:F:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;SMLPEDVho:N:Q:F:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1287,6 +1314,9 @@ int main(int argc, char* argv[]) {
                     samp_prefix = args.getOpt("samp") ? args.getOpt("samp") : "";
   const bool bigwig = args.getOpt("bigwig") != nullptr;
   if (bigwig && cov_prefix.empty()) GError("Error: --bigwig needs --cov\n");
+  const bool want_index = args.getOpt("index") != nullptr;
+  if (want_index && strcmp(outfname, "-") == 0)
+    GError("Error: --index needs an output file (-o FILE): an index addresses file offsets, standard output has none\n");
   const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty();
   while (const char* ifn = args.nextNonOpt()) inRecords.addFile(tbh_realpath(ifn).c_str());
 
@@ -1307,7 +1337,14 @@ int main(int argc, char* argv[]) {
     tfiles.open(cov_prefix, junc_prefix, samp_prefix, bigwig, h->target_name, h->target_len);
     trecs.reset(new TrackRecs());
   }
-  Output out(outfname, inRecords.header(), dev, env, trecs.get());
+  // the index: a reference a BAI cannot address is refused before the output is created; an older index of the same name goes now
+  tbh::BaiIndex bai;
+  if (want_index) {
+    std::string err;
+    if (!bai.init(inRecords.header()->target_name, inRecords.header()->target_len, err)) GError("Error: --index: %s\n", err.c_str());
+    (void)unlink((std::string(outfname) + ".bai").c_str());
+  }
+  Output out(outfname, inRecords.header(), dev, env, trecs.get(), want_index ? &bai : nullptr);
   const Inputs inp(inRecords);
   const Routes can = eligible_routes(env, opt, inp);
   Route r = Route::fall_through;

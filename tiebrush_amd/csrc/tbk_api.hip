@@ -618,6 +618,7 @@ void tbk_destroy(tbk_ctx* ctx) {
     if (p) (void)hipHostFree(p);
   if (ctx->bounce) (void)hipHostFree(ctx->bounce);
   tbk_enc_free(ctx);
+  tbk_ix_free(ctx);
   tbk_stager_free(ctx);
   if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
   if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);

@@ -169,6 +169,7 @@ struct tbk_ctx {
   std::vector<uint8_t> unpack_tbm;
   void* bam_dev = nullptr;       // device-decoded BAM input (bamdev.hip): inflated streams + record index + the SoA tile's arrays
   void* enc = nullptr;           // the encoder's device buffers (bgzdef.hip)
+  void* ix = nullptr;            // the pinned host arrays of the last tbk_bam_encode_indexed's index part (baix.hip)
   void* stager = nullptr;        // pinned ring + upload stream of the staged host -> device copies (bamdev.hip)
   char* bounce = nullptr;        // a few megabytes of page-locked memory: results of moderate size come back through it (tbk_api.hip: d2h)
   // the last collapse's results, kept for the output side (tbk_collapse_opts.keep_results): one allocation, four columns of kept_n groups
@@ -188,6 +189,19 @@ struct tbk_ctx {
 };
 void tbk_stager_free(tbk_ctx* ctx);
 void tbk_enc_free(tbk_ctx* ctx);
+void tbk_ix_free(tbk_ctx* ctx);
+// baix.hip: the index part of a run the encoder has just packed.  All pointers are device memory of the encoder, alive until its next call.
+struct TbkIxIn {
+  uint32_t n;             // records
+  const uint8_t* pay;     // the payload stream: the tagged records back to back, block_size first
+  const uint64_t* ooff;   // [n + 1] their offsets in it
+  uint32_t nmem;          // members
+  const uint64_t* cut;    // [nmem + 1] the members' first payload bytes
+  const uint64_t* moff;   // [nmem + 1] the members' offsets in the packed run
+  uint64_t ztotal;        // bytes of the packed run
+};
+int tbk_ix_check_opts(tbk_ctx* ctx, const tbk_ix_opts* ix);  // TBK_EINVAL for a reference a BAI cannot address
+int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& in, const tbk_ix_opts* ix, tbk_ix_part* part);
 // the tile tbk_bam_decode left on the context: inflated streams, record offsets, record count (false: there is none)
 bool tbk_bam_dev_records(tbk_ctx* ctx, const uint8_t** inf, const uint64_t** rec, uint32_t* n);
 

@@ -3,7 +3,7 @@
 # this image, gcc's sanitizers are).  Builds tiebrush_amd/_build_san_* and oracle/_build_san_* and runs, under each build:
 #   - the CPU tests that drive the host codec, the formats, the oracle and the files -> files tool (pytest, the libraries through ctypes:
 #     the sanitizer runtime is preloaded into python),
-#   - tbh_tool round trips on the reference's fixtures (cat / soa / fastsoa / mergeorder / mkbam with worker threads).
+#   - tbh_tool round trips on the reference's fixtures (cat / bai / soa / fastsoa / mergeorder / mkbam with worker threads).
 # usage: bash tools/san_check.sh [address,undefined|thread ...]   (default: both);  the summary goes to stdout, details to /tmp/tbk_san/
 set -u
 cd "$(dirname "$0")/.."
@@ -20,12 +20,12 @@ for SAN in $MODES; do
   export ASAN_OPTIONS=detect_leaks=0:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1
   export TSAN_OPTIONS="halt_on_error=0 exitcode=66 report_signal_unsafe=0"
   # -- the CPU tests on the sanitized libraries and tools
-  TESTS="tests/test_host_codec.py tests/test_host_formats.py tests/test_oracle_golden.py tests/test_cpu_e2e_tool.py tests/test_metamorphic_cpu.py"
+  TESTS="tests/test_host_codec.py tests/test_host_formats.py tests/test_oracle_golden.py tests/test_cpu_e2e_tool.py tests/test_metamorphic_cpu.py tests/test_bai_host.py"
   if [ "$SAN" = thread ]; then
     # (ThreadSanitizer's runtime preloaded into an uninstrumented python deadlocks at start-up: under it the tests drive the sanitized
     # TOOLS — tbh_tool, tb_cpu_e2e: the threaded loader, the inflate / deflate pools, the writer — and load the plain libraries)
     TBK_TEST_TBH_TOOL=$HB/tbh_tool TBK_TEST_CPU_E2E=$OB/tb_cpu_e2e \
-      python -m pytest tests/test_host_codec.py tests/test_host_formats.py tests/test_cpu_e2e_tool.py -x -q -p no:cacheprovider > $LOG/pytest_$tag.log 2>&1
+      python -m pytest tests/test_host_codec.py tests/test_host_formats.py tests/test_cpu_e2e_tool.py tests/test_bai_host.py -x -q -p no:cacheprovider > $LOG/pytest_$tag.log 2>&1
   else
     LD_PRELOAD="$RT" TBK_HOST_LIB=$HB/libtbh.so TB_ORACLE_BUILD_DIR=$OB TBK_TEST_TBH_TOOL=$HB/tbh_tool TBK_TEST_CPU_E2E=$OB/tb_cpu_e2e \
       python -m pytest $TESTS -x -q -p no:cacheprovider > $LOG/pytest_$tag.log 2>&1
@@ -38,6 +38,7 @@ for SAN in $MODES; do
   G=tests/golden
   ( set -e
     $HB/tbh_tool cat $G/t1/t1.bam $W/t1.bam
+    $HB/tbh_tool bai $W/t1.bam
     $HB/tbh_tool mergeorder $G/t2/t2s0.bam $G/t2/t2s1.bam $G/t2/t2s2.bam > $W/order.txt
     $HB/tbh_tool soa $W/soa $G/t2/t2s*.bam
     $HB/tbh_tool fastsoa $W/fsoa $G/t2/t2s*.bam
