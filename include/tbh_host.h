@@ -47,6 +47,15 @@ int tbh_bai_index_file(const char* bam_path, const char* bai_path);
 /* reg2bin of the half-open interval [beg, end) (SAM specification 5.3) */
 uint32_t tbh_bai_reg2bin(int64_t beg, int64_t end);
 
+/* The same as a CSI index (CSIv1, min_shift 14), which addresses references beyond 2^29: the builder behind `tiebrush --csi`, written
+ * BGZF-compressed to csi_path (NULL: bam_path + ".csi").  0 on success, -1 otherwise. */
+int tbh_csi_index_file(const char* bam_path, const char* csi_path);
+/* the depth such an index takes for a longest reference of max_len: the smallest d with max_len + 256 <= 2^(14 + 3 d), at most 6 */
+int tbh_csi_depth(uint64_t max_len);
+/* reg2bin of [beg, end) with `depth` levels below bin 0 (depth 5: tbh_bai_reg2bin); UINT32_MAX for a depth outside [0, 6] or an
+ * interval that is empty or not inside [0, 2^(14 + 3 depth)] */
+uint32_t tbh_csi_reg2bin(int64_t beg, int64_t end, int depth);
+
 #ifdef __cplusplus
 }
 #endif

@@ -331,7 +331,8 @@ int tbk_bam_encode(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t ou
  * = the next record's vbeg (the last record's: *out_bytes << 16).  The records must come with nondecreasing refID. */
 typedef struct tbk_ix_opts {
   uint32_t n_ref;           /* references in the output header                                                        */
-  uint32_t reserved;
+  uint32_t reserved;        /* the format: 0 = BAI (references up to 2^29); k >= 1 = CSI of depth k - 1 (min_shift 14, depth <= 6):
+                               bin = reg2bin(beg, end, depth), references and ends up to 2^(14 + 3 * depth).  Zero the struct. */
   const uint32_t* ref_len;  /* HOST [n_ref]: their lengths (the layout of the linear table)                            */
   uint64_t* rec_vbeg;       /* optional HOST [n + 1]: every record's vbeg, then the run's end                          */
 } tbk_ix_opts;
@@ -359,7 +360,8 @@ typedef struct tbk_ix_part {
   const tbk_ix_ref* refs;
 } tbk_ix_part;
 /* tbk_bam_encode, and the index part of the run it wrote.  TBK_EINVAL (nothing faults) for a refID outside [0, n_ref), a negative pos,
- * an end beyond 2^29 (BAI cannot address it), or refIDs that decrease. */
+ * an end beyond 2^29 (BAI cannot address it; CSI: beyond 2^(14 + 3 * depth)) or beyond its reference's last window, refIDs that decrease,
+ * a reference longer than the format addresses (named in tbk_last_error), or a CSI depth above 6. */
 int tbk_bam_encode_indexed(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes,
                            const tbk_ix_opts* ix, tbk_ix_part* part);
 /* (ABI version 8) Groups [first, first + n) of the results kept by the last tbk_collapse_tile with keep_results, into HOST arrays (any

@@ -198,7 +198,8 @@ def load():
 
 # (TBK_HOST_LIB: the sanitizer builds of tools/san_check.sh)
 HOST_LIB_PATH = os.environ.get("TBK_HOST_LIB") or os.path.join(_HERE, "_build", "libtbh.so")
-HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin"]   # include/tbh_host.h
+HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin",
+                "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin"]   # include/tbh_host.h
 _host = None
 
 
@@ -223,6 +224,12 @@ def load_host():
     H.tbh_bai_index_file.restype = C.c_int
     H.tbh_bai_reg2bin.argtypes = [C.c_int64, C.c_int64]
     H.tbh_bai_reg2bin.restype = C.c_uint32
+    H.tbh_csi_index_file.argtypes = [C.c_char_p, C.c_char_p]
+    H.tbh_csi_index_file.restype = C.c_int
+    H.tbh_csi_depth.argtypes = [C.c_uint64]
+    H.tbh_csi_depth.restype = C.c_int
+    H.tbh_csi_reg2bin.argtypes = [C.c_int64, C.c_int64, C.c_int]
+    H.tbh_csi_reg2bin.restype = C.c_uint32
     _host = H
     return H
 

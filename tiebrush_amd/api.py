@@ -379,13 +379,18 @@ class Context:
         from_ctx: the Context that holds them (and the decoded tile), when it is not this one"""
         return self._bam_encode(rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, None)
 
-    def bam_encode_indexed(self, rep, yc, yx, yd, ref_len, n_dev=0, host_records=None, kept_first=None, from_ctx=None):
+    def bam_encode_indexed(self, rep, yc, yx, yd, ref_len, n_dev=0, host_records=None, kept_first=None, from_ctx=None, csi_depth=None):
         """tbk_bam_encode_indexed: bam_encode's (run, payload bytes) and the run's index part (BAI) as a dict of numpy arrays:
         chunks (structured: tid, bin, beg, end), lin (uint64, UINT64_MAX = no record) with lin_first, refs (structured: tid, n_records, first,
-        last), rec_vbeg (uint64 [n + 1]).  Virtual offsets are relative to the run's first byte.  ref_len: the header's reference lengths"""
-        return self._bam_encode(rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, np.ascontiguousarray(ref_len, dtype=np.uint32))
+        last), rec_vbeg (uint64 [n + 1]).  Virtual offsets are relative to the run's first byte.  ref_len: the header's reference lengths.
+        csi_depth: None for the BAI's bins (references up to 2^29); an integer d for a CSI's bins of that depth (tbk_ix_opts.reserved = d + 1:
+        references up to 2^(14 + 3 d), d <= 6)"""
+        if csi_depth is not None and not 0 <= int(csi_depth) < 2 ** 32 - 1:
+            raise ValueError("csi_depth must be None or a non-negative integer")
+        return self._bam_encode(rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, np.ascontiguousarray(ref_len, dtype=np.uint32),
+                                0 if csi_depth is None else int(csi_depth) + 1)
 
-    def _bam_encode(self, rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, ref_len):
+    def _bam_encode(self, rep, yc, yx, yd, n_dev, host_records, kept_first, from_ctx, ref_len, ix_format=0):
         rep = np.ascontiguousarray(rep, dtype=np.uint32)
         n = len(rep)
         e = _lib.EncIn()
@@ -418,7 +423,7 @@ class Context:
         else:
             vb = np.zeros(n + 1, dtype=np.uint64)
             io, part = _lib.IxOpts(), _lib.IxPart()
-            io.n_ref, io.ref_len, io.rec_vbeg = len(ref_len), ref_len.ctypes.data, vb.ctypes.data
+            io.n_ref, io.reserved, io.ref_len, io.rec_vbeg = len(ref_len), ix_format, ref_len.ctypes.data, vb.ctypes.data
             call = lambda: self.L.tbk_bam_encode_indexed(self.h, C.byref(e), out.ctypes.data, out.size, C.byref(need), C.byref(pay), C.byref(io), C.byref(part))
         rc = call()
         if rc == -4:

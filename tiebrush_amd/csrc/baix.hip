@@ -15,6 +15,8 @@
 //                 table's bytes are the same from run to run.  (The other form, one atomicMin per window a record touches plus a fill from
 //                 the right, needs the same scan for the fill and 64-bit atomics on top.)
 //   ix_refs_k     per reference between the run's first and last: its record range by two bisections in M
+// tbk_ix_opts.reserved selects the bins: 0 the BAI's (depth 5, ends up to 2^29), k >= 1 a CSI's of depth k - 1 (ends up to 2^(14 + 3 (k - 1))).
+// The runs, the chunks, the window table and the part are the same for both; the host's combiner turns the table into a CSI's loff per bin.
 #include <stdlib.h>
 #include <string.h>
 
@@ -29,6 +31,7 @@ namespace {
 
 constexpr uint32_t IX_E_RANGE = 8u, IX_E_UNSORTED = 16u, IX_E_MALFORMED = 32u;  // bits of ctx->d_err inside this call
 constexpr uint64_t IX_MAX_END = 1ull << 29;                                      // what a BAI's bins and windows address
+constexpr uint32_t IX_MAX_DEPTH = 6;                                             // CSI: 2^(14 + 3 * 6) covers every BAM length (< 2^31)
 
 __device__ __forceinline__ uint32_t ix_rd32(const uint8_t* p) {
   uint32_t v;
@@ -45,10 +48,20 @@ __device__ __forceinline__ uint32_t ix_reg2bin(uint32_t beg, uint32_t end) {
   if (beg >> 26 == end >> 26) return 1u + (beg >> 26);
   return 0u;
 }
+// the same scheme with `depth` levels below bin 0 (CSI, min_shift 14; htslib hts_reg2bin(beg, end, 14, depth)); end <= 2^(14 + 3 * depth)
+__device__ __forceinline__ uint32_t ix_reg2bin_depth(uint64_t beg, uint64_t end, uint32_t depth) {
+  --end;
+  uint32_t s = 14, t = ((1u << (3 * depth)) - 1u) / 7u;
+  for (uint32_t l = depth; l > 0; --l) {
+    if (beg >> s == end >> s) return t + (uint32_t)(beg >> s);
+    s += 3, t -= 1u << (3 * (l - 1));
+  }
+  return 0u;
+}
 
 __global__ __launch_bounds__(256) void ix_rec_k(uint32_t n, const uint8_t* __restrict__ pay, const uint64_t* __restrict__ ooff, uint32_t nmem,
                                                 const uint64_t* __restrict__ cut, const uint64_t* __restrict__ moff, uint64_t ztotal, uint32_t n_ref,
-                                                const uint64_t* __restrict__ base, uint64_t* __restrict__ key, uint64_t* __restrict__ tend,
+                                                const uint64_t* __restrict__ base, uint32_t fmt, uint64_t* __restrict__ key, uint64_t* __restrict__ tend,
                                                 uint64_t* __restrict__ vbeg, uint32_t* __restrict__ err) {
   const uint32_t g = (blockIdx.x * blockDim.x + threadIdx.x) >> 4, sub = threadIdx.x & 15u;
   if (g > n) return;  // (the sixteen lanes of a record leave together)
@@ -77,14 +90,16 @@ __global__ __launch_bounds__(256) void ix_rec_k(uint32_t n, const uint8_t* __res
   for (int d = 8; d >= 1; d >>= 1) rl += __shfl_xor(rl, d, 16);
   if (sub != 0) return;
   uint32_t bad = ok ? 0u : IX_E_MALFORMED;
+  // (64 bits up to the packing below: pos = 2^31 - 1 with 1M ends on 2^31, which still fits the low word of tid << 32 | end)
   const uint64_t end = (uint64_t)(uint32_t)pos + (rl ? rl : 1ull);
-  if (ok && (tid < 0 || (uint32_t)tid >= n_ref || pos < 0 || end > IX_MAX_END)) bad |= IX_E_RANGE;
+  const uint64_t max_end = fmt ? 1ull << (14 + 3 * (fmt - 1)) : IX_MAX_END;  // fmt: tbk_ix_opts.reserved (0 BAI, k CSI of depth k - 1)
+  if (ok && (tid < 0 || (uint32_t)tid >= n_ref || pos < 0 || end > max_end)) bad |= IX_E_RANGE;
   if (!bad && ((end - 1) >> 14) >= base[tid + 1] - base[tid]) bad |= IX_E_RANGE;  // (ends behind its reference's last window)
   if (bad) {
     atomicOr(err, bad);
     key[g] = 0, tend[g] = 0;
   } else {
-    key[g] = (uint64_t)(uint32_t)tid << 32 | ix_reg2bin((uint32_t)pos, (uint32_t)end);
+    key[g] = (uint64_t)(uint32_t)tid << 32 | (fmt ? ix_reg2bin_depth((uint64_t)(uint32_t)pos, end, fmt - 1) : ix_reg2bin((uint32_t)pos, (uint32_t)end));
     tend[g] = (uint64_t)(uint32_t)tid << 32 | end;
   }
   // the record's member: the last m < nmem with cut[m] <= o (an empty member shares its cut with the next one, which wins)
@@ -239,6 +254,20 @@ void tbk_ix_free(tbk_ctx* ctx) {
 
 int tbk_ix_check_opts(tbk_ctx* ctx, const tbk_ix_opts* ix) {
   if (!ix || (ix->n_ref && !ix->ref_len) || ix->n_ref >= (1u << 31)) return TBK_EINVAL;
+  if (ix->reserved) {  // CSI of depth reserved - 1
+    const uint32_t depth = ix->reserved - 1;
+    if (depth > IX_MAX_DEPTH) {
+      ctx->last_error = "bam_encode_indexed: CSI depth " + std::to_string(depth) + " is above " + std::to_string(IX_MAX_DEPTH);
+      return TBK_EINVAL;
+    }
+    for (uint32_t t = 0; t < ix->n_ref; ++t)
+      if (ix->ref_len[t] > (1ull << (14 + 3 * depth))) {
+        ctx->last_error = "bam_encode_indexed: reference " + std::to_string(t) + " is longer than 2^" + std::to_string(14 + 3 * depth) + ": a CSI of depth " +
+                          std::to_string(depth) + " cannot address it";
+        return TBK_EINVAL;
+      }
+    return 0;
+  }
   for (uint32_t t = 0; t < ix->n_ref; ++t)
     if (ix->ref_len[t] > IX_MAX_END) {
       ctx->last_error = "bam_encode_indexed: reference " + std::to_string(t) + " is longer than 2^29: a BAI cannot address it";
@@ -274,8 +303,8 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
   TBK_HIP(hipMemcpyAsync(d_base, hp, ((size_t)n_ref + 1) * 8, hipMemcpyHostToDevice, st));
   uint64_t* sc = ctx->d_scalars;
   TBK_HIP(hipMemsetAsync(sc, 0, 16 * sizeof(uint64_t), st));
-  TBK_LAUNCH(ctx, "ix_rec", ix_rec_k, cdiv(((uint64_t)n + 1) * 16, 256), 256, 0, n, I.pay, I.ooff, I.nmem, I.cut, I.moff, I.ztotal, n_ref, d_base, key, tend, vbeg,
-             ctx->d_err);
+  TBK_LAUNCH(ctx, "ix_rec", ix_rec_k, cdiv(((uint64_t)n + 1) * 16, 256), 256, 0, n, I.pay, I.ooff, I.nmem, I.cut, I.moff, I.ztotal, n_ref, d_base, ix->reserved, key, tend,
+             vbeg, ctx->d_err);
   TBK_LAUNCH(ctx, "ix_head", ix_head_k, cdiv((uint64_t)n + 1, 256), 256, 0, n, key, head, ctx->d_err);
   TBK_TRY(tbk_exscan_u32(ctx, head, ex, n + 1, sc + 4));
   TBK_TRY((scan_op_run<IxMax, IxMaxOp, IxMaxLoad, IxMaxStore>(ctx, "ix_max_scan", n, IxMaxLoad{tend}, IxMaxStore{M}, IxMaxOp{}, IxMax{0u, 0u})));
@@ -284,8 +313,10 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
   TBK_TRY(tbk_sync_err(ctx, &eb));  // (the run count sizes the sort, the reference range the two tables)
   if (eb) {
     ctx->last_error = (eb & IX_E_MALFORMED)  ? "bam_encode_indexed: a malformed record"
-                      : (eb & IX_E_RANGE)    ? "bam_encode_indexed: a record outside what a BAI addresses (refID not in the header, negative pos, or an end beyond 2^29 "
-                                               "or its reference)"
+                      : (eb & IX_E_RANGE)    ? (ix->reserved ? "bam_encode_indexed: a record outside what the CSI addresses (refID not in the header, negative pos, or an end "
+                                                               "beyond 2^(14 + 3 * depth) or its reference)"
+                                                             : "bam_encode_indexed: a record outside what a BAI addresses (refID not in the header, negative pos, or an end beyond 2^29 "
+                                                               "or its reference)")
                       : (eb & IX_E_UNSORTED) ? "bam_encode_indexed: the records' refIDs decrease"
                                              : "bam_encode_indexed: device error";
     return (eb & (IX_E_MALFORMED | IX_E_RANGE | IX_E_UNSORTED)) ? TBK_EINVAL : TBK_EHIP;
@@ -307,13 +338,15 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
   uint64_t* d_lin = ws_alloc<uint64_t>(ctx, n_lin);
   tbk_ix_ref* d_refs = ws_alloc<tbk_ix_ref>(ctx, n_t);
   if (!sb.hi2 || !sb.lo2 || !sb.val2 || !esorted || !mh || !mex || !d_chunks || !d_lin || !d_refs) return TBK_ENOMEM;
-  // the bits that can differ: refIDs below n_ref, bins below 2^16, virtual offsets below the run's end
+  // the bits that can differ: refIDs below n_ref, bins below 2^16 (a CSI of depth 6: below (8^7 - 1) / 7 = 299593, 19 bits), virtual offsets
+  // below the run's end (a shallow CSI keeps the BAI's 16 bin bits: the same passes)
   auto bits_below = [](uint64_t x) {
     uint64_t m = 0;
     while (m < x) m = m << 1 | 1;
     return m;
   };
-  TBK_TRY(tbk_radix_sort128(ctx, &sb, R, bits_below(n_ref) << 32 | 0xffffull, bits_below(I.ztotal) << 16 | 0xffffull, true));
+  const uint64_t n_bins = ix->reserved ? ((1ull << (3 * ix->reserved)) - 1) / 7 : 37449;
+  TBK_TRY(tbk_radix_sort128(ctx, &sb, R, bits_below(n_ref) << 32 | bits_below(n_bins) | 0xffffull, bits_below(I.ztotal) << 16 | 0xffffull, true));
   TBK_LAUNCH(ctx, "ix_mhead", ix_mhead_k, cdiv((uint64_t)R + 1, 256), 256, 0, R, sb.hi, sb.lo, sb.val, rend, esorted, mh);
   TBK_TRY(tbk_exscan_u32(ctx, mh, mex, R + 1, sc + 7));
   TBK_LAUNCH(ctx, "ix_chunks", ix_chunks_k, cdiv(R, 256), 256, 0, R, sb.hi, sb.lo, esorted, mh, mex, d_chunks);

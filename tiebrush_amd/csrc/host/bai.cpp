@@ -38,18 +38,25 @@ bool member_at(const uint8_t* z, size_t zn, size_t at, size_t* size, size_t* cda
 }
 }  // namespace
 
-// UCSC binning (SAM specification 5.3; htslib hts_reg2bin(beg, end, 14, 5))
-uint32_t bai_reg2bin(int64_t beg, int64_t end) {
+// UCSC binning (SAM specification 5.3; htslib hts_reg2bin(beg, end, 14, depth): 5 for a BAI)
+uint32_t bai_reg2bin(int64_t beg, int64_t end, int depth) {
   --end;
-  if (beg >> 14 == end >> 14) return (uint32_t)(4681 + (beg >> 14));
-  if (beg >> 17 == end >> 17) return (uint32_t)(585 + (beg >> 17));
-  if (beg >> 20 == end >> 20) return (uint32_t)(73 + (beg >> 20));
-  if (beg >> 23 == end >> 23) return (uint32_t)(9 + (beg >> 23));
-  if (beg >> 26 == end >> 26) return (uint32_t)(1 + (beg >> 26));
+  int s = 14;
+  int64_t t = ((1ll << (3 * depth)) - 1) / 7;
+  for (int l = depth; l > 0; --l) {
+    if (beg >> s == end >> s) return (uint32_t)(t + (beg >> s));
+    s += 3, t -= 1ll << (3 * (l - 1));
+  }
   return 0;
 }
 
-bool bai_rec_span(const uint8_t* r, size_t len, int32_t* tid, int32_t* beg, int32_t* end) {
+int csi_depth(uint64_t max_len) {
+  int d = 0;
+  while (d < kCsiMaxDepth && max_len + 256 > (1ull << (14 + 3 * d))) ++d;
+  return d;
+}
+
+bool bai_rec_span(const uint8_t* r, size_t len, int32_t* tid, int32_t* beg, int64_t* end) {
   if (len < 32) return false;
   const uint32_t l_qname = r[8], n_cig = (uint32_t)r[12] | (uint32_t)r[13] << 8;
   if (32ull + l_qname + 4ull * n_cig > len) return false;
@@ -60,8 +67,7 @@ bool bai_rec_span(const uint8_t* r, size_t len, int32_t* tid, int32_t* beg, int3
     const uint32_t c = le32(r + 32 + l_qname + 4 * (size_t)i);
     if ((0x18Du >> (c & 15u)) & 1u) rl += c >> 4;  // M D N = X consume the reference
   }
-  const uint64_t e = (uint64_t)(uint32_t)*beg + (rl ? rl : 1);
-  *end = e > (uint64_t)INT32_MAX ? INT32_MAX : (int32_t)e;
+  *end = (int64_t)((uint64_t)(uint32_t)*beg + (rl ? rl : 1));  // (at most 2^32 + 65535 * 2^28)
   return true;
 }
 
@@ -91,18 +97,20 @@ bool bai_member_voffsets(const uint8_t* z, size_t zn, std::vector<BaiRec>& recs,
   return true;
 }
 
-bool bai_build_part(const BaiRec* recs, size_t n, uint64_t vend_last, const std::vector<uint32_t>& ref_len, BaiPart& out, std::string& err) {
+bool bai_build_part(const BaiRec* recs, size_t n, uint64_t vend_last, const std::vector<uint32_t>& ref_len, BaiPart& out, std::string& err, int depth) {
   out.chunks.clear(), out.lin.clear(), out.refs.clear();
   out.lin_first = 0;
   if (n == 0) return true;
   const size_t n_ref = ref_len.size();
   std::vector<uint64_t> base(n_ref + 1, 0);
   for (size_t t = 0; t < n_ref; ++t) base[t + 1] = base[t] + (((uint64_t)ref_len[t] + 16383) >> 14);
+  const uint64_t max_end = 1ull << (14 + 3 * depth);
   for (size_t i = 0; i < n; ++i) {
     const BaiRec& r = recs[i];
-    if (r.tid < 0 || (size_t)r.tid >= n_ref || r.beg < 0 || r.end <= r.beg || (uint64_t)r.end > kBaiMaxRef ||
+    if (r.tid < 0 || (size_t)r.tid >= n_ref || r.beg < 0 || r.end <= r.beg || (uint64_t)r.end > max_end ||
         (((uint64_t)r.end - 1) >> 14) >= base[(size_t)r.tid + 1] - base[(size_t)r.tid]) {
-      err = "bai: record " + std::to_string(i) + " lies outside what a BAI addresses (refID not in the header, negative pos, or an end beyond 2^29 or its reference)";
+      err = "bai: record " + std::to_string(i) + " lies outside what " + (depth == kBaiDepth ? std::string("a BAI") : "an index of depth " + std::to_string(depth)) +
+            " addresses (refID not in the header, negative pos, or an end beyond 2^" + std::to_string(14 + 3 * depth) + " or its reference)";
       return false;
     }
     if (i && r.tid < recs[i - 1].tid) {
@@ -113,9 +121,9 @@ bool bai_build_part(const BaiRec* recs, size_t n, uint64_t vend_last, const std:
   auto vend = [&](size_t i) { return i + 1 < n ? recs[i + 1].vbeg : vend_last; };
   // runs of equal (tid, bin)
   for (size_t i = 0; i < n;) {
-    const uint32_t bin = bai_reg2bin(recs[i].beg, recs[i].end);
+    const uint32_t bin = bai_reg2bin(recs[i].beg, recs[i].end, depth);
     size_t j = i + 1;
-    while (j < n && recs[j].tid == recs[i].tid && bai_reg2bin(recs[j].beg, recs[j].end) == bin) ++j;
+    while (j < n && recs[j].tid == recs[i].tid && bai_reg2bin(recs[j].beg, recs[j].end, depth) == bin) ++j;
     out.chunks.push_back(BaiChunk{recs[i].tid, bin, recs[i].vbeg, vend(j - 1)});
     i = j;
   }
@@ -134,7 +142,7 @@ bool bai_build_part(const BaiRec* recs, size_t n, uint64_t vend_last, const std:
   out.chunks.resize(l + 1);
   // linear table and per-reference ranges
   const int32_t t0 = recs[0].tid, t1 = recs[n - 1].tid;
-  int32_t max_end_last = 0;
+  int64_t max_end_last = 0;
   for (size_t i = n; i-- > 0 && recs[i].tid == t1;) max_end_last = std::max(max_end_last, recs[i].end);
   out.lin_first = base[(size_t)t0];
   out.lin.assign((size_t)(base[(size_t)t1] + (((uint64_t)max_end_last - 1) >> 14) + 1 - out.lin_first), ~0ull);
@@ -158,12 +166,25 @@ bool BaiIndex::init(const std::vector<std::string>& names, const std::vector<uin
       err = "reference " + (t < names.size() ? names[t] : std::to_string(t)) + " is longer than 2^29 (" + std::to_string(lens[t]) + "): a BAI index cannot address it";
       return false;
     }
+  csi_ = false, depth_ = kBaiDepth;
+  set_refs(lens);
+  return true;
+}
+
+bool BaiIndex::init_csi(const std::vector<std::string>&, const std::vector<uint32_t>& lens, std::string&) {
+  uint64_t longest = 0;
+  for (uint32_t l : lens) longest = std::max<uint64_t>(longest, l);
+  csi_ = true, depth_ = csi_depth(longest);  // (BAM lengths are below 2^31: depth 6 covers them)
+  set_refs(lens);
+  return true;
+}
+
+void BaiIndex::set_refs(const std::vector<uint32_t>& lens) {
   len_ = lens;
   base_.assign(lens.size() + 1, 0);
   for (size_t t = 0; t < lens.size(); ++t) base_[t + 1] = base_[t] + (((uint64_t)lens[t] + 16383) >> 14);
   ref_.assign(lens.size(), Ref());
   active_ = true;
-  return true;
 }
 
 void BaiIndex::add(uint64_t file_base, const BaiChunk* chunks, size_t n_chunks, uint64_t lin_first, const uint64_t* lin, size_t n_lin, const BaiRef* refs,
@@ -198,8 +219,38 @@ void BaiIndex::add(uint64_t file_base, const BaiChunk* chunks, size_t n_chunks, 
   }
 }
 
+// CSIv1 before compression: a bin's loff is the linear table's entry of the bin's first 16 kb window (a record of the bin ends behind the
+// bin's start, so the entry exists); the table itself is not written
+void BaiIndex::serialize_csi(std::vector<uint8_t>& o) const {
+  o.insert(o.end(), {'C', 'S', 'I', 1});
+  put32(o, 14), put32(o, (uint32_t)depth_), put32(o, 0);
+  put32(o, (uint32_t)ref_.size());
+  std::vector<uint32_t> first((size_t)depth_ + 2, 0);  // first[l]: the first bin of level l; first[depth + 1] + 1: the meta bin
+  for (int l = 0; l <= depth_; ++l) first[(size_t)l + 1] = first[(size_t)l] + (1u << (3 * l));
+  for (const Ref& r : ref_) {
+    if (r.n == 0) {
+      put32(o, 0);
+      continue;
+    }
+    put32(o, (uint32_t)r.bins.size() + 1);
+    for (const auto& b : r.bins) {
+      int l = depth_;
+      while (b.first < first[(size_t)l]) --l;
+      const uint64_t w = (uint64_t)(b.first - first[(size_t)l]) << (3 * (depth_ - l));
+      put32(o, b.first);
+      put64(o, w < r.lin.size() && r.lin[w] != ~0ull ? r.lin[w] : 0);
+      put32(o, (uint32_t)b.second.size());
+      for (const auto& c : b.second) put64(o, c.first), put64(o, c.second);
+    }
+    put32(o, first[(size_t)depth_ + 1] + 1), put64(o, 0), put32(o, 2);  // the meta bin: what the BAI's pseudo-bin holds
+    put64(o, r.first), put64(o, r.last), put64(o, r.n), put64(o, 0);
+  }
+  put64(o, 0);  // n_no_coor
+}
+
 void BaiIndex::serialize(std::vector<uint8_t>& o) const {
   o.clear();
+  if (csi_) return serialize_csi(o);
   o.insert(o.end(), {'B', 'A', 'I', 1});
   put32(o, (uint32_t)ref_.size());
   for (const Ref& r : ref_) {
@@ -225,6 +276,16 @@ bool BaiIndex::write(const std::string& path, std::string& err) const {
   std::vector<uint8_t> o;
   serialize(o);
   const std::string tmp = path + ".tmp";
+  if (csi_) {  // BGZF members and the EOF member, by the host codec
+    BgzfWriter w;
+    const bool ok = w.open(tmp, 6, 1) && w.write(o.data(), o.size());
+    if (!(w.close() && ok) || rename(tmp.c_str(), path.c_str()) != 0) {
+      (void)unlink(tmp.c_str());
+      err = "cannot write " + path;
+      return false;
+    }
+    return true;
+  }
   FILE* f = fopen(tmp.c_str(), "wb");
   if (!f) {
     err = "cannot create " + tmp;
@@ -239,7 +300,7 @@ bool BaiIndex::write(const std::string& path, std::string& err) const {
   return true;
 }
 
-bool bai_index_file(const std::string& bam_path, const std::string& bai_path, std::string& err) {
+bool bai_index_file(const std::string& bam_path, const std::string& bai_path, std::string& err, bool csi) {
   std::vector<uint8_t> z;
   {
     FILE* f = fopen(bam_path.c_str(), "rb");
@@ -304,7 +365,7 @@ bool bai_index_file(const std::string& bam_path, const std::string& bai_path, st
     p += 8 + (size_t)ln;
   }
   BaiIndex ix;
-  if (!ix.init(names, lens, err)) return false;
+  if (!(csi ? ix.init_csi(names, lens, err) : ix.init(names, lens, err))) return false;
   // records; a payload offset's virtual offset: the member that holds the byte (the end of the payload: the EOF member, else the file's end)
   size_t mi = 0;
   auto voff = [&](uint64_t q) {
@@ -333,7 +394,7 @@ bool bai_index_file(const std::string& bam_path, const std::string& bai_path, st
     p += 4 + (size_t)bs;
   }
   BaiPart part;
-  if (!bai_build_part(recs.data(), recs.size(), voff(pay.size()), lens, part, err)) return false;
+  if (!bai_build_part(recs.data(), recs.size(), voff(pay.size()), lens, part, err, ix.depth())) return false;
   ix.add(0, part);
   return ix.write(bai_path, err);
 }

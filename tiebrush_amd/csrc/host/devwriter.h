@@ -66,7 +66,7 @@ class DeviceWriter {
   // output — TBK_EUNSUPPORTED (a record too long for a BGZF member of its own: bgzdef.hip) or TBK_ENOMEM / no pinned memory, on ANY
   // chunk: the chunks before the refused one are written in full and *groups_done says how many groups that was, so the caller's host
   // writer takes the groups from there on (a long read far into the output does not cost the run).  Any other failure is fatal
-  // (GError).  *payload / *zbytes: bytes of tagged records / of BGZF members written.  With `bai` (tiebrush --index) every chunk goes
+  // (GError).  *payload / *zbytes: bytes of tagged records / of BGZF members written.  With `bai` (tiebrush --index / --csi) every chunk goes
   // through tbk_bam_encode_indexed and the write stage, which knows where the chunk's members land in the file, hands its index part on.
   bool write(tbk_ctx* ctx, GSamWriter& out, uint32_t ng, const uint32_t* rep, const double* yc, const int64_t* yx, const int32_t* yd, uint32_t n_dev,
              const std::function<tbh::RecView(uint32_t)>& host_record, uint64_t* payload, uint64_t* zbytes, std::string& why, uint32_t* groups_done,
@@ -152,7 +152,7 @@ class DeviceWriter {
     std::vector<tbh::BaiPart> ixpart(bai ? nchunk : 0);  // (a chunk's part: copied out of its context before that encodes again)
     tbk_ix_opts ixo;
     memset(&ixo, 0, sizeof(ixo));
-    if (bai) ixo.n_ref = (uint32_t)bai->ref_len().size(), ixo.ref_len = bai->ref_len().data();
+    if (bai) ixo.n_ref = (uint32_t)bai->ref_len().size(), ixo.ref_len = bai->ref_len().data(), ixo.reserved = bai->ix_format();  // (0: BAI; --csi: depth + 1)
     tbk_ix_part ixp[2];
     auto tnow = [] { return std::chrono::steady_clock::now(); };
     auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };

@@ -107,4 +107,15 @@ int tbh_bai_index_file(const char* bam_path, const char* bai_path) {
 }
 uint32_t tbh_bai_reg2bin(int64_t beg, int64_t end) { return tbh::bai_reg2bin(beg, end); }
 
+int tbh_csi_index_file(const char* bam_path, const char* csi_path) {
+  if (!bam_path) return fail("tbh_csi_index_file: null argument");
+  std::string err;
+  if (!tbh::bai_index_file(bam_path, csi_path ? std::string(csi_path) : std::string(bam_path) + ".csi", err, true)) return fail("tbh_csi_index_file: " + err);
+  return 0;
+}
+int tbh_csi_depth(uint64_t max_len) { return tbh::csi_depth(max_len); }
+uint32_t tbh_csi_reg2bin(int64_t beg, int64_t end, int depth) {
+  return depth < 0 || depth > tbh::kCsiMaxDepth || beg < 0 || end <= beg || end > (1ll << (14 + 3 * depth)) ? UINT32_MAX : tbh::bai_reg2bin(beg, end, depth);
+}
+
 }  // extern "C"

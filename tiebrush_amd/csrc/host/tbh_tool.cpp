@@ -4,6 +4,7 @@
 //   soa OUTDIR IN1.bam ...        dump the SoA tile arrays (one raw little-endian file per array)
 //   tags IN.bam OUT.bam SPEC...   apply tag edits to every record: YC=f:2.5  YX=i:255  YD=i:0  YD=del
 //   bai IN.bam                    write IN.bam.bai with the host index builder alone (bai.h: what `tiebrush --index` builds as it writes)
+//   csi IN.bam                    write IN.bam.csi the same way (what `tiebrush --csi` builds: references beyond 2^29 included)
 //   mkbam SOADIR PREFIX [LEVEL [THREADS]]   encode the raw SoA arrays of a synthetic tile (file_off, tid, pos, flag, mapq, strand,
 //                                 nh, cig_off, cig as little-endian files + header.txt) as PREFIX<f>.bam, one per input file: the
 //                                 records tiebrush_amd.synth.write_bams writes (SEQ '*', QNAME r<f>_<i>, NH:C / XS:A), files in parallel
@@ -372,6 +373,14 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai ...\n");
+  if (cmd == "csi" && argc == 3) {
+    std::string err;
+    if (!tbh::bai_index_file(argv[2], std::string(argv[2]) + ".csi", err, true)) {
+      fprintf(stderr, "tbh_tool csi: %s\n", err.c_str());
+      return 1;
+    }
+    return 0;
+  }
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi ...\n");
   return 2;
 }

@@ -78,7 +78,9 @@ static const char* USAGE =
     "  --bigwig             write the coverage track as PREFIX.bigwig (as tiecov -W; needs --cov)\n"
     "                       (the tracks are what tiecov writes when it reads OUT.bam; not with --ranks)\n"
     "  --index              also write the output's BAM index OUT.bam.bai (what samtools index makes of OUT.bam; not with --ranks,\n"
-    "                       not when the output goes to standard output)\n";
+    "                       not when the output goes to standard output)\n"
+    "  --csi                also write the output's CSI index OUT.bam.csi (what samtools index -c makes of OUT.bam: for references\n"
+    "                       longer than 2^29, which a BAI cannot address; not with --index, --ranks or standard output)\n";
 
 // a buffer that is allocated, not initialised (untouched pages cost nothing), on huge pages when it is large, and not freed at
 // the end: these buffers live as long as the process, which ends with _exit — returning gigabytes page by page first only
@@ -496,7 +498,7 @@ class Output {
   uint64_t dev_payload = 0, dev_z = 0;
 
   Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env, TrackRecs* tracks, tbh::BaiIndex* bai = nullptr)
-      : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env), tracks_(tracks), bai_(bai), bai_path_(std::string(fname) + ".bai") {}
+      : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env), tracks_(tracks), bai_(bai), bai_path_(std::string(fname) + (bai && bai->csi() ? ".csi" : ".bai")) {}
   // (the end of the file: the EOF member; the index goes out once that is on disk)
   void close() {
     file_.reset();
@@ -550,7 +552,7 @@ class Output {
         const std::vector<tbh::BaiRec>& sr = slice_recs[slice++];
         tbh::BaiPart part;
         std::string err;
-        if (!tbh::bai_build_part(sr.data(), sr.size(), (uint64_t)n << 16, bai_->ref_len(), part, err)) GError("Error: indexing the output failed: %s\n", err.c_str());
+        if (!tbh::bai_build_part(sr.data(), sr.size(), (uint64_t)n << 16, bai_->ref_len(), part, err, bai_->depth())) GError("Error: indexing the output failed: %s\n", err.c_str());
         bai_->add(file_->tell(), part);
       }
       return file_->write_members(z, n), true;
@@ -574,7 +576,7 @@ class Output {
   Device& dev_;
   const Env& env_;
   TrackRecs* tracks_;
-  tbh::BaiIndex* bai_;  // --index: the parts of everything that goes into the file, in file order
+  tbh::BaiIndex* bai_;  // --index / --csi: the parts of everything that goes into the file, in file order
   std::string bai_path_;
 
   // fetch: the values of groups [0, ng) are on the device only (keep_results)
@@ -1235,10 +1237,11 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
 
 // the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
-  bool ranks = false, tracks = false, index = false;
+  bool ranks = false, tracks = false, index = false, csi = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
     index = index || strcmp(argv[i], "--index") == 0;
+    csi = csi || strcmp(argv[i], "--csi") == 0;
     for (const char* o : {"--cov", "--junc", "--samp", "--bigwig"}) {
       const size_t k = strlen(o);
       tracks = tracks || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
@@ -1246,6 +1249,7 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
   }
   if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
   if (ranks && index) GError("Error: --index is not available with --ranks (index the output afterwards)\n");
+  if (ranks && csi) GError("Error: --csi is not available with --ranks (index the output afterwards)\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -1254,7 +1258,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;SMLPEDVho:N:Q:F:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;csi;SMLPEDVho:N:Q:F:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1317,6 +1321,10 @@ int main(int argc, char* argv[]) {
   const bool want_index = args.getOpt("index") != nullptr;
   if (want_index && strcmp(outfname, "-") == 0)
     GError("Error: --index needs an output file (-o FILE): an index addresses file offsets, standard output has none\n");
+  const bool want_csi = args.getOpt("csi") != nullptr;
+  if (want_csi && want_index) GError("Error: --csi and --index do not go together (their bins differ: one run builds one index)\n");
+  if (want_csi && strcmp(outfname, "-") == 0)
+    GError("Error: --csi needs an output file (-o FILE, not -o -): an index addresses file offsets, standard output has none\n");
   const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty();
   while (const char* ifn = args.nextNonOpt()) inRecords.addFile(tbh_realpath(ifn).c_str());
 
@@ -1344,7 +1352,12 @@ int main(int argc, char* argv[]) {
     if (!bai.init(inRecords.header()->target_name, inRecords.header()->target_len, err)) GError("Error: --index: %s\n", err.c_str());
     (void)unlink((std::string(outfname) + ".bai").c_str());
   }
-  Output out(outfname, inRecords.header(), dev, env, trecs.get(), want_index ? &bai : nullptr);
+  if (want_csi) {  // (any header: the depth follows its longest reference)
+    std::string err;
+    if (!bai.init_csi(inRecords.header()->target_name, inRecords.header()->target_len, err)) GError("Error: --csi: %s\n", err.c_str());
+    (void)unlink((std::string(outfname) + ".csi").c_str());
+  }
+  Output out(outfname, inRecords.header(), dev, env, trecs.get(), want_index || want_csi ? &bai : nullptr);
   const Inputs inp(inRecords);
   const Routes can = eligible_routes(env, opt, inp);
   Route r = Route::fall_through;

@@ -200,7 +200,7 @@ struct TbkIxIn {
   const uint64_t* moff;   // [nmem + 1] the members' offsets in the packed run
   uint64_t ztotal;        // bytes of the packed run
 };
-int tbk_ix_check_opts(tbk_ctx* ctx, const tbk_ix_opts* ix);  // TBK_EINVAL for a reference a BAI cannot address
+int tbk_ix_check_opts(tbk_ctx* ctx, const tbk_ix_opts* ix);  // TBK_EINVAL for a reference the format (tbk_ix_opts.reserved) cannot address
 int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& in, const tbk_ix_opts* ix, tbk_ix_part* part);
 // the tile tbk_bam_decode left on the context: inflated streams, record offsets, record count (false: there is none)
 bool tbk_bam_dev_records(tbk_ctx* ctx, const uint8_t** inf, const uint64_t** rec, uint32_t* n);

@@ -52,10 +52,13 @@ def _parse(argv):
     ap.add_argument("-V", "--verbose", action="store_true")
     ap.add_argument("--level", type=int, default=6, help="deflate level of the output")
     ap.add_argument("--index", action="store_true")
+    ap.add_argument("--csi", action="store_true")
     ap.add_argument("inputs", nargs="+")
     a = ap.parse_args(argv)
     if a.index:
         ap.error("--index is not available with --ranks (the ranks' parts are joined by a process that has not seen their records)")
+    if a.csi:
+        ap.error("--csi is not available with --ranks (the ranks' parts are joined by a process that has not seen their records)")
     if a.collapse_same or a.store_frac:
         ap.error("-A and --store-frac need the single-GPU path's ordered passes (run tiebrush without --ranks)")
     if a.F or a.keep_unmap:
