@@ -27,6 +27,7 @@
 
 #include <chrono>
 
+#include "cb_tiles.hpp"
 #include "dev_common.hpp"
 #include "rx_w64.hpp"
 #include "scan_op.hpp"
@@ -2629,17 +2630,91 @@ __device__ __forceinline__ uint32_t g2c_key_ops(uint64_t k1) {  // CIGAR words t
   const uint32_t shape = (uint32_t)k1;
   return shape == 0x80000000u ? 1u : ((shape >> 30) == 3u ? 3u : 0u);
 }
-__global__ void g2c_count_key_k(uint32_t ng, const uint64_t* __restrict__ key, const uint32_t* __restrict__ rep, const uint32_t* __restrict__ cig_off,
-                                uint32_t* __restrict__ cnt, uint32_t* __restrict__ cfirst) {
-  uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= ng) return;
-  uint32_t n = g2c_key_ops(key[2 * (size_t)o + 1]);
-  if (n == 0) {
-    const uint32_t c0 = cig_off[rep[o]];
-    n = cig_off[rep[o] + 1] - c0;
-    cfirst[o] = c0;
+// The first pass of the key path, one block per CB_TILE groups in the thread order of tiecov's tile passes (cb_agg_k: a thread owns four
+// consecutive groups of every row): the CIGAR words every group needs (cnt; cfirst for the groups whose representative is fetched), and
+// — every group's reference and end are known here: pos + span from the key, walk_exons over the representative's CIGAR otherwise, as
+// the gather pass computes them — the tile's aggregate of the bundle monoid, which tiecov's bundle passes start from (cb_agg_k's
+// result without its pass over tid and end).  The block that finishes last turns the aggregates into "everything before the tile"
+// (cb_spine_block) and the tiles' sums of cnt into their exclusive prefixes (tsum, in place; *total = their sum): the gather pass
+// needs no scan of cnt beyond one tile.  No block waits for another.
+__global__ __launch_bounds__(CB_NT) void g2c_count_key_k(uint32_t ng, const uint64_t* __restrict__ key, const uint32_t* __restrict__ rep,
+                                                         const uint32_t* __restrict__ cig_off, const uint32_t* __restrict__ cig,
+                                                         uint32_t* __restrict__ cnt, uint32_t* __restrict__ cfirst, uint4* __restrict__ part,
+                                                         unsigned long long* __restrict__ tsum, uint32_t* __restrict__ done,
+                                                         unsigned long long* __restrict__ total) {
+  constexpr uint32_t NWV = CB_NT / 64;
+  __shared__ CbAgg wl[CB_ROWS * NWV];
+  __shared__ unsigned long long wsum[CB_ROWS * NWV];
+  const CbOp op{};
+  const CbAgg none{0, INT32_MIN, INT32_MIN, 1u};
+  for (uint32_t r = 0; r < CB_ROWS; ++r) {
+    const uint64_t i = (uint64_t)blockIdx.x * CB_TILE + ((uint64_t)r * CB_NT + threadIdx.x) * 4u;
+    CbAgg a = none;
+    uint32_t n4[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (i + e < ng) {
+        const uint32_t o = (uint32_t)(i + e);
+        const uint64_t k0 = key[2 * (size_t)o], k1 = key[2 * (size_t)o + 1];
+        const int32_t tidv = (int32_t)(uint32_t)(k0 >> 33) - 1, posv = (int32_t)(uint32_t)((k0 >> 2) & 0x7FFFFFFFull) - 1;
+        uint32_t n = g2c_key_ops(k1);
+        int l = (int)(uint32_t)(k1 >> 32);  // the span (the key's shapes consume it whole)
+        if (n == 0) {
+          const uint32_t rp = rep[o];
+          const uint32_t c0 = cig_off[rp];
+          n = cig_off[rp + 1] - c0;
+          cfirst[o] = c0;
+          int nex = 0;
+          l = walk_exons(posv, cig + c0, n, [](int, int) {}, &nex);
+        }
+        n4[e] = n;
+        a = op(a, CbAgg{tidv, tidv, posv + l, 1u});
+      }
+    }
+    if (i + 3 < ng) {
+      *reinterpret_cast<uint4*>(cnt + i) = make_uint4(n4[0], n4[1], n4[2], n4[3]);  // (i is a multiple of 4, the array 256-byte aligned)
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (i + e < ng) cnt[i + e] = n4[e];
+    }
+    a = wave_incl_scan_op(a, op);
+    const unsigned long long sum = wave_sum((unsigned long long)n4[0] + n4[1] + n4[2] + n4[3]);
+    if (lane_id() == 63) {
+      wl[r * NWV + (threadIdx.x >> 6)] = a;
+      wsum[r * NWV + (threadIdx.x >> 6)] = sum;
+    }
   }
-  cnt[o] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    CbAgg run = none;
+    unsigned long long sum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < CB_ROWS * NWV; ++q) {
+      run = op(run, wl[q]);
+      sum += wsum[q];
+    }
+    uint64_t* o = reinterpret_cast<uint64_t*>(part + blockIdx.x);
+    cb_put(o, (uint64_t)(uint32_t)run.first_tid | ((uint64_t)(uint32_t)run.last_tid << 32));
+    cb_put(o + 1, (uint64_t)(uint32_t)run.mx | ((uint64_t)run.whole << 32));
+    cb_put(reinterpret_cast<uint64_t*>(tsum + blockIdx.x), sum);
+  }
+  if (!cb_last_block(done)) return;
+  const uint32_t ntiles = gridDim.x;
+  cb_spine_block<CB_NT>(part, ntiles, wl);
+  // the tiles' sums -> the sum of the tiles before each: a slice of the tiles per thread, as in cb_spine_block
+  const uint32_t per = (ntiles + CB_NT - 1u) / CB_NT;
+  const uint32_t i0 = threadIdx.x * per < ntiles ? threadIdx.x * per : ntiles, i1 = i0 + per < ntiles ? i0 + per : ntiles;
+  unsigned long long mine = 0;
+  for (uint32_t q = i0; q < i1; ++q) mine += cb_get(reinterpret_cast<const uint64_t*>(tsum + q));
+  unsigned long long tot;
+  unsigned long long run = block_excl_sum<unsigned long long, CB_NT>(mine, wsum, &tot);
+  for (uint32_t q = i0; q < i1; ++q) {
+    const unsigned long long v = cb_get(reinterpret_cast<const uint64_t*>(tsum + q));
+    tsum[q] = run;
+    run += v;
+  }
+  if (threadIdx.x == 0) *total = tot;
 }
 struct G2cPrep {  // the first pass of tbk_coverage_tile, per view record (cov.hip: cov_prep_k) — and its three scalars
   int32_t *start, *end, *yi;
@@ -2649,13 +2724,38 @@ struct G2cPrep {  // the first pass of tbk_coverage_tile, per view record (cov.h
 __global__ __launch_bounds__(256) void g2c_gather_key_k(uint32_t ng, const uint64_t* __restrict__ key, const double* __restrict__ yc,
                                                         const int64_t* __restrict__ yx, const uint32_t* __restrict__ cfirst,
                                                         const uint32_t* __restrict__ cnt, const uint32_t* __restrict__ cig,
-                                                        const uint32_t* __restrict__ ooff, uint32_t total, int32_t* __restrict__ o_tid,
+                                                        const unsigned long long* __restrict__ tbase, const uint4* __restrict__ part,
+                                                        uint32_t ntiles, uint32_t total, int32_t* __restrict__ o_tid,
                                                         int32_t* __restrict__ o_pos, uint8_t* __restrict__ o_strand, double* __restrict__ o_yc,
                                                         int64_t* __restrict__ o_yx, uint32_t* __restrict__ o_cig_off, uint32_t* __restrict__ o_cig,
-                                                        G2cPrep P) {
+                                                        uint4* __restrict__ o_part, G2cPrep P) {
+  // Whole tiles of CB_TILE groups, a thread per group and row of 256 as before: a group's place in the view's CIGAR words is the tile's
+  // base (the count pass's last block) plus the groups before it in the tile — the rows' wave sums through LDS, then a wave scan per
+  // row (cnt is read twice, the second time from cache, where the device-wide scan wrote and this pass read an array of offsets).
+  constexpr uint32_t NROW = CB_TILE / 256u;
+  __shared__ uint32_t s_w[NROW * 4u];
+  for (uint32_t q = blockIdx.x * 256u + threadIdx.x; q < ntiles; q += gridDim.x * 256u) o_part[q] = part[q];  // tiecov's tile aggregates: into the view's storage
   unsigned long long mb = 0, ay = 0, nji = 0;
   uint32_t eb = 0;
-  for (uint32_t o = blockIdx.x * blockDim.x + threadIdx.x; o < ng; o += gridDim.x * blockDim.x) {
+  for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (uniform)
+  const uint32_t o0 = tile * CB_TILE;
+  for (uint32_t j = 0; j < NROW; ++j) {
+    const uint32_t o = o0 + j * 256u + threadIdx.x;
+    const uint32_t s = wave_sum(o < ng ? cnt[o] : 0u);
+    if (lane_id() == 0) s_w[j * 4u + (threadIdx.x >> 6)] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64u) {
+    const uint32_t v = s_w[threadIdx.x];
+    s_w[threadIdx.x] = wave_incl_sum(v) - v;
+  }
+  __syncthreads();
+  const uint32_t base = (uint32_t)tbase[tile];
+  for (uint32_t j = 0; j < NROW; ++j) {
+    const uint32_t o = o0 + j * 256u + threadIdx.x;
+    const uint32_t cn = o < ng ? cnt[o] : 0u;
+    const uint32_t d = base + s_w[j * 4u + (threadIdx.x >> 6)] + wave_incl_sum(cn) - cn;
+    if (o >= ng) continue;
     const uint64_t k0 = key[2 * (size_t)o], k1 = key[2 * (size_t)o + 1];
     const int32_t tidv = (int32_t)(uint32_t)(k0 >> 33) - 1, posv = (int32_t)(uint32_t)((k0 >> 2) & 0x7FFFFFFFull) - 1;
     o_tid[o] = tidv;
@@ -2665,7 +2765,6 @@ __global__ __launch_bounds__(256) void g2c_gather_key_k(uint32_t ng, const uint6
     const double y0 = (double)(float)yc[o];  // the YC:f tag round trip (bam_aux_update_float, tiebrush.cpp:509)
     o_yc[o] = y0;
     o_yx[o] = yx[o];
-    const uint32_t d = ooff[o];
     o_cig_off[o] = d;
     if (o + 1 == ng) o_cig_off[ng] = total;
     const uint32_t shape = (uint32_t)k1, span = (uint32_t)(k1 >> 32);
@@ -2684,7 +2783,7 @@ __global__ __launch_bounds__(256) void g2c_gather_key_k(uint32_t ng, const uint6
       nex = 2;
       mb += span - g;
     } else {
-      const uint32_t c0 = cfirst[o], n = cnt[o];
+      const uint32_t c0 = cfirst[o], n = cn;
       l = walk_exons(posv, cig + c0, n, [](int, int) {}, &nex);
       for (uint32_t k = 0; k < n; ++k) {
         const uint32_t w = cig[c0 + k];
@@ -2710,6 +2809,8 @@ __global__ __launch_bounds__(256) void g2c_gather_key_k(uint32_t ng, const uint6
     P.end[o] = posv + l;
     P.jcnt[o] = (uint32_t)(nex - 1);
     nji += (unsigned long long)(nex - 1);
+  }
+  __syncthreads();  // (the rows' sums are read no more: the next tile may write its own)
   }
   __shared__ unsigned long long red_mb[4], red_ay[4], red_nj[4];
   __shared__ uint32_t red_e[4];
@@ -2787,22 +2888,35 @@ int tbk_cov_view_build(tbk_ctx* ctx, const int32_t* r_tid, const int32_t* r_pos,
   ctx->view_prep.valid = false;  // (the context's view is about to change)
   if (ng == 0) return 0;
   uint32_t* cnt = ws_alloc<uint32_t>(ctx, ng);
-  uint32_t* ooff = ws_alloc<uint32_t>(ctx, ng);
   uint32_t* cfirst = ws_alloc<uint32_t>(ctx, ng);
-  if (!cfirst) return TBK_ENOMEM;
+  if (!cnt || !cfirst) return TBK_ENOMEM;
   const uint32_t B = 256;
-  if (g_key)
-    TBK_LAUNCH(ctx, "g2c_count", g2c_count_key_k, cdiv(ng, B), B, 0, ng, g_key, g_rep, r_cig_off, cnt, cfirst);
-  else
+  static_assert(CB_NT == 256 && CB_TILE % 256 == 0 && CB_TILE / 256 * 4 == 64, "g2c_gather_key_k: rows of 256 groups, 64 wave sums per tile");
+  const uint32_t ntiles = cdiv(ng, CB_TILE);  // (g_key) tiecov's tiles
+  uint32_t* ooff = nullptr;
+  uint4* part = nullptr;
+  unsigned long long* tbase = nullptr;
+  if (g_key) {
+    part = ws_alloc<uint4>(ctx, ntiles);
+    tbase = ws_alloc<unsigned long long>(ctx, ntiles);
+    if (!part || !tbase) return TBK_ENOMEM;
+    uint32_t* done = (uint32_t*)(ctx->d_scalars + 21);  // blocks of the count pass that have finished: the last one scans the tiles
+    TBK_HIP(hipMemsetAsync(done, 0, sizeof(uint64_t), ctx->stream));
+    TBK_LAUNCH(ctx, "g2c_count", g2c_count_key_k, ntiles, CB_NT, 0, ng, g_key, g_rep, r_cig_off, r_cig, cnt, cfirst, part, tbase, done,
+               (unsigned long long*)(ctx->d_scalars + 20));
+  } else {
+    ooff = ws_alloc<uint32_t>(ctx, ng);
+    if (!ooff) return TBK_ENOMEM;
     TBK_LAUNCH(ctx, "g2c_count", g2c_count_k, cdiv(ng, B), B, 0, ng, g_rep, r_cig_off, cnt, cfirst);
-  TBK_TRY(tbk_exscan_u32(ctx, cnt, ooff, ng, ctx->d_scalars + 20));
+    TBK_TRY(tbk_exscan_u32(ctx, cnt, ooff, ng, ctx->d_scalars + 20));
+  }
   TBK_HIP(hipMemcpyAsync(ctx->h_scalars + 20, ctx->d_scalars + 20, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   const uint64_t total = ctx->h_scalars[20];
   if (total >= (1ull << 32)) return TBK_E2BIG;
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t need = al((size_t)ng * 4) * 2 + al(ng) + al((size_t)ng * 8) * 2 + al((size_t)(ng + 1) * 4) + al((size_t)total * 4 + 4) +
-                (g_key ? al((size_t)ng * 4) * 5 : 0);
+                (g_key ? al((size_t)ng * 4) * 5 + al((size_t)ntiles * sizeof(uint4)) : 0);
   if (need > ctx->d_view_cap) {
     if (ctx->d_view) (void)hipFree(ctx->d_view);
     ctx->d_view = nullptr;
@@ -2825,16 +2939,18 @@ int tbk_cov_view_build(tbk_ctx* ctx, const int32_t* r_tid, const int32_t* r_pos,
   uint32_t* o_cig_off = (uint32_t*)take((size_t)(ng + 1) * 4);
   uint32_t* o_cig = (uint32_t*)take((size_t)total * 4 + 4);
   G2cPrep P{};
+  uint4* o_part = nullptr;  // (g_key) per tile of CB_TILE records: the bundle aggregate of the tiles before it
   if (g_key) {  // ... and what the first pass of tbk_coverage_tile would compute from the view (see TbkCtx::view_prep)
     P.start = (int32_t*)take((size_t)ng * 4);
     P.end = (int32_t*)take((size_t)ng * 4);
     P.yi = (int32_t*)take((size_t)ng * 4);
     P.jcnt = (uint32_t*)take((size_t)ng * 4);
     P.ridx = (uint32_t*)take((size_t)ng * 4);
+    o_part = (uint4*)take((size_t)ntiles * sizeof(uint4));
     P.sums = (unsigned long long*)(ctx->d_scalars + 24);
     TBK_HIP(hipMemsetAsync(P.sums, 0, 4 * sizeof(uint64_t), ctx->stream));
-    TBK_LAUNCH(ctx, "g2c_gather", g2c_gather_key_k, (cdiv(ng, B) < 4096u ? cdiv(ng, B) : 4096u), B, 0, ng, g_key, g_yc, g_yx, cfirst, cnt, r_cig, ooff,
-               (uint32_t)total, o_tid, o_pos, o_strand, o_yc, o_yx, o_cig_off, o_cig, P);
+    TBK_LAUNCH(ctx, "g2c_gather", g2c_gather_key_k, ntiles, B, 0, ng, g_key, g_yc, g_yx, cfirst, cnt, r_cig, tbase, part, ntiles, (uint32_t)total,
+               o_tid, o_pos, o_strand, o_yc, o_yx, o_cig_off, o_cig, o_part, P);
     TBK_HIP(hipMemcpyAsync(ctx->h_scalars + 24, ctx->d_scalars + 24, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   } else
     TBK_LAUNCH(ctx, "g2c_gather", g2c_gather_k, cdiv(ng, B), B, 0, ng, g_rep, g_yc, g_yx, r_tid, r_pos, r_strand, cfirst, cnt, r_cig, ooff,
@@ -2860,6 +2976,8 @@ int tbk_cov_view_build(tbk_ctx* ctx, const int32_t* r_tid, const int32_t* r_pos,
     V.yi = P.yi;
     V.jcnt = P.jcnt;
     V.ridx = P.ridx;
+    V.agg = o_part;
+    V.agg_tiles = ntiles;
     V.n_bases = ctx->h_scalars[24];
     V.sum_abs = ctx->h_scalars[25];
     V.err = (uint32_t)ctx->h_scalars[26];

@@ -20,6 +20,7 @@
 // record order exactly as the reference does.
 #include <thread>
 
+#include "cb_tiles.hpp"
 #include "dev_common.hpp"
 #include "scan_op.hpp"
 #include "tbk_internal.h"
@@ -190,25 +191,6 @@ struct BundleStore {
 //   (2) with the aggregate of the records before it, every record knows whether it opens a bundle: heads counted per tile, scanned;
 //   (3) the same walk again, now numbering: bundle of every record, head flags, the bundle table.
 // 32 bytes read and 8 written per record instead of the look-back kernel's waits: 0.53 -> 0.3 ms on config 3.
-struct CbAgg {
-  int32_t first_tid, last_tid;  // last_tid == INT32_MIN: no record
-  int32_t mx;                   // maximum end over the trailing records that share last_tid
-  uint32_t whole;               // every record shares one tid
-};
-struct CbOp {
-  __device__ __forceinline__ CbAgg operator()(const CbAgg& a, const CbAgg& b) const {
-    if (b.last_tid == INT32_MIN) return a;
-    if (a.last_tid == INT32_MIN) return b;
-    CbAgg r;
-    r.first_tid = a.first_tid;
-    r.last_tid = b.last_tid;
-    const bool joins = b.whole && b.first_tid == a.last_tid;
-    r.mx = joins ? (a.mx > b.mx ? a.mx : b.mx) : b.mx;
-    r.whole = joins ? a.whole : 0u;
-    return r;
-  }
-};
-constexpr uint32_t CB_NT = 256, CB_ROWS = 4, CB_TILE = CB_NT * 4 * CB_ROWS;
 __device__ __forceinline__ void cb_load4(const int32_t* __restrict__ a, uint64_t i, uint32_t m, int32_t fill, int32_t v[4]) {
   if (i + 3 < m) {
     const int4 q = *reinterpret_cast<const int4*>(a + i);  // (i is a multiple of 4, the arrays 256-byte aligned)
@@ -216,80 +198,6 @@ __device__ __forceinline__ void cb_load4(const int32_t* __restrict__ a, uint64_t
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = i + e < m ? a[i + e] : fill;
-  }
-}
-template <class T, class Op>
-__device__ __forceinline__ T wave_incl_scan_op(T v, Op op) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T o = shfl_up_t(v, d);
-    if ((int)lane_id() >= d) v = op(o, v);
-  }
-  return v;
-}
-// True in every thread of the block that finishes last; `done` starts at zero.  What the blocks hand to the last one travels without
-// fences: thread 0 writes its block's result with agent-scope stores (cb_put), waits for them to be acknowledged and counts the block;
-// the last block reads the results with agent-scope loads (cb_get).  (A __threadfence per block writes back and invalidates L2: with
-// 6 k blocks it made this pass — and the junction kernels beside it — five times slower.)
-__device__ __forceinline__ void cb_put(uint64_t* p, uint64_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint64_t cb_get(const uint64_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ uint4 cb_get4(const uint4* p) {
-  const uint64_t a = cb_get(reinterpret_cast<const uint64_t*>(p)), b = cb_get(reinterpret_cast<const uint64_t*>(p) + 1);
-  return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
-}
-__device__ __forceinline__ bool cb_last_block(uint32_t* __restrict__ done) {  // (called behind thread 0's cb_put's)
-  __shared__ uint32_t s_last;
-  if (threadIdx.x == 0) {
-    // The block is counted BEHIND its results: they are write-through stores (agent scope), so what orders them before the counter is
-    // the wait for their acknowledgement — stated explicitly: a workgroup-scope release fence compiles to no wait at all here (the
-    // counter could pass the results, and the last block scan entries that were not there yet), an agent-scope release to an L2
-    // write-back per block (buffer_wbl2: 0.37 -> 0.69 ms for the two passes, and the junction kernels beside them as much slower).
-    __builtin_amdgcn_s_waitcnt(TBK_WAIT_VMCNT0);  // vmcnt(0): on gfx9 stores count there too
-    __asm__ volatile("" ::: "memory");
-    s_last = atomicAdd(done, 1u) == gridDim.x - 1u ? 1u : 0u;
-  }
-  __syncthreads();
-  return s_last != 0u;
-}
-// The tile aggregates -> for every tile the aggregate of the tiles before it, by ONE block of NT threads: a slice of the tiles per
-// thread with eight loads in flight at a time, the slices' aggregates by wave scans and one fold of the wave totals.  It runs in the
-// block of cb_agg_k that finishes last (cb_last_block): as a kernel of its own between the passes — one block — it waited for a CU
-// with room while the junction branch's grids filled the GPU (100-200 us of a 1.4 ms coverage call, whatever the streams' priorities).
-template <uint32_t NT>
-__device__ __forceinline__ void cb_spine_block(uint4* __restrict__ part, uint32_t ntiles, CbAgg* wl /* [NT / 64] */) {
-  const CbOp op{};
-  const CbAgg none{0, INT32_MIN, INT32_MIN, 1u};
-  auto un = [](const uint4& v) { return CbAgg{(int32_t)v.x, (int32_t)v.y, (int32_t)v.z, v.w}; };
-  auto pk = [](const CbAgg& a) { return make_uint4((uint32_t)a.first_tid, (uint32_t)a.last_tid, (uint32_t)a.mx, a.whole); };
-  const uint4 none4 = pk(none);
-  const uint32_t per = (ntiles + NT - 1u) / NT, i0 = threadIdx.x * per, i1 = i0 + per < ntiles ? i0 + per : ntiles;
-  CbAgg a = none;
-  for (uint32_t q0 = i0; q0 < i1; q0 += 8u) {
-    uint4 v8[8];
-#pragma unroll
-    for (uint32_t u = 0; u < 8u; ++u) v8[u] = q0 + u < i1 ? cb_get4(part + q0 + u) : none4;
-#pragma unroll
-    for (uint32_t u = 0; u < 8u; ++u) a = op(a, un(v8[u]));
-  }
-  const CbAgg inc = wave_incl_scan_op(a, op);
-  if (lane_id() == 63) wl[threadIdx.x >> 6] = inc;
-  CbAgg run = shfl_up_t(inc, 1);
-  __syncthreads();  // (every slice has been read: the writes below may begin)
-  {
-    CbAgg acc = none;
-    const uint32_t wv = threadIdx.x >> 6;
-    for (uint32_t q = 0; q < wv; ++q) acc = op(acc, wl[q]);
-    run = lane_id() == 0 ? acc : op(acc, run);
-  }
-  for (uint32_t q0 = i0; q0 < i1; q0 += 8u) {
-    uint4 v8[8];
-#pragma unroll
-    for (uint32_t u = 0; u < 8u; ++u) v8[u] = q0 + u < i1 ? cb_get4(part + q0 + u) : none4;
-#pragma unroll
-    for (uint32_t u = 0; u < 8u; ++u) {
-      if (q0 + u < i1) part[q0 + u] = pk(run);
-      run = op(run, un(v8[u]));
-    }
   }
 }
 __global__ __launch_bounds__(CB_NT) void cb_agg_k(uint32_t m, const int32_t* __restrict__ tid, const int32_t* __restrict__ end, uint4* __restrict__ part,
@@ -1953,11 +1861,14 @@ struct JuncSide {  // the junction branch on the side context's worker; collecte
 // ONE read-back (number of bundles, span, spill pieces, spilling records), then spill fill from the list, the tile kernel, a pass
 // over the tiles and the interval writer.  Returns 1 when the tile tables proved too small (the caller then runs the general
 // chain), a negative status on errors.  The interval count is left in scalar 8 for the caller's final read-back.
-static int cov_intervals_lean(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out, CovArrays A, uint32_t m, bool all_valid, uint64_t sum_abs) {
+// `pre_part`: the tiles' aggregates as cb_agg_k leaves them, where the view builder has left them with the view (null: cb_agg_k runs).
+static int cov_intervals_lean(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out, CovArrays A, uint32_t m, bool all_valid, uint64_t sum_abs,
+                              const uint4* pre_part) {
   const uint32_t B = 256;
   uint64_t* sc = ctx->d_scalars;
   const uint32_t cbt = cdiv(m, CB_TILE);
-  uint4* cpart = ws_alloc<uint4>(ctx, cbt);
+  uint4* own_part = pre_part ? nullptr : ws_alloc<uint4>(ctx, cbt);
+  const uint4* cpart = pre_part ? pre_part : own_part;
   uint32_t* hcnt = ws_alloc<uint32_t>(ctx, cbt);
   uint32_t* hbase = ws_alloc<uint32_t>(ctx, cbt);
   long long* xsum = ws_alloc<long long>(ctx, cbt);
@@ -1981,7 +1892,7 @@ static int cov_intervals_lean(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* o
   TBK_HIP(hipMemsetAsync(T.cnt, 0, ((size_t)T.cap + 1) * 4, ctx->stream));
   uint32_t* done = (uint32_t*)(sc + 16);  // [0] cb_agg_k's blocks, [1] cl_heads_k<false>'s: the last one of each runs the scan over the tiles
   TBK_HIP(hipMemsetAsync(done, 0, sizeof(uint64_t), ctx->stream));
-  TBK_LAUNCH(ctx, "cov_bundles", cb_agg_k, cbt, CB_NT, 0, m, A.tid, A.end, cpart, done);
+  if (!pre_part) TBK_LAUNCH(ctx, "cov_bundles", cb_agg_k, cbt, CB_NT, 0, m, A.tid, A.end, own_part, done);
   TBK_LAUNCH(ctx, "cov_bundles", cl_heads_k<false>, cbt, CB_NT, 0, m, A, cpart, hcnt, xsum, (const uint32_t*)nullptr, (const long long*)nullptr, in->cig_off,
              in->cig, T, L, sc, ctx->d_err, done + 1, hbase, xbase);
   TBK_LAUNCH(ctx, "cov_place", cl_heads_k<true>, cbt, CB_NT, 0, m, A, cpart, hcnt, xsum, hbase, xbase, in->cig_off, in->cig, T, L, sc, ctx->d_err,
@@ -2131,7 +2042,8 @@ static int cov_run(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out, bool sa
   bool lean_done = false;
   if (want_cov && !fractional && !sample_mode && !ctx->dbg.cov_legacy && !ctx->dbg.cov_bundle_scan) {
     const size_t ws_mark = ctx->ws_off;
-    const int lrc = cov_intervals_lean(ctx, in, out, A, m, all_valid, sum_abs);
+    const uint4* pre_part = (prepared && V.agg && V.agg_tiles == cdiv(m, CB_TILE)) ? (const uint4*)V.agg : nullptr;
+    const int lrc = cov_intervals_lean(ctx, in, out, A, m, all_valid, sum_abs, pre_part);
     if (lrc < 0) return lrc;
     lean_done = lrc == 0;
     if (!lean_done) {  // tile tables too small for this input: give the arena back and take the general chain

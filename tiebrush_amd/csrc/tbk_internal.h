@@ -142,6 +142,8 @@ struct tbk_ctx {
     uint32_t n = 0;
     int32_t *start = nullptr, *end = nullptr, *yi = nullptr;
     uint32_t *jcnt = nullptr, *ridx = nullptr;
+    const void* agg = nullptr;  // uint4 [agg_tiles], in the view's storage: per tile of 4096 records the bundle aggregate of the tiles before it
+    uint32_t agg_tiles = 0;     // (what cb_agg_k computes from tid and end: the lean interval chain then starts at cl_heads_k)
     uint64_t n_bases = 0, sum_abs = 0, n_junc = 0;  // n_junc: junction items (sum of jcnt)
     uint32_t err = 0;  // TBK_DERR_FATALOP / _NCIGAR (raised only when intervals are wanted) / _FRACTIONAL
   } view_prep;

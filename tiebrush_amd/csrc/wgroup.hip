@@ -359,10 +359,14 @@ __global__ void wg_offsets_edges_k(const uint32_t* __restrict__ run_off, uint32_
 // The stream kernel finds, for one run at a time, consecutive bounds: it writes the matrix run-major (offT[f * nrows + r], whole
 // lines — written bound-major, every word dirtied a line of its own: 1.28 GB of writes for 92 MB of matrix on config 3), and this
 // pass turns it into the bound-major form the window kernels read a row of per window, 64 x 64 words at a time through LDS.
-__global__ __launch_bounds__(256) void wg_offsets_transpose_k(const uint32_t* __restrict__ offT, uint32_t k, uint32_t nrows, uint32_t* __restrict__ off) {
+// `wbase` (k <= 64, one block column: the block holds every run of its 64 rows) — the pass also leaves wbase[r], the records of all runs
+// before row r (wg_rowsum_k's sum, which otherwise reads the matrix back); null: the caller runs wg_rowsum_k.
+__global__ __launch_bounds__(256) void wg_offsets_transpose_k(const uint32_t* __restrict__ offT, uint32_t k, uint32_t nrows, uint32_t* __restrict__ off,
+                                                             uint32_t* __restrict__ wbase) {
   __shared__ uint32_t tile[64][65];
   const uint32_t r0 = blockIdx.x * 64, f0 = blockIdx.y * 64;
   const uint32_t tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const uint32_t start = (wbase && tx < k) ? offT[(size_t)tx * nrows] : 0u;  // row 0 = run starts (f0 = 0)
   for (uint32_t y = ty; y < 64; y += 4) {  // tile[y][x] = offT[f0 + y][r0 + x]
     const uint32_t f = f0 + y, r = r0 + tx;
     if (f < k && r < nrows) tile[y][tx] = offT[(size_t)f * nrows + r];
@@ -370,7 +374,13 @@ __global__ __launch_bounds__(256) void wg_offsets_transpose_k(const uint32_t* __
   __syncthreads();
   for (uint32_t y = ty; y < 64; y += 4) {  // off[r0 + y][f0 + x] = tile[x][y]
     const uint32_t r = r0 + y, f = f0 + tx;
-    if (f < k && r < nrows) off[(size_t)r * k + f] = tile[tx][y];
+    const bool in = f < k && r < nrows;
+    const uint32_t v = in ? tile[tx][y] : 0u;
+    if (in) off[(size_t)r * k + f] = v;
+    if (wbase) {  // (uniform; every lane takes part in the sum)
+      const uint32_t sum = wave_sum(in ? v - start : 0u);
+      if (tx == 0 && r < nrows) wbase[r] = sum;
+    }
   }
 }
 struct WgRaw {                 // raw mode: the window kernels read the records themselves (WgIn::chi / clo / cval / ceff are null)
@@ -534,7 +544,7 @@ struct WgTemp {                // per window, at the window's record base
   unsigned long long* rep;     // min (effend << 32 | record)
   uint32_t* pinc;              // incidence: sample | window-local group << 16
   uint32_t *wg_cnt, *wp_cnt;   // per window: groups, incidences
-  uint32_t* wbase;             // [nw + 1] per window: record base (wg_rowsum_k)
+  uint32_t* wbase;             // [nw + 1] per window: record base (wg_offsets_transpose_k; more than 64 files: wg_rowsum_k)
   uint64_t* fmask;             // (<= 64 files, the YD stage places its items by list: tbk_yd_by_list) the set of a group's files as a
                                // bit mask instead of the incidence list pinc: nothing downstream walks incidences then
   uint32_t* vsrc;              // sparse verification list (WgRaw::sparse): the records ...
@@ -1809,8 +1819,16 @@ struct WgFinal {
   double* yc;
   long long *yxin, *ydin;
   unsigned long long* rep;
+  uint8_t* tie;   // 1: the group opens a (tid, start, strand, end) tie set — it differs from the group before it in hi or in the span
   WgDirectOut D;  // (rep == nullptr: the caller writes its results itself)
 };
+// The tie flag of a group needs the key of the group before it in key order.  Inside a window that is the lane below (or lane 63 of
+// the round before); the FIRST group of a window opens a tie set without a look at the window before: every bound in W is a value of
+// the partition key (wg_split_k: v or v + 1 of a sampled key), the offsets pass puts a record in window w exactly when
+// W[w - 1] <= key < W[w] (wg_offsets_stream_k, both forms), and the partition key is a function of hi alone — hi >> 2 in the compacted
+// form, raw_key(tid, pos) in the raw form and for group partials, where every passing record is mapped and carries
+// hi = (tid + 1, pos + 1, strand) (record_key; tid < 0 folds onto one key, which only makes windows coarser).  Two groups with equal hi
+// therefore have equal partition keys and lie in one window, so the last group of any earlier window differs in hi.
 __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const uint32_t* __restrict__ gbase, const uint32_t* __restrict__ pbase,
                                                    WgFinal F) {
   const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;  // one wave per window (no block-wide step below)
@@ -1818,10 +1836,22 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
   const uint32_t ng = T.wg_cnt[w], np = T.wp_cnt[w];
   if (!ng) return;
   const uint32_t wb = T.wbase[w], gb = gbase[w], pb = pbase[w];
+  uint64_t c_hi = 0;    // lane 63's key of the round before (a further round follows full rounds only)
+  uint32_t c_span = 0;
   for (uint32_t g = lane; g < ng; g += 64) {
     // (every load before the first store: the arrays are not known to be distinct, a load behind a store would wait for its turn)
     const uint32_t sg = gb + g;
     const uint64_t hi = T.hi[wb + g], lo = T.lo[wb + g];
+    const uint32_t span = (uint32_t)(lo >> 32);
+    uint64_t p_hi = __shfl_up((unsigned long long)hi, 1, 64);  // (lane g - 1 is active whenever lane g is)
+    uint32_t p_span = __shfl_up(span, 1, 64);
+    if (lane == 0) {
+      p_hi = c_hi;
+      p_span = c_span;
+    }
+    c_hi = __shfl((unsigned long long)hi, 63, 64);
+    c_span = __shfl(span, 63, 64);
+    const uint8_t tie = (g == 0 || hi != p_hi || span != p_span) ? 1 : 0;
     const unsigned long long r = T.rep[wb + g];
     const uint32_t cnt = T.cnt[wb + g], nsv = T.ns[wb + g];
     const uint64_t fm = F.fmask ? T.fmask[wb + g] : 0ull;
@@ -1833,6 +1863,7 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
     }
     F.ghi[sg] = hi;
     F.glo[sg] = lo;
+    F.tie[sg] = tie;
     F.rep[sg] = r;
     F.gmem[sg] = (uint32_t)(r & 0xFFFFFFFFull);
     F.yc[sg] = (double)cnt;
@@ -1870,11 +1901,6 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
     F.pfile[pb + p] = (uint16_t)pi;
     if (F.pgrp) F.pgrp[pb + p] = gb + (pi >> 16);
   }
-}
-__global__ void wg_tie_k(uint32_t ng, const uint64_t* __restrict__ ghi, const uint64_t* __restrict__ glo, uint8_t* __restrict__ tie) {
-  uint32_t sg = blockIdx.x * blockDim.x + threadIdx.x;
-  if (sg >= ng) return;
-  tie[sg] = (sg == 0 || ghi[sg] != ghi[sg - 1] || (glo[sg] >> 32) != (glo[sg - 1] >> 32)) ? 1 : 0;
 }
 // RAW, sparse list (WgRaw::sparse): one 64-thread block per window walks the window's entries
 __global__ __launch_bounds__(256) void wg_finish_sparse_k(uint32_t nw, const uint32_t* __restrict__ wbase, const uint32_t* __restrict__ vcnt,
@@ -2160,7 +2186,7 @@ bool tbk_window_supported(uint32_t k) { return k >= 1 && k <= 1024; }
 // the offsets matrix of k runs against nW bounds, bound-major in `off` ([nrows * k], nrows = nW + 2)
 static int wg_offsets_build(tbk_ctx* ctx, bool raw, const uint64_t* chi, const int32_t* rtid, const int32_t* rpos, const int32_t* ctid,
                             const uint32_t* d_run_off, uint32_t k,
-                            uint32_t m, const uint64_t* W, uint32_t nW, uint32_t nrows, uint32_t* off) {
+                            uint32_t m, const uint64_t* W, uint32_t nW, uint32_t nrows, uint32_t* off, uint32_t* wbase /* [nrows] */) {
   uint32_t* offT = ws_alloc<uint32_t>(ctx, (size_t)nrows * k);
   if (!offT) return TBK_ENOMEM;
   // chunks per block: eight where that still leaves a few thousand blocks, fewer on small inputs (the owner's side of the multi-rank
@@ -2171,7 +2197,10 @@ static int wg_offsets_build(tbk_ctx* ctx, bool raw, const uint64_t* chi, const i
   else
     TBK_LAUNCH(ctx, "wg_offsets", wg_offsets_stream_k<false>, cdiv(m, WG_OC * og), 256, 0, chi, rtid, rpos, ctid, d_run_off, k, m, W, nW, nrows, offT, ctx->d_err, og);
   TBK_LAUNCH(ctx, "wg_offsets_edges", wg_offsets_edges_k, k, 256, 0, d_run_off, k, nrows, offT);
-  TBK_LAUNCH(ctx, "wg_offsets_transpose", wg_offsets_transpose_k, dim3(cdiv(nrows, 64u), cdiv(k, 64u)), 256, 0, offT, k, nrows, off);
+  // (k <= 64: the transpose sees whole rows and sums them on the way; more runs than one tile holds: a pass of its own)
+  TBK_LAUNCH(ctx, "wg_offsets_transpose", wg_offsets_transpose_k, dim3(cdiv(nrows, 64u), cdiv(k, 64u)), 256, 0, offT, k, nrows, off,
+             k <= 64 ? wbase : nullptr);
+  if (k > 64) TBK_LAUNCH(ctx, "wg_rowsum", wg_rowsum_k, cdiv(nrows, 4), 256, 0, off, k, nrows, wbase);
   return 0;
 }
 
@@ -2227,8 +2256,7 @@ int tbk_partial_reduce_device(tbk_ctx* ctx, int strategy, const int32_t* rows, u
     TBK_LAUNCH(ctx, "pr_sample_rank", pr_sample_rank_k, cdiv(ns, B), B, 0, chi, m, s, ns, d_run_off, k, g, Z);
     TBK_LAUNCH(ctx, "wg_split", wg_split_k, cdiv(nsp, B), B, 0, Z, 1u, nsp, W);
   }
-  TBK_TRY(wg_offsets_build(ctx, false, chi, nullptr, nullptr, nullptr, d_run_off, k, m, W, nW, nrows, off));
-  TBK_LAUNCH(ctx, "wg_rowsum", wg_rowsum_k, cdiv(nrows, 4), 256, 0, off, k, nrows, wbase);
+  TBK_TRY(wg_offsets_build(ctx, false, chi, nullptr, nullptr, nullptr, d_run_off, k, m, W, nW, nrows, off, wbase));
   ColIn I{};
   I.n = m;
   I.k = k;
@@ -2333,8 +2361,10 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
     TBK_TRY(tbk_radix_sort_w64(ctx, &Y, &Y2, ns, ~0ull, false));
     TBK_LAUNCH(ctx, "wg_split", wg_split_k, cdiv(nsp, B), B, 0, Y, g, nsp, W);
   }
-  TBK_TRY(wg_offsets_build(ctx, raw, chi, I.tid, I.pos, ctid, d_run_off, k, m, W, nW, nrows, off));
   WgTemp T;
+  T.wbase = ws_alloc<uint32_t>(ctx, (size_t)nw + 1);
+  if (!T.wbase) return TBK_ENOMEM;
+  TBK_TRY(wg_offsets_build(ctx, raw, chi, I.tid, I.pos, ctid, d_run_off, k, m, W, nW, nrows, off, T.wbase));
   T.hi = scratch_hi;
   T.lo = scratch_lo;
   T.cnt = ws_alloc<uint32_t>(ctx, m);
@@ -2344,7 +2374,6 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   T.pinc = ws_alloc<uint32_t>(ctx, m);
   T.wg_cnt = ws_alloc<uint32_t>(ctx, nw);
   T.wp_cnt = ws_alloc<uint32_t>(ctx, nw);
-  T.wbase = ws_alloc<uint32_t>(ctx, (size_t)nw + 1);
   T.cslot = ws_alloc<uint32_t>(ctx, m);
   T.fmask = nullptr;
   if (raw && !part && k <= 64 && tbk_yd_by_list(ctx, k)) {
@@ -2376,7 +2405,6 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   // LDS of the hash kernel: the pieces' tables (8 k + 4 bytes) and the group table share WG_LDS_HASH (four blocks per CU)
   const uint32_t gcap = (WG_LDS_HASH - (8u * k + 8u)) / (44u + 4u * nwords);
   const uint32_t lds_hash = gcap * (44u + 4u * nwords) + 8u * k + 8u;
-  TBK_LAUNCH(ctx, "wg_rowsum", wg_rowsum_k, cdiv(nrows, 4), 256, 0, off, k, nrows, T.wbase);
   const uint32_t ovf_cap = nw;
   uint32_t* ovf = ws_alloc<uint32_t>(ctx, (size_t)ovf_cap + 1);
   uint32_t* ovf2 = ws_alloc<uint32_t>(ctx, (size_t)ovf_cap + 1);
@@ -2521,9 +2549,8 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   if (!out->tie || (want_rec_sg && !out->rec_sg)) return TBK_ENOMEM;
   if (ng) {
     WgFinal F{out->gfmask, out->ghi, out->glo, out->gmem, out->gpoff, out->pgrp, out->first, out->ns, slot2sg, out->pfile, out->yc, out->yxin,
-              out->ydin, out->rep, (raw && direct) ? *direct : WgDirectOut{}};
+              out->ydin, out->rep, out->tie, (raw && direct) ? *direct : WgDirectOut{}};
     TBK_LAUNCH(ctx, "wg_compact", wg_compact_k, cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F);
-    TBK_LAUNCH(ctx, "wg_tie", wg_tie_k, cdiv(ng, B), B, 0, ng, out->ghi, out->glo, out->tie);
     if (want_rec_sg) TBK_HIP(hipMemsetAsync(out->rec_sg, 0xFF, (size_t)I.n * 4, ctx->stream));  // (records that did not pass)
     if (raw) {  // (nothing to verify and no record -> group map wanted: every key word was exact)
       if (ctx->h_scalars[6] != 0 && R.sparse)
