@@ -478,3 +478,30 @@ def test_literal_yd_machine_on_synthetic_tiles(ctx, profile, strategy, kw, monke
     assert int(np.asarray(got["yd"]).max()) > 0
     tbk_debug(monkeypatch, yd_literal="1", path="window")
     _check(ctx, tile, strategy=strategy, **kw)
+
+
+@pytest.mark.parametrize("scan", ["lookback", "3pass"])
+def test_sort_path_under_each_form_of_the_scan_engine(scan, monkeypatch):
+    """scan= forces one form for every scan_op_run.  A sort-path collapse of 3 * 2048 + 5 passing records — three full tiles of the
+    effective-end scan and a short one, long reads that carry an end across them — under each form, against the oracle; the form that
+    ran shows in the launches under the scan's name: one for the look-back, reduce and down-sweep for the three-launch form (its spine
+    kernel only runs beyond 2048 tiles)"""
+    from helpers import tile_from_records
+    from tiebrush_amd import api
+    rng = np.random.default_rng(41)
+    files = []
+    for m in (2050, 2050, 2049):
+        pos = np.sort(rng.integers(0, 4000, m))
+        files.append([(0, int(p), 0, 60, "+-."[int(rng.integers(0, 3))], 1,
+                       [(int(rng.choice([20, 30, 50, 900])), 0)] if rng.random() < 0.7 else [(15, 0), (int(rng.choice([40, 2500])), 3), (20, 0)]) for p in pos])
+    tile = tile_from_records(files)
+    tbk_debug(monkeypatch, path="sort", scan=scan)
+    c = api.Context(0)
+    c.set_profiling(True)
+    try:
+        _, want = _check(c, tile)
+        assert want["n_passed"] == 3 * 2048 + 5
+        kt = c.kernel_times()
+        assert not any(k.startswith("wg_") for k in kt) and kt["col_effkey_scan"][1] == (1 if scan == "lookback" else 2), kt
+    finally:
+        c.close()

@@ -42,7 +42,7 @@ def test_golden_tiecov(ctx, name, device, bam_loader):
     assert junction_lines(got, names) == read_lines(os.path.join(GOLDEN, name, name + ".junctions.bed"))
 
 
-@pytest.mark.parametrize("bundles", ["lean", "legacy", "scan", "refused", "junc_radix", "junc_overflow"])
+@pytest.mark.parametrize("bundles", ["lean", "legacy", "scan", "refused", "junc_radix", "junc_overflow", "no_junc_agg"])
 @pytest.mark.parametrize("profile,n", [("c2", 100000), ("c3", 60000), ("c5", 60000)])
 def test_synthetic_collapsed(ctx, profile, n, bundles, monkeypatch):
     """(interval chain: the lean one — one read-back, compacted starts from the head sums —, the general one behind it
@@ -60,6 +60,8 @@ def test_synthetic_collapsed(ctx, profile, n, bundles, monkeypatch):
         tbk_debug(monkeypatch, junc_radix="1")
     elif bundles == "junc_overflow":       # ... and a home block with more items than its sort takes: the radix path takes over
         tbk_debug(monkeypatch, jh_cap="2")
+    elif bundles == "no_junc_agg":         # every junction item through the sort: none summed up per read beforehand
+        tbk_debug(monkeypatch, no_junc_agg="1")
     tile = synth.make_tile(3, n, profile, n_loci=3000)
     groups = orc.collapse(tile)
     cin = synth.collapsed_to_cov_input(tile, groups)

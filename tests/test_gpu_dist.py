@@ -372,6 +372,29 @@ def test_shard_prepare_matches_host_restatement_and_rejects_unsorted():
     ctx.close()
 
 
+@pytest.mark.parametrize("scan", ["lookback", "3pass"])
+def test_shard_prepare_under_each_form_of_the_scan_engine(scan, monkeypatch):
+    """scan= forces one form for every scan_op_run: tbk_shard_prepare's running maximum of the read ends (shard_eff_scan) over a tile of
+    several scan tiles under each form, against the numpy restatement; the look-back launches the scan's name once, the three-launch form
+    twice (reduce and down-sweep)"""
+    from tiebrush_amd import api, dist, synth
+    tile = synth.make_tile(3, 2050, "c5", n_loci=40)
+    assert tile.n_records > 3 * 2048
+    kw = dict(max_nh=5, min_qual=1, keep_secondary=True)
+    tbk_debug(monkeypatch, scan=scan)
+    ctx = api.Context(0)
+    ctx.set_profiling(True)
+    try:
+        key, emax, effend, passm = ctx.shard_prepare(api.to_device(tile, "cuda:0"), **kw)
+        kt = ctx.kernel_times()
+        hk, hm, he, hp = dist._prepare_np(tile, **kw)
+        assert np.array_equal(key.cpu().numpy(), hk) and np.array_equal(emax.cpu().numpy(), hm)
+        assert np.array_equal(effend.cpu().numpy(), he) and np.array_equal(passm.cpu().numpy() & 1, hp)
+        assert kt["shard_eff_scan"][1] == (1 if scan == "lookback" else 2), kt
+    finally:
+        ctx.close()
+
+
 def _two_proc_worker(rank, world, port, q, mode):
     import os
     import sys

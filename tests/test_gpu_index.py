@@ -76,6 +76,32 @@ def test_library_part_on_the_synthetic_records(ctx):
     assert [int(t) for t in part["refs"]["tid"]] == [0, 2]
 
 
+@pytest.mark.parametrize("scan", ["lookback", "3pass"])
+def test_library_part_under_each_form_of_the_scan_engine(scan, monkeypatch):
+    """scan= forces one form for every scan_op_run: the running maximum of the record ends (ix_max_scan) over 3 * 2048 + 5 records — three
+    full tiles and a short one, long records that carry their end across them, two references — under each form, against the restatement;
+    the look-back launches the scan's name once, the three-launch form twice (reduce and down-sweep)"""
+    from helpers import tbk_debug
+    from tiebrush_amd import api, bamio
+    n = 3 * 2048 + 5
+    rng = np.random.default_rng(29)
+    ref_len = [200000, 1000, 300000]
+    tid = np.sort(rng.choice([0, 2], n))
+    pos = rng.integers(0, 150000, n)
+    pos = pos[np.lexsort((pos, tid))]
+    recs = {i: bamio.encode_record(int(tid[i]), int(pos[i]), 0, 60, [int(rng.choice([30, 50, 2000, 40000])) << 4], b"r%d" % i)[4:] for i in range(n)}
+    tbk_debug(monkeypatch, scan=scan)
+    c = api.Context(0)
+    c.set_profiling(True)
+    try:
+        run, _, part = c.bam_encode_indexed(np.arange(n, dtype=np.uint32), np.ones(n), np.ones(n), np.zeros(n), ref_len, n_dev=0, host_records=recs)
+        kt = c.kernel_times()
+        check_part(run, part, ref_len)
+        assert kt["ix_max_scan"][1] == (1 if scan == "lookback" else 2), kt
+    finally:
+        c.close()
+
+
 def test_library_refusals_leave_the_context_usable(ctx):
     from tiebrush_amd import bamio
     from tiebrush_amd.api import TbkError

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(256) void rx_bits_k(const uint64_t* __restrict__ hi
 }
 
 // per-tile digit counts -> table[digit * ntiles + tile]
-__global__ __launch_bounds__(RX_NT) void rx_hist_k(const uint64_t* __restrict__ word, uint32_t shift, uint32_t n, uint32_t ntiles,
+__global__ __launch_bounds__(RX_NT) void rx_hist_k(const uint64_t* __restrict__ word, uint32_t digit /*rx_digit_of*/, uint32_t n, uint32_t ntiles,
                                                    uint32_t iter, uint32_t* __restrict__ table) {
   __shared__ uint32_t h[256];
   h[threadIdx.x] = 0;
@@ -252,7 +252,7 @@ __global__ __launch_bounds__(RX_NT) void rx_hist_k(const uint64_t* __restrict__ 
     for (int e = 0; e < RX_E; ++e) {
       uint64_t i = base + (uint64_t)it * RX_SUB + (uint64_t)e * RX_NT + threadIdx.x;
       bool valid = i < n;
-      uint32_t d = (uint32_t)((w[e] >> shift) & 0xFFu);
+      uint32_t d = rx_digit(w[e], digit);
       uint64_t peers = match_digit(d, valid);
       if (valid && (peers & lanemask_lt()) == 0) atomicAdd(&h[d], (uint32_t)__popcll(peers));
     }
@@ -285,7 +285,7 @@ __global__ __launch_bounds__(256) void rx_rowscan_k(uint32_t* __restrict__ table
 __global__ __launch_bounds__(RX_NT) void rx_scatter_k(const uint64_t* __restrict__ hi, const uint64_t* __restrict__ lo,
                                                       const uint32_t* __restrict__ val, uint64_t* __restrict__ hi2,
                                                       uint64_t* __restrict__ lo2, uint32_t* __restrict__ val2, int use_hi,
-                                                      uint32_t shift, uint32_t n, uint32_t ntiles, uint32_t iter,
+                                                      uint32_t digit /*rx_digit_of*/, uint32_t n, uint32_t ntiles, uint32_t iter,
                                                       const uint32_t* __restrict__ table, const uint32_t* __restrict__ totals) {
   __shared__ uint32_t digit_base[256];  // global offset of the next element of each digit for this tile
   __shared__ uint32_t wave_cnt[4][256];
@@ -323,7 +323,7 @@ __global__ __launch_bounds__(RX_NT) void rx_scatter_k(const uint64_t* __restrict
     for (int e = 0; e < RX_E; ++e) {
       uint64_t i = sub_base + (uint64_t)w * (64 * RX_E) + (uint64_t)e * 64 + lane_id();
       bool valid = i < n;
-      uint32_t d = (uint32_t)(((use_hi ? khi[e] : klo[e]) >> shift) & 0xFFu);
+      uint32_t d = rx_digit(use_hi ? khi[e] : klo[e], digit);
       uint64_t peers = match_digit(d, valid);
       uint32_t before = (uint32_t)__popcll(peers & lanemask_lt());
       uint32_t base = valid ? wave_cnt[w][d] : 0u;
@@ -357,7 +357,7 @@ __global__ __launch_bounds__(RX_NT) void rx_scatter_k(const uint64_t* __restrict
       uint32_t cnt_sub = (uint32_t)((n - sub_base) < (uint64_t)RX_SUB ? (n - sub_base) : (uint64_t)RX_SUB);
       for (uint32_t s = t; s < cnt_sub; s += RX_NT) {
         uint64_t h = s_hi[s], l = s_lo[s];
-        uint32_t d = (uint32_t)(((use_hi ? h : l) >> shift) & 0xFFu);
+        uint32_t d = rx_digit(use_hi ? h : l, digit);
         uint32_t g = digit_base[d] + (s - lpos[d]);
         hi2[g] = h;
         lo2[g] = l;
@@ -382,9 +382,9 @@ uint32_t tbk_rx_iter_for(uint32_t n) {
   return it;
 }
 static uint32_t rx_iter_for(uint32_t n) { return tbk_rx_iter_for(n); }
-int tbk_rx_hist_rowscan(tbk_ctx* ctx, const uint64_t* word, uint32_t shift, uint32_t n, uint32_t ntiles, uint32_t iter, uint32_t* table,
+int tbk_rx_hist_rowscan(tbk_ctx* ctx, const uint64_t* word, uint32_t digit, uint32_t n, uint32_t ntiles, uint32_t iter, uint32_t* table,
                         uint32_t* totals) {
-  TBK_LAUNCH(ctx, "rx_hist", rx_hist_k, ntiles, RX_NT, 0, word, shift, n, ntiles, iter, table);
+  TBK_LAUNCH(ctx, "rx_hist", rx_hist_k, ntiles, RX_NT, 0, word, digit, n, ntiles, iter, table);
   TBK_LAUNCH(ctx, "rx_rowscan", rx_rowscan_k, 256, 256, 0, table, ntiles, totals);
   return 0;
 }
@@ -419,10 +419,11 @@ int tbk_radix_sort128(tbk_ctx* ctx, SortBufs* b, uint32_t n, uint64_t only_hi, u
     for (uint32_t shift = 0; shift < 64; shift += 8) {
       if (((vary >> shift) & 0xFFull) == 0) continue;
       const uint64_t* src = word == 0 ? b->lo : b->hi;
-      TBK_LAUNCH(ctx, "rx_hist", rx_hist_k, ntiles, RX_NT, 0, src, shift, n, ntiles, iter, table);
+      const uint32_t digit = rx_digit_of(shift, vary);  // only the varying bits of the mask order the keys: the byte's other bits are payload
+      TBK_LAUNCH(ctx, "rx_hist", rx_hist_k, ntiles, RX_NT, 0, src, digit, n, ntiles, iter, table);
       TBK_LAUNCH(ctx, "rx_rowscan", rx_rowscan_k, 256, 256, 0, table, ntiles, totals);
       TBK_LAUNCH(ctx, "rx_scatter", rx_scatter_k, ntiles, RX_NT, 0, b->hi, b->lo, b->val, b->hi2, b->lo2, b->val2, word,
-                 shift, n, ntiles, iter, table, totals);
+                 digit, n, ntiles, iter, table, totals);
       std::swap(b->hi, b->hi2);
       std::swap(b->lo, b->lo2);
       std::swap(b->val, b->val2);

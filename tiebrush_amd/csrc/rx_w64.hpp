@@ -16,8 +16,8 @@ constexpr int RX_SUB = RX_NT * RX_E;       // 2048
 constexpr int RX_MAX_ITER = 16;            // sub-tiles per tile (runtime choice: tile = RX_SUB * iter)
 
 uint32_t tbk_rx_iter_for(uint32_t n);
-// per-tile digit counts of `word` at `shift` -> table, row scans -> table / totals (prims.hip)
-int tbk_rx_hist_rowscan(tbk_ctx* ctx, const uint64_t* word, uint32_t shift, uint32_t n, uint32_t ntiles, uint32_t iter, uint32_t* table,
+// per-tile digit counts of `word` at `digit` (rx_digit_of below) -> table, row scans -> table / totals (prims.hip)
+int tbk_rx_hist_rowscan(tbk_ctx* ctx, const uint64_t* word, uint32_t digit, uint32_t n, uint32_t ntiles, uint32_t iter, uint32_t* table,
                         uint32_t* totals);
 // the bits of `mask` that differ between some two words (one reduction + one read-back)
 int tbk_rx_vary_bits(tbk_ctx* ctx, const uint64_t* w, uint32_t n, uint64_t mask, uint64_t* vary);
@@ -33,12 +33,18 @@ __device__ __forceinline__ uint64_t match_digit(uint32_t d, bool valid) {
   return peers;
 }
 
+// A pass's digit travels as one word: the shift in its low byte, above it the bits of that byte that take part in the ordering.  A mask
+// may end inside a byte (collapse.hip's YD split, baix.hip's index sort); the byte's other bits are payload, and a digit that took
+// them in would reorder equal keys.
+__host__ __device__ __forceinline__ uint32_t rx_digit_of(uint32_t shift, uint64_t vary) { return shift | ((uint32_t)((vary >> shift) & 0xFFull) << 8); }
+__device__ __forceinline__ uint32_t rx_digit(uint64_t w, uint32_t digit) { return (uint32_t)(w >> (digit & 0xFFu)) & (digit >> 8); }
+
 struct RxNoEmit {
   __device__ __forceinline__ void operator()(uint32_t, uint64_t) const {}
 };
 
 template <class Emit>
-__global__ __launch_bounds__(RX_NT) void w64_scatter_k(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t shift, uint32_t n,
+__global__ __launch_bounds__(RX_NT) void w64_scatter_k(const uint64_t* __restrict__ in, uint64_t* __restrict__ out, uint32_t digit /*rx_digit_of*/, uint32_t n,
                                                        uint32_t ntiles, uint32_t iter, const uint32_t* __restrict__ table,
                                                        const uint32_t* __restrict__ totals, int do_emit, Emit emit) {
   __shared__ uint32_t digit_base[256];
@@ -71,7 +77,7 @@ __global__ __launch_bounds__(RX_NT) void w64_scatter_k(const uint64_t* __restric
     for (int e = 0; e < RX_E; ++e) {
       uint64_t i = sub_base + (uint64_t)w * (64 * RX_E) + (uint64_t)e * 64 + lane_id();
       bool valid = i < n;
-      uint32_t d = (uint32_t)((kk[e] >> shift) & 0xFFu);
+      uint32_t d = rx_digit(kk[e], digit);
       uint64_t peers = match_digit(d, valid);
       uint32_t before = (uint32_t)__popcll(peers & lanemask_lt());
       uint32_t base = valid ? wave_cnt[w][d] : 0u;
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(RX_NT) void w64_scatter_k(const uint64_t* __restric
     uint32_t cnt_sub = (uint32_t)((n - sub_base) < (uint64_t)RX_SUB ? (n - sub_base) : (uint64_t)RX_SUB);
     for (uint32_t q = t; q < cnt_sub; q += RX_NT) {
       uint64_t kq = s_w[q];
-      uint32_t d = (uint32_t)((kq >> shift) & 0xFFu);
+      uint32_t d = rx_digit(kq, digit);
       const uint32_t g = digit_base[d] + (q - lpos[d]);
       out[g] = kq;
       if (do_emit) emit(g, kq);
@@ -139,8 +145,9 @@ int tbk_radix_sort_w64_emit(tbk_ctx* ctx, uint64_t** w, uint64_t** w2, uint32_t 
     if (((vary >> shift) & 0xFFull) != 0) last = (int)shift;
   for (uint32_t shift = 0; shift < 64; shift += 8) {
     if (((vary >> shift) & 0xFFull) == 0) continue;
-    TBK_TRY(tbk_rx_hist_rowscan(ctx, *w, shift, n, ntiles, iter, table, totals));
-    TBK_LAUNCH(ctx, scatter_name, (w64_scatter_k<Emit>), ntiles, RX_NT, 0, *w, *w2, shift, n, ntiles, iter, table, totals,
+    const uint32_t digit = rx_digit_of(shift, vary);
+    TBK_TRY(tbk_rx_hist_rowscan(ctx, *w, digit, n, ntiles, iter, table, totals));
+    TBK_LAUNCH(ctx, scatter_name, (w64_scatter_k<Emit>), ntiles, RX_NT, 0, *w, *w2, digit, n, ntiles, iter, table, totals,
                (has_emit && (int)shift == last) ? 1 : 0, emit);
     std::swap(*w, *w2);
   }

@@ -334,6 +334,11 @@ extern "C" int tbk_shard_prepare(tbk_ctx* ctx, const tbk_collapse_opts* o, const
   TBK_HIP(hipSetDevice(ctx->device));
   const uint32_t n = in->n_records;
   if (n == 0) return 0;
+  tbk_prof_begin_call(ctx);  // (without the brackets a profiled context kept this call's events for ever and tbk_kernel_times never named its kernels)
+  struct ProfEnd {
+    tbk_ctx* c;
+    ~ProfEnd() { tbk_prof_end_call(c); }
+  } prof_end{ctx};
   TBK_TRY(tbk_ws_reserve(ctx, (size_t)n * 16 + ((size_t)1 << 20)));
   uint64_t* sc = ctx->d_scalars;
   TBK_HIP(hipMemsetAsync(sc, 0, 16 * sizeof(uint64_t), ctx->stream));

@@ -287,7 +287,8 @@ struct SortBufs {
   uint64_t *hi2, *lo2;
   uint32_t* val2;
 };
-// only_hi / only_lo: bits that take part in the ordering (the rest are payload that must not reorder equal keys).
+// only_hi / only_lo: bits that take part in the ordering (the rest are payload that must not reorder equal keys; a mask may end inside a
+// byte: every pass takes only the mask's bits of its digit).
 // masks_are_exact: the caller knows which bits can differ (e.g. a small id range) — no scan of the keys, no read-back
 int tbk_radix_sort128(tbk_ctx* ctx, SortBufs* b, uint32_t n, uint64_t only_hi = ~0ull, uint64_t only_lo = ~0ull,
                       bool masks_are_exact = false);
