@@ -56,6 +56,17 @@ int tbh_csi_depth(uint64_t max_len);
  * interval that is empty or not inside [0, 2^(14 + 3 depth)] */
 uint32_t tbh_csi_reg2bin(int64_t beg, int64_t end, int depth);
 
+/* The region query behind `tiecov -r` (csrc/host/bai_read.h): the chunks a reader of the 0-based half-open [beg, end)
+ * on reference tid has to read, through the index at index_path (NULL: bam_path + ".csi", bam_path + ".bai", then the .bai beside
+ * the file's stem, the first that exists; BAI or CSI by its magic).  The chunks are sorted and disjoint: the bins of reg2bins minus
+ * the pseudo / meta bin, chunks that end at or before the linear index's (the bin's loff) offset dropped, neighbours that overlap,
+ * touch or meet in one BGZF member merged.  Returns the number of chunks; they are written as virtual offsets to chunk_beg /
+ * chunk_end when that number is <= cap (otherwise nothing is written: call again with room).  -1 on failure (tbh_last_error): no
+ * index, an index whose n_ref is not the header's, a truncated index, tid / beg / end out of range.
+ * The reference reads no region and no index (tiecov.cpp walks the whole file): this replaces no interface of it. */
+int64_t tbh_index_query(const char* bam_path, const char* index_path, int32_t tid, int64_t beg, int64_t end, uint64_t* chunk_beg, uint64_t* chunk_end,
+                        uint64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

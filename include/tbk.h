@@ -541,6 +541,42 @@ int tbk_track_names(tbk_ctx* ctx, uint32_t n_names, const uint64_t* off, const c
  * takes slice k (TBK_DEBUG fmt_slice=BYTES sets the slice size, default 32 MiB). */
 int tbk_format_track(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes);
 
+/* ---- The tracks of one region (ABI version 8, appended) -------------------------------------------------------------
+ * What `tiecov -r REGION` runs on the chunks the output's index (.bai / .csi) names for the region.  The reference has no region
+ * option and reads no index — tiecov.cpp:435-499 walks every record through GSamReader::next (GSam.h:506-516) — so these entries
+ * replace no interface of it; the contract is that the rows equal the rows of its whole-file run on the region, bit for bit. */
+
+/* tbk_bam_decode for record streams that do not start at a BAM header.  Span s is a run of whole BGZF members (comp[s] /
+ * comp_bytes[s], host memory); its records are the inflated bytes from offset first_uoff[s] of the first member's payload up to
+ * offset last_uoff[s] of the last member's payload (0: the end of the last member), whole records back to back, which may straddle
+ * members.  n_ref is the header's reference count (a refID outside [-1, n_ref) is TBK_EINVAL, as in a file).  The kernels are
+ * tbk_bam_decode's without the header pass; YC / YX are read for every record.  *tile describes a DEVICE tile in context-owned memory
+ * (valid until tbk_bam_release or the next decode) whose "files" are the spans: span_off_out[n_spans + 1] (host, caller's) receives
+ * their record ranges and is what tile->file_off points to.  *tag_seen_out = a DEVICE array [n_records] in the same memory: bit 0 set
+ * when the record carries YC, bit 1 when it carries YX (tile->yc_in alone is 0.0 for an absent tag and for YC:f:0).
+ * TBK_EINVAL for an offset outside its member, a block_size below 32, a record that runs past its span's end — nothing faults and the
+ * context takes the next call.  n_spans == 0, or spans without payload, give an empty tile and status 0. */
+int tbk_bam_decode_spans(tbk_ctx* ctx, uint32_t n_spans, const uint8_t* const* comp, const uint64_t* comp_bytes, const uint32_t* first_uoff,
+                         const uint32_t* last_uoff, int32_t n_ref, tbk_soa_in* tile, uint32_t* span_off_out, const uint8_t** tag_seen_out);
+
+/* The records of a DEVICE tile that overlap [beg, end) (0-based, half-open) on reference tid, in file order, as tiecov's input:
+ * record i is kept when tile->tid[i] == tid && pos < end && rec_end > beg, rec_end = pos + the CIGAR's reference length over
+ * M D N = X, pos + 1 when that is 0 (the index's own rule).  view->yc / view->yx are the tags where tag_seen says they
+ * are present and 1.0 / 1 where not (tiecov.cpp:482-485); tag_seen == NULL: tile->yc_in / yx_in as they are, 1.0 / 1 when those are
+ * NULL.  The view lives in context-owned device memory, valid until the next tbk_region_view / tbk_groups_to_cov_in on ctx (it
+ * survives tbk_coverage_tile, tbk_sample_tile and the clips).  *n_kept = view->n_records. */
+int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, int32_t tid, int64_t beg, int64_t end, tbk_cov_in* view,
+                    uint32_t* n_kept);
+
+/* Cut the rows of a tbk_coverage_tile call to [beg, end) on tid, in place (rows->mem HOST or DEVICE), and rewrite n_intervals /
+ * n_junctions.  Interval rows outside the region are dropped, a row across an edge is trimmed to it and keeps its value.  Junction
+ * rows are kept whole when j_start < end && j_end > beg, in their order (the caller numbers them from 1).  tbk_sample_clip: the same
+ * for the rows of tbk_sample_tile.  TBK_EINVAL for interval rows that are not sorted by (tid, start).
+ * (With these entries tbk_coverage_tile / tbk_sample_tile also take a DEVICE input with HOST output arrays: the rows are computed on
+ * the device and copied back.) */
+int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end);
+int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, int64_t beg, int64_t end);
+
 #ifdef __cplusplus
 }
 #endif

@@ -27,7 +27,8 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_collapse_opts_default", "tbk_collapse_tile", "tbk_collapse_finish_yd", "tbk_coverage_tile", "tbk_sample_tile",
            "tbk_groups_to_cov_in", "tbk_bgzf_inflate", "tbk_bam_decode", "tbk_bam_records", "tbk_bam_release", "tbk_shard_prepare", "tbk_shard_probe_max", "tbk_shard_probe_next",
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
-           "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed"]
+           "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
+           "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip"]
 
 
 class CollapseOpts(C.Structure):
@@ -192,6 +193,14 @@ def load():
     L.tbk_track_names.restype = C.c_int
     L.tbk_format_track.argtypes = [_P, C.POINTER(TrackRows), TRACK_SINK, _P, C.POINTER(C.c_uint64)]
     L.tbk_format_track.restype = C.c_int
+    L.tbk_bam_decode_spans.argtypes = [_P, C.c_uint32, _P, _P, _P, _P, C.c_int32, C.POINTER(SoaIn), _P, C.POINTER(_P)]
+    L.tbk_bam_decode_spans.restype = C.c_int
+    L.tbk_region_view.argtypes = [_P, C.POINTER(SoaIn), _P, C.c_int32, C.c_int64, C.c_int64, C.POINTER(CovIn), C.POINTER(C.c_uint32)]
+    L.tbk_region_view.restype = C.c_int
+    L.tbk_cov_clip.argtypes = [_P, C.POINTER(CovOut), C.c_int32, C.c_int64, C.c_int64]
+    L.tbk_cov_clip.restype = C.c_int
+    L.tbk_sample_clip.argtypes = [_P, C.POINTER(SampleOut), C.c_int32, C.c_int64, C.c_int64]
+    L.tbk_sample_clip.restype = C.c_int
     _lib = L
     return L
 
@@ -199,7 +208,7 @@ def load():
 # (TBK_HOST_LIB: the sanitizer builds of tools/san_check.sh)
 HOST_LIB_PATH = os.environ.get("TBK_HOST_LIB") or os.path.join(_HERE, "_build", "libtbh.so")
 HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin",
-                "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin"]   # include/tbh_host.h
+                "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin", "tbh_index_query"]   # include/tbh_host.h
 _host = None
 
 
@@ -230,6 +239,8 @@ def load_host():
     H.tbh_csi_depth.restype = C.c_int
     H.tbh_csi_reg2bin.argtypes = [C.c_int64, C.c_int64, C.c_int]
     H.tbh_csi_reg2bin.restype = C.c_uint32
+    H.tbh_index_query.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_uint64]
+    H.tbh_index_query.restype = C.c_int64
     _host = H
     return H
 

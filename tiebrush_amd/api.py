@@ -459,6 +459,67 @@ class Context:
         self._bam_keep = (bufs, tb, fo)
         return s, fo
 
+    def bam_decode_spans(self, spans, n_ref):
+        """tbk_bam_decode_spans: spans = [(bytes of whole BGZF members, first_uoff, last_uoff)] -> (SoaIn struct of the device-resident
+        tile, span_off [n_spans + 1], tag_seen: device pointer of the per-record YC / YX presence bits, or None).  The arrays live in the
+        context until bam_release() or the next decode."""
+        k = len(spans)
+        bufs = [np.frombuffer(z, dtype=np.uint8) for z, _, _ in spans]
+        ptrs = (C.c_void_p * max(k, 1))(*[b.ctypes.data if len(b) else None for b in bufs])
+        sizes = np.array([len(b) for b in bufs], dtype=np.uint64)
+        fu = np.array([s[1] for s in spans], dtype=np.uint32)
+        lu = np.array([s[2] for s in spans], dtype=np.uint32)
+        so = np.zeros(k + 1, dtype=np.uint32)
+        s, seen = _lib.SoaIn(), C.c_void_p()
+        self._check(self.L.tbk_bam_decode_spans(self.h, k, ptrs, sizes.ctypes.data, fu.ctypes.data, lu.ctypes.data, int(n_ref), C.byref(s), so.ctypes.data,
+                                                C.byref(seen)), "tbk_bam_decode_spans")
+        self._bam_keep = (bufs, so)
+        return s, so, seen.value
+
+    def region_view(self, tile_struct, tag_seen, tid, beg, end) -> DeviceCovView:
+        """tbk_region_view: the records of a device tile (bam_decode_spans / bam_decode) overlapping [beg, end) on tid, as tiecov's input"""
+        v, nk = _lib.CovIn(), C.c_uint32(0)
+        self._check(self.L.tbk_region_view(self.h, C.byref(tile_struct), tag_seen, int(tid), int(beg), int(end), C.byref(v), C.byref(nk)), "tbk_region_view")
+        assert int(nk.value) == int(v.n_records)
+        return DeviceCovView(v, int(v.n_records), int(v.n_cigar_ops))
+
+    def cov_clip(self, res, tid, beg, end):
+        """tbk_cov_clip: the result dict of coverage() cut to [beg, end) on tid (numpy rows or device tensors), as a new dict"""
+        keep = []
+        dev = any(_is_torch(res.get(k)) for k in ("iv_tid", "j_tid"))
+        a, b = (len(res["iv_tid"]) if "iv_tid" in res else 0), (len(res["j_tid"]) if "j_tid" in res else 0)
+        own = {k: (v.clone() if _is_torch(v) else np.array(v, copy=True)) for k, v in res.items() if k[:3] == "iv_" or k[:2] == "j_"}
+
+        def ptr(name, dt):
+            return _addr(own[name], dt, keep) if name in own and _numel(own[name]) else None
+        o = _lib.CovOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, a, ptr("iv_tid", np.int32), ptr("iv_start", np.int32), ptr("iv_end", np.int32),
+                        ptr("iv_val", np.float64), b, ptr("j_tid", np.int32), ptr("j_start", np.int32), ptr("j_end", np.int32), ptr("j_strand", np.uint8),
+                        ptr("j_val", np.float64), a, b, 0, 0)
+        self._order_after_torch(dev)
+        self._check(self.L.tbk_cov_clip(self.h, C.byref(o), int(tid), int(beg), int(end)), "tbk_cov_clip")
+        out = dict(n_intervals=int(o.n_intervals), n_junctions=int(o.n_junctions))
+        for k, v in own.items():
+            out[k] = v[:out["n_intervals"] if k[:3] == "iv_" else out["n_junctions"]]
+        return out
+
+    def sample_clip(self, res, tid, beg, end):
+        """tbk_sample_clip: the result dict of sample() cut to [beg, end) on tid, as a new dict"""
+        keep = []
+        dev = _is_torch(res["s_tid"])
+        a = len(res["s_tid"])
+        own = {k: (v.clone() if _is_torch(v) else np.array(v, copy=True)) for k, v in res.items() if k[:2] == "s_"}
+
+        def ptr(name, dt):
+            return _addr(own[name], dt, keep) if a else None
+        o = _lib.SampleOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, a, ptr("s_tid", np.int32), ptr("s_start", np.int32), ptr("s_end", np.int32),
+                           ptr("s_count", np.int64), ptr("s_heat", np.float32), a)
+        self._order_after_torch(dev)
+        self._check(self.L.tbk_sample_clip(self.h, C.byref(o), int(tid), int(beg), int(end)), "tbk_sample_clip")
+        m = int(o.n_intervals)
+        out = {k: v[:m] for k, v in own.items()}
+        out["n_sample"] = m
+        return out
+
     def bam_records(self, idx):
         """tbk_bam_records: (bytes of the packed records, offsets [n+1])"""
         idx = np.ascontiguousarray(idx, dtype=np.uint32)
@@ -841,13 +902,18 @@ class Context:
 
     def sample(self, cin: CovInput, num_samples: int, cap_intervals=None):
         keep = []
-        dev = _is_torch(cin.tid)
-        n = _numel(cin.tid)
-        nc = _numel(cin.cig)
-        s = _lib.CovIn(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, n, nc, _addr(cin.tid, np.int32, keep, n),
-                       _addr(cin.pos, np.int32, keep, n), _addr(cin.flag, np.uint16, keep, n),
-                       _addr(cin.cig_off, np.uint32, keep, n + 1), _addr(cin.cig, np.uint32, keep, nc), None, None,
-                       _addr(cin.yx, np.int64, keep, n))
+        if isinstance(cin, DeviceCovView):                      # (region_view / groups_to_cov_in: the view carries yx)
+            s, dev = cin.struct, True
+            if cap_intervals is None:
+                cap_intervals = 2 * cin.n_cigar_ops + 2 * cin.n_records + 16
+        else:
+            dev = _is_torch(cin.tid)
+            n = _numel(cin.tid)
+            nc = _numel(cin.cig)
+            s = _lib.CovIn(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, n, nc, _addr(cin.tid, np.int32, keep, n),
+                           _addr(cin.pos, np.int32, keep, n), _addr(cin.flag, np.uint16, keep, n),
+                           _addr(cin.cig_off, np.uint32, keep, n + 1), _addr(cin.cig, np.uint32, keep, nc), None, None,
+                           _addr(cin.yx, np.int64, keep, n))
         if cap_intervals is None:
             if dev:
                 raise ValueError("cap_intervals is required for device inputs")
@@ -893,6 +959,22 @@ class Context:
         text = b"".join(parts)
         assert len(text) == total.value
         return text
+
+
+def index_query(bam_path, tid, beg, end, index_path=None):
+    """tbh_index_query: the chunks [(vbeg, vend)] a reader of [beg, end) on reference tid has to read, through the file's index
+    (index_path None: PATH.csi, PATH.bai, then the .bai beside the stem).  Host only."""
+    H = _lib.load_host()
+    ip = None if index_path is None else os.fsencode(index_path)
+    cap = 64
+    while True:
+        cb, ce = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+        n = H.tbh_index_query(os.fsencode(bam_path), ip, int(tid), int(beg), int(end), cb.ctypes.data, ce.ctypes.data, cap)
+        if n < 0:
+            raise RuntimeError((H.tbh_last_error() or b"").decode())
+        if n <= cap:
+            return [(int(cb[i]), int(ce[i])) for i in range(n)]
+        cap = int(n)
 
 
 def to_numpy(d):

@@ -683,7 +683,8 @@ __global__ __launch_bounds__(IDX_NT) void bam_index_k(const uint8_t* __restrict_
 //   bam_imem_count_k: records per member;  bam_imem_scan_k: per file, the members' counts -> offsets, the file's total;
 //   bam_imem_emit_k: the walks again, writing rec[cap_off[f] + offset + i]
 __device__ __forceinline__ uint32_t bam_imem_walk(const uint8_t* __restrict__ inf, const BgzMember& M, uint64_t s0, uint64_t fend, uint64_t* out, bool* aligned) {
-  const uint64_t end = M.dst + M.isize;
+  const uint64_t mend = M.dst + M.isize;
+  const uint64_t end = mend < fend ? mend : fend;  // (a span of tbk_bam_decode_spans may end inside its last member; a file ends with one)
   uint64_t p = M.dst > s0 ? M.dst : s0;
   uint32_t c = 0;
   bool ok = true;
@@ -751,6 +752,7 @@ struct BamSoA {
   int64_t *yx, *yd;
   uint32_t *nmd, *nqn; // MD / name byte counts (optional)
   uint8_t* md_has;
+  uint8_t* seen;       // (optional) bit 0: the record carries YC, bit 1: YX — yc / yx alone cannot tell an absent tag from YC:f:0
 };
 
 // one thread per record: validation as the host loader's (bam.cpp index_records), core fields, one aux scan
@@ -879,6 +881,7 @@ __global__ void bam_fields_k(uint32_t n, const uint8_t* __restrict__ inf, const 
     S.yx[i] = yx;
     S.yd[i] = yd;
   }
+  if (S.seen) S.seen[i] = (uint8_t)((seen >> 3) & 3u);
   if (want_md) {
     S.nmd[i] = nmd;
     S.md_has[i] = md_has;
@@ -986,6 +989,7 @@ struct BamDev {
   uint64_t* rec = nullptr;     // [n] offset of every record (its block_size field) in `inf`
   uint32_t n = 0;
   std::vector<void*> owned;    // device allocations of the decoded tile
+  std::vector<uint8_t> tbm_host;  // tbk_bam_decode_spans: what tile->tbmerged points to
 };
 
 }  // namespace
@@ -1109,8 +1113,18 @@ static T* bd_alloc(BamDev* B, size_t n) {
   return (T*)p;
 }
 
-extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const* comp, const uint64_t* comp_bytes, const uint8_t* tbmerged,
-                              int want_md, int want_names, tbk_soa_in* tile, uint32_t* file_off_out) {
+namespace {
+// tbk_bam_decode_spans: the "files" are record streams cut out of a file — no BAM header, the first record at first_uoff[f] of the
+// first member's payload, the stream's end at last_uoff[f] of the last member's (0: where that member ends)
+struct SpanArgs {
+  const uint32_t *first_uoff, *last_uoff;
+  int32_t n_ref;             // the header's: what bam_header_k reads from a file
+  const uint8_t** seen_out;  // device [n_records]: BamSoA::seen
+};
+}  // namespace
+
+static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const* comp, const uint64_t* comp_bytes, const uint8_t* tbmerged, int want_md,
+                           int want_names, tbk_soa_in* tile, uint32_t* file_off_out, const SpanArgs* sp) {
   if (!ctx || !comp || !comp_bytes || !tile || !file_off_out || n_files == 0 || n_files > 65535) return TBK_EINVAL;
   TBK_HIP(hipSetDevice(ctx->device));
   TBK_TRY(tbk_collapse_finish_yd(ctx));  // (a deferred YD stage may still read the tile of the previous decode)
@@ -1120,7 +1134,8 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
   // ---- member table of every file (the files are walked side by side: a mapping of the page cache faults its pages in as the walk
   // touches them); inflated streams laid out file after file, 256-byte aligned ----
   std::vector<BgzMember> mt;
-  std::vector<uint64_t> cbase(k + 1, 0), fbase(k, 0), fbytes(k, 0);
+  std::vector<uint64_t> cbase(k + 1, 0), fbase(k, 0), fbytes(k, 0), first(k, 0);
+  std::vector<uint32_t> isz_first(k, 0), isz_last(k, 0);  // payload bytes of every file's first and last member
   uint64_t ctot = 0, itot = 0;
   {
     std::vector<std::vector<BgzMember>> fm(k);
@@ -1160,6 +1175,8 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
           if (m.isize > 65536) break;
           m.dst = isz;
           m.file = f;
+          if (off == 0) isz_first[f] = m.isize;
+          isz_last[f] = m.isize;
           isz += m.isize;
           if (m.isize) fm[f].push_back(m);
           off += (uint64_t)bsize + 1;
@@ -1189,9 +1206,24 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
       itot += fi[f];
       fbytes[f] = fi[f];
       ctot += comp_bytes[f];
+      if (sp) {  // (what the kernels cannot see: an offset outside its member)
+        if (sp->first_uoff[f] > isz_first[f] || sp->last_uoff[f] > isz_last[f]) return TBK_EINVAL;
+        if (sp->last_uoff[f]) fbytes[f] = fi[f] - isz_last[f] + sp->last_uoff[f];
+        first[f] = sp->first_uoff[f];
+        if (first[f] > fbytes[f]) return TBK_EINVAL;
+      }
     }
   }
   cbase[k] = ctot;
+  if (mt.empty() && sp) {  // spans without payload: an empty tile
+    memset(tile, 0, sizeof(*tile));
+    tile->mem = TBK_MEM_DEVICE;
+    tile->n_files = k;
+    tile->file_off = file_off_out;
+    for (uint32_t f = 0; f <= k; ++f) file_off_out[f] = 0;
+    *sp->seen_out = nullptr;
+    return 0;
+  }
   if (mt.empty()) {
     memset(tile, 0, sizeof(*tile));
     for (uint32_t f = 0; f <= k; ++f) file_off_out[f] = 0;
@@ -1216,8 +1248,8 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
   TBK_HIP(hipMemcpyAsync(d_tab, fbase.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
   TBK_HIP(hipMemcpyAsync(d_tab + k, fbytes.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
   TBK_HIP(hipMemcpyAsync(d_tab + 3 * k, cap_off.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
-  std::vector<uint8_t> tb(k, 0);
-  if (tbmerged) memcpy(tb.data(), tbmerged, k);
+  std::vector<uint8_t> tb(k, sp ? 1 : 0);  // (spans: YC / YX of every record are read)
+  if (tbmerged && !sp) memcpy(tb.data(), tbmerged, k);
   TBK_HIP(hipMemcpyAsync(d_tbm, tb.data(), k, hipMemcpyHostToDevice, ctx->stream));
   TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
   // the files go up in groups of ~ 192 MB through the pinned ring, and a group is inflated while the next one is on its way
@@ -1241,7 +1273,14 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
       f0 = f1;
     }
   }
-  TBK_LAUNCH(ctx, "bam_header", bam_header_k, cdiv(k, 64), 64, 0, k, B->inf, d_tab, d_tab + k, d_tab + 2 * k, d_nref, ctx->d_err);
+  std::vector<int32_t> nref_h;
+  if (sp) {
+    nref_h.assign(k, sp->n_ref);
+    TBK_HIP(hipMemcpyAsync(d_tab + 2 * k, first.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
+    TBK_HIP(hipMemcpyAsync(d_nref, nref_h.data(), k * 4, hipMemcpyHostToDevice, ctx->stream));
+  } else {
+    TBK_LAUNCH(ctx, "bam_header", bam_header_k, cdiv(k, 64), 64, 0, k, B->inf, d_tab, d_tab + k, d_tab + 2 * k, d_nref, ctx->d_err);
+  }
   // the record index: a lane per member where every member begins with a record (htslib's writers), the chain per file otherwise
   std::vector<uint32_t> cnt(k, 0);
   uint32_t eb = 0;
@@ -1310,6 +1349,10 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
     S.yx = bd_alloc<int64_t>(B, n);
     S.yd = bd_alloc<int64_t>(B, n);
   }
+  if (sp) {
+    S.seen = bd_alloc<uint8_t>(B, n);
+    if (!S.seen) return TBK_ENOMEM;
+  }
   uint32_t *md_off = nullptr, *qn_off = nullptr;
   if (want_md) {
     S.nmd = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
@@ -1368,6 +1411,11 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
   tile->n_cigar_ops = (uint32_t)ncig;
   tile->file_off = file_off_out;
   tile->tbmerged = tbmerged;
+  if (sp) {
+    B->tbm_host = tb;
+    tile->tbmerged = B->tbm_host.data();
+    *sp->seen_out = S.seen;
+  }
   tile->tid = S.tid;
   tile->pos = S.pos;
   tile->flag = S.flag;
@@ -1389,6 +1437,29 @@ extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* con
   // (the arena for the collapse of this tile is the caller's to reserve — tbk_reserve_tile —: it knows whether the tile will be joined
   // with a host part first, and an allocation of gigabytes is now and then 0.1 s of the driver's time: one, not two)
   return tbk_check_launch(ctx, "bam_decode");
+}
+
+extern "C" int tbk_bam_decode(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const* comp, const uint64_t* comp_bytes, const uint8_t* tbmerged,
+                              int want_md, int want_names, tbk_soa_in* tile, uint32_t* file_off_out) {
+  return bam_decode_impl(ctx, n_files, comp, comp_bytes, tbmerged, want_md, want_names, tile, file_off_out, nullptr);
+}
+
+extern "C" int tbk_bam_decode_spans(tbk_ctx* ctx, uint32_t n_spans, const uint8_t* const* comp, const uint64_t* comp_bytes, const uint32_t* first_uoff,
+                                    const uint32_t* last_uoff, int32_t n_ref, tbk_soa_in* tile, uint32_t* span_off_out, const uint8_t** tag_seen_out) {
+  if (!ctx || !tile || !span_off_out || !tag_seen_out || n_ref < 0) return TBK_EINVAL;
+  if (n_spans == 0) {  // no chunk: an empty tile (the tile of an earlier decode is released, as by every decode)
+    TBK_TRY(tbk_collapse_finish_yd(ctx));
+    tbk_bam_release(ctx);
+    memset(tile, 0, sizeof(*tile));
+    tile->mem = TBK_MEM_DEVICE;
+    tile->file_off = span_off_out;
+    span_off_out[0] = 0;
+    *tag_seen_out = nullptr;
+    return 0;
+  }
+  if (!first_uoff || !last_uoff) return TBK_EINVAL;
+  SpanArgs sp{first_uoff, last_uoff, n_ref, tag_seen_out};
+  return bam_decode_impl(ctx, n_spans, comp, comp_bytes, nullptr, 0, 0, tile, span_off_out, &sp);
 }
 
 namespace {

@@ -1936,7 +1936,10 @@ static int cov_intervals_lean(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* o
   TBK_LAUNCH(ctx, "cov_tile", (cov_tile_k<ACC, ID, true>), ntiles, COVT_NT, 0, m, S, A, in->cig_off, in->cig, in->yc, T.first, tile_off, \
              sp_seg, sp_rec, cp_pos, cp_val, tile_cp_base, tile_cp_cnt, cp_alloc, cp_cap, ctx->d_err, O)
   const bool small = sum_abs < (1ull << 31);  // int32 accumulators when the depth cannot overflow them
-  if (small && all_valid)
+  // (ntiles == 0: records without a covered base only — I and S and nothing else, the whole input of a narrow `tiecov -r` — give no
+  // tile and no row; a launch of no blocks is an error)
+  if (!ntiles) {
+  } else if (small && all_valid)
     COV_TILE_LAUNCH(int32_t, true);
   else if (small)
     COV_TILE_LAUNCH(int32_t, false);
@@ -1945,10 +1948,11 @@ static int cov_intervals_lean(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* o
   else
     COV_TILE_LAUNCH(long long, false);
 #undef COV_TILE_LAUNCH
-  TBK_LAUNCH(ctx, "cov_iv_count", cl_iv_count_k, cdiv(ntiles, B), B, 0, ntiles, O, icnt);
+  if (ntiles) TBK_LAUNCH(ctx, "cov_iv_count", cl_iv_count_k, cdiv(ntiles, B), B, 0, ntiles, O, icnt);
   TBK_TRY(tbk_exscan_u32(ctx, icnt, ioff, ntiles, sc + 8));
-  TBK_LAUNCH(ctx, "cov_iv_write", cl_iv_emit_k, ntiles, 256, 0, ntiles, S, nb, A, cp_pos, cp_val, tile_cp_base, tile_cp_cnt, O, ioff, T.tb, out->cap_intervals,
-             out->iv_tid, out->iv_start, out->iv_end, out->iv_val);
+  if (ntiles)
+    TBK_LAUNCH(ctx, "cov_iv_write", cl_iv_emit_k, ntiles, 256, 0, ntiles, S, nb, A, cp_pos, cp_val, tile_cp_base, tile_cp_cnt, O, ioff, T.tb, out->cap_intervals,
+               out->iv_tid, out->iv_start, out->iv_end, out->iv_val);
   return 0;
 }
 
@@ -2123,7 +2127,8 @@ static int cov_run(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out, bool sa
     if (nspill)
       TBK_LAUNCH(ctx, "cov_spill_fill", cov_spill_fill_k, cdiv(m, B), B, 0, m, A, in->cig_off, in->cig, tile_off, tile_fill,
                  sp_seg, sp_rec);
-    if (sample_mode) {
+    if (!ntiles) {  // (no covered base: no tile, no change point, no row)
+    } else if (sample_mode) {
       TBK_LAUNCH(ctx, "sample_tile", (cov_tile_ordered_k<true>), ntiles, COV_NT, 0, m, S, A, in->cig_off, in->cig, in->yc, in->yx,
                  tile_first, tile_off, sp_seg, sp_rec, cp_pos, cp_val, tile_cp_base, tile_cp_cnt, cp_alloc, cp_cap, ctx->d_err);
     } else if (fractional) {
@@ -2145,8 +2150,9 @@ static int cov_run(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out, bool sa
 #undef COV_TILE_LAUNCH
     }
     TBK_TRY(tbk_exscan_u32(ctx, tile_cp_cnt, tile_cp_off, ntiles, sc + 6));
-    TBK_LAUNCH(ctx, "cov_cp_gather", cov_cp_gather_k, ntiles, 64, 0, ntiles, tile_cp_base, tile_cp_cnt, tile_cp_off, cp_pos, cp_val,
-               sp, sv);
+    if (ntiles)
+      TBK_LAUNCH(ctx, "cov_cp_gather", cov_cp_gather_k, ntiles, 64, 0, ntiles, tile_cp_base, tile_cp_cnt, tile_cp_off, cp_pos, cp_val,
+                 sp, sv);
     TBK_TRY(tbk_sync_err(ctx, &eb));
     if (eb) return tbk_derr_to_status(ctx, eb);
     const uint32_t ncp = (uint32_t)ctx->h_scalars[6];

@@ -1,0 +1,374 @@
+// bai_read.cpp — BAI / CSI reader, region query, region parser, chunk reads (bai_read.h)
+#include "bai_read.h"
+
+#include <errno.h>
+#include <fcntl.h>
+#include <string.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <algorithm>
+
+#include "bgzf.h"
+
+namespace tbh {
+namespace {
+inline uint32_t le32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+inline uint64_t le64(const uint8_t* p) { return (uint64_t)le32(p) | (uint64_t)le32(p + 4) << 32; }
+
+bool slurp(const std::string& path, std::vector<uint8_t>& out) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) return false;
+  uint8_t buf[1 << 16];
+  size_t got;
+  out.clear();
+  while ((got = fread(buf, 1, sizeof(buf), f)) > 0) out.insert(out.end(), buf, buf + got);
+  const bool ok = !ferror(f);
+  fclose(f);
+  return ok;
+}
+bool exists(const std::string& p) {
+  struct stat st;
+  return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode);
+}
+// the size of the BGZF member whose first bytes are h[0, n) (n >= 12 + its XLEN); 0 when it is not one
+size_t member_size(const uint8_t* h, size_t n) {
+  if (n < 18 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return 0;
+  const size_t xlen = (size_t)h[10] | (size_t)h[11] << 8;
+  if (12 + xlen > n) return 0;
+  for (size_t x = 12; x + 4 <= 12 + xlen;) {
+    const size_t sl = (size_t)h[x + 2] | (size_t)h[x + 3] << 8;
+    if (h[x] == 'B' && h[x + 1] == 'C' && sl == 2 && x + 6 <= 12 + xlen) {
+      const size_t bsize = ((size_t)h[x + 4] | (size_t)h[x + 5] << 8) + 1;
+      return bsize < 12 + xlen + 8 ? 0 : bsize;
+    }
+    x += 4 + sl;
+  }
+  return 0;
+}
+}  // namespace
+
+bool RegionIndex::load(const std::string& path, std::string& err) {
+  std::vector<uint8_t> b;
+  if (!slurp(path, b)) {
+    err = "cannot read the index " + path;
+    return false;
+  }
+  if (!parse(b, err)) {
+    err = path + ": " + err;
+    return false;
+  }
+  return true;
+}
+
+bool RegionIndex::parse(const std::vector<uint8_t>& file_bytes, std::string& err) {
+  refs_.clear();
+  std::vector<uint8_t> inflated;
+  const std::vector<uint8_t>* src = &file_bytes;
+  if (file_bytes.size() >= 4 && memcmp(file_bytes.data(), "BAI\1", 4) == 0) {
+    csi_ = false, min_shift_ = 14, depth_ = 5;
+  } else if (file_bytes.size() >= 18 && file_bytes[0] == 31 && file_bytes[1] == 139) {
+    size_t used = 0;
+    std::string e;
+    if (!bgzf_inflate_chunk(file_bytes.data(), file_bytes.size(), true, inflated, &used, e, 1, "index") || used != file_bytes.size()) {
+      err = "truncated or damaged CSI index (" + (e.empty() ? std::string("a cut member") : e) + ")";
+      return false;
+    }
+    if (inflated.size() < 4 || memcmp(inflated.data(), "CSI\1", 4) != 0) {
+      err = "not a BAI or CSI index (magic)";
+      return false;
+    }
+    csi_ = true;
+    src = &inflated;
+  } else {
+    err = "not a BAI or CSI index (magic)";
+    return false;
+  }
+  const uint8_t* b = src->data();
+  const size_t n = src->size();
+  size_t p = 4;
+  auto need = [&](size_t k) { return k <= n && p <= n - k; };
+  const char* cut = "truncated index";
+  int32_t n_ref;
+  if (csi_) {
+    if (!need(16)) return err = cut, false;
+    min_shift_ = (int32_t)le32(b + p), depth_ = (int32_t)le32(b + p + 4);
+    const int32_t l_aux = (int32_t)le32(b + p + 8);
+    p += 12;
+    if (min_shift_ < 1 || min_shift_ > 30 || depth_ < 0 || depth_ > 10 || min_shift_ + 3 * depth_ > 62 || l_aux < 0) return err = "CSI header out of range", false;
+    if (!need((size_t)l_aux + 4)) return err = cut, false;
+    p += (size_t)l_aux;
+  } else if (!need(4)) {
+    return err = cut, false;
+  }
+  n_ref = (int32_t)le32(b + p);
+  p += 4;
+  if (n_ref < 0) return err = "negative n_ref", false;
+  const uint32_t skip_bin = csi_ ? (uint32_t)(((1ull << (3 * (depth_ + 1))) - 1) / 7 + 1) : 37450u;
+  for (int32_t t = 0; t < n_ref; ++t) {
+    if (!need(4)) return err = cut, false;
+    const int32_t n_bin = (int32_t)le32(b + p);
+    p += 4;
+    if (n_bin < 0) return err = "negative n_bin", false;
+    Ref R;
+    for (int32_t k = 0; k < n_bin; ++k) {
+      if (!need(csi_ ? 16 : 8)) return err = cut, false;
+      Bin B;
+      B.bin = le32(b + p);
+      B.loff = csi_ ? le64(b + p + 4) : 0;
+      const int32_t nc = (int32_t)le32(b + p + (csi_ ? 12 : 4));
+      p += csi_ ? 16 : 8;
+      if (nc < 0 || !need((size_t)nc * 16)) return err = cut, false;
+      if (B.bin != skip_bin) {
+        B.chunks.resize((size_t)nc);
+        for (int32_t c = 0; c < nc; ++c) B.chunks[(size_t)c] = IdxChunk{le64(b + p + 16 * (size_t)c), le64(b + p + 16 * (size_t)c + 8)};
+        R.bins.push_back(std::move(B));
+      }
+      p += (size_t)nc * 16;
+    }
+    if (!csi_) {
+      if (!need(4)) return err = cut, false;
+      const int32_t n_intv = (int32_t)le32(b + p);
+      p += 4;
+      if (n_intv < 0 || !need((size_t)n_intv * 8)) return err = cut, false;
+      R.lin.resize((size_t)n_intv);
+      for (int32_t w = 0; w < n_intv; ++w) R.lin[(size_t)w] = le64(b + p + 8 * (size_t)w);
+      p += (size_t)n_intv * 8;
+    }
+    std::sort(R.bins.begin(), R.bins.end(), [](const Bin& a, const Bin& c) { return a.bin < c.bin; });
+    refs_.push_back(std::move(R));
+  }
+  // (n_no_coor is optional in both formats)
+  if (p != n && p + 8 != n) return err = "trailing bytes behind the index", false;
+  return true;
+}
+
+const RegionIndex::Bin* RegionIndex::find(const Ref& r, uint32_t bin) const {
+  auto it = std::lower_bound(r.bins.begin(), r.bins.end(), bin, [](const Bin& a, uint32_t b) { return a.bin < b; });
+  return it != r.bins.end() && it->bin == bin ? &*it : nullptr;
+}
+
+void RegionIndex::query(int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out) const {
+  out.clear();
+  if (tid < 0 || (size_t)tid >= refs_.size() || beg < 0) return;
+  const int64_t reach = 1ll << (min_shift_ + 3 * depth_);  // no record the index holds ends behind it
+  if (end > reach) end = reach;
+  if (beg >= end) return;
+  const Ref& R = refs_[(size_t)tid];
+  uint64_t min_off = 0;
+  if (!csi_) {
+    const uint64_t w = (uint64_t)beg >> 14;
+    if (!R.lin.empty()) min_off = w < R.lin.size() ? R.lin[w] : R.lin.back();
+  } else {
+    uint64_t b = ((1ull << (3 * depth_)) - 1) / 7 + ((uint64_t)beg >> min_shift_);
+    for (;;) {
+      if (const Bin* B = find(R, (uint32_t)b)) {
+        min_off = B->loff;
+        break;
+      }
+      if (b == 0) break;
+      b = (b - 1) >> 3;
+    }
+  }
+  std::vector<IdxChunk> all;
+  auto take = [&](uint64_t bin) {
+    if (const Bin* B = find(R, (uint32_t)bin))
+      for (const IdxChunk& c : B->chunks)
+        if (c.end > min_off && c.beg < c.end) all.push_back(c);
+  };
+  take(0);
+  for (int l = 1; l <= depth_; ++l) {
+    const int s = min_shift_ + 3 * (depth_ - l);
+    const uint64_t first = ((1ull << (3 * l)) - 1) / 7;
+    // (the bins present are few: walk them, not the range, when the range is the longer of the two)
+    const uint64_t lo = first + ((uint64_t)beg >> s), hi = first + ((uint64_t)(end - 1) >> s);
+    if (hi - lo + 1 <= R.bins.size()) {
+      for (uint64_t bin = lo; bin <= hi; ++bin) take(bin);
+    } else {
+      for (const Bin& B : R.bins)
+        if (B.bin >= lo && B.bin <= hi) take(B.bin);
+    }
+  }
+  std::sort(all.begin(), all.end(), [](const IdxChunk& a, const IdxChunk& c) { return a.beg < c.beg || (a.beg == c.beg && a.end < c.end); });
+  for (const IdxChunk& c : all) {
+    if (!out.empty() && (out.back().end >> 16) >= (c.beg >> 16)) {
+      if (c.end > out.back().end) out.back().end = c.end;
+    } else {
+      out.push_back(c);
+    }
+  }
+}
+
+bool find_index(const std::string& bam_path, const std::string& explicit_path, std::string& found, std::string& err) {
+  if (!explicit_path.empty()) {
+    if (exists(explicit_path)) return found = explicit_path, true;
+    err = "no index found: " + explicit_path + " does not exist";
+    return false;
+  }
+  std::vector<std::string> tries = {bam_path + ".csi", bam_path + ".bai"};
+  const size_t dot = bam_path.rfind('.'), slash = bam_path.rfind('/');
+  if (dot != std::string::npos && (slash == std::string::npos || dot > slash + 1)) tries.push_back(bam_path.substr(0, dot) + ".bai");
+  for (const std::string& t : tries)
+    if (exists(t)) return found = t, true;
+  err = "no index found for " + bam_path + " (tried";
+  for (size_t i = 0; i < tries.size(); ++i) err += (i ? ", " : " ") + tries[i];
+  err += "): write one with `tiebrush --index` / `--csi`, or name it with --index-file";
+  return false;
+}
+
+static bool parse_coord(const std::string& s, int64_t* v) {  // digits and commas, at least one digit, no more than 2^40
+  int64_t x = 0;
+  bool any = false;
+  for (char c : s) {
+    if (c == ',') continue;
+    if (c < '0' || c > '9') return false;
+    x = x * 10 + (c - '0');
+    any = true;
+    if (x > (1ll << 40)) return false;
+  }
+  *v = x;
+  return any;
+}
+
+bool parse_region(const BamHeader& hdr, const std::string& region, int32_t* tid, int64_t* beg, int64_t* end, std::string& err) {
+  if (region.empty()) return err = "malformed region '' (expected NAME, NAME:BEG or NAME:BEG-END)", false;
+  int t = hdr.name2tid(region);
+  if (t >= 0) {
+    *tid = t, *beg = 0, *end = hdr.target_len[(size_t)t];
+    return true;
+  }
+  const size_t colon = region.rfind(':');
+  if (colon == std::string::npos) return err = "unknown reference name '" + region + "'", false;
+  const std::string name = region.substr(0, colon), range = region.substr(colon + 1);
+  t = hdr.name2tid(name);
+  if (t < 0) return err = "unknown reference name '" + name + "' (region '" + region + "')", false;
+  const int64_t len = hdr.target_len[(size_t)t];
+  const std::string bad = "malformed region '" + region + "' (expected NAME, NAME:BEG or NAME:BEG-END, 1-based, BEG >= 1)";
+  int64_t b1 = 0, e1 = len;
+  const size_t dash = range.find('-');
+  if (!parse_coord(range.substr(0, dash), &b1) || b1 < 1) return err = bad, false;
+  if (dash != std::string::npos) {
+    if (!parse_coord(range.substr(dash + 1), &e1)) return err = bad, false;
+    if (b1 > e1) return err = "malformed region '" + region + "': BEG > END", false;
+  }
+  *tid = t;
+  *end = std::min(e1, len);
+  *beg = std::min(b1 - 1, *end);  // (a BEG behind the reference: the empty region at its end)
+  return true;
+}
+
+bool read_spans(const std::string& bam_path, const std::vector<IdxChunk>& chunks, std::vector<RegionSpan>& spans, uint64_t* bytes_read, std::string& err) {
+  spans.clear();
+  if (bytes_read) *bytes_read = 0;
+  const int fd = open(bam_path.c_str(), O_RDONLY);
+  if (fd < 0) return err = "cannot open " + bam_path, false;
+  struct stat st;
+  if (fstat(fd, &st) != 0) {
+    close(fd);
+    return err = "cannot stat " + bam_path, false;
+  }
+  const uint64_t fsize = (uint64_t)st.st_size;
+  auto rd = [&](uint64_t at, uint8_t* dst, size_t n) {
+    while (n) {
+      const ssize_t got = pread(fd, dst, n, (off_t)at);
+      if (got < 0 && errno == EINTR) continue;
+      if (got <= 0) return false;
+      dst += got, at += (uint64_t)got, n -= (size_t)got;
+    }
+    return true;
+  };
+  bool ok = true;
+  uint64_t prev_end = 0;
+  for (const IdxChunk& c : chunks) {
+    const uint64_t c0 = c.beg >> 16, c1 = c.end >> 16;
+    const uint32_t u1 = (uint32_t)(c.end & 0xffff);
+    char where[96];
+    snprintf(where, sizeof(where), "%llx-%llx", (unsigned long long)c.beg, (unsigned long long)c.end);
+    if (c.beg >= c.end || c0 + 18 > fsize || c1 > fsize || (u1 && c1 + 18 > fsize) || c0 < prev_end) {
+      err = "the index names a chunk outside " + bam_path + " (" + where + ", file size " + std::to_string(fsize) + ")";
+      ok = false;
+      break;
+    }
+    uint64_t stop = c1;
+    if (u1) {  // the last member is part of the chunk: its size is in its own header
+      uint8_t h[18 + 256];
+      const size_t hn = (size_t)std::min<uint64_t>(sizeof(h), fsize - c1);
+      const size_t ms = rd(c1, h, hn) ? member_size(h, hn) : 0;
+      if (!ms || c1 + ms > fsize) {
+        err = "the index names a chunk that does not end in a BGZF member of " + bam_path + " (" + where + ")";
+        ok = false;
+        break;
+      }
+      stop = c1 + ms;
+    }
+    RegionSpan s;
+    s.first_uoff = (uint32_t)(c.beg & 0xffff), s.last_uoff = u1;
+    s.z.resize((size_t)(stop - c0));
+    if (!rd(c0, s.z.data(), s.z.size())) {
+      err = "read failed on " + bam_path;
+      ok = false;
+      break;
+    }
+    if (bytes_read) *bytes_read += s.z.size();
+    prev_end = stop;
+    spans.push_back(std::move(s));
+  }
+  close(fd);
+  return ok;
+}
+
+bool inflate_span(const RegionSpan& s, std::vector<uint8_t>& records, std::string& err) {
+  records.clear();
+  std::vector<uint8_t> pay;
+  size_t used = 0, last_isize = 0;
+  if (!s.z.empty() && (!bgzf_inflate_chunk(s.z.data(), s.z.size(), true, pay, &used, err, 1, "chunk") || used != s.z.size())) {
+    if (err.empty()) err = "a chunk is not a run of whole BGZF members";
+    return false;
+  }
+  if (s.z.size() >= 4) last_isize = le32(s.z.data() + s.z.size() - 4);
+  size_t stop = pay.size();
+  if (s.last_uoff) {
+    if (s.last_uoff > last_isize || last_isize > pay.size()) return err = "a chunk ends behind its last member's payload", false;
+    stop = pay.size() - last_isize + s.last_uoff;
+  }
+  if (s.first_uoff > stop) return err = "a chunk begins behind its end", false;
+  records.assign(pay.begin() + s.first_uoff, pay.begin() + (ptrdiff_t)stop);
+  return true;
+}
+
+bool span_records(const RegionSpan& s, uint64_t file_off, std::vector<BaiRec>& recs, std::string& err) {
+  recs.clear();
+  std::vector<uint8_t> r;
+  if (!inflate_span(s, r, err)) return false;
+  for (size_t p = 0; p < r.size();) {
+    if (r.size() - p < 4) return err = "a chunk does not end on a record", false;
+    const uint32_t bs = le32(r.data() + p);
+    BaiRec b;
+    if (bs < 32 || bs > r.size() - p - 4 || !bai_rec_span(r.data() + p + 4, bs, &b.tid, &b.beg, &b.end)) return err = "a chunk does not end on a record", false;
+    b.vbeg = s.first_uoff + p;
+    recs.push_back(b);
+    p += 4 + (size_t)bs;
+  }
+  if (!bai_member_voffsets(s.z.data(), s.z.size(), recs, err)) return false;
+  for (BaiRec& b : recs) b.vbeg += file_off << 16;
+  return true;
+}
+
+bool index_query_file(const std::string& bam_path, const std::string& index_path, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out,
+                      std::string& err) {
+  BamFile bf;
+  if (!bf.open(bam_path, err, 1)) return false;
+  std::string found;
+  if (!find_index(bam_path, index_path, found, err)) return false;
+  RegionIndex ix;
+  if (!ix.load(found, err)) return false;
+  if (ix.n_ref() != (size_t)bf.hdr.n_targets) {
+    err = found + ": the index has " + std::to_string(ix.n_ref()) + " references, the header of " + bam_path + " has " + std::to_string(bf.hdr.n_targets);
+    return false;
+  }
+  if (tid < 0 || tid >= bf.hdr.n_targets || beg < 0 || end < beg) return err = "index query: tid / beg / end out of range", false;
+  ix.query(tid, beg, end, out);
+  return true;
+}
+
+}  // namespace tbh

@@ -1,0 +1,82 @@
+// bai_read.h — the reader of the indexes bai.h writes (BAI, SAM specification 5.2; CSI v1), the region query behind `tiecov -r`, and
+// the region parser.  The reference reads no index at all (it has no region option; tiecov.cpp walks the whole file
+// through GSamReader::next), so nothing here replaces a reference interface: the rules are the SAM specification's and samtools' own
+// region syntax.
+//   query      bins of reg2bins(beg, end) minus the pseudo / meta bin -> chunks that end behind min_off -> sorted by beg -> neighbours
+//              that overlap, touch, or end and begin in the same BGZF member merged.  After the merge no file byte is in two chunks: a
+//              parent-bin record between two runs of a leaf bin lies INSIDE the leaf bin's merged chunk (§4d "same block" rule) and
+//              would otherwise be read twice.
+//   min_off    BAI: lin[beg >> 14], the last entry when the window lies beyond the table (0 for an empty table);
+//              CSI: the loff of the leaf bin that holds beg, or of its nearest present ancestor (0: none)
+#pragma once
+#include <stdint.h>
+
+#include <string>
+#include <vector>
+
+#include "bai.h"
+#include "bam.h"
+
+namespace tbh {
+
+struct IdxChunk {
+  uint64_t beg, end;  // virtual offsets: member offset << 16 | offset in the member's payload
+};
+
+class RegionIndex {
+ public:
+  // the format comes from the magic: "BAI\1", or a BGZF file whose payload starts with "CSI\1"
+  bool load(const std::string& path, std::string& err);
+  bool parse(const std::vector<uint8_t>& file_bytes, std::string& err);
+  bool csi() const { return csi_; }
+  int min_shift() const { return min_shift_; }
+  int depth() const { return depth_; }
+  size_t n_ref() const { return refs_.size(); }
+  // the chunks a reader of [beg, end) on tid has to read: sorted, disjoint, merged (see above); beg < end, both >= 0
+  void query(int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out) const;
+
+ private:
+  struct Bin {
+    uint32_t bin;
+    uint64_t loff;
+    std::vector<IdxChunk> chunks;
+  };
+  struct Ref {
+    std::vector<Bin> bins;  // ascending bin number (sorted after parsing), pseudo / meta bin dropped
+    std::vector<uint64_t> lin;
+  };
+  const Bin* find(const Ref& r, uint32_t bin) const;
+  bool csi_ = false;
+  int min_shift_ = 14, depth_ = 5;
+  std::vector<Ref> refs_;
+};
+
+// IN.bam.csi, IN.bam.bai, then IN.bai (IN.bam with its last extension replaced): the first that exists; `explicit_path` (not empty)
+// is taken as it is.  false: err names the paths tried.
+bool find_index(const std::string& bam_path, const std::string& explicit_path, std::string& found, std::string& err);
+
+// NAME | NAME:BEG | NAME:BEG-END, 1-based inclusive, commas allowed in the numbers; the whole string is tried as a name first (a name
+// may hold ':').  Out: tid and the 0-based half-open [beg, end), END cut to the reference's length.
+bool parse_region(const BamHeader& hdr, const std::string& region, int32_t* tid, int64_t* beg, int64_t* end, std::string& err);
+
+// One merged chunk's bytes: the whole BGZF members from the chunk's first member on; the records are the inflated bytes from first_uoff
+// in the first member up to last_uoff in the last one (0: the last member read is whole, the chunk ends where it ends).
+struct RegionSpan {
+  std::vector<uint8_t> z;
+  uint32_t first_uoff = 0, last_uoff = 0;
+};
+// pread of the chunks' byte ranges (the last member's size comes from its BSIZE field); a chunk that points outside the file is refused
+bool read_spans(const std::string& bam_path, const std::vector<IdxChunk>& chunks, std::vector<RegionSpan>& spans, uint64_t* bytes_read, std::string& err);
+// inflate a span on the host and cut it to its record bytes (block_size fields included); false on a malformed span
+bool inflate_span(const RegionSpan& s, std::vector<uint8_t>& records, std::string& err);
+
+// the records of a span by the host codec: tid / beg / end by the index's own rule (bai.h) and the virtual offset of each, the span's
+// first member lying at file_off
+bool span_records(const RegionSpan& s, uint64_t file_off, std::vector<BaiRec>& recs, std::string& err);
+
+// header + index + query in one step (tbh_index_query, `tbh_tool query`, tiecov -r): opens the header of bam_path, finds and loads the
+// index, refuses an index whose n_ref is not the header's
+bool index_query_file(const std::string& bam_path, const std::string& index_path, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out,
+                      std::string& err);
+
+}  // namespace tbh

@@ -10,6 +10,7 @@
 #include "../../../include/tbh_host.h"
 #include "GSam.h"
 #include "bai.h"
+#include "bai_read.h"
 #include "bgzf.h"
 #include "tagwrite.h"
 #include "tmerge.h"
@@ -116,6 +117,18 @@ int tbh_csi_index_file(const char* bam_path, const char* csi_path) {
 int tbh_csi_depth(uint64_t max_len) { return tbh::csi_depth(max_len); }
 uint32_t tbh_csi_reg2bin(int64_t beg, int64_t end, int depth) {
   return depth < 0 || depth > tbh::kCsiMaxDepth || beg < 0 || end <= beg || end > (1ll << (14 + 3 * depth)) ? UINT32_MAX : tbh::bai_reg2bin(beg, end, depth);
+}
+
+
+int64_t tbh_index_query(const char* bam_path, const char* index_path, int32_t tid, int64_t beg, int64_t end, uint64_t* chunk_beg, uint64_t* chunk_end,
+                        uint64_t cap) {
+  if (!bam_path || (cap && (!chunk_beg || !chunk_end))) return fail("tbh_index_query: null argument");
+  std::string err;
+  std::vector<tbh::IdxChunk> ch;
+  if (!tbh::index_query_file(bam_path, index_path ? index_path : "", tid, beg, end, ch, err)) return fail("tbh_index_query: " + err);
+  if (ch.size() <= cap)
+    for (size_t i = 0; i < ch.size(); ++i) chunk_beg[i] = ch[i].beg, chunk_end[i] = ch[i].end;
+  return (int64_t)ch.size();
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 //   tags IN.bam OUT.bam SPEC...   apply tag edits to every record: YC=f:2.5  YX=i:255  YD=i:0  YD=del
 //   bai IN.bam                    write IN.bam.bai with the host index builder alone (bai.h: what `tiebrush --index` builds as it writes)
 //   csi IN.bam                    write IN.bam.csi the same way (what `tiebrush --csi` builds: references beyond 2^29 included)
+//   query IN.bam REGION [INDEX]   the chunks the index names for REGION (bai_read.h), one line "vbeg vend" in hex each, then the number of
+//                                 records in the chunks and of those overlapping the region, by the host codec ("hit vbeg" per overlap)
 //   mkbam SOADIR PREFIX [LEVEL [THREADS]]   encode the raw SoA arrays of a synthetic tile (file_off, tid, pos, flag, mapq, strand,
 //                                 nh, cig_off, cig as little-endian files + header.txt) as PREFIX<f>.bam, one per input file: the
 //                                 records tiebrush_amd.synth.write_bams writes (SEQ '*', QNAME r<f>_<i>, NH:C / XS:A), files in parallel
@@ -18,6 +20,7 @@
 
 #include "GSam.h"
 #include "bai.h"
+#include "bai_read.h"
 #include "bgzf.h"
 #include "fastload.h"
 #include "tmerge.h"
@@ -381,6 +384,37 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi ...\n");
+  if (cmd == "query" && (argc == 4 || argc == 5)) {
+    std::string err;
+    tbh::BamFile bf;
+    int32_t tid = 0;
+    int64_t beg = 0, end = 0;
+    std::vector<tbh::IdxChunk> chunks;
+    std::vector<tbh::RegionSpan> spans;
+    if (!bf.open(argv[2], err, 1) || !tbh::parse_region(bf.hdr, argv[3], &tid, &beg, &end, err) ||
+        (beg < end && !tbh::index_query_file(argv[2], argc == 5 ? argv[4] : "", tid, beg, end, chunks, err)) || !tbh::read_spans(argv[2], chunks, spans, nullptr, err)) {
+      fprintf(stderr, "tbh_tool query: %s\n", err.c_str());
+      return 1;
+    }
+    printf("region %d %lld %lld\n", tid, (long long)beg, (long long)end);
+    uint64_t n_rec = 0, n_hit = 0;
+    std::vector<uint64_t> hits;
+    for (size_t c = 0; c < chunks.size(); ++c) {
+      printf("%llx %llx\n", (unsigned long long)chunks[c].beg, (unsigned long long)chunks[c].end);
+      std::vector<tbh::BaiRec> recs;
+      if (!tbh::span_records(spans[c], chunks[c].beg >> 16, recs, err)) {
+        fprintf(stderr, "tbh_tool query: %s\n", err.c_str());
+        return 1;
+      }
+      n_rec += recs.size();
+      for (const tbh::BaiRec& r : recs)
+        if (r.tid == tid && r.beg < end && r.end > beg) hits.push_back(r.vbeg);
+    }
+    n_hit = hits.size();
+    printf("records %llu\noverlapping %llu\n", (unsigned long long)n_rec, (unsigned long long)n_hit);
+    for (uint64_t v : hits) printf("hit %llx\n", (unsigned long long)v);
+    return 0;
+  }
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|query ...\n");
   return 2;
 }

@@ -1,11 +1,14 @@
 // tiecov — drop-in command line of the reference's coverage tool (/root/reference/src/tiecov.cpp:345-573).
 // The per-record loop (:435-499: bundles, addCov, addJunction, addMean, flushes) is replaced by
 // tbk_coverage_tile / tbk_sample_tile (HIP); BAM decode and text output stay on the host.
+// With -r REGION (no counterpart in the reference) only the chunks the file's index names for the region are read, and
+// they are inflated, decoded, filtered, summarised and cut to the region on the device (region_main below).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
+#include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
@@ -13,6 +16,7 @@
 #include "../../../include/tbk.h"
 #include "GSam.h"
 #include "args.h"
+#include "bai_read.h"
 #include "tracks.h"
 
 #define VERSION "0.0.7"
@@ -21,7 +25,7 @@ static const char* USAGE =
     "TieCov v" VERSION " (MI355X build)\n"
     "Summarises a (TieBrush-collapsed) BAM file as BED-like tracks.\n"
     "\n"
-    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] input.bam\n"
+    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [-r REGION] input.bam\n"
     "\n"
     "  -h,--help    print this text and exit\n"
     "  --version    print the version and exit\n"
@@ -29,10 +33,173 @@ static const char* USAGE =
     "  -j PREFIX    splice junctions as BED\n"
     "  -s PREFIX    estimated number of samples per position as bedGraph (needs @CO SAMPLE: header lines)\n"
     "  -W           write the coverage (-c) as a bigWig file (PREFIX.bigwig) instead of a bedGraph\n"
+    "  -r,--region REGION   only the tracks of REGION: NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive, commas allowed), read\n"
+    "               through the file's index (input.bam.csi, input.bam.bai or input.bai; `tiebrush --index` / `--csi` write one)\n"
+    "  --index-file PATH    the index to use with -r\n"
     " At least one of -c / -j / -s is required.\n";
 
+// ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
+// how often -r / --region is given (Args keeps the last value of a repeated option)
+static int count_region_opts(int argc, char** argv) {
+  int n = 0;
+  for (int i = 1; i < argc; ++i) {
+    const std::string a = argv[i];
+    if (a == "--region" || a == "--index-file") {
+      n += a == "--region";
+      ++i;
+    } else if (a.compare(0, 9, "--region=") == 0) {
+      ++n;
+    } else if (a.size() > 1 && a[0] == '-' && a[1] != '-') {
+      for (size_t k = 1; k < a.size(); ++k) {
+        const char c = a[k];
+        if (c == 'r') ++n;
+        if (c == 'r' || c == 'c' || c == 's' || c == 'j') {  // the rest of the word, or the next word, is its value
+          if (k + 1 == a.size()) ++i;
+          break;
+        }
+      }
+    }
+  }
+  return n;
+}
+
+static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::string& region, const std::string& index_file, const std::string& covfname,
+                       const std::string& jfname, const std::string& sfname, bool bigwig) {
+  const bool timing = getenv("TBK_TIMING") != nullptr;
+  const auto t0 = std::chrono::steady_clock::now();
+  auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+  // every refusal comes before an output file exists
+  std::string err;
+  int32_t rtid = 0;
+  int64_t beg = 0, end = 0;
+  if (!tbh::parse_region(*hdr, region, &rtid, &beg, &end, err)) GError("Error: %s\n", err.c_str());
+  int num_samples = 0;
+  if (!sfname.empty()) {
+    num_samples = (int)hdr->co_samples().size();
+    if (num_samples == 0) GError("Error: no sample lines found in header");
+  }
+  std::vector<tbh::IdxChunk> chunks;
+  if (!tbh::index_query_file(infname, index_file, rtid, beg, end, chunks, err)) GError("Error: %s\n", err.c_str());
+  const double ms_index = ms();
+  // the context comes up beside the file reads
+  tbk_ctx* ctx = nullptr;
+  const int dev = getenv("TBK_DEVICE") ? atoi(getenv("TBK_DEVICE")) : 0;
+  int rc = 0;
+  std::thread ctx_thread([&]() { rc = tbk_create(dev, &ctx); });
+  std::vector<tbh::RegionSpan> spans;
+  uint64_t bytes_read = 0;
+  const bool read_ok = tbh::read_spans(infname, chunks, spans, &bytes_read, err);
+  const double ms_read = ms();
+  ctx_thread.join();
+  if (!read_ok) GError("Error: %s\n", err.c_str());
+  if (rc != 0) GError("Error: cannot use GPU %d (%s); this build has no CPU coverage path\n", dev, tbk_strerror(rc));
+  const double ms_ctx = ms();
+  const uint32_t k = (uint32_t)spans.size();
+  std::vector<const uint8_t*> comp(k);
+  std::vector<uint64_t> comp_bytes(k);
+  std::vector<uint32_t> first_uoff(k), last_uoff(k), span_off(k + 1, 0);
+  for (uint32_t i = 0; i < k; ++i) comp[i] = spans[i].z.data(), comp_bytes[i] = spans[i].z.size(), first_uoff[i] = spans[i].first_uoff, last_uoff[i] = spans[i].last_uoff;
+  tbk_soa_in tile;
+  const uint8_t* tag_seen = nullptr;
+  rc = tbk_bam_decode_spans(ctx, k, comp.data(), comp_bytes.data(), first_uoff.data(), last_uoff.data(), hdr->n_targets, &tile, span_off.data(), &tag_seen);
+  if (rc == TBK_E2BIG) GError("Error: input too large for one tile\n");
+  if (rc != 0) GError("Error: could not decode the chunks of %s the index names (%s %s): is the index the file's own?\n", infname.c_str(), tbk_strerror(rc), tbk_last_error(ctx));
+  tbk_cov_in in;
+  uint32_t n_kept = 0;
+  rc = tbk_region_view(ctx, &tile, tag_seen, rtid, beg, end, &in, &n_kept);
+  if (rc == TBK_E2BIG) GError("Error: input too large for one tile\n");
+  if (rc != 0) GError("Error: GPU region filter failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+  const double ms_decode = ms();
+  const size_t n = in.n_records, co = in.n_cigar_ops;
+  // file names and header lines as without -r (tracks.cpp)
+  tbh::TrackFiles tf;
+  {
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens;
+    for (int t = 0; t < hdr->n_targets; ++t) {
+      names.push_back(hdr->target_name[t]);
+      lens.push_back(hdr->target_len[t]);
+    }
+    tf.open(covfname, jfname, sfname, bigwig, names, lens);
+  }
+  FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
+  const bool cov_bw = tf.cov_bw;
+  if (coutf || cov_bw || joutf) {
+    const size_t ci = (coutf || cov_bw) ? 2 * co + 2 * n + 16 : 0, cj = joutf ? co + 16 : 0;
+    std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
+    std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
+    std::vector<uint8_t> jstr(cj ? cj : 1);
+    tbk_cov_out o;
+    memset(&o, 0, sizeof(o));
+    o.mem = TBK_MEM_HOST;
+    o.cap_intervals = (uint32_t)ci;
+    o.iv_tid = it.data();
+    o.iv_start = is.data();
+    o.iv_end = ie.data();
+    o.iv_val = iv.data();
+    o.cap_junctions = (uint32_t)cj;
+    o.j_tid = jt.data();
+    o.j_start = js.data();
+    o.j_end = je.data();
+    o.j_strand = jstr.data();
+    o.j_val = jv.data();
+    if (n) {
+      rc = tbk_coverage_tile(ctx, &in, &o);
+      if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+      if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+      rc = tbk_cov_clip(ctx, &o, rtid, beg, end);
+      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+    }
+    if (coutf) tbh::emit_cov_lines(coutf, hdr->target_name, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
+    if (cov_bw) {
+      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
+      tf.close_bigwig();
+    }
+    if (joutf) tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);  // (numbered from 1)
+  }
+  if (soutf) {
+    size_t cs = 2 * co + 2 * n + 16;
+    std::vector<int32_t> st, ss, se;
+    std::vector<int64_t> sc;
+    std::vector<float> sh;
+    tbk_sample_out so;
+    memset(&so, 0, sizeof(so));
+    for (int attempt = 0; n && attempt < 2; ++attempt) {
+      st.resize(cs);
+      ss.resize(cs);
+      se.resize(cs);
+      sc.resize(cs);
+      sh.resize(cs);
+      memset(&so, 0, sizeof(so));
+      so.mem = TBK_MEM_HOST;
+      so.cap_intervals = (uint32_t)cs;
+      so.iv_tid = st.data();
+      so.iv_start = ss.data();
+      so.iv_end = se.data();
+      so.iv_count = sc.data();
+      so.iv_heat = sh.data();
+      rc = tbk_sample_tile(ctx, &in, num_samples, &so);
+      if (rc != TBK_E2BIG) break;
+      cs = (size_t)so.n_intervals + 16;
+    }
+    if (n) {
+      if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+      if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+      rc = tbk_sample_clip(ctx, &so, rtid, beg, end);
+      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+    }
+    tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());
+  }
+  tf.close();
+  if (timing)
+    fprintf(stderr, "tiecov -r phases ms: index %.1f | chunk reads %.1f (%llu bytes in %u chunks) | context up at %.1f | decode + filter %.1f (%u of %u records) | tracks %.1f\n",
+            ms_index, ms_read - ms_index, (unsigned long long)bytes_read, k, ms_ctx, ms_decode - ms_ctx, n_kept, tile.n_records, ms() - ms_decode);
+  tbk_destroy(ctx);
+  return 0;
+}
+
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;DVWhc:s:j:");
+  Args args(argc, argv, "help;verbose;version;region=;index-file=;DVWhc:s:j:r:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -66,6 +233,12 @@ int main(int argc, char* argv[]) {
   std::string infname = args.nextNonOpt();
   GSamReader samreader(infname.c_str(), SAM_QNAME | SAM_FLAG | SAM_RNAME | SAM_POS | SAM_CIGAR | SAM_AUX);
   sam_hdr_t* hdr = samreader.header();
+  if (args.getOpt('r') || args.getOpt("region") || args.getOpt("index-file")) {
+    if (count_region_opts(argc, argv) > 1) GError("Error: -r / --region given more than once (one region per run)\n");
+    const char* r = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");
+    if (!r) GError("Error: --index-file needs -r REGION\n");
+    return region_main(hdr, infname, r, args.getOpt("index-file") ? args.getOpt("index-file") : "", covfname, jfname, sfname, bigwig);
+  }
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;
   {

@@ -1,0 +1,377 @@
+// region.hip — the device side of `tiecov -r`: the records of a decoded tile that overlap a region as tiecov's input
+// view (tbk_region_view), and the rows of a coverage / sample call cut to the region (tbk_cov_clip, tbk_sample_clip).
+//
+// The reference has no region option (tiecov.cpp walks the whole file); the contract is that the rows equal the whole-file run's rows
+// on the region, bit for bit.  These are bandwidth-trivial passes of one thread per record or row, each kernel a launch of its own
+// (no hand-off between workgroups inside a launch); what can go wrong is at the edges: n = 0, the last partial wave, an end beyond 2^31.
+//   rv_flag_k      keep[i] = tid == rtid && pos < end && rec_end > beg, rec_end by the index's rule (pos + the CIGAR's reference length
+//                  over M D N = X, pos + 1 when that is 0); kcig[i] = the kept record's CIGAR count
+//   two exclusive scans (tbk_exscan_u32) over keep and kcig, n + 1 elements each: the last ones are the totals
+//   rv_scatter_k   the compacted tid / pos / flag / strand / yc / yx, the CSR cig_off and the gathered CIGAR words, in file order
+//   clip_bisect_k  interval rows are sorted and disjoint: the rows of the region are one range, found by two bisections
+//   clip_cov_k / clip_samp_k   that range, its rows trimmed to the region, into scratch (then copied over the caller's rows)
+//   clip_jflag_k / clip_jscat_k   junction rows are only sorted inside a bundle: keep flag, scan, scatter; rows are not trimmed
+#include "dev_common.hpp"
+#include "tbk_internal.h"
+
+namespace {
+
+constexpr int RG_NT = 256;
+
+__global__ __launch_bounds__(RG_NT) void rv_flag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ pos,
+                                                   const uint32_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, int32_t rtid, int64_t beg,
+                                                   int64_t end, uint32_t* __restrict__ keep /* [n + 1] */, uint32_t* __restrict__ kcig /* [n + 1] */) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i > n) return;
+  uint32_t k = 0, kc = 0;
+  if (i < n && tid[i] == rtid) {
+    const uint32_t c0 = cig_off[i], nc = cig_off[i + 1] - c0;
+    int64_t rl = 0;
+    for (uint32_t q = 0; q < nc; ++q) {
+      const uint32_t w = cig[c0 + q];
+      if ((0x18Du >> (w & 15u)) & 1u) rl += (int64_t)(w >> 4);
+    }
+    const int64_t p = pos[i], e = p + (rl ? rl : 1);
+    if (p < end && e > beg) k = 1, kc = nc;
+  }
+  keep[i] = k;
+  kcig[i] = kc;
+}
+
+struct RvOut {
+  int32_t *tid, *pos;
+  uint16_t* flag;
+  uint8_t* strand;
+  double* yc;
+  int64_t* yx;
+  uint32_t *cig_off, *cig;
+};
+
+__global__ __launch_bounds__(RG_NT) void rv_scatter_k(uint32_t n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ koff /* [n + 1] */,
+                                                      const uint32_t* __restrict__ coff /* [n + 1] */, const int32_t* __restrict__ tid,
+                                                      const int32_t* __restrict__ pos, const uint16_t* __restrict__ flag, const uint8_t* __restrict__ strand,
+                                                      const uint32_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, const double* __restrict__ yc,
+                                                      const int64_t* __restrict__ yx, const uint8_t* __restrict__ seen, RvOut O) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {  // the CSR's closing offset
+    O.cig_off[koff[n]] = coff[n];
+    return;
+  }
+  if (!keep[i]) return;
+  const uint32_t o = koff[i], d = coff[i];
+  const uint32_t sn = seen ? seen[i] : 3u;
+  O.tid[o] = tid[i];
+  O.pos[o] = pos[i];
+  O.flag[o] = flag[i];
+  O.strand[o] = strand[i];
+  O.yc[o] = (yc && (sn & 1u)) ? yc[i] : 1.0;          // tiecov.cpp:482-485: YC absent -> 1.0, YX absent -> 1; a present YC:f:0 stays 0
+  O.yx[o] = (yx && (sn & 2u)) ? yx[i] : (int64_t)1;
+  O.cig_off[o] = d;
+  const uint32_t c0 = cig_off[i], nc = cig_off[i + 1] - c0;
+  for (uint32_t q = 0; q < nc; ++q) O.cig[d + q] = cig[c0 + q];
+}
+
+// res[0] = the first row that ends behind beg on rtid (or lies on a later reference), res[1] = the first row that starts at or behind
+// end on rtid (or lies on a later reference): rows [res[0], res[1]) are the region's
+__global__ void clip_bisect_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv, int32_t rtid,
+                              int64_t beg, int64_t end, uint32_t* __restrict__ res) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    if (tid[m] > rtid || (tid[m] == rtid && (int64_t)endv[m] > beg))
+      hi = m;
+    else
+      lo = m + 1;
+  }
+  const uint32_t first = lo;
+  hi = n;
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    if (tid[m] > rtid || (tid[m] == rtid && (int64_t)start[m] >= end))
+      hi = m;
+    else
+      lo = m + 1;
+  }
+  res[0] = first;
+  res[1] = lo;
+}
+
+__device__ __forceinline__ int32_t clip_lo(int32_t s, int64_t beg) { return (int64_t)s < beg ? (int32_t)beg : s; }
+__device__ __forceinline__ int32_t clip_hi(int32_t e, int64_t end) { return (int64_t)e > end ? (int32_t)end : e; }
+
+__global__ __launch_bounds__(RG_NT) void clip_cov_k(uint32_t m, uint32_t first, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
+                                                    const int32_t* __restrict__ endv, const double* __restrict__ val, int64_t beg, int64_t end,
+                                                    int32_t* __restrict__ o_tid, int32_t* __restrict__ o_start, int32_t* __restrict__ o_end,
+                                                    double* __restrict__ o_val) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i >= m) return;
+  const uint64_t s = (uint64_t)first + i;
+  o_tid[i] = tid[s];
+  o_start[i] = clip_lo(start[s], beg);
+  o_end[i] = clip_hi(endv[s], end);
+  o_val[i] = val[s];
+}
+__global__ __launch_bounds__(RG_NT) void clip_samp_k(uint32_t m, uint32_t first, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
+                                                     const int32_t* __restrict__ endv, const int64_t* __restrict__ cnt, const float* __restrict__ heat,
+                                                     int64_t beg, int64_t end, int32_t* __restrict__ o_tid, int32_t* __restrict__ o_start,
+                                                     int32_t* __restrict__ o_end, int64_t* __restrict__ o_cnt, float* __restrict__ o_heat) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i >= m) return;
+  const uint64_t s = (uint64_t)first + i;
+  o_tid[i] = tid[s];
+  o_start[i] = clip_lo(start[s], beg);
+  o_end[i] = clip_hi(endv[s], end);
+  o_cnt[i] = cnt[s];
+  o_heat[i] = heat[s];
+}
+
+__global__ __launch_bounds__(RG_NT) void clip_jflag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
+                                                      const int32_t* __restrict__ endv, int32_t rtid, int64_t beg, int64_t end,
+                                                      uint32_t* __restrict__ keep /* [n + 1] */) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i > n) return;
+  keep[i] = (i < n && tid[i] == rtid && (int64_t)start[i] < end && (int64_t)endv[i] > beg) ? 1u : 0u;
+}
+__global__ __launch_bounds__(RG_NT) void clip_jscat_k(uint32_t n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ koff,
+                                                      const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv,
+                                                      const uint8_t* __restrict__ strand, const double* __restrict__ val, int32_t* __restrict__ o_tid,
+                                                      int32_t* __restrict__ o_start, int32_t* __restrict__ o_end, uint8_t* __restrict__ o_strand,
+                                                      double* __restrict__ o_val) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i >= n || !keep[i]) return;
+  const uint32_t o = koff[i];
+  o_tid[o] = tid[i];
+  o_start[o] = start[i];
+  o_end[o] = endv[i];
+  o_strand[o] = strand[i];
+  o_val[o] = val[i];
+}
+
+// rows of the caller (host or device) -> device pointers: a device array as it is, a host array through a copy into the arena
+template <class T>
+int rows_in(tbk_ctx* ctx, int mem, const T* p, size_t n, const T** d) {
+  if (mem == TBK_MEM_DEVICE) {
+    *d = p;
+    return 0;
+  }
+  T* a = ws_alloc<T>(ctx, n);
+  if (!a) return TBK_ENOMEM;
+  TBK_HIP(hipMemcpyAsync(a, p, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+  *d = a;
+  return 0;
+}
+// m clipped rows from scratch back over the caller's array
+template <class T>
+int rows_out(tbk_ctx* ctx, int mem, T* dst, const T* scratch, size_t m) {
+  if (!m) return 0;
+  TBK_HIP(hipMemcpyAsync(dst, scratch, m * sizeof(T), mem == TBK_MEM_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+  return 0;
+}
+
+bool region_ok(int mem, int32_t tid, int64_t beg, int64_t end) { return (mem == TBK_MEM_HOST || mem == TBK_MEM_DEVICE) && tid >= 0 && beg >= 0 && end >= beg; }
+
+struct ProfEnd {
+  tbk_ctx* c;
+  ~ProfEnd() { tbk_prof_end_call(c); }
+};
+
+// interval rows (tid, start, end sorted and disjoint): the range of the region -> *first, *m
+int clip_range(tbk_ctx* ctx, uint32_t n, const int32_t* d_tid, const int32_t* d_start, const int32_t* d_end, int32_t tid, int64_t beg, int64_t end,
+               uint32_t* first, uint32_t* m) {
+  uint32_t* d_res = ws_alloc<uint32_t>(ctx, 2);
+  if (!d_res) return TBK_ENOMEM;
+  TBK_LAUNCH(ctx, "clip_bisect", clip_bisect_k, 1, 64, 0, n, d_tid, d_start, d_end, tid, beg, end, d_res);
+  uint32_t res[2] = {0, 0};
+  TBK_HIP(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  if (res[0] > res[1] || res[1] > n) {  // (rows that are not sorted)
+    ctx->last_error = "clip: interval rows are not sorted by reference and start";
+    return TBK_EINVAL;
+  }
+  *first = res[0];
+  *m = res[1] - res[0];
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, int32_t tid, int64_t beg, int64_t end, tbk_cov_in* view,
+                               uint32_t* n_kept) {
+  if (!ctx || !tile || !view || !n_kept || tile->mem != TBK_MEM_DEVICE || tid < 0 || beg < 0 || end < beg) return TBK_EINVAL;
+  const uint32_t n = tile->n_records;
+  if (n && (!tile->tid || !tile->pos || !tile->flag || !tile->strand || !tile->cig_off || (tile->n_cigar_ops && !tile->cig))) return TBK_EINVAL;
+  if (n == UINT32_MAX) return TBK_E2BIG;
+  TBK_HIP(hipSetDevice(ctx->device));
+  memset(view, 0, sizeof(*view));
+  view->mem = TBK_MEM_DEVICE;
+  *n_kept = 0;
+  ctx->view_prep.valid = false;  // (the context's view is about to change)
+  if (n == 0) return 0;
+  tbk_prof_begin_call(ctx);
+  ProfEnd prof_end{ctx};
+  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 16 + ((size_t)1 << 20)));
+  uint32_t* keep = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* kcig = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* koff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* coff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  if (!keep || !kcig || !koff || !coff) return TBK_ENOMEM;
+  const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
+  TBK_LAUNCH(ctx, "region_flag", rv_flag_k, grid, RG_NT, 0, n, tile->tid, tile->pos, tile->cig_off, tile->cig, tid, beg, end, keep, kcig);
+  TBK_TRY(tbk_exscan_u32(ctx, keep, koff, n + 1, nullptr));
+  TBK_TRY(tbk_exscan_u32(ctx, kcig, coff, n + 1, nullptr));
+  uint32_t tot[2] = {0, 0};
+  TBK_HIP(hipMemcpyAsync(&tot[0], koff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(&tot[1], coff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  const size_t nk = tot[0], nc = tot[1];  // (nc < 2^32: a subset of the tile's CIGAR words, whose count is a uint32)
+  if (nk == 0) return tbk_check_launch(ctx, "region_view");
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t need = al(nk * 4) * 2 + al(nk * 2) + al(nk) + al(nk * 8) * 2 + al((nk + 1) * 4) + al(nc * 4 + 4);
+  if (need > ctx->d_view_cap) {
+    if (ctx->d_view) (void)hipFree(ctx->d_view);
+    ctx->d_view = nullptr;
+    ctx->d_view_cap = 0;
+    const size_t cap = need + need / 4;
+    TBK_HIP(hipMalloc((void**)&ctx->d_view, cap));
+    ctx->d_view_cap = cap;
+  }
+  char* p = ctx->d_view;
+  auto take = [&](size_t bytes) {
+    char* r = p;
+    p += al(bytes);
+    return r;
+  };
+  RvOut O;
+  O.tid = (int32_t*)take(nk * 4);
+  O.pos = (int32_t*)take(nk * 4);
+  O.flag = (uint16_t*)take(nk * 2);
+  O.strand = (uint8_t*)take(nk);
+  O.yc = (double*)take(nk * 8);
+  O.yx = (int64_t*)take(nk * 8);
+  O.cig_off = (uint32_t*)take((nk + 1) * 4);
+  O.cig = (uint32_t*)take(nc * 4 + 4);
+  TBK_LAUNCH(ctx, "region_scatter", rv_scatter_k, grid, RG_NT, 0, n, keep, koff, coff, tile->tid, tile->pos, tile->flag, tile->strand, tile->cig_off, tile->cig,
+             tile->yc_in, tile->yx_in, tag_seen, O);
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  TBK_TRY(tbk_check_launch(ctx, "region_view"));
+  view->n_records = (uint32_t)nk;
+  view->n_cigar_ops = (uint32_t)nc;
+  view->tid = O.tid;
+  view->pos = O.pos;
+  view->flag = O.flag;
+  view->cig_off = O.cig_off;
+  view->cig = O.cig;
+  view->yc = O.yc;
+  view->strand = O.strand;
+  view->yx = O.yx;
+  *n_kept = (uint32_t)nk;
+  return 0;
+}
+
+extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end) {
+  if (!ctx || !rows || !region_ok(rows->mem, tid, beg, end)) return TBK_EINVAL;
+  const uint32_t ni = rows->cap_intervals ? rows->n_intervals : 0, nj = rows->cap_junctions ? rows->n_junctions : 0;
+  if (ni > rows->cap_intervals || nj > rows->cap_junctions || ni == UINT32_MAX || nj == UINT32_MAX) return TBK_EINVAL;
+  if (ni && (!rows->iv_tid || !rows->iv_start || !rows->iv_end || !rows->iv_val)) return TBK_EINVAL;
+  if (nj && (!rows->j_tid || !rows->j_start || !rows->j_end || !rows->j_strand || !rows->j_val)) return TBK_EINVAL;
+  if (!ni && !nj) return 0;
+  TBK_HIP(hipSetDevice(ctx->device));
+  tbk_prof_begin_call(ctx);
+  ProfEnd prof_end{ctx};
+  const int mem = rows->mem;
+  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 48 + (size_t)nj * 64 + ((size_t)1 << 20)));
+  if (ni) {
+    const int32_t *d_tid, *d_start, *d_end;
+    const double* d_val;
+    TBK_TRY(rows_in(ctx, mem, rows->iv_tid, ni, &d_tid));
+    TBK_TRY(rows_in(ctx, mem, rows->iv_start, ni, &d_start));
+    TBK_TRY(rows_in(ctx, mem, rows->iv_end, ni, &d_end));
+    TBK_TRY(rows_in(ctx, mem, rows->iv_val, ni, &d_val));
+    uint32_t first = 0, m = 0;
+    TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
+    if (m) {
+      int32_t *s_tid = ws_alloc<int32_t>(ctx, m), *s_start = ws_alloc<int32_t>(ctx, m), *s_end = ws_alloc<int32_t>(ctx, m);
+      double* s_val = ws_alloc<double>(ctx, m);
+      if (!s_tid || !s_start || !s_end || !s_val) return TBK_ENOMEM;
+      TBK_LAUNCH(ctx, "clip_cov", clip_cov_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_val, beg, end, s_tid, s_start, s_end, s_val);
+      TBK_TRY(rows_out(ctx, mem, rows->iv_tid, s_tid, m));
+      TBK_TRY(rows_out(ctx, mem, rows->iv_start, s_start, m));
+      TBK_TRY(rows_out(ctx, mem, rows->iv_end, s_end, m));
+      TBK_TRY(rows_out(ctx, mem, rows->iv_val, s_val, m));
+    }
+    rows->n_intervals = m;
+  }
+  if (nj) {
+    const int32_t *d_tid, *d_start, *d_end;
+    const uint8_t* d_strand;
+    const double* d_val;
+    TBK_TRY(rows_in(ctx, mem, rows->j_tid, nj, &d_tid));
+    TBK_TRY(rows_in(ctx, mem, rows->j_start, nj, &d_start));
+    TBK_TRY(rows_in(ctx, mem, rows->j_end, nj, &d_end));
+    TBK_TRY(rows_in(ctx, mem, rows->j_strand, nj, &d_strand));
+    TBK_TRY(rows_in(ctx, mem, rows->j_val, nj, &d_val));
+    uint32_t* keep = ws_alloc<uint32_t>(ctx, (size_t)nj + 1);
+    uint32_t* koff = ws_alloc<uint32_t>(ctx, (size_t)nj + 1);
+    int32_t *s_tid = ws_alloc<int32_t>(ctx, nj), *s_start = ws_alloc<int32_t>(ctx, nj), *s_end = ws_alloc<int32_t>(ctx, nj);
+    uint8_t* s_strand = ws_alloc<uint8_t>(ctx, nj);
+    double* s_val = ws_alloc<double>(ctx, nj);
+    if (!keep || !koff || !s_tid || !s_start || !s_end || !s_strand || !s_val) return TBK_ENOMEM;
+    TBK_LAUNCH(ctx, "clip_junc", clip_jflag_k, cdiv((uint64_t)nj + 1, RG_NT), RG_NT, 0, nj, d_tid, d_start, d_end, tid, beg, end, keep);
+    TBK_TRY(tbk_exscan_u32(ctx, keep, koff, nj + 1, nullptr));
+    TBK_LAUNCH(ctx, "clip_junc", clip_jscat_k, cdiv(nj, RG_NT), RG_NT, 0, nj, keep, koff, d_tid, d_start, d_end, d_strand, d_val, s_tid, s_start, s_end, s_strand,
+               s_val);
+    uint32_t m = 0;
+    TBK_HIP(hipMemcpyAsync(&m, koff + nj, 4, hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    if (m > nj) return TBK_EHIP;
+    TBK_TRY(rows_out(ctx, mem, rows->j_tid, s_tid, m));
+    TBK_TRY(rows_out(ctx, mem, rows->j_start, s_start, m));
+    TBK_TRY(rows_out(ctx, mem, rows->j_end, s_end, m));
+    TBK_TRY(rows_out(ctx, mem, rows->j_strand, s_strand, m));
+    TBK_TRY(rows_out(ctx, mem, rows->j_val, s_val, m));
+    rows->n_junctions = m;
+  }
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  return tbk_check_launch(ctx, "cov_clip");
+}
+
+extern "C" int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, int64_t beg, int64_t end) {
+  if (!ctx || !rows || !region_ok(rows->mem, tid, beg, end)) return TBK_EINVAL;
+  const uint32_t ni = rows->n_intervals;
+  if (ni > rows->cap_intervals || ni == UINT32_MAX) return TBK_EINVAL;
+  if (ni && (!rows->iv_tid || !rows->iv_start || !rows->iv_end || !rows->iv_count || !rows->iv_heat)) return TBK_EINVAL;
+  if (!ni) return 0;
+  TBK_HIP(hipSetDevice(ctx->device));
+  tbk_prof_begin_call(ctx);
+  ProfEnd prof_end{ctx};
+  const int mem = rows->mem;
+  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 56 + ((size_t)1 << 20)));
+  const int32_t *d_tid, *d_start, *d_end;
+  const int64_t* d_cnt;
+  const float* d_heat;
+  TBK_TRY(rows_in(ctx, mem, rows->iv_tid, ni, &d_tid));
+  TBK_TRY(rows_in(ctx, mem, rows->iv_start, ni, &d_start));
+  TBK_TRY(rows_in(ctx, mem, rows->iv_end, ni, &d_end));
+  TBK_TRY(rows_in(ctx, mem, rows->iv_count, ni, &d_cnt));
+  TBK_TRY(rows_in(ctx, mem, rows->iv_heat, ni, &d_heat));
+  uint32_t first = 0, m = 0;
+  TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
+  if (m) {
+    int32_t *s_tid = ws_alloc<int32_t>(ctx, m), *s_start = ws_alloc<int32_t>(ctx, m), *s_end = ws_alloc<int32_t>(ctx, m);
+    int64_t* s_cnt = ws_alloc<int64_t>(ctx, m);
+    float* s_heat = ws_alloc<float>(ctx, m);
+    if (!s_tid || !s_start || !s_end || !s_cnt || !s_heat) return TBK_ENOMEM;
+    TBK_LAUNCH(ctx, "clip_sample", clip_samp_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_cnt, d_heat, beg, end, s_tid, s_start, s_end, s_cnt,
+               s_heat);
+    TBK_TRY(rows_out(ctx, mem, rows->iv_tid, s_tid, m));
+    TBK_TRY(rows_out(ctx, mem, rows->iv_start, s_start, m));
+    TBK_TRY(rows_out(ctx, mem, rows->iv_end, s_end, m));
+    TBK_TRY(rows_out(ctx, mem, rows->iv_count, s_cnt, m));
+    TBK_TRY(rows_out(ctx, mem, rows->iv_heat, s_heat, m));
+  }
+  rows->n_intervals = m;
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  return tbk_check_launch(ctx, "sample_clip");
+}

@@ -722,28 +722,30 @@ int tbk_coverage_tile(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out) {
   if (in->n_records && (!in->tid || !in->pos || !in->cig_off || (in->n_cigar_ops && !in->cig))) return TBK_EINVAL;  // flag may be NULL
   if (out->cap_intervals && (!out->iv_tid || !out->iv_start || !out->iv_end || !out->iv_val)) return TBK_EINVAL;
   if (out->cap_junctions && (!out->j_tid || !out->j_start || !out->j_end || !out->j_strand || !out->j_val)) return TBK_EINVAL;
-  if (in->mem != out->mem) return TBK_EINVAL;
+  if (in->mem != out->mem && !(in->mem == TBK_MEM_DEVICE && out->mem == TBK_MEM_HOST)) return TBK_EINVAL;  // (a device view may deliver host rows)
   TBK_HIP(hipSetDevice(ctx->device));
   tbk_prof_begin_call(ctx);
   size_t hint = (size_t)in->n_records * 96 + (size_t)in->n_cigar_ops * 64 + ((size_t)32 << 20);  // (the lean chain's tile tables: 12 MB at least)
   TBK_TRY(ws_begin_call(ctx, hint));
   RegGuard reg_guard{ctx};
   int rc;
-  if (in->mem == TBK_MEM_DEVICE) {
+  if (in->mem == TBK_MEM_DEVICE && out->mem == TBK_MEM_DEVICE) {
     rc = tbk_coverage_device(ctx, in, out);
   } else {
     tbk_cov_in din = *in;
     tbk_cov_out dout = *out;
     din.mem = dout.mem = TBK_MEM_DEVICE;
     size_t n = in->n_records;
-    TBK_TRY(h2d(ctx, in->tid, n, &din.tid));
-    TBK_TRY(h2d(ctx, in->pos, n, &din.pos));
-    TBK_TRY(h2d(ctx, in->flag, n, &din.flag));
-    TBK_TRY(h2d(ctx, in->cig_off, n + 1, &din.cig_off));
-    TBK_TRY(h2d(ctx, in->cig, (size_t)in->n_cigar_ops, &din.cig));
-    TBK_TRY(h2d(ctx, in->yc, n, &din.yc));
-    TBK_TRY(h2d(ctx, in->strand, n, &din.strand));
-    din.yx = nullptr;
+    if (in->mem == TBK_MEM_HOST) {
+      TBK_TRY(h2d(ctx, in->tid, n, &din.tid));
+      TBK_TRY(h2d(ctx, in->pos, n, &din.pos));
+      TBK_TRY(h2d(ctx, in->flag, n, &din.flag));
+      TBK_TRY(h2d(ctx, in->cig_off, n + 1, &din.cig_off));
+      TBK_TRY(h2d(ctx, in->cig, (size_t)in->n_cigar_ops, &din.cig));
+      TBK_TRY(h2d(ctx, in->yc, n, &din.yc));
+      TBK_TRY(h2d(ctx, in->strand, n, &din.strand));
+      din.yx = nullptr;
+    }
     TBK_TRY(dalloc(ctx, out->iv_tid, out->cap_intervals, &dout.iv_tid));
     TBK_TRY(dalloc(ctx, out->iv_start, out->cap_intervals, &dout.iv_start));
     TBK_TRY(dalloc(ctx, out->iv_end, out->cap_intervals, &dout.iv_end));
@@ -970,27 +972,29 @@ int tbk_kept_results(tbk_ctx* ctx, uint32_t first, uint32_t n, uint32_t* rep, do
 
 int tbk_sample_tile(tbk_ctx* ctx, const tbk_cov_in* in, int32_t num_samples, tbk_sample_out* out) {
   if (!ctx || !in || !out || num_samples <= 0) return TBK_EINVAL;
-  if (in->mem != out->mem) return TBK_EINVAL;
+  if (in->mem != out->mem && !(in->mem == TBK_MEM_DEVICE && out->mem == TBK_MEM_HOST)) return TBK_EINVAL;  // (a device view may deliver host rows)
   TBK_HIP(hipSetDevice(ctx->device));
   tbk_prof_begin_call(ctx);
   TBK_TRY(ws_begin_call(ctx, (size_t)in->n_records * 96 + ((size_t)8 << 20)));
   RegGuard reg_guard{ctx};
   int rc;
-  if (in->mem == TBK_MEM_DEVICE) {
+  if (in->mem == TBK_MEM_DEVICE && out->mem == TBK_MEM_DEVICE) {
     rc = tbk_sample_device(ctx, in, num_samples, out);
   } else {
     tbk_cov_in din = *in;
     tbk_sample_out dout = *out;
     din.mem = dout.mem = TBK_MEM_DEVICE;
     size_t n = in->n_records;
-    TBK_TRY(h2d(ctx, in->tid, n, &din.tid));
-    TBK_TRY(h2d(ctx, in->pos, n, &din.pos));
-    TBK_TRY(h2d(ctx, in->flag, n, &din.flag));
-    TBK_TRY(h2d(ctx, in->cig_off, n + 1, &din.cig_off));
-    TBK_TRY(h2d(ctx, in->cig, (size_t)in->n_cigar_ops, &din.cig));
-    TBK_TRY(h2d(ctx, in->yx, n, &din.yx));
-    din.yc = nullptr;
-    din.strand = nullptr;
+    if (in->mem == TBK_MEM_HOST) {
+      TBK_TRY(h2d(ctx, in->tid, n, &din.tid));
+      TBK_TRY(h2d(ctx, in->pos, n, &din.pos));
+      TBK_TRY(h2d(ctx, in->flag, n, &din.flag));
+      TBK_TRY(h2d(ctx, in->cig_off, n + 1, &din.cig_off));
+      TBK_TRY(h2d(ctx, in->cig, (size_t)in->n_cigar_ops, &din.cig));
+      TBK_TRY(h2d(ctx, in->yx, n, &din.yx));
+      din.yc = nullptr;
+      din.strand = nullptr;
+    }
     TBK_TRY(dalloc(ctx, out->iv_tid, out->cap_intervals, &dout.iv_tid));
     TBK_TRY(dalloc(ctx, out->iv_start, out->cap_intervals, &dout.iv_start));
     TBK_TRY(dalloc(ctx, out->iv_end, out->cap_intervals, &dout.iv_end));
