@@ -100,13 +100,14 @@ def test_edge_cases(ctx, chain, monkeypatch):
         return soa.CovInput(tid, pos, flag, off, cig, yc, st)
 
     # adjacent bundles (start == b_end + 1) with equal depth must not merge; unmapped skipped;
-    # D inside a read leaves a zero gap; tile boundary crossing at 8192; tid change; I/S ignored
+    # D inside a read leaves a zero gap; tid change; I/S ignored; a long read over several tiles.  (Tiles are cut in COMPACTED
+    # coordinates, bundles laid end to end: nothing here is placed on a tile edge on purpose — tests/test_gpu_cov_edges.py does that.)
     recs = [
         (0, 10, 0, [(50, M)], 3.0, "."),
         (0, 60, 0, [(50, M)], 3.0, "."),          # adjacent: new bundle, same depth
         (0, 60, 4, [(50, M)], 9.0, "."),          # unmapped: skipped
         (0, 200, 0, [(10, M), (5, D), (10, M)], 2.0, "."),
-        (0, 8150, 0, [(3, S), (100, M), (2, S)], 1.0, "."),   # crosses the first tile end in cpos? (cpos small) fine
+        (0, 8150, 0, [(3, S), (100, M), (2, S)], 1.0, "."),   # opens the fourth bundle: compacted offset 125, it crosses no tile edge
         (0, 9000, 0, [(30, M), (1000, N), (20, M), (2, I), (30, M)], 4.0, "+"),
         (0, 9000, 16, [(30, M), (1000, N), (50, M)], 2.0, "+"),
         (0, 9010, 0, [(20, M), (1000, N), (50, M)], 1.0, "-"),
