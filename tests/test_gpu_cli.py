@@ -627,3 +627,57 @@ def test_tiebrush_ranks_four_ranks_equal_single_gpu(tmp_path):
     assert a.n == b.n == 3479
     for i in range(a.n):
         assert bamio.record_bytes(a, i) == bamio.record_bytes(b, i), i
+
+
+def _hand_built_paths(scene, d):
+    os.makedirs(d, exist_ok=True)
+    paths = []
+    for i, f in enumerate(scene.files):
+        paths.append(os.path.join(d, "in%d.bam" % i))
+        with open(paths[-1], "wb") as fh:
+            fh.write(f)
+    return paths
+
+
+def test_hand_built_mixed_scene_is_the_same_output_on_every_decode_route(tmp_path):
+    """tests/bam_craft.py's mixed scene (tags of every width, arrays in front of NH, one file cut into members by hand) through the host
+    decode, the device decode and the hybrid of both: one output, byte for byte after inflation"""
+    import bam_craft as bc
+    from tiebrush_amd import bamio
+    paths = _hand_built_paths(bc.well_formed()["mixed"], str(tmp_path / "in"))
+    out = str(tmp_path / "o.bam")                           # (one path: the header's @PG line quotes the command line)
+    streams = {}
+    for tag, env, said in (("host", dict(TBK_DEVICE_DECODE="0"), None), ("device", dict(TBK_DEVICE_DECODE="1"), "device decode:"),
+                           ("hybrid", dict(TBK_HYBRID="1", TBK_HYBRID_SHARE="50"), "hybrid path ms: device")):
+        r = subprocess.run([os.path.join(BIN, "tiebrush"), "-o", out] + paths, check=True, capture_output=True, text=True,
+                           env=dict(os.environ, TBK_TIMING="1", **env))
+        if said:
+            assert said in r.stderr, (tag, r.stderr[-600:])
+        data = open(out, "rb").read()
+        assert data.endswith(bamio._BGZF_EOF)
+        streams[tag] = bamio.bgzf_decompress(data)
+        os.remove(out)
+    assert bamio.parse_bam(streams["host"]).n == 630          # (the oracle's groups of this scene: test_gpu_bam_decode_edges.py)
+    assert streams["device"] == streams["host"] and streams["hybrid"] == streams["host"]
+
+
+@pytest.mark.parametrize("name", ["bad/block_size_31/middle", "bad/l_read_name_0/last", "bad/bad_magic/first"], ids=["chain", "fields", "header"])
+def test_hand_built_malformed_inputs_end_the_device_decode_cleanly(tmp_path, name):
+    """one malformed scene for each stage of the device decode that can refuse a file: an error exit (no signal), a message, and no
+    output that reads as a complete BAM file"""
+    import bam_craft as bc
+    from tiebrush_amd import bamio
+    paths = _hand_built_paths(bc.malformed()[name], str(tmp_path / "in"))
+    out = str(tmp_path / "o.bam")
+    r = subprocess.run([os.path.join(BIN, "tiebrush"), "-o", out] + paths, capture_output=True, text=True, env=dict(os.environ, TBK_DEVICE_DECODE="1"), timeout=120)
+    assert r.returncode > 0, (r.returncode, r.stderr[-600:])
+    assert r.stderr.strip() != ""
+    if os.path.exists(out):
+        data = open(out, "rb").read()
+        complete = data.endswith(bamio._BGZF_EOF)
+        if complete:
+            try:
+                bamio.parse_bam(bamio.bgzf_decompress(data))
+            except Exception:
+                complete = False
+        assert not complete
