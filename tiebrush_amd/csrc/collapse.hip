@@ -353,7 +353,8 @@ __global__ void col_tie_sort_k(ColIn I, int strategy, const uint64_t* __restrict
     }
     gperm[sg + b] = x;
   }
-  for (uint32_t a = 0; a < e; ++a) ginv[gperm[sg + a]] = sg + a;
+  if (ginv)  // (null: nothing will read the inverse)
+    for (uint32_t a = 0; a < e; ++a) ginv[gperm[sg + a]] = sg + a;
 }
 
 // ---- YD ----------------------------------------------------------------------------------------------------
@@ -509,183 +510,11 @@ __device__ __forceinline__ YsAgg ys_combine(const YsAgg& a, const YsAgg& b) {
   r.whole = joins ? a.whole : 0u;
   return r;
 }
-// A tile's items of list c are the set bits of column c, wave by wave.  The walk is two-level: every (wave, list) cell — two per
-// thread — folds its few items (three or four on average), thread c chains the sixteen cells of its list (ys_chain_cells), and the
-// cells are walked once more where the heads are wanted.  Aggregates live in LDS as three words (the `whole` bit rides in bit 31
-// of first_tid: tid + 1 < 2^31).
-struct YsCells {
-  uint32_t (*a)[YS_NL];  // first_tid | whole << 31
-  uint32_t (*b)[YS_NL];  // last_tid
-  int32_t (*m)[YS_NL];   // mx
-  __device__ __forceinline__ YsAgg get(uint32_t x, uint32_t c) const { return YsAgg{a[x][c] & 0x7FFFFFFFu, b[x][c], m[x][c], a[x][c] >> 31}; }
-  __device__ __forceinline__ void put(uint32_t x, uint32_t c, const YsAgg& v) const {
-    a[x][c] = v.first_tid | (v.whole << 31);
-    b[x][c] = v.last_tid;
-    m[x][c] = v.mx;
-  }
-};
-// cells -> the aggregate of the list's items before each cell (start: before the tile); returns the aggregate behind the last cell
-__device__ __forceinline__ YsAgg ys_chain_cells(const YsCells& P, uint32_t c, YsAgg run) {
-  for (uint32_t x = 0; x < YS_NT / 64; ++x) {
-    const YsAgg mine = P.get(x, c);
-    P.put(x, c, run);
-    run = ys_combine(run, mine);
-  }
-  return run;
-}
-__global__ __launch_bounds__(YS_NT) void yd_lcount_k(YsIn S, const uint4* __restrict__ gpk /* YdGroups::pk */, uint32_t ntiles,
-                                                     uint32_t* __restrict__ table /* [YS_NL][ntiles] */, uint4* __restrict__ agg /* [YS_NL][ntiles] */,
-                                                     uint64_t* __restrict__ gwb /* [ntiles][YS_NT / 64][YS_NL]: the columns, for yd_lscatter_k */) {
-  __shared__ uint64_t wb[YS_NT / 64][YS_NL];
-  __shared__ uint32_t g_tid[YS_NT];
-  __shared__ int32_t g_e1[YS_NT];
-  __shared__ uint32_t pa[YS_NT / 64][YS_NL], pb[YS_NT / 64][YS_NL];
-  __shared__ int32_t pm[YS_NT / 64][YS_NL];
-  const YsCells P{pa, pb, pm};
-  uint64_t lo = 0, hi = 0;
-  {
-    const uint32_t o = blockIdx.x * YS_NT + threadIdx.x;
-    if (o < S.ng) {
-      const uint32_t sg = S.gperm[o];
-      const uint32_t c = (uint32_t)S.ghi[sg] & 3u;
-      const uint32_t n = S.gfmask ? 0u : S.ns[sg], p0 = S.gfmask ? 0u : S.gpoff[sg];
-      uint64_t files = 0;
-      if (S.gfmask)
-        files = S.gfmask[sg];
-      else
-        for (uint32_t i = 0; i < n; ++i) files |= 1ull << S.pfile[p0 + i];
-      ys_mask_from_files(files, c, &lo, &hi);
-      const uint4 g = gpk[o];
-      g_tid[threadIdx.x] = g.x;
-      g_e1[threadIdx.x] = (int32_t)g.z + 1;
-    }
-  }
-  {
-    const uint32_t x = threadIdx.x >> 6, l = lane_id();
-    const uint64_t a = wave_bit_transpose(lo), b = wave_bit_transpose(hi);  // lane c: the groups of this wave in lists c and 64 + c
-    wb[x][l] = a;
-    wb[x][64u + l] = b;
-    uint64_t* out = gwb + (size_t)blockIdx.x * (YS_NT / 64) * YS_NL + x * YS_NL;  // (groups past ng: empty rows, zero bits)
-    out[l] = a;
-    out[64u + l] = b;
-  }
-  __syncthreads();
-  for (uint32_t q = threadIdx.x; q < (YS_NT / 64) * YS_NL; q += YS_NT) {
-    const uint32_t x = q / YS_NL, c = q % YS_NL;
-    YsAgg A{0u, 0u, INT32_MIN, 1u};
-    for (uint64_t m = wb[x][c]; m; m &= m - 1) {
-      const uint32_t g = x * 64u + (uint32_t)__builtin_ctzll(m);
-      A = ys_combine(A, YsAgg{g_tid[g], g_tid[g], g_e1[g], 1u});
-    }
-    P.put(x, c, A);
-  }
-  __syncthreads();
-  if (threadIdx.x < YS_NL) {
-    const uint32_t c = threadIdx.x;
-    uint32_t n = 0;
-    YsAgg A{0u, 0u, INT32_MIN, 1u};
-    for (uint32_t x = 0; x < YS_NT / 64; ++x) {
-      n += (uint32_t)__builtin_popcountll(wb[x][c]);
-      A = ys_combine(A, P.get(x, c));
-    }
-    table[(size_t)c * ntiles + blockIdx.x] = n;
-    agg[(size_t)c * ntiles + blockIdx.x] = make_uint4(A.first_tid, A.last_tid, (uint32_t)A.mx, A.whole);
-  }
-}
-// block l: row l of the aggregates -> exclusive prefix in place (the aggregate of the list's items in the tiles before)
-__global__ __launch_bounds__(256) void yd_lagg_scan_k(uint4* __restrict__ agg, uint32_t ntiles) {
-  __shared__ uint4 part[256];
-  uint4* row = agg + (size_t)blockIdx.x * ntiles;
-  const uint32_t per = (ntiles + 255u) / 256u, i0 = threadIdx.x * per, i1 = i0 + per < ntiles ? i0 + per : ntiles;
-  auto un = [](const uint4& v) { return YsAgg{v.x, v.y, (int32_t)v.z, v.w}; };
-  auto pk = [](const YsAgg& a) { return make_uint4(a.first_tid, a.last_tid, (uint32_t)a.mx, a.whole); };
-  YsAgg A{0u, 0u, INT32_MIN, 1u};
-  for (uint32_t i = i0; i < i1; ++i) A = ys_combine(A, un(row[i]));
-  part[threadIdx.x] = pk(A);
-  __syncthreads();
-  if (threadIdx.x == 0) {  // 256 partial aggregates: a serial exclusive scan
-    YsAgg run{0u, 0u, INT32_MIN, 1u};
-    for (uint32_t q = 0; q < 256; ++q) {
-      const YsAgg mine = un(part[q]);
-      part[q] = pk(run);
-      run = ys_combine(run, mine);
-    }
-  }
-  __syncthreads();
-  YsAgg run = un(part[threadIdx.x]);
-  for (uint32_t i = i0; i < i1; ++i) {
-    const YsAgg mine = un(row[i]);
-    row[i] = pk(run);
-    run = ys_combine(run, mine);
-  }
-}
-// block l: row l of the table -> exclusive prefix in place, row total -> totals[l]
-__global__ __launch_bounds__(1024) void yd_lscan_k(uint32_t* __restrict__ table, uint32_t ntiles, uint64_t* __restrict__ totals,
-                                                   unsigned long long* __restrict__ nit /* zeroed: the items of all lists */) {
-  __shared__ uint32_t sm[16];
-  __shared__ uint32_t carry_s;
-  uint32_t* row = table + (size_t)blockIdx.x * ntiles;
-  constexpr uint32_t E = 8;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (uint32_t base = 0; base < ntiles; base += 1024 * E) {
-    const uint32_t i0 = base + threadIdx.x * E;
-    uint32_t v[E], s = 0;
-#pragma unroll
-    for (uint32_t e = 0; e < E; ++e) {
-      v[e] = i0 + e < ntiles ? row[i0 + e] : 0u;
-      s += v[e];
-    }
-    uint32_t tot;
-    uint32_t ex = carry_s + block_excl_sum<uint32_t, 1024>(s, sm, &tot);
-#pragma unroll
-    for (uint32_t e = 0; e < E; ++e) {
-      if (i0 + e < ntiles) row[i0 + e] = ex;
-      ex += v[e];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) carry_s += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    totals[blockIdx.x] = carry_s;
-    atomicAdd(nit, (unsigned long long)carry_s);  // (128 blocks: the sum that was a launch of its own)
-  }
-}
-
-// The item -> group word: the low half of the 64-bit item words of the radix split, or (items placed by list) an array of its own.
-struct YdWords {
-  const uint64_t* w64;
-  const uint32_t* w32;
-  __device__ __forceinline__ uint32_t group(uint32_t t) const { return w32 ? w32[t] : (uint32_t)w64[t]; }
-};
-struct YdItems {
-  uint4* pk;      // (tid + 1, start, end, offset of the item's exon list in the per-group exon arrays): written with one store
-  uint32_t* nex;  // exon count (contiguous: the input of the node-offset scan); items placed by list: bit 31 = the item opens a chain
-  // Items placed by list (<= 64 inputs) are lean: (start, end) only — 16 bytes an item with the exon count and the group word
-  // instead of 24.  The reference id is not needed behind the placement (the heads are flagged there), and the exon offset, which
-  // only the spliced items use (one in twelve on config 3), is read from the item's group.
-  uint2* se = nullptr;
-  const uint32_t* gxoff = nullptr;  // per group: offset of its exon list (YdGroups::xoff)
-  __device__ __forceinline__ uint4 rec(uint32_t t) const {
-    if (se) {
-      const uint2 a = se[t];
-      return make_uint4(0u, a.x, a.y, 0u);
-    }
-    return pk[t];
-  }
-  __device__ __forceinline__ uint32_t xo_of(const uint4& it, uint32_t group) const { return se ? gxoff[group] : it.w; }
-  __device__ __forceinline__ uint32_t tidp1(uint32_t t) const { return reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t]; }
-  __device__ __forceinline__ int32_t start(uint32_t t) const { return (int32_t) reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 1]; }
-  __device__ __forceinline__ int32_t end(uint32_t t) const { return (int32_t) reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 2]; }
-  __device__ __forceinline__ uint32_t xo(uint32_t t) const { return reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 3]; }
-};
-
 // per output group (computed once, every item of the group reuses it): coordinates, exon count, exon list
 struct YdGroups {
   uint4* pk;       // (tid + 1, start, end, exon word): one 16-byte gather per item instead of four
-  uint32_t* nex;   // the exon counts, contiguous, as the input of the offset scan
-  uint32_t* xoff;
+  uint32_t* nex;   // the exon counts, contiguous, as the input of the offset scan (null where the count pass sums them per tile)
+  uint32_t* xoff;  // first slot of a FAR group's exons in the groups' exon arrays (items placed by list: no other entry is written)
 };
 // The exon word of a group / an item (YdGroups::pk.w, YdItems::nex): the exon count — or, with bit 30 set, the two exons themselves:
 // a group whose key word is the exact code of the shape M N M carries the first block a : 10 and the gap g : 20 (strategy.hpp), so
@@ -719,22 +548,18 @@ __device__ __forceinline__ uint32_t yd_exons_from_key(uint64_t lo, uint32_t st, 
   }
   return 0u;
 }
-
-__global__ void yd_groups_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ gperm, GroupAcc G, const uint64_t* __restrict__ shi,
-                            const uint64_t* __restrict__ slo, YdGroups Q) {
-  uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
-  if (o >= ng) return;
-  uint32_t sg = gperm[o];
-  uint32_t q = G.first[sg];
-  uint64_t h = shi[q], l = slo[q];
-  int32_t st = (int32_t)(uint32_t)((h >> 2) & 0x7FFFFFFFull);
+// A group's record (tid + 1, start, end, exon word) from its key (h, l); the representative's CIGAR — rep[sg], a chain of dependent
+// loads — is walked only when the key word is no exact code.  Both makers of the records call this, yd_groups_k and the count pass of
+// the items placed by list (yd_lcount_k<true>): one definition of the coordinates and of the X2 packing.
+__device__ __forceinline__ uint4 yd_group_rec(const ColIn& I, uint64_t h, uint64_t l, const unsigned long long* __restrict__ rep, uint32_t sg) {
+  const int32_t st = (int32_t)(uint32_t)((h >> 2) & 0x7FFFFFFFull);
   const uint32_t tidp1 = (uint32_t)(h >> 33);
   const uint32_t en = (uint32_t)(st + (int32_t)(uint32_t)(l >> 32) - 1);
   uint32_t e0, s1;
   const uint32_t nk = yd_exons_from_key(l, (uint32_t)st, en, &e0, &s1);
   int nex = (int)nk;
   if (nex == 0) {
-    const uint32_t r = (uint32_t)(G.rep[sg] & 0xFFFFFFFFull);
+    const uint32_t r = (uint32_t)(rep[sg] & 0xFFFFFFFFull);
     walk_exons(I.pos[r], I.cig + I.cig_off[r], I.cig_off[r + 1] - I.cig_off[r], [](int, int) {}, &nex);
   }
   uint32_t xw = (uint32_t)nex;
@@ -742,10 +567,229 @@ __global__ void yd_groups_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ g
     const uint32_t a = e0 - (uint32_t)st + 1u, g = s1 - e0 - 1u;
     if (a < (1u << 10) && g < (1u << 20)) xw = YD_X2 | (a << 20) | g;
   }
-  // the exon arrays hold the groups whose exons no item word can say: several exons, not the exact two-exon shape (a single exon is
-  // (start, end); yd_gexons_k walks only those — a few per cent of an RNA-seq sample — and the offset scan counts only them)
-  Q.nex[o] = yd_nex_far(xw) ? (uint32_t)nex : 0u;
-  Q.pk[o] = make_uint4(tidp1, (uint32_t)st, en, xw);
+  return make_uint4(tidp1, (uint32_t)st, en, xw);
+}
+// the exon arrays hold the groups whose exons no item word can say: several exons, not the exact two-exon shape (a single exon is
+// (start, end); yd_gexons_k walks only those — a few per cent of an RNA-seq sample — and the offsets count only them)
+__device__ __forceinline__ uint32_t yd_far_count(uint32_t w) { return yd_nex_far(w) ? (w & 0x3FFFFFFFu) : 0u; }
+
+// A tile's items of list c are the set bits of column c, wave by wave.  The walk is two-level: every (wave, list) cell — two per
+// thread — folds its few items (three or four on average), thread c chains the sixteen cells of its list (ys_chain_cells), and the
+// cells are walked once more where the heads are wanted.  Aggregates live in LDS as three words (the `whole` bit rides in bit 31
+// of first_tid: tid + 1 < 2^31).
+struct YsCells {
+  uint32_t (*a)[YS_NL];  // first_tid | whole << 31
+  uint32_t (*b)[YS_NL];  // last_tid
+  int32_t (*m)[YS_NL];   // mx
+  __device__ __forceinline__ YsAgg get(uint32_t x, uint32_t c) const { return YsAgg{a[x][c] & 0x7FFFFFFFu, b[x][c], m[x][c], a[x][c] >> 31}; }
+  __device__ __forceinline__ void put(uint32_t x, uint32_t c, const YsAgg& v) const {
+    a[x][c] = v.first_tid | (v.whole << 31);
+    b[x][c] = v.last_tid;
+    m[x][c] = v.mx;
+  }
+};
+// cells -> the aggregate of the list's items before each cell (start: before the tile); returns the aggregate behind the last cell
+__device__ __forceinline__ YsAgg ys_chain_cells(const YsCells& P, uint32_t c, YsAgg run) {
+  for (uint32_t x = 0; x < YS_NT / 64; ++x) {
+    const YsAgg mine = P.get(x, c);
+    P.put(x, c, run);
+    run = ys_combine(run, mine);
+  }
+  return run;
+}
+// FRONT: the pass makes the groups' records itself — it holds the key's first word already, the second is all the record needs for
+// nearly every group (yd_group_rec), and no pass of its own (yd_groups_k) then reads the permutation and the keys a second time to
+// write what this one would read back.  The exon offsets come without a device-wide scan over the mostly-zero counts: the tile's far
+// exons are one more row of the table (row YS_NL), yd_lscan_k turns the row into the tiles' bases, and yd_lscatter_k adds the prefix
+// inside the tile.  The keys are the groups' own arrays here (WgOut::ghi / glo, WgOut::first == identity: wg_compact_k is the only
+// producer of a job whose items are placed by list — the merge of group partials, pr_compact_k, has no YD stage), so the first-record
+// indirection of yd_groups_k is not taken.  !FRONT (yd_front=split): the records are read from gpk.
+template <bool FRONT>
+__global__ __launch_bounds__(YS_NT) void yd_lcount_k(YsIn S, ColIn I, const uint64_t* __restrict__ glo, const unsigned long long* __restrict__ rep,
+                                                     uint4* __restrict__ gpk /* YdGroups::pk: FRONT ? written : read */, uint32_t ntiles,
+                                                     uint32_t* __restrict__ table /* [YS_NL + FRONT][ntiles] */, uint4* __restrict__ agg /* [YS_NL][ntiles] */,
+                                                     uint64_t* __restrict__ gwb /* [ntiles][YS_NT / 64][YS_NL]: the columns, for yd_lscatter_k */) {
+  __shared__ uint64_t wb[YS_NT / 64][YS_NL];
+  __shared__ uint32_t g_tid[YS_NT];
+  __shared__ int32_t g_e1[YS_NT];
+  __shared__ uint32_t pa[YS_NT / 64][YS_NL], pb[YS_NT / 64][YS_NL];
+  __shared__ int32_t pm[YS_NT / 64][YS_NL];
+  __shared__ uint32_t wfar[YS_NT / 64];  // (FRONT) far exons of the wave's groups
+  const YsCells P{pa, pb, pm};
+  uint64_t lo = 0, hi = 0;
+  {
+    const uint32_t o = blockIdx.x * YS_NT + threadIdx.x;
+    uint32_t nfar = 0;
+    if (o < S.ng) {
+      const uint32_t sg = S.gperm[o];
+      const uint64_t h = S.ghi[sg];
+      const uint32_t c = (uint32_t)h & 3u;
+      const uint32_t n = S.gfmask ? 0u : S.ns[sg], p0 = S.gfmask ? 0u : S.gpoff[sg];
+      uint64_t files = 0;
+      if (S.gfmask)
+        files = S.gfmask[sg];
+      else
+        for (uint32_t i = 0; i < n; ++i) files |= 1ull << S.pfile[p0 + i];
+      ys_mask_from_files(files, c, &lo, &hi);
+      uint4 g;
+      if constexpr (FRONT) {
+        g = yd_group_rec(I, h, glo[sg], rep, sg);
+        gpk[o] = g;
+        nfar = yd_far_count(g.w);
+      } else {
+        g = gpk[o];
+      }
+      g_tid[threadIdx.x] = g.x;
+      g_e1[threadIdx.x] = (int32_t)g.z + 1;
+    }
+    if constexpr (FRONT) {
+      nfar = wave_sum(nfar);
+      if (lane_id() == 0) wfar[threadIdx.x >> 6] = nfar;
+    }
+  }
+  {
+    const uint32_t x = threadIdx.x >> 6, l = lane_id();
+    const uint64_t a = wave_bit_transpose(lo), b = wave_bit_transpose(hi);  // lane c: the groups of this wave in lists c and 64 + c
+    wb[x][l] = a;
+    wb[x][64u + l] = b;
+    uint64_t* out = gwb + (size_t)blockIdx.x * (YS_NT / 64) * YS_NL + x * YS_NL;  // (groups past ng: empty rows, zero bits)
+    out[l] = a;
+    out[64u + l] = b;
+  }
+  __syncthreads();
+  for (uint32_t q = threadIdx.x; q < (YS_NT / 64) * YS_NL; q += YS_NT) {
+    const uint32_t x = q / YS_NL, c = q % YS_NL;
+    YsAgg A{0u, 0u, INT32_MIN, 1u};
+    for (uint64_t m = wb[x][c]; m; m &= m - 1) {
+      const uint32_t g = x * 64u + (uint32_t)__builtin_ctzll(m);
+      A = ys_combine(A, YsAgg{g_tid[g], g_tid[g], g_e1[g], 1u});
+    }
+    P.put(x, c, A);
+  }
+  __syncthreads();
+  if (threadIdx.x < YS_NL) {
+    const uint32_t c = threadIdx.x;
+    uint32_t n = 0;
+    YsAgg A{0u, 0u, INT32_MIN, 1u};
+    for (uint32_t x = 0; x < YS_NT / 64; ++x) {
+      n += (uint32_t)__builtin_popcountll(wb[x][c]);
+      A = ys_combine(A, P.get(x, c));
+    }
+    table[(size_t)c * ntiles + blockIdx.x] = n;
+    agg[(size_t)c * ntiles + blockIdx.x] = make_uint4(A.first_tid, A.last_tid, (uint32_t)A.mx, A.whole);
+  }
+  if constexpr (FRONT) {
+    if (threadIdx.x == YS_NL) {  // (a wave with no list's row to write) the tile's far exons: row YS_NL
+      uint32_t n = 0;
+      for (uint32_t x = 0; x < YS_NT / 64; ++x) n += wfar[x];
+      table[(size_t)YS_NL * ntiles + blockIdx.x] = n;
+    }
+  }
+}
+// block l: row l of the aggregates -> exclusive prefix in place (the aggregate of the list's items in the tiles before)
+__global__ __launch_bounds__(256) void yd_lagg_scan_k(uint4* __restrict__ agg, uint32_t ntiles) {
+  __shared__ uint4 part[256];
+  uint4* row = agg + (size_t)blockIdx.x * ntiles;
+  const uint32_t per = (ntiles + 255u) / 256u, i0 = threadIdx.x * per, i1 = i0 + per < ntiles ? i0 + per : ntiles;
+  auto un = [](const uint4& v) { return YsAgg{v.x, v.y, (int32_t)v.z, v.w}; };
+  auto pk = [](const YsAgg& a) { return make_uint4(a.first_tid, a.last_tid, (uint32_t)a.mx, a.whole); };
+  YsAgg A{0u, 0u, INT32_MIN, 1u};
+  for (uint32_t i = i0; i < i1; ++i) A = ys_combine(A, un(row[i]));
+  part[threadIdx.x] = pk(A);
+  __syncthreads();
+  if (threadIdx.x == 0) {  // 256 partial aggregates: a serial exclusive scan
+    YsAgg run{0u, 0u, INT32_MIN, 1u};
+    for (uint32_t q = 0; q < 256; ++q) {
+      const YsAgg mine = un(part[q]);
+      part[q] = pk(run);
+      run = ys_combine(run, mine);
+    }
+  }
+  __syncthreads();
+  YsAgg run = un(part[threadIdx.x]);
+  for (uint32_t i = i0; i < i1; ++i) {
+    const YsAgg mine = un(row[i]);
+    row[i] = pk(run);
+    run = ys_combine(run, mine);
+  }
+}
+// block l: row l of the table -> exclusive prefix in place, row total -> totals[l].  Block YS_NL (launched when the count pass made the
+// groups' records, yd_lcount_k<true>): the row of the tiles' far exons -> every tile's first slot in the groups' exon arrays, its
+// total -> *ngex; that row counts exons, not items, and stays out of nit.
+__global__ __launch_bounds__(1024) void yd_lscan_k(uint32_t* __restrict__ table, uint32_t ntiles, uint64_t* __restrict__ totals,
+                                                   unsigned long long* __restrict__ nit /* zeroed: the items of all lists */,
+                                                   unsigned long long* __restrict__ ngex) {
+  __shared__ uint32_t sm[16];
+  __shared__ uint32_t carry_s;
+  uint32_t* row = table + (size_t)blockIdx.x * ntiles;
+  constexpr uint32_t E = 8;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  for (uint32_t base = 0; base < ntiles; base += 1024 * E) {
+    const uint32_t i0 = base + threadIdx.x * E;
+    uint32_t v[E], s = 0;
+#pragma unroll
+    for (uint32_t e = 0; e < E; ++e) {
+      v[e] = i0 + e < ntiles ? row[i0 + e] : 0u;
+      s += v[e];
+    }
+    uint32_t tot;
+    uint32_t ex = carry_s + block_excl_sum<uint32_t, 1024>(s, sm, &tot);
+#pragma unroll
+    for (uint32_t e = 0; e < E; ++e) {
+      if (i0 + e < ntiles) row[i0 + e] = ex;
+      ex += v[e];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) carry_s += tot;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    totals[blockIdx.x] = carry_s;
+    if (blockIdx.x < YS_NL)
+      atomicAdd(nit, (unsigned long long)carry_s);  // (128 blocks: the sum that was a launch of its own)
+    else
+      *ngex = carry_s;
+  }
+}
+
+// The item -> group word: the low half of the 64-bit item words of the radix split, or (items placed by list) an array of its own.
+struct YdWords {
+  const uint64_t* w64;
+  const uint32_t* w32;
+  __device__ __forceinline__ uint32_t group(uint32_t t) const { return w32 ? w32[t] : (uint32_t)w64[t]; }
+};
+struct YdItems {
+  uint4* pk;      // (tid + 1, start, end, offset of the item's exon list in the per-group exon arrays): written with one store
+  uint32_t* nex;  // exon count (contiguous: the input of the node-offset scan); items placed by list: bit 31 = the item opens a chain
+  // Items placed by list (<= 64 inputs) are lean: (start, end) only — 16 bytes an item with the exon count and the group word
+  // instead of 24.  The reference id is not needed behind the placement (the heads are flagged there), and the exon offset, which
+  // only the spliced items use (one in twelve on config 3), is read from the item's group.
+  uint2* se = nullptr;
+  const uint32_t* gxoff = nullptr;  // per group: offset of its exon list (YdGroups::xoff)
+  __device__ __forceinline__ uint4 rec(uint32_t t) const {
+    if (se) {
+      const uint2 a = se[t];
+      return make_uint4(0u, a.x, a.y, 0u);
+    }
+    return pk[t];
+  }
+  __device__ __forceinline__ uint32_t xo_of(const uint4& it, uint32_t group) const { return se ? gxoff[group] : it.w; }
+  __device__ __forceinline__ uint32_t tidp1(uint32_t t) const { return reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t]; }
+  __device__ __forceinline__ int32_t start(uint32_t t) const { return (int32_t) reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 1]; }
+  __device__ __forceinline__ int32_t end(uint32_t t) const { return (int32_t) reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 2]; }
+  __device__ __forceinline__ uint32_t xo(uint32_t t) const { return reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 3]; }
+};
+
+__global__ void yd_groups_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ gperm, GroupAcc G, const uint64_t* __restrict__ shi,
+                            const uint64_t* __restrict__ slo, YdGroups Q) {
+  uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= ng) return;
+  uint32_t sg = gperm[o];
+  uint32_t q = G.first[sg];
+  const uint4 g = yd_group_rec(I, shi[q], slo[q], G.rep, sg);
+  Q.nex[o] = yd_far_count(g.w);  // (the input of the offset scan)
+  Q.pk[o] = g;
 }
 
 __global__ void yd_gexons_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ gperm, GroupAcc G, const uint64_t* __restrict__ slo, YdGroups Q,
@@ -753,7 +797,7 @@ __global__ void yd_gexons_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ g
   uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= ng) return;
   const uint4 pk = Q.pk[o];
-  if (!yd_nex_far(pk.w)) return;  // (nothing reads the arrays for it: yd_groups_k counted no slot)
+  if (!yd_nex_far(pk.w)) return;  // (nothing reads the arrays for it: no slot was counted, yd_far_count)
   const uint32_t sg = gperm[o];
   uint32_t w = Q.xoff[o];
   {
@@ -808,7 +852,10 @@ static_assert(YS_NC == 2 * YS_NT && YS_CAP >= 4 * YS_NC, "the staging array hold
 __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t ntiles, const uint32_t* __restrict__ table,
                                                        const uint64_t* __restrict__ totals, const uint4* __restrict__ agg,
                                                        const uint64_t* __restrict__ gwb /* yd_lcount_k's columns */, YdGroups Q,
-                                                       YdItems Y, uint32_t* __restrict__ item) {
+                                                       YdItems Y, uint32_t* __restrict__ item,
+                                                       const uint32_t* __restrict__ xbase /* the tiles' first exon slots (row YS_NL of the
+                                                       table behind yd_lscan_k), or null: Q.xoff is made already */) {
+  __shared__ uint32_t wfar[YS_NT / 64];  // far exons of a wave's groups
   __shared__ uint32_t off[YS_NL];      // first position of this tile's items of list c, less pre[c]
   __shared__ uint32_t pre[YS_NL + 1];  // the tile's items in lists before c
   __shared__ uint32_t lsum[YS_NL];     // items of list c in this tile
@@ -823,8 +870,24 @@ __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t nti
   const uint64_t m0 = col[t], m1 = col[YS_NT + t];
   if (t < YS_NL) lbase[t] = (uint32_t)totals[t];
   const uint32_t o = blockIdx.x * YS_NT + t;
-  if (o < ng) grec[t] = Q.pk[o];
+  uint32_t nfar = 0, finc = 0;
+  if (o < ng) {
+    const uint4 g = Q.pk[o];
+    grec[t] = g;
+    nfar = yd_far_count(g.w);
+  }
+  if (xbase) {
+    finc = wave_incl_sum(nfar);
+    if (lane_id() == 63) wfar[t >> 6] = finc;
+  }
   __syncthreads();
+  // the exon offset of a far group: the tile's base and the far exons of the tile's groups before it.  Only far groups get one —
+  // its readers (YdItems::xo_of in the list machines, yd_gexons_k) ask for the offset of a far item / group and no other.
+  if (xbase && nfar) {
+    uint32_t b = xbase[blockIdx.x] + finc - nfar;
+    for (uint32_t x = 0; x < (t >> 6); ++x) b += wfar[x];
+    Q.xoff[o] = b;
+  }
   auto fold = [&](uint64_t m, uint32_t x) {  // the cell's items -> one aggregate
     pa[x][c] = (uint32_t)__builtin_popcountll(m);
     YsAgg A{0u, 0u, INT32_MIN, 1u};
@@ -1930,6 +1993,7 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
     uint64_t nit64;
     const bool by_list = J.win && (!J.pgrp || tbk_yd_by_list(ctx, I.k));  // (no per-incidence group array: the window stage has decided)
     static_assert(YS_NL == 128, "tbk_yd_by_list (wgroup.h) knows the number of lists");
+    const bool split_front = ctx->dbg.yd_front_split;
     const uint32_t ys_tiles = cdiv(ng, YS_NT);
     const YsIn S{ng, J.gperm, J.G.ns, J.gpoff, J.pfile, J.shi, J.gfmask};
     uint32_t* ys_table = nullptr;
@@ -1938,19 +2002,26 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
     uint64_t* ys_wb = nullptr;  // the tiles' bit columns (yd_lcount_k -> yd_lscatter_k)
     uint32_t *yd_d = nullptr, *ys_item = nullptr;
     YdGroups Q{};
-    if (by_list) {  // the groups' coordinates first (the first pass folds them); then items and aggregates per (list, tile of groups)
+    if (by_list) {  // items and aggregates per (list, tile of groups); the count pass makes the groups' records on its way (it folds them)
       Q.pk = ws_alloc<uint4>(ctx, ng);
-      Q.nex = ws_alloc<uint32_t>(ctx, ng);
+      Q.nex = split_front ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
       Q.xoff = ws_alloc<uint32_t>(ctx, ng);
-      ys_table = ws_alloc<uint32_t>(ctx, (size_t)YS_NL * ys_tiles);
+      ys_table = ws_alloc<uint32_t>(ctx, (size_t)(YS_NL + 1) * ys_tiles);  // (row YS_NL: the tiles' far exons)
       ys_agg = ws_alloc<uint4>(ctx, (size_t)YS_NL * ys_tiles);
       ys_totals = ws_alloc<uint64_t>(ctx, YS_NL + 1);
       ys_wb = ws_alloc<uint64_t>(ctx, (size_t)ys_tiles * YS_NC);
-      if (!Q.xoff || !ys_table || !ys_agg || !ys_totals || !ys_wb) return TBK_ENOMEM;
-      TBK_LAUNCH(ctx, "yd_groups", yd_groups_k, cdiv(ng, B), B, 0, I, ng, J.gperm, J.G, J.shi, J.slo, Q);
-      TBK_TRY(tbk_exscan_u32(ctx, Q.nex, Q.xoff, ng, sc + 5));
-      TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k, ys_tiles, YS_NT, 0, S, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
-      TBK_LAUNCH(ctx, "yd_lscan", yd_lscan_k, YS_NL, 1024, 0, ys_table, ys_tiles, ys_totals, (unsigned long long*)(sc + 2));
+      if (!Q.xoff || (split_front && !Q.nex) || !ys_table || !ys_agg || !ys_totals || !ys_wb) return TBK_ENOMEM;
+      if (split_front) {  // yd_front=split (test hook): the records and the exon offsets by passes of their own, as on the other paths
+        TBK_LAUNCH(ctx, "yd_groups", yd_groups_k, cdiv(ng, B), B, 0, I, ng, J.gperm, J.G, J.shi, J.slo, Q);
+        TBK_TRY(tbk_exscan_u32(ctx, Q.nex, Q.xoff, ng, sc + 5));
+        TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k<false>, ys_tiles, YS_NT, 0, S, I, J.slo, J.G.rep, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
+        TBK_LAUNCH(ctx, "yd_lscan", yd_lscan_k, YS_NL, 1024, 0, ys_table, ys_tiles, ys_totals, (unsigned long long*)(sc + 2),
+                   (unsigned long long*)nullptr);
+      } else {  // the count pass makes the records; the exon offsets ride through its table (sc[5]: the exons of all far groups)
+        TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k<true>, ys_tiles, YS_NT, 0, S, I, J.slo, J.G.rep, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
+        TBK_LAUNCH(ctx, "yd_lscan", yd_lscan_k, YS_NL + 1, 1024, 0, ys_table, ys_tiles, ys_totals, (unsigned long long*)(sc + 2),
+                   (unsigned long long*)(sc + 5));
+      }
       TBK_LAUNCH(ctx, "yd_lscan", yd_lagg_scan_k, YS_NL, 256, 0, ys_agg, ys_tiles);
     } else if (J.win) {  // items per output group straight from the per-group sample counts
       ocnt = ws_alloc<uint32_t>(ctx, ng);
@@ -2012,7 +2083,8 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
         TBK_TRY(tbk_exscan_u32(ctx, Q.nex, Q.xoff, ng, sc + 5));
       }
       if (by_list) {
-        TBK_LAUNCH(ctx, "yd_scatter", yd_lscatter_k, ys_tiles, YS_NT, 0, ng, ys_tiles, ys_table, ys_totals, ys_agg, ys_wb, Q, Y, io);
+        TBK_LAUNCH(ctx, "yd_scatter", yd_lscatter_k, ys_tiles, YS_NT, 0, ng, ys_tiles, ys_table, ys_totals, ys_agg, ys_wb, Q, Y, io,
+                   split_front ? (const uint32_t*)nullptr : ys_table + (size_t)YS_NL * ys_tiles);
       } else {  // stable split by list id (file * 2 + strand list); group order is already in place.  The id range is known:
         uint32_t bits = 1;  // no scan for the varying bits
         while ((1ull << bits) < 2ull * I.k) ++bits;
@@ -2364,10 +2436,13 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       G.tie = wo.tie;
       g_yd = ws_alloc<int32_t>(ctx, ng);
       gperm = ws_alloc<uint32_t>(ctx, ng);
-      ginv = ws_alloc<uint32_t>(ctx, ng);
-      if (!ginv) return TBK_ENOMEM;
       // (items placed by list leave their distances with the items, yd_lgather_k: nothing accumulates in g_yd then)
-      if (!(!wo.pgrp || tbk_yd_by_list(ctx, I.k))) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
+      const bool yd_by_list = !wo.pgrp || tbk_yd_by_list(ctx, I.k);
+      // the inverse permutation has two readers on this path, col_recgroup_w_k and yd_fill_w_k (items NOT placed by list): not made
+      // when neither will run
+      ginv = (out->rec_group || !yd_by_list) ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
+      if (!gperm || ((out->rec_group || !yd_by_list) && !ginv)) return TBK_ENOMEM;
+      if (!yd_by_list) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
       const uint64_t* png = sc + 1;  // (tbk_window_groups left the group count there)
       TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng, B), B, 0, I, O.strategy, png, wo.gmem, G, gperm, ginv);
       // (effend == nullptr: the effective end of the representative — or the low word of its explicit priority — rides in the
@@ -2442,10 +2517,13 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       G.tie = wo.tie;
       g_yd = ws_alloc<int32_t>(ctx, ng);
       gperm = ws_alloc<uint32_t>(ctx, ng);
-      ginv = ws_alloc<uint32_t>(ctx, ng);
-      if (!ginv) return TBK_ENOMEM;
       // (items placed by list leave their distances with the items, yd_lgather_k: nothing accumulates in g_yd then)
-      if (!(!wo.pgrp || tbk_yd_by_list(ctx, I.k))) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
+      const bool yd_by_list = !wo.pgrp || tbk_yd_by_list(ctx, I.k);
+      // the inverse permutation has two readers on this path, col_recgroup_w_k and yd_fill_w_k (items NOT placed by list): not made
+      // when neither will run
+      ginv = (out->rec_group || !yd_by_list) ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
+      if (!gperm || ((out->rec_group || !yd_by_list) && !ginv)) return TBK_ENOMEM;
+      if (!yd_by_list) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
       const uint64_t* png = sc + 1;  // (tbk_window_groups left the group count there)
       TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng, B), B, 0, I, O.strategy, png, wo.gmem, G, gperm, ginv);
       TBK_LAUNCH(ctx, "col_write", col_write_k<false>, cdiv(ng, B), B, 0, png, gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,

@@ -511,6 +511,7 @@ void tbk_debug_parse(const char* spec, TbkDebug* out) {
     else if (k == "yd_bgrid") out->yd_bgrid = (uint32_t)u;
     else if (k == "yd_radix") out->yd_radix = on;
     else if (k == "yd_literal") out->yd_literal = on;
+    else if (k == "yd_front") out->yd_front_split = v == "split";
     else if (k == "yd_own_arena") out->yd_own_arena = on;
     else if (k == "wg_dense_verify") out->wg_dense_verify = on;
     else if (k == "wg_rank_merge") out->wg_rank_merge = on;

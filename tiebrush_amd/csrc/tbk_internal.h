@@ -95,6 +95,8 @@ struct TbkDebug {
   uint32_t yd_bgrid = 0;      // yd_bgrid=N: blocks of the chain bucketing (0: default)
   bool yd_radix = false;      // yd_radix=1: the YD items through the stable radix split for any tile
   bool yd_literal = false;    // yd_literal=1: every chain through yd_run_k, the literal list machine (normally the lists that outgrow the others)
+  bool yd_front_split = false;  // yd_front=split: (items placed by list) the groups' records and exon offsets by passes of their own, yd_groups_k and
+                                // a device-wide scan, ahead of the count pass (default, yd_front=fused: the count pass makes them)
   bool yd_own_arena = false;  // yd_own_arena=1: a deferred YD stage never borrows the main arena
   bool wg_dense_verify = false, wg_rank_merge = false;  // window path: per-record verification form; merge-sort ranking of a window's groups
   bool cov_legacy = false, cov_bundle_scan = false, cov_prep = false, junc_radix = false, no_junc_agg = false;
