@@ -577,6 +577,31 @@ int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_see
 int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end);
 int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, int64_t beg, int64_t end);
 
+/* ---- One region of indexed inputs as a collapse tile (ABI version 8, appended) ------------------------------------------
+ * What `tiebrush -r REGION` runs on the chunks every input's index names for the region.  The reference has no region option
+ * (tiebrush.cpp:570-592 pops every record of every input through TInputFiles::next), so these entries replace no interface of it. */
+
+/* tbk_bam_decode for files given as runs of spans.  Spans [span_first[f], span_first[f+1]) are file f's chunks in file order (a file
+ * may have none; span_first[n_files + 1] is HOST, span_first[0] = 0); comp / comp_bytes / first_uoff / last_uoff describe the spans as
+ * in tbk_bam_decode_spans.  Per file exactly what tbk_bam_decode does: YC / YX / YD read only for files flagged in tbmerged, MD with
+ * want_md, QNAME + hash with want_names.  file_off_out[n_files + 1] = record ranges per FILE, what tile->file_off points to;
+ * tile->tbmerged is the caller's array.  TBK_E2BIG for more than 65535 spans in all; no span at all: an empty tile, status 0. */
+int tbk_bam_decode_file_spans(tbk_ctx* ctx, uint32_t n_files, const uint32_t* span_first, const uint8_t* const* comp, const uint64_t* comp_bytes,
+                              const uint32_t* first_uoff, const uint32_t* last_uoff, int32_t n_ref, const uint8_t* tbmerged, int want_md,
+                              int want_names, tbk_soa_in* tile, uint32_t* file_off_out);
+
+/* The records of the tile the last decode on ctx returned that overlap [beg, end) on tid (tbk_region_view's rule), as a collapse tile:
+ * every column the input carries (tid pos flag mapq strand nh, CIGAR CSR, yc / yx / yd_in, MD CSR + md_has, qname CSR + qname_hash; a
+ * column the input lacks stays NULL), file order kept, file_off_out[n_files + 1] (HOST, caller's; may be the input's own array) the
+ * kept ranges per file, and the context's record-offset table compacted alike — afterwards tbk_collapse_tile, tbk_bam_records,
+ * tbk_bam_encode(_indexed), tbk_groups_to_cov_in and tbk_kept_results speak in the compacted indices.  SEQ / QUAL never move: the
+ * inflated records stay where they are.  The input tile is consumed; *out lives in context-owned memory until tbk_bam_release or the
+ * next decode.  TBK_EINVAL for a tile that is not the context's decoded one (a joined tile included): nothing is changed and the
+ * context takes the next call.  Only the struct the decode filled in, passed on unchanged, is supported: the tile is recognised by its
+ * tid column and record count, so a struct that carries those beside columns of the caller's own is not refused. */
+int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid, int64_t beg, int64_t end, tbk_soa_in* out, uint32_t* file_off_out,
+                    uint32_t* n_kept);
+
 #ifdef __cplusplus
 }
 #endif

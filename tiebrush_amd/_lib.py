@@ -28,7 +28,7 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_groups_to_cov_in", "tbk_bgzf_inflate", "tbk_bam_decode", "tbk_bam_records", "tbk_bam_release", "tbk_shard_prepare", "tbk_shard_probe_max", "tbk_shard_probe_next",
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
-           "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip"]
+           "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region"]
 
 
 class CollapseOpts(C.Structure):
@@ -201,6 +201,10 @@ def load():
     L.tbk_cov_clip.restype = C.c_int
     L.tbk_sample_clip.argtypes = [_P, C.POINTER(SampleOut), C.c_int32, C.c_int64, C.c_int64]
     L.tbk_sample_clip.restype = C.c_int
+    L.tbk_bam_decode_file_spans.argtypes = [_P, C.c_uint32, _P, _P, _P, _P, _P, C.c_int32, _P, C.c_int, C.c_int, C.POINTER(SoaIn), _P]
+    L.tbk_bam_decode_file_spans.restype = C.c_int
+    L.tbk_tile_region.argtypes = [_P, C.POINTER(SoaIn), C.c_int32, C.c_int64, C.c_int64, C.POINTER(SoaIn), _P, C.POINTER(C.c_uint32)]
+    L.tbk_tile_region.restype = C.c_int
     _lib = L
     return L
 

@@ -483,6 +483,39 @@ class Context:
         assert int(nk.value) == int(v.n_records)
         return DeviceCovView(v, int(v.n_records), int(v.n_cigar_ops))
 
+    def bam_decode_file_spans(self, file_spans, n_ref, tbmerged=None, want_md=False, want_names=False):
+        """tbk_bam_decode_file_spans: file_spans = per input file the list of its spans [(bytes of whole BGZF members, first_uoff,
+        last_uoff)] (a file may have none) -> (SoaIn struct of the device-resident tile, file_off [n_files + 1]).  The arrays live in the
+        context until bam_release() or the next decode."""
+        k = len(file_spans)
+        spans = [s for f in file_spans for s in f]
+        m = len(spans)
+        first = np.zeros(k + 1, dtype=np.uint32)
+        first[1:] = np.cumsum([len(f) for f in file_spans])
+        bufs = [np.frombuffer(z, dtype=np.uint8) for z, _, _ in spans]
+        ptrs = (C.c_void_p * max(m, 1))(*[b.ctypes.data if len(b) else None for b in bufs])
+        sizes = np.array([len(b) for b in bufs], dtype=np.uint64)
+        fu = np.array([s[1] for s in spans], dtype=np.uint32)
+        lu = np.array([s[2] for s in spans], dtype=np.uint32)
+        tb = np.ascontiguousarray(tbmerged if tbmerged is not None else np.zeros(k, np.uint8), dtype=np.uint8)
+        fo = np.zeros(k + 1, dtype=np.uint32)
+        s = _lib.SoaIn()
+        self._check(self.L.tbk_bam_decode_file_spans(self.h, k, first.ctypes.data, ptrs, sizes.ctypes.data, fu.ctypes.data, lu.ctypes.data, int(n_ref),
+                                                     tb.ctypes.data, int(want_md), int(want_names), C.byref(s), fo.ctypes.data), "tbk_bam_decode_file_spans")
+        self._bam_keep = (bufs, tb, fo)
+        return s, fo
+
+    def tile_region(self, tile_struct, tid, beg, end):
+        """tbk_tile_region: the records of the context's decoded tile overlapping [beg, end) on tid as a collapse tile -> (SoaIn struct,
+        file_off [n_files + 1]); the input tile is consumed, tile indices are the compacted ones from here on"""
+        k = int(tile_struct.n_files)
+        fo = np.zeros(k + 1, dtype=np.uint32)
+        out, nk = _lib.SoaIn(), C.c_uint32(0)
+        self._check(self.L.tbk_tile_region(self.h, C.byref(tile_struct), int(tid), int(beg), int(end), C.byref(out), fo.ctypes.data, C.byref(nk)), "tbk_tile_region")
+        assert int(nk.value) == int(out.n_records)
+        self._region_keep = (fo, getattr(self, "_bam_keep", None))
+        return out, fo
+
     def cov_clip(self, res, tid, beg, end):
         """tbk_cov_clip: the result dict of coverage() cut to [beg, end) on tid (numpy rows or device tensors), as a new dict"""
         keep = []

@@ -990,6 +990,7 @@ struct BamDev {
   uint32_t n = 0;
   std::vector<void*> owned;    // device allocations of the decoded tile
   std::vector<uint8_t> tbm_host;  // tbk_bam_decode_spans: what tile->tbmerged points to
+  const int32_t* tile_tid = nullptr;  // the tid column of the tile the decode returned (tbk_tile_region: is a tile this one?)
 };
 
 }  // namespace
@@ -1119,7 +1120,8 @@ namespace {
 struct SpanArgs {
   const uint32_t *first_uoff, *last_uoff;
   int32_t n_ref;             // the header's: what bam_header_k reads from a file
-  const uint8_t** seen_out;  // device [n_records]: BamSoA::seen
+  const uint8_t** seen_out;  // device [n_records]: BamSoA::seen (NULL: not wanted)
+  const uint8_t* span_tbm;   // host [n_spans]: the tbmerged flag of the file that owns the span (NULL: YC / YX / YD read for every record)
 };
 }  // namespace
 
@@ -1221,7 +1223,7 @@ static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const*
     tile->n_files = k;
     tile->file_off = file_off_out;
     for (uint32_t f = 0; f <= k; ++f) file_off_out[f] = 0;
-    *sp->seen_out = nullptr;
+    if (sp->seen_out) *sp->seen_out = nullptr;
     return 0;
   }
   if (mt.empty()) {
@@ -1250,6 +1252,7 @@ static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const*
   TBK_HIP(hipMemcpyAsync(d_tab + 3 * k, cap_off.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
   std::vector<uint8_t> tb(k, sp ? 1 : 0);  // (spans: YC / YX of every record are read)
   if (tbmerged && !sp) memcpy(tb.data(), tbmerged, k);
+  if (sp && sp->span_tbm) memcpy(tb.data(), sp->span_tbm, k);
   TBK_HIP(hipMemcpyAsync(d_tbm, tb.data(), k, hipMemcpyHostToDevice, ctx->stream));
   TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
   // the files go up in groups of ~ 192 MB through the pinned ring, and a group is inflated while the next one is on its way
@@ -1349,7 +1352,7 @@ static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const*
     S.yx = bd_alloc<int64_t>(B, n);
     S.yd = bd_alloc<int64_t>(B, n);
   }
-  if (sp) {
+  if (sp && sp->seen_out) {
     S.seen = bd_alloc<uint8_t>(B, n);
     if (!S.seen) return TBK_ENOMEM;
   }
@@ -1414,8 +1417,9 @@ static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const*
   if (sp) {
     B->tbm_host = tb;
     tile->tbmerged = B->tbm_host.data();
-    *sp->seen_out = S.seen;
+    if (sp->seen_out) *sp->seen_out = S.seen;
   }
+  B->tile_tid = S.tid;
   tile->tid = S.tid;
   tile->pos = S.pos;
   tile->flag = S.flag;
@@ -1458,8 +1462,64 @@ extern "C" int tbk_bam_decode_spans(tbk_ctx* ctx, uint32_t n_spans, const uint8_
     return 0;
   }
   if (!first_uoff || !last_uoff) return TBK_EINVAL;
-  SpanArgs sp{first_uoff, last_uoff, n_ref, tag_seen_out};
+  SpanArgs sp{first_uoff, last_uoff, n_ref, tag_seen_out, nullptr};
   return bam_decode_impl(ctx, n_spans, comp, comp_bytes, nullptr, 0, 0, tile, span_off_out, &sp);
+}
+
+// files given as runs of spans (include/tbk.h): the spans are decoded as tbk_bam_decode_spans decodes them, each under the tbmerged flag of
+// the file that owns it, and the spans' record ranges are folded to the files' on the host
+extern "C" int tbk_bam_decode_file_spans(tbk_ctx* ctx, uint32_t n_files, const uint32_t* span_first, const uint8_t* const* comp, const uint64_t* comp_bytes,
+                                         const uint32_t* first_uoff, const uint32_t* last_uoff, int32_t n_ref, const uint8_t* tbmerged, int want_md,
+                                         int want_names, tbk_soa_in* tile, uint32_t* file_off_out) {
+  if (!ctx || !tile || !file_off_out || !span_first || n_ref < 0 || n_files == 0 || n_files > 65535 || span_first[0] != 0) return TBK_EINVAL;
+  for (uint32_t f = 0; f < n_files; ++f)
+    if (span_first[f + 1] < span_first[f]) return TBK_EINVAL;
+  const uint32_t n_spans = span_first[n_files];
+  if (n_spans > 65535) {  // (bam_decode_impl's bound on its "files": a grid dimension of the record index's kernels)
+    ctx->last_error = "more than 65535 spans";
+    return TBK_E2BIG;
+  }
+  if (n_spans == 0) {  // no file has a chunk: an empty tile (the tile of an earlier decode is released, as by every decode)
+    TBK_TRY(tbk_collapse_finish_yd(ctx));
+    tbk_bam_release(ctx);
+    memset(tile, 0, sizeof(*tile));
+    tile->mem = TBK_MEM_DEVICE;
+    tile->n_files = n_files;
+    tile->file_off = file_off_out;
+    tile->tbmerged = tbmerged;
+    for (uint32_t f = 0; f <= n_files; ++f) file_off_out[f] = 0;
+    return 0;
+  }
+  if (!comp || !comp_bytes || !first_uoff || !last_uoff) return TBK_EINVAL;
+  std::vector<uint8_t> span_tbm(n_spans, 0);
+  for (uint32_t f = 0; f < n_files; ++f)
+    for (uint32_t s = span_first[f]; s < span_first[f + 1]; ++s) span_tbm[s] = tbmerged && tbmerged[f] ? 1 : 0;
+  std::vector<uint32_t> span_off((size_t)n_spans + 1, 0);
+  SpanArgs sp{first_uoff, last_uoff, n_ref, nullptr, span_tbm.data()};
+  const int rc = bam_decode_impl(ctx, n_spans, comp, comp_bytes, nullptr, want_md, want_names, tile, span_off.data(), &sp);
+  for (uint32_t f = 0; f <= n_files; ++f) file_off_out[f] = rc == 0 ? span_off[span_first[f]] : 0;
+  if (rc != 0) return rc;
+  tile->n_files = n_files;
+  tile->file_off = file_off_out;
+  tile->tbmerged = tbmerged;
+  return 0;
+}
+
+// ---- what tbk_tile_region (region.hip) needs of the decoded tile --------------------------------------------------------------------
+bool tbk_bam_dev_is_tile(tbk_ctx* ctx, const tbk_soa_in* tile) {
+  BamDev* B = (BamDev*)ctx->bam_dev;
+  return B && B->inf && B->rec && tile->mem == TBK_MEM_DEVICE && tile->tid == B->tile_tid && tile->n_records == B->n;
+}
+void* tbk_bam_dev_alloc(tbk_ctx* ctx, size_t bytes) {
+  BamDev* B = (BamDev*)ctx->bam_dev;
+  return B ? (void*)bd_alloc<uint8_t>(B, bytes) : nullptr;
+}
+void tbk_bam_dev_compacted(tbk_ctx* ctx, uint64_t* rec, uint32_t n, const int32_t* tid) {
+  BamDev* B = (BamDev*)ctx->bam_dev;
+  if (!B) return;
+  if (rec) B->rec = rec;  // (the old table stays among the tile's allocations until the release)
+  B->n = n;
+  B->tile_tid = tid;
 }
 
 namespace {

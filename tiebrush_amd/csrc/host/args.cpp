@@ -78,6 +78,32 @@ Args::Args(int argc, char** argv, const char* fmt) {
   }
 }
 
+int count_value_option(int argc, char** argv, const char* long_name, char short_name, const char* const* value_longs, const char* value_shorts) {
+  const std::string lname = std::string("--") + long_name, lname_eq = lname + "=";
+  int n = 0;
+  for (int i = 1; i < argc; ++i) {
+    const std::string a = argv[i];
+    bool other = false;
+    for (const char* const* v = value_longs; v && *v; ++v) other = other || a == std::string("--") + *v;
+    if (a == lname || other) {
+      n += a == lname;
+      ++i;
+    } else if (a.compare(0, lname_eq.size(), lname_eq) == 0) {
+      ++n;
+    } else if (a.size() > 1 && a[0] == '-' && a[1] != '-') {
+      for (size_t k = 1; k < a.size(); ++k) {
+        const char c = a[k];
+        if (c == short_name) ++n;
+        if (c == short_name || (value_shorts && strchr(value_shorts, c))) {  // the rest of the word, or the next word, is its value
+          if (k + 1 == a.size()) ++i;
+          break;
+        }
+      }
+    }
+  }
+  return n;
+}
+
 const char* Args::getOpt(const char* name) const {
   auto it = opts_.find(name);
   return it == opts_.end() ? nullptr : it->second.c_str();

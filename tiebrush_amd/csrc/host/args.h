@@ -29,3 +29,9 @@ class Args {
   size_t pos_ = 0;
   std::string err_;
 };
+
+// How often a repeatable-looking option is given on a command line: Args keeps the last value of a repeated option, so a tool that takes
+// one value only (tiecov / tiebrush -r REGION: one region per run) counts the occurrences itself.  long_name / short_name: the option
+// counted, which takes a value; value_longs (NULL-terminated) / value_shorts: the tool's other options that take a value in the next word
+// (or, short ones, in the rest of their word), whose values are not looked at.
+int count_value_option(int argc, char** argv, const char* long_name, char short_name, const char* const* value_longs, const char* value_shorts);

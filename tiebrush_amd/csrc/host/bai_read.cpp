@@ -8,6 +8,8 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
+#include <thread>
 
 #include "bgzf.h"
 
@@ -45,6 +47,36 @@ size_t member_size(const uint8_t* h, size_t n) {
     x += 4 + sl;
   }
   return 0;
+}
+bool pread_all(int fd, uint64_t at, uint8_t* dst, size_t n) {
+  while (n) {
+    const ssize_t got = pread(fd, dst, n, (off_t)at);
+    if (got < 0 && errno == EINTR) continue;
+    if (got <= 0) return false;
+    dst += got, at += (uint64_t)got, n -= (size_t)got;
+  }
+  return true;
+}
+// where the bytes of chunk c end in its file (*stop): c.end's member, or behind it when the chunk ends inside it (the member's size is in
+// its own header, which is read).  false, with err, for a chunk that lies outside the file of fsize bytes, begins before prev_end (the
+// stop of the chunk before it) or does not end in a member.  `index` is how the message names the index.
+bool chunk_extent(int fd, uint64_t fsize, const IdxChunk& c, uint64_t prev_end, uint64_t* stop, const std::string& index, const std::string& bam_path,
+                  std::string& err) {
+  const uint64_t c0 = c.beg >> 16, c1 = c.end >> 16;
+  const uint32_t u1 = (uint32_t)(c.end & 0xffff);
+  char where[96];
+  snprintf(where, sizeof(where), "%llx-%llx", (unsigned long long)c.beg, (unsigned long long)c.end);
+  if (c.beg >= c.end || c0 + 18 > fsize || c1 > fsize || (u1 && c1 + 18 > fsize) || c0 < prev_end)
+    return err = index + " names a chunk outside " + bam_path + " (" + where + ", file size " + std::to_string(fsize) + ")", false;
+  *stop = c1;
+  if (u1) {  // the last member is part of the chunk
+    uint8_t h[18 + 256];
+    const size_t hn = (size_t)std::min<uint64_t>(sizeof(h), fsize - c1);
+    const size_t ms = pread_all(fd, c1, h, hn) ? member_size(h, hn) : 0;
+    if (!ms || c1 + ms > fsize) return err = index + " names a chunk that does not end in a BGZF member of " + bam_path + " (" + where + ")", false;
+    *stop = c1 + ms;
+  }
+  return true;
 }
 }  // namespace
 
@@ -268,41 +300,18 @@ bool read_spans(const std::string& bam_path, const std::vector<IdxChunk>& chunks
     return err = "cannot stat " + bam_path, false;
   }
   const uint64_t fsize = (uint64_t)st.st_size;
-  auto rd = [&](uint64_t at, uint8_t* dst, size_t n) {
-    while (n) {
-      const ssize_t got = pread(fd, dst, n, (off_t)at);
-      if (got < 0 && errno == EINTR) continue;
-      if (got <= 0) return false;
-      dst += got, at += (uint64_t)got, n -= (size_t)got;
-    }
-    return true;
-  };
+  auto rd = [&](uint64_t at, uint8_t* dst, size_t n) { return pread_all(fd, at, dst, n); };
   bool ok = true;
   uint64_t prev_end = 0;
   for (const IdxChunk& c : chunks) {
-    const uint64_t c0 = c.beg >> 16, c1 = c.end >> 16;
-    const uint32_t u1 = (uint32_t)(c.end & 0xffff);
-    char where[96];
-    snprintf(where, sizeof(where), "%llx-%llx", (unsigned long long)c.beg, (unsigned long long)c.end);
-    if (c.beg >= c.end || c0 + 18 > fsize || c1 > fsize || (u1 && c1 + 18 > fsize) || c0 < prev_end) {
-      err = "the index names a chunk outside " + bam_path + " (" + where + ", file size " + std::to_string(fsize) + ")";
+    const uint64_t c0 = c.beg >> 16;
+    uint64_t stop = 0;
+    if (!chunk_extent(fd, fsize, c, prev_end, &stop, "the index", bam_path, err)) {
       ok = false;
       break;
     }
-    uint64_t stop = c1;
-    if (u1) {  // the last member is part of the chunk: its size is in its own header
-      uint8_t h[18 + 256];
-      const size_t hn = (size_t)std::min<uint64_t>(sizeof(h), fsize - c1);
-      const size_t ms = rd(c1, h, hn) ? member_size(h, hn) : 0;
-      if (!ms || c1 + ms > fsize) {
-        err = "the index names a chunk that does not end in a BGZF member of " + bam_path + " (" + where + ")";
-        ok = false;
-        break;
-      }
-      stop = c1 + ms;
-    }
     RegionSpan s;
-    s.first_uoff = (uint32_t)(c.beg & 0xffff), s.last_uoff = u1;
+    s.first_uoff = (uint32_t)(c.beg & 0xffff), s.last_uoff = (uint32_t)(c.end & 0xffff);
     s.z.resize((size_t)(stop - c0));
     if (!rd(c0, s.z.data(), s.z.size())) {
       err = "read failed on " + bam_path;
@@ -368,6 +377,66 @@ bool index_query_file(const std::string& bam_path, const std::string& index_path
   }
   if (tid < 0 || tid >= bf.hdr.n_targets || beg < 0 || end < beg) return err = "index query: tid / beg / end out of range", false;
   ix.query(tid, beg, end, out);
+  return true;
+}
+
+bool region_input_chunks(const std::string& bam_path, int32_t file_n_ref, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& chunks,
+                         std::string& index_path, std::string& err) {
+  chunks.clear();
+  if (!find_index(bam_path, "", index_path, err)) {  // (the paths tried; the advice is find_index's caller's)
+    const size_t cut = err.find("): ");
+    if (cut != std::string::npos) err = err.substr(0, cut) + "): write one with `tiebrush --index` / `--csi` or `samtools index`";
+    return false;
+  }
+  RegionIndex ix;
+  if (!ix.load(index_path, err)) {
+    if (err.find(index_path) == std::string::npos) err = index_path + ": " + err;
+    return false;
+  }
+  if (ix.n_ref() != (size_t)file_n_ref) {
+    err = index_path + ": the index has " + std::to_string(ix.n_ref()) + " references, the header of " + bam_path + " has " + std::to_string(file_n_ref);
+    return false;
+  }
+  if (tid < 0 || tid >= file_n_ref || beg < 0 || end < beg) return err = bam_path + ": index query: tid / beg / end out of range", false;
+  if (beg < end) ix.query(tid, beg, end, chunks);
+  if (chunks.empty()) return true;
+  const int fd = open(bam_path.c_str(), O_RDONLY);  // (read_spans' own conditions, the header of each chunk's last member included)
+  if (fd < 0) return err = "cannot open " + bam_path, false;
+  struct stat st;
+  bool ok = fstat(fd, &st) == 0;
+  if (!ok) err = "cannot stat " + bam_path;
+  uint64_t prev = 0;
+  for (size_t i = 0; ok && i < chunks.size(); ++i) ok = chunk_extent(fd, (uint64_t)st.st_size, chunks[i], prev, &prev, "the index " + index_path, bam_path, err);
+  close(fd);
+  return ok;
+}
+
+bool read_spans_many(const std::vector<std::string>& paths, const std::vector<std::vector<IdxChunk>>& chunks, int threads,
+                     std::vector<std::vector<RegionSpan>>& spans, uint64_t* bytes_read, std::string& err) {
+  const size_t k = paths.size();
+  spans.assign(k, {});
+  std::vector<uint64_t> bytes(k, 0);
+  std::vector<std::string> errs(k);
+  std::vector<uint8_t> ok(k, 1);
+  std::atomic<size_t> next{0};
+  auto work = [&]() {
+    for (;;) {
+      const size_t f = next.fetch_add(1);
+      if (f >= k) break;
+      if (chunks[f].empty()) continue;
+      ok[f] = read_spans(paths[f], chunks[f], spans[f], &bytes[f], errs[f]) ? 1 : 0;
+    }
+  };
+  const size_t nt = std::min<size_t>(k, (size_t)std::max(1, threads));
+  std::vector<std::thread> th;
+  for (size_t t = 1; t < nt; ++t) th.emplace_back(work);
+  work();
+  for (auto& x : th) x.join();
+  if (bytes_read) *bytes_read = 0;
+  for (size_t f = 0; f < k; ++f) {
+    if (!ok[f]) return err = errs[f], false;
+    if (bytes_read) *bytes_read += bytes[f];
+  }
   return true;
 }
 

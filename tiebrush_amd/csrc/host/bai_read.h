@@ -79,4 +79,15 @@ bool span_records(const RegionSpan& s, uint64_t file_off, std::vector<BaiRec>& r
 bool index_query_file(const std::string& bam_path, const std::string& index_path, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out,
                       std::string& err);
 
+// One input of `tiebrush -r`: its index found (find_index's order), loaded and checked against the file — the index's
+// n_ref is file_n_ref, the file's header's — and queried; every chunk checked against the file by read_spans' own conditions, the header
+// of the member it ends in read (so that a caller can refuse before it has created anything: what read_spans refuses, this refuses).
+// err names the file concerned.
+bool region_input_chunks(const std::string& bam_path, int32_t file_n_ref, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& chunks,
+                         std::string& index_path, std::string& err);
+// The spans of several inputs, read on `threads` threads (file after file on each): spans[f] = read_spans(paths[f], chunks[f]).  false:
+// err is the first failing file's.  *bytes_read = the sum over all inputs.
+bool read_spans_many(const std::vector<std::string>& paths, const std::vector<std::vector<IdxChunk>>& chunks, int threads,
+                     std::vector<std::vector<RegionSpan>>& spans, uint64_t* bytes_read, std::string& err);
+
 }  // namespace tbh

@@ -415,6 +415,46 @@ int main(int argc, char** argv) {
     for (uint64_t v : hits) printf("hit %llx\n", (unsigned long long)v);
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|query ...\n");
+  // the host plumbing of `tiebrush -r`: REGION against the first input's header, every input's index found, checked and
+  // queried (region_input_chunks), the chunks of all inputs read on THREADS threads (read_spans_many), the records counted by the host codec
+  if (cmd == "mquery" && argc >= 5) {
+    std::string err;
+    const int threads = atoi(argv[3]);
+    std::vector<std::string> paths(argv + 4, argv + argc);
+    int32_t tid = 0;
+    int64_t beg = 0, end = 0;
+    std::vector<std::vector<tbh::IdxChunk>> chunks(paths.size());
+    std::vector<std::vector<tbh::RegionSpan>> spans;
+    uint64_t bytes = 0;
+    for (size_t f = 0; f < paths.size(); ++f) {
+      tbh::BamFile bf;
+      std::string ix;
+      if (!bf.open(paths[f], err, 1) || (f == 0 && !tbh::parse_region(bf.hdr, argv[2], &tid, &beg, &end, err)) ||
+          !tbh::region_input_chunks(paths[f], bf.hdr.n_targets, tid, beg, end, chunks[f], ix, err)) {
+        fprintf(stderr, "tbh_tool mquery: %s\n", err.c_str());
+        return 1;
+      }
+    }
+    if (!tbh::read_spans_many(paths, chunks, threads, spans, &bytes, err)) {
+      fprintf(stderr, "tbh_tool mquery: %s\n", err.c_str());
+      return 1;
+    }
+    printf("region %d %lld %lld\nbytes %llu\n", tid, (long long)beg, (long long)end, (unsigned long long)bytes);
+    for (size_t f = 0; f < paths.size(); ++f) {
+      uint64_t n_rec = 0, n_hit = 0;
+      for (size_t c = 0; c < chunks[f].size(); ++c) {
+        std::vector<tbh::BaiRec> recs;
+        if (!tbh::span_records(spans[f][c], chunks[f][c].beg >> 16, recs, err)) {
+          fprintf(stderr, "tbh_tool mquery: %s: %s\n", paths[f].c_str(), err.c_str());
+          return 1;
+        }
+        n_rec += recs.size();
+        for (const tbh::BaiRec& r : recs) n_hit += r.tid == tid && r.beg < end && r.end > beg;
+      }
+      printf("file %zu chunks %zu records %llu overlapping %llu\n", f, chunks[f].size(), (unsigned long long)n_rec, (unsigned long long)n_hit);
+    }
+    return 0;
+  }
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|query|mquery ...\n");
   return 2;
 }

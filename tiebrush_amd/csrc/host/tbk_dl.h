@@ -32,6 +32,8 @@ struct TbkApi {
   decltype(&tbk_host_free) host_free = nullptr;
   decltype(&tbk_set_profiling) set_profiling = nullptr;
   decltype(&tbk_kernel_times) kernel_times = nullptr;
+  decltype(&tbk_bam_decode_file_spans) bam_decode_file_spans = nullptr;  // -r REGION
+  decltype(&tbk_tile_region) tile_region = nullptr;
   // optional: only the track options (--cov / --junc / --samp) need them; has_tracks() says whether the library has them all
   decltype(&tbk_coverage_tile) coverage_tile = nullptr;
   decltype(&tbk_sample_tile) sample_tile = nullptr;
@@ -80,6 +82,8 @@ struct TbkApi {
     TBK_BIND(host_free, tbk_host_free)
     TBK_BIND(set_profiling, tbk_set_profiling)
     TBK_BIND(kernel_times, tbk_kernel_times)
+    TBK_BIND(bam_decode_file_spans, tbk_bam_decode_file_spans)
+    TBK_BIND(tile_region, tbk_tile_region)
 #undef TBK_BIND
     coverage_tile = (decltype(coverage_tile))dlsym(h, "tbk_coverage_tile");
     sample_tile = (decltype(sample_tile))dlsym(h, "tbk_sample_tile");

@@ -2,6 +2,8 @@
 // with the per-record main loop (:570-592) replaced by one call into the MI355X hot path:
 //   decode every input into a SoA tile (host: BGZF inflate + record / aux scan on every core, fastload.cpp; inputs larger than
 //   memory stream through TInputFiles::next_tile)  ->  tbk_collapse_tile (HIP)  ->  tag + deflate + write (host).
+// With -r REGION (no counterpart in the reference) only the chunks that every input's index names for the region are read,
+// and they are inflated, decoded and filtered on the device (run_region below).
 // libtbk.so (and with it the HIP runtime) is bound with dlopen on a helper thread while the inputs are read (tbk_dl.h).
 // There is no CPU implementation of the collapse in this binary: without a usable GPU it exits with an error.
 #include <errno.h>
@@ -38,6 +40,8 @@
 #include "fastload.h"
 #include "tagwrite.h"
 #include "bai.h"
+#include "bai_read.h"
+#include "sam.h"
 #include "tbk_dl.h"
 #include "tmerge.h"
 #include "tracks.h"
@@ -70,6 +74,10 @@ static const char* USAGE =
     "  -A,--collapse-same   do not count the same read of the same sample twice\n"
     "  --store-frac         YC adds 1/NH per alignment (needs --keep-secondary)\n"
     "  -V,--verbose         echo the command line\n"
+    "  -r,--region REGION   collapse only the alignments that overlap REGION: NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive,\n"
+    "                       commas allowed; one region per run), read through every input's index (IN.bam.csi, IN.bam.bai or IN.bai;\n"
+    "                       `tiebrush --index` / `--csi` and `samtools index` write one).  The output is what the same command line\n"
+    "                       without -r makes of inputs cut to their records that overlap the region; not with --ranks\n"
     "  --ranks N            shard the input files over N GPUs of this node (one process each), one output BAM\n"
     "  --writer WHICH       device (default): the output records are tagged and BGZF-compressed on the GPU; host: by the CPU cores\n"
     "  --cov PREFIX         also write tiecov's coverage track of the output (as tiecov -c; - or stdout: standard output)\n"
@@ -1010,6 +1018,47 @@ static Route run_whole_host(Device& dev, Output& out, const tbk_collapse_opts& o
   return account_whole(tot, res, tms(t0, t1), tms(t1, t2), tms(t2, t3));
 }
 
+// The end of a route whose tile lies decoded on the device (run_device_decode, run_region): one collapse, the output records by the
+// device writer — or the representatives' raw records fetched (tbk_bam_records) for the host writer —, the write, the tile's release.
+// Returns 0, or TBK_ENOMEM / TBK_E2BIG (the tile is more than the GPU takes: nothing is released, the caller decides); anything else is
+// fatal here.
+struct DeviceTail {
+  tbk_groups_out res;
+  Clock t_col, t_rec, t_rel;         // the collapse done; the records fetched (or written by the device writer); the tile released
+  std::function<void()> on_release;  // (the route's phase line)
+};
+static int device_tile_tail(Device& dev, Output& out, const tbk_collapse_opts& opt, const Env& env, tbk_soa_in* in, DeviceTail& T) {
+  int rc = collapse_whole(dev, out, env, opt, false, in, &T.res);
+  T.t_col = T.t_rec = T.t_rel = tnow();
+  RawBuf<uint64_t> roff;
+  RawBuf<uint8_t> blob;
+  bool released = false;
+  auto release = [&]() {
+    T.t_rec = tnow();
+    dev.api.bam_release(dev.ctx);
+    released = true;
+    T.t_rel = tnow();
+    if (T.on_release) T.on_release();
+  };
+  auto fetch = [&]() {
+    rc = fetch_device_records(dev, env, out.rep.data(), T.res.n_groups, 96, blob, roff);
+    if (rc == 0) release();
+    return rc == 0;
+  };
+  auto rec = [&](uint32_t g) {  // (the device writer asks for none: every record is on the device)
+    tbh::RecView v;
+    v.p = blob.data() + roff[g] + 4;
+    v.len = (uint32_t)(roff[g + 1] - roff[g] - 4);
+    return v;
+  };
+  if (rc == 0)  // (false only when the fetch fails: rc says why)
+    (void)out.write(dev.ctx, T.res.n_groups, out.rep.data(), out.yc.data(), out.yx.data(), out.yd.data(), (uint32_t)in->n_records, rec, nullptr, fetch);
+  if (rc == TBK_ENOMEM || rc == TBK_E2BIG) return rc;
+  if (rc != 0) GError("Error: GPU collapse / fetching the representative records failed: %s (%s)\n", dev.api.strerror_(rc), dev.api.last_error(dev.ctx));
+  if (!released) release();
+  return 0;
+}
+
 // ---- device decode: when the inputs fit, their BGZF members go to the GPU as they are — inflate, record index, aux
 // scan and SoA happen there (tbk_bam_decode), the collapse reads the tile where it lies, and only the representatives' raw records come
 // back (tbk_bam_records) to be tagged.  Anything it cannot take falls through to the streaming route.
@@ -1036,45 +1085,143 @@ static Route run_device_decode(Device& dev, Output& out, const tbk_collapse_opts
     dev.api.bam_release(dev.ctx);  // (whatever the failed decode left on the device goes back before the streaming route sizes its tiles)
     return Route::fall_through;
   }
-  tbk_groups_out res;
-  rc = collapse_whole(dev, out, env, opt, false, &in, &res);
-  auto t_col = tnow(), t_rec = t_col, t2 = t_col;
-  RawBuf<uint64_t> roff;
-  RawBuf<uint8_t> blob;
-  bool released = false;
-  auto release = [&]() {
-    t_rec = tnow();
-    dev.api.bam_release(dev.ctx);
-    released = true;
-    t2 = tnow();
+  DeviceTail T;
+  T.on_release = [&]() {
     if (env.timing)
       fprintf(stderr, "device path ms: read files %.1f | wait for the HIP context %.1f | decode %.1f | collapse %.1f | fetch representatives %.1f | release %.1f\n",
-              tms(t0, t_read), tms(t_read, t_ctxw), tms(t_ctxw, t1), tms(t1, t_col), tms(t_col, t_rec), tms(t_rec, t2));
+              tms(t0, t_read), tms(t_read, t_ctxw), tms(t_ctxw, t1), tms(t1, T.t_col), tms(T.t_col, T.t_rec), tms(T.t_rec, T.t_rel));
   };
-  auto fetch = [&]() {
-    rc = fetch_device_records(dev, env, out.rep.data(), res.n_groups, 96, blob, roff);
-    if (rc == 0) release();
-    return rc == 0;
-  };
-  auto rec = [&](uint32_t g) {  // (the device writer asks for none: every record is on the device)
-    tbh::RecView v;
-    v.p = blob.data() + roff[g] + 4;
-    v.len = (uint32_t)(roff[g + 1] - roff[g] - 4);
-    return v;
-  };
-  if (rc == 0)  // (false only when the fetch fails: rc says why)
-    (void)out.write(dev.ctx, res.n_groups, out.rep.data(), out.yc.data(), out.yx.data(), out.yd.data(), (uint32_t)in.n_records, rec, nullptr, fetch);
+  rc = device_tile_tail(dev, out, opt, env, &in, T);
   if (rc == TBK_ENOMEM || rc == TBK_E2BIG) {  // decoded, but the whole input as one tile is more than the GPU takes:
     out.fall_through("device decode given up", why_rc(dev, rc));  // give the device copies back and let the streaming route bound the tile
     dev.api.bam_release(dev.ctx);
     return Route::fall_through;
   }
-  if (rc != 0) GError("Error: GPU collapse / fetching the representative records failed: %s (%s)\n", dev.api.strerror_(rc), dev.api.last_error(dev.ctx));
-  if (!released) release();
   auto t3 = tnow();
-  account_whole(tot, res, tms(t0, t1), tms(t1, t2), tms(t2, t3));
+  account_whole(tot, T.res, tms(t0, t1), tms(t1, T.t_rel), tms(T.t_rel, t3));
   if (env.timing) fprintf(stderr, "device decode: %zu records from %llu compressed bytes\n", (size_t)in.n_records, (unsigned long long)inp.total);
   return Route::done;
+}
+
+// ---- -r REGION (the reference has no region option): only the chunks that every input's index names for the region are
+// read; they are inflated and decoded on the device with the records grouped by input file (tbk_bam_decode_file_spans), the records that
+// overlap the region are compacted into a collapse tile there (tbk_tile_region), and from then on the run is the device decode route's.
+// One tile, no fall-through: the output is what the same command line without -r makes of inputs cut to the region.
+struct RegionPlan {
+  int32_t tid = 0;
+  int64_t beg = 0, end = 0;                        // 0-based, half-open
+  std::vector<std::string> paths;
+  std::vector<std::vector<tbh::IdxChunk>> chunks;  // per input, as its index names them
+  size_t n_chunks = 0;
+  double ms_index = 0;
+};
+static bool list_argument(const std::string& p) { return !tbh::bgzf_probe(p) && !tbh::sam_probe(p); }
+// what -r refuses of the inputs before they are opened: standard input, and (unless the one argument is a list of paths) anything
+// that is not a BGZF file
+static void refuse_region_inputs(TInputFiles& in, bool before_open) {
+  const bool list = before_open && in.freaders.size() == 1 && in.freaders[0]->fname != "-" && list_argument(in.freaders[0]->fname);
+  for (const TSamReader* r : in.freaders) {
+    if (r->fname == "-") GError("Error: -r: the input - (standard input) has no index; -r takes BGZF-compressed BAM files\n");
+    if (!list && !tbh::bgzf_probe(r->fname)) GError("Error: -r: %s is not a BGZF-compressed BAM file (SAM text has no index)\n", r->fname.c_str());
+  }
+}
+// every refusal that needs no device, in the order of DESIGN.md §4f; nothing has been created when one of them ends the run
+static RegionPlan plan_region(TInputFiles& in, const std::string& region) {
+  RegionPlan P;
+  auto t0 = tnow();
+  std::string err;
+  sam_hdr_t* mh = in.header();
+  if (!tbh::parse_region(*mh, region, &P.tid, &P.beg, &P.end, err)) GError("Error: -r: %s\n", err.c_str());
+  const std::string& rname = mh->target_name[(size_t)P.tid];
+  const size_t k = in.freaders.size();
+  if (k > 65535) GError("Error: -r: %zu inputs; the device decode takes 65535\n", k);
+  P.chunks.resize(k);
+  for (size_t f = 0; f < k; ++f) {
+    const std::string& path = in.freaders[f]->fname;
+    P.paths.push_back(path);
+    sam_hdr_t* h = in.freaders[f]->samreader->header();
+    // (the header merge has refused, with the file's name, a list that has another name at a position or a name at another position:
+    // an input's list is the head of the merged one, and can only be too short for the region's reference)
+    if (P.tid >= h->n_targets)
+      GError("Error: -r: %s does not list the region's reference %s as reference %d, as the merged header does\n", path.c_str(), rname.c_str(), (int)P.tid);
+    std::string index_path;
+    if (!tbh::region_input_chunks(path, h->n_targets, P.tid, P.beg, P.end, P.chunks[f], index_path, err)) GError("Error: -r: %s\n", err.c_str());
+    P.n_chunks += P.chunks[f].size();
+  }
+  if (P.n_chunks > 65535)
+    GError("Error: -r: the indexes of the %zu inputs name %zu chunks for the region in all; the device decode takes 65535 (first input: %s)\n", k, P.n_chunks,
+           P.paths[0].c_str());
+  P.ms_index = tms(t0, tnow());
+  return P;
+}
+
+static Route run_region(Device& dev, Output& out, const tbk_collapse_opts& opt, const Env& env, const Inputs& inp, const RegionPlan& plan, int32_t n_ref,
+                        Totals& tot) {
+  const size_t k = plan.paths.size();
+  auto t0 = tnow();
+  // the chunk reads, on every thread, beside the context's bring-up
+  std::vector<std::vector<tbh::RegionSpan>> spans;
+  uint64_t bytes_read = 0;
+  std::string err;
+  const bool read_ok = tbh::read_spans_many(plan.paths, plan.chunks, env.threads, spans, &bytes_read, err);
+  auto t_read = tnow();
+  dev.wait();
+  auto t_ctx = tnow();
+  if (!read_ok) GError("Error: -r: %s\n", err.c_str());
+  std::vector<uint32_t> span_first(k + 1, 0), first_uoff, last_uoff, fo(k + 1, 0);
+  std::vector<const uint8_t*> comp;
+  std::vector<uint64_t> comp_bytes;
+  for (size_t f = 0; f < k; ++f) {
+    for (const tbh::RegionSpan& s : spans[f]) comp.push_back(s.z.data()), comp_bytes.push_back(s.z.size()), first_uoff.push_back(s.first_uoff), last_uoff.push_back(s.last_uoff);
+    span_first[f + 1] = (uint32_t)comp.size();
+  }
+  const int want_md = opt.strategy == TBK_STRAT_FULL, want_names = opt.collapse_same != 0;
+  auto too_large = [&](int rc) { GError("Error: -r: region too large for one tile (%s)\n", why_rc(dev, rc).c_str()); };
+  tbk_soa_in tile;
+  int rc = dev.api.bam_decode_file_spans(dev.ctx, (uint32_t)k, span_first.data(), comp.data(), comp_bytes.data(), first_uoff.data(), last_uoff.data(), n_ref,
+                                         inp.merged.data(), want_md, want_names, &tile, fo.data());
+  if (rc == TBK_ENOMEM || rc == TBK_E2BIG) too_large(rc);
+  if (rc == TBK_EINVAL) {  // a malformed span: the inputs' spans one by one name the file
+    const std::string why = why_rc(dev, rc);
+    for (size_t f = 0; f < k; ++f) {
+      const uint32_t a = span_first[f], b = span_first[f + 1];
+      if (a == b) continue;
+      const uint32_t one[2] = {0, b - a};
+      uint32_t fo1[2] = {0, 0};
+      tbk_soa_in t1;
+      if (dev.api.bam_decode_file_spans(dev.ctx, 1, one, comp.data() + a, comp_bytes.data() + a, first_uoff.data() + a, last_uoff.data() + a, n_ref,
+                                        inp.merged.data() + f, want_md, want_names, &t1, fo1) == TBK_EINVAL)
+        GError("Error: -r: could not decode the chunks of %s its index names (%s): is the index the file's own?\n", plan.paths[f].c_str(), why.c_str());
+    }
+    GError("Error: -r: could not decode the chunks the indexes name (%s; first input: %s): is the index the file's own?\n", why.c_str(), plan.paths[0].c_str());
+  }
+  if (rc != 0) GError("Error: -r: decoding the chunks on the GPU failed: %s (first input: %s)\n", why_rc(dev, rc).c_str(), plan.paths[0].c_str());
+  auto t_dec = tnow();
+  const uint32_t n_decoded = tile.n_records;
+  tbk_soa_in in;
+  uint32_t n_kept = 0;
+  rc = dev.api.tile_region(dev.ctx, &tile, plan.tid, plan.beg, plan.end, &in, fo.data(), &n_kept);
+  if (rc == TBK_ENOMEM || rc == TBK_E2BIG) too_large(rc);
+  if (rc != 0) GError("Error: -r: GPU region filter failed: %s\n", why_rc(dev, rc).c_str());
+  auto t_fil = tnow();
+  spans.clear();
+  DeviceTail T;
+  memset(&T.res, 0, sizeof(T.res));
+  T.t_col = T.t_rec = T.t_rel = t_fil;
+  if (n_kept) {  // (a region without a record: header + EOF member)
+    rc = device_tile_tail(dev, out, opt, env, &in, T);
+    if (rc != 0) too_large(rc);
+  } else {
+    dev.api.bam_release(dev.ctx);
+  }
+  auto t3 = tnow();
+  if (env.timing)
+    fprintf(stderr,
+            "region path ms: index queries %.1f | chunk reads %.1f (%llu bytes in %zu chunks of %zu inputs, %llu bytes in all) | context up at %.1f | decode %.1f | "
+            "filter %.1f (%u of %u records) | collapse %.1f | write %.1f\n",
+            plan.ms_index, tms(t0, t_read), (unsigned long long)bytes_read, plan.n_chunks, k, (unsigned long long)inp.total, tms(dev.t_start, t_ctx), tms(t_ctx, t_dec),
+            tms(t_dec, t_fil), n_kept, n_decoded, tms(t_fil, T.t_col), tms(T.t_col, t3));
+  return account_whole(tot, T.res, tms(t0, t_dec), tms(t_dec, T.t_col), tms(T.t_col, t3));
 }
 
 // ---- streaming route: the inputs go through in tiles (TInputFiles::next_tile), and the OUTPUT side of tile i runs beside the input
@@ -1237,6 +1384,8 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
 
 // the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
+  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", nullptr};
+  const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQF");
   bool ranks = false, tracks = false, index = false, csi = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
@@ -1250,6 +1399,8 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
   if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
   if (ranks && index) GError("Error: --index is not available with --ranks (index the output afterwards)\n");
   if (ranks && csi) GError("Error: --csi is not available with --ranks (index the output afterwards)\n");
+  if (regions > 1) GError("Error: -r / --region given more than once (one region per run)\n");
+  if (ranks && regions) GError("Error: -r / --region is not available with --ranks\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -1258,7 +1409,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;csi;SMLPEDVho:N:Q:F:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;csi;region=;SMLPEDVho:N:Q:F:r:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1326,10 +1477,25 @@ int main(int argc, char* argv[]) {
   if (want_csi && strcmp(outfname, "-") == 0)
     GError("Error: --csi needs an output file (-o FILE, not -o -): an index addresses file offsets, standard output has none\n");
   const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty();
-  while (const char* ifn = args.nextNonOpt()) inRecords.addFile(tbh_realpath(ifn).c_str());
+  const char* region = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");
+  while (const char* ifn = args.nextNonOpt()) {
+    if (region && strcmp(ifn, "-") == 0) GError("Error: -r: the input - (standard input) has no index; -r takes BGZF-compressed BAM files\n");
+    inRecords.addFile(tbh_realpath(ifn).c_str());
+  }
 
-  Device dev(env, opt, dev_writer, tracks, tnow());
-  inRecords.start();
+  // -r REGION: the inputs are opened, the region resolved against the merged header and every input's index queried BEFORE the device
+  // is brought up or any output file exists (plan_region's refusals)
+  std::unique_ptr<RegionPlan> rplan;
+  const Clock t_begin = tnow();
+  if (region) {
+    refuse_region_inputs(inRecords, true);
+    inRecords.name_ref_file = true;
+    inRecords.start();
+    refuse_region_inputs(inRecords, false);
+    rplan.reset(new RegionPlan(plan_region(inRecords, region)));
+  }
+  Device dev(env, opt, dev_writer, tracks, region ? t_begin : tnow());
+  if (!region) inRecords.start();
   auto t_ctx = tnow();
   Totals tot;
   // the tracks: the output header's sample lines (load_sample_info, commons.h:47-71) are checked before any work, the files opened
@@ -1361,7 +1527,8 @@ int main(int argc, char* argv[]) {
   const Inputs inp(inRecords);
   const Routes can = eligible_routes(env, opt, inp);
   Route r = Route::fall_through;
-  if (can.hybrid) r = run_hybrid(dev, out, opt, env, inp, tot);
+  if (rplan) r = run_region(dev, out, opt, env, inp, *rplan, inRecords.header()->n_targets, tot);
+  else if (can.hybrid) r = run_hybrid(dev, out, opt, env, inp, tot);
   else if (can.whole_host) r = run_whole_host(dev, out, opt, env, inp, tot);
   if (r == Route::fall_through && can.device_decode) r = run_device_decode(dev, out, opt, env, inp, tot);
   if (r == Route::fall_through) run_streaming(dev, out, opt, env, inRecords, tot);
@@ -1381,6 +1548,7 @@ int main(int argc, char* argv[]) {
     fprintf(stderr, "timing ms: open+context %.1f | inflate+index %.1f | SoA %.1f | collapse (PCIe incl.) %.1f | tag+queue %.1f | total to writer close %.1f\n",
             tms(dev.t_start, t_ctx), tot.ms_inflate, tot.ms_load, tot.ms_gpu, tot.ms_tag, tms(dev.t_start, t_closed));
   double p = 100.00 - (double)(tot.out * 100.00) / (double)tot.in;
+  if (rplan && !tot.in) p = 0.0;  // (-r: a region without a record; without -r the line is what it always was)
   GMessage("%ld input records written as %ld (%.2f%% reduction)\n", (long)tot.in, (long)tot.out, p);
   fflush(stdout);
   fflush(stderr);

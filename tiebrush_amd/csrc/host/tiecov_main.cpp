@@ -41,26 +41,8 @@ static const char* USAGE =
 // ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
 // how often -r / --region is given (Args keeps the last value of a repeated option)
 static int count_region_opts(int argc, char** argv) {
-  int n = 0;
-  for (int i = 1; i < argc; ++i) {
-    const std::string a = argv[i];
-    if (a == "--region" || a == "--index-file") {
-      n += a == "--region";
-      ++i;
-    } else if (a.compare(0, 9, "--region=") == 0) {
-      ++n;
-    } else if (a.size() > 1 && a[0] == '-' && a[1] != '-') {
-      for (size_t k = 1; k < a.size(); ++k) {
-        const char c = a[k];
-        if (c == 'r') ++n;
-        if (c == 'r' || c == 'c' || c == 's' || c == 'j') {  // the rest of the word, or the next word, is its value
-          if (k + 1 == a.size()) ++i;
-          break;
-        }
-      }
-    }
-  }
-  return n;
+  static const char* const value_longs[] = {"index-file", nullptr};
+  return count_value_option(argc, argv, "region", 'r', value_longs, "csj");
 }
 
 static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::string& region, const std::string& index_file, const std::string& covfname,

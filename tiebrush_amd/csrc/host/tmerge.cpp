@@ -113,6 +113,8 @@ bool TInputFiles::addSam(GSamReader* r, int fidx) {  // tmerge.cpp:57-147
     sam_hdr_t* hi = swapHdr ? h : mHdr;
     for (int i = 0; i < lo->n_targets; ++i) {
       int m = hi->name2tid(lo->target_name[i]);
+      if (m < 0 && name_ref_file)
+        GError("Error: -r: ref %s not seen before: %s does not list the references the inputs before it list\n", lo->target_name[i].c_str(), r->fileName());
       if (m < 0) GError("Error: ref %s not seen before!\n", lo->target_name[i].c_str());
       if (m != i) GError("Error: ref %s from file %s does not have the expected id#!", lo->target_name[i].c_str(), r->fileName());
     }

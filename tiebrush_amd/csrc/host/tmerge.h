@@ -60,6 +60,7 @@ struct TInputFiles {
   std::vector<TInputRecord*> recs;  // one head record per file, kept sorted like the reference's GList
   std::string headerfilename;
   bool headerfiletbMerged = false;
+  bool name_ref_file = false;  // tiebrush -r: the refusal of a reference no earlier input lists names the file that brings it
 
   ~TInputFiles();
   sam_hdr_t* header() { return mHdr; }

@@ -1,5 +1,6 @@
 // region.hip — the device side of `tiecov -r`: the records of a decoded tile that overlap a region as tiecov's input
-// view (tbk_region_view), and the rows of a coverage / sample call cut to the region (tbk_cov_clip, tbk_sample_clip).
+// view (tbk_region_view), and the rows of a coverage / sample call cut to the region (tbk_cov_clip, tbk_sample_clip); and of `tiebrush -r`
+// (DESIGN.md §4f): the same records as a collapse tile (tbk_tile_region, at the end of this file).
 //
 // The reference has no region option (tiecov.cpp walks the whole file); the contract is that the rows equal the whole-file run's rows
 // on the region, bit for bit.  These are bandwidth-trivial passes of one thread per record or row, each kernel a launch of its own
@@ -374,4 +375,210 @@ extern "C" int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, 
   rows->n_intervals = m;
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   return tbk_check_launch(ctx, "sample_clip");
+}
+
+// ---- tbk_tile_region: the region's records of a decoded tile as a collapse tile -------------------------------------------
+// The flags and the kept CIGAR counts are rv_flag_k's; what a collapse tile carries beyond tiecov's view — nh, mapq, yd_in, the MD and QNAME
+// CSRs, qname_hash, the record-offset table behind tbk_bam_records and the encoders — moves in the same scatter pass.
+//   rv_flag_k       keep / kcig as above
+//   rt_lens_k       kmd[i] / kqn[i] = the kept record's MD / QNAME byte counts (only with those columns)
+//   up to four exclusive scans (tbk_exscan_u32), n + 1 elements each
+//   rt_scatter_k    a thread per record: the columns, the three CSR payloads and the record offset, file order kept
+//   rt_fileoff_k    file_off_out[f] = the keep scan read at the old file_off[f]
+namespace {
+
+struct RtCols {
+  int32_t *tid, *pos, *nh;
+  uint16_t* flag;
+  uint8_t *mapq, *strand;
+  uint32_t *cig_off, *cig;
+  double* yc;
+  int64_t *yx, *yd;
+  uint32_t* md_off;
+  uint8_t *md, *md_has;
+  uint64_t* qh;
+  uint32_t* qn_off;
+  uint8_t* qn;
+  uint64_t* rec;
+};
+
+__global__ __launch_bounds__(RG_NT) void rt_lens_k(uint32_t n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ md_off,
+                                                   const uint32_t* __restrict__ qn_off, uint32_t* __restrict__ kmd /* [n + 1] or NULL */,
+                                                   uint32_t* __restrict__ kqn /* [n + 1] or NULL */) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i > n) return;
+  const bool k = i < n && keep[i];
+  if (kmd) kmd[i] = k ? md_off[i + 1] - md_off[i] : 0u;
+  if (kqn) kqn[i] = k ? qn_off[i + 1] - qn_off[i] : 0u;
+}
+
+__global__ __launch_bounds__(RG_NT) void rt_scatter_k(uint32_t n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ koff /* [n + 1] */,
+                                                      const uint32_t* __restrict__ coff, const uint32_t* __restrict__ moff, const uint32_t* __restrict__ qoff,
+                                                      RtCols I, RtCols O) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i > n) return;
+  if (i == n) {  // the CSRs' closing offsets
+    const uint32_t o = koff[n];
+    O.cig_off[o] = coff[n];
+    if (I.md_off) O.md_off[o] = moff[n];
+    if (I.qn_off) O.qn_off[o] = qoff[n];
+    return;
+  }
+  if (!keep[i]) return;
+  const uint32_t o = koff[i];
+  O.tid[o] = I.tid[i];
+  O.pos[o] = I.pos[i];
+  O.nh[o] = I.nh[i];
+  O.flag[o] = I.flag[i];
+  O.mapq[o] = I.mapq[i];
+  O.strand[o] = I.strand[i];
+  O.rec[o] = I.rec[i];
+  if (I.yc) {
+    O.yc[o] = I.yc[i];
+    O.yx[o] = I.yx[i];
+    O.yd[o] = I.yd[i];
+  }
+  {
+    const uint32_t d = coff[i], c0 = I.cig_off[i], nc = I.cig_off[i + 1] - c0;
+    O.cig_off[o] = d;
+    for (uint32_t q = 0; q < nc; ++q) O.cig[d + q] = I.cig[c0 + q];
+  }
+  if (I.md_off) {
+    const uint32_t d = moff[i], m0 = I.md_off[i], nm = I.md_off[i + 1] - m0;
+    O.md_off[o] = d;
+    O.md_has[o] = I.md_has[i];
+    for (uint32_t q = 0; q < nm; ++q) O.md[d + q] = I.md[m0 + q];
+  }
+  if (I.qn_off) {
+    const uint32_t d = qoff[i], q0 = I.qn_off[i], nq = I.qn_off[i + 1] - q0;
+    O.qn_off[o] = d;
+    O.qh[o] = I.qh[i];
+    for (uint32_t q = 0; q < nq; ++q) O.qn[d + q] = I.qn[q0 + q];
+  }
+}
+
+__global__ void rt_fileoff_k(uint32_t k1, const uint32_t* __restrict__ file_off, const uint32_t* __restrict__ koff, uint32_t* __restrict__ out) {
+  const uint32_t f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f < k1) out[f] = koff[file_off[f]];
+}
+
+template <class T>
+T* rt_alloc(tbk_ctx* ctx, size_t n) {
+  return (T*)tbk_bam_dev_alloc(ctx, (n ? n : 1) * sizeof(T));
+}
+
+}  // namespace
+
+extern "C" int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid, int64_t beg, int64_t end, tbk_soa_in* out, uint32_t* file_off_out,
+                               uint32_t* n_kept) {
+  if (!ctx || !tile || !out || !file_off_out || !n_kept || tile->mem != TBK_MEM_DEVICE || tid < 0 || beg < 0 || end < beg) return TBK_EINVAL;
+  const uint32_t n = tile->n_records, k = tile->n_files;
+  if (k == 0 || !tile->file_off || tile->prio_hi || tile->prio_lo) return TBK_EINVAL;
+  if (tile->file_off[0] != 0 || tile->file_off[k] != n) return TBK_EINVAL;
+  for (uint32_t f = 0; f < k; ++f)
+    if (tile->file_off[f + 1] < tile->file_off[f]) return TBK_EINVAL;
+  if (n == UINT32_MAX) return TBK_E2BIG;
+  const bool has_y = tile->yc_in != nullptr, has_md = tile->md_off != nullptr, has_qn = tile->qname_off != nullptr;
+  if (n) {
+    if (!tbk_bam_dev_is_tile(ctx, tile)) {
+      ctx->last_error = "tile_region: not the tile the last decode on this context returned";
+      return TBK_EINVAL;
+    }
+    if (!tile->tid || !tile->pos || !tile->flag || !tile->mapq || !tile->strand || !tile->nh || !tile->cig_off || (tile->n_cigar_ops && !tile->cig) ||
+        (has_y && (!tile->yx_in || !tile->yd_in)) || (has_md && !tile->md_has) || (has_qn && !tile->qname_hash))
+      return TBK_EINVAL;
+  }
+  TBK_HIP(hipSetDevice(ctx->device));
+  TBK_TRY(tbk_collapse_finish_yd(ctx));  // (a deferred YD stage may still read the tile)
+  const tbk_soa_in in = *tile;           // (out may be the caller's input struct, file_off_out its file_off)
+  const std::vector<uint32_t> fo_in(tile->file_off, tile->file_off + (size_t)k + 1);
+  memset(out, 0, sizeof(*out));
+  out->mem = TBK_MEM_DEVICE;
+  out->n_files = k;
+  out->file_off = file_off_out;
+  out->tbmerged = in.tbmerged;
+  for (uint32_t f = 0; f <= k; ++f) file_off_out[f] = 0;
+  *n_kept = 0;
+  ctx->view_prep.valid = false;
+  if (n == 0) return 0;
+  const uint8_t* d_inf = nullptr;
+  const uint64_t* d_rec = nullptr;
+  uint32_t n_rec = 0;
+  if (!tbk_bam_dev_records(ctx, &d_inf, &d_rec, &n_rec) || n_rec != n) return TBK_EINVAL;
+  tbk_prof_begin_call(ctx);
+  ProfEnd prof_end{ctx};
+  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 32 + ((size_t)k + 1) * 8 + ((size_t)1 << 20)));
+  uint32_t* keep = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* kcig = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* koff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* coff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t *kmd = nullptr, *moff = nullptr, *kqn = nullptr, *qoff = nullptr;
+  if (has_md) kmd = ws_alloc<uint32_t>(ctx, (size_t)n + 1), moff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  if (has_qn) kqn = ws_alloc<uint32_t>(ctx, (size_t)n + 1), qoff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* d_fo = ws_alloc<uint32_t>(ctx, (size_t)k + 1);
+  uint32_t* d_fo_out = ws_alloc<uint32_t>(ctx, (size_t)k + 1);
+  if (!keep || !kcig || !koff || !coff || (has_md && !moff) || (has_qn && !qoff) || !d_fo || !d_fo_out) return TBK_ENOMEM;
+  const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
+  TBK_HIP(hipMemcpyAsync(d_fo, fo_in.data(), ((size_t)k + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+  TBK_LAUNCH(ctx, "region_flag", rv_flag_k, grid, RG_NT, 0, n, in.tid, in.pos, in.cig_off, in.cig, tid, beg, end, keep, kcig);
+  TBK_TRY(tbk_exscan_u32(ctx, keep, koff, n + 1, nullptr));
+  TBK_TRY(tbk_exscan_u32(ctx, kcig, coff, n + 1, nullptr));
+  if (has_md || has_qn) {
+    TBK_LAUNCH(ctx, "tile_region_lens", rt_lens_k, grid, RG_NT, 0, n, keep, in.md_off, in.qname_off, kmd, kqn);
+    if (has_md) TBK_TRY(tbk_exscan_u32(ctx, kmd, moff, n + 1, nullptr));
+    if (has_qn) TBK_TRY(tbk_exscan_u32(ctx, kqn, qoff, n + 1, nullptr));
+  }
+  uint32_t tot[4] = {0, 0, 0, 0};
+  TBK_HIP(hipMemcpyAsync(&tot[0], koff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(&tot[1], coff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (has_md) TBK_HIP(hipMemcpyAsync(&tot[2], moff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  if (has_qn) TBK_HIP(hipMemcpyAsync(&tot[3], qoff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  TBK_TRY(tbk_check_launch(ctx, "tile_region"));
+  const size_t nk = tot[0], nc = tot[1], nm = tot[2], nq = tot[3];  // (subsets of the tile's counts, which are uint32)
+  if (nk > n || nc > in.n_cigar_ops) return TBK_EHIP;
+  RtCols I{}, O{};
+  I.tid = const_cast<int32_t*>(in.tid), I.pos = const_cast<int32_t*>(in.pos), I.nh = const_cast<int32_t*>(in.nh);
+  I.flag = const_cast<uint16_t*>(in.flag), I.mapq = const_cast<uint8_t*>(in.mapq), I.strand = const_cast<uint8_t*>(in.strand);
+  I.cig_off = const_cast<uint32_t*>(in.cig_off), I.cig = const_cast<uint32_t*>(in.cig);
+  I.yc = const_cast<double*>(in.yc_in), I.yx = const_cast<int64_t*>(in.yx_in), I.yd = const_cast<int64_t*>(in.yd_in);
+  I.md_off = const_cast<uint32_t*>(in.md_off), I.md = const_cast<uint8_t*>(in.md), I.md_has = const_cast<uint8_t*>(in.md_has);
+  I.qh = const_cast<uint64_t*>(in.qname_hash), I.qn_off = const_cast<uint32_t*>(in.qname_off), I.qn = const_cast<uint8_t*>(in.qname);
+  I.rec = const_cast<uint64_t*>(d_rec);
+  O.tid = rt_alloc<int32_t>(ctx, nk), O.pos = rt_alloc<int32_t>(ctx, nk), O.nh = rt_alloc<int32_t>(ctx, nk);
+  O.flag = rt_alloc<uint16_t>(ctx, nk), O.mapq = rt_alloc<uint8_t>(ctx, nk), O.strand = rt_alloc<uint8_t>(ctx, nk);
+  O.cig_off = rt_alloc<uint32_t>(ctx, nk + 1), O.cig = rt_alloc<uint32_t>(ctx, nc);
+  O.rec = rt_alloc<uint64_t>(ctx, nk);
+  bool ok = O.tid && O.pos && O.nh && O.flag && O.mapq && O.strand && O.cig_off && O.cig && O.rec;
+  if (has_y) {
+    O.yc = rt_alloc<double>(ctx, nk), O.yx = rt_alloc<int64_t>(ctx, nk), O.yd = rt_alloc<int64_t>(ctx, nk);
+    ok = ok && O.yc && O.yx && O.yd;
+  }
+  if (has_md) {
+    O.md_off = rt_alloc<uint32_t>(ctx, nk + 1), O.md = rt_alloc<uint8_t>(ctx, nm), O.md_has = rt_alloc<uint8_t>(ctx, nk);
+    ok = ok && O.md_off && O.md && O.md_has;
+  }
+  if (has_qn) {
+    O.qn_off = rt_alloc<uint32_t>(ctx, nk + 1), O.qn = rt_alloc<uint8_t>(ctx, nq), O.qh = rt_alloc<uint64_t>(ctx, nk);
+    ok = ok && O.qn_off && O.qn && O.qh;
+  }
+  if (!ok) {
+    (void)hipGetLastError();
+    return TBK_ENOMEM;
+  }
+  TBK_LAUNCH(ctx, "tile_region_scatter", rt_scatter_k, grid, RG_NT, 0, n, keep, koff, coff, moff, qoff, I, O);
+  TBK_LAUNCH(ctx, "tile_region_fileoff", rt_fileoff_k, cdiv((uint64_t)k + 1, 256), 256, 0, k + 1, d_fo, koff, d_fo_out);
+  TBK_HIP(hipMemcpyAsync(file_off_out, d_fo_out, ((size_t)k + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  TBK_TRY(tbk_check_launch(ctx, "tile_region"));
+  tbk_bam_dev_compacted(ctx, O.rec, (uint32_t)nk, O.tid);
+  out->n_records = (uint32_t)nk;
+  out->n_cigar_ops = (uint32_t)nc;
+  out->tid = O.tid, out->pos = O.pos, out->flag = O.flag, out->mapq = O.mapq, out->strand = O.strand, out->nh = O.nh;
+  out->cig_off = O.cig_off, out->cig = O.cig;
+  out->yc_in = O.yc, out->yx_in = O.yx, out->yd_in = O.yd;
+  out->md_off = O.md_off, out->md = O.md, out->md_has = O.md_has;
+  out->qname_hash = O.qh, out->qname_off = O.qn_off, out->qname = O.qn;
+  *n_kept = (uint32_t)nk;
+  return 0;
 }

@@ -208,6 +208,14 @@ int tbk_ix_check_opts(tbk_ctx* ctx, const tbk_ix_opts* ix);  // TBK_EINVAL for a
 int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& in, const tbk_ix_opts* ix, tbk_ix_part* part);
 // the tile tbk_bam_decode left on the context: inflated streams, record offsets, record count (false: there is none)
 bool tbk_bam_dev_records(tbk_ctx* ctx, const uint8_t** inf, const uint64_t** rec, uint32_t* n);
+// tbk_tile_region's hold on that tile: whether `tile` is the one the last decode returned (not a joined one, not another context's: told
+// by the tid column and the record count alone, so only the struct the decode filled in, unchanged, is supported — a struct with the
+// context's tid column and other columns of the caller's is not told apart); device
+// memory that lives and dies with the tile; and the hand-over of the compacted record-offset table (rec NULL: the table stays), the
+// kept count and the compacted tile's tid column
+bool tbk_bam_dev_is_tile(tbk_ctx* ctx, const tbk_soa_in* tile);
+void* tbk_bam_dev_alloc(tbk_ctx* ctx, size_t bytes);
+void tbk_bam_dev_compacted(tbk_ctx* ctx, uint64_t* rec, uint32_t n, const int32_t* tid);
 
 // side context (created on first use; nullptr if that fails -> the caller runs the branch inline), and the call
 // bracket a branch thread puts around its work on it

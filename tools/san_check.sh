@@ -39,6 +39,13 @@ for SAN in $MODES; do
   ( set -e
     $HB/tbh_tool cat $G/t1/t1.bam $W/t1.bam
     $HB/tbh_tool bai $W/t1.bam
+    # (the host plumbing of `tiebrush -r`: many inputs, index queries, chunk reads on several threads)
+    for i in 0 1 2 3; do cp $G/t1/t1s$i.bam $W/s$i.bam; done
+    $HB/tbh_tool bai $W/s0.bam; $HB/tbh_tool csi $W/s1.bam; $HB/tbh_tool bai $W/s2.bam; $HB/tbh_tool csi $W/s3.bam
+    $HB/tbh_tool mquery chr12:98,595,000-98,596,000 4 $W/s0.bam $W/s1.bam $W/s2.bam $W/s3.bam
+    # (a shorter file under a longer file's index, whose chunk ends behind it: refused with status 1, nothing else)
+    cp $G/t1/t1s5.bam $W/short.bam; cp $W/s0.bam.bai $W/short.bam.bai
+    rc=0; $HB/tbh_tool mquery chr12 4 $W/s1.bam $W/short.bam 2> $W/short.err || rc=$?; cat $W/short.err; [ $rc -eq 1 ] && grep -q "names a chunk outside" $W/short.err
     $HB/tbh_tool mergeorder $G/t2/t2s0.bam $G/t2/t2s1.bam $G/t2/t2s2.bam > $W/order.txt
     $HB/tbh_tool soa $W/soa $G/t2/t2s*.bam
     $HB/tbh_tool fastsoa $W/fsoa $G/t2/t2s*.bam
