@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TBK_ABI_VERSION 8
+#define TBK_ABI_VERSION 9
 
 typedef struct tbk_ctx tbk_ctx;
 
@@ -239,6 +239,22 @@ int tbk_collapse_finish_yd(tbk_ctx* ctx);
  * auxiliary stream of the YD stage (a hardware queue) and the first dispatch of its list machines.  A command line calls it on the
  * thread that brings the device up, beside its decode; a long-lived caller never needs it. */
 int tbk_warmup(tbk_ctx* ctx);
+/* (ABI version 9) The route the context's last tbk_collapse_tile took: which form of the collapse stage produced the result and what
+ * sent the tile there.  The first four fields are host bookkeeping of the call and always filled.  The window path's counts are
+ * recorded only while the debug key wg_stats=1 is set (tbk_set_debug); they describe the last window attempt of the call that ran its
+ * window kernels, whether or not its result was kept. */
+enum { TBK_ROUTE_NONE = 0, TBK_ROUTE_RAW_WINDOW = 1, TBK_ROUTE_COMPACTED_WINDOW = 2, TBK_ROUTE_SORT = 3 };
+typedef struct tbk_collapse_route {
+  int32_t form;            /* TBK_ROUTE_*: the form whose result the call returned (NONE: no result — an error, or nothing passed) */
+  int32_t reseeds;         /* key-hash collisions met: seeds given up before the result (or before TBK_ECOLLISION) */
+  uint8_t raw_handed_back; /* the raw window form refused the input (an inversion, a mapped read without a reference) */
+  uint8_t big_bucket;      /* a pile-up with more distinct alignments than the window path holds sent the tile to the sort path */
+  uint8_t wg_stats;        /* 1: the four counts below were recorded */
+  uint8_t reserved;
+  uint32_t nw, nw_live;    /* windows of the partition; windows that hold records */
+  uint32_t ovf1, ovf2;     /* windows that overflowed the first table; the second one (= the LDS sort kernel's worklist) */
+} tbk_collapse_route;
+int tbk_last_route(const tbk_ctx* ctx, tbk_collapse_route* out);
 int tbk_coverage_tile(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out);
 int tbk_sample_tile(tbk_ctx* ctx, const tbk_cov_in* in, int32_t num_samples, tbk_sample_out* out);
 

@@ -232,7 +232,7 @@ def test_long_reference_view(ctx, tmp_path):
 
 def test_abi_versions_unchanged():
     from tiebrush_amd import _lib
-    assert _lib.load().tbk_abi_version() == 8 and _lib.load_host().tbh_abi_version() == 1
+    assert _lib.load().tbk_abi_version() == 9 and _lib.load_host().tbh_abi_version() == 1
 
 
 # ---- the command line -------------------------------------------------------------------------------------------------------------------

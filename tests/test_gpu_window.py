@@ -3,12 +3,15 @@ its forms: RAW (keys, filter and effective ends computed inside the window kerne
 (TBK_RAW=0: key pass + scan + compaction first).  Small adversarial tiles (one window), synthetic tiles of many windows with
 every tier (hash table, second table, LDS sort), pile-ups with unsorted ends (the effective-end scan across waves, rows and
 chunks), unmapped records inside and behind the files, inputs the raw form hands back to the general path."""
+import os
+
 import numpy as np
 import pytest
 
 from helpers import tbk_debug
 
-from test_gpu_fuzz import STRATS, _cmp, _rand_tile
+from test_gpu_fuzz import STRATS, _rand_tile
+from test_gpu_fuzz import _cmp as _cmp_with_rec_group
 
 pytestmark = pytest.mark.gpu
 
@@ -35,6 +38,23 @@ def window_mode(request, monkeypatch):
 
 
 from helpers import tile_from_records as _tile  # noqa: E402
+
+
+def _cmp(ctx, tile, **kw):
+    """test_gpu_fuzz._cmp asks for the record -> group map, and with it every passing record leaves its slot (the kernels of
+    raw-dense-verify).  The raw mode is the form of a plain tiebrush run: it runs once more without the map — only the records whose key
+    word is hashed are listed per window (wg_finish_sparse_k) — and everything else is compared again."""
+    from tiebrush_amd import api
+    want = _cmp_with_rec_group(ctx, tile, **kw)
+    dbg = os.environ.get("TBK_DEBUG", "")
+    if "raw=1" in dbg.split(",") and "wg_dense_verify" not in dbg:
+        got = api.to_numpy(ctx.collapse(tile, **kw))
+        assert got["n_groups"] == want["n_groups"] and got["n_passed"] == want["n_passed"], kw
+        for k in ("rep", "yc", "yx", "yd", "g_start", "g_end"):
+            assert np.array_equal(np.asarray(got[k]), np.asarray(want[k])), (k, kw)
+        route = ctx.collapse_route()
+        assert not want["n_passed"] or route["form"] in ("raw", "compacted", "sort") and (route["form"] == "raw" or route["raw_handed_back"] or route["big_bucket"]), route
+    return want
 
 
 @pytest.mark.parametrize("seed", range(4))

@@ -51,7 +51,7 @@ def test_usage_lists_the_track_options(tmp_path):
 def test_track_symbols_are_bound():
     assert "tbk_track_names" in _lib.SYMBOLS and "tbk_format_track" in _lib.SYMBOLS
     L = _lib.load()
-    assert L.tbk_abi_version() == 8
+    assert L.tbk_abi_version() == 9
     assert hasattr(L, "tbk_track_names") and hasattr(L, "tbk_format_track")
     fields = [f for f, _ in _lib.TrackRows._fields_]
     assert fields[:4] == ["mem", "kind", "n", "reserved"] and fields[-1] == "first_junc"

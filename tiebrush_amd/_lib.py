@@ -28,13 +28,22 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_groups_to_cov_in", "tbk_bgzf_inflate", "tbk_bam_decode", "tbk_bam_records", "tbk_bam_release", "tbk_shard_prepare", "tbk_shard_probe_max", "tbk_shard_probe_next",
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
-           "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region"]
+           "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route"]
 
 
 class CollapseOpts(C.Structure):
     _fields_ = [("strategy", C.c_int32), ("max_nh", C.c_int32), ("min_qual", C.c_int32), ("flags_mask", C.c_uint32),
                 ("keep_supplementary", C.c_uint8), ("keep_secondary", C.c_uint8), ("keep_unmapped", C.c_uint8),
                 ("collapse_same", C.c_uint8), ("store_frac", C.c_uint8), ("defer_yd", C.c_uint8), ("keep_results", C.c_uint8), ("reserved", C.c_uint8 * 1)]
+
+
+class CollapseRoute(C.Structure):
+    _fields_ = [("form", C.c_int32), ("reseeds", C.c_int32), ("raw_handed_back", C.c_uint8), ("big_bucket", C.c_uint8),
+                ("wg_stats", C.c_uint8), ("reserved", C.c_uint8), ("nw", C.c_uint32), ("nw_live", C.c_uint32), ("ovf1", C.c_uint32),
+                ("ovf2", C.c_uint32)]
+
+
+ROUTE_FORMS = {0: "none", 1: "raw", 2: "compacted", 3: "sort"}
 
 
 class SoaIn(C.Structure):
@@ -143,6 +152,8 @@ def load():
     L.tbk_get_stream.restype = _P
     L.tbk_set_profiling.argtypes = [_P, C.c_int]
     L.tbk_set_debug.argtypes = [_P, C.c_char_p]
+    L.tbk_last_route.argtypes = [_P, C.POINTER(CollapseRoute)]
+    L.tbk_last_route.restype = C.c_int
     L.tbk_kernel_times.argtypes = [_P, C.POINTER(KernelTime), C.c_int]
     L.tbk_host_alloc.argtypes = [C.c_size_t, C.POINTER(_P)]
     L.tbk_host_free.argtypes = [_P]

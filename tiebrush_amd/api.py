@@ -173,6 +173,17 @@ class Context:
     def last_message(self) -> str:
         return (self.L.tbk_last_error(self.h) or b"").decode()
 
+    def collapse_route(self) -> dict:
+        """tbk_last_route: the route the last collapse on this context took — form ("raw" / "compacted" window path, "sort", "none": no
+        result), reseeds, raw_handed_back, big_bucket; with the debug key wg_stats=1 also nw, nw_live, ovf1, ovf2 of the window path"""
+        r = _lib.CollapseRoute()
+        self._check(self._lib.tbk_last_route(self.h, C.byref(r)), "tbk_last_route")
+        d = dict(form=_lib.ROUTE_FORMS[int(r.form)], reseeds=int(r.reseeds), raw_handed_back=bool(r.raw_handed_back),
+                 big_bucket=bool(r.big_bucket))
+        if r.wg_stats:
+            d.update(nw=int(r.nw), nw_live=int(r.nw_live), ovf1=int(r.ovf1), ovf2=int(r.ovf2))
+        return d
+
     def stream_ptr(self):
         return self.L.tbk_get_stream(self.h)
 

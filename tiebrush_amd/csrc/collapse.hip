@@ -2217,6 +2217,7 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
   const uint32_t B = 256;
   out->n_groups = 0;
   out->n_passed = 0;
+  ctx->route = tbk_collapse_route{};
   if (out->rec_group) TBK_HIP(hipMemsetAsync(out->rec_group, 0xFF, (size_t)n * 4, ctx->stream));
   if (n == 0) return 0;
   uint64_t* sc = ctx->d_scalars;  // [0]=n_pass [1]=n_groups [2]=n_items [3]=n_chains [4]=n_nodes
@@ -2390,6 +2391,19 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
   bool lean = use_runs && !O.store_frac && !any_tbm && n >= runs_min;
   const uint64_t seeds[4] = {TBK_KEY_SEED0, 0xA5A5F00DCAFE1234ull, 0x0123456789ABCDEFull, 0xDEADBEEF0BADF00Dull};
   int attempt = 0;
+  // the route of this call for tbk_last_route: host bookkeeping, written back on every way out of the loop
+  struct RouteNote {
+    tbk_ctx* c;
+    const int* attempt;
+    int form = TBK_ROUTE_NONE;
+    bool handed_back = false, big = false;
+    ~RouteNote() {
+      c->route.form = form;
+      c->route.reseeds = *attempt;
+      c->route.raw_handed_back = handed_back;
+      c->route.big_bucket = big;
+    }
+  } route{ctx, &attempt};
   for (;;) {
     if (attempt == 4) return TBK_ECOLLISION;
     O.seed = seeds[attempt];
@@ -2410,6 +2424,8 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       if (eb & (TBK_DERR_RAWORDER | TBK_DERR_BIGBUCKET | TBK_DERR_FRACTIONAL)) {  // not this path's kind of input (the general front end
         TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));     // decides what is an error), or a pile-up beyond the
         use_raw = false;                                                            // group table
+        route.handed_back |= (eb & TBK_DERR_RAWORDER) != 0;
+        route.big |= (eb & TBK_DERR_BIGBUCKET) != 0;
         if ((eb & (TBK_DERR_BIGBUCKET | TBK_DERR_FRACTIONAL)) || part) use_win = false;
         part = false;
         continue;
@@ -2462,6 +2478,7 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       if (eb) return tbk_derr_to_status(ctx, eb);
       win_out = wo;
       win_done = true;
+      route.form = TBK_ROUTE_RAW_WINDOW;
       if (attempt > 0) {
         char b[96];
         snprintf(b, sizeof(b), "info: key-hash collision, reseeded %d time(s)", attempt);
@@ -2496,6 +2513,7 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       if (eb & TBK_DERR_BIGBUCKET) {  // a pile-up with more distinct alignments than the LDS table holds: sort path
         TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
         use_win = false;
+        route.big = true;
         continue;
       }
       if (eb & TBK_DERR_COLLISION) {  // reseed
@@ -2537,6 +2555,7 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       if (eb) return tbk_derr_to_status(ctx, eb);
       win_out = wo;
       win_done = true;
+      route.form = TBK_ROUTE_COMPACTED_WINDOW;
       if (attempt > 0) {
         char b[96];
         snprintf(b, sizeof(b), "info: key-hash collision, reseeded %d time(s)", attempt);
@@ -2652,6 +2671,7 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
     }
     if (eb & ~TBK_DERR_FRACTIONAL) return tbk_derr_to_status(ctx, eb);
     sb = s2;
+    route.form = TBK_ROUTE_SORT;
     if (attempt > 0) {
       char b[96];
       snprintf(b, sizeof(b), "info: key-hash collision, reseeded %d time(s)", attempt);

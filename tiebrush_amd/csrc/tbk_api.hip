@@ -513,6 +513,8 @@ void tbk_debug_parse(const char* spec, TbkDebug* out) {
     else if (k == "yd_literal") out->yd_literal = on;
     else if (k == "yd_front") out->yd_front_split = v == "split";
     else if (k == "yd_own_arena") out->yd_own_arena = on;
+    else if (k == "wg_stats") out->wg_stats = on;
+    else if (k == "wg_og") out->wg_og = (uint32_t)u;
     else if (k == "wg_dense_verify") out->wg_dense_verify = on;
     else if (k == "wg_rank_merge") out->wg_rank_merge = on;
     else if (k == "cov_legacy") out->cov_legacy = on;
@@ -630,6 +632,11 @@ void tbk_destroy(tbk_ctx* ctx) {
   delete ctx;
 }
 
+int tbk_last_route(const tbk_ctx* ctx, tbk_collapse_route* out) {
+  if (!ctx || !out) return TBK_EINVAL;
+  *out = ctx->route;
+  return 0;
+}
 const char* tbk_last_error(const tbk_ctx* ctx) { return ctx ? ctx->last_error.c_str() : ""; }
 
 int tbk_set_stream(tbk_ctx* ctx, void* s) {

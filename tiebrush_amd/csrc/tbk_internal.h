@@ -98,6 +98,8 @@ struct TbkDebug {
   bool yd_front_split = false;  // yd_front=split: (items placed by list) the groups' records and exon offsets by passes of their own, yd_groups_k and
                                 // a device-wide scan, ahead of the count pass (default, yd_front=fused: the count pass makes them)
   bool yd_own_arena = false;  // yd_own_arena=1: a deferred YD stage never borrows the main arena
+  uint32_t wg_og = 0;         // wg_og=N: chunks per block of the window path's offsets pass, 1 .. 8 (0: by the tile's size — one below 8 M records)
+  bool wg_stats = false;      // wg_stats=1: the window path's window and overflow counts are read back for tbk_last_route
   bool wg_dense_verify = false, wg_rank_merge = false;  // window path: per-record verification form; merge-sort ranking of a window's groups
   bool cov_legacy = false, cov_bundle_scan = false, cov_prep = false, junc_radix = false, no_junc_agg = false;
   uint64_t cov_tile_cap = 0;  // cov_tile_cap=N: capacity of the lean chain's tile tables (0: by the input)
@@ -155,6 +157,7 @@ struct tbk_ctx {
   size_t ev_used = 0;
   std::vector<tbk_kernel_time> last_times;
   std::string last_error;
+  tbk_collapse_route route{};    // tbk_last_route: the last collapse's (tbk_collapse_device, tbk_window_groups)
   int num_cu = 256;
   // deferred YD stage (tbk_collapse_opts.defer_yd): a private side context + helper thread
   void* yd_job = nullptr;        // prepared by tbk_collapse_device, consumed by tbk_collapse_yd_run

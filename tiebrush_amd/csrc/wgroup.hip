@@ -2191,7 +2191,7 @@ static int wg_offsets_build(tbk_ctx* ctx, bool raw, const uint64_t* chi, const i
   if (!offT) return TBK_ENOMEM;
   // chunks per block: eight where that still leaves a few thousand blocks, fewer on small inputs (the owner's side of the multi-rank
   // protocol: 7 M rows as 450 blocks took twice as long as 3 600 blocks of one chunk)
-  const uint32_t og = std::min<uint32_t>(WG_OG, std::max<uint32_t>(1u, m / (WG_OC * 2048u)));
+  const uint32_t og = std::min<uint32_t>(WG_OG, std::max<uint32_t>(1u, ctx->dbg.wg_og ? ctx->dbg.wg_og : m / (WG_OC * 2048u)));  // (wg_og: test hook)
   if (raw)
     TBK_LAUNCH(ctx, "wg_offsets", wg_offsets_stream_k<true>, cdiv(m, WG_OC * og), 256, 0, chi, rtid, rpos, ctid, d_run_off, k, m, W, nW, nrows, offT, ctx->d_err, og);
   else
@@ -2411,7 +2411,7 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   if (!ovf || !ovf2) return TBK_ENOMEM;
   TBK_HIP(hipMemsetAsync(ovf, 0, sizeof(uint32_t), ctx->stream));
   TBK_HIP(hipMemsetAsync(ovf2, 0, sizeof(uint32_t), ctx->stream));
-  const uint32_t* ovf1_dbg = ovf;  // (TBK_WG_DEBUG: the first tier's overflow count)
+  const uint32_t* ovf1_dbg = ovf;  // (TBK_WG_DEBUG, wg_stats: the first tier's overflow count)
   // the windows that hold records (every splitter owns two bounds, so about half of the windows are empty by construction):
   // the hash kernel's grid is exactly those — an empty block would hold a table's worth of LDS while it finds out
   uint32_t* wlist = ws_alloc<uint32_t>(ctx, nw);
@@ -2494,12 +2494,23 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   }
   if (T.fmask) TBK_LAUNCH(ctx, "wg_fmask", wg_fmask_k, std::min<uint32_t>(nw, 1024u), 64, 0, ovf, ovf_cap, T);
   uint64_t* sc = ctx->d_scalars;
+  if (ctx->dbg.wg_stats) {  // (test hook) the two overflow counts ride back with the counters below: sc[9], sc[10], zeroed by the caller
+    TBK_HIP(hipMemcpyAsync(sc + 9, ovf1_dbg, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+    TBK_HIP(hipMemcpyAsync(sc + 10, ovf2, sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+  }
   if (spread) TBK_LAUNCH(ctx, "wg_spread_sum", wg_spread_sum_k, 1, 64, 0, spread, (unsigned long long*)(sc + 0), (unsigned long long*)(sc + 6));
   TBK_TRY(tbk_exscan_u32(ctx, T.wg_cnt, gbase, nw, sc + 1));
   TBK_TRY(tbk_exscan_u32(ctx, T.wp_cnt, pbase, nw, sc + 2));
   uint32_t eb = 0;
   TBK_TRY(tbk_sync_err(ctx, &eb));
   *err_bits = eb;
+  if (ctx->dbg.wg_stats) {
+    ctx->route.wg_stats = 1;
+    ctx->route.nw = nw;
+    ctx->route.nw_live = nw_live;
+    ctx->route.ovf1 = (uint32_t)ctx->h_scalars[9];
+    ctx->route.ovf2 = (uint32_t)ctx->h_scalars[10];
+  }
   if (T.dbg) {
     unsigned long long h[32];
     TBK_HIP(hipMemcpy(h, T.dbg, sizeof(h), hipMemcpyDeviceToHost));
