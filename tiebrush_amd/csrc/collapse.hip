@@ -2411,7 +2411,7 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
     if (use_raw && use_win) {
       uint32_t eb = 0;
       WgOut wo;
-      // (the compaction pass writes the results at their key-order places; col_write_k below only rewrites the members of tie sets)
+      // (the compaction pass writes the results at their key-order places; only the members of tie sets are rewritten behind it)
       WgDirectOut direct;
       direct.cap = out->cap_groups;
       direct.rep = out->rep, direct.yc = out->yc, direct.yx = out->yx;
@@ -2451,27 +2451,28 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       G.first = wo.first;
       G.tie = wo.tie;
       g_yd = ws_alloc<int32_t>(ctx, ng);
-      gperm = ws_alloc<uint32_t>(ctx, ng);
+      // the output order and its inverse (made where col_recgroup_w_k or yd_fill_w_k, items NOT placed by list, will read it) come with
+      // the groups: the compaction wrote the identity and wg_tie_k permuted the tie sets of several groups and rewrote their members'
+      // results (wo.ties_done; wg_back=split: col_tie_sort_k and col_write_k<tied only> do both here, a pass over every group each)
+      gperm = wo.gperm;
+      ginv = wo.ginv;
       // (items placed by list leave their distances with the items, yd_lgather_k: nothing accumulates in g_yd then)
       const bool yd_by_list = !wo.pgrp || tbk_yd_by_list(ctx, I.k);
-      // the inverse permutation has two readers on this path, col_recgroup_w_k and yd_fill_w_k (items NOT placed by list): not made
-      // when neither will run
-      ginv = (out->rec_group || !yd_by_list) ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
       if (!gperm || ((out->rec_group || !yd_by_list) && !ginv)) return TBK_ENOMEM;
       if (!yd_by_list) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
       const uint64_t* png = sc + 1;  // (tbk_window_groups left the group count there)
-      TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng, B), B, 0, I, O.strategy, png, wo.gmem, G, gperm, ginv);
+      if (!wo.ties_done) TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng, B), B, 0, I, O.strategy, png, wo.gmem, G, gperm, ginv);
       // (effend == nullptr: the effective end of the representative — or the low word of its explicit priority — rides in the
       // high word of G.rep)
-      if (direct_on)
+      if (direct_on && !wo.ties_done)
         TBK_LAUNCH(ctx, "col_write", col_write_k<true>, cdiv(ng, B), B, 0, png, gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,
                    out->yx, out->g_start, out->g_end, (const int32_t*)nullptr, out->rep_effend, out->g_key, O.strategy);
-      else
+      else if (!direct_on)  // (the caller's arrays are not all there: nothing was written in key order, every group is written here)
         TBK_LAUNCH(ctx, "col_write", col_write_k<false>, cdiv(ng, B), B, 0, png, gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,
                    out->yx, out->g_start, out->g_end, (const int32_t*)nullptr, out->rep_effend, out->g_key, O.strategy);
       if (out->rec_group) TBK_LAUNCH(ctx, "col_recgroup", col_recgroup_w_k, cdiv(n, B), B, 0, n, wo.rec_sg, ginv, out->rec_group);
       TBK_TRY(tbk_sync_err(ctx, &eb));
-      if (eb & TBK_DERR_COLLISION) {  // (the verification pass, wg_finish_raw_k): reseed
+      if (eb & TBK_DERR_COLLISION) {  // (the verification: the compaction's waves, or wg_finish_raw_k): reseed
         ++attempt;
         continue;
       }

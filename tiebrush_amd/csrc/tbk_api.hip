@@ -517,6 +517,7 @@ void tbk_debug_parse(const char* spec, TbkDebug* out) {
     else if (k == "wg_og") out->wg_og = (uint32_t)u;
     else if (k == "wg_dense_verify") out->wg_dense_verify = on;
     else if (k == "wg_rank_merge") out->wg_rank_merge = on;
+    else if (k == "wg_back") out->wg_back_split = v == "split";
     else if (k == "cov_legacy") out->cov_legacy = on;
     else if (k == "cov_bundle_scan") out->cov_bundle_scan = on;
     else if (k == "cov_prep") out->cov_prep = on;

@@ -101,6 +101,9 @@ struct TbkDebug {
   uint32_t wg_og = 0;         // wg_og=N: chunks per block of the window path's offsets pass, 1 .. 8 (0: by the tile's size — one below 8 M records)
   bool wg_stats = false;      // wg_stats=1: the window path's window and overflow counts are read back for tbk_last_route
   bool wg_dense_verify = false, wg_rank_merge = false;  // window path: per-record verification form; merge-sort ranking of a window's groups
+  bool wg_back_split = false;  // wg_back=split: (raw window form) the verification of the listed records, the tie sets (col_tie_sort_k, col_write_k)
+                               // and the scan of the incidence counts as passes of their own behind the compaction (default, wg_back=fused:
+                               // the compaction wave verifies and writes the identity order, wg_tie_k touches the tie sets alone)
   bool cov_legacy = false, cov_bundle_scan = false, cov_prep = false, junc_radix = false, no_junc_agg = false;
   uint64_t cov_tile_cap = 0;  // cov_tile_cap=N: capacity of the lean chain's tile tables (0: by the input)
   uint32_t jh_cap = 0;        // jh_cap=N: items a junction home may hold (0: JH_CAP)

@@ -21,11 +21,17 @@ struct WgOut {
   unsigned long long* rep = nullptr;
   uint32_t* first = nullptr;        // == identity: the "sorted arrays" of the later stages are the group arrays
   uint8_t* tie = nullptr;
+  // RAW: output order -> group and (want_ginv) its inverse, written by the compaction (identity) and wg_tie_k (the tie sets of several
+  // groups, whose members' results it also rewrites through the permutation).  ties_done == false (wg_back=split, or the compacted
+  // form): the arrays are allocated, col_tie_sort_k and col_write_k fill them and place the results.
+  uint32_t *gperm = nullptr, *ginv = nullptr;
+  bool ties_done = false;
 };
 
 // The caller's result arrays (tbk_groups_out), for the compaction pass to fill in key order — which IS the output order except inside
-// a tie set (groups that share bucket, strand and end: the reference comparator orders those, col_tie_sort_k), so the collapse only
-// rewrites the members of tie sets afterwards (col_write_k<tied only>) instead of reading every group's accumulators back.
+// a tie set (groups that share bucket, strand and end: the reference comparator orders those), so only the members of tie sets are
+// rewritten afterwards (wg_tie_k; wg_back=split: col_tie_sort_k and col_write_k<tied only>) instead of reading every group's
+// accumulators back.
 struct WgDirectOut {
   uint32_t cap = 0;  // entries the arrays hold (a tile with more groups is refused by the caller: nothing beyond cap is written)
   uint32_t* rep = nullptr;
@@ -40,8 +46,8 @@ struct WgDirectOut {
 // value); ceff: the effective end of the k-way merge of every compacted record (or, for cross-rank tiles, the low word of the
 // explicit merge priority); scratch_hi / scratch_lo: two dead 8-byte-per-record arrays (>= m) to work in.
 // Returns 0 and fills *out (arrays from ctx's workspace), or a TBK status; TBK_DERR_BIGBUCKET / _COLLISION come back in *err_bits
-// (the counts in *out are then meaningless).  The last kernel queued (wg_finish) may still raise TBK_DERR_COLLISION in ctx->d_err:
-// the caller's next read-back must treat it as a reseed request.
+// (the counts in *out are then meaningless).  The kernels queued last (wg_compact's verification of the listed records, or wg_finish)
+// may still raise TBK_DERR_COLLISION in ctx->d_err: the caller's next read-back must treat it as a reseed request.
 int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const uint64_t* chi, const uint64_t* clo, const uint32_t* cval,
                       const uint32_t* ceff, uint32_t m, const uint32_t* d_run_off, uint64_t* scratch_hi, uint64_t* scratch_lo,
                       bool want_rec_sg, uint64_t seed, WgOut* out, uint32_t* err_bits, const tbkd::ColOpt* raw_opt = nullptr, bool part = false,

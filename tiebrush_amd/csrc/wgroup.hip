@@ -1821,6 +1821,14 @@ struct WgFinal {
   unsigned long long* rep;
   uint8_t* tie;   // 1: the group opens a (tid, start, strand, end) tie set — it differs from the group before it in hi or in the span
   WgDirectOut D;  // (rep == nullptr: the caller writes its results itself)
+  uint32_t *gperm, *ginv;  // (raw form, optional) output order -> group and its inverse: the identity here, wg_tie_k permutes the tie sets
+  uint32_t* tcnt;          // (with gperm) [nw] window space: the window's groups that FOLLOW another one in a tie set — zero: wg_tie_k has
+                           // nothing to do there
+};
+struct WgVerify {  // VERIFY: the sparse verification list of the raw form (WgRaw::sparse), walked by the wave that owns the window
+  ColIn I;
+  int strategy;
+  uint32_t* err;
 };
 // The tie flag of a group needs the key of the group before it in key order.  Inside a window that is the lane below (or lane 63 of
 // the round before); the FIRST group of a window opens a tie set without a look at the window before: every bound in W is a value of
@@ -1829,21 +1837,60 @@ struct WgFinal {
 // form, raw_key(tid, pos) in the raw form and for group partials, where every passing record is mapped and carries
 // hi = (tid + 1, pos + 1, strand) (record_key; tid < 0 folds onto one key, which only makes windows coarser).  Two groups with equal hi
 // therefore have equal partition keys and lie in one window, so the last group of any earlier window differs in hi.
+//
+// VERIFY: the wave also compares the window's listed records — those whose key word is hashed, entry e = record vsrc[wbase + e] with slot
+// cslot[wbase + e] — with their group's representative (TBK_DERR_COLLISION: the host reseeds).  The list and the arrays behind it are
+// window-space arrays of the tier kernels: nothing of it depends on the copies below.  The chain of dependent loads (entry -> slot ->
+// representative) of the first 64 entries flies with the first round of groups — the entry beside the round's loads, the slot behind
+// them in the queue, the representative behind the shuffles, all ahead of the round's first store (the whole chain ahead of the loop
+// cost a quarter more: 1.2 ms against 0.98 on 64 files x 5 M reads); the CIGAR compare and the rare further rounds of entries come
+// behind the copies.  pbase == nullptr: the files travel as masks, there is no incidence.
+template <bool VERIFY>
 __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const uint32_t* __restrict__ gbase, const uint32_t* __restrict__ pbase,
-                                                   WgFinal F) {
+                                                   WgFinal F, WgVerify V) {
   const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;  // one wave per window (no block-wide step below)
   if (w >= nw) return;
-  const uint32_t ng = T.wg_cnt[w], np = T.wp_cnt[w];
-  if (!ng) return;
-  const uint32_t wb = T.wbase[w], gb = gbase[w], pb = pbase[w];
+  // (the window's scalars in one go, ahead of the look at ng: a wave lives for a handful of memory round trips, each one counts)
+  const uint32_t ng = T.wg_cnt[w], np = pbase ? T.wp_cnt[w] : 0u;
+  const uint32_t wb = T.wbase[w], gb = gbase[w], pb = pbase ? pbase[w] : 0u;
+  uint32_t vn = 0, vj = 0, vcs = 0, vanchor = 0;
+  if constexpr (VERIFY) vn = T.vcnt[w];
+  if (!ng) {  // (no group: no passing record, so no listed one)
+    if (F.tcnt && lane == 0) F.tcnt[w] = 0;
+    return;
+  }
+  const bool vact = VERIFY && lane < vn;
+  if (vact) {  // in flight together with the first round's loads; slot and representative follow inside that round
+    vj = T.vsrc[wb + lane];
+    vcs = T.cslot[wb + lane];
+  }
   uint64_t c_hi = 0;    // lane 63's key of the round before (a further round follows full rounds only)
   uint32_t c_span = 0;
-  for (uint32_t g = lane; g < ng; g += 64) {
+  uint32_t nfollow = 0;  // groups that do not open a tie set (wave-uniform)
+  for (uint32_t g0 = 0; g0 < ng; g0 += 64) {  // (whole rounds: the lanes behind the last group ride along, the chain of a listed record
+                                              // may sit in any lane)
     // (every load before the first store: the arrays are not known to be distinct, a load behind a store would wait for its turn)
-    const uint32_t sg = gb + g;
-    const uint64_t hi = T.hi[wb + g], lo = T.lo[wb + g];
+    const uint32_t g = g0 + lane, sg = gb + g;
+    const bool act = g < ng;
+    uint64_t hi = 0, lo = 0, fm = 0;
+    unsigned long long r = 0;
+    uint32_t cnt = 0, nsv = 0, po = 0, yx = 0, yd = 0;
+    if (act) {
+      hi = T.hi[wb + g];
+      lo = T.lo[wb + g];
+      r = T.rep[wb + g];
+      cnt = T.cnt[wb + g];
+      nsv = T.ns[wb + g];
+      if (F.fmask) fm = T.fmask[wb + g];
+      else po = T.poff[wb + g];
+      if (F.yxin) {  // (group partials only: plain inputs carry no YX / YD — the arrays are null and the writers of the results know)
+        yx = T.yx[wb + g];
+        yd = T.yd[wb + g];
+      }
+    }
+    if (vact && g0 == 0) vcs = T.c2r[vcs];  // (behind the round's loads in the queue: it waits for the entry alone)
     const uint32_t span = (uint32_t)(lo >> 32);
-    uint64_t p_hi = __shfl_up((unsigned long long)hi, 1, 64);  // (lane g - 1 is active whenever lane g is)
+    uint64_t p_hi = __shfl_up((unsigned long long)hi, 1, 64);
     uint32_t p_span = __shfl_up(span, 1, 64);
     if (lane == 0) {
       p_hi = c_hi;
@@ -1852,15 +1899,9 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
     c_hi = __shfl((unsigned long long)hi, 63, 64);
     c_span = __shfl(span, 63, 64);
     const uint8_t tie = (g == 0 || hi != p_hi || span != p_span) ? 1 : 0;
-    const unsigned long long r = T.rep[wb + g];
-    const uint32_t cnt = T.cnt[wb + g], nsv = T.ns[wb + g];
-    const uint64_t fm = F.fmask ? T.fmask[wb + g] : 0ull;
-    const uint32_t po = F.fmask ? 0u : T.poff[wb + g];
-    uint32_t yx = 0, yd = 0;
-    if (F.yxin) {  // (group partials only: plain inputs carry no YX / YD — the arrays are null and the writers of the results know)
-      yx = T.yx[wb + g];
-      yd = T.yd[wb + g];
-    }
+    nfollow += (uint32_t)__popcll(__ballot(act && !tie));
+    if (vact && g0 == 0) vanchor = (uint32_t)(T.rep[vcs] & 0xFFFFFFFFull);
+    if (!act) continue;
     F.ghi[sg] = hi;
     F.glo[sg] = lo;
     F.tie[sg] = tie;
@@ -1873,7 +1914,9 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
       F.ydin[sg] = (long long)yd;
     }
     F.first[sg] = sg;
-    if (F.D.rep && sg < F.D.cap) {  // the caller's results in key order (col_write_k's lines; it rewrites the members of tie sets)
+    if (F.gperm) F.gperm[sg] = sg;
+    if (F.ginv) F.ginv[sg] = sg;
+    if (F.D.rep && sg < F.D.cap) {  // the caller's results in key order (col_write_k's lines; the members of tie sets are rewritten behind)
       const int32_t st = (int32_t)(uint32_t)((hi >> 2) & 0x7FFFFFFFull);
       F.D.rep[sg] = (uint32_t)(r & 0xFFFFFFFFull);
       if (F.D.rep_effend) F.D.rep_effend[sg] = (int32_t)(uint32_t)(r >> 32);
@@ -1900,6 +1943,84 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
     const uint32_t pi = T.pinc[wb + p];
     F.pfile[pb + p] = (uint16_t)pi;
     if (F.pgrp) F.pgrp[pb + p] = gb + (pi >> 16);
+  }
+  if (F.tcnt && lane == 0) F.tcnt[w] = nfollow;
+  if constexpr (VERIFY) {
+    if (lane < vn && vanchor != vj && !strategy_equal(V.I, V.strategy, vj, vanchor)) atomicOr(V.err, TBK_DERR_COLLISION);
+    for (uint32_t e = 64u + lane; e < vn; e += 64) {
+      const uint32_t j = T.vsrc[wb + e];
+      const uint32_t anchor = (uint32_t)(T.rep[T.c2r[T.cslot[wb + e]]] & 0xFFFFFFFFull);
+      if (anchor != j && !strategy_equal(V.I, V.strategy, j, anchor)) atomicOr(V.err, TBK_DERR_COLLISION);
+    }
+  }
+}
+// ---- tie sets of the raw form: one wave per window --------------------------------------------------------------------
+// The compaction has written every group at its key-order place (the caller's results, WgDirectOut, and the identity in gperm / ginv),
+// which is its output place unless it belongs to a tie set of several groups.  Tie sets never cross a window (above), so the wave of a
+// window finds the heads of such sets in its own tie bytes — a group that opens a set and whose successor, in the same window, does not —
+// and the head's lane does what col_tie_sort_k and col_write_k do for the set: the insertion sort by the reference comparator on the
+// groups' representatives, then the members' results and the inverse through the permutation.  Which windows hold such a set the
+// compaction has left in window space (WgFinal::tcnt, the way vcnt tells of listed records): a block reads the counts of 256 windows,
+// lists those with one in LDS, and its waves take the listed windows in turn — nothing is appended to a device-wide list, and a window
+// without such a set costs the four bytes of its count.
+__device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t lane, const WgFinal& F, const WgVerify& V);
+__global__ __launch_bounds__(256) void wg_tie_k(uint32_t nw, const uint32_t* __restrict__ wg_cnt, const uint32_t* __restrict__ gbase, WgFinal F,
+                                               WgVerify V) {
+  __shared__ uint32_t s_n, s_w[256];
+  if (threadIdx.x == 0) s_n = 0;
+  __syncthreads();
+  const uint32_t w0 = blockIdx.x * 256u + threadIdx.x;
+  if (w0 < nw && F.tcnt[w0]) s_w[atomicAdd(&s_n, 1u)] = w0;
+  __syncthreads();
+  const uint32_t n = s_n, lane = threadIdx.x & 63u;
+  for (uint32_t i = threadIdx.x >> 6; i < n; i += 4) wg_tie_window(wg_cnt[s_w[i]], gbase[s_w[i]], lane, F, V);
+}
+// one wave on a window of ng groups, the first of them group gb
+__device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t lane, const WgFinal& F, const WgVerify& V) {
+  for (uint32_t g = lane; g + 1 < ng; g += 64) {
+    const uint32_t sg = gb + g;
+    if (!F.tie[sg] || F.tie[sg + 1]) continue;  // not a head, or a set of one: in place
+    uint32_t e = 2;
+    while (g + e < ng && !F.tie[sg + e]) ++e;
+    for (uint32_t a = 1; a < e; ++a) {
+      const uint32_t x = F.gperm[sg + a];
+      const uint32_t rx = F.gmem[x];
+      uint32_t b = a;
+      while (b > 0) {
+        const uint32_t y = F.gperm[sg + b - 1];
+        if (strategy_cmp(V.I, V.strategy, rx, F.gmem[y]) < 0) {
+          F.gperm[sg + b] = y;
+          --b;
+        } else {
+          break;
+        }
+      }
+      F.gperm[sg + b] = x;
+    }
+    for (uint32_t a = 0; a < e; ++a) {
+      const uint32_t o = sg + a, s = F.gperm[o];
+      if (F.ginv) F.ginv[s] = o;
+      if (!F.D.rep || o >= F.D.cap) continue;
+      const unsigned long long r = F.rep[s];
+      const uint64_t hi = F.ghi[s], lo = F.glo[s];
+      const int32_t st = (int32_t)(uint32_t)((hi >> 2) & 0x7FFFFFFFull);
+      F.D.rep[o] = (uint32_t)(r & 0xFFFFFFFFull);
+      if (F.D.rep_effend) F.D.rep_effend[o] = (int32_t)(uint32_t)(r >> 32);
+      F.D.yc[o] = F.yc[s];
+      F.D.yx[o] = (F.yxin ? (int64_t)F.yxin[s] : 0ll) + (int64_t)F.ns[s];
+      if (F.D.g_start) F.D.g_start[o] = st;
+      if (F.D.g_end) F.D.g_end[o] = st + (int32_t)(uint32_t)(lo >> 32) - 1;
+      if (F.D.g_key) {
+        const uint32_t h32 = (uint32_t)lo;
+        uint32_t shape = 0;
+        if (F.D.strategy == TBK_STRAT_CIGAR || F.D.strategy == TBK_STRAT_CLIP) {  // (-E codes speak of exons, which may hold I and D)
+          if (h32 == (0x80000000u | C_M)) shape = 0x80000000u;
+          if ((h32 >> 30) == 3u) shape = h32;
+        }
+        F.D.g_key[2 * (size_t)o] = hi;
+        F.D.g_key[2 * (size_t)o + 1] = (lo & 0xFFFFFFFF00000000ull) | shape;
+      }
+    }
   }
 }
 // RAW, sparse list (WgRaw::sparse): one 64-thread block per window walks the window's entries
@@ -2390,7 +2511,10 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   }
   T.c2r = ws_alloc<uint32_t>(ctx, m);
   uint32_t* gbase = ws_alloc<uint32_t>(ctx, nw);
-  uint32_t* pbase = ws_alloc<uint32_t>(ctx, nw);
+  // (the files travel as masks: every window's incidence count is zero — no bases, no scan of them, and the compaction takes a null
+  // pbase; wg_back=split keeps the scan of zeros)
+  const bool no_inc = T.fmask && !ctx->dbg.wg_back_split;
+  uint32_t* pbase = no_inc ? nullptr : ws_alloc<uint32_t>(ctx, nw);
   T.dbg = nullptr;
   T.yx = T.yd = nullptr;
   if (part) {
@@ -2398,7 +2522,7 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
     T.yd = ws_alloc<uint32_t>(ctx, m);
     if (!T.yd) return TBK_ENOMEM;
   }
-  if (!T.pinc || !pbase || !T.c2r) return TBK_ENOMEM;
+  if (!T.pinc || (!no_inc && !pbase) || !T.c2r) return TBK_ENOMEM;
   if (raw && !R.sparse) TBK_HIP(hipMemsetAsync(T.cslot, 0xFF, (size_t)m * 4, ctx->stream));  // (only the records wg_finish_raw_k must visit get a slot)
   WgIn In{chi, clo, cval, ceff, off, W, k, nw, ctx->dbg.wg_rank_merge ? 1u : 0u};
   const uint32_t nwords = cdiv(k, 32);
@@ -2500,7 +2624,7 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   }
   if (spread) TBK_LAUNCH(ctx, "wg_spread_sum", wg_spread_sum_k, 1, 64, 0, spread, (unsigned long long*)(sc + 0), (unsigned long long*)(sc + 6));
   TBK_TRY(tbk_exscan_u32(ctx, T.wg_cnt, gbase, nw, sc + 1));
-  TBK_TRY(tbk_exscan_u32(ctx, T.wp_cnt, pbase, nw, sc + 2));
+  if (pbase) TBK_TRY(tbk_exscan_u32(ctx, T.wp_cnt, pbase, nw, sc + 2));
   uint32_t eb = 0;
   TBK_TRY(tbk_sync_err(ctx, &eb));
   *err_bits = eb;
@@ -2532,7 +2656,7 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
               h[i * 4 + 2], h[i * 4 + 1] ? (double)h[i * 4] / (double)h[i * 4 + 1] : 0.0, h[i * 4 + 3], (double)h[i * 4] / 1e6);
   }
   if (eb) return 0;  // the caller decides (reseed / sort path / error)
-  const uint32_t ng = (uint32_t)ctx->h_scalars[1], np = (uint32_t)ctx->h_scalars[2];
+  const uint32_t ng = (uint32_t)ctx->h_scalars[1], np = pbase ? (uint32_t)ctx->h_scalars[2] : 0u;
   out->ng = ng;
   out->np = np;
   ctx->ws_top_mode = false;  // the group arrays: from the bottom
@@ -2553,20 +2677,40 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   out->first = ws_alloc<uint32_t>(ctx, ng);
   out->tie = ws_alloc<uint8_t>(ctx, ng);
   out->rec_sg = want_rec_sg ? ws_alloc<uint32_t>(ctx, I.n) : nullptr;
+  // (raw) the output order and its inverse.  The inverse has two readers, col_recgroup_w_k and yd_fill_w_k (items NOT placed by list):
+  // not made when neither will run
+  const bool want_ginv = want_rec_sg || (out->pgrp && !tbk_yd_by_list(ctx, k));
+  const bool back_split = ctx->dbg.wg_back_split;
+  if (raw) {
+    out->gperm = ws_alloc<uint32_t>(ctx, ng);
+    out->ginv = want_ginv ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
+    if (ng && (!out->gperm || (want_ginv && !out->ginv))) return TBK_ENOMEM;
+    out->ties_done = !back_split;
+  }
   ctx->ws_top_mode = true;
   uint32_t* slot2sg = want_rec_sg ? ws_alloc<uint32_t>(ctx, m) : nullptr;  // (scratch)
+  uint32_t* tcnt = out->ties_done ? ws_alloc<uint32_t>(ctx, nw) : nullptr;   // (scratch: the windows wg_tie_k must visit)
+  if (out->ties_done && !tcnt) return TBK_ENOMEM;
   ctx->ws_top_mode = false;
   if (want_rec_sg && !slot2sg) return TBK_ENOMEM;
   if (!out->tie || (want_rec_sg && !out->rec_sg)) return TBK_ENOMEM;
   if (ng) {
     WgFinal F{out->gfmask, out->ghi, out->glo, out->gmem, out->gpoff, out->pgrp, out->first, out->ns, slot2sg, out->pfile, out->yc, out->yxin,
-              out->ydin, out->rep, out->tie, (raw && direct) ? *direct : WgDirectOut{}};
-    TBK_LAUNCH(ctx, "wg_compact", wg_compact_k, cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F);
+              out->ydin, out->rep, out->tie, (raw && direct) ? *direct : WgDirectOut{},
+              out->ties_done ? out->gperm : nullptr, out->ties_done ? out->ginv : nullptr, tcnt};
+    const WgVerify V{I, strategy, ctx->d_err};
+    // the listed records are verified by the compaction's own waves (wg_back=split: by a pass of their own behind it)
+    const bool list_live = raw && R.sparse && ctx->h_scalars[6] != 0;
+    if (list_live && !back_split)
+      TBK_LAUNCH(ctx, "wg_compact", wg_compact_k<true>, cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
+    else
+      TBK_LAUNCH(ctx, "wg_compact", wg_compact_k<false>, cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
+    if (out->ties_done) TBK_LAUNCH(ctx, "col_tie_sets", wg_tie_k, cdiv(nw, 256u), 256, 0, nw, T.wg_cnt, gbase, F, V);
     if (want_rec_sg) TBK_HIP(hipMemsetAsync(out->rec_sg, 0xFF, (size_t)I.n * 4, ctx->stream));  // (records that did not pass)
     if (raw) {  // (nothing to verify and no record -> group map wanted: every key word was exact)
-      if (ctx->h_scalars[6] != 0 && R.sparse)
+      if (list_live && back_split)
         TBK_LAUNCH(ctx, "wg_finish", wg_finish_sparse_k, cdiv(nw, 4u), 256, 0, nw, T.wbase, T.vcnt, T.vsrc, T.cslot, T.c2r, T.rep, I, strategy, ctx->d_err);
-      else if (ctx->h_scalars[6] != 0)
+      else if (ctx->h_scalars[6] != 0 && !R.sparse)
         TBK_LAUNCH(ctx, "wg_finish", wg_finish_raw_k, cdiv(m, B), B, 0, m, T.cslot, T.c2r, T.rep, slot2sg, out->rec_sg, I, strategy, ctx->d_err);
     } else
       TBK_LAUNCH(ctx, "wg_finish", wg_finish_k, cdiv(m, B), B, 0, m, clo, cval, T.cslot, T.c2r, T.rep, slot2sg, out->rec_sg, I, strategy,
