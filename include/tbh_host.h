@@ -67,6 +67,22 @@ uint32_t tbh_csi_reg2bin(int64_t beg, int64_t end, int depth);
 int64_t tbh_index_query(const char* bam_path, const char* index_path, int32_t tid, int64_t beg, int64_t end, uint64_t* chunk_beg, uint64_t* chunk_end,
                         uint64_t cap);
 
+/* ---- Several regions in one run (appended; tbh_abi_version stays 1, the symbols are found by name) ----
+ * The region table of `tiecov -R` / `tiebrush -R`: the BED file at bed_path (`chrom start end`, 0-based half-open, tabs or spaces,
+ * further columns ignored; blank lines and lines beginning with '#', "track" or "browser" skipped; a trailing CR tolerated) against the
+ * header of bam_path, normalised: ends cut to the reference's length, empty intervals dropped, sorted by (tid, beg), intervals that
+ * overlap or abut merged.  Returns the number R >= 1 of intervals; they are written to tid / beg / end when R <= cap (otherwise
+ * nothing is written: call again with room).  -1 on failure (tbh_last_error names the line): fewer than three fields, a start or end
+ * that is not a non-negative integer, start > end, a chrom the header does not list, a file without any region. */
+int64_t tbh_regions_from_bed(const char* bam_path, const char* bed_path, int32_t* tid, int64_t* beg, int64_t* end, uint64_t cap);
+
+/* tbh_index_query for a normalised table of n >= 1 intervals (HOST arrays; sorted by (tid, beg), disjoint, non-empty, non-adjacent:
+ * anything else is a failure): the union of the intervals' chunk lists, sorted by their begin and merged over the whole set by
+ * tbh_index_query's rule, so that no file byte is in two chunks although nearby intervals name the same ones.  For n == 1 the result
+ * is tbh_index_query's, element for element.  Return value, cap and failures as there. */
+int64_t tbh_index_query_regions(const char* bam_path, const char* index_path, uint32_t n, const int32_t* tid, const int64_t* beg, const int64_t* end,
+                                uint64_t* chunk_beg, uint64_t* chunk_end, uint64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -618,6 +618,37 @@ int tbk_bam_decode_file_spans(tbk_ctx* ctx, uint32_t n_files, const uint32_t* sp
 int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid, int64_t beg, int64_t end, tbk_soa_in* out, uint32_t* file_off_out,
                     uint32_t* n_kept);
 
+/* ---- Several regions in one run (ABI version 9, appended) ----------------------------------------------------------------
+ * What `tiecov -R BED` / `tiebrush -R BED` run: the four entries above for a region TABLE U instead of one region.  The reference has
+ * no region option, so these replace no interface of it either.
+ * U is n >= 1 intervals [beg[r], end[r]) on tid[r] (0-based, half-open) in HOST arrays: sorted by (tid, beg), disjoint, non-empty and
+ * non-adjacent (intervals that overlap or abut are ONE interval: a row across their joint must not be cut in two).  A table that is not,
+ * n == 0, a tid < 0 or a beg < 0 is TBK_EINVAL, found on the host before anything is launched or changed.  The table is uploaded once
+ * per call; it need not outlive the call.  With n == 1 each entry gives exactly what its one-region sibling gives. */
+typedef struct {
+  uint32_t n;
+  const int32_t* tid;
+  const int64_t* beg;
+  const int64_t* end;
+} tbk_regions;
+
+/* tbk_region_view for a table: record i is kept when it overlaps ANY interval of U (the same rec_end rule); a record that overlaps
+ * two intervals is kept once; file order kept.  Lifetimes as there. */
+int tbk_regions_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, const tbk_regions* regions, tbk_cov_in* view, uint32_t* n_kept);
+
+/* tbk_cov_clip / tbk_sample_clip for a table.  Interval rows: the rows intersected with U in (tid, start) order — a row is trimmed to
+ * EACH interval of U it meets and keeps its values, so a row that reaches across the gap between two intervals comes out once per
+ * interval and the rows can GROW: m <= n_intervals + n - 1.  When m exceeds cap_intervals the call is TBK_E2BIG, no row is touched
+ * (junction rows included) and the count needed is left in rows->n_intervals: size the arrays with n added, or call again with room.
+ * Junction rows: kept whole, once, in their order, when they overlap any interval (j_start < end && j_end > beg).
+ * TBK_EINVAL for interval rows that are not sorted by (tid, start) and disjoint; nothing faults and the context takes the next call. */
+int tbk_cov_clip_regions(tbk_ctx* ctx, tbk_cov_out* rows, const tbk_regions* regions);
+int tbk_sample_clip_regions(tbk_ctx* ctx, tbk_sample_out* rows, const tbk_regions* regions);
+
+/* tbk_tile_region for a table: the records of the context's decoded tile that overlap any interval of U as a collapse tile.  The input
+ * tile is consumed; lifetimes, file_off_out and the TBK_EINVAL-before-anything-changes rule are tbk_tile_region's. */
+int tbk_tile_regions(tbk_ctx* ctx, const tbk_soa_in* tile, const tbk_regions* regions, tbk_soa_in* out, uint32_t* file_off_out, uint32_t* n_kept);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,7 +28,8 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_groups_to_cov_in", "tbk_bgzf_inflate", "tbk_bam_decode", "tbk_bam_records", "tbk_bam_release", "tbk_shard_prepare", "tbk_shard_probe_max", "tbk_shard_probe_next",
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
-           "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route"]
+           "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route",
+           "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions"]
 
 
 class CollapseOpts(C.Structure):
@@ -102,6 +103,10 @@ class IxRef(C.Structure):
 
 class IxPart(C.Structure):
     _fields_ = [("n_chunks", C.c_uint32), ("n_refs", C.c_uint32), ("n_lin", C.c_uint64), ("lin_first", C.c_uint64), ("chunks", _P), ("lin", _P), ("refs", _P)]
+
+
+class Regions(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("tid", _P), ("beg", _P), ("end", _P)]
 
 
 TRACK = {"cov": 0, "junc": 1, "sample": 2}
@@ -216,6 +221,14 @@ def load():
     L.tbk_bam_decode_file_spans.restype = C.c_int
     L.tbk_tile_region.argtypes = [_P, C.POINTER(SoaIn), C.c_int32, C.c_int64, C.c_int64, C.POINTER(SoaIn), _P, C.POINTER(C.c_uint32)]
     L.tbk_tile_region.restype = C.c_int
+    L.tbk_regions_view.argtypes = [_P, C.POINTER(SoaIn), _P, C.POINTER(Regions), C.POINTER(CovIn), C.POINTER(C.c_uint32)]
+    L.tbk_regions_view.restype = C.c_int
+    L.tbk_cov_clip_regions.argtypes = [_P, C.POINTER(CovOut), C.POINTER(Regions)]
+    L.tbk_cov_clip_regions.restype = C.c_int
+    L.tbk_sample_clip_regions.argtypes = [_P, C.POINTER(SampleOut), C.POINTER(Regions)]
+    L.tbk_sample_clip_regions.restype = C.c_int
+    L.tbk_tile_regions.argtypes = [_P, C.POINTER(SoaIn), C.POINTER(Regions), C.POINTER(SoaIn), _P, C.POINTER(C.c_uint32)]
+    L.tbk_tile_regions.restype = C.c_int
     _lib = L
     return L
 
@@ -223,7 +236,8 @@ def load():
 # (TBK_HOST_LIB: the sanitizer builds of tools/san_check.sh)
 HOST_LIB_PATH = os.environ.get("TBK_HOST_LIB") or os.path.join(_HERE, "_build", "libtbh.so")
 HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin",
-                "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin", "tbh_index_query"]   # include/tbh_host.h
+                "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin", "tbh_index_query",
+                "tbh_regions_from_bed", "tbh_index_query_regions"]   # include/tbh_host.h
 _host = None
 
 
@@ -256,6 +270,10 @@ def load_host():
     H.tbh_csi_reg2bin.restype = C.c_uint32
     H.tbh_index_query.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.c_int64, C.c_int64, _P, _P, C.c_uint64]
     H.tbh_index_query.restype = C.c_int64
+    H.tbh_regions_from_bed.argtypes = [C.c_char_p, C.c_char_p, _P, _P, _P, C.c_uint64]
+    H.tbh_regions_from_bed.restype = C.c_int64
+    H.tbh_index_query_regions.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64]
+    H.tbh_index_query_regions.restype = C.c_int64
     _host = H
     return H
 

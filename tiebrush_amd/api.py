@@ -564,6 +564,78 @@ class Context:
         out["n_sample"] = m
         return out
 
+    # ---- the same for a region table [(tid, beg, end)] (tbk_regions) ----
+    def regions_view(self, tile_struct, tag_seen, table) -> DeviceCovView:
+        """tbk_regions_view: the records of a device tile overlapping any interval of the table, as tiecov's input"""
+        u, _keep = _regions(table)
+        v, nk = _lib.CovIn(), C.c_uint32(0)
+        self._check(self.L.tbk_regions_view(self.h, C.byref(tile_struct), tag_seen, C.byref(u), C.byref(v), C.byref(nk)), "tbk_regions_view")
+        assert int(nk.value) == int(v.n_records)
+        return DeviceCovView(v, int(v.n_records), int(v.n_cigar_ops))
+
+    def tile_regions(self, tile_struct, table):
+        """tbk_tile_regions: the records of the context's decoded tile overlapping any interval of the table as a collapse tile -> (SoaIn
+        struct, file_off [n_files + 1]); the input tile is consumed"""
+        u, _keep = _regions(table)
+        k = int(tile_struct.n_files)
+        fo = np.zeros(k + 1, dtype=np.uint32)
+        out, nk = _lib.SoaIn(), C.c_uint32(0)
+        self._check(self.L.tbk_tile_regions(self.h, C.byref(tile_struct), C.byref(u), C.byref(out), fo.ctypes.data, C.byref(nk)), "tbk_tile_regions")
+        assert int(nk.value) == int(out.n_records)
+        self._region_keep = (fo, getattr(self, "_bam_keep", None))
+        return out, fo
+
+    def cov_clip_regions(self, res, table, cap_intervals=None):
+        """tbk_cov_clip_regions: the result dict of coverage() cut to the table, as a new dict.  The interval rows can grow by
+        len(table) - 1: the arrays are sized cap_intervals (default: the rows + len(table)).  On TBK_E2BIG the TbkError carries
+        .needed (the count the call asks for) and .rows (the arrays as the call left them)."""
+        keep = []
+        u, _keep = _regions(table)
+        dev = any(_is_torch(res.get(k)) for k in ("iv_tid", "j_tid"))
+        a, b = (len(res["iv_tid"]) if "iv_tid" in res else 0), (len(res["j_tid"]) if "j_tid" in res else 0)
+        cap = a + len(table) if cap_intervals is None else int(cap_intervals)
+        own = {k: (_grown(v, cap) if k[:3] == "iv_" else (v.clone() if _is_torch(v) else np.array(v, copy=True)))
+               for k, v in res.items() if k[:3] == "iv_" or k[:2] == "j_"}
+
+        def ptr(name, dt):
+            return _addr(own[name], dt, keep) if name in own and _numel(own[name]) else None
+        o = _lib.CovOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, cap if "iv_tid" in own else 0, ptr("iv_tid", np.int32), ptr("iv_start", np.int32),
+                        ptr("iv_end", np.int32), ptr("iv_val", np.float64), b, ptr("j_tid", np.int32), ptr("j_start", np.int32), ptr("j_end", np.int32),
+                        ptr("j_strand", np.uint8), ptr("j_val", np.float64), a, b, 0, 0)
+        self._order_after_torch(dev)
+        self._check_grow(self.L.tbk_cov_clip_regions(self.h, C.byref(o), C.byref(u)), "tbk_cov_clip_regions", o, own)
+        out = dict(n_intervals=int(o.n_intervals), n_junctions=int(o.n_junctions))
+        for k, v in own.items():
+            out[k] = v[:out["n_intervals"] if k[:3] == "iv_" else out["n_junctions"]]
+        return out
+
+    def sample_clip_regions(self, res, table, cap_intervals=None):
+        """tbk_sample_clip_regions: the result dict of sample() cut to the table, as a new dict (capacity and TBK_E2BIG as cov_clip_regions)"""
+        keep = []
+        u, _keep = _regions(table)
+        dev = _is_torch(res["s_tid"])
+        a = len(res["s_tid"])
+        cap = a + len(table) if cap_intervals is None else int(cap_intervals)
+        own = {k: _grown(v, cap) for k, v in res.items() if k[:2] == "s_"}
+
+        def ptr(name, dt):
+            return _addr(own[name], dt, keep) if cap else None
+        o = _lib.SampleOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, cap, ptr("s_tid", np.int32), ptr("s_start", np.int32), ptr("s_end", np.int32),
+                           ptr("s_count", np.int64), ptr("s_heat", np.float32), a)
+        self._order_after_torch(dev)
+        self._check_grow(self.L.tbk_sample_clip_regions(self.h, C.byref(o), C.byref(u)), "tbk_sample_clip_regions", o, own)
+        m = int(o.n_intervals)
+        out = {k: v[:m] for k, v in own.items()}
+        out["n_sample"] = m
+        return out
+
+    def _check_grow(self, rc, what, o, own):
+        if rc == -4:
+            e = TbkError(rc, "%s: %d interval rows needed" % (what, int(o.n_intervals)))
+            e.needed, e.rows = int(o.n_intervals), own
+            raise e
+        self._check(rc, what)
+
     def bam_records(self, idx):
         """tbk_bam_records: (bytes of the packed records, offsets [n+1])"""
         idx = np.ascontiguousarray(idx, dtype=np.uint32)
@@ -1014,6 +1086,61 @@ def index_query(bam_path, tid, beg, end, index_path=None):
     while True:
         cb, ce = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
         n = H.tbh_index_query(os.fsencode(bam_path), ip, int(tid), int(beg), int(end), cb.ctypes.data, ce.ctypes.data, cap)
+        if n < 0:
+            raise RuntimeError((H.tbh_last_error() or b"").decode())
+        if n <= cap:
+            return [(int(cb[i]), int(ce[i])) for i in range(n)]
+        cap = int(n)
+
+
+def _table_arrays(table):
+    t = [(int(a), int(b), int(c)) for a, b, c in table]
+    return (np.array([x[0] for x in t], dtype=np.int32), np.array([x[1] for x in t], dtype=np.int64), np.array([x[2] for x in t], dtype=np.int64))
+
+
+def _regions(table):
+    """[(tid, beg, end)] -> (tbk_regions struct over host arrays, the arrays to keep alive)"""
+    tid, beg, end = _table_arrays(table)
+    return _lib.Regions(len(tid), tid.ctypes.data, beg.ctypes.data, end.ctypes.data), (tid, beg, end)
+
+
+def _grown(v, cap):
+    """a copy of the rows v in an array of cap elements (the rest zero)"""
+    if _is_torch(v):
+        g = _torch().zeros(cap, dtype=v.dtype, device=v.device)
+    else:
+        v = np.asarray(v)
+        g = np.zeros(cap, dtype=v.dtype)
+    g[:min(cap, len(v))] = v[:cap]
+    return g
+
+
+def regions_from_bed(bam_path, bed_path):
+    """tbh_regions_from_bed: the BED file's intervals against the header of bam_path as the normalised table [(tid, beg, end)]: sorted,
+    merged where they overlap or abut, ends cut to the reference, empty ones dropped.  RuntimeError (with the line number) for a
+    malformed line, an unknown chrom, a file without a region.  Host only."""
+    H = _lib.load_host()
+    cap = 64
+    while True:
+        t, b, e = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
+        n = H.tbh_regions_from_bed(os.fsencode(bam_path), os.fsencode(bed_path), t.ctypes.data, b.ctypes.data, e.ctypes.data, cap)
+        if n < 0:
+            raise RuntimeError((H.tbh_last_error() or b"").decode())
+        if n <= cap:
+            return [(int(t[i]), int(b[i]), int(e[i])) for i in range(n)]
+        cap = int(n)
+
+
+def index_query_regions(bam_path, table, index_path=None):
+    """tbh_index_query_regions: index_query for a normalised table [(tid, beg, end)]: the chunks of all intervals, merged over the whole
+    set so that no file byte is in two of them.  Host only."""
+    H = _lib.load_host()
+    ip = None if index_path is None else os.fsencode(index_path)
+    tid, beg, end = _table_arrays(table)
+    cap = 64
+    while True:
+        cb, ce = np.zeros(cap, dtype=np.uint64), np.zeros(cap, dtype=np.uint64)
+        n = H.tbh_index_query_regions(os.fsencode(bam_path), ip, len(tid), tid.ctypes.data, beg.ctypes.data, end.ctypes.data, cb.ctypes.data, ce.ctypes.data, cap)
         if n < 0:
             raise RuntimeError((H.tbh_last_error() or b"").decode())
         if n <= cap:

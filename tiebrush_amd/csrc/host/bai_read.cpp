@@ -181,7 +181,30 @@ const RegionIndex::Bin* RegionIndex::find(const Ref& r, uint32_t bin) const {
 }
 
 void RegionIndex::query(int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out) const {
+  std::vector<IdxChunk> all;
+  collect(tid, beg, end, all);
+  merge(all, out);
+}
+
+void RegionIndex::query_regions(const RegionTable& U, std::vector<IdxChunk>& out) const {
+  std::vector<IdxChunk> all;
+  for (size_t r = 0; r < U.n(); ++r) collect(U.tid[r], U.beg[r], U.end[r], all);
+  merge(all, out);
+}
+
+void RegionIndex::merge(std::vector<IdxChunk>& all, std::vector<IdxChunk>& out) {
   out.clear();
+  std::sort(all.begin(), all.end(), [](const IdxChunk& a, const IdxChunk& c) { return a.beg < c.beg || (a.beg == c.beg && a.end < c.end); });
+  for (const IdxChunk& c : all) {
+    if (!out.empty() && (out.back().end >> 16) >= (c.beg >> 16)) {
+      if (c.end > out.back().end) out.back().end = c.end;
+    } else {
+      out.push_back(c);
+    }
+  }
+}
+
+void RegionIndex::collect(int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& all) const {
   if (tid < 0 || (size_t)tid >= refs_.size() || beg < 0) return;
   const int64_t reach = 1ll << (min_shift_ + 3 * depth_);  // no record the index holds ends behind it
   if (end > reach) end = reach;
@@ -202,7 +225,6 @@ void RegionIndex::query(int32_t tid, int64_t beg, int64_t end, std::vector<IdxCh
       b = (b - 1) >> 3;
     }
   }
-  std::vector<IdxChunk> all;
   auto take = [&](uint64_t bin) {
     if (const Bin* B = find(R, (uint32_t)bin))
       for (const IdxChunk& c : B->chunks)
@@ -219,14 +241,6 @@ void RegionIndex::query(int32_t tid, int64_t beg, int64_t end, std::vector<IdxCh
     } else {
       for (const Bin& B : R.bins)
         if (B.bin >= lo && B.bin <= hi) take(B.bin);
-    }
-  }
-  std::sort(all.begin(), all.end(), [](const IdxChunk& a, const IdxChunk& c) { return a.beg < c.beg || (a.beg == c.beg && a.end < c.end); });
-  for (const IdxChunk& c : all) {
-    if (!out.empty() && (out.back().end >> 16) >= (c.beg >> 16)) {
-      if (c.end > out.back().end) out.back().end = c.end;
-    } else {
-      out.push_back(c);
     }
   }
 }
@@ -287,6 +301,81 @@ bool parse_region(const BamHeader& hdr, const std::string& region, int32_t* tid,
   *end = std::min(e1, len);
   *beg = std::min(b1 - 1, *end);  // (a BEG behind the reference: the empty region at its end)
   return true;
+}
+
+bool RegionTable::normalised() const {
+  if (tid.empty() || beg.size() != tid.size() || end.size() != tid.size()) return false;
+  for (size_t r = 0; r < tid.size(); ++r) {
+    if (tid[r] < 0 || beg[r] < 0 || end[r] <= beg[r]) return false;
+    if (r && (tid[r] < tid[r - 1] || (tid[r] == tid[r - 1] && beg[r] <= end[r - 1]))) return false;
+  }
+  return true;
+}
+
+static bool bed_coord(const std::string& s, int64_t* v) {  // digits only, no more than 2^40
+  if (s.empty()) return false;
+  int64_t x = 0;
+  for (char c : s) {
+    if (c < '0' || c > '9') return false;
+    x = x * 10 + (c - '0');
+    if (x > (1ll << 40)) return false;
+  }
+  *v = x;
+  return true;
+}
+
+bool regions_from_bed(const BamHeader& hdr, const std::string& text, const std::string& what, RegionTable& U, std::string& err) {
+  struct Iv {
+    int32_t tid;
+    int64_t beg, end;
+  };
+  std::vector<Iv> iv;
+  size_t lineno = 0;
+  bool any = false;
+  for (size_t p = 0; p < text.size();) {
+    size_t nl = text.find('\n', p);
+    if (nl == std::string::npos) nl = text.size();
+    std::string line = text.substr(p, nl - p);
+    p = nl + 1;
+    ++lineno;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    const std::string at = what + " line " + std::to_string(lineno) + ": ";
+    std::vector<std::string> f;
+    for (size_t q = 0; q < line.size() && f.size() < 3;) {
+      while (q < line.size() && (line[q] == '\t' || line[q] == ' ')) ++q;
+      size_t e = q;
+      while (e < line.size() && line[e] != '\t' && line[e] != ' ') ++e;
+      if (e > q) f.push_back(line.substr(q, e - q));
+      q = e;
+    }
+    if (f.empty() || f[0][0] == '#' || f[0] == "track" || f[0] == "browser") continue;
+    if (f.size() < 3) return err = at + "fewer than three fields (expected chrom start end)", false;
+    int64_t b = 0, e = 0;
+    if (!bed_coord(f[1], &b)) return err = at + "the start '" + f[1] + "' is not a non-negative integer", false;
+    if (!bed_coord(f[2], &e)) return err = at + "the end '" + f[2] + "' is not a non-negative integer", false;
+    if (b > e) return err = at + "start > end", false;
+    const int t = hdr.name2tid(f[0]);
+    if (t < 0) return err = at + "unknown reference name '" + f[0] + "'", false;
+    any = true;
+    e = std::min<int64_t>(e, hdr.target_len[(size_t)t]);
+    if (b < e) iv.push_back(Iv{(int32_t)t, b, e});
+  }
+  U = RegionTable();
+  std::sort(iv.begin(), iv.end(), [](const Iv& a, const Iv& c) { return a.tid < c.tid || (a.tid == c.tid && (a.beg < c.beg || (a.beg == c.beg && a.end < c.end))); });
+  for (const Iv& x : iv) {
+    if (U.n() && U.tid.back() == x.tid && x.beg <= U.end.back())  // overlap or abut: one interval
+      U.end.back() = std::max(U.end.back(), x.end);
+    else
+      U.add(x.tid, x.beg, x.end);
+  }
+  if (U.n() == 0) return err = what + ": no region" + (any ? " left (every interval is empty on its reference)" : " in it"), false;
+  return true;
+}
+
+bool regions_from_bed_file(const BamHeader& hdr, const std::string& bed_path, RegionTable& U, std::string& err) {
+  std::vector<uint8_t> b;
+  if (!slurp(bed_path, b)) return err = "cannot read the regions file " + bed_path, false;
+  return regions_from_bed(hdr, std::string(b.begin(), b.end()), bed_path, U, err);
 }
 
 bool read_spans(const std::string& bam_path, const std::vector<IdxChunk>& chunks, std::vector<RegionSpan>& spans, uint64_t* bytes_read, std::string& err) {
@@ -363,8 +452,24 @@ bool span_records(const RegionSpan& s, uint64_t file_off, std::vector<BaiRec>& r
   return true;
 }
 
+// the intervals of U against a header of n_ref references: what index_query_file's one region has always been held to
+static bool table_in_range(const RegionTable& U, int32_t n_ref) {
+  for (size_t r = 0; r < U.n(); ++r)
+    if (U.tid[r] < 0 || U.tid[r] >= n_ref || U.beg[r] < 0 || U.end[r] < U.beg[r]) return false;
+  return true;
+}
+static RegionTable table_of_one(int32_t tid, int64_t beg, int64_t end) {
+  RegionTable U;
+  U.add(tid, beg, end);
+  return U;
+}
+
 bool index_query_file(const std::string& bam_path, const std::string& index_path, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out,
                       std::string& err) {
+  return index_query_regions_file(bam_path, index_path, table_of_one(tid, beg, end), out, err);
+}
+
+bool index_query_regions_file(const std::string& bam_path, const std::string& index_path, const RegionTable& U, std::vector<IdxChunk>& out, std::string& err) {
   BamFile bf;
   if (!bf.open(bam_path, err, 1)) return false;
   std::string found;
@@ -375,13 +480,19 @@ bool index_query_file(const std::string& bam_path, const std::string& index_path
     err = found + ": the index has " + std::to_string(ix.n_ref()) + " references, the header of " + bam_path + " has " + std::to_string(bf.hdr.n_targets);
     return false;
   }
-  if (tid < 0 || tid >= bf.hdr.n_targets || beg < 0 || end < beg) return err = "index query: tid / beg / end out of range", false;
-  ix.query(tid, beg, end, out);
+  if (!table_in_range(U, bf.hdr.n_targets)) return err = "index query: tid / beg / end out of range", false;
+  if (U.n() > 1 && !U.normalised()) return err = "index query: the region table is not sorted, disjoint, non-empty and non-adjacent", false;
+  ix.query_regions(U, out);
   return true;
 }
 
 bool region_input_chunks(const std::string& bam_path, int32_t file_n_ref, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& chunks,
                          std::string& index_path, std::string& err) {
+  return regions_input_chunks(bam_path, file_n_ref, table_of_one(tid, beg, end), chunks, index_path, err);
+}
+
+bool regions_input_chunks(const std::string& bam_path, int32_t file_n_ref, const RegionTable& U, std::vector<IdxChunk>& chunks, std::string& index_path,
+                          std::string& err) {
   chunks.clear();
   if (!find_index(bam_path, "", index_path, err)) {  // (the paths tried; the advice is find_index's caller's)
     const size_t cut = err.find("): ");
@@ -397,8 +508,8 @@ bool region_input_chunks(const std::string& bam_path, int32_t file_n_ref, int32_
     err = index_path + ": the index has " + std::to_string(ix.n_ref()) + " references, the header of " + bam_path + " has " + std::to_string(file_n_ref);
     return false;
   }
-  if (tid < 0 || tid >= file_n_ref || beg < 0 || end < beg) return err = bam_path + ": index query: tid / beg / end out of range", false;
-  if (beg < end) ix.query(tid, beg, end, chunks);
+  if (!table_in_range(U, file_n_ref)) return err = bam_path + ": index query: tid / beg / end out of range", false;
+  ix.query_regions(U, chunks);  // (an empty interval names no chunk)
   if (chunks.empty()) return true;
   const int fd = open(bam_path.c_str(), O_RDONLY);  // (read_spans' own conditions, the header of each chunk's last member included)
   if (fd < 0) return err = "cannot open " + bam_path, false;

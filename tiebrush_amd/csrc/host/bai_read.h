@@ -23,6 +23,16 @@ struct IdxChunk {
   uint64_t beg, end;  // virtual offsets: member offset << 16 | offset in the member's payload
 };
 
+// A region table U: R intervals [beg, end) on tid, 0-based half-open.  Normalised: sorted by (tid, beg), disjoint,
+// non-empty and non-adjacent (intervals that overlap or abut are one).
+struct RegionTable {
+  std::vector<int32_t> tid;
+  std::vector<int64_t> beg, end;
+  size_t n() const { return tid.size(); }
+  void add(int32_t t, int64_t b, int64_t e) { tid.push_back(t), beg.push_back(b), end.push_back(e); }
+  bool normalised() const;
+};
+
 class RegionIndex {
  public:
   // the format comes from the magic: "BAI\1", or a BGZF file whose payload starts with "CSI\1"
@@ -34,6 +44,9 @@ class RegionIndex {
   size_t n_ref() const { return refs_.size(); }
   // the chunks a reader of [beg, end) on tid has to read: sorted, disjoint, merged (see above); beg < end, both >= 0
   void query(int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out) const;
+  // the same for every interval of a region table: the union of the intervals' chunk lists, sorted and merged by the
+  // same rule over the whole set, so that no file byte is in two chunks; for a table of one it is query's result
+  void query_regions(const RegionTable& U, std::vector<IdxChunk>& out) const;
 
  private:
   struct Bin {
@@ -46,6 +59,8 @@ class RegionIndex {
     std::vector<uint64_t> lin;
   };
   const Bin* find(const Ref& r, uint32_t bin) const;
+  void collect(int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& all) const;  // the chunks of one interval, neither sorted nor merged
+  static void merge(std::vector<IdxChunk>& all, std::vector<IdxChunk>& out);
   bool csi_ = false;
   int min_shift_ = 14, depth_ = 5;
   std::vector<Ref> refs_;
@@ -58,6 +73,14 @@ bool find_index(const std::string& bam_path, const std::string& explicit_path, s
 // NAME | NAME:BEG | NAME:BEG-END, 1-based inclusive, commas allowed in the numbers; the whole string is tried as a name first (a name
 // may hold ':').  Out: tid and the 0-based half-open [beg, end), END cut to the reference's length.
 bool parse_region(const BamHeader& hdr, const std::string& region, int32_t* tid, int64_t* beg, int64_t* end, std::string& err);
+
+// BED text (`chrom start end` separated by tabs or spaces, 0-based half-open; further columns ignored; blank lines and lines beginning
+// with '#', "track" or "browser" skipped; a trailing '\r' tolerated) -> the normalised table: an end beyond the reference cut to its
+// length, empty intervals dropped, the rest sorted by (tid, beg) and merged where they overlap or abut.  false, with the line number in
+// err: fewer than three fields, a start or end that is not a non-negative integer, start > end, a chrom the header does not list;
+// (without a line number) a text that yields no region at all.  `what` names the text in the messages (the file's path).
+bool regions_from_bed(const BamHeader& hdr, const std::string& text, const std::string& what, RegionTable& U, std::string& err);
+bool regions_from_bed_file(const BamHeader& hdr, const std::string& bed_path, RegionTable& U, std::string& err);
 
 // One merged chunk's bytes: the whole BGZF members from the chunk's first member on; the records are the inflated bytes from first_uoff
 // in the first member up to last_uoff in the last one (0: the last member read is whole, the chunk ends where it ends).
@@ -79,12 +102,18 @@ bool span_records(const RegionSpan& s, uint64_t file_off, std::vector<BaiRec>& r
 bool index_query_file(const std::string& bam_path, const std::string& index_path, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& out,
                       std::string& err);
 
+// the same for a normalised region table (tbh_index_query_regions, `tbh_tool rquery`, tiecov -R)
+bool index_query_regions_file(const std::string& bam_path, const std::string& index_path, const RegionTable& U, std::vector<IdxChunk>& out, std::string& err);
+
 // One input of `tiebrush -r`: its index found (find_index's order), loaded and checked against the file — the index's
 // n_ref is file_n_ref, the file's header's — and queried; every chunk checked against the file by read_spans' own conditions, the header
 // of the member it ends in read (so that a caller can refuse before it has created anything: what read_spans refuses, this refuses).
 // err names the file concerned.
 bool region_input_chunks(const std::string& bam_path, int32_t file_n_ref, int32_t tid, int64_t beg, int64_t end, std::vector<IdxChunk>& chunks,
                          std::string& index_path, std::string& err);
+// the same for a normalised region table (`tiebrush -R`)
+bool regions_input_chunks(const std::string& bam_path, int32_t file_n_ref, const RegionTable& U, std::vector<IdxChunk>& chunks, std::string& index_path,
+                          std::string& err);
 // The spans of several inputs, read on `threads` threads (file after file on each): spans[f] = read_spans(paths[f], chunks[f]).  false:
 // err is the first failing file's.  *bytes_read = the sum over all inputs.
 bool read_spans_many(const std::vector<std::string>& paths, const std::vector<std::vector<IdxChunk>>& chunks, int threads,

@@ -131,4 +131,29 @@ int64_t tbh_index_query(const char* bam_path, const char* index_path, int32_t ti
   return (int64_t)ch.size();
 }
 
+int64_t tbh_regions_from_bed(const char* bam_path, const char* bed_path, int32_t* tid, int64_t* beg, int64_t* end, uint64_t cap) {
+  if (!bam_path || !bed_path || (cap && (!tid || !beg || !end))) return fail("tbh_regions_from_bed: null argument");
+  std::string err;
+  tbh::BamFile bf;
+  if (!bf.open(bam_path, err, 1)) return fail("tbh_regions_from_bed: " + err);
+  tbh::RegionTable U;
+  if (!tbh::regions_from_bed_file(bf.hdr, bed_path, U, err)) return fail("tbh_regions_from_bed: " + err);
+  if (U.n() <= cap)
+    for (size_t r = 0; r < U.n(); ++r) tid[r] = U.tid[r], beg[r] = U.beg[r], end[r] = U.end[r];
+  return (int64_t)U.n();
+}
+
+int64_t tbh_index_query_regions(const char* bam_path, const char* index_path, uint32_t n, const int32_t* tid, const int64_t* beg, const int64_t* end,
+                                uint64_t* chunk_beg, uint64_t* chunk_end, uint64_t cap) {
+  if (!bam_path || !n || !tid || !beg || !end || (cap && (!chunk_beg || !chunk_end))) return fail("tbh_index_query_regions: null argument or an empty table");
+  tbh::RegionTable U;
+  for (uint32_t r = 0; r < n; ++r) U.add(tid[r], beg[r], end[r]);
+  std::string err;
+  std::vector<tbh::IdxChunk> ch;
+  if (!tbh::index_query_regions_file(bam_path, index_path ? index_path : "", U, ch, err)) return fail("tbh_index_query_regions: " + err);
+  if (ch.size() <= cap)
+    for (size_t i = 0; i < ch.size(); ++i) chunk_beg[i] = ch[i].beg, chunk_end[i] = ch[i].end;
+  return (int64_t)ch.size();
+}
+
 }  // extern "C"

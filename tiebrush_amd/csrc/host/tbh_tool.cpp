@@ -7,6 +7,9 @@
 //   csi IN.bam                    write IN.bam.csi the same way (what `tiebrush --csi` builds: references beyond 2^29 included)
 //   query IN.bam REGION [INDEX]   the chunks the index names for REGION (bai_read.h), one line "vbeg vend" in hex each, then the number of
 //                                 records in the chunks and of those overlapping the region, by the host codec ("hit vbeg" per overlap)
+//   rquery IN.bam REGIONS.bed [INDEX]   the same for the region table of a BED file: "regions R", a "region tid beg end"
+//                                 line per interval of the normalised table, the chunks merged over the whole table, records, hits
+//   mquery REGION THREADS IN1.bam ... / mrquery REGIONS.bed THREADS IN1.bam ...   the host plumbing of `tiebrush -r` / `-R`, per input
 //   mkbam SOADIR PREFIX [LEVEL [THREADS]]   encode the raw SoA arrays of a synthetic tile (file_off, tid, pos, flag, mapq, strand,
 //                                 nh, cig_off, cig as little-endian files + header.txt) as PREFIX<f>.bam, one per input file: the
 //                                 records tiebrush_amd.synth.write_bams writes (SEQ '*', QNAME r<f>_<i>, NH:C / XS:A), files in parallel
@@ -54,6 +57,13 @@ static void dump(const std::string& dir, const char* name, const std::vector<T>&
   if (!f) GError("cannot write %s/%s\n", dir.c_str(), name);
   if (!v.empty()) fwrite(v.data(), sizeof(T), v.size(), f);
   fclose(f);
+}
+
+// does the record overlap any interval of the table (brute force: the check is not the code under test)
+static bool overlaps_any(const tbh::RegionTable& U, const tbh::BaiRec& r) {
+  for (size_t q = 0; q < U.n(); ++q)
+    if (r.tid == U.tid[q] && r.beg < U.end[q] && r.end > U.beg[q]) return true;
+  return false;
 }
 
 int main(int argc, char** argv) {
@@ -384,31 +394,43 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  if (cmd == "query" && (argc == 4 || argc == 5)) {
+  // query: one REGION; rquery FILE.bam REGIONS.bed [INDEX]: the normalised table of a BED file, "regions R" first
+  if ((cmd == "query" || cmd == "rquery") && (argc == 4 || argc == 5)) {
+    const bool bed = cmd == "rquery";
+    const std::string me = "tbh_tool " + cmd;
     std::string err;
     tbh::BamFile bf;
-    int32_t tid = 0;
-    int64_t beg = 0, end = 0;
+    tbh::RegionTable U;
     std::vector<tbh::IdxChunk> chunks;
     std::vector<tbh::RegionSpan> spans;
-    if (!bf.open(argv[2], err, 1) || !tbh::parse_region(bf.hdr, argv[3], &tid, &beg, &end, err) ||
-        (beg < end && !tbh::index_query_file(argv[2], argc == 5 ? argv[4] : "", tid, beg, end, chunks, err)) || !tbh::read_spans(argv[2], chunks, spans, nullptr, err)) {
-      fprintf(stderr, "tbh_tool query: %s\n", err.c_str());
+    bool ok = bf.open(argv[2], err, 1);
+    if (ok && bed) {
+      ok = tbh::regions_from_bed_file(bf.hdr, argv[3], U, err);
+    } else if (ok) {
+      int32_t tid = 0;
+      int64_t beg = 0, end = 0;
+      ok = tbh::parse_region(bf.hdr, argv[3], &tid, &beg, &end, err);
+      U.add(tid, beg, end);
+    }
+    if (!ok || (U.beg[0] < U.end[0] && !tbh::index_query_regions_file(argv[2], argc == 5 ? argv[4] : "", U, chunks, err)) ||
+        !tbh::read_spans(argv[2], chunks, spans, nullptr, err)) {
+      fprintf(stderr, "%s: %s\n", me.c_str(), err.c_str());
       return 1;
     }
-    printf("region %d %lld %lld\n", tid, (long long)beg, (long long)end);
+    if (bed) printf("regions %zu\n", U.n());
+    for (size_t r = 0; r < U.n(); ++r) printf("region %d %lld %lld\n", U.tid[r], (long long)U.beg[r], (long long)U.end[r]);
     uint64_t n_rec = 0, n_hit = 0;
     std::vector<uint64_t> hits;
     for (size_t c = 0; c < chunks.size(); ++c) {
       printf("%llx %llx\n", (unsigned long long)chunks[c].beg, (unsigned long long)chunks[c].end);
       std::vector<tbh::BaiRec> recs;
       if (!tbh::span_records(spans[c], chunks[c].beg >> 16, recs, err)) {
-        fprintf(stderr, "tbh_tool query: %s\n", err.c_str());
+        fprintf(stderr, "%s: %s\n", me.c_str(), err.c_str());
         return 1;
       }
       n_rec += recs.size();
       for (const tbh::BaiRec& r : recs)
-        if (r.tid == tid && r.beg < end && r.end > beg) hits.push_back(r.vbeg);
+        if (overlaps_any(U, r)) hits.push_back(r.vbeg);
     }
     n_hit = hits.size();
     printf("records %llu\noverlapping %llu\n", (unsigned long long)n_rec, (unsigned long long)n_hit);
@@ -417,44 +439,56 @@ int main(int argc, char** argv) {
   }
   // the host plumbing of `tiebrush -r`: REGION against the first input's header, every input's index found, checked and
   // queried (region_input_chunks), the chunks of all inputs read on THREADS threads (read_spans_many), the records counted by the host codec
-  if (cmd == "mquery" && argc >= 5) {
+  // mrquery REGIONS.bed THREADS IN1.bam ...: the same for the table of a BED file (`tiebrush -R`), "regions R" first
+  if ((cmd == "mquery" || cmd == "mrquery") && argc >= 5) {
+    const bool bed = cmd == "mrquery";
+    const std::string me = "tbh_tool " + cmd;
     std::string err;
     const int threads = atoi(argv[3]);
     std::vector<std::string> paths(argv + 4, argv + argc);
-    int32_t tid = 0;
-    int64_t beg = 0, end = 0;
+    tbh::RegionTable U;
     std::vector<std::vector<tbh::IdxChunk>> chunks(paths.size());
     std::vector<std::vector<tbh::RegionSpan>> spans;
     uint64_t bytes = 0;
     for (size_t f = 0; f < paths.size(); ++f) {
       tbh::BamFile bf;
       std::string ix;
-      if (!bf.open(paths[f], err, 1) || (f == 0 && !tbh::parse_region(bf.hdr, argv[2], &tid, &beg, &end, err)) ||
-          !tbh::region_input_chunks(paths[f], bf.hdr.n_targets, tid, beg, end, chunks[f], ix, err)) {
-        fprintf(stderr, "tbh_tool mquery: %s\n", err.c_str());
+      bool ok = bf.open(paths[f], err, 1);
+      if (ok && f == 0 && bed) {
+        ok = tbh::regions_from_bed_file(bf.hdr, argv[2], U, err);
+      } else if (ok && f == 0) {
+        int32_t tid = 0;
+        int64_t beg = 0, end = 0;
+        ok = tbh::parse_region(bf.hdr, argv[2], &tid, &beg, &end, err);
+        U.add(tid, beg, end);
+      }
+      if (!ok || !tbh::regions_input_chunks(paths[f], bf.hdr.n_targets, U, chunks[f], ix, err)) {
+        fprintf(stderr, "%s: %s\n", me.c_str(), err.c_str());
         return 1;
       }
     }
     if (!tbh::read_spans_many(paths, chunks, threads, spans, &bytes, err)) {
-      fprintf(stderr, "tbh_tool mquery: %s\n", err.c_str());
+      fprintf(stderr, "%s: %s\n", me.c_str(), err.c_str());
       return 1;
     }
-    printf("region %d %lld %lld\nbytes %llu\n", tid, (long long)beg, (long long)end, (unsigned long long)bytes);
+    if (bed) printf("regions %zu\n", U.n());
+    for (size_t r = 0; r < U.n(); ++r) printf("region %d %lld %lld\n", U.tid[r], (long long)U.beg[r], (long long)U.end[r]);
+    printf("bytes %llu\n", (unsigned long long)bytes);
     for (size_t f = 0; f < paths.size(); ++f) {
       uint64_t n_rec = 0, n_hit = 0;
       for (size_t c = 0; c < chunks[f].size(); ++c) {
         std::vector<tbh::BaiRec> recs;
         if (!tbh::span_records(spans[f][c], chunks[f][c].beg >> 16, recs, err)) {
-          fprintf(stderr, "tbh_tool mquery: %s: %s\n", paths[f].c_str(), err.c_str());
+          fprintf(stderr, "%s: %s: %s\n", me.c_str(), paths[f].c_str(), err.c_str());
           return 1;
         }
         n_rec += recs.size();
-        for (const tbh::BaiRec& r : recs) n_hit += r.tid == tid && r.beg < end && r.end > beg;
+        for (const tbh::BaiRec& r : recs) n_hit += overlaps_any(U, r);
       }
       printf("file %zu chunks %zu records %llu overlapping %llu\n", f, chunks[f].size(), (unsigned long long)n_rec, (unsigned long long)n_hit);
     }
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|query|mquery ...\n");
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|query|rquery|mquery|mrquery ...\n");
   return 2;
 }

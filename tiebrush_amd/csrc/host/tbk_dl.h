@@ -34,6 +34,7 @@ struct TbkApi {
   decltype(&tbk_kernel_times) kernel_times = nullptr;
   decltype(&tbk_bam_decode_file_spans) bam_decode_file_spans = nullptr;  // -r REGION
   decltype(&tbk_tile_region) tile_region = nullptr;
+  decltype(&tbk_tile_regions) tile_regions = nullptr;  // -R FILE
   // optional: only the track options (--cov / --junc / --samp) need them; has_tracks() says whether the library has them all
   decltype(&tbk_coverage_tile) coverage_tile = nullptr;
   decltype(&tbk_sample_tile) sample_tile = nullptr;
@@ -84,6 +85,7 @@ struct TbkApi {
     TBK_BIND(kernel_times, tbk_kernel_times)
     TBK_BIND(bam_decode_file_spans, tbk_bam_decode_file_spans)
     TBK_BIND(tile_region, tbk_tile_region)
+    TBK_BIND(tile_regions, tbk_tile_regions)
 #undef TBK_BIND
     coverage_tile = (decltype(coverage_tile))dlsym(h, "tbk_coverage_tile");
     sample_tile = (decltype(sample_tile))dlsym(h, "tbk_sample_tile");

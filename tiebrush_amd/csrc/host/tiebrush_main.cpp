@@ -78,6 +78,8 @@ static const char* USAGE =
     "                       commas allowed; one region per run), read through every input's index (IN.bam.csi, IN.bam.bai or IN.bai;\n"
     "                       `tiebrush --index` / `--csi` and `samtools index` write one).  The output is what the same command line\n"
     "                       without -r makes of inputs cut to their records that overlap the region; not with --ranks\n"
+    "  -R,--regions-file FILE   the same for several regions in one run: FILE is BED (chrom start end, 0-based half-open; further\n"
+    "                       columns ignored); a record that overlaps two of them is kept once; not with -r or --ranks\n"
     "  --ranks N            shard the input files over N GPUs of this node (one process each), one output BAM\n"
     "  --writer WHICH       device (default): the output records are tagged and BGZF-compressed on the GPU; host: by the CPU cores\n"
     "  --cov PREFIX         also write tiecov's coverage track of the output (as tiecov -c; - or stdout: standard output)\n"
@@ -1107,9 +1109,12 @@ static Route run_device_decode(Device& dev, Output& out, const tbk_collapse_opts
 // read; they are inflated and decoded on the device with the records grouped by input file (tbk_bam_decode_file_spans), the records that
 // overlap the region are compacted into a collapse tile there (tbk_tile_region), and from then on the run is the device decode route's.
 // One tile, no fall-through: the output is what the same command line without -r makes of inputs cut to the region.
+// -R FILE is the same run over the region table of a BED file: every input's chunks merged over the whole table
+// (regions_input_chunks), the records that overlap any interval kept once (tbk_tile_regions).
 struct RegionPlan {
-  int32_t tid = 0;
-  int64_t beg = 0, end = 0;                        // 0-based, half-open
+  tbh::RegionTable U;                              // -r: the region itself (it may be empty); -R: the normalised table
+  bool one = true;                                 // -r: the one-region entries
+  const char* opt = "-r";                          // how the messages name the option
   std::vector<std::string> paths;
   std::vector<std::vector<tbh::IdxChunk>> chunks;  // per input, as its index names them
   size_t n_chunks = 0;
@@ -1118,23 +1123,32 @@ struct RegionPlan {
 static bool list_argument(const std::string& p) { return !tbh::bgzf_probe(p) && !tbh::sam_probe(p); }
 // what -r refuses of the inputs before they are opened: standard input, and (unless the one argument is a list of paths) anything
 // that is not a BGZF file
-static void refuse_region_inputs(TInputFiles& in, bool before_open) {
+static void refuse_region_inputs(TInputFiles& in, bool before_open, const char* o) {
   const bool list = before_open && in.freaders.size() == 1 && in.freaders[0]->fname != "-" && list_argument(in.freaders[0]->fname);
   for (const TSamReader* r : in.freaders) {
-    if (r->fname == "-") GError("Error: -r: the input - (standard input) has no index; -r takes BGZF-compressed BAM files\n");
-    if (!list && !tbh::bgzf_probe(r->fname)) GError("Error: -r: %s is not a BGZF-compressed BAM file (SAM text has no index)\n", r->fname.c_str());
+    if (r->fname == "-") GError("Error: %s: the input - (standard input) has no index; %s takes BGZF-compressed BAM files\n", o, o);
+    if (!list && !tbh::bgzf_probe(r->fname)) GError("Error: %s: %s is not a BGZF-compressed BAM file (SAM text has no index)\n", o, r->fname.c_str());
   }
 }
 // every refusal that needs no device, in the order of DESIGN.md §4f; nothing has been created when one of them ends the run
-static RegionPlan plan_region(TInputFiles& in, const std::string& region) {
+static RegionPlan plan_region(TInputFiles& in, const char* region, const char* regions_file) {
   RegionPlan P;
   auto t0 = tnow();
   std::string err;
   sam_hdr_t* mh = in.header();
-  if (!tbh::parse_region(*mh, region, &P.tid, &P.beg, &P.end, err)) GError("Error: -r: %s\n", err.c_str());
-  const std::string& rname = mh->target_name[(size_t)P.tid];
+  if (regions_file) {
+    P.one = false, P.opt = "-R";
+    if (!tbh::regions_from_bed_file(*mh, regions_file, P.U, err)) GError("Error: -R: %s\n", err.c_str());
+  } else {
+    int32_t tid = 0;
+    int64_t beg = 0, end = 0;
+    if (!tbh::parse_region(*mh, region, &tid, &beg, &end, err)) GError("Error: -r: %s\n", err.c_str());
+    P.U.add(tid, beg, end);
+  }
+  const int32_t max_tid = P.U.tid.back();  // (the table is sorted)
+  const std::string& rname = mh->target_name[(size_t)max_tid];
   const size_t k = in.freaders.size();
-  if (k > 65535) GError("Error: -r: %zu inputs; the device decode takes 65535\n", k);
+  if (k > 65535) GError("Error: %s: %zu inputs; the device decode takes 65535\n", P.opt, k);
   P.chunks.resize(k);
   for (size_t f = 0; f < k; ++f) {
     const std::string& path = in.freaders[f]->fname;
@@ -1142,15 +1156,18 @@ static RegionPlan plan_region(TInputFiles& in, const std::string& region) {
     sam_hdr_t* h = in.freaders[f]->samreader->header();
     // (the header merge has refused, with the file's name, a list that has another name at a position or a name at another position:
     // an input's list is the head of the merged one, and can only be too short for the region's reference)
-    if (P.tid >= h->n_targets)
-      GError("Error: -r: %s does not list the region's reference %s as reference %d, as the merged header does\n", path.c_str(), rname.c_str(), (int)P.tid);
+    if (max_tid >= h->n_targets)
+      GError("Error: %s: %s does not list the region's reference %s as reference %d, as the merged header does\n", P.opt, path.c_str(), rname.c_str(), (int)max_tid);
     std::string index_path;
-    if (!tbh::region_input_chunks(path, h->n_targets, P.tid, P.beg, P.end, P.chunks[f], index_path, err)) GError("Error: -r: %s\n", err.c_str());
+    if (!tbh::regions_input_chunks(path, h->n_targets, P.U, P.chunks[f], index_path, err)) GError("Error: %s: %s\n", P.opt, err.c_str());
     P.n_chunks += P.chunks[f].size();
   }
-  if (P.n_chunks > 65535)
+  if (P.n_chunks > 65535 && P.one)
     GError("Error: -r: the indexes of the %zu inputs name %zu chunks for the region in all; the device decode takes 65535 (first input: %s)\n", k, P.n_chunks,
            P.paths[0].c_str());
+  if (P.n_chunks > 65535)
+    GError("Error: -R: the indexes of the %zu inputs name %zu chunks for the %zu regions in all; the device decode takes 65535 (first input: %s)\n", k,
+           P.n_chunks, P.U.n(), P.paths[0].c_str());
   P.ms_index = tms(t0, tnow());
   return P;
 }
@@ -1167,7 +1184,7 @@ static Route run_region(Device& dev, Output& out, const tbk_collapse_opts& opt, 
   auto t_read = tnow();
   dev.wait();
   auto t_ctx = tnow();
-  if (!read_ok) GError("Error: -r: %s\n", err.c_str());
+  if (!read_ok) GError("Error: %s: %s\n", plan.opt, err.c_str());
   std::vector<uint32_t> span_first(k + 1, 0), first_uoff, last_uoff, fo(k + 1, 0);
   std::vector<const uint8_t*> comp;
   std::vector<uint64_t> comp_bytes;
@@ -1176,7 +1193,7 @@ static Route run_region(Device& dev, Output& out, const tbk_collapse_opts& opt, 
     span_first[f + 1] = (uint32_t)comp.size();
   }
   const int want_md = opt.strategy == TBK_STRAT_FULL, want_names = opt.collapse_same != 0;
-  auto too_large = [&](int rc) { GError("Error: -r: region too large for one tile (%s)\n", why_rc(dev, rc).c_str()); };
+  auto too_large = [&](int rc) { GError("Error: %s: region too large for one tile (%s)\n", plan.opt, why_rc(dev, rc).c_str()); };
   tbk_soa_in tile;
   int rc = dev.api.bam_decode_file_spans(dev.ctx, (uint32_t)k, span_first.data(), comp.data(), comp_bytes.data(), first_uoff.data(), last_uoff.data(), n_ref,
                                          inp.merged.data(), want_md, want_names, &tile, fo.data());
@@ -1191,18 +1208,24 @@ static Route run_region(Device& dev, Output& out, const tbk_collapse_opts& opt, 
       tbk_soa_in t1;
       if (dev.api.bam_decode_file_spans(dev.ctx, 1, one, comp.data() + a, comp_bytes.data() + a, first_uoff.data() + a, last_uoff.data() + a, n_ref,
                                         inp.merged.data() + f, want_md, want_names, &t1, fo1) == TBK_EINVAL)
-        GError("Error: -r: could not decode the chunks of %s its index names (%s): is the index the file's own?\n", plan.paths[f].c_str(), why.c_str());
+        GError("Error: %s: could not decode the chunks of %s its index names (%s): is the index the file's own?\n", plan.opt, plan.paths[f].c_str(), why.c_str());
     }
-    GError("Error: -r: could not decode the chunks the indexes name (%s; first input: %s): is the index the file's own?\n", why.c_str(), plan.paths[0].c_str());
+    GError("Error: %s: could not decode the chunks the indexes name (%s; first input: %s): is the index the file's own?\n", plan.opt, why.c_str(), plan.paths[0].c_str());
   }
-  if (rc != 0) GError("Error: -r: decoding the chunks on the GPU failed: %s (first input: %s)\n", why_rc(dev, rc).c_str(), plan.paths[0].c_str());
+  if (rc != 0) GError("Error: %s: decoding the chunks on the GPU failed: %s (first input: %s)\n", plan.opt, why_rc(dev, rc).c_str(), plan.paths[0].c_str());
   auto t_dec = tnow();
   const uint32_t n_decoded = tile.n_records;
   tbk_soa_in in;
   uint32_t n_kept = 0;
-  rc = dev.api.tile_region(dev.ctx, &tile, plan.tid, plan.beg, plan.end, &in, fo.data(), &n_kept);
+  if (plan.one) {
+    rc = dev.api.tile_region(dev.ctx, &tile, plan.U.tid[0], plan.U.beg[0], plan.U.end[0], &in, fo.data(), &n_kept);
+  } else {
+    tbk_regions regs;
+    regs.n = (uint32_t)plan.U.n(), regs.tid = plan.U.tid.data(), regs.beg = plan.U.beg.data(), regs.end = plan.U.end.data();
+    rc = dev.api.tile_regions(dev.ctx, &tile, &regs, &in, fo.data(), &n_kept);
+  }
   if (rc == TBK_ENOMEM || rc == TBK_E2BIG) too_large(rc);
-  if (rc != 0) GError("Error: -r: GPU region filter failed: %s\n", why_rc(dev, rc).c_str());
+  if (rc != 0) GError("Error: %s: GPU region filter failed: %s\n", plan.opt, why_rc(dev, rc).c_str());
   auto t_fil = tnow();
   spans.clear();
   DeviceTail T;
@@ -1217,9 +1240,9 @@ static Route run_region(Device& dev, Output& out, const tbk_collapse_opts& opt, 
   auto t3 = tnow();
   if (env.timing)
     fprintf(stderr,
-            "region path ms: index queries %.1f | chunk reads %.1f (%llu bytes in %zu chunks of %zu inputs, %llu bytes in all) | context up at %.1f | decode %.1f | "
+            "region path ms: index queries %.1f (%zu regions) | chunk reads %.1f (%llu bytes in %zu chunks of %zu inputs, %llu bytes in all) | context up at %.1f | decode %.1f | "
             "filter %.1f (%u of %u records) | collapse %.1f | write %.1f\n",
-            plan.ms_index, tms(t0, t_read), (unsigned long long)bytes_read, plan.n_chunks, k, (unsigned long long)inp.total, tms(dev.t_start, t_ctx), tms(t_ctx, t_dec),
+            plan.ms_index, plan.U.n(), tms(t0, t_read), (unsigned long long)bytes_read, plan.n_chunks, k, (unsigned long long)inp.total, tms(dev.t_start, t_ctx), tms(t_ctx, t_dec),
             tms(t_dec, t_fil), n_kept, n_decoded, tms(t_fil, T.t_col), tms(T.t_col, t3));
   return account_whole(tot, T.res, tms(t0, t_dec), tms(t_dec, T.t_col), tms(T.t_col, t3));
 }
@@ -1384,8 +1407,10 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
 
 // the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
-  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", nullptr};
-  const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQF");
+  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", nullptr};
+  const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQFR");
+  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", nullptr};
+  const int region_files = count_value_option(argc, argv, "regions-file", 'R', value_longs_R, "oNQFr");
   bool ranks = false, tracks = false, index = false, csi = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
@@ -1401,6 +1426,9 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
   if (ranks && csi) GError("Error: --csi is not available with --ranks (index the output afterwards)\n");
   if (regions > 1) GError("Error: -r / --region given more than once (one region per run)\n");
   if (ranks && regions) GError("Error: -r / --region is not available with --ranks\n");
+  if (region_files > 1) GError("Error: -R / --regions-file given more than once (one file of regions per run)\n");
+  if (region_files && regions) GError("Error: -R / --regions-file and -r / --region do not go together\n");
+  if (ranks && region_files) GError("Error: -R / --regions-file is not available with --ranks\n");
 }
 
 int main(int argc, char* argv[]) {
@@ -1409,7 +1437,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;csi;region=;SMLPEDVho:N:Q:F:r:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;csi;region=;regions-file=;SMLPEDVho:N:Q:F:r:R:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1478,8 +1506,11 @@ int main(int argc, char* argv[]) {
     GError("Error: --csi needs an output file (-o FILE, not -o -): an index addresses file offsets, standard output has none\n");
   const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty();
   const char* region = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");
+  const char* regions_file = args.getOpt('R') ? args.getOpt('R') : args.getOpt("regions-file");
+  const bool regional = region || regions_file;
+  const char* ropt = regions_file ? "-R" : "-r";
   while (const char* ifn = args.nextNonOpt()) {
-    if (region && strcmp(ifn, "-") == 0) GError("Error: -r: the input - (standard input) has no index; -r takes BGZF-compressed BAM files\n");
+    if (regional && strcmp(ifn, "-") == 0) GError("Error: %s: the input - (standard input) has no index; %s takes BGZF-compressed BAM files\n", ropt, ropt);
     inRecords.addFile(tbh_realpath(ifn).c_str());
   }
 
@@ -1487,15 +1518,15 @@ int main(int argc, char* argv[]) {
   // is brought up or any output file exists (plan_region's refusals)
   std::unique_ptr<RegionPlan> rplan;
   const Clock t_begin = tnow();
-  if (region) {
-    refuse_region_inputs(inRecords, true);
+  if (regional) {
+    refuse_region_inputs(inRecords, true, ropt);
     inRecords.name_ref_file = true;
     inRecords.start();
-    refuse_region_inputs(inRecords, false);
-    rplan.reset(new RegionPlan(plan_region(inRecords, region)));
+    refuse_region_inputs(inRecords, false, ropt);
+    rplan.reset(new RegionPlan(plan_region(inRecords, region, regions_file)));
   }
-  Device dev(env, opt, dev_writer, tracks, region ? t_begin : tnow());
-  if (!region) inRecords.start();
+  Device dev(env, opt, dev_writer, tracks, regional ? t_begin : tnow());
+  if (!regional) inRecords.start();
   auto t_ctx = tnow();
   Totals tot;
   // the tracks: the output header's sample lines (load_sample_info, commons.h:47-71) are checked before any work, the files opened

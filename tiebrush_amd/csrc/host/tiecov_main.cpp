@@ -2,7 +2,8 @@
 // The per-record loop (:435-499: bundles, addCov, addJunction, addMean, flushes) is replaced by
 // tbk_coverage_tile / tbk_sample_tile (HIP); BAM decode and text output stay on the host.
 // With -r REGION (no counterpart in the reference) only the chunks the file's index names for the region are read, and
-// they are inflated, decoded, filtered, summarised and cut to the region on the device (region_main below).
+// they are inflated, decoded, filtered, summarised and cut to the region on the device (regions_main below).
+// With -R FILE the same for the region table of a BED file, in one run: the chunks are merged over the whole table.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -25,7 +26,7 @@ static const char* USAGE =
     "TieCov v" VERSION " (MI355X build)\n"
     "Summarises a (TieBrush-collapsed) BAM file as BED-like tracks.\n"
     "\n"
-    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [-r REGION] input.bam\n"
+    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [-r REGION | -R FILE] input.bam\n"
     "\n"
     "  -h,--help    print this text and exit\n"
     "  --version    print the version and exit\n"
@@ -35,33 +36,45 @@ static const char* USAGE =
     "  -W           write the coverage (-c) as a bigWig file (PREFIX.bigwig) instead of a bedGraph\n"
     "  -r,--region REGION   only the tracks of REGION: NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive, commas allowed), read\n"
     "               through the file's index (input.bam.csi, input.bam.bai or input.bai; `tiebrush --index` / `--csi` write one)\n"
-    "  --index-file PATH    the index to use with -r\n"
+    "  -R,--regions-file FILE   the tracks of several regions in one run: FILE is BED (chrom start end, 0-based half-open; further\n"
+    "               columns ignored), its intervals sorted and merged where they overlap or abut; read through the index like -r\n"
+    "  --index-file PATH    the index to use with -r / -R\n"
     " At least one of -c / -j / -s is required.\n";
 
 // ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
 // how often -r / --region is given (Args keeps the last value of a repeated option)
 static int count_region_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", nullptr};
-  return count_value_option(argc, argv, "region", 'r', value_longs, "csj");
+  static const char* const value_longs[] = {"index-file", "regions-file", nullptr};
+  return count_value_option(argc, argv, "region", 'r', value_longs, "csjR");
+}
+static int count_regions_file_opts(int argc, char** argv) {
+  static const char* const value_longs[] = {"index-file", "region", nullptr};
+  return count_value_option(argc, argv, "regions-file", 'R', value_longs, "csjr");
 }
 
-static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::string& region, const std::string& index_file, const std::string& covfname,
-                       const std::string& jfname, const std::string& sfname, bool bigwig) {
+// The run of -r (one: U is the region itself, which may be empty, and goes through the one-region entries) and of -R (U is the
+// normalised table of the BED file, through the table entries): every other statement is shared.
+static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::RegionTable& U, bool one, const std::string& index_file,
+                        const std::string& covfname, const std::string& jfname, const std::string& sfname, bool bigwig,
+                        const std::chrono::steady_clock::time_point t0) {
   const bool timing = getenv("TBK_TIMING") != nullptr;
-  const auto t0 = std::chrono::steady_clock::now();
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   // every refusal comes before an output file exists
   std::string err;
-  int32_t rtid = 0;
-  int64_t beg = 0, end = 0;
-  if (!tbh::parse_region(*hdr, region, &rtid, &beg, &end, err)) GError("Error: %s\n", err.c_str());
+  const int32_t rtid = U.tid[0];
+  const int64_t beg = U.beg[0], end = U.end[0];
+  const uint32_t R = (uint32_t)U.n();
+  tbk_regions regs;
+  regs.n = R, regs.tid = U.tid.data(), regs.beg = U.beg.data(), regs.end = U.end.data();
   int num_samples = 0;
   if (!sfname.empty()) {
     num_samples = (int)hdr->co_samples().size();
     if (num_samples == 0) GError("Error: no sample lines found in header");
   }
   std::vector<tbh::IdxChunk> chunks;
-  if (!tbh::index_query_file(infname, index_file, rtid, beg, end, chunks, err)) GError("Error: %s\n", err.c_str());
+  if (!tbh::index_query_regions_file(infname, index_file, U, chunks, err)) GError("Error: %s\n", err.c_str());
+  if (!one && chunks.size() > 65535)
+    GError("Error: the index names %zu chunks for the %u regions; the device decode takes 65535\n", chunks.size(), R);
   const double ms_index = ms();
   // the context comes up beside the file reads
   tbk_ctx* ctx = nullptr;
@@ -88,7 +101,7 @@ static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::st
   if (rc != 0) GError("Error: could not decode the chunks of %s the index names (%s %s): is the index the file's own?\n", infname.c_str(), tbk_strerror(rc), tbk_last_error(ctx));
   tbk_cov_in in;
   uint32_t n_kept = 0;
-  rc = tbk_region_view(ctx, &tile, tag_seen, rtid, beg, end, &in, &n_kept);
+  rc = one ? tbk_region_view(ctx, &tile, tag_seen, rtid, beg, end, &in, &n_kept) : tbk_regions_view(ctx, &tile, tag_seen, &regs, &in, &n_kept);
   if (rc == TBK_E2BIG) GError("Error: input too large for one tile\n");
   if (rc != 0) GError("Error: GPU region filter failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
   const double ms_decode = ms();
@@ -107,7 +120,8 @@ static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::st
   FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
   const bool cov_bw = tf.cov_bw;
   if (coutf || cov_bw || joutf) {
-    const size_t ci = (coutf || cov_bw) ? 2 * co + 2 * n + 16 : 0, cj = joutf ? co + 16 : 0;
+    // (a clip over a table can grow the interval rows by R - 1: the arrays are sized with R added)
+    const size_t ci = (coutf || cov_bw) ? 2 * co + 2 * n + 16 + R : 0, cj = joutf ? co + 16 : 0;
     std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
     std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
     std::vector<uint8_t> jstr(cj ? cj : 1);
@@ -129,7 +143,7 @@ static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::st
       rc = tbk_coverage_tile(ctx, &in, &o);
       if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
       if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-      rc = tbk_cov_clip(ctx, &o, rtid, beg, end);
+      rc = one ? tbk_cov_clip(ctx, &o, rtid, beg, end) : tbk_cov_clip_regions(ctx, &o, &regs);
       if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
     }
     if (coutf) tbh::emit_cov_lines(coutf, hdr->target_name, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
@@ -140,7 +154,7 @@ static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::st
     if (joutf) tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);  // (numbered from 1)
   }
   if (soutf) {
-    size_t cs = 2 * co + 2 * n + 16;
+    size_t cs = 2 * co + 2 * n + 16 + R;
     std::vector<int32_t> st, ss, se;
     std::vector<int64_t> sc;
     std::vector<float> sh;
@@ -162,26 +176,26 @@ static int region_main(sam_hdr_t* hdr, const std::string& infname, const std::st
       so.iv_heat = sh.data();
       rc = tbk_sample_tile(ctx, &in, num_samples, &so);
       if (rc != TBK_E2BIG) break;
-      cs = (size_t)so.n_intervals + 16;
+      cs = (size_t)so.n_intervals + 16 + R;
     }
     if (n) {
       if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
       if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-      rc = tbk_sample_clip(ctx, &so, rtid, beg, end);
+      rc = one ? tbk_sample_clip(ctx, &so, rtid, beg, end) : tbk_sample_clip_regions(ctx, &so, &regs);
       if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
     }
     tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());
   }
   tf.close();
   if (timing)
-    fprintf(stderr, "tiecov -r phases ms: index %.1f | chunk reads %.1f (%llu bytes in %u chunks) | context up at %.1f | decode + filter %.1f (%u of %u records) | tracks %.1f\n",
-            ms_index, ms_read - ms_index, (unsigned long long)bytes_read, k, ms_ctx, ms_decode - ms_ctx, n_kept, tile.n_records, ms() - ms_decode);
+    fprintf(stderr, "tiecov %s phases ms: %u regions | index %.1f | chunk reads %.1f (%llu bytes in %u chunks) | context up at %.1f | decode + filter %.1f (%u of %u records) | tracks %.1f\n",
+            one ? "-r" : "-R", R, ms_index, ms_read - ms_index, (unsigned long long)bytes_read, k, ms_ctx, ms_decode - ms_ctx, n_kept, tile.n_records, ms() - ms_decode);
   tbk_destroy(ctx);
   return 0;
 }
 
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;region=;index-file=;DVWhc:s:j:r:");
+  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;DVWhc:s:j:r:R:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -215,11 +229,26 @@ int main(int argc, char* argv[]) {
   std::string infname = args.nextNonOpt();
   GSamReader samreader(infname.c_str(), SAM_QNAME | SAM_FLAG | SAM_RNAME | SAM_POS | SAM_CIGAR | SAM_AUX);
   sam_hdr_t* hdr = samreader.header();
-  if (args.getOpt('r') || args.getOpt("region") || args.getOpt("index-file")) {
+  if (args.getOpt('r') || args.getOpt("region") || args.getOpt('R') || args.getOpt("regions-file") || args.getOpt("index-file")) {
+    const auto t0 = std::chrono::steady_clock::now();
     if (count_region_opts(argc, argv) > 1) GError("Error: -r / --region given more than once (one region per run)\n");
+    if (count_regions_file_opts(argc, argv) > 1) GError("Error: -R / --regions-file given more than once (one file of regions per run)\n");
     const char* r = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");
-    if (!r) GError("Error: --index-file needs -r REGION\n");
-    return region_main(hdr, infname, r, args.getOpt("index-file") ? args.getOpt("index-file") : "", covfname, jfname, sfname, bigwig);
+    const char* rf = args.getOpt('R') ? args.getOpt('R') : args.getOpt("regions-file");
+    if (r && rf) GError("Error: -R / --regions-file and -r / --region do not go together\n");
+    if (!r && !rf) GError("Error: --index-file needs -r REGION\n");
+    const std::string index_file = args.getOpt("index-file") ? args.getOpt("index-file") : "";
+    std::string err;
+    tbh::RegionTable U;
+    if (rf) {
+      if (!tbh::regions_from_bed_file(*hdr, rf, U, err)) GError("Error: -R: %s\n", err.c_str());
+    } else {
+      int32_t rtid = 0;
+      int64_t beg = 0, end = 0;
+      if (!tbh::parse_region(*hdr, r, &rtid, &beg, &end, err)) GError("Error: %s\n", err.c_str());
+      U.add(rtid, beg, end);
+    }
+    return regions_main(hdr, infname, U, rf == nullptr, index_file, covfname, jfname, sfname, bigwig, t0);
   }
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;

@@ -12,12 +12,30 @@
 //   clip_bisect_k  interval rows are sorted and disjoint: the rows of the region are one range, found by two bisections
 //   clip_cov_k / clip_samp_k   that range, its rows trimmed to the region, into scratch (then copied over the caller's rows)
 //   clip_jflag_k / clip_jscat_k   junction rows are only sorted inside a bundle: keep flag, scan, scatter; rows are not trimmed
+//
+// The same four entries for a region TABLE U (`tiecov -R` / `tiebrush -R`, DESIGN.md §4g: tbk_regions_view, tbk_cov_clip_regions,
+// tbk_sample_clip_regions, tbk_tile_regions) share every host statement with their one-region siblings; only these kernels differ:
+//   rs_flag_k      rv_flag_k's keep / kcig by ONE bisection of U per record (the first interval that ends behind pos decides "overlaps any")
+//   clip_order_k   interval rows that are not sorted and disjoint are refused (they could overflow the scan below)
+//   clip_mrange_k  clip_bisect_k's two bisections, a thread per interval of U: first[r], count[r]; a scan of the counts: off[r], m
+//   clip_mcov_k / clip_msamp_k   a thread per OUTPUT row: its interval by a bisection of off, its source row, trimmed to that interval
+//   clip_mjflag_k  a junction row is kept when it overlaps any interval: the same single probe of U
 #include "dev_common.hpp"
 #include "tbk_internal.h"
 
 namespace {
 
 constexpr int RG_NT = 256;
+
+// the end of a record by the index's rule: pos + the reference length of its nc CIGAR words at cig + c0 over M D N = X, pos + 1 when that is 0
+__device__ __forceinline__ int64_t rec_end_of(int64_t p, const uint32_t* __restrict__ cig, uint32_t c0, uint32_t nc) {
+  int64_t rl = 0;
+  for (uint32_t q = 0; q < nc; ++q) {
+    const uint32_t w = cig[c0 + q];
+    if ((0x18Du >> (w & 15u)) & 1u) rl += (int64_t)(w >> 4);
+  }
+  return p + (rl ? rl : 1);
+}
 
 __global__ __launch_bounds__(RG_NT) void rv_flag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ pos,
                                                    const uint32_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, int32_t rtid, int64_t beg,
@@ -27,13 +45,54 @@ __global__ __launch_bounds__(RG_NT) void rv_flag_k(uint32_t n, const int32_t* __
   uint32_t k = 0, kc = 0;
   if (i < n && tid[i] == rtid) {
     const uint32_t c0 = cig_off[i], nc = cig_off[i + 1] - c0;
-    int64_t rl = 0;
-    for (uint32_t q = 0; q < nc; ++q) {
-      const uint32_t w = cig[c0 + q];
-      if ((0x18Du >> (w & 15u)) & 1u) rl += (int64_t)(w >> 4);
-    }
-    const int64_t p = pos[i], e = p + (rl ? rl : 1);
+    const int64_t p = pos[i], e = rec_end_of(p, cig, c0, nc);
     if (p < end && e > beg) k = 1, kc = nc;
+  }
+  keep[i] = k;
+  kcig[i] = kc;
+}
+
+// ---- a region table U on the device: R sorted, disjoint, non-empty, non-adjacent intervals, in global memory ----------
+struct RegTab {
+  uint32_t n;
+  const int32_t* tid;
+  const int64_t *beg, *end;
+};
+// the first interval with (tid, end) > (t, p) in lexicographic order (n: none).  U is disjoint and sorted, so its ends ascend with its
+// begins: every interval before that one ends at or before p, every one behind it begins later than it does — [p, e) on t overlaps ANY
+// interval exactly when that one lies on t and begins before e.
+__device__ __forceinline__ uint32_t tab_probe(const RegTab& U, int32_t t, int64_t p) {
+  uint32_t lo = 0, hi = U.n;
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    const int32_t mt = U.tid[m];
+    if (mt > t || (mt == t && U.end[m] > p))
+      hi = m;
+    else
+      lo = m + 1;
+  }
+  return lo;
+}
+__device__ __forceinline__ bool tab_overlaps(const RegTab& U, int32_t t, int64_t p, int64_t e) {
+  const uint32_t r = tab_probe(U, t, p);
+  return r < U.n && U.tid[r] == t && U.beg[r] < e;
+}
+
+// rv_flag_k for a table: the same keep / kcig, so everything behind the flags runs unchanged.  Records arrive in file order: the probes of
+// a wave fall on a few neighbouring entries of the table, which stays in global memory.
+__global__ __launch_bounds__(RG_NT) void rs_flag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ pos,
+                                                   const uint32_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, RegTab U,
+                                                   uint32_t* __restrict__ keep /* [n + 1] */, uint32_t* __restrict__ kcig /* [n + 1] */) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i > n) return;
+  uint32_t k = 0, kc = 0;
+  if (i < n) {
+    const uint32_t c0 = cig_off[i], nc = cig_off[i + 1] - c0;
+    const int64_t p = pos[i];
+    const int32_t t = tid[i];
+    const uint32_t r = tab_probe(U, t, p);
+    // (the CIGAR is walked only for a record that starts before its candidate interval)
+    if (r < U.n && U.tid[r] == t && (U.beg[r] <= p || U.beg[r] < rec_end_of(p, cig, c0, nc))) k = 1, kc = nc;
   }
   keep[i] = k;
   kcig[i] = kc;
@@ -135,6 +194,99 @@ __global__ __launch_bounds__(RG_NT) void clip_jflag_k(uint32_t n, const int32_t*
   if (i > n) return;
   keep[i] = (i < n && tid[i] == rtid && (int64_t)start[i] < end && (int64_t)endv[i] > beg) ? 1u : 0u;
 }
+// ---- the clips over a table: an interval row may come out once per interval of U that it meets, so the rows can grow (m <= n + R - 1) ----
+// clip_bisect_k's two bisections, a thread per interval r of U: rows [first[r], first[r] + count[r]) meet interval r; count[R] = 0 closes
+// the scan.  The second bisection starts at the first one's result: first + count <= n whatever the rows' order.
+__global__ __launch_bounds__(RG_NT) void clip_mrange_k(RegTab U, uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
+                                                       const int32_t* __restrict__ endv, uint32_t* __restrict__ first /* [R] */,
+                                                       uint32_t* __restrict__ count /* [R + 1] */) {
+  const uint64_t r = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (r > U.n) return;
+  if (r == U.n) {
+    count[r] = 0;
+    return;
+  }
+  const int32_t rtid = U.tid[r];
+  const int64_t beg = U.beg[r], end = U.end[r];
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    if (tid[m] > rtid || (tid[m] == rtid && (int64_t)endv[m] > beg))
+      hi = m;
+    else
+      lo = m + 1;
+  }
+  const uint32_t f = lo;
+  hi = n;
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    if (tid[m] > rtid || (tid[m] == rtid && (int64_t)start[m] >= end))
+      hi = m;
+    else
+      lo = m + 1;
+  }
+  first[r] = f;
+  count[r] = lo - f;
+}
+// *bad = 1 when a row ends before it starts, lies on an earlier reference than its predecessor or starts before that one ends: rows that
+// are sorted and disjoint give m <= n + R - 1, anything else could overflow the scan (*bad is zeroed before the launch; every writer
+// stores the same 1)
+__global__ __launch_bounds__(RG_NT) void clip_order_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
+                                                      const int32_t* __restrict__ endv, uint32_t* __restrict__ bad) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i >= n) return;
+  if (endv[i] < start[i] || (i + 1 < n && (tid[i + 1] < tid[i] || (tid[i + 1] == tid[i] && start[i + 1] < endv[i])))) *bad = 1u;
+}
+// output row i -> its interval r (the last one whose scanned offset is <= i; off[R] = m > i) and its source row
+__device__ __forceinline__ uint32_t clip_mfind(uint32_t i, uint32_t R, const uint32_t* __restrict__ off, const uint32_t* __restrict__ first, uint32_t* src) {
+  uint32_t lo = 0, hi = R;  // the first r in [0, R] with off[r] > i
+  while (lo < hi) {
+    const uint32_t m = lo + (hi - lo) / 2;
+    if (off[m] > i)
+      hi = m;
+    else
+      lo = m + 1;
+  }
+  const uint32_t r = lo - 1;  // (off[0] = 0 <= i: lo >= 1)
+  *src = first[r] + (i - off[r]);
+  return r;
+}
+__global__ __launch_bounds__(RG_NT) void clip_mcov_k(uint32_t m, RegTab U, const uint32_t* __restrict__ off /* [R + 1] */, const uint32_t* __restrict__ first,
+                                                     const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv,
+                                                     const double* __restrict__ val, int32_t* __restrict__ o_tid, int32_t* __restrict__ o_start,
+                                                     int32_t* __restrict__ o_end, double* __restrict__ o_val) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i >= m) return;
+  uint32_t s;
+  const uint32_t r = clip_mfind((uint32_t)i, U.n, off, first, &s);
+  o_tid[i] = tid[s];
+  o_start[i] = clip_lo(start[s], U.beg[r]);
+  o_end[i] = clip_hi(endv[s], U.end[r]);
+  o_val[i] = val[s];
+}
+__global__ __launch_bounds__(RG_NT) void clip_msamp_k(uint32_t m, RegTab U, const uint32_t* __restrict__ off, const uint32_t* __restrict__ first,
+                                                      const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv,
+                                                      const int64_t* __restrict__ cnt, const float* __restrict__ heat, int32_t* __restrict__ o_tid,
+                                                      int32_t* __restrict__ o_start, int32_t* __restrict__ o_end, int64_t* __restrict__ o_cnt,
+                                                      float* __restrict__ o_heat) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i >= m) return;
+  uint32_t s;
+  const uint32_t r = clip_mfind((uint32_t)i, U.n, off, first, &s);
+  o_tid[i] = tid[s];
+  o_start[i] = clip_lo(start[s], U.beg[r]);
+  o_end[i] = clip_hi(endv[s], U.end[r]);
+  o_cnt[i] = cnt[s];
+  o_heat[i] = heat[s];
+}
+// a junction row is kept when it overlaps any interval of U: rs_flag_k's one probe, with j_start / j_end
+__global__ __launch_bounds__(RG_NT) void clip_mjflag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
+                                                       const int32_t* __restrict__ endv, RegTab U, uint32_t* __restrict__ keep /* [n + 1] */) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i > n) return;
+  keep[i] = (i < n && tab_overlaps(U, tid[i], (int64_t)start[i], (int64_t)endv[i])) ? 1u : 0u;
+}
+
 __global__ __launch_bounds__(RG_NT) void clip_jscat_k(uint32_t n, const uint32_t* __restrict__ keep, const uint32_t* __restrict__ koff,
                                                       const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv,
                                                       const uint8_t* __restrict__ strand, const double* __restrict__ val, int32_t* __restrict__ o_tid,
@@ -171,8 +323,6 @@ int rows_out(tbk_ctx* ctx, int mem, T* dst, const T* scratch, size_t m) {
   return 0;
 }
 
-bool region_ok(int mem, int32_t tid, int64_t beg, int64_t end) { return (mem == TBK_MEM_HOST || mem == TBK_MEM_DEVICE) && tid >= 0 && beg >= 0 && end >= beg; }
-
 struct ProfEnd {
   tbk_ctx* c;
   ~ProfEnd() { tbk_prof_end_call(c); }
@@ -196,11 +346,81 @@ int clip_range(tbk_ctx* ctx, uint32_t n, const int32_t* d_tid, const int32_t* d_
   return 0;
 }
 
-}  // namespace
+// what an entry selects by: one region, or (U != NULL) a table — the one-region entries and their table siblings share every statement
+// but the flag / range kernels
+struct Sel {
+  const tbk_regions* U;
+  int32_t tid;
+  int64_t beg, end;
+};
+// sorted by (tid, beg), disjoint, non-empty, non-adjacent; n >= 1, tid >= 0, beg >= 0 (checked on the host before anything is launched)
+bool regions_ok(const tbk_regions* U) {
+  if (!U || U->n == 0 || !U->tid || !U->beg || !U->end) return false;
+  for (uint32_t r = 0; r < U->n; ++r) {
+    if (U->tid[r] < 0 || U->beg[r] < 0 || U->end[r] <= U->beg[r]) return false;
+    if (r && (U->tid[r] < U->tid[r - 1] || (U->tid[r] == U->tid[r - 1] && U->beg[r] <= U->end[r - 1]))) return false;
+  }
+  return true;
+}
+bool sel_ok(const Sel& s) { return s.U ? regions_ok(s.U) : (s.tid >= 0 && s.beg >= 0 && s.end >= s.beg); }
+size_t tab_bytes(const Sel& s) { return s.U ? (size_t)s.U->n * 32 + 4096 : 0; }  // (the table and, for the clips, first / count / off)
 
-extern "C" int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, int32_t tid, int64_t beg, int64_t end, tbk_cov_in* view,
-                               uint32_t* n_kept) {
-  if (!ctx || !tile || !view || !n_kept || tile->mem != TBK_MEM_DEVICE || tid < 0 || beg < 0 || end < beg) return TBK_EINVAL;
+// the device form of U, uploaded once per call into the workspace (after the call's tbk_ws_reserve)
+int tab_upload(tbk_ctx* ctx, const tbk_regions* U, RegTab* T) {
+  int32_t* t = ws_alloc<int32_t>(ctx, U->n);
+  int64_t *b = ws_alloc<int64_t>(ctx, U->n), *e = ws_alloc<int64_t>(ctx, U->n);
+  if (!t || !b || !e) return TBK_ENOMEM;
+  TBK_HIP(hipMemcpyAsync(t, U->tid, (size_t)U->n * 4, hipMemcpyHostToDevice, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(b, U->beg, (size_t)U->n * 8, hipMemcpyHostToDevice, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(e, U->end, (size_t)U->n * 8, hipMemcpyHostToDevice, ctx->stream));
+  T->n = U->n, T->tid = t, T->beg = b, T->end = e;
+  return 0;
+}
+
+// keep / kcig of the tile's records for the selection
+int flag_records(tbk_ctx* ctx, const Sel& s, uint32_t n, const int32_t* tid, const int32_t* pos, const uint32_t* cig_off, const uint32_t* cig, uint32_t* keep,
+                 uint32_t* kcig) {
+  const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
+  if (s.U) {
+    RegTab T;
+    TBK_TRY(tab_upload(ctx, s.U, &T));
+    TBK_LAUNCH(ctx, "regions_flag", rs_flag_k, grid, RG_NT, 0, n, tid, pos, cig_off, cig, T, keep, kcig);
+  } else {
+    TBK_LAUNCH(ctx, "region_flag", rv_flag_k, grid, RG_NT, 0, n, tid, pos, cig_off, cig, s.tid, s.beg, s.end, keep, kcig);
+  }
+  return 0;
+}
+
+// interval rows against a table: *m output rows, row i from source row first[r] + (i - off[r]) of the interval r that off places it in
+int clip_mrange(tbk_ctx* ctx, const RegTab& T, uint32_t n, const int32_t* d_tid, const int32_t* d_start, const int32_t* d_end, uint32_t** first, uint32_t** off,
+                uint64_t* m) {
+  const uint32_t R = T.n;
+  uint32_t* count = ws_alloc<uint32_t>(ctx, (size_t)R + 1);
+  uint32_t* bad = ws_alloc<uint32_t>(ctx, 1);
+  *first = ws_alloc<uint32_t>(ctx, R);
+  *off = ws_alloc<uint32_t>(ctx, (size_t)R + 1);
+  if (!count || !bad || !*first || !*off) return TBK_ENOMEM;
+  TBK_HIP(hipMemsetAsync(bad, 0, 4, ctx->stream));
+  TBK_LAUNCH(ctx, "clip_order", clip_order_k, cdiv(n, RG_NT), RG_NT, 0, n, d_tid, d_start, d_end, bad);
+  TBK_LAUNCH(ctx, "clip_mrange", clip_mrange_k, cdiv((uint64_t)R + 1, RG_NT), RG_NT, 0, T, n, d_tid, d_start, d_end, *first, count);
+  uint32_t res[2] = {0, 0};
+  // (a sum of counts beyond n + R - 1 needs rows that overlap or lie out of order, and those are refused here first)
+  TBK_HIP(hipMemcpyAsync(&res[0], bad, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  if (res[0]) {
+    ctx->last_error = "clip: interval rows are not sorted by reference and start, or overlap";
+    return TBK_EINVAL;
+  }
+  TBK_TRY(tbk_exscan_u32(ctx, count, *off, R + 1, nullptr));
+  TBK_HIP(hipMemcpyAsync(&res[1], *off + R, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipStreamSynchronize(ctx->stream));
+  *m = res[1];
+  if (*m > (uint64_t)n + R - 1) return TBK_EHIP;
+  return 0;
+}
+
+int region_view_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, const Sel& sel, tbk_cov_in* view, uint32_t* n_kept) {
+  if (!ctx || !tile || !view || !n_kept || tile->mem != TBK_MEM_DEVICE || !sel_ok(sel)) return TBK_EINVAL;
   const uint32_t n = tile->n_records;
   if (n && (!tile->tid || !tile->pos || !tile->flag || !tile->strand || !tile->cig_off || (tile->n_cigar_ops && !tile->cig))) return TBK_EINVAL;
   if (n == UINT32_MAX) return TBK_E2BIG;
@@ -212,14 +432,14 @@ extern "C" int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8
   if (n == 0) return 0;
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
-  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 16 + ((size_t)1 << 20)));
+  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 16 + tab_bytes(sel) + ((size_t)1 << 20)));
   uint32_t* keep = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   uint32_t* kcig = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   uint32_t* koff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   uint32_t* coff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   if (!keep || !kcig || !koff || !coff) return TBK_ENOMEM;
   const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
-  TBK_LAUNCH(ctx, "region_flag", rv_flag_k, grid, RG_NT, 0, n, tile->tid, tile->pos, tile->cig_off, tile->cig, tid, beg, end, keep, kcig);
+  TBK_TRY(flag_records(ctx, sel, n, tile->tid, tile->pos, tile->cig_off, tile->cig, keep, kcig));
   TBK_TRY(tbk_exscan_u32(ctx, keep, koff, n + 1, nullptr));
   TBK_TRY(tbk_exscan_u32(ctx, kcig, coff, n + 1, nullptr));
   uint32_t tot[2] = {0, 0};
@@ -271,18 +491,24 @@ extern "C" int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8
   return 0;
 }
 
-extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end) {
-  if (!ctx || !rows || !region_ok(rows->mem, tid, beg, end)) return TBK_EINVAL;
+int cov_clip_impl(tbk_ctx* ctx, tbk_cov_out* rows, const Sel& sel) {
+  if (!ctx || !rows || (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE) || !sel_ok(sel)) return TBK_EINVAL;
   const uint32_t ni = rows->cap_intervals ? rows->n_intervals : 0, nj = rows->cap_junctions ? rows->n_junctions : 0;
   if (ni > rows->cap_intervals || nj > rows->cap_junctions || ni == UINT32_MAX || nj == UINT32_MAX) return TBK_EINVAL;
   if (ni && (!rows->iv_tid || !rows->iv_start || !rows->iv_end || !rows->iv_val)) return TBK_EINVAL;
   if (nj && (!rows->j_tid || !rows->j_start || !rows->j_end || !rows->j_strand || !rows->j_val)) return TBK_EINVAL;
   if (!ni && !nj) return 0;
+  const int32_t tid = sel.tid;
+  const int64_t beg = sel.beg, end = sel.end;
+  const size_t R = sel.U ? sel.U->n : 0;
+  if ((uint64_t)ni + R >= UINT32_MAX) return TBK_E2BIG;
   TBK_HIP(hipSetDevice(ctx->device));
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
   const int mem = rows->mem;
-  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 48 + (size_t)nj * 64 + ((size_t)1 << 20)));
+  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 48 + (ni ? R * 24 : 0) + tab_bytes(sel) + (size_t)nj * 64 + ((size_t)1 << 20)));
+  RegTab T{};
+  if (sel.U) TBK_TRY(tab_upload(ctx, sel.U, &T));
   if (ni) {
     const int32_t *d_tid, *d_start, *d_end;
     const double* d_val;
@@ -290,13 +516,26 @@ extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_
     TBK_TRY(rows_in(ctx, mem, rows->iv_start, ni, &d_start));
     TBK_TRY(rows_in(ctx, mem, rows->iv_end, ni, &d_end));
     TBK_TRY(rows_in(ctx, mem, rows->iv_val, ni, &d_val));
-    uint32_t first = 0, m = 0;
-    TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
+    uint32_t first = 0, m = 0, *m_first = nullptr, *m_off = nullptr;
+    if (sel.U) {
+      uint64_t mm = 0;
+      TBK_TRY(clip_mrange(ctx, T, ni, d_tid, d_start, d_end, &m_first, &m_off, &mm));
+      if (mm > rows->cap_intervals) {  // the rows grew beyond the caller's arrays: nothing is written, the count needed is reported
+        rows->n_intervals = (uint32_t)mm;
+        return TBK_E2BIG;
+      }
+      m = (uint32_t)mm;
+    } else {
+      TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
+    }
     if (m) {
       int32_t *s_tid = ws_alloc<int32_t>(ctx, m), *s_start = ws_alloc<int32_t>(ctx, m), *s_end = ws_alloc<int32_t>(ctx, m);
       double* s_val = ws_alloc<double>(ctx, m);
       if (!s_tid || !s_start || !s_end || !s_val) return TBK_ENOMEM;
-      TBK_LAUNCH(ctx, "clip_cov", clip_cov_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_val, beg, end, s_tid, s_start, s_end, s_val);
+      if (sel.U)
+        TBK_LAUNCH(ctx, "clip_mcov", clip_mcov_k, cdiv(m, RG_NT), RG_NT, 0, m, T, m_off, m_first, d_tid, d_start, d_end, d_val, s_tid, s_start, s_end, s_val);
+      else
+        TBK_LAUNCH(ctx, "clip_cov", clip_cov_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_val, beg, end, s_tid, s_start, s_end, s_val);
       TBK_TRY(rows_out(ctx, mem, rows->iv_tid, s_tid, m));
       TBK_TRY(rows_out(ctx, mem, rows->iv_start, s_start, m));
       TBK_TRY(rows_out(ctx, mem, rows->iv_end, s_end, m));
@@ -319,7 +558,10 @@ extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_
     uint8_t* s_strand = ws_alloc<uint8_t>(ctx, nj);
     double* s_val = ws_alloc<double>(ctx, nj);
     if (!keep || !koff || !s_tid || !s_start || !s_end || !s_strand || !s_val) return TBK_ENOMEM;
-    TBK_LAUNCH(ctx, "clip_junc", clip_jflag_k, cdiv((uint64_t)nj + 1, RG_NT), RG_NT, 0, nj, d_tid, d_start, d_end, tid, beg, end, keep);
+    if (sel.U)
+      TBK_LAUNCH(ctx, "clip_mjunc", clip_mjflag_k, cdiv((uint64_t)nj + 1, RG_NT), RG_NT, 0, nj, d_tid, d_start, d_end, T, keep);
+    else
+      TBK_LAUNCH(ctx, "clip_junc", clip_jflag_k, cdiv((uint64_t)nj + 1, RG_NT), RG_NT, 0, nj, d_tid, d_start, d_end, tid, beg, end, keep);
     TBK_TRY(tbk_exscan_u32(ctx, keep, koff, nj + 1, nullptr));
     TBK_LAUNCH(ctx, "clip_junc", clip_jscat_k, cdiv(nj, RG_NT), RG_NT, 0, nj, keep, koff, d_tid, d_start, d_end, d_strand, d_val, s_tid, s_start, s_end, s_strand,
                s_val);
@@ -338,17 +580,23 @@ extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_
   return tbk_check_launch(ctx, "cov_clip");
 }
 
-extern "C" int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, int64_t beg, int64_t end) {
-  if (!ctx || !rows || !region_ok(rows->mem, tid, beg, end)) return TBK_EINVAL;
+int sample_clip_impl(tbk_ctx* ctx, tbk_sample_out* rows, const Sel& sel) {
+  if (!ctx || !rows || (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE) || !sel_ok(sel)) return TBK_EINVAL;
   const uint32_t ni = rows->n_intervals;
   if (ni > rows->cap_intervals || ni == UINT32_MAX) return TBK_EINVAL;
   if (ni && (!rows->iv_tid || !rows->iv_start || !rows->iv_end || !rows->iv_count || !rows->iv_heat)) return TBK_EINVAL;
   if (!ni) return 0;
+  const int32_t tid = sel.tid;
+  const int64_t beg = sel.beg, end = sel.end;
+  const size_t R = sel.U ? sel.U->n : 0;
+  if ((uint64_t)ni + R >= UINT32_MAX) return TBK_E2BIG;
   TBK_HIP(hipSetDevice(ctx->device));
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
   const int mem = rows->mem;
-  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 56 + ((size_t)1 << 20)));
+  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 56 + R * 24 + tab_bytes(sel) + ((size_t)1 << 20)));
+  RegTab T{};
+  if (sel.U) TBK_TRY(tab_upload(ctx, sel.U, &T));
   const int32_t *d_tid, *d_start, *d_end;
   const int64_t* d_cnt;
   const float* d_heat;
@@ -357,15 +605,29 @@ extern "C" int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, 
   TBK_TRY(rows_in(ctx, mem, rows->iv_end, ni, &d_end));
   TBK_TRY(rows_in(ctx, mem, rows->iv_count, ni, &d_cnt));
   TBK_TRY(rows_in(ctx, mem, rows->iv_heat, ni, &d_heat));
-  uint32_t first = 0, m = 0;
-  TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
+  uint32_t first = 0, m = 0, *m_first = nullptr, *m_off = nullptr;
+  if (sel.U) {
+    uint64_t mm = 0;
+    TBK_TRY(clip_mrange(ctx, T, ni, d_tid, d_start, d_end, &m_first, &m_off, &mm));
+    if (mm > rows->cap_intervals) {  // (as in cov_clip_impl)
+      rows->n_intervals = (uint32_t)mm;
+      return TBK_E2BIG;
+    }
+    m = (uint32_t)mm;
+  } else {
+    TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
+  }
   if (m) {
     int32_t *s_tid = ws_alloc<int32_t>(ctx, m), *s_start = ws_alloc<int32_t>(ctx, m), *s_end = ws_alloc<int32_t>(ctx, m);
     int64_t* s_cnt = ws_alloc<int64_t>(ctx, m);
     float* s_heat = ws_alloc<float>(ctx, m);
     if (!s_tid || !s_start || !s_end || !s_cnt || !s_heat) return TBK_ENOMEM;
-    TBK_LAUNCH(ctx, "clip_sample", clip_samp_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_cnt, d_heat, beg, end, s_tid, s_start, s_end, s_cnt,
-               s_heat);
+    if (sel.U)
+      TBK_LAUNCH(ctx, "clip_msample", clip_msamp_k, cdiv(m, RG_NT), RG_NT, 0, m, T, m_off, m_first, d_tid, d_start, d_end, d_cnt, d_heat, s_tid, s_start, s_end,
+                 s_cnt, s_heat);
+    else
+      TBK_LAUNCH(ctx, "clip_sample", clip_samp_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_cnt, d_heat, beg, end, s_tid, s_start, s_end, s_cnt,
+                 s_heat);
     TBK_TRY(rows_out(ctx, mem, rows->iv_tid, s_tid, m));
     TBK_TRY(rows_out(ctx, mem, rows->iv_start, s_start, m));
     TBK_TRY(rows_out(ctx, mem, rows->iv_end, s_end, m));
@@ -375,6 +637,30 @@ extern "C" int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, 
   rows->n_intervals = m;
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   return tbk_check_launch(ctx, "sample_clip");
+}
+
+}  // namespace
+
+extern "C" int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, int32_t tid, int64_t beg, int64_t end, tbk_cov_in* view,
+                               uint32_t* n_kept) {
+  return region_view_impl(ctx, tile, tag_seen, Sel{nullptr, tid, beg, end}, view, n_kept);
+}
+extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end) { return cov_clip_impl(ctx, rows, Sel{nullptr, tid, beg, end}); }
+extern "C" int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, int64_t beg, int64_t end) {
+  return sample_clip_impl(ctx, rows, Sel{nullptr, tid, beg, end});
+}
+// ---- the same for a region table ----
+extern "C" int tbk_regions_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, const tbk_regions* regions, tbk_cov_in* view, uint32_t* n_kept) {
+  if (!regions) return TBK_EINVAL;
+  return region_view_impl(ctx, tile, tag_seen, Sel{regions, 0, 0, 0}, view, n_kept);
+}
+extern "C" int tbk_cov_clip_regions(tbk_ctx* ctx, tbk_cov_out* rows, const tbk_regions* regions) {
+  if (!regions) return TBK_EINVAL;
+  return cov_clip_impl(ctx, rows, Sel{regions, 0, 0, 0});
+}
+extern "C" int tbk_sample_clip_regions(tbk_ctx* ctx, tbk_sample_out* rows, const tbk_regions* regions) {
+  if (!regions) return TBK_EINVAL;
+  return sample_clip_impl(ctx, rows, Sel{regions, 0, 0, 0});
 }
 
 // ---- tbk_tile_region: the region's records of a decoded tile as a collapse tile -------------------------------------------
@@ -467,11 +753,8 @@ T* rt_alloc(tbk_ctx* ctx, size_t n) {
   return (T*)tbk_bam_dev_alloc(ctx, (n ? n : 1) * sizeof(T));
 }
 
-}  // namespace
-
-extern "C" int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid, int64_t beg, int64_t end, tbk_soa_in* out, uint32_t* file_off_out,
-                               uint32_t* n_kept) {
-  if (!ctx || !tile || !out || !file_off_out || !n_kept || tile->mem != TBK_MEM_DEVICE || tid < 0 || beg < 0 || end < beg) return TBK_EINVAL;
+int tile_region_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const Sel& sel, tbk_soa_in* out, uint32_t* file_off_out, uint32_t* n_kept) {
+  if (!ctx || !tile || !out || !file_off_out || !n_kept || tile->mem != TBK_MEM_DEVICE || !sel_ok(sel)) return TBK_EINVAL;
   const uint32_t n = tile->n_records, k = tile->n_files;
   if (k == 0 || !tile->file_off || tile->prio_hi || tile->prio_lo) return TBK_EINVAL;
   if (tile->file_off[0] != 0 || tile->file_off[k] != n) return TBK_EINVAL;
@@ -507,7 +790,7 @@ extern "C" int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid
   if (!tbk_bam_dev_records(ctx, &d_inf, &d_rec, &n_rec) || n_rec != n) return TBK_EINVAL;
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
-  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 32 + ((size_t)k + 1) * 8 + ((size_t)1 << 20)));
+  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 32 + ((size_t)k + 1) * 8 + tab_bytes(sel) + ((size_t)1 << 20)));
   uint32_t* keep = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   uint32_t* kcig = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   uint32_t* koff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
@@ -520,7 +803,7 @@ extern "C" int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid
   if (!keep || !kcig || !koff || !coff || (has_md && !moff) || (has_qn && !qoff) || !d_fo || !d_fo_out) return TBK_ENOMEM;
   const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
   TBK_HIP(hipMemcpyAsync(d_fo, fo_in.data(), ((size_t)k + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  TBK_LAUNCH(ctx, "region_flag", rv_flag_k, grid, RG_NT, 0, n, in.tid, in.pos, in.cig_off, in.cig, tid, beg, end, keep, kcig);
+  TBK_TRY(flag_records(ctx, sel, n, in.tid, in.pos, in.cig_off, in.cig, keep, kcig));
   TBK_TRY(tbk_exscan_u32(ctx, keep, koff, n + 1, nullptr));
   TBK_TRY(tbk_exscan_u32(ctx, kcig, coff, n + 1, nullptr));
   if (has_md || has_qn) {
@@ -581,4 +864,15 @@ extern "C" int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid
   out->qname_hash = O.qh, out->qname_off = O.qn_off, out->qname = O.qn;
   *n_kept = (uint32_t)nk;
   return 0;
+}
+
+}  // namespace
+
+extern "C" int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid, int64_t beg, int64_t end, tbk_soa_in* out, uint32_t* file_off_out,
+                               uint32_t* n_kept) {
+  return tile_region_impl(ctx, tile, Sel{nullptr, tid, beg, end}, out, file_off_out, n_kept);
+}
+extern "C" int tbk_tile_regions(tbk_ctx* ctx, const tbk_soa_in* tile, const tbk_regions* regions, tbk_soa_in* out, uint32_t* file_off_out, uint32_t* n_kept) {
+  if (!regions) return TBK_EINVAL;
+  return tile_region_impl(ctx, tile, Sel{regions, 0, 0, 0}, out, file_off_out, n_kept);
 }
