@@ -186,8 +186,11 @@ struct GroupAcc {
   long long* yxin;
   long long* ydin;
   unsigned long long* rep;
-  uint32_t* first;  // sorted position of the group head
+  uint32_t* first;  // sorted position of the group head; null: the identity (the lean form of the window path's compaction)
   uint8_t* tie;
+  // (the lean form of the window path's compaction, wgroup.hip: rep, yc, ns and first are null) the caller's representatives, by OUTPUT
+  // place — written by the compaction and wg_tie_k, read by the YD stage for the groups whose key word is no exact code
+  const uint32_t* orep;
 };
 
 // wave-segmented reductions over lanes holding equal (sorted) keys
@@ -551,7 +554,9 @@ __device__ __forceinline__ uint32_t yd_exons_from_key(uint64_t lo, uint32_t st, 
 // A group's record (tid + 1, start, end, exon word) from its key (h, l); the representative's CIGAR — rep[sg], a chain of dependent
 // loads — is walked only when the key word is no exact code.  Both makers of the records call this, yd_groups_k and the count pass of
 // the items placed by list (yd_lcount_k<true>): one definition of the coordinates and of the X2 packing.
-__device__ __forceinline__ uint4 yd_group_rec(const ColIn& I, uint64_t h, uint64_t l, const unsigned long long* __restrict__ rep, uint32_t sg) {
+// rep == nullptr: the representative is orep[o], the caller's array by output place.
+__device__ __forceinline__ uint4 yd_group_rec(const ColIn& I, uint64_t h, uint64_t l, const unsigned long long* __restrict__ rep, uint32_t sg,
+                                              const uint32_t* __restrict__ orep, uint32_t o) {
   const int32_t st = (int32_t)(uint32_t)((h >> 2) & 0x7FFFFFFFull);
   const uint32_t tidp1 = (uint32_t)(h >> 33);
   const uint32_t en = (uint32_t)(st + (int32_t)(uint32_t)(l >> 32) - 1);
@@ -559,7 +564,7 @@ __device__ __forceinline__ uint4 yd_group_rec(const ColIn& I, uint64_t h, uint64
   const uint32_t nk = yd_exons_from_key(l, (uint32_t)st, en, &e0, &s1);
   int nex = (int)nk;
   if (nex == 0) {
-    const uint32_t r = (uint32_t)(rep[sg] & 0xFFFFFFFFull);
+    const uint32_t r = rep ? (uint32_t)(rep[sg] & 0xFFFFFFFFull) : orep[o];
     walk_exons(I.pos[r], I.cig + I.cig_off[r], I.cig_off[r + 1] - I.cig_off[r], [](int, int) {}, &nex);
   }
   uint32_t xw = (uint32_t)nex;
@@ -606,6 +611,7 @@ __device__ __forceinline__ YsAgg ys_chain_cells(const YsCells& P, uint32_t c, Ys
 // indirection of yd_groups_k is not taken.  !FRONT (yd_front=split): the records are read from gpk.
 template <bool FRONT>
 __global__ __launch_bounds__(YS_NT) void yd_lcount_k(YsIn S, ColIn I, const uint64_t* __restrict__ glo, const unsigned long long* __restrict__ rep,
+                                                     const uint32_t* __restrict__ orep /* rep == nullptr: the representatives by output place */,
                                                      uint4* __restrict__ gpk /* YdGroups::pk: FRONT ? written : read */, uint32_t ntiles,
                                                      uint32_t* __restrict__ table /* [YS_NL + FRONT][ntiles] */, uint4* __restrict__ agg /* [YS_NL][ntiles] */,
                                                      uint64_t* __restrict__ gwb /* [ntiles][YS_NT / 64][YS_NL]: the columns, for yd_lscatter_k */) {
@@ -633,7 +639,7 @@ __global__ __launch_bounds__(YS_NT) void yd_lcount_k(YsIn S, ColIn I, const uint
       ys_mask_from_files(files, c, &lo, &hi);
       uint4 g;
       if constexpr (FRONT) {
-        g = yd_group_rec(I, h, glo[sg], rep, sg);
+        g = yd_group_rec(I, h, glo[sg], rep, sg, orep, o);
         gpk[o] = g;
         nfar = yd_far_count(g.w);
       } else {
@@ -786,8 +792,8 @@ __global__ void yd_groups_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ g
   uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= ng) return;
   uint32_t sg = gperm[o];
-  uint32_t q = G.first[sg];
-  const uint4 g = yd_group_rec(I, shi[q], slo[q], G.rep, sg);
+  uint32_t q = G.first ? G.first[sg] : sg;
+  const uint4 g = yd_group_rec(I, shi[q], slo[q], G.rep, sg, G.orep, o);
   Q.nex[o] = yd_far_count(g.w);  // (the input of the offset scan)
   Q.pk[o] = g;
 }
@@ -802,7 +808,7 @@ __global__ void yd_gexons_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ g
   uint32_t w = Q.xoff[o];
   {
     uint32_t e0, s1;
-    const uint32_t nk = yd_exons_from_key(slo[G.first[sg]], pk.y, pk.z, &e0, &s1);
+    const uint32_t nk = yd_exons_from_key(slo[G.first ? G.first[sg] : sg], pk.y, pk.z, &e0, &s1);
     if (nk) {
       ex_s[w] = pk.y;
       ex_e[w] = e0;
@@ -813,7 +819,7 @@ __global__ void yd_gexons_k(ColIn I, uint32_t ng, const uint32_t* __restrict__ g
       return;
     }
   }
-  uint32_t r = (uint32_t)(G.rep[sg] & 0xFFFFFFFFull);
+  uint32_t r = G.rep ? (uint32_t)(G.rep[sg] & 0xFFFFFFFFull) : G.orep[o];
   int nex = 0;
   walk_exons(I.pos[r], I.cig + I.cig_off[r], I.cig_off[r + 1] - I.cig_off[r],
              [&](int es, int ee) {
@@ -2014,11 +2020,11 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
       if (split_front) {  // yd_front=split (test hook): the records and the exon offsets by passes of their own, as on the other paths
         TBK_LAUNCH(ctx, "yd_groups", yd_groups_k, cdiv(ng, B), B, 0, I, ng, J.gperm, J.G, J.shi, J.slo, Q);
         TBK_TRY(tbk_exscan_u32(ctx, Q.nex, Q.xoff, ng, sc + 5));
-        TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k<false>, ys_tiles, YS_NT, 0, S, I, J.slo, J.G.rep, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
+        TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k<false>, ys_tiles, YS_NT, 0, S, I, J.slo, J.G.rep, J.G.orep, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
         TBK_LAUNCH(ctx, "yd_lscan", yd_lscan_k, YS_NL, 1024, 0, ys_table, ys_tiles, ys_totals, (unsigned long long*)(sc + 2),
                    (unsigned long long*)nullptr);
       } else {  // the count pass makes the records; the exon offsets ride through its table (sc[5]: the exons of all far groups)
-        TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k<true>, ys_tiles, YS_NT, 0, S, I, J.slo, J.G.rep, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
+        TBK_LAUNCH(ctx, "yd_lcount", yd_lcount_k<true>, ys_tiles, YS_NT, 0, S, I, J.slo, J.G.rep, J.G.orep, Q.pk, ys_tiles, ys_table, ys_agg, ys_wb);
         TBK_LAUNCH(ctx, "yd_lscan", yd_lscan_k, YS_NL + 1, 1024, 0, ys_table, ys_tiles, ys_totals, (unsigned long long*)(sc + 2),
                    (unsigned long long*)(sc + 5));
       }
@@ -2450,6 +2456,7 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       G.rep = wo.rep;
       G.first = wo.first;
       G.tie = wo.tie;
+      G.orep = out->rep;
       g_yd = ws_alloc<int32_t>(ctx, ng);
       // the output order and its inverse (made where col_recgroup_w_k or yd_fill_w_k, items NOT placed by list, will read it) come with
       // the groups: the compaction wrote the identity and wg_tie_k permuted the tie sets of several groups and rewrote their members'

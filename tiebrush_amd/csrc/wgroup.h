@@ -14,7 +14,9 @@ struct WgOut {
   uint32_t* pgrp = nullptr;         // [np] group of the incidence; null when the YD stage places its items by list (tbk_yd_by_list)
   uint64_t* gfmask = nullptr;       // [ng] (<= 64 files and tbk_yd_by_list) the group's files as a bit mask: np = 0, no incidence arrays
   uint32_t* rec_sg = nullptr;       // optional [n]: group (key order) of every passing record, 0xFFFFFFFF otherwise
-  // per-group accumulators, as the sort path's reduction leaves them
+  // per-group accumulators, as the sort path's reduction leaves them.  The LEAN form of the raw compaction (wgroup.hip: files as
+  // masks, ties done there, no record -> group map, no group partials, the caller's rep / yc / yx present and ng <= cap): gmem, yc,
+  // ns, rep and first are null — the caller's arrays (WgDirectOut) hold the values, by output place
   double* yc = nullptr;
   uint32_t* ns = nullptr;
   long long *yxin = nullptr, *ydin = nullptr;

@@ -1830,6 +1830,27 @@ struct WgVerify {  // VERIFY: the sparse verification list of the raw form (WgRa
   int strategy;
   uint32_t* err;
 };
+// the caller's lines of the group with representative word r, count yc, YX yx and key (hi, lo), at output place o (col_write_k's lines)
+__device__ __forceinline__ void wg_direct_store(const WgDirectOut& D, uint32_t o, unsigned long long r, double yc, int64_t yx, uint64_t hi,
+                                                uint64_t lo) {
+  const int32_t st = (int32_t)(uint32_t)((hi >> 2) & 0x7FFFFFFFull);
+  D.rep[o] = (uint32_t)(r & 0xFFFFFFFFull);
+  if (D.rep_effend) D.rep_effend[o] = (int32_t)(uint32_t)(r >> 32);
+  D.yc[o] = yc;
+  D.yx[o] = yx;
+  if (D.g_start) D.g_start[o] = st;
+  if (D.g_end) D.g_end[o] = st + (int32_t)(uint32_t)(lo >> 32) - 1;
+  if (D.g_key) {
+    const uint32_t h32 = (uint32_t)lo;
+    uint32_t shape = 0;
+    if (D.strategy == TBK_STRAT_CIGAR || D.strategy == TBK_STRAT_CLIP) {  // (-E codes speak of exons, which may hold I and D)
+      if (h32 == (0x80000000u | C_M)) shape = 0x80000000u;
+      if ((h32 >> 30) == 3u) shape = h32;
+    }
+    D.g_key[2 * (size_t)o] = hi;
+    D.g_key[2 * (size_t)o + 1] = (lo & 0xFFFFFFFF00000000ull) | shape;
+  }
+}
 // The tie flag of a group needs the key of the group before it in key order.  Inside a window that is the lane below (or lane 63 of
 // the round before); the FIRST group of a window opens a tie set without a look at the window before: every bound in W is a value of
 // the partition key (wg_split_k: v or v + 1 of a sampled key), the offsets pass puts a record in window w exactly when
@@ -1845,7 +1866,13 @@ struct WgVerify {  // VERIFY: the sparse verification list of the raw form (WgRa
 // them in the queue, the representative behind the shuffles, all ahead of the round's first store (the whole chain ahead of the loop
 // cost a quarter more: 1.2 ms against 0.98 on 64 files x 5 M reads); the CIGAR compare and the rare further rounds of entries come
 // behind the copies.  pbase == nullptr: the files travel as masks, there is no incidence.
-template <bool VERIFY>
+//
+// LEAN (raw form, files as masks, ties done here, the caller's arrays all present and large enough, no record -> group map, no group
+// partials): the caller's arrays are the only copy of the representative, the count and the sample count — WgFinal::rep, gmem, yc, ns
+// and first are null and not stored (first is the identity, gmem the low word of rep, yc / ns what D.yc / D.yx say).  wg_tie_k, their
+// only reader ahead of the YD stage, takes them from window space; the YD stage reads the caller's rep.  73 bytes stored per group
+// instead of 101.
+template <bool VERIFY, bool LEAN>
 __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const uint32_t* __restrict__ gbase, const uint32_t* __restrict__ pbase,
                                                    WgFinal F, WgVerify V) {
   const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;  // one wave per window (no block-wide step below)
@@ -1905,36 +1932,21 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
     F.ghi[sg] = hi;
     F.glo[sg] = lo;
     F.tie[sg] = tie;
-    F.rep[sg] = r;
-    F.gmem[sg] = (uint32_t)(r & 0xFFFFFFFFull);
-    F.yc[sg] = (double)cnt;
-    F.ns[sg] = nsv;
-    if (F.yxin) {
-      F.yxin[sg] = (long long)yx;
-      F.ydin[sg] = (long long)yd;
+    if constexpr (!LEAN) {
+      F.rep[sg] = r;
+      F.gmem[sg] = (uint32_t)(r & 0xFFFFFFFFull);
+      F.yc[sg] = (double)cnt;
+      F.ns[sg] = nsv;
+      if (F.yxin) {
+        F.yxin[sg] = (long long)yx;
+        F.ydin[sg] = (long long)yd;
+      }
+      F.first[sg] = sg;
     }
-    F.first[sg] = sg;
     if (F.gperm) F.gperm[sg] = sg;
     if (F.ginv) F.ginv[sg] = sg;
-    if (F.D.rep && sg < F.D.cap) {  // the caller's results in key order (col_write_k's lines; the members of tie sets are rewritten behind)
-      const int32_t st = (int32_t)(uint32_t)((hi >> 2) & 0x7FFFFFFFull);
-      F.D.rep[sg] = (uint32_t)(r & 0xFFFFFFFFull);
-      if (F.D.rep_effend) F.D.rep_effend[sg] = (int32_t)(uint32_t)(r >> 32);
-      F.D.yc[sg] = (double)cnt;
-      F.D.yx[sg] = (F.yxin ? (int64_t)yx : 0ll) + (int64_t)nsv;
-      if (F.D.g_start) F.D.g_start[sg] = st;
-      if (F.D.g_end) F.D.g_end[sg] = st + (int32_t)(uint32_t)(lo >> 32) - 1;
-      if (F.D.g_key) {
-        const uint32_t h32 = (uint32_t)lo;
-        uint32_t shape = 0;
-        if (F.D.strategy == TBK_STRAT_CIGAR || F.D.strategy == TBK_STRAT_CLIP) {  // (-E codes speak of exons, which may hold I and D)
-          if (h32 == (0x80000000u | C_M)) shape = 0x80000000u;
-          if ((h32 >> 30) == 3u) shape = h32;
-        }
-        F.D.g_key[2 * (size_t)sg] = hi;
-        F.D.g_key[2 * (size_t)sg + 1] = (lo & 0xFFFFFFFF00000000ull) | shape;
-      }
-    }
+    // the caller's results in key order (the members of tie sets are rewritten behind)
+    if (F.D.rep && sg < F.D.cap) wg_direct_store(F.D, sg, r, (double)cnt, (F.yxin ? (int64_t)yx : 0ll) + (int64_t)nsv, hi, lo);
     if (F.fmask) F.fmask[sg] = fm;
     if (!F.fmask) F.gpoff[sg] = pb + po;  // (file masks: no incidence list to point into)
     if (F.slot2sg) F.slot2sg[wb + g] = sg;
@@ -1963,9 +1975,16 @@ __global__ __launch_bounds__(256) void wg_compact_k(uint32_t nw, WgTemp T, const
 // compaction has left in window space (WgFinal::tcnt, the way vcnt tells of listed records): a block reads the counts of 256 windows,
 // lists those with one in LDS, and its waves take the listed windows in turn — nothing is appended to a device-wide list, and a window
 // without such a set costs the four bytes of its count.
-__device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t lane, const WgFinal& F, const WgVerify& V);
+// F.gmem == nullptr (the lean form of the compaction): a member's representative, count and sample count are read where the tier
+// kernels left them — member s of the window is entry wbase[w] + s - gb of T.rep / T.cnt / T.ns.
+struct WgTieSrc {
+  const unsigned long long* rep;
+  const uint32_t *cnt, *ns, *wbase;
+};
+__device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t wb, uint32_t lane, const WgFinal& F, const WgTieSrc& S,
+                                              const WgVerify& V);
 __global__ __launch_bounds__(256) void wg_tie_k(uint32_t nw, const uint32_t* __restrict__ wg_cnt, const uint32_t* __restrict__ gbase, WgFinal F,
-                                               WgVerify V) {
+                                               WgTieSrc S, WgVerify V) {
   __shared__ uint32_t s_n, s_w[256];
   if (threadIdx.x == 0) s_n = 0;
   __syncthreads();
@@ -1973,10 +1992,13 @@ __global__ __launch_bounds__(256) void wg_tie_k(uint32_t nw, const uint32_t* __r
   if (w0 < nw && F.tcnt[w0]) s_w[atomicAdd(&s_n, 1u)] = w0;
   __syncthreads();
   const uint32_t n = s_n, lane = threadIdx.x & 63u;
-  for (uint32_t i = threadIdx.x >> 6; i < n; i += 4) wg_tie_window(wg_cnt[s_w[i]], gbase[s_w[i]], lane, F, V);
+  for (uint32_t i = threadIdx.x >> 6; i < n; i += 4) wg_tie_window(wg_cnt[s_w[i]], gbase[s_w[i]], S.wbase[s_w[i]], lane, F, S, V);
 }
-// one wave on a window of ng groups, the first of them group gb
-__device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t lane, const WgFinal& F, const WgVerify& V) {
+// one wave on a window of ng groups, the first of them group gb (window space: entry wb)
+__device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t wb, uint32_t lane, const WgFinal& F, const WgTieSrc& S,
+                                              const WgVerify& V) {
+  const bool lean = F.gmem == nullptr;
+  auto member = [&](uint32_t s) { return lean ? (uint32_t)(S.rep[wb + (s - gb)] & 0xFFFFFFFFull) : F.gmem[s]; };
   for (uint32_t g = lane; g + 1 < ng; g += 64) {
     const uint32_t sg = gb + g;
     if (!F.tie[sg] || F.tie[sg + 1]) continue;  // not a head, or a set of one: in place
@@ -1984,11 +2006,11 @@ __device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t
     while (g + e < ng && !F.tie[sg + e]) ++e;
     for (uint32_t a = 1; a < e; ++a) {
       const uint32_t x = F.gperm[sg + a];
-      const uint32_t rx = F.gmem[x];
+      const uint32_t rx = member(x);
       uint32_t b = a;
       while (b > 0) {
         const uint32_t y = F.gperm[sg + b - 1];
-        if (strategy_cmp(V.I, V.strategy, rx, F.gmem[y]) < 0) {
+        if (strategy_cmp(V.I, V.strategy, rx, member(y)) < 0) {
           F.gperm[sg + b] = y;
           --b;
         } else {
@@ -2001,25 +2023,10 @@ __device__ __forceinline__ void wg_tie_window(uint32_t ng, uint32_t gb, uint32_t
       const uint32_t o = sg + a, s = F.gperm[o];
       if (F.ginv) F.ginv[s] = o;
       if (!F.D.rep || o >= F.D.cap) continue;
-      const unsigned long long r = F.rep[s];
+      const unsigned long long r = lean ? S.rep[wb + (s - gb)] : F.rep[s];
       const uint64_t hi = F.ghi[s], lo = F.glo[s];
-      const int32_t st = (int32_t)(uint32_t)((hi >> 2) & 0x7FFFFFFFull);
-      F.D.rep[o] = (uint32_t)(r & 0xFFFFFFFFull);
-      if (F.D.rep_effend) F.D.rep_effend[o] = (int32_t)(uint32_t)(r >> 32);
-      F.D.yc[o] = F.yc[s];
-      F.D.yx[o] = (F.yxin ? (int64_t)F.yxin[s] : 0ll) + (int64_t)F.ns[s];
-      if (F.D.g_start) F.D.g_start[o] = st;
-      if (F.D.g_end) F.D.g_end[o] = st + (int32_t)(uint32_t)(lo >> 32) - 1;
-      if (F.D.g_key) {
-        const uint32_t h32 = (uint32_t)lo;
-        uint32_t shape = 0;
-        if (F.D.strategy == TBK_STRAT_CIGAR || F.D.strategy == TBK_STRAT_CLIP) {  // (-E codes speak of exons, which may hold I and D)
-          if (h32 == (0x80000000u | C_M)) shape = 0x80000000u;
-          if ((h32 >> 30) == 3u) shape = h32;
-        }
-        F.D.g_key[2 * (size_t)o] = hi;
-        F.D.g_key[2 * (size_t)o + 1] = (lo & 0xFFFFFFFF00000000ull) | shape;
-      }
+      wg_direct_store(F.D, o, r, lean ? (double)S.cnt[wb + (s - gb)] : F.yc[s],
+                      lean ? (int64_t)S.ns[wb + (s - gb)] : (F.yxin ? (int64_t)F.yxin[s] : 0ll) + (int64_t)F.ns[s], hi, lo);
     }
   }
 }
@@ -2660,21 +2667,23 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   out->ng = ng;
   out->np = np;
   ctx->ws_top_mode = false;  // the group arrays: from the bottom
+  // the lean form of the compaction (wg_compact_k): the caller's arrays hold the representative, the count and the sample count
+  const bool lean = raw && T.fmask && !want_rec_sg && !part && !ctx->dbg.wg_back_split && direct && direct->rep && ng <= direct->cap;
   out->ghi = ws_alloc<uint64_t>(ctx, ng);
   out->glo = ws_alloc<uint64_t>(ctx, ng);
-  out->gmem = ws_alloc<uint32_t>(ctx, ng);
+  out->gmem = lean ? nullptr : ws_alloc<uint32_t>(ctx, ng);
   out->gpoff = ws_alloc<uint32_t>(ctx, ng);
   out->gfmask = T.fmask ? ws_alloc<uint64_t>(ctx, ng) : nullptr;
   if (T.fmask && !out->gfmask) return TBK_ENOMEM;
   out->pfile = ws_alloc<uint16_t>(ctx, np);
   out->pgrp = tbk_yd_by_list(ctx, k) ? nullptr : ws_alloc<uint32_t>(ctx, np);
-  out->yc = ws_alloc<double>(ctx, ng);
-  out->ns = ws_alloc<uint32_t>(ctx, ng);
+  out->yc = lean ? nullptr : ws_alloc<double>(ctx, ng);
+  out->ns = lean ? nullptr : ws_alloc<uint32_t>(ctx, ng);
   out->yxin = part ? ws_alloc<long long>(ctx, ng) : nullptr;
   out->ydin = part ? ws_alloc<long long>(ctx, ng) : nullptr;
   if (part && !out->ydin) return TBK_ENOMEM;
-  out->rep = ws_alloc<unsigned long long>(ctx, ng);
-  out->first = ws_alloc<uint32_t>(ctx, ng);
+  out->rep = lean ? nullptr : ws_alloc<unsigned long long>(ctx, ng);
+  out->first = lean ? nullptr : ws_alloc<uint32_t>(ctx, ng);
   out->tie = ws_alloc<uint8_t>(ctx, ng);
   out->rec_sg = want_rec_sg ? ws_alloc<uint32_t>(ctx, I.n) : nullptr;
   // (raw) the output order and its inverse.  The inverse has two readers, col_recgroup_w_k and yd_fill_w_k (items NOT placed by list):
@@ -2701,11 +2710,16 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
     const WgVerify V{I, strategy, ctx->d_err};
     // the listed records are verified by the compaction's own waves (wg_back=split: by a pass of their own behind it)
     const bool list_live = raw && R.sparse && ctx->h_scalars[6] != 0;
-    if (list_live && !back_split)
-      TBK_LAUNCH(ctx, "wg_compact", wg_compact_k<true>, cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
+    if (lean && list_live)
+      TBK_LAUNCH(ctx, "wg_compact", (wg_compact_k<true, true>), cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
+    else if (lean)
+      TBK_LAUNCH(ctx, "wg_compact", (wg_compact_k<false, true>), cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
+    else if (list_live && !back_split)
+      TBK_LAUNCH(ctx, "wg_compact", (wg_compact_k<true, false>), cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
     else
-      TBK_LAUNCH(ctx, "wg_compact", wg_compact_k<false>, cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
-    if (out->ties_done) TBK_LAUNCH(ctx, "col_tie_sets", wg_tie_k, cdiv(nw, 256u), 256, 0, nw, T.wg_cnt, gbase, F, V);
+      TBK_LAUNCH(ctx, "wg_compact", (wg_compact_k<false, false>), cdiv(nw, 4u), 256, 0, nw, T, gbase, pbase, F, V);
+    if (out->ties_done)
+      TBK_LAUNCH(ctx, "col_tie_sets", wg_tie_k, cdiv(nw, 256u), 256, 0, nw, T.wg_cnt, gbase, F, WgTieSrc{T.rep, T.cnt, T.ns, T.wbase}, V);
     if (want_rec_sg) TBK_HIP(hipMemsetAsync(out->rec_sg, 0xFF, (size_t)I.n * 4, ctx->stream));  // (records that did not pass)
     if (raw) {  // (nothing to verify and no record -> group map wanted: every key word was exact)
       if (list_live && back_split)
