@@ -587,7 +587,8 @@ int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_see
 /* Cut the rows of a tbk_coverage_tile call to [beg, end) on tid, in place (rows->mem HOST or DEVICE), and rewrite n_intervals /
  * n_junctions.  Interval rows outside the region are dropped, a row across an edge is trimmed to it and keeps its value.  Junction
  * rows are kept whole when j_start < end && j_end > beg, in their order (the caller numbers them from 1).  tbk_sample_clip: the same
- * for the rows of tbk_sample_tile.  TBK_EINVAL for interval rows that are not sorted by (tid, start).
+ * for the rows of tbk_sample_tile.  TBK_EINVAL for interval rows that are not sorted by (tid, start) and disjoint; nothing faults and
+ * the context takes the next call (the rows of tbk_coverage_tile / tbk_sample_tile always are).
  * (With these entries tbk_coverage_tile / tbk_sample_tile also take a DEVICE input with HOST output arrays: the rows are computed on
  * the device and copied back.) */
 int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end);

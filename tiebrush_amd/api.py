@@ -487,12 +487,22 @@ class Context:
         self._bam_keep = (bufs, so)
         return s, so, seen.value
 
-    def region_view(self, tile_struct, tag_seen, tid, beg, end) -> DeviceCovView:
-        """tbk_region_view: the records of a device tile (bam_decode_spans / bam_decode) overlapping [beg, end) on tid, as tiecov's input"""
+    # ---- the region entries: one region (tid, beg, end) or a table [(tid, beg, end)] (tbk_regions).  Each pair of
+    # methods shares one body, given the C entry and the arguments that name the selection. ----
+    def _region_view(self, name, tile_struct, tag_seen, sel) -> DeviceCovView:
         v, nk = _lib.CovIn(), C.c_uint32(0)
-        self._check(self.L.tbk_region_view(self.h, C.byref(tile_struct), tag_seen, int(tid), int(beg), int(end), C.byref(v), C.byref(nk)), "tbk_region_view")
+        self._check(getattr(self.L, name)(self.h, C.byref(tile_struct), tag_seen, *sel, C.byref(v), C.byref(nk)), name)
         assert int(nk.value) == int(v.n_records)
         return DeviceCovView(v, int(v.n_records), int(v.n_cigar_ops))
+
+    def region_view(self, tile_struct, tag_seen, tid, beg, end) -> DeviceCovView:
+        """tbk_region_view: the records of a device tile (bam_decode_spans / bam_decode) overlapping [beg, end) on tid, as tiecov's input"""
+        return self._region_view("tbk_region_view", tile_struct, tag_seen, (int(tid), int(beg), int(end)))
+
+    def regions_view(self, tile_struct, tag_seen, table) -> DeviceCovView:
+        """tbk_regions_view: the records of a device tile overlapping any interval of the table, as tiecov's input"""
+        u, _keep = _regions(table)
+        return self._region_view("tbk_regions_view", tile_struct, tag_seen, (C.byref(u),))
 
     def bam_decode_file_spans(self, file_spans, n_ref, tbmerged=None, want_md=False, want_names=False):
         """tbk_bam_decode_file_spans: file_spans = per input file the list of its spans [(bytes of whole BGZF members, first_uoff,
@@ -516,86 +526,34 @@ class Context:
         self._bam_keep = (bufs, tb, fo)
         return s, fo
 
-    def tile_region(self, tile_struct, tid, beg, end):
-        """tbk_tile_region: the records of the context's decoded tile overlapping [beg, end) on tid as a collapse tile -> (SoaIn struct,
-        file_off [n_files + 1]); the input tile is consumed, tile indices are the compacted ones from here on"""
+    def _tile_region(self, name, tile_struct, sel):
         k = int(tile_struct.n_files)
         fo = np.zeros(k + 1, dtype=np.uint32)
         out, nk = _lib.SoaIn(), C.c_uint32(0)
-        self._check(self.L.tbk_tile_region(self.h, C.byref(tile_struct), int(tid), int(beg), int(end), C.byref(out), fo.ctypes.data, C.byref(nk)), "tbk_tile_region")
+        self._check(getattr(self.L, name)(self.h, C.byref(tile_struct), *sel, C.byref(out), fo.ctypes.data, C.byref(nk)), name)
         assert int(nk.value) == int(out.n_records)
         self._region_keep = (fo, getattr(self, "_bam_keep", None))
         return out, fo
 
-    def cov_clip(self, res, tid, beg, end):
-        """tbk_cov_clip: the result dict of coverage() cut to [beg, end) on tid (numpy rows or device tensors), as a new dict"""
-        keep = []
-        dev = any(_is_torch(res.get(k)) for k in ("iv_tid", "j_tid"))
-        a, b = (len(res["iv_tid"]) if "iv_tid" in res else 0), (len(res["j_tid"]) if "j_tid" in res else 0)
-        own = {k: (v.clone() if _is_torch(v) else np.array(v, copy=True)) for k, v in res.items() if k[:3] == "iv_" or k[:2] == "j_"}
-
-        def ptr(name, dt):
-            return _addr(own[name], dt, keep) if name in own and _numel(own[name]) else None
-        o = _lib.CovOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, a, ptr("iv_tid", np.int32), ptr("iv_start", np.int32), ptr("iv_end", np.int32),
-                        ptr("iv_val", np.float64), b, ptr("j_tid", np.int32), ptr("j_start", np.int32), ptr("j_end", np.int32), ptr("j_strand", np.uint8),
-                        ptr("j_val", np.float64), a, b, 0, 0)
-        self._order_after_torch(dev)
-        self._check(self.L.tbk_cov_clip(self.h, C.byref(o), int(tid), int(beg), int(end)), "tbk_cov_clip")
-        out = dict(n_intervals=int(o.n_intervals), n_junctions=int(o.n_junctions))
-        for k, v in own.items():
-            out[k] = v[:out["n_intervals"] if k[:3] == "iv_" else out["n_junctions"]]
-        return out
-
-    def sample_clip(self, res, tid, beg, end):
-        """tbk_sample_clip: the result dict of sample() cut to [beg, end) on tid, as a new dict"""
-        keep = []
-        dev = _is_torch(res["s_tid"])
-        a = len(res["s_tid"])
-        own = {k: (v.clone() if _is_torch(v) else np.array(v, copy=True)) for k, v in res.items() if k[:2] == "s_"}
-
-        def ptr(name, dt):
-            return _addr(own[name], dt, keep) if a else None
-        o = _lib.SampleOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, a, ptr("s_tid", np.int32), ptr("s_start", np.int32), ptr("s_end", np.int32),
-                           ptr("s_count", np.int64), ptr("s_heat", np.float32), a)
-        self._order_after_torch(dev)
-        self._check(self.L.tbk_sample_clip(self.h, C.byref(o), int(tid), int(beg), int(end)), "tbk_sample_clip")
-        m = int(o.n_intervals)
-        out = {k: v[:m] for k, v in own.items()}
-        out["n_sample"] = m
-        return out
-
-    # ---- the same for a region table [(tid, beg, end)] (tbk_regions; DESIGN.md 4g) ----
-    def regions_view(self, tile_struct, tag_seen, table) -> DeviceCovView:
-        """tbk_regions_view: the records of a device tile overlapping any interval of the table, as tiecov's input"""
-        u, _keep = _regions(table)
-        v, nk = _lib.CovIn(), C.c_uint32(0)
-        self._check(self.L.tbk_regions_view(self.h, C.byref(tile_struct), tag_seen, C.byref(u), C.byref(v), C.byref(nk)), "tbk_regions_view")
-        assert int(nk.value) == int(v.n_records)
-        return DeviceCovView(v, int(v.n_records), int(v.n_cigar_ops))
+    def tile_region(self, tile_struct, tid, beg, end):
+        """tbk_tile_region: the records of the context's decoded tile overlapping [beg, end) on tid as a collapse tile -> (SoaIn struct,
+        file_off [n_files + 1]); the input tile is consumed, tile indices are the compacted ones from here on"""
+        return self._tile_region("tbk_tile_region", tile_struct, (int(tid), int(beg), int(end)))
 
     def tile_regions(self, tile_struct, table):
         """tbk_tile_regions: the records of the context's decoded tile overlapping any interval of the table as a collapse tile -> (SoaIn
         struct, file_off [n_files + 1]); the input tile is consumed"""
         u, _keep = _regions(table)
-        k = int(tile_struct.n_files)
-        fo = np.zeros(k + 1, dtype=np.uint32)
-        out, nk = _lib.SoaIn(), C.c_uint32(0)
-        self._check(self.L.tbk_tile_regions(self.h, C.byref(tile_struct), C.byref(u), C.byref(out), fo.ctypes.data, C.byref(nk)), "tbk_tile_regions")
-        assert int(nk.value) == int(out.n_records)
-        self._region_keep = (fo, getattr(self, "_bam_keep", None))
-        return out, fo
+        return self._tile_region("tbk_tile_regions", tile_struct, (C.byref(u),))
 
-    def cov_clip_regions(self, res, table, cap_intervals=None):
-        """tbk_cov_clip_regions: the result dict of coverage() cut to the table, as a new dict.  The interval rows can grow by
-        len(table) - 1: the arrays are sized cap_intervals (default: the rows + len(table)).  On TBK_E2BIG the TbkError carries
-        .needed (the count the call asks for) and .rows (the arrays as the call left them)."""
+    def _cov_clip(self, name, res, sel, cap):
+        """the clips of coverage() rows: own copies of the rows (the interval columns in arrays of cap elements: None for the rows' own
+        count, which one region never exceeds), the call, the rows that came out"""
         keep = []
-        u, _keep = _regions(table)
         dev = any(_is_torch(res.get(k)) for k in ("iv_tid", "j_tid"))
         a, b = (len(res["iv_tid"]) if "iv_tid" in res else 0), (len(res["j_tid"]) if "j_tid" in res else 0)
-        cap = a + len(table) if cap_intervals is None else int(cap_intervals)
-        own = {k: (_grown(v, cap) if k[:3] == "iv_" else (v.clone() if _is_torch(v) else np.array(v, copy=True)))
-               for k, v in res.items() if k[:3] == "iv_" or k[:2] == "j_"}
+        cap = a if cap is None else cap
+        own = {k: _grown(v, cap if k[:3] == "iv_" else len(v)) for k, v in res.items() if k[:3] == "iv_" or k[:2] == "j_"}
 
         def ptr(name, dt):
             return _addr(own[name], dt, keep) if name in own and _numel(own[name]) else None
@@ -603,19 +561,30 @@ class Context:
                         ptr("iv_end", np.int32), ptr("iv_val", np.float64), b, ptr("j_tid", np.int32), ptr("j_start", np.int32), ptr("j_end", np.int32),
                         ptr("j_strand", np.uint8), ptr("j_val", np.float64), a, b, 0, 0)
         self._order_after_torch(dev)
-        self._check_grow(self.L.tbk_cov_clip_regions(self.h, C.byref(o), C.byref(u)), "tbk_cov_clip_regions", o, own)
+        self._check_grow(getattr(self.L, name)(self.h, C.byref(o), *sel), name, o, own)
         out = dict(n_intervals=int(o.n_intervals), n_junctions=int(o.n_junctions))
         for k, v in own.items():
             out[k] = v[:out["n_intervals"] if k[:3] == "iv_" else out["n_junctions"]]
         return out
 
-    def sample_clip_regions(self, res, table, cap_intervals=None):
-        """tbk_sample_clip_regions: the result dict of sample() cut to the table, as a new dict (capacity and TBK_E2BIG as cov_clip_regions)"""
-        keep = []
+    def cov_clip(self, res, tid, beg, end):
+        """tbk_cov_clip: the result dict of coverage() cut to [beg, end) on tid (numpy rows or device tensors), as a new dict"""
+        return self._cov_clip("tbk_cov_clip", res, (int(tid), int(beg), int(end)), None)
+
+    def cov_clip_regions(self, res, table, cap_intervals=None):
+        """tbk_cov_clip_regions: the result dict of coverage() cut to the table, as a new dict.  The interval rows can grow by
+        len(table) - 1: the arrays are sized cap_intervals (default: the rows + len(table)).  On TBK_E2BIG the TbkError carries
+        .needed (the count the call asks for) and .rows (the arrays as the call left them)."""
         u, _keep = _regions(table)
+        a = len(res["iv_tid"]) if "iv_tid" in res else 0
+        return self._cov_clip("tbk_cov_clip_regions", res, (C.byref(u),), a + len(table) if cap_intervals is None else int(cap_intervals))
+
+    def _sample_clip(self, name, res, sel, cap):
+        """the clips of sample() rows (as _cov_clip)"""
+        keep = []
         dev = _is_torch(res["s_tid"])
         a = len(res["s_tid"])
-        cap = a + len(table) if cap_intervals is None else int(cap_intervals)
+        cap = a if cap is None else cap
         own = {k: _grown(v, cap) for k, v in res.items() if k[:2] == "s_"}
 
         def ptr(name, dt):
@@ -623,11 +592,20 @@ class Context:
         o = _lib.SampleOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, cap, ptr("s_tid", np.int32), ptr("s_start", np.int32), ptr("s_end", np.int32),
                            ptr("s_count", np.int64), ptr("s_heat", np.float32), a)
         self._order_after_torch(dev)
-        self._check_grow(self.L.tbk_sample_clip_regions(self.h, C.byref(o), C.byref(u)), "tbk_sample_clip_regions", o, own)
+        self._check_grow(getattr(self.L, name)(self.h, C.byref(o), *sel), name, o, own)
         m = int(o.n_intervals)
         out = {k: v[:m] for k, v in own.items()}
         out["n_sample"] = m
         return out
+
+    def sample_clip(self, res, tid, beg, end):
+        """tbk_sample_clip: the result dict of sample() cut to [beg, end) on tid, as a new dict"""
+        return self._sample_clip("tbk_sample_clip", res, (int(tid), int(beg), int(end)), None)
+
+    def sample_clip_regions(self, res, table, cap_intervals=None):
+        """tbk_sample_clip_regions: the result dict of sample() cut to the table, as a new dict (capacity and TBK_E2BIG as cov_clip_regions)"""
+        u, _keep = _regions(table)
+        return self._sample_clip("tbk_sample_clip_regions", res, (C.byref(u),), len(res["s_tid"]) + len(table) if cap_intervals is None else int(cap_intervals))
 
     def _check_grow(self, rc, what, o, own):
         if rc == -4:

@@ -52,6 +52,106 @@ static int count_regions_file_opts(int argc, char** argv) {
   return count_value_option(argc, argv, "regions-file", 'R', value_longs, "csjr");
 }
 
+// ---- what every run does with its records: the tracks -----------------------------------------------------------------------------
+// file names and header lines: tracks.cpp (tiecov.cpp:365-402)
+static void open_tracks(tbh::TrackFiles& tf, sam_hdr_t* hdr, const std::string& covfname, const std::string& jfname, const std::string& sfname, bool bigwig) {
+  std::vector<std::string> names;
+  std::vector<uint32_t> lens;
+  for (int t = 0; t < hdr->n_targets; ++t) {
+    names.push_back(hdr->target_name[t]);
+    lens.push_back(hdr->target_len[t]);
+  }
+  tf.open(covfname, jfname, sfname, bigwig, names, lens);
+}
+
+// the cut of a region run: the table, through the one-region entries (one: the table is the region itself, which may be empty) or the
+// table entries
+struct TrackClip {
+  const tbk_regions* U;
+  bool one;
+};
+
+// The rows of tbk_coverage_tile / tbk_sample_tile for `in` (host arrays, or a device view), cut to *clip where one is given, into the
+// open files of tf.  An input of no records goes the same way: the calls give no rows and status 0.
+static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int num_samples, tbh::TrackFiles& tf, const TrackClip* clip) {
+  const size_t n = in.n_records, co = in.n_cigar_ops;
+  const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
+  FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
+  const bool cov_bw = tf.cov_bw;
+  int rc = 0;
+  if (coutf || cov_bw || joutf) {
+    const size_t ci = (coutf || cov_bw) ? 2 * co + 2 * n + 16 + extra : 0, cj = joutf ? co + 16 : 0;
+    std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
+    std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
+    std::vector<uint8_t> jstr(cj ? cj : 1);
+    tbk_cov_out o;
+    memset(&o, 0, sizeof(o));
+    o.mem = TBK_MEM_HOST;
+    o.cap_intervals = (uint32_t)ci;
+    o.iv_tid = it.data();
+    o.iv_start = is.data();
+    o.iv_end = ie.data();
+    o.iv_val = iv.data();
+    o.cap_junctions = (uint32_t)cj;
+    o.j_tid = jt.data();
+    o.j_start = js.data();
+    o.j_end = je.data();
+    o.j_strand = jstr.data();
+    o.j_val = jv.data();
+    rc = tbk_coverage_tile(ctx, &in, &o);
+    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+    if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+    if (clip) {
+      const tbk_regions* U = clip->U;
+      rc = clip->one ? tbk_cov_clip(ctx, &o, U->tid[0], U->beg[0], U->end[0]) : tbk_cov_clip_regions(ctx, &o, U);
+      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+    }
+    if (coutf) tbh::emit_cov_lines(coutf, hdr->target_name, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());  // flushCoverage, tiecov.cpp:237
+    if (cov_bw) {  // flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the same intervals, the value as a float
+      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
+      tf.close_bigwig();
+    }
+    if (joutf)  // CJunc::write, tiecov.cpp:91-95 (numbered from 1)
+      tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
+  }
+  if (soutf) {
+    // the value of the track changes only where an M segment starts or ends: at most 2 intervals per CIGAR operation + 2 per
+    // record, as for the coverage track (not one per covered base); if a call still reports TBK_E2BIG it also reports the
+    // count it needs, and the call is repeated with that
+    size_t cs = 2 * co + 2 * n + 16 + extra;
+    std::vector<int32_t> st, ss, se;
+    std::vector<int64_t> sc;
+    std::vector<float> sh;
+    tbk_sample_out so;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      st.resize(cs);
+      ss.resize(cs);
+      se.resize(cs);
+      sc.resize(cs);
+      sh.resize(cs);
+      memset(&so, 0, sizeof(so));
+      so.mem = TBK_MEM_HOST;
+      so.cap_intervals = (uint32_t)cs;
+      so.iv_tid = st.data();
+      so.iv_start = ss.data();
+      so.iv_end = se.data();
+      so.iv_count = sc.data();
+      so.iv_heat = sh.data();
+      rc = tbk_sample_tile(ctx, &in, num_samples, &so);
+      if (rc != TBK_E2BIG) break;
+      cs = (size_t)so.n_intervals + 16 + extra;
+    }
+    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+    if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+    if (clip) {
+      const tbk_regions* U = clip->U;
+      rc = clip->one ? tbk_sample_clip(ctx, &so, U->tid[0], U->beg[0], U->end[0]) : tbk_sample_clip_regions(ctx, &so, U);
+      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+    }
+    tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
+  }
+}
+
 // The run of -r (one: U is the region itself, which may be empty, and goes through the one-region entries) and of -R (U is the
 // normalised table of the BED file, through the table entries): every other statement is shared.
 static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::RegionTable& U, bool one, const std::string& index_file,
@@ -61,8 +161,6 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   // every refusal comes before an output file exists
   std::string err;
-  const int32_t rtid = U.tid[0];
-  const int64_t beg = U.beg[0], end = U.end[0];
   const uint32_t R = (uint32_t)U.n();
   tbk_regions regs;
   regs.n = R, regs.tid = U.tid.data(), regs.beg = U.beg.data(), regs.end = U.end.data();
@@ -101,91 +199,15 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
   if (rc != 0) GError("Error: could not decode the chunks of %s the index names (%s %s): is the index the file's own?\n", infname.c_str(), tbk_strerror(rc), tbk_last_error(ctx));
   tbk_cov_in in;
   uint32_t n_kept = 0;
-  rc = one ? tbk_region_view(ctx, &tile, tag_seen, rtid, beg, end, &in, &n_kept) : tbk_regions_view(ctx, &tile, tag_seen, &regs, &in, &n_kept);
+  rc = one ? tbk_region_view(ctx, &tile, tag_seen, U.tid[0], U.beg[0], U.end[0], &in, &n_kept) : tbk_regions_view(ctx, &tile, tag_seen, &regs, &in, &n_kept);
   if (rc == TBK_E2BIG) GError("Error: input too large for one tile\n");
   if (rc != 0) GError("Error: GPU region filter failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
   const double ms_decode = ms();
-  const size_t n = in.n_records, co = in.n_cigar_ops;
-  // file names and header lines as without -r (tracks.cpp)
+  // file names and header lines as without -r
   tbh::TrackFiles tf;
-  {
-    std::vector<std::string> names;
-    std::vector<uint32_t> lens;
-    for (int t = 0; t < hdr->n_targets; ++t) {
-      names.push_back(hdr->target_name[t]);
-      lens.push_back(hdr->target_len[t]);
-    }
-    tf.open(covfname, jfname, sfname, bigwig, names, lens);
-  }
-  FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
-  const bool cov_bw = tf.cov_bw;
-  if (coutf || cov_bw || joutf) {
-    // (a clip over a table can grow the interval rows by R - 1: the arrays are sized with R added)
-    const size_t ci = (coutf || cov_bw) ? 2 * co + 2 * n + 16 + R : 0, cj = joutf ? co + 16 : 0;
-    std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
-    std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
-    std::vector<uint8_t> jstr(cj ? cj : 1);
-    tbk_cov_out o;
-    memset(&o, 0, sizeof(o));
-    o.mem = TBK_MEM_HOST;
-    o.cap_intervals = (uint32_t)ci;
-    o.iv_tid = it.data();
-    o.iv_start = is.data();
-    o.iv_end = ie.data();
-    o.iv_val = iv.data();
-    o.cap_junctions = (uint32_t)cj;
-    o.j_tid = jt.data();
-    o.j_start = js.data();
-    o.j_end = je.data();
-    o.j_strand = jstr.data();
-    o.j_val = jv.data();
-    if (n) {
-      rc = tbk_coverage_tile(ctx, &in, &o);
-      if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
-      if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-      rc = one ? tbk_cov_clip(ctx, &o, rtid, beg, end) : tbk_cov_clip_regions(ctx, &o, &regs);
-      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-    }
-    if (coutf) tbh::emit_cov_lines(coutf, hdr->target_name, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
-    if (cov_bw) {
-      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
-      tf.close_bigwig();
-    }
-    if (joutf) tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);  // (numbered from 1)
-  }
-  if (soutf) {
-    size_t cs = 2 * co + 2 * n + 16 + R;
-    std::vector<int32_t> st, ss, se;
-    std::vector<int64_t> sc;
-    std::vector<float> sh;
-    tbk_sample_out so;
-    memset(&so, 0, sizeof(so));
-    for (int attempt = 0; n && attempt < 2; ++attempt) {
-      st.resize(cs);
-      ss.resize(cs);
-      se.resize(cs);
-      sc.resize(cs);
-      sh.resize(cs);
-      memset(&so, 0, sizeof(so));
-      so.mem = TBK_MEM_HOST;
-      so.cap_intervals = (uint32_t)cs;
-      so.iv_tid = st.data();
-      so.iv_start = ss.data();
-      so.iv_end = se.data();
-      so.iv_count = sc.data();
-      so.iv_heat = sh.data();
-      rc = tbk_sample_tile(ctx, &in, num_samples, &so);
-      if (rc != TBK_E2BIG) break;
-      cs = (size_t)so.n_intervals + 16 + R;
-    }
-    if (n) {
-      if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
-      if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-      rc = one ? tbk_sample_clip(ctx, &so, rtid, beg, end) : tbk_sample_clip_regions(ctx, &so, &regs);
-      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-    }
-    tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());
-  }
+  open_tracks(tf, hdr, covfname, jfname, sfname, bigwig);
+  const TrackClip clip{&regs, one};
+  write_tracks(ctx, hdr, in, num_samples, tf, &clip);
   tf.close();
   if (timing)
     fprintf(stderr, "tiecov %s phases ms: %u regions | index %.1f | chunk reads %.1f (%llu bytes in %u chunks) | context up at %.1f | decode + filter %.1f (%u of %u records) | tracks %.1f\n",
@@ -252,19 +274,9 @@ int main(int argc, char* argv[]) {
   }
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;
-  {
-    std::vector<std::string> names;
-    std::vector<uint32_t> lens;
-    for (int t = 0; t < hdr->n_targets; ++t) {
-      names.push_back(hdr->target_name[t]);
-      lens.push_back(hdr->target_len[t]);
-    }
-    tf.open(covfname, jfname, sfname, bigwig, names, lens);
-  }
-  FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
-  const bool cov_bw = tf.cov_bw;
+  open_tracks(tf, hdr, covfname, jfname, sfname, bigwig);
   int num_samples = 0;
-  if (soutf) {  // load_sample_info (commons.h:47-71)
+  if (tf.samp) {  // load_sample_info (commons.h:47-71)
     num_samples = (int)hdr->co_samples().size();
     if (num_samples == 0) GError("Error: no sample lines found in header");
   }
@@ -341,67 +353,7 @@ int main(int argc, char* argv[]) {
   in.yc = yc.data();
   in.strand = strand.data();
   in.yx = yx.data();
-  if (coutf || cov_bw || joutf) {
-    size_t ci = (coutf || cov_bw) ? 2 * (size_t)co + 2 * n + 16 : 0, cj = joutf ? (size_t)co + 16 : 0;
-    std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
-    std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
-    std::vector<uint8_t> jstr(cj ? cj : 1);
-    tbk_cov_out o;
-    memset(&o, 0, sizeof(o));
-    o.mem = TBK_MEM_HOST;
-    o.cap_intervals = (uint32_t)ci;
-    o.iv_tid = it.data();
-    o.iv_start = is.data();
-    o.iv_end = ie.data();
-    o.iv_val = iv.data();
-    o.cap_junctions = (uint32_t)cj;
-    o.j_tid = jt.data();
-    o.j_start = js.data();
-    o.j_end = je.data();
-    o.j_strand = jstr.data();
-    o.j_val = jv.data();
-    rc = tbk_coverage_tile(ctx, &in, &o);
-    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
-    if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-    if (coutf) tbh::emit_cov_lines(coutf, hdr->target_name, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());  // flushCoverage, tiecov.cpp:237
-    if (cov_bw) {  // flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the same intervals, the value as a float
-      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
-      tf.close_bigwig();
-    }
-    if (joutf)  // CJunc::write, tiecov.cpp:91-95
-      tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
-  }
-  if (soutf) {
-    // the value of the track changes only where an M segment starts or ends: at most 2 intervals per CIGAR operation + 2 per
-    // record, as for the coverage track (not one per covered base); if a call still reports TBK_E2BIG it also reports the
-    // count it needs, and the call is repeated with that
-    size_t cs = 2 * (size_t)co + 2 * (size_t)n + 16;
-    std::vector<int32_t> st, ss, se;
-    std::vector<int64_t> sc;
-    std::vector<float> sh;
-    tbk_sample_out so;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      st.resize(cs);
-      ss.resize(cs);
-      se.resize(cs);
-      sc.resize(cs);
-      sh.resize(cs);
-      memset(&so, 0, sizeof(so));
-      so.mem = TBK_MEM_HOST;
-      so.cap_intervals = (uint32_t)cs;
-      so.iv_tid = st.data();
-      so.iv_start = ss.data();
-      so.iv_end = se.data();
-      so.iv_count = sc.data();
-      so.iv_heat = sh.data();
-      rc = tbk_sample_tile(ctx, &in, num_samples, &so);
-      if (rc != TBK_E2BIG) break;
-      cs = (size_t)so.n_intervals + 16;
-    }
-    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
-    if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
-    tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
-  }
+  write_tracks(ctx, hdr, in, num_samples, tf, nullptr);
   tf.close();
   tbk_destroy(ctx);
   return 0;

@@ -1,25 +1,27 @@
-// region.hip — the device side of `tiecov -r`: the records of a decoded tile that overlap a region as tiecov's input
-// view (tbk_region_view), and the rows of a coverage / sample call cut to the region (tbk_cov_clip, tbk_sample_clip); and of `tiebrush -r`
-// (DESIGN.md §4f): the same records as a collapse tile (tbk_tile_region, at the end of this file).
+// region.hip — the device side of `tiecov -r` / `-R`: the records of a decoded tile that overlap a region table U
+// as tiecov's input view (tbk_region_view, tbk_regions_view), and the rows of a coverage / sample call cut to U (tbk_cov_clip,
+// tbk_sample_clip and their _regions forms); and of `tiebrush -r` / `-R`: the same records as a collapse tile
+// (tbk_tile_region, tbk_tile_regions, at the end of this file).
+//
+// There is ONE path: a table of R sorted, disjoint intervals on the device.  A one-region entry builds the table of its one interval
+// (which, unlike a caller's table, may be empty) and runs what the table entry runs; the two families differ in their extern "C"
+// wrappers' argument checks and nowhere else.
 //
 // The reference has no region option (tiecov.cpp walks the whole file); the contract is that the rows equal the whole-file run's rows
 // on the region, bit for bit.  These are bandwidth-trivial passes of one thread per record or row, each kernel a launch of its own
 // (no hand-off between workgroups inside a launch); what can go wrong is at the edges: n = 0, the last partial wave, an end beyond 2^31.
-//   rv_flag_k      keep[i] = tid == rtid && pos < end && rec_end > beg, rec_end by the index's rule (pos + the CIGAR's reference length
-//                  over M D N = X, pos + 1 when that is 0); kcig[i] = the kept record's CIGAR count
+//   rs_flag_k      keep[i] = the record overlaps any interval of U, by ONE bisection of U per record (the first interval that ends
+//                  behind pos decides); rec_end by the index's rule (pos + the CIGAR's reference length over M D N = X, pos + 1 when
+//                  that is 0); kcig[i] = the kept record's CIGAR count
 //   two exclusive scans (tbk_exscan_u32) over keep and kcig, n + 1 elements each: the last ones are the totals
 //   rv_scatter_k   the compacted tid / pos / flag / strand / yc / yx, the CSR cig_off and the gathered CIGAR words, in file order
-//   clip_bisect_k  interval rows are sorted and disjoint: the rows of the region are one range, found by two bisections
-//   clip_cov_k / clip_samp_k   that range, its rows trimmed to the region, into scratch (then copied over the caller's rows)
-//   clip_jflag_k / clip_jscat_k   junction rows are only sorted inside a bundle: keep flag, scan, scatter; rows are not trimmed
-//
-// The same four entries for a region TABLE U (`tiecov -R` / `tiebrush -R`, DESIGN.md §4g: tbk_regions_view, tbk_cov_clip_regions,
-// tbk_sample_clip_regions, tbk_tile_regions) share every host statement with their one-region siblings; only these kernels differ:
-//   rs_flag_k      rv_flag_k's keep / kcig by ONE bisection of U per record (the first interval that ends behind pos decides "overlaps any")
 //   clip_order_k   interval rows that are not sorted and disjoint are refused (they could overflow the scan below)
-//   clip_mrange_k  clip_bisect_k's two bisections, a thread per interval of U: first[r], count[r]; a scan of the counts: off[r], m
-//   clip_mcov_k / clip_msamp_k   a thread per OUTPUT row: its interval by a bisection of off, its source row, trimmed to that interval
-//   clip_mjflag_k  a junction row is kept when it overlaps any interval: the same single probe of U
+//   clip_mrange_k  interval rows are sorted and disjoint: the rows of an interval of U are one range, found by two bisections, a thread
+//                  per interval: first[r], count[r]; a scan of the counts: off[r], m
+//   clip_rows_k    a thread per OUTPUT row: its interval by a bisection of off, its source row, trimmed to that interval, into scratch
+//                  (then copied over the caller's rows); one template for the coverage rows (val) and the sample rows (count, heat)
+//   clip_mjflag_k / clip_jscat_k   junction rows are only sorted inside a bundle: keep flag (rs_flag_k's single probe of U), scan,
+//                  scatter; rows are not trimmed
 #include "dev_common.hpp"
 #include "tbk_internal.h"
 
@@ -37,22 +39,8 @@ __device__ __forceinline__ int64_t rec_end_of(int64_t p, const uint32_t* __restr
   return p + (rl ? rl : 1);
 }
 
-__global__ __launch_bounds__(RG_NT) void rv_flag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ pos,
-                                                   const uint32_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, int32_t rtid, int64_t beg,
-                                                   int64_t end, uint32_t* __restrict__ keep /* [n + 1] */, uint32_t* __restrict__ kcig /* [n + 1] */) {
-  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
-  if (i > n) return;
-  uint32_t k = 0, kc = 0;
-  if (i < n && tid[i] == rtid) {
-    const uint32_t c0 = cig_off[i], nc = cig_off[i + 1] - c0;
-    const int64_t p = pos[i], e = rec_end_of(p, cig, c0, nc);
-    if (p < end && e > beg) k = 1, kc = nc;
-  }
-  keep[i] = k;
-  kcig[i] = kc;
-}
-
-// ---- a region table U on the device: R sorted, disjoint, non-empty, non-adjacent intervals, in global memory ----------
+// ---- a region table U on the device: R >= 1 sorted, disjoint, non-adjacent intervals in global memory; a caller's table
+// has no empty interval, the table of a one-region entry may be one ----------------------------------------------------------------------
 struct RegTab {
   uint32_t n;
   const int32_t* tid;
@@ -60,7 +48,7 @@ struct RegTab {
 };
 // the first interval with (tid, end) > (t, p) in lexicographic order (n: none).  U is disjoint and sorted, so its ends ascend with its
 // begins: every interval before that one ends at or before p, every one behind it begins later than it does — [p, e) on t overlaps ANY
-// interval exactly when that one lies on t and begins before e.
+// interval exactly when that one lies on t and begins before e.  (The one empty interval [b, b): found when p < b, met when b < e.)
 __device__ __forceinline__ uint32_t tab_probe(const RegTab& U, int32_t t, int64_t p) {
   uint32_t lo = 0, hi = U.n;
   while (lo < hi) {
@@ -78,8 +66,7 @@ __device__ __forceinline__ bool tab_overlaps(const RegTab& U, int32_t t, int64_t
   return r < U.n && U.tid[r] == t && U.beg[r] < e;
 }
 
-// rv_flag_k for a table: the same keep / kcig, so everything behind the flags runs unchanged.  Records arrive in file order: the probes of
-// a wave fall on a few neighbouring entries of the table, which stays in global memory.
+// Records arrive in file order: the probes of a wave fall on a few neighbouring entries of the table, which stays in global memory.
 __global__ __launch_bounds__(RG_NT) void rs_flag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ pos,
                                                    const uint32_t* __restrict__ cig_off, const uint32_t* __restrict__ cig, RegTab U,
                                                    uint32_t* __restrict__ keep /* [n + 1] */, uint32_t* __restrict__ kcig /* [n + 1] */) {
@@ -132,71 +119,10 @@ __global__ __launch_bounds__(RG_NT) void rv_scatter_k(uint32_t n, const uint32_t
   for (uint32_t q = 0; q < nc; ++q) O.cig[d + q] = cig[c0 + q];
 }
 
-// res[0] = the first row that ends behind beg on rtid (or lies on a later reference), res[1] = the first row that starts at or behind
-// end on rtid (or lies on a later reference): rows [res[0], res[1]) are the region's
-__global__ void clip_bisect_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv, int32_t rtid,
-                              int64_t beg, int64_t end, uint32_t* __restrict__ res) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t m = lo + (hi - lo) / 2;
-    if (tid[m] > rtid || (tid[m] == rtid && (int64_t)endv[m] > beg))
-      hi = m;
-    else
-      lo = m + 1;
-  }
-  const uint32_t first = lo;
-  hi = n;
-  while (lo < hi) {
-    const uint32_t m = lo + (hi - lo) / 2;
-    if (tid[m] > rtid || (tid[m] == rtid && (int64_t)start[m] >= end))
-      hi = m;
-    else
-      lo = m + 1;
-  }
-  res[0] = first;
-  res[1] = lo;
-}
-
-__device__ __forceinline__ int32_t clip_lo(int32_t s, int64_t beg) { return (int64_t)s < beg ? (int32_t)beg : s; }
-__device__ __forceinline__ int32_t clip_hi(int32_t e, int64_t end) { return (int64_t)e > end ? (int32_t)end : e; }
-
-__global__ __launch_bounds__(RG_NT) void clip_cov_k(uint32_t m, uint32_t first, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
-                                                    const int32_t* __restrict__ endv, const double* __restrict__ val, int64_t beg, int64_t end,
-                                                    int32_t* __restrict__ o_tid, int32_t* __restrict__ o_start, int32_t* __restrict__ o_end,
-                                                    double* __restrict__ o_val) {
-  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
-  if (i >= m) return;
-  const uint64_t s = (uint64_t)first + i;
-  o_tid[i] = tid[s];
-  o_start[i] = clip_lo(start[s], beg);
-  o_end[i] = clip_hi(endv[s], end);
-  o_val[i] = val[s];
-}
-__global__ __launch_bounds__(RG_NT) void clip_samp_k(uint32_t m, uint32_t first, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
-                                                     const int32_t* __restrict__ endv, const int64_t* __restrict__ cnt, const float* __restrict__ heat,
-                                                     int64_t beg, int64_t end, int32_t* __restrict__ o_tid, int32_t* __restrict__ o_start,
-                                                     int32_t* __restrict__ o_end, int64_t* __restrict__ o_cnt, float* __restrict__ o_heat) {
-  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
-  if (i >= m) return;
-  const uint64_t s = (uint64_t)first + i;
-  o_tid[i] = tid[s];
-  o_start[i] = clip_lo(start[s], beg);
-  o_end[i] = clip_hi(endv[s], end);
-  o_cnt[i] = cnt[s];
-  o_heat[i] = heat[s];
-}
-
-__global__ __launch_bounds__(RG_NT) void clip_jflag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
-                                                      const int32_t* __restrict__ endv, int32_t rtid, int64_t beg, int64_t end,
-                                                      uint32_t* __restrict__ keep /* [n + 1] */) {
-  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
-  if (i > n) return;
-  keep[i] = (i < n && tid[i] == rtid && (int64_t)start[i] < end && (int64_t)endv[i] > beg) ? 1u : 0u;
-}
-// ---- the clips over a table: an interval row may come out once per interval of U that it meets, so the rows can grow (m <= n + R - 1) ----
-// clip_bisect_k's two bisections, a thread per interval r of U: rows [first[r], first[r] + count[r]) meet interval r; count[R] = 0 closes
-// the scan.  The second bisection starts at the first one's result: first + count <= n whatever the rows' order.
+// ---- the clips: an interval row may come out once per interval of U that it meets, so the rows can grow (m <= n + R - 1) ----
+// A thread per interval r of U: first[r] = the first row that ends behind beg on its reference (or lies on a later one), then the first
+// row that starts at or behind end there (or lies on a later one): rows [first[r], first[r] + count[r]) meet interval r; count[R] = 0
+// closes the scan.  The second bisection starts at the first one's result: first + count <= n whatever the rows' order.
 __global__ __launch_bounds__(RG_NT) void clip_mrange_k(RegTab U, uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
                                                        const int32_t* __restrict__ endv, uint32_t* __restrict__ first /* [R] */,
                                                        uint32_t* __restrict__ count /* [R + 1] */) {
@@ -237,47 +163,34 @@ __global__ __launch_bounds__(RG_NT) void clip_order_k(uint32_t n, const int32_t*
   if (i >= n) return;
   if (endv[i] < start[i] || (i + 1 < n && (tid[i + 1] < tid[i] || (tid[i + 1] == tid[i] && start[i + 1] < endv[i])))) *bad = 1u;
 }
-// output row i -> its interval r (the last one whose scanned offset is <= i; off[R] = m > i) and its source row
-__device__ __forceinline__ uint32_t clip_mfind(uint32_t i, uint32_t R, const uint32_t* __restrict__ off, const uint32_t* __restrict__ first, uint32_t* src) {
-  uint32_t lo = 0, hi = R;  // the first r in [0, R] with off[r] > i
+
+__device__ __forceinline__ int32_t clip_lo(int32_t s, int64_t beg) { return (int64_t)s < beg ? (int32_t)beg : s; }
+__device__ __forceinline__ int32_t clip_hi(int32_t e, int64_t end) { return (int64_t)e > end ? (int32_t)end : e; }
+
+// Output row i: its interval r is the last one whose scanned offset is <= i (off[R] = m > i), its source row first[r] + (i - off[r]).
+// The payload columns ride along: a (coverage: val; sample: count) and, where the rows have a second one, b (sample: heat; else NULL).
+template <class A, class B>
+__global__ __launch_bounds__(RG_NT) void clip_rows_k(uint32_t m, RegTab U, const uint32_t* __restrict__ off /* [R + 1] */, const uint32_t* __restrict__ first,
+                                                     const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv,
+                                                     const A* __restrict__ a, const B* __restrict__ b, int32_t* __restrict__ o_tid,
+                                                     int32_t* __restrict__ o_start, int32_t* __restrict__ o_end, A* __restrict__ o_a, B* __restrict__ o_b) {
+  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
+  if (i >= m) return;
+  uint32_t lo = 0, hi = U.n;  // the first r in [0, R] with off[r] > i
   while (lo < hi) {
-    const uint32_t m = lo + (hi - lo) / 2;
-    if (off[m] > i)
-      hi = m;
+    const uint32_t mid = lo + (hi - lo) / 2;
+    if (off[mid] > i)
+      hi = mid;
     else
-      lo = m + 1;
+      lo = mid + 1;
   }
   const uint32_t r = lo - 1;  // (off[0] = 0 <= i: lo >= 1)
-  *src = first[r] + (i - off[r]);
-  return r;
-}
-__global__ __launch_bounds__(RG_NT) void clip_mcov_k(uint32_t m, RegTab U, const uint32_t* __restrict__ off /* [R + 1] */, const uint32_t* __restrict__ first,
-                                                     const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv,
-                                                     const double* __restrict__ val, int32_t* __restrict__ o_tid, int32_t* __restrict__ o_start,
-                                                     int32_t* __restrict__ o_end, double* __restrict__ o_val) {
-  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
-  if (i >= m) return;
-  uint32_t s;
-  const uint32_t r = clip_mfind((uint32_t)i, U.n, off, first, &s);
+  const uint32_t s = first[r] + ((uint32_t)i - off[r]);
   o_tid[i] = tid[s];
   o_start[i] = clip_lo(start[s], U.beg[r]);
   o_end[i] = clip_hi(endv[s], U.end[r]);
-  o_val[i] = val[s];
-}
-__global__ __launch_bounds__(RG_NT) void clip_msamp_k(uint32_t m, RegTab U, const uint32_t* __restrict__ off, const uint32_t* __restrict__ first,
-                                                      const int32_t* __restrict__ tid, const int32_t* __restrict__ start, const int32_t* __restrict__ endv,
-                                                      const int64_t* __restrict__ cnt, const float* __restrict__ heat, int32_t* __restrict__ o_tid,
-                                                      int32_t* __restrict__ o_start, int32_t* __restrict__ o_end, int64_t* __restrict__ o_cnt,
-                                                      float* __restrict__ o_heat) {
-  const uint64_t i = (uint64_t)blockIdx.x * RG_NT + threadIdx.x;
-  if (i >= m) return;
-  uint32_t s;
-  const uint32_t r = clip_mfind((uint32_t)i, U.n, off, first, &s);
-  o_tid[i] = tid[s];
-  o_start[i] = clip_lo(start[s], U.beg[r]);
-  o_end[i] = clip_hi(endv[s], U.end[r]);
-  o_cnt[i] = cnt[s];
-  o_heat[i] = heat[s];
+  o_a[i] = a[s];
+  if (b) o_b[i] = b[s];
 }
 // a junction row is kept when it overlaps any interval of U: rs_flag_k's one probe, with j_start / j_end
 __global__ __launch_bounds__(RG_NT) void clip_mjflag_k(uint32_t n, const int32_t* __restrict__ tid, const int32_t* __restrict__ start,
@@ -328,32 +241,9 @@ struct ProfEnd {
   ~ProfEnd() { tbk_prof_end_call(c); }
 };
 
-// interval rows (tid, start, end sorted and disjoint): the range of the region -> *first, *m
-int clip_range(tbk_ctx* ctx, uint32_t n, const int32_t* d_tid, const int32_t* d_start, const int32_t* d_end, int32_t tid, int64_t beg, int64_t end,
-               uint32_t* first, uint32_t* m) {
-  uint32_t* d_res = ws_alloc<uint32_t>(ctx, 2);
-  if (!d_res) return TBK_ENOMEM;
-  TBK_LAUNCH(ctx, "clip_bisect", clip_bisect_k, 1, 64, 0, n, d_tid, d_start, d_end, tid, beg, end, d_res);
-  uint32_t res[2] = {0, 0};
-  TBK_HIP(hipMemcpyAsync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, ctx->stream));
-  TBK_HIP(hipStreamSynchronize(ctx->stream));
-  if (res[0] > res[1] || res[1] > n) {  // (rows that are not sorted)
-    ctx->last_error = "clip: interval rows are not sorted by reference and start";
-    return TBK_EINVAL;
-  }
-  *first = res[0];
-  *m = res[1] - res[0];
-  return 0;
-}
-
-// what an entry selects by: one region, or (U != NULL) a table — the one-region entries and their table siblings share every statement
-// but the flag / range kernels
-struct Sel {
-  const tbk_regions* U;
-  int32_t tid;
-  int64_t beg, end;
-};
-// sorted by (tid, beg), disjoint, non-empty, non-adjacent; n >= 1, tid >= 0, beg >= 0 (checked on the host before anything is launched)
+// a one-region entry's region; it may be empty (`-r` of a BEG behind the reference's end gives one)
+bool region_ok(int32_t tid, int64_t beg, int64_t end) { return tid >= 0 && beg >= 0 && end >= beg; }
+// a caller's table: sorted by (tid, beg), disjoint, non-empty, non-adjacent; n >= 1, tid >= 0, beg >= 0
 bool regions_ok(const tbk_regions* U) {
   if (!U || U->n == 0 || !U->tid || !U->beg || !U->end) return false;
   for (uint32_t r = 0; r < U->n; ++r) {
@@ -362,36 +252,41 @@ bool regions_ok(const tbk_regions* U) {
   }
   return true;
 }
-bool sel_ok(const Sel& s) { return s.U ? regions_ok(s.U) : (s.tid >= 0 && s.beg >= 0 && s.end >= s.beg); }
-size_t tab_bytes(const Sel& s) { return s.U ? (size_t)s.U->n * 32 + 4096 : 0; }  // (the table and, for the clips, first / count / off)
+// The implementations below take a table that its wrapper has checked (on the host, before anything is launched or changed).
+size_t tab_bytes(const tbk_regions& U) { return (size_t)U.n * 32 + 4096; }  // (the table and, for the clips, first / count / off)
 
 // the device form of U, uploaded once per call into the workspace (after the call's tbk_ws_reserve)
-int tab_upload(tbk_ctx* ctx, const tbk_regions* U, RegTab* T) {
-  int32_t* t = ws_alloc<int32_t>(ctx, U->n);
-  int64_t *b = ws_alloc<int64_t>(ctx, U->n), *e = ws_alloc<int64_t>(ctx, U->n);
+int tab_upload(tbk_ctx* ctx, const tbk_regions& U, RegTab* T) {
+  int32_t* t = ws_alloc<int32_t>(ctx, U.n);
+  int64_t *b = ws_alloc<int64_t>(ctx, U.n), *e = ws_alloc<int64_t>(ctx, U.n);
   if (!t || !b || !e) return TBK_ENOMEM;
-  TBK_HIP(hipMemcpyAsync(t, U->tid, (size_t)U->n * 4, hipMemcpyHostToDevice, ctx->stream));
-  TBK_HIP(hipMemcpyAsync(b, U->beg, (size_t)U->n * 8, hipMemcpyHostToDevice, ctx->stream));
-  TBK_HIP(hipMemcpyAsync(e, U->end, (size_t)U->n * 8, hipMemcpyHostToDevice, ctx->stream));
-  T->n = U->n, T->tid = t, T->beg = b, T->end = e;
+  TBK_HIP(hipMemcpyAsync(t, U.tid, (size_t)U.n * 4, hipMemcpyHostToDevice, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(b, U.beg, (size_t)U.n * 8, hipMemcpyHostToDevice, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(e, U.end, (size_t)U.n * 8, hipMemcpyHostToDevice, ctx->stream));
+  T->n = U.n, T->tid = t, T->beg = b, T->end = e;
   return 0;
 }
 
-// keep / kcig of the tile's records for the selection
-int flag_records(tbk_ctx* ctx, const Sel& s, uint32_t n, const int32_t* tid, const int32_t* pos, const uint32_t* cig_off, const uint32_t* cig, uint32_t* keep,
-                 uint32_t* kcig) {
-  const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
-  if (s.U) {
-    RegTab T;
-    TBK_TRY(tab_upload(ctx, s.U, &T));
-    TBK_LAUNCH(ctx, "regions_flag", rs_flag_k, grid, RG_NT, 0, n, tid, pos, cig_off, cig, T, keep, kcig);
-  } else {
-    TBK_LAUNCH(ctx, "region_flag", rv_flag_k, grid, RG_NT, 0, n, tid, pos, cig_off, cig, s.tid, s.beg, s.end, keep, kcig);
-  }
+// the opening of tbk_region_view and tbk_tile_region: keep / kcig of the tile's n records against U and their exclusive scans koff / coff,
+// n + 1 elements each in the workspace (the last ones are the totals; the caller reads them with whatever else it scans)
+struct Kept {
+  uint32_t *keep, *kcig, *koff, *coff;
+};
+int flag_and_scan(tbk_ctx* ctx, const tbk_regions& U, uint32_t n, const int32_t* tid, const int32_t* pos, const uint32_t* cig_off, const uint32_t* cig, Kept* K) {
+  K->keep = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  K->kcig = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  K->koff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  K->coff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  if (!K->keep || !K->kcig || !K->koff || !K->coff) return TBK_ENOMEM;
+  RegTab T;
+  TBK_TRY(tab_upload(ctx, U, &T));
+  TBK_LAUNCH(ctx, "regions_flag", rs_flag_k, cdiv((uint64_t)n + 1, RG_NT), RG_NT, 0, n, tid, pos, cig_off, cig, T, K->keep, K->kcig);
+  TBK_TRY(tbk_exscan_u32(ctx, K->keep, K->koff, n + 1, nullptr));
+  TBK_TRY(tbk_exscan_u32(ctx, K->kcig, K->coff, n + 1, nullptr));
   return 0;
 }
 
-// interval rows against a table: *m output rows, row i from source row first[r] + (i - off[r]) of the interval r that off places it in
+// interval rows against the table: *m output rows, row i from source row first[r] + (i - off[r]) of the interval r that off places it in
 int clip_mrange(tbk_ctx* ctx, const RegTab& T, uint32_t n, const int32_t* d_tid, const int32_t* d_start, const int32_t* d_end, uint32_t** first, uint32_t** off,
                 uint64_t* m) {
   const uint32_t R = T.n;
@@ -419,8 +314,41 @@ int clip_mrange(tbk_ctx* ctx, const RegTab& T, uint32_t n, const int32_t* d_tid,
   return 0;
 }
 
-int region_view_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, const Sel& sel, tbk_cov_in* view, uint32_t* n_kept) {
-  if (!ctx || !tile || !view || !n_kept || tile->mem != TBK_MEM_DEVICE || !sel_ok(sel)) return TBK_EINVAL;
+// The interval rows of a clip, n >= 1 of them in the caller's arrays (mem HOST or DEVICE; cap elements each), cut to the table in place:
+// *n_rows becomes the count that comes out.  When that exceeds cap nothing is written, *n_rows is the count needed and the call is
+// TBK_E2BIG.  a and b are the payload columns (b NULL: the rows have one).
+template <class A, class B>
+int clip_intervals(tbk_ctx* ctx, const RegTab& T, int mem, uint32_t n, uint32_t cap, uint32_t* n_rows, int32_t* tid, int32_t* start, int32_t* end, A* a, B* b) {
+  const int32_t *d_tid, *d_start, *d_end;
+  const A* d_a;
+  const B* d_b = nullptr;
+  TBK_TRY(rows_in(ctx, mem, tid, n, &d_tid));
+  TBK_TRY(rows_in(ctx, mem, start, n, &d_start));
+  TBK_TRY(rows_in(ctx, mem, end, n, &d_end));
+  TBK_TRY(rows_in(ctx, mem, a, n, &d_a));
+  if (b) TBK_TRY(rows_in(ctx, mem, b, n, &d_b));
+  uint32_t *first = nullptr, *off = nullptr;
+  uint64_t m = 0;
+  TBK_TRY(clip_mrange(ctx, T, n, d_tid, d_start, d_end, &first, &off, &m));
+  *n_rows = (uint32_t)m;
+  if (m > cap) return TBK_E2BIG;  // the rows grew beyond the caller's arrays
+  if (!m) return 0;
+  int32_t *s_tid = ws_alloc<int32_t>(ctx, m), *s_start = ws_alloc<int32_t>(ctx, m), *s_end = ws_alloc<int32_t>(ctx, m);
+  A* s_a = ws_alloc<A>(ctx, m);
+  B* s_b = b ? ws_alloc<B>(ctx, m) : nullptr;
+  if (!s_tid || !s_start || !s_end || !s_a || (b && !s_b)) return TBK_ENOMEM;
+  TBK_LAUNCH(ctx, "clip_rows", (clip_rows_k<A, B>), cdiv(m, RG_NT), RG_NT, 0, (uint32_t)m, T, off, first, d_tid, d_start, d_end, d_a, d_b, s_tid, s_start, s_end, s_a,
+             s_b);
+  TBK_TRY(rows_out(ctx, mem, tid, s_tid, m));
+  TBK_TRY(rows_out(ctx, mem, start, s_start, m));
+  TBK_TRY(rows_out(ctx, mem, end, s_end, m));
+  TBK_TRY(rows_out(ctx, mem, a, s_a, m));
+  if (b) TBK_TRY(rows_out(ctx, mem, b, s_b, m));
+  return 0;
+}
+
+int region_view_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, const tbk_regions& U, tbk_cov_in* view, uint32_t* n_kept) {
+  if (!ctx || !tile || !view || !n_kept || tile->mem != TBK_MEM_DEVICE) return TBK_EINVAL;
   const uint32_t n = tile->n_records;
   if (n && (!tile->tid || !tile->pos || !tile->flag || !tile->strand || !tile->cig_off || (tile->n_cigar_ops && !tile->cig))) return TBK_EINVAL;
   if (n == UINT32_MAX) return TBK_E2BIG;
@@ -432,19 +360,12 @@ int region_view_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_se
   if (n == 0) return 0;
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
-  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 16 + tab_bytes(sel) + ((size_t)1 << 20)));
-  uint32_t* keep = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint32_t* kcig = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint32_t* koff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint32_t* coff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  if (!keep || !kcig || !koff || !coff) return TBK_ENOMEM;
-  const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
-  TBK_TRY(flag_records(ctx, sel, n, tile->tid, tile->pos, tile->cig_off, tile->cig, keep, kcig));
-  TBK_TRY(tbk_exscan_u32(ctx, keep, koff, n + 1, nullptr));
-  TBK_TRY(tbk_exscan_u32(ctx, kcig, coff, n + 1, nullptr));
+  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 16 + tab_bytes(U) + ((size_t)1 << 20)));
+  Kept K;
+  TBK_TRY(flag_and_scan(ctx, U, n, tile->tid, tile->pos, tile->cig_off, tile->cig, &K));
   uint32_t tot[2] = {0, 0};
-  TBK_HIP(hipMemcpyAsync(&tot[0], koff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
-  TBK_HIP(hipMemcpyAsync(&tot[1], coff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(&tot[0], K.koff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
+  TBK_HIP(hipMemcpyAsync(&tot[1], K.coff + n, 4, hipMemcpyDeviceToHost, ctx->stream));
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   const size_t nk = tot[0], nc = tot[1];  // (nc < 2^32: a subset of the tile's CIGAR words, whose count is a uint32)
   if (nk == 0) return tbk_check_launch(ctx, "region_view");
@@ -473,8 +394,8 @@ int region_view_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_se
   O.yx = (int64_t*)take(nk * 8);
   O.cig_off = (uint32_t*)take((nk + 1) * 4);
   O.cig = (uint32_t*)take(nc * 4 + 4);
-  TBK_LAUNCH(ctx, "region_scatter", rv_scatter_k, grid, RG_NT, 0, n, keep, koff, coff, tile->tid, tile->pos, tile->flag, tile->strand, tile->cig_off, tile->cig,
-             tile->yc_in, tile->yx_in, tag_seen, O);
+  TBK_LAUNCH(ctx, "region_scatter", rv_scatter_k, cdiv((uint64_t)n + 1, RG_NT), RG_NT, 0, n, K.keep, K.koff, K.coff, tile->tid, tile->pos, tile->flag, tile->strand,
+             tile->cig_off, tile->cig, tile->yc_in, tile->yx_in, tag_seen, O);
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   TBK_TRY(tbk_check_launch(ctx, "region_view"));
   view->n_records = (uint32_t)nk;
@@ -491,58 +412,24 @@ int region_view_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_se
   return 0;
 }
 
-int cov_clip_impl(tbk_ctx* ctx, tbk_cov_out* rows, const Sel& sel) {
-  if (!ctx || !rows || (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE) || !sel_ok(sel)) return TBK_EINVAL;
+int cov_clip_impl(tbk_ctx* ctx, tbk_cov_out* rows, const tbk_regions& U) {
+  if (!ctx || !rows || (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE)) return TBK_EINVAL;
   const uint32_t ni = rows->cap_intervals ? rows->n_intervals : 0, nj = rows->cap_junctions ? rows->n_junctions : 0;
   if (ni > rows->cap_intervals || nj > rows->cap_junctions || ni == UINT32_MAX || nj == UINT32_MAX) return TBK_EINVAL;
   if (ni && (!rows->iv_tid || !rows->iv_start || !rows->iv_end || !rows->iv_val)) return TBK_EINVAL;
   if (nj && (!rows->j_tid || !rows->j_start || !rows->j_end || !rows->j_strand || !rows->j_val)) return TBK_EINVAL;
   if (!ni && !nj) return 0;
-  const int32_t tid = sel.tid;
-  const int64_t beg = sel.beg, end = sel.end;
-  const size_t R = sel.U ? sel.U->n : 0;
-  if ((uint64_t)ni + R >= UINT32_MAX) return TBK_E2BIG;
+  const size_t R = U.n;
+  if ((uint64_t)ni + R - 1 >= UINT32_MAX) return TBK_E2BIG;  // (the most rows that can come out)
   TBK_HIP(hipSetDevice(ctx->device));
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
   const int mem = rows->mem;
-  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 48 + (ni ? R * 24 : 0) + tab_bytes(sel) + (size_t)nj * 64 + ((size_t)1 << 20)));
-  RegTab T{};
-  if (sel.U) TBK_TRY(tab_upload(ctx, sel.U, &T));
-  if (ni) {
-    const int32_t *d_tid, *d_start, *d_end;
-    const double* d_val;
-    TBK_TRY(rows_in(ctx, mem, rows->iv_tid, ni, &d_tid));
-    TBK_TRY(rows_in(ctx, mem, rows->iv_start, ni, &d_start));
-    TBK_TRY(rows_in(ctx, mem, rows->iv_end, ni, &d_end));
-    TBK_TRY(rows_in(ctx, mem, rows->iv_val, ni, &d_val));
-    uint32_t first = 0, m = 0, *m_first = nullptr, *m_off = nullptr;
-    if (sel.U) {
-      uint64_t mm = 0;
-      TBK_TRY(clip_mrange(ctx, T, ni, d_tid, d_start, d_end, &m_first, &m_off, &mm));
-      if (mm > rows->cap_intervals) {  // the rows grew beyond the caller's arrays: nothing is written, the count needed is reported
-        rows->n_intervals = (uint32_t)mm;
-        return TBK_E2BIG;
-      }
-      m = (uint32_t)mm;
-    } else {
-      TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
-    }
-    if (m) {
-      int32_t *s_tid = ws_alloc<int32_t>(ctx, m), *s_start = ws_alloc<int32_t>(ctx, m), *s_end = ws_alloc<int32_t>(ctx, m);
-      double* s_val = ws_alloc<double>(ctx, m);
-      if (!s_tid || !s_start || !s_end || !s_val) return TBK_ENOMEM;
-      if (sel.U)
-        TBK_LAUNCH(ctx, "clip_mcov", clip_mcov_k, cdiv(m, RG_NT), RG_NT, 0, m, T, m_off, m_first, d_tid, d_start, d_end, d_val, s_tid, s_start, s_end, s_val);
-      else
-        TBK_LAUNCH(ctx, "clip_cov", clip_cov_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_val, beg, end, s_tid, s_start, s_end, s_val);
-      TBK_TRY(rows_out(ctx, mem, rows->iv_tid, s_tid, m));
-      TBK_TRY(rows_out(ctx, mem, rows->iv_start, s_start, m));
-      TBK_TRY(rows_out(ctx, mem, rows->iv_end, s_end, m));
-      TBK_TRY(rows_out(ctx, mem, rows->iv_val, s_val, m));
-    }
-    rows->n_intervals = m;
-  }
+  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 48 + (ni ? R * 24 : 0) + tab_bytes(U) + (size_t)nj * 64 + ((size_t)1 << 20)));
+  RegTab T;
+  TBK_TRY(tab_upload(ctx, U, &T));
+  // (on TBK_E2BIG no row is touched, junction rows included, and the count needed is left in n_intervals)
+  if (ni) TBK_TRY(clip_intervals(ctx, T, mem, ni, rows->cap_intervals, &rows->n_intervals, rows->iv_tid, rows->iv_start, rows->iv_end, rows->iv_val, (float*)nullptr));
   if (nj) {
     const int32_t *d_tid, *d_start, *d_end;
     const uint8_t* d_strand;
@@ -558,10 +445,7 @@ int cov_clip_impl(tbk_ctx* ctx, tbk_cov_out* rows, const Sel& sel) {
     uint8_t* s_strand = ws_alloc<uint8_t>(ctx, nj);
     double* s_val = ws_alloc<double>(ctx, nj);
     if (!keep || !koff || !s_tid || !s_start || !s_end || !s_strand || !s_val) return TBK_ENOMEM;
-    if (sel.U)
-      TBK_LAUNCH(ctx, "clip_mjunc", clip_mjflag_k, cdiv((uint64_t)nj + 1, RG_NT), RG_NT, 0, nj, d_tid, d_start, d_end, T, keep);
-    else
-      TBK_LAUNCH(ctx, "clip_junc", clip_jflag_k, cdiv((uint64_t)nj + 1, RG_NT), RG_NT, 0, nj, d_tid, d_start, d_end, tid, beg, end, keep);
+    TBK_LAUNCH(ctx, "clip_mjunc", clip_mjflag_k, cdiv((uint64_t)nj + 1, RG_NT), RG_NT, 0, nj, d_tid, d_start, d_end, T, keep);
     TBK_TRY(tbk_exscan_u32(ctx, keep, koff, nj + 1, nullptr));
     TBK_LAUNCH(ctx, "clip_junc", clip_jscat_k, cdiv(nj, RG_NT), RG_NT, 0, nj, keep, koff, d_tid, d_start, d_end, d_strand, d_val, s_tid, s_start, s_end, s_strand,
                s_val);
@@ -580,93 +464,60 @@ int cov_clip_impl(tbk_ctx* ctx, tbk_cov_out* rows, const Sel& sel) {
   return tbk_check_launch(ctx, "cov_clip");
 }
 
-int sample_clip_impl(tbk_ctx* ctx, tbk_sample_out* rows, const Sel& sel) {
-  if (!ctx || !rows || (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE) || !sel_ok(sel)) return TBK_EINVAL;
+int sample_clip_impl(tbk_ctx* ctx, tbk_sample_out* rows, const tbk_regions& U) {
+  if (!ctx || !rows || (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE)) return TBK_EINVAL;
   const uint32_t ni = rows->n_intervals;
   if (ni > rows->cap_intervals || ni == UINT32_MAX) return TBK_EINVAL;
   if (ni && (!rows->iv_tid || !rows->iv_start || !rows->iv_end || !rows->iv_count || !rows->iv_heat)) return TBK_EINVAL;
   if (!ni) return 0;
-  const int32_t tid = sel.tid;
-  const int64_t beg = sel.beg, end = sel.end;
-  const size_t R = sel.U ? sel.U->n : 0;
-  if ((uint64_t)ni + R >= UINT32_MAX) return TBK_E2BIG;
+  const size_t R = U.n;
+  if ((uint64_t)ni + R - 1 >= UINT32_MAX) return TBK_E2BIG;  // (as in cov_clip_impl)
   TBK_HIP(hipSetDevice(ctx->device));
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
-  const int mem = rows->mem;
-  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 56 + R * 24 + tab_bytes(sel) + ((size_t)1 << 20)));
-  RegTab T{};
-  if (sel.U) TBK_TRY(tab_upload(ctx, sel.U, &T));
-  const int32_t *d_tid, *d_start, *d_end;
-  const int64_t* d_cnt;
-  const float* d_heat;
-  TBK_TRY(rows_in(ctx, mem, rows->iv_tid, ni, &d_tid));
-  TBK_TRY(rows_in(ctx, mem, rows->iv_start, ni, &d_start));
-  TBK_TRY(rows_in(ctx, mem, rows->iv_end, ni, &d_end));
-  TBK_TRY(rows_in(ctx, mem, rows->iv_count, ni, &d_cnt));
-  TBK_TRY(rows_in(ctx, mem, rows->iv_heat, ni, &d_heat));
-  uint32_t first = 0, m = 0, *m_first = nullptr, *m_off = nullptr;
-  if (sel.U) {
-    uint64_t mm = 0;
-    TBK_TRY(clip_mrange(ctx, T, ni, d_tid, d_start, d_end, &m_first, &m_off, &mm));
-    if (mm > rows->cap_intervals) {  // (as in cov_clip_impl)
-      rows->n_intervals = (uint32_t)mm;
-      return TBK_E2BIG;
-    }
-    m = (uint32_t)mm;
-  } else {
-    TBK_TRY(clip_range(ctx, ni, d_tid, d_start, d_end, tid, beg, end, &first, &m));
-  }
-  if (m) {
-    int32_t *s_tid = ws_alloc<int32_t>(ctx, m), *s_start = ws_alloc<int32_t>(ctx, m), *s_end = ws_alloc<int32_t>(ctx, m);
-    int64_t* s_cnt = ws_alloc<int64_t>(ctx, m);
-    float* s_heat = ws_alloc<float>(ctx, m);
-    if (!s_tid || !s_start || !s_end || !s_cnt || !s_heat) return TBK_ENOMEM;
-    if (sel.U)
-      TBK_LAUNCH(ctx, "clip_msample", clip_msamp_k, cdiv(m, RG_NT), RG_NT, 0, m, T, m_off, m_first, d_tid, d_start, d_end, d_cnt, d_heat, s_tid, s_start, s_end,
-                 s_cnt, s_heat);
-    else
-      TBK_LAUNCH(ctx, "clip_sample", clip_samp_k, cdiv(m, RG_NT), RG_NT, 0, m, first, d_tid, d_start, d_end, d_cnt, d_heat, beg, end, s_tid, s_start, s_end, s_cnt,
-                 s_heat);
-    TBK_TRY(rows_out(ctx, mem, rows->iv_tid, s_tid, m));
-    TBK_TRY(rows_out(ctx, mem, rows->iv_start, s_start, m));
-    TBK_TRY(rows_out(ctx, mem, rows->iv_end, s_end, m));
-    TBK_TRY(rows_out(ctx, mem, rows->iv_count, s_cnt, m));
-    TBK_TRY(rows_out(ctx, mem, rows->iv_heat, s_heat, m));
-  }
-  rows->n_intervals = m;
+  TBK_TRY(tbk_ws_reserve(ctx, (size_t)ni * 56 + R * 24 + tab_bytes(U) + ((size_t)1 << 20)));
+  RegTab T;
+  TBK_TRY(tab_upload(ctx, U, &T));
+  TBK_TRY(clip_intervals(ctx, T, rows->mem, ni, rows->cap_intervals, &rows->n_intervals, rows->iv_tid, rows->iv_start, rows->iv_end, rows->iv_count, rows->iv_heat));
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   return tbk_check_launch(ctx, "sample_clip");
 }
 
 }  // namespace
 
+// The one-region entries: the table of the one interval [beg, end) on tid, on the stack.
 extern "C" int tbk_region_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, int32_t tid, int64_t beg, int64_t end, tbk_cov_in* view,
                                uint32_t* n_kept) {
-  return region_view_impl(ctx, tile, tag_seen, Sel{nullptr, tid, beg, end}, view, n_kept);
+  if (!region_ok(tid, beg, end)) return TBK_EINVAL;
+  return region_view_impl(ctx, tile, tag_seen, tbk_regions{1, &tid, &beg, &end}, view, n_kept);
 }
-extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end) { return cov_clip_impl(ctx, rows, Sel{nullptr, tid, beg, end}); }
+extern "C" int tbk_cov_clip(tbk_ctx* ctx, tbk_cov_out* rows, int32_t tid, int64_t beg, int64_t end) {
+  if (!region_ok(tid, beg, end)) return TBK_EINVAL;
+  return cov_clip_impl(ctx, rows, tbk_regions{1, &tid, &beg, &end});
+}
 extern "C" int tbk_sample_clip(tbk_ctx* ctx, tbk_sample_out* rows, int32_t tid, int64_t beg, int64_t end) {
-  return sample_clip_impl(ctx, rows, Sel{nullptr, tid, beg, end});
+  if (!region_ok(tid, beg, end)) return TBK_EINVAL;
+  return sample_clip_impl(ctx, rows, tbk_regions{1, &tid, &beg, &end});
 }
-// ---- the same for a region table ----
+// ---- the same for a caller's table ----
 extern "C" int tbk_regions_view(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, const tbk_regions* regions, tbk_cov_in* view, uint32_t* n_kept) {
-  if (!regions) return TBK_EINVAL;
-  return region_view_impl(ctx, tile, tag_seen, Sel{regions, 0, 0, 0}, view, n_kept);
+  if (!regions_ok(regions)) return TBK_EINVAL;
+  return region_view_impl(ctx, tile, tag_seen, *regions, view, n_kept);
 }
 extern "C" int tbk_cov_clip_regions(tbk_ctx* ctx, tbk_cov_out* rows, const tbk_regions* regions) {
-  if (!regions) return TBK_EINVAL;
-  return cov_clip_impl(ctx, rows, Sel{regions, 0, 0, 0});
+  if (!regions_ok(regions)) return TBK_EINVAL;
+  return cov_clip_impl(ctx, rows, *regions);
 }
 extern "C" int tbk_sample_clip_regions(tbk_ctx* ctx, tbk_sample_out* rows, const tbk_regions* regions) {
-  if (!regions) return TBK_EINVAL;
-  return sample_clip_impl(ctx, rows, Sel{regions, 0, 0, 0});
+  if (!regions_ok(regions)) return TBK_EINVAL;
+  return sample_clip_impl(ctx, rows, *regions);
 }
 
 // ---- tbk_tile_region: the region's records of a decoded tile as a collapse tile -------------------------------------------
-// The flags and the kept CIGAR counts are rv_flag_k's; what a collapse tile carries beyond tiecov's view — nh, mapq, yd_in, the MD and QNAME
-// CSRs, qname_hash, the record-offset table behind tbk_bam_records and the encoders — moves in the same scatter pass.
-//   rv_flag_k       keep / kcig as above
+// The flags, the kept CIGAR counts and their scans are tbk_region_view's (flag_and_scan); what a collapse tile carries beyond tiecov's view —
+// nh, mapq, yd_in, the MD and QNAME CSRs, qname_hash, the record-offset table behind tbk_bam_records and the encoders — moves in the same
+// scatter pass.  (rv_scatter_k and rt_scatter_k stay two kernels: they carry different columns.)
+//   rs_flag_k       keep / kcig as above
 //   rt_lens_k       kmd[i] / kqn[i] = the kept record's MD / QNAME byte counts (only with those columns)
 //   up to four exclusive scans (tbk_exscan_u32), n + 1 elements each
 //   rt_scatter_k    a thread per record: the columns, the three CSR payloads and the record offset, file order kept
@@ -753,8 +604,8 @@ T* rt_alloc(tbk_ctx* ctx, size_t n) {
   return (T*)tbk_bam_dev_alloc(ctx, (n ? n : 1) * sizeof(T));
 }
 
-int tile_region_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const Sel& sel, tbk_soa_in* out, uint32_t* file_off_out, uint32_t* n_kept) {
-  if (!ctx || !tile || !out || !file_off_out || !n_kept || tile->mem != TBK_MEM_DEVICE || !sel_ok(sel)) return TBK_EINVAL;
+int tile_region_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const tbk_regions& U, tbk_soa_in* out, uint32_t* file_off_out, uint32_t* n_kept) {
+  if (!ctx || !tile || !out || !file_off_out || !n_kept || tile->mem != TBK_MEM_DEVICE) return TBK_EINVAL;
   const uint32_t n = tile->n_records, k = tile->n_files;
   if (k == 0 || !tile->file_off || tile->prio_hi || tile->prio_lo) return TBK_EINVAL;
   if (tile->file_off[0] != 0 || tile->file_off[k] != n) return TBK_EINVAL;
@@ -790,22 +641,18 @@ int tile_region_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const Sel& sel, tbk_s
   if (!tbk_bam_dev_records(ctx, &d_inf, &d_rec, &n_rec) || n_rec != n) return TBK_EINVAL;
   tbk_prof_begin_call(ctx);
   ProfEnd prof_end{ctx};
-  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 32 + ((size_t)k + 1) * 8 + tab_bytes(sel) + ((size_t)1 << 20)));
-  uint32_t* keep = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint32_t* kcig = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint32_t* koff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint32_t* coff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  TBK_TRY(tbk_ws_reserve(ctx, ((size_t)n + 1) * 32 + ((size_t)k + 1) * 8 + tab_bytes(U) + ((size_t)1 << 20)));
   uint32_t *kmd = nullptr, *moff = nullptr, *kqn = nullptr, *qoff = nullptr;
   if (has_md) kmd = ws_alloc<uint32_t>(ctx, (size_t)n + 1), moff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   if (has_qn) kqn = ws_alloc<uint32_t>(ctx, (size_t)n + 1), qoff = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
   uint32_t* d_fo = ws_alloc<uint32_t>(ctx, (size_t)k + 1);
   uint32_t* d_fo_out = ws_alloc<uint32_t>(ctx, (size_t)k + 1);
-  if (!keep || !kcig || !koff || !coff || (has_md && !moff) || (has_qn && !qoff) || !d_fo || !d_fo_out) return TBK_ENOMEM;
+  if ((has_md && (!kmd || !moff)) || (has_qn && (!kqn || !qoff)) || !d_fo || !d_fo_out) return TBK_ENOMEM;
   const uint32_t grid = cdiv((uint64_t)n + 1, RG_NT);
   TBK_HIP(hipMemcpyAsync(d_fo, fo_in.data(), ((size_t)k + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-  TBK_TRY(flag_records(ctx, sel, n, in.tid, in.pos, in.cig_off, in.cig, keep, kcig));
-  TBK_TRY(tbk_exscan_u32(ctx, keep, koff, n + 1, nullptr));
-  TBK_TRY(tbk_exscan_u32(ctx, kcig, coff, n + 1, nullptr));
+  Kept K;
+  TBK_TRY(flag_and_scan(ctx, U, n, in.tid, in.pos, in.cig_off, in.cig, &K));
+  const uint32_t *keep = K.keep, *koff = K.koff, *coff = K.coff;
   if (has_md || has_qn) {
     TBK_LAUNCH(ctx, "tile_region_lens", rt_lens_k, grid, RG_NT, 0, n, keep, in.md_off, in.qname_off, kmd, kqn);
     if (has_md) TBK_TRY(tbk_exscan_u32(ctx, kmd, moff, n + 1, nullptr));
@@ -870,9 +717,10 @@ int tile_region_impl(tbk_ctx* ctx, const tbk_soa_in* tile, const Sel& sel, tbk_s
 
 extern "C" int tbk_tile_region(tbk_ctx* ctx, const tbk_soa_in* tile, int32_t tid, int64_t beg, int64_t end, tbk_soa_in* out, uint32_t* file_off_out,
                                uint32_t* n_kept) {
-  return tile_region_impl(ctx, tile, Sel{nullptr, tid, beg, end}, out, file_off_out, n_kept);
+  if (!region_ok(tid, beg, end)) return TBK_EINVAL;
+  return tile_region_impl(ctx, tile, tbk_regions{1, &tid, &beg, &end}, out, file_off_out, n_kept);
 }
 extern "C" int tbk_tile_regions(tbk_ctx* ctx, const tbk_soa_in* tile, const tbk_regions* regions, tbk_soa_in* out, uint32_t* file_off_out, uint32_t* n_kept) {
-  if (!regions) return TBK_EINVAL;
-  return tile_region_impl(ctx, tile, Sel{regions, 0, 0, 0}, out, file_off_out, n_kept);
+  if (!regions_ok(regions)) return TBK_EINVAL;
+  return tile_region_impl(ctx, tile, *regions, out, file_off_out, n_kept);
 }
