@@ -759,20 +759,22 @@ __global__ __launch_bounds__(1024) void yd_lscan_k(uint32_t* __restrict__ table,
   }
 }
 
-// The item -> group word: the low half of the 64-bit item words of the radix split, or (items placed by list) an array of its own.
+// The item -> group word of the radix split: the low half of its 64-bit item words.  Items placed by list have none the list
+// machines could read: their distances go to the items' own slots (yd_d), a far item carries its exon offset, and the one reader
+// of their group word, yd_lgather_k, knows its tile and takes a 16-bit index inside it.
 struct YdWords {
   const uint64_t* w64;
-  const uint32_t* w32;
-  __device__ __forceinline__ uint32_t group(uint32_t t) const { return w32 ? w32[t] : (uint32_t)w64[t]; }
+  __device__ __forceinline__ uint32_t group(uint32_t t) const { return (uint32_t)w64[t]; }
 };
 struct YdItems {
   uint4* pk;      // (tid + 1, start, end, offset of the item's exon list in the per-group exon arrays): written with one store
   uint32_t* nex;  // exon count (contiguous: the input of the node-offset scan); items placed by list: bit 31 = the item opens a chain
-  // Items placed by list (<= 64 inputs) are lean: (start, end) only — 16 bytes an item with the exon count and the group word
-  // instead of 24.  The reference id is not needed behind the placement (the heads are flagged there), and the exon offset, which
-  // only the spliced items use (one in twelve on config 3), is read from the item's group.
+  // Items placed by list (<= 64 inputs) are lean: (start, end) only — 14 bytes an item with the exon count and the group index
+  // instead of 24.  The reference id is not needed behind the placement (the heads are flagged there).  A FAR item holds the offset
+  // of its exon list where the others hold their end: every exon of it comes from the exon arrays, so nothing reads its end, and
+  // the list machines form the addresses of its exons from the item alone — no item -> group word, no group -> offset word, two
+  // dependent round trips per batch of yd_wave_k that nothing could hide (round 12).
   uint2* se = nullptr;
-  const uint32_t* gxoff = nullptr;  // per group: offset of its exon list (YdGroups::xoff)
   __device__ __forceinline__ uint4 rec(uint32_t t) const {
     if (se) {
       const uint2 a = se[t];
@@ -780,7 +782,7 @@ struct YdItems {
     }
     return pk[t];
   }
-  __device__ __forceinline__ uint32_t xo_of(const uint4& it, uint32_t group) const { return se ? gxoff[group] : it.w; }
+  __device__ __forceinline__ uint32_t xo_of(const uint4& it) const { return se ? it.z : it.w; }  // (of a far item; rec() of a lean item: .z)
   __device__ __forceinline__ uint32_t tidp1(uint32_t t) const { return reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t]; }
   __device__ __forceinline__ int32_t start(uint32_t t) const { return (int32_t) reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 1]; }
   __device__ __forceinline__ int32_t end(uint32_t t) const { return (int32_t) reinterpret_cast<const uint32_t*>(pk)[4 * (size_t)t + 2]; }
@@ -852,13 +854,14 @@ struct YdEmit {
 // per 64 items, against three scattered stores per item if the walk wrote the items itself.  A tile holds up to
 // 1024 x 128 items (every group in all 128 lists); the entries of one round fill YS_CAP slots, and a denser tile takes rounds over
 // index ranges, each walk writing only the entries of the current round.
-constexpr uint32_t YS_CAP = 15360;  // staging slots (60 KB: two workgroups per CU): config 3's tiles average 7.3 k items
+constexpr uint32_t YS_CAP = 14336;  // staging slots (56 KB; with the groups' records and exon offsets 80 KB: two workgroups per CU):
+                                    // config 3's tiles average 7.3 k items
 constexpr uint32_t YS_NC = (YS_NT / 64) * YS_NL;  // (wave, list) cells of a tile: two per thread
 static_assert(YS_NC == 2 * YS_NT && YS_CAP >= 4 * YS_NC, "the staging array holds the cells' aggregates and counts first");
 __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t ntiles, const uint32_t* __restrict__ table,
                                                        const uint64_t* __restrict__ totals, const uint4* __restrict__ agg,
                                                        const uint64_t* __restrict__ gwb /* yd_lcount_k's columns */, YdGroups Q,
-                                                       YdItems Y, uint32_t* __restrict__ item,
+                                                       YdItems Y, uint16_t* __restrict__ item /* the item's group inside its tile */,
                                                        const uint32_t* __restrict__ xbase /* the tiles' first exon slots (row YS_NL of the
                                                        table behind yd_lscan_k), or null: Q.xoff is made already */) {
   __shared__ uint32_t wfar[YS_NT / 64];  // far exons of a wave's groups
@@ -867,6 +870,7 @@ __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t nti
   __shared__ uint32_t lsum[YS_NL];     // items of list c in this tile
   __shared__ uint32_t lbase[YS_NL];    // items of list c in the whole call, then of the lists before c
   __shared__ uint4 grec[YS_NT];        // (tid + 1, start, end, exon word) of the tile's groups
+  __shared__ uint32_t gxo[YS_NT];      // exon offset of the tile's far groups (no other entry is written or read)
   __shared__ uint32_t stage[YS_CAP];   // entries: group | list << 10 | head << 17 — first the cells' aggregates and counts
   const YsCells P{reinterpret_cast<uint32_t(*)[YS_NL]>(stage), reinterpret_cast<uint32_t(*)[YS_NL]>(stage + YS_NC),
                   reinterpret_cast<int32_t(*)[YS_NL]>(stage + 2 * YS_NC)};
@@ -875,12 +879,22 @@ __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t nti
   const uint64_t* col = gwb + (size_t)blockIdx.x * YS_NC;
   const uint64_t m0 = col[t], m1 = col[YS_NT + t];
   if (t < YS_NL) lbase[t] = (uint32_t)totals[t];
+  // the tile's table words, asked for here beside the columns and the records: they are used behind the second and the third barrier,
+  // where the whole workgroup would wait for the round trip of a few lanes
+  uint4 av = make_uint4(0u, 0u, 0u, 0u);
+  uint32_t tb0 = 0, tb1 = 0;
+  if (t < YS_NL) av = agg[(size_t)t * ntiles + blockIdx.x];
+  if (t < 64) {
+    tb0 = table[(size_t)(2 * t) * ntiles + blockIdx.x];
+    tb1 = table[(size_t)(2 * t + 1) * ntiles + blockIdx.x];
+  }
   const uint32_t o = blockIdx.x * YS_NT + t;
   uint32_t nfar = 0, finc = 0;
   if (o < ng) {
     const uint4 g = Q.pk[o];
     grec[t] = g;
     nfar = yd_far_count(g.w);
+    if (!xbase && nfar) gxo[t] = Q.xoff[o];  // (yd_front=split: an earlier pass made the offsets)
   }
   if (xbase) {
     finc = wave_incl_sum(nfar);
@@ -888,11 +902,12 @@ __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t nti
   }
   __syncthreads();
   // the exon offset of a far group: the tile's base and the far exons of the tile's groups before it.  Only far groups get one —
-  // its readers (YdItems::xo_of in the list machines, yd_gexons_k) ask for the offset of a far item / group and no other.
+  // its readers (the copy-out loop below, for the far items; yd_gexons_k) ask for the offset of a far item / group and no other.
   if (xbase && nfar) {
     uint32_t b = xbase[blockIdx.x] + finc - nfar;
     for (uint32_t x = 0; x < (t >> 6); ++x) b += wfar[x];
     Q.xoff[o] = b;
+    gxo[t] = b;
   }
   auto fold = [&](uint64_t m, uint32_t x) {  // the cell's items -> one aggregate
     pa[x][c] = (uint32_t)__builtin_popcountll(m);
@@ -907,7 +922,6 @@ __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t nti
   fold(m1, x1);
   __syncthreads();
   if (t < YS_NL) {  // every cell of list t learns the aggregate of the list's items before it (the tiles before included) ...
-    const uint4 av = agg[(size_t)t * ntiles + blockIdx.x];
     (void)ys_chain_cells(P, t, YsAgg{av.x, av.y, (int32_t)av.z, av.w});
     uint32_t run = 0;  // ... and how many of them are in the tile
     for (uint32_t x = 0; x < YS_NT / 64; ++x) {
@@ -924,8 +938,8 @@ __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t nti
     pre[2 * t] = inc - a - b;
     pre[2 * t + 1] = inc - b;
     if (t == 63) pre[YS_NL] = inc;
-    off[2 * t] = tinc - ta - tb + table[(size_t)(2 * t) * ntiles + blockIdx.x] - (inc - a - b);
-    off[2 * t + 1] = tinc - tb + table[(size_t)(2 * t + 1) * ntiles + blockIdx.x] - (inc - b);
+    off[2 * t] = tinc - ta - tb + tb0 - (inc - a - b);
+    off[2 * t + 1] = tinc - tb + tb1 - (inc - b);
   }
   __syncthreads();
   const YsAgg A0 = P.get(x0, c), A1 = P.get(x1, c);
@@ -951,9 +965,9 @@ __global__ __launch_bounds__(YS_NT) void yd_lscatter_k(uint32_t ng, uint32_t nti
       const uint32_t e = stage[i], g = e & (YS_NT - 1u), l = (e >> 10) & (YS_NL - 1u);
       const uint4 v = grec[g];
       const uint32_t pos = off[l] + r0 + i;
-      Y.se[pos] = make_uint2(v.y, v.z);
+      Y.se[pos] = make_uint2(v.y, yd_nex_far(v.w) ? gxo[g] : v.z);  // (a far item: its exon offset for the end nothing reads)
       Y.nex[pos] = v.w | ((e >> 17) << 31);  // (bit 31: the item opens a chain — read by yd_number)
-      item[pos] = blockIdx.x * YS_NT + g;
+      item[pos] = (uint16_t)g;
     }
   }
 }
@@ -1221,13 +1235,13 @@ __global__ void yd_run_k(const uint32_t* __restrict__ ids, const uint32_t* __res
     uint32_t rstart = it.y;
     const uint32_t xw = Y.nex[t], nex = yd_nex_count(xw);
     // the item's exons: in the groups' arrays, or (one exon; the exact two-exon shape) said by the item itself
-    uint32_t ls[2] = {it.y, 0u}, le[2] = {it.z, it.z};
+    uint32_t ls[2] = {it.y, 0u}, le[2] = {it.z, it.z};  // (read only where the item is not far: a far lean item has no end)
     if (yd_nex_x2(xw)) {
       le[0] = it.y + yd_x2_a(xw) - 1u;
       ls[1] = le[0] + yd_x2_g(xw) + 1u;
     }
     const bool far = yd_nex_far(xw);
-    const uint32_t xo = far ? Y.xo_of(it, v.group(t)) : 0u;
+    const uint32_t xo = far ? Y.xo_of(it) : 0u;
     const uint32_t* const pxs = far ? ex_s + xo : ls;
     const uint32_t* const pxe = far ? ex_e + xo : le;
     int d;
@@ -1378,10 +1392,9 @@ __global__ __launch_bounds__(64) void yd_lane_k(const uint32_t* __restrict__ ids
         const uint32_t xw = Y.nex[idx];
         const uint32_t nx = yd_nex_count(xw);
         const bool x2 = yd_nex_x2(xw), far = nx > 1 && !x2;  // far: the exons lie in the groups' arrays (x2: they ride in the word)
-        const uint32_t o = (!yd_d || far) ? v.group(idx) : 0u;  // (yd_d: the distances go to the items' own slots — only such an item
-                                                                // looks its group up, for the exon list)
+        const uint32_t o = !yd_d ? v.group(idx) : 0u;  // (yd_d: the distances go to the items' own slots, no item looks its group up)
         const uint32_t w = q * RS + i0;
-        const uint32_t axo = far ? Y.xo_of(a, o) : 0u;
+        const uint32_t axo = far ? Y.xo_of(a) : 0u;
         const uint32_t x2e0 = a.y + yd_x2_a(xw) - 1u;
         S_start[w] = a.y;
         S_xo[w] = axo;
@@ -1542,29 +1555,65 @@ __global__ __launch_bounds__(64) void yd_wave_k(const uint32_t* __restrict__ ids
   uint32_t SP = 0, EP = 0, DP = 0xFFFFFFFFu;
   int P = -1;
   bool mirror_ok = false;
-  // batch loader: lane l holds item tb+l.  The next batch is requested before the current one is processed so that
-  // its global-load latency hides behind the (long, scalar-ish) item loop.
+  // batch loader: lane l holds item tb + l, fetched two batches deep.  An item comes in two dependent stages — its words (start, end
+  // or exon offset, exon word), then, for a far item, the first exons at the offset the words gave — and a stage requested in one
+  // iteration is consumed in the next: at the top of the iteration for batch b the wave asks for the words of batch b + 2, forms
+  // the far lanes' addresses of batch b + 1 from the words it asked for an iteration ago and asks for those exons, and only then
+  // enters the item loop of batch b, whose exons were asked for an iteration ago.  Both round trips lie under an item loop
+  // (microseconds).  Before round 12 the next batch was asked for in one piece ahead of the item loop, and its dependent stages
+  // (then four) were all waited for there: DESIGN.md §3.
+  // Every load is guarded by its item lying inside the chain: short chains read nothing behind their last item.
+  struct Words {
+    uint32_t start, z, xw, o;
+  };
   struct Batch {
     uint32_t start, nex, xo, o, e0, s1, e1, s2, e2;
   };
-  auto load_batch = [&](uint32_t tb) {
-    Batch b;
-    const uint32_t t = tb + (uint32_t)lane;
-    const bool have = t < t1;
+  auto load_words = [&](uint32_t tb, uint32_t ahead) {  // (tb < t1) the words of batch tb + ahead
+    Words w;
+    const bool have = t1 - tb > ahead + (uint32_t)lane;
+    const uint32_t t = tb + ahead + (uint32_t)lane;
     const uint4 it = have ? Y.rec(t) : make_uint4(0u, 0u, 0u, 0u);
-    b.start = it.y;
-    const uint32_t xw = have ? Y.nex[t] : 0u;
-    b.nex = yd_nex_count(xw);
-    const bool x2 = yd_nex_x2(xw), far = b.nex > 1u && !x2;  // far: the exons lie in the groups' arrays (x2: they ride in the word)
-    b.o = have && (!yd_d || far) ? v.group(t) : 0u;  // (yd_d: only such an item looks its group up, for the exon list)
-    b.xo = far ? Y.xo_of(it, b.o) : 0u;
-    const uint32_t x2e0 = it.y + yd_x2_a(xw) - 1u;
-    b.e0 = far ? ex_e[b.xo] : (x2 ? x2e0 : it.z);  // first exon end (its start is the read start); a single exon ends where the
-                                                   // read ends: no gather (three items in four, a 64-byte sector each)
-    b.s1 = far ? ex_s[b.xo + 1] : (x2 ? x2e0 + yd_x2_g(xw) + 1u : 0u);
-    b.e1 = far ? ex_e[b.xo + 1] : (x2 ? it.z : 0u);
-    b.s2 = (far && b.nex > 2) ? ex_s[b.xo + 2] : 0u;
-    b.e2 = (far && b.nex > 2) ? ex_e[b.xo + 2] : 0u;
+    w.start = it.y;
+    w.xw = have ? Y.nex[t] : 0u;
+    w.z = yd_nex_far(w.xw) ? Y.xo_of(it) : it.z;  // a far item: the offset of its exon list (nothing reads its end); else: the end
+    w.o = have && !yd_d ? v.group(t) : 0u;  // (yd_d: the distances go to the items' own slots, no item looks its group up)
+    return w;
+  };
+  // the first three exons of the far lanes.  Loads and nothing else: a value the other lanes compute into the register a load is
+  // about to fill — far ? ex_e[xo] : end — makes the compiler wait for every load in flight (s_waitcnt vmcnt(0): it knows no lane
+  // masks), in front of the item loop; so the registers are zeroed, the far lanes load, and make_batch picks an iteration later.
+  struct Exons {
+    uint32_t e0, s1, e1, s2, e2;
+  };
+  auto load_exons = [&](const Words& w) {
+    Exons g{0u, 0u, 0u, 0u, 0u};
+    const uint32_t n = yd_nex_count(w.xw);
+    if (yd_nex_far(w.xw)) {
+      g.e0 = ex_e[w.z];
+      g.s1 = ex_s[w.z + 1];
+      g.e1 = ex_e[w.z + 1];
+      if (n > 2u) {
+        g.s2 = ex_s[w.z + 2];
+        g.e2 = ex_e[w.z + 2];
+      }
+    }
+    return g;
+  };
+  auto make_batch = [&](const Words& w, const Exons& g) {
+    Batch b;
+    b.start = w.start;
+    b.nex = yd_nex_count(w.xw);
+    b.o = w.o;
+    const bool x2 = yd_nex_x2(w.xw), far = yd_nex_far(w.xw);  // far: the exons lie in the groups' arrays (x2: they ride in the word)
+    b.xo = far ? w.z : 0u;
+    const uint32_t x2e0 = w.start + yd_x2_a(w.xw) - 1u;
+    b.e0 = far ? g.e0 : (x2 ? x2e0 : w.z);  // first exon end (its start is the read start); a single exon ends where the read ends:
+                                            // no gather (three items in four, a 64-byte sector each)
+    b.s1 = far ? g.s1 : (x2 ? x2e0 + yd_x2_g(w.xw) + 1u : 0u);
+    b.e1 = far ? g.e1 : (x2 ? w.z : 0u);
+    b.s2 = g.s2;
+    b.e2 = g.e2;
     return b;
   };
   auto set_mirror = [&](int p) {  // (uniform) node p becomes the active island
@@ -1576,10 +1625,13 @@ __global__ __launch_bounds__(64) void yd_wave_k(const uint32_t* __restrict__ ids
     }
     mirror_ok = true;
   };
-  Batch nxt = load_batch(t0);
+  Words wn = load_words(t0, 0u), wnn = load_words(t0, 64u);  // (the chain's start: both batches' words in one round trip)
+  Exons gn = load_exons(wn);
   for (uint32_t tb = t0; tb < t1 && !overflow; tb += 64) {
-    const Batch cur = nxt;
-    if (tb + 64 < t1) nxt = load_batch(tb + 64);
+    const Batch cur = make_batch(wn, gn);
+    wn = wnn;
+    wnn = load_words(tb, 128u);
+    gn = load_exons(wn);
     const bool have = tb + (uint32_t)lane < t1;
     const uint32_t it_start = cur.start, it_nex = cur.nex, it_xo = cur.xo, it_o = cur.o, it_e0 = cur.e0;
     const uint32_t it_s1 = cur.s1, it_e1 = cur.e1, it_s2 = cur.s2, it_e2 = cur.e2;
@@ -1839,11 +1891,11 @@ __global__ void col_write_yd_k(uint32_t ng, const uint32_t* __restrict__ gperm, 
 // whole lines) instead of one device-scope atomicMax per item on the groups' array — on a chip of eight L2s such an atomic is a round
 // trip to the memory side, 22 bytes of write traffic each by the counters (3.7 GB per launch of yd_wave_k on config 3).  This pass
 // folds them per tile of YS_NT groups: the tile's items of list c are the segment [base[c], base[c] + n[c]) of that list (the
-// placement's own table), their group words say where they belong, and the maxima meet in LDS.  It writes the YD output itself
+// placement's own table), their 16-bit group words say where in the tile they belong, and the maxima meet in LDS.  It writes the YD output itself
 // (col_write_yd_k's job on the other paths: int dmax = spd.maxYD, tiebrush.cpp:511-524).
 __global__ __launch_bounds__(512) void yd_lgather_k(uint32_t ng, uint32_t ntiles, const uint32_t* __restrict__ table,
                                                     const uint64_t* __restrict__ totals, const uint32_t* __restrict__ yd_d,
-                                                    const uint32_t* __restrict__ item, const uint32_t* __restrict__ gperm, GroupAcc G,
+                                                    const uint16_t* __restrict__ item, const uint32_t* __restrict__ gperm, GroupAcc G,
                                                     uint32_t cap, int32_t* __restrict__ yd) {
   __shared__ uint32_t base[YS_NL], lsum[YS_NL];
   __shared__ int32_t mx[YS_NT];
@@ -1881,13 +1933,13 @@ __global__ __launch_bounds__(512) void yd_lgather_k(uint32_t ng, uint32_t ntiles
   }
 #pragma unroll
   for (uint32_t j = 0; j < NSEG; ++j)
-    if (dv[j]) atomicMax(&mx[gv[j] - b * YS_NT], (int32_t)dv[j]);
+    if (dv[j]) atomicMax(&mx[gv[j]], (int32_t)dv[j]);
   for (uint32_t j = 0; j < NSEG; ++j) {  // segments of more than 64 items (a tile of 1024 groups may hold 1024 of a list)
     const uint32_t c = wv + j * (512 / 64);
     const uint32_t p0 = base[c], n = lsum[c];
     for (uint32_t i = 64 + ln; i < n; i += 64) {
       const uint32_t d = yd_d[p0 + i];
-      if (d) atomicMax(&mx[item[p0 + i] - b * YS_NT], (int32_t)d);
+      if (d) atomicMax(&mx[item[p0 + i]], (int32_t)d);
     }
   }
   __syncthreads();
@@ -2006,7 +2058,8 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
     uint4* ys_agg = nullptr;
     uint64_t* ys_totals = nullptr;
     uint64_t* ys_wb = nullptr;  // the tiles' bit columns (yd_lcount_k -> yd_lscatter_k)
-    uint32_t *yd_d = nullptr, *ys_item = nullptr;
+    uint32_t* yd_d = nullptr;
+    uint16_t* ys_item = nullptr;
     YdGroups Q{};
     if (by_list) {  // items and aggregates per (list, tile of groups); the count pass makes the groups' records on its way (it folds them)
       Q.pk = ws_alloc<uint4>(ctx, ng);
@@ -2052,7 +2105,7 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
       // items: one word each, list id (file * 2 + strand list) : 32 | group in output order : 32
       uint64_t* iv = by_list ? nullptr : ws_alloc<uint64_t>(ctx, nit);
       uint64_t* iv2 = by_list ? nullptr : ws_alloc<uint64_t>(ctx, nit);
-      uint32_t* io = by_list ? ws_alloc<uint32_t>(ctx, nit) : nullptr;  // items placed by list: the item -> group array
+      uint16_t* io = by_list ? ws_alloc<uint16_t>(ctx, nit) : nullptr;  // items placed by list: the item's group inside its tile
       yd_d = by_list ? ws_alloc<uint32_t>(ctx, nit) : nullptr;          // ... and every item's distance (yd_lgather_k folds them)
       if (by_list && (!io || !yd_d)) return TBK_ENOMEM;
       ys_item = io;
@@ -2060,7 +2113,6 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
       if (by_list) {
         Y.pk = nullptr;
         Y.se = ws_alloc<uint2>(ctx, nit);
-        Y.gxoff = Q.xoff;  // (by_list: the groups' records were made above)
         if (!Y.se) return TBK_ENOMEM;
       } else {
         Y.pk = ws_alloc<uint4>(ctx, nit);
@@ -2160,17 +2212,17 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
       if (n_long && !literal) {
         hipStream_t keep = ctx->stream;
         if (aux) ctx->stream = aux;
-        TBK_LAUNCH(ctx, "yd_wave", yd_wave_k, n_long, 64, 0, ids_long, n_wave, nchains, nit, chain_first, Y, YdWords{iv, io}, noff, ex_s, ex_e, J.g_yd,
+        TBK_LAUNCH(ctx, "yd_wave", yd_wave_k, n_long, 64, 0, ids_long, n_wave, nchains, nit, chain_first, Y, YdWords{iv}, noff, ex_s, ex_e, J.g_yd,
                    yd_d, ids_over, n_over);
         ctx->stream = keep;
         if (aux) TBK_HIP(hipEventRecord(ctx->aux_done, aux));
       }
       if (n_lane && !literal)
-        TBK_LAUNCH(ctx, "yd_lane", yd_lane_k<8>, cdiv(n_lane, 64), 64, 0, ids_lane, n_lane, nchains, nit, chain_first, Y, YdWords{iv, io}, ex_s, ex_e, J.g_yd,
+        TBK_LAUNCH(ctx, "yd_lane", yd_lane_k<8>, cdiv(n_lane, 64), 64, 0, ids_lane, n_lane, nchains, nit, chain_first, Y, YdWords{iv}, ex_s, ex_e, J.g_yd,
                    yd_d, ids_over, n_over);
       if (n_long && aux) TBK_HIP(hipStreamWaitEvent(ctx->stream, ctx->aux_done, 0));
       // chains whose list outgrew its lane's / wave's slots (count only known on the device: launch for the upper bound)
-      TBK_LAUNCH(ctx, "yd_run_overflow", yd_run_k, cdiv(nchains, 64), 64, 0, ids_over, n_over, nchains, nit, chain_first, Y, YdWords{iv, io}, noff, ex_s, ex_e,
+      TBK_LAUNCH(ctx, "yd_run_overflow", yd_run_k, cdiv(nchains, 64), 64, 0, ids_over, n_over, nchains, nit, chain_first, Y, YdWords{iv}, noff, ex_s, ex_e,
                  N, J.g_yd, yd_d);
     }
     if (by_list) {  // the distances lie with the items (no item: every segment is empty): folded per tile of groups, written as YD
@@ -2198,7 +2250,7 @@ int tbk_collapse_warm(tbk_ctx* ctx) {
   uint32_t* z = (uint32_t*)sc;  // zeros: the id list, the counts, chain_first[0]
   YdItems Y{};
   Y.pk = (uint4*)sc, Y.nex = z;
-  const YdWords W{nullptr, z};
+  const YdWords W{nullptr};
   const SegNodes N{z, z, (int32_t*)z};
   hipStream_t aux = tbk_aux_stream(ctx);
   if (aux) {
