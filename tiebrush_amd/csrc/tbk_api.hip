@@ -515,6 +515,7 @@ void tbk_debug_parse(const char* spec, TbkDebug* out) {
     else if (k == "yd_own_arena") out->yd_own_arena = on;
     else if (k == "wg_stats") out->wg_stats = on;
     else if (k == "wg_og") out->wg_og = (uint32_t)u;
+    else if (k == "wg_offsets") out->wg_offsets_block = v == "block";
     else if (k == "wg_dense_verify") out->wg_dense_verify = on;
     else if (k == "wg_rank_merge") out->wg_rank_merge = on;
     else if (k == "wg_back") out->wg_back_split = v == "split";

@@ -98,7 +98,9 @@ struct TbkDebug {
   bool yd_front_split = false;  // yd_front=split: (items placed by list) the groups' records and exon offsets by passes of their own, yd_groups_k and
                                 // a device-wide scan, ahead of the count pass (default, yd_front=fused: the count pass makes them)
   bool yd_own_arena = false;  // yd_own_arena=1: a deferred YD stage never borrows the main arena
-  uint32_t wg_og = 0;         // wg_og=N: chunks per block of the window path's offsets pass, 1 .. 8 (0: by the tile's size — one below 8 M records)
+  uint32_t wg_og = 0;         // wg_og=N: chunks per block of the window path's offsets pass, 1 .. 8 (0: by the tile's size — one below 8 M records);
+                              // the wave kernel of the raw form: N chunks = 2 N steps of 1024 records share a wave's carried state
+  bool wg_offsets_block = false;  // wg_offsets=block: the raw form's offsets pass by the block kernel (wg_offsets_stream_k) instead of one wave per stretch
   bool wg_stats = false;      // wg_stats=1: the window path's window and overflow counts are read back for tbk_last_route
   bool wg_dense_verify = false, wg_rank_merge = false;  // window path: per-record verification form; merge-sort ranking of a window's groups
   bool wg_back_split = false;  // wg_back=split: (raw window form) the verification of the listed records, the tie sets (col_tie_sort_k, col_write_k)

@@ -62,6 +62,12 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
 //  — WgOut::yc is the sum of the carried integral YC, yxin / ydin the sum / maximum of the carried YX / YD, no
 // incidences (np = 0); TBK_DERR_FRACTIONAL in *err_bits: a carried value this form cannot hold — run the sort path.
 bool tbk_window_supported(uint32_t k);
+// The raw form's offsets pass on its own (test infrastructure: tests/support/offsets_probe.hip): the reference ids per chunk, then what
+// tbk_window_groups runs between its splitters and its window kernels — the stream or wave kernel (TbkDebug::wg_offsets_block, wg_og),
+// the edges, the transpose.  tid / pos: n records in k runs (d_run_off [k + 1], device), W: nW sorted bounds (any values).
+// off: [(nW + 2) * k] bound-major, wbase: [nW + 2]; everything runs on ctx->stream, TBK_DERR_RAWORDER arrives in ctx->d_err.
+int tbk_wg_offsets_raw(tbk_ctx* ctx, const int32_t* tid, const int32_t* pos, const uint32_t* d_run_off, uint32_t k, uint32_t n, const uint64_t* W,
+                       uint32_t nW, uint32_t* off, uint32_t* wbase);
 // The YD stage of a window-path tile places its items by list without a sort when the tile has at most 64 input files (collapse.hip:
 // yd_lcount_k / yd_lscatter_k) and needs no per-incidence group array then (yd_radix: test hook, the radix split for any tile).
 inline bool tbk_yd_by_list(const tbk_ctx* ctx, uint32_t k) { return 2u * k <= 128u && !ctx->dbg.yd_radix; }

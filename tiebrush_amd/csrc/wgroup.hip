@@ -174,7 +174,8 @@ __device__ __forceinline__ uint32_t wg_upper_bound(const uint64_t* __restrict__ 
   return lo;
 }
 // A block takes WG_OG consecutive chunks.  Inside a run the bounds of consecutive chunks follow one another: the lower end of a chunk's
-// range in W is the upper end of the chunk before it, and the upper end lies a few bounds further (2.3 per chunk on config 3) — ONE
+// range in W is the upper end of the chunk before it, and the upper end lies 4 k bounds further on average (nW = m / 512 bounds over a
+// run's m / k records: ~ 255 per chunk at k = 64, counted with tests/offsets_model.py — not the "2.3" this comment once gave) — ONE
 // round of 256 probes behind the lower end finds it, where the search over all of W takes three dependent rounds; those probes and the
 // next chunk's positions are asked for while the current chunk's bisections run, so a chunk no longer waits for memory at all (one
 // chunk per block, each behind its own four round trips, was 0.83 ms for 1.3 GB of positions).
@@ -343,6 +344,282 @@ __global__ __launch_bounds__(256) void wg_offsets_stream_k(const uint64_t* __res
     }
   }
   if (RAW && bad) atomicOr(err, TBK_DERR_RAWORDER);
+}
+// The raw form's offsets pass, one WAVE per stretch of records and no block barrier (the block kernel above executes everything that
+// is uniform per chunk — the bisection over the runs' offsets, the loop over segments, the probe counts — in all four waves and
+// meets three to four barriers per chunk).  A wave owns `steps` * WV_ST consecutive records and takes them in steps: WV_ST records
+// where ctid gives the chunk one reference id — the keys are then the 31-bit positions, and a bound is taken relative to the id's
+// first key (WvPos) — and half as many 64-bit keys in a chunk of mixed ids (WvKey), so that a wave's LDS slice is 4 KB either way.
+// Of a step lane l loads records 256 q + 4 l .. + 3 (four 16-byte loads, each instruction a contiguous KB) and puts their keys into
+// the slice, for the bisections and for the sortedness check, which reads them back with the key before each quad (the key before the
+// step is carried).  The loads are not fetched a step ahead: the sixteen registers that would hold them cost a wave per SIMD, and five
+// resident waves without them were faster than four with.  The run, the upper end in W of the segment
+// before (c_rhi) and that segment's last key (c_klast) are carried in scalars; the run is looked up once per wave.  Bounds of a
+// segment: W[r + lane + 64 i], i < 3, asked for a step ahead (a step spans ~ 2 k bounds of a tile's nW = m / 512: 128 at k = 64);
+// while a round of 64 lies at or below the segment's last key the next is taken with it, each lane bisecting its up to three bounds
+// side by side (one chain of dependent LDS reads instead of three), and a segment that takes all 192 fetches the next 192.  The
+// 64-ary search over all of W runs where a segment has no carried state (a wave's first step).  Keys are the block kernel's (the
+// chunk's reference id where ctid has one), so the same inversions raise TBK_DERR_RAWORDER and the same ones stay hidden for
+// wg_hash_window to find.  Whatever the input: every LDS index lies inside the segment, every row index below nW, every entry
+// written inside [run start, run end].
+constexpr uint32_t WV_ST = 1024;
+__device__ __forceinline__ uint32_t wv_upper_bound(const uint64_t* __restrict__ W, uint32_t lo, uint32_t hi, uint64_t v, uint32_t lane) {
+  // first r in [lo, hi] with W[r] > v (hi: none), 64 evenly spaced probes per round; every quantity but the probe is wave-uniform
+  while (lo < hi) {
+    const uint32_t step = (hi - lo + 63u) >> 6;
+    const uint32_t p = lo + lane * step;
+    const bool le = p < hi && W[p] <= v;
+    const uint32_t T = (uint32_t)__builtin_popcountll(__ballot(le));
+    if (T == 0) {
+      hi = lo;
+    } else {
+      const uint32_t pT = lo + T * step;  // the first probe that was beyond, or beyond the interval
+      hi = T < 64u && pT < hi ? pT : hi;
+      lo = lo + (T - 1u) * step + 1u;
+      lo = lo > hi ? hi : lo;
+    }
+  }
+  return lo;
+}
+// The two key domains of a step.  of(): a 64-bit key or bound in the step's domain — order kept against every key of the step;
+// full(): a key of the step as the 64-bit key.
+struct WvPos {  // a chunk of one reference id: key = the position (0 for a chunk of unplaced reads), base = the id's first key
+  using K = uint32_t;
+  static constexpr uint32_t NQ = 4;  // quads per lane: a step of 1024 records
+  uint64_t base;
+  __device__ __forceinline__ K of(uint64_t v) const {
+    const uint64_t d = v - base;
+    return v <= base ? 0u : d > 0x7FFFFFFFull ? 0x80000000u : (uint32_t)d;  // (beyond every position: beyond every key)
+  }
+  __device__ __forceinline__ uint64_t full(K x) const { return base | x; }
+};
+struct WvKey {  // a chunk of mixed ids: the keys themselves, 512 records
+  using K = uint64_t;
+  static constexpr uint32_t NQ = 2;
+  __device__ __forceinline__ K of(uint64_t v) const { return v; }
+  __device__ __forceinline__ uint64_t full(K x) const { return x; }
+};
+struct WvState {  // carried from step to step
+  uint32_t f;             // the run the next record lies in (or an empty run before it)
+  bool have_ab;           // a / b = run_off[f] / run_off[f + 1] are loaded
+  uint32_t a, b;
+  bool carry;             // c_rhi / c_klast / wp hold for the segment that ended the step before
+  uint32_t c_rhi;
+  uint64_t c_klast, wp[3];  // wp[i] = W[c_rhi + lane + 64 i]
+  bool bad;
+};
+// src[i0 + 256 q + 4 lane .. + 3], q < NQ (0 beyond n)
+template <uint32_t NQ>
+__device__ __forceinline__ void wv_load(const int32_t* __restrict__ src, uint32_t i0, uint32_t n, uint32_t lane, int32_t* v) {
+  const uint32_t rem = n - i0;  // (i0 < n)
+#pragma unroll
+  for (uint32_t q = 0; q < NQ; ++q) {
+    const uint32_t o = 256u * q + 4u * lane;
+    if (o < rem && rem - o >= 4u) {
+      const int4 x = *reinterpret_cast<const int4*>(src + (size_t)i0 + o);
+      v[4 * q] = x.x, v[4 * q + 1] = x.y, v[4 * q + 2] = x.z, v[4 * q + 3] = x.w;
+    } else {
+#pragma unroll
+      for (uint32_t e = 0; e < 4; ++e) v[4 * q + e] = o + e < rem ? src[(size_t)i0 + o + e] : 0;
+    }
+  }
+}
+__device__ __forceinline__ void wv_probes(const uint64_t* __restrict__ W, uint32_t nW, uint32_t r, uint32_t lane, uint64_t (&wp)[3]) {
+#pragma unroll
+  for (uint32_t i = 0; i < 3; ++i) wp[i] = r < nW && nW - r > lane + 64u * i ? W[r + lane + 64u * i] : ~0ull;
+}
+// NC bisections side by side over key[lo0, hi0): res[c] = the first index whose key is >= p[c] (hi0: none)
+template <uint32_t NC, uint32_t LEN, class K>
+__device__ __forceinline__ void wv_bisect(const K* key, uint32_t lo0, uint32_t hi0, const K (&p)[3], uint32_t (&res)[3]) {
+  uint32_t lo[NC], hi[NC];
+#pragma unroll
+  for (uint32_t c = 0; c < NC; ++c) lo[c] = lo0, hi[c] = hi0;
+  const uint32_t iters = 32u - (uint32_t)__builtin_clz(hi0 - lo0);  // (uniform; hi0 > lo0) an interval of L halves to nothing in floor(log2 L) + 1
+  for (uint32_t it = 0; it < iters; ++it) {
+#pragma unroll
+    for (uint32_t c = 0; c < NC; ++c) {
+      const uint32_t mid = lo[c] + ((hi[c] - lo[c]) >> 1);  // (< hi0 while the chain is open; hi0 <= LEN)
+      const bool open = lo[c] < hi[c];
+      const bool lt = key[mid < LEN ? mid : LEN - 1u] < p[c];
+      lo[c] = open && lt ? mid + 1u : lo[c];
+      hi[c] = open && !lt ? mid : hi[c];
+    }
+  }
+#pragma unroll
+  for (uint32_t c = 0; c < NC; ++c) res[c] = lo[c];
+}
+// one step: records [i0, i1), i1 - i0 <= 256 NQ; kq[4 q + e] = the key of record i0 + 256 q + 4 lane + e (anything beyond i1)
+template <class D>
+__device__ __forceinline__ void wv_step(const D dom, typename D::K* key, typename D::K (&kq)[4 * D::NQ], uint32_t i0, uint32_t i1, uint32_t lane,
+                                        const int32_t* __restrict__ rtid, const int32_t* __restrict__ rpos, const int32_t* __restrict__ ctid,
+                                        const uint32_t* __restrict__ run_off, uint32_t k, uint32_t n, const uint64_t* __restrict__ W, uint32_t nW,
+                                        uint32_t nrows, uint32_t* __restrict__ offT, WvState& S) {
+  using K = typename D::K;
+  constexpr uint32_t NQ = D::NQ, LEN = 256u * NQ;
+  const uint32_t len = i1 - i0;
+  __builtin_amdgcn_wave_barrier();  // (the bisections of the step before have read the slice)
+#pragma unroll
+  for (uint32_t q = 0; q < NQ; ++q) {
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) {
+      const uint32_t j = 256u * q + 4u * lane + e;
+      kq[4 * q + e] = j < len ? kq[4 * q + e] : (K)~(K)0;  // beyond the step: the largest value (never an inversion, never read by a bisection)
+      key[j] = kq[4 * q + e];
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  uint64_t pk0 = 0;    // the key before the step's first record when both lie in one run (0: nothing to compare)
+  uint32_t nocmp = 0;  // bit 4 q + e: this lane's record (q, e) starts a run — never compared with the record before it
+  while (S.f < k) {
+    if (!S.have_ab) {
+      S.a = run_off[S.f];
+      S.b = run_off[S.f + 1];
+      S.have_ab = true;
+    }
+    const uint32_t f = S.f, a = S.a, b = S.b;
+    if (a >= i1) break;
+    if (b <= i0 || a == b || b > n || a > b) {  // (b > n, a > b: not a table of runs; nothing of it is touched)
+      ++S.f;
+      S.have_ab = false;
+      continue;
+    }
+    const uint32_t sa = a > i0 ? a : i0, sb = b < i1 ? b : i1;  // the run's records inside this step: i0 <= sa < sb <= i1
+    const bool has_lo = sa > a;                                  // (then sa == i0: the record before is outside the step)
+    const bool cont = has_lo && S.carry;                         // it continues the segment the step before ended with
+    uint64_t klo = 0;
+    if (cont) {
+      klo = S.c_klast;
+    } else if (has_lo) {  // (a wave's first step)
+      const int32_t pc = ctid[(sa - 1u) / WG_TC];
+      klo = raw_key(pc != WG_TC_MIXED ? pc : rtid[sa - 1u], rpos[sa - 1u]);
+    }
+    if (has_lo) {
+      pk0 = klo;
+    } else if (sa > i0) {
+      const uint32_t j = sa - i0;
+      nocmp |= lane == ((j & 255u) >> 2) ? 1u << ((j >> 8) * 4u + (j & 3u)) : 0u;
+    }
+    const uint64_t khi = dom.full(key[sb - 1u - i0]);  // (uniform address)
+    const bool ends = sb == b;                         // the run ends here: every bound that is left
+    uint32_t r = cont ? S.c_rhi : has_lo ? wv_upper_bound(W, 0u, nW, klo, lane) : 0u;
+    uint64_t wp[3];
+    if (cont) {
+#pragma unroll
+      for (uint32_t i = 0; i < 3; ++i) wp[i] = S.wp[i];
+    } else {
+      wv_probes(W, nW, r, lane, wp);
+    }
+    uint32_t* const col = offT + (size_t)f * nrows + 1u;
+    for (;;) {  // bounds r + lane + 64 i (r <= nW): a round is taken while the one before it was taken whole
+      const K pd[3] = {dom.of(wp[0]), dom.of(wp[1]), dom.of(wp[2])};
+      uint32_t res[3];
+      const bool t0 = r < nW && lane < nW - r && (ends || wp[0] <= khi);
+      const uint32_t c0 = (uint32_t)__builtin_popcountll(__ballot(t0));
+      uint32_t tot = c0;
+      if (c0 < 64u) {
+        wv_bisect<1, LEN, K>(key, sa - i0, sb - i0, pd, res);
+        if (t0) col[r + lane] = i0 + res[0];  // (consecutive lanes: consecutive words)
+      } else {
+        const bool t1 = lane + 64u < nW - r && (ends || wp[1] <= khi);
+        const uint32_t c1 = (uint32_t)__builtin_popcountll(__ballot(t1));
+        const bool t2 = c1 == 64u && lane + 128u < nW - r && (ends || wp[2] <= khi);
+        const uint32_t c2 = (uint32_t)__builtin_popcountll(__ballot(t2));
+        tot = 64u + c1 + c2;
+        wv_bisect<3, LEN, K>(key, sa - i0, sb - i0, pd, res);
+        col[r + lane] = i0 + res[0];
+        if (t1) col[r + lane + 64u] = i0 + res[1];
+        if (t2) col[r + lane + 128u] = i0 + res[2];
+      }
+      r += tot;  // (every bound counted lies below nW)
+      if (tot < 192u) break;
+      wv_probes(W, nW, r, lane, wp);
+    }
+    if (!ends) {  // the run goes on in the next step (sb == i1 == the next i0): its state and its probes; f stays
+      S.carry = true;
+      S.c_rhi = r;
+      S.c_klast = khi;
+      wv_probes(W, nW, r, lane, S.wp);
+      break;
+    }
+    S.carry = false;
+    ++S.f;
+    S.have_ab = false;
+  }
+  // sortedness: every lane reads its sixteen keys back and the key before each quad (the step's first record: pk0) — the registers
+  // that held them are free while the bisections run
+  const K pk0d = dom.of(pk0);
+  bool bad = false;
+#pragma unroll
+  for (uint32_t q = 0; q < NQ; ++q) {
+    const uint32_t j0 = 256u * q + 4u * lane;
+    K x[4];
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) x[e] = key[j0 + e];
+    const K prev = key[j0 ? j0 - 1u : 0u];
+    const K before = j0 ? prev : pk0d;
+#pragma unroll
+    for (uint32_t e = 0; e < 4; ++e) {
+      const K pk = e == 0 ? before : x[e - 1];
+      bad |= pk > x[e] && !((nocmp >> (4 * q + e)) & 1u);
+    }
+  }
+  S.bad |= bad;
+}
+__global__ __launch_bounds__(256) void wg_offsets_wave_k(const int32_t* __restrict__ rtid, const int32_t* __restrict__ rpos,
+                                                         const int32_t* __restrict__ ctid, const uint32_t* __restrict__ run_off, uint32_t k,
+                                                         uint32_t n, const uint64_t* __restrict__ W, uint32_t nW, uint32_t nrows,
+                                                         uint32_t* __restrict__ offT, uint32_t* __restrict__ err, uint32_t steps /* per wave */) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_key[4][WV_ST];
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wid = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint64_t start64 = (uint64_t)(blockIdx.x * 4u + wid) * steps * WV_ST;
+  if (start64 >= n) return;  // (uniform per wave; no barrier anywhere below)
+  const uint32_t start = (uint32_t)start64;
+  const uint32_t end = n - start < steps * WV_ST ? n : start + steps * WV_ST;  // (steps <= 16)
+  WvState S;
+  {  // the run the wave's first record lies in: last f with run_off[f] <= start, looked up once and advanced from then on
+    uint32_t lo = 0, hi = k;
+    while (hi - lo > 1) {
+      const uint32_t mid = (lo + hi) >> 1;
+      if (run_off[mid] <= start)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    S.f = lo;
+  }
+  S.have_ab = false;
+  S.a = S.b = 0;
+  S.carry = false;
+  S.c_rhi = 0;
+  S.c_klast = 0;
+  S.wp[0] = S.wp[1] = S.wp[2] = ~0ull;
+  S.bad = false;
+  for (uint32_t i0 = start; i0 < end;) {
+    int32_t npos[16];
+    wv_load<4>(rpos, i0, n, lane, npos);
+    const int32_t ct = ctid[i0 / WG_TC];  // (uniform) the chunk's reference id, or: read them
+    uint32_t i1;
+    if (ct != WG_TC_MIXED) {
+      i1 = end - i0 < WV_ST ? end : i0 + WV_ST;
+      uint32_t kq[16];
+#pragma unroll
+      for (uint32_t u = 0; u < 16; ++u) kq[u] = ct < 0 ? 0u : (uint32_t)npos[u] & 0x7FFFFFFFu;
+      wv_step(WvPos{raw_key(ct, 0)}, &s_key[wid][0], kq, i0, i1, lane, rtid, rpos, ctid, run_off, k, n, W, nW, nrows, offT, S);
+    } else {
+      i1 = end - i0 < WV_ST / 2u ? end : i0 + WV_ST / 2u;
+      int32_t nt[8];
+      wv_load<2>(rtid, i0, n, lane, nt);
+      uint64_t kq[8];
+#pragma unroll
+      for (uint32_t u = 0; u < 8; ++u) kq[u] = raw_key(nt[u], npos[u]);  // (the first two quads of the positions)
+      wv_step(WvKey{}, reinterpret_cast<uint64_t*>(&s_key[wid][0]), kq, i0, i1, lane, rtid, rpos, ctid, run_off, k, n, W, nW, nrows, offT, S);
+    }
+    i0 = i1;
+  }
+  if (S.bad) atomicOr(err, TBK_DERR_RAWORDER);
 }
 // (one block per run)
 __global__ void wg_offsets_edges_k(const uint32_t* __restrict__ run_off, uint32_t k, uint32_t nrows, uint32_t* __restrict__ offT) {
@@ -2320,7 +2597,14 @@ static int wg_offsets_build(tbk_ctx* ctx, bool raw, const uint64_t* chi, const i
   // chunks per block: eight where that still leaves a few thousand blocks, fewer on small inputs (the owner's side of the multi-rank
   // protocol: 7 M rows as 450 blocks took twice as long as 3 600 blocks of one chunk)
   const uint32_t og = std::min<uint32_t>(WG_OG, std::max<uint32_t>(1u, ctx->dbg.wg_og ? ctx->dbg.wg_og : m / (WG_OC * 2048u)));  // (wg_og: test hook)
-  if (raw)
+  // the raw form: one wave per og chunks (2 og steps of WV_ST records) unless wg_offsets=block asks for the block kernel (test hook and
+  // A/B switch); the wave kernel's 16-byte loads want the arrays aligned, as every array of a tile on the device is
+  const bool wave = raw && !ctx->dbg.wg_offsets_block && (((uintptr_t)rtid | (uintptr_t)rpos) & 15u) == 0;
+  if (wave) {
+    const uint32_t steps = og * (WG_OC / WV_ST);
+    TBK_LAUNCH(ctx, "wg_offsets", wg_offsets_wave_k, cdiv(cdiv(m, WV_ST * steps), 4u), 256, 0, rtid, rpos, ctid, d_run_off, k, m, W, nW, nrows, offT, ctx->d_err,
+               steps);
+  } else if (raw)
     TBK_LAUNCH(ctx, "wg_offsets", wg_offsets_stream_k<true>, cdiv(m, WG_OC * og), 256, 0, chi, rtid, rpos, ctid, d_run_off, k, m, W, nW, nrows, offT, ctx->d_err, og);
   else
     TBK_LAUNCH(ctx, "wg_offsets", wg_offsets_stream_k<false>, cdiv(m, WG_OC * og), 256, 0, chi, rtid, rpos, ctid, d_run_off, k, m, W, nW, nrows, offT, ctx->d_err, og);
@@ -2330,6 +2614,16 @@ static int wg_offsets_build(tbk_ctx* ctx, bool raw, const uint64_t* chi, const i
              k <= 64 ? wbase : nullptr);
   if (k > 64) TBK_LAUNCH(ctx, "wg_rowsum", wg_rowsum_k, cdiv(nrows, 4), 256, 0, off, k, nrows, wbase);
   return 0;
+}
+
+int tbk_wg_offsets_raw(tbk_ctx* ctx, const int32_t* tid, const int32_t* pos, const uint32_t* d_run_off, uint32_t k, uint32_t n, const uint64_t* W,
+                       uint32_t nW, uint32_t* off, uint32_t* wbase) {
+  if (!tbk_window_supported(k) || n == 0) return TBK_EINVAL;
+  const uint32_t nchunks = cdiv(n, WG_TC);
+  int32_t* ctid = ws_alloc<int32_t>(ctx, nchunks);
+  if (!ctid) return TBK_ENOMEM;
+  TBK_LAUNCH(ctx, "wg_sample", wg_tidchunks_k, cdiv(nchunks, 256u), 256, 0, tid, n, d_run_off, k, nchunks, ctid);
+  return wg_offsets_build(ctx, true, nullptr, tid, pos, ctid, d_run_off, k, n, W, nW, nW + 2u, off, wbase);
 }
 
 int tbk_partial_reduce_device(tbk_ctx* ctx, int strategy, const int32_t* rows, uint32_t n2, const uint32_t* run_off_host, uint32_t k,
