@@ -35,7 +35,11 @@ def test_constants_are_the_kernel_sources():
     assert const("WG_TC") == "4096" and const("WG_OC") == "2048" and const("WG_OG") == "8"
     assert const("WG_LDS_HASH") == "40448" and const("WG_LDS_HASH2") == "64 * 1024"
     assert "(gcap >> 2) * 3u" in src and "(WG_LDS_HASH - (8u * k + 8u)) / (44u + 4u * nwords)" in src
-    assert "bool tbk_window_supported(uint32_t k) { return k >= 1 && k <= 1024; }" in src
+    csrc = os.path.join(ROOT, "tiebrush_amd", "csrc")
+    assert "inline bool tbk_window_supported(uint32_t k) { return collapse_window_supported(k); }" in open(os.path.join(csrc, "wgroup.h")).read()
+    plan = open(os.path.join(csrc, "collapse_plan.hpp")).read()
+    assert "inline bool collapse_window_supported(uint32_t k) { return k >= 1 && k <= COLP_WINDOW_MAX_FILES; }" in plan
+    assert "constexpr uint32_t COLP_WINDOW_MAX_FILES = 1024;" in plan
     assert (wm.WG_GC64, wm.WG_GC64_2) == (767, 1250)
     assert wm.thresholds(1, True) == wm.thresholds(64, True) == (573, 936)
     assert wm.thresholds(1, False) == (630, 1023) and wm.thresholds(64, False) == (573, 936)

@@ -2021,6 +2021,7 @@ struct YdJob {  // everything the YD stage needs from the main stage (device poi
   int32_t* out_yd;
   // window path: incidences instead of sorted records (val / flags / fidx / sgid are unused then)
   bool win = false;
+  bool by_list = false;  // the items are placed by list: the window stage has decided (WgOut::yd_by_list)
   uint32_t np = 0;
   const uint16_t* pfile = nullptr;
   const uint32_t *pgrp = nullptr, *gpoff = nullptr;
@@ -2049,7 +2050,7 @@ int tbk_collapse_yd_run(tbk_ctx* ctx, void* jobp) {
   {
     uint32_t *icnt = nullptr, *ioff = nullptr, *ocnt = nullptr, *ooff = nullptr;
     uint64_t nit64;
-    const bool by_list = J.win && (!J.pgrp || tbk_yd_by_list(ctx, I.k));  // (no per-incidence group array: the window stage has decided)
+    const bool by_list = J.by_list;
     static_assert(YS_NL == 128, "tbk_yd_by_list (wgroup.h) knows the number of lists");
     const bool split_front = ctx->dbg.yd_front_split;
     const uint32_t ys_tiles = cdiv(ng, YS_NT);
@@ -2270,90 +2271,33 @@ int tbk_collapse_warm(tbk_ctx* ctx) {
 }
 
 // =============================================================================================================
-int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_in* in, tbk_groups_out* out) {
-  const uint32_t n = in->n_records;
-  const uint32_t B = 256;
-  out->n_groups = 0;
-  out->n_passed = 0;
-  ctx->route = tbk_collapse_route{};
-  if (out->rec_group) TBK_HIP(hipMemsetAsync(out->rec_group, 0xFF, (size_t)n * 4, ctx->stream));
-  if (n == 0) return 0;
-  uint64_t* sc = ctx->d_scalars;  // [0]=n_pass [1]=n_groups [2]=n_items [3]=n_chains [4]=n_nodes
-  ColIn I;
-  I.n = n;
-  I.k = in->n_files;
-  {
-    uint32_t* d_fo = ws_alloc<uint32_t>(ctx, in->n_files + 1);
-    uint8_t* d_tb = ws_alloc<uint8_t>(ctx, in->n_files);
-    if (!d_fo || !d_tb) return TBK_ENOMEM;
-    // The caller's host arrays may be transient.  Small tables are staged through the context's pinned block, so the
-    // upload is a true asynchronous copy and needs no wait; large ones go straight from the caller's memory and are
-    // waited for.
-    const size_t fo_bytes = (size_t)(in->n_files + 1) * 4, tb_bytes = in->n_files;
-    if (fo_bytes + tb_bytes <= 4096 * sizeof(uint64_t)) {
-      char* stage = (char*)tbk_stage_acquire(ctx);
-      memcpy(stage, in->file_off, fo_bytes);
-      TBK_HIP(hipMemcpyAsync(d_fo, stage, fo_bytes, hipMemcpyHostToDevice, ctx->stream));
-      if (in->tbmerged) {
-        memcpy(stage + fo_bytes, in->tbmerged, tb_bytes);
-        TBK_HIP(hipMemcpyAsync(d_tb, stage + fo_bytes, tb_bytes, hipMemcpyHostToDevice, ctx->stream));
-      } else {
-        TBK_HIP(hipMemsetAsync(d_tb, 0, tb_bytes, ctx->stream));
-      }
-      tbk_stage_release(ctx);
-    } else {
-      TBK_HIP(hipMemcpyAsync(d_fo, in->file_off, fo_bytes, hipMemcpyHostToDevice, ctx->stream));
-      if (in->tbmerged) {
-        TBK_HIP(hipMemcpyAsync(d_tb, in->tbmerged, tb_bytes, hipMemcpyHostToDevice, ctx->stream));
-      } else {
-        TBK_HIP(hipMemsetAsync(d_tb, 0, tb_bytes, ctx->stream));
-      }
-      TBK_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    I.file_off = d_fo;
-    I.tbm = d_tb;
-  }
-  I.tid = in->tid;
-  I.pos = in->pos;
-  I.flag = in->flag;
-  I.mapq = in->mapq;
-  I.strand = in->strand;
-  I.nh = in->nh;
-  I.cig_off = in->cig_off;
-  I.cig = in->cig;
-  I.yc_in = in->yc_in;
-  I.yx_in = in->yx_in;
-  I.yd_in = in->yd_in;
-  I.md_off = in->md_off;
-  I.md = in->md;
-  I.md_has = in->md_has;
-  I.qh = in->qname_hash;
-  I.qn_off = in->qname_off;
-  I.qn = in->qname;
-  I.qh_mask = ~0ull;
-  I.qh_mask = ctx->dbg.qhash_mask;
-  I.prio_hi = in->prio_hi;
-  I.prio_lo = in->prio_lo;
-  ColOpt O;
-  O.strategy = o->strategy;
-  O.max_nh = o->max_nh;
-  O.min_qual = o->min_qual;
-  O.keep_supp = o->keep_supplementary;
-  O.keep_sec = o->keep_secondary;
-  O.collapse_same = o->collapse_same;
-  O.store_frac = o->store_frac;
-  O.hash_mask = ctx->dbg.hash_mask;
+// The driver: collapse_plan.hpp says which route a tile takes first and where a route's error bits send it; one function per route.
+static_assert(int(COLP_ROUTE_RAW_WINDOW) == int(TBK_ROUTE_RAW_WINDOW) && int(COLP_ROUTE_COMPACTED_WINDOW) == int(TBK_ROUTE_COMPACTED_WINDOW) &&
+                  int(COLP_ROUTE_SORT) == int(TBK_ROUTE_SORT) && int(COLP_STRAT_FULL) == int(TBK_STRAT_FULL),
+              "collapse_plan.hpp restates tbk.h");
+static_assert(uint32_t(COLP_ERR_COLLISION) == uint32_t(TBK_DERR_COLLISION) && uint32_t(COLP_ERR_FRACTIONAL) == uint32_t(TBK_DERR_FRACTIONAL) &&
+                  uint32_t(COLP_ERR_BIGBUCKET) == uint32_t(TBK_DERR_BIGBUCKET) && uint32_t(COLP_ERR_RAWORDER) == uint32_t(TBK_DERR_RAWORDER),
+              "collapse_plan.hpp restates the device's error bits");
 
-  // per-record arrays of the key pass / scan / compaction (the raw window path never touches them: allocated when the tile takes
-  // the general front end)
+namespace {
+// The per-record arrays a route needs beyond the input, allocated when the first route that needs them runs and kept for the routes
+// the tile is handed on to.
+struct ColArrays {
+  tbk_ctx* ctx;
+  uint32_t n;
+  uint32_t *head_off = nullptr, *run_off = nullptr;  // [files + 1]
+  // the key pass / scan / compaction (the raw window path never touches them)
   uint64_t *khi = nullptr, *klo = nullptr;
   int32_t* kend = nullptr;
   uint8_t* kflags = nullptr;
   uint16_t* fidx = nullptr;
   int32_t* effend = nullptr;
-  uint32_t* ceff = nullptr;  // (window path on compacted records, allocated below)
+  uint32_t* ceff = nullptr;  // (window path on compacted records: its route allocates it)
   SortBufs sb{};
-  auto front_arrays = [&]() -> bool {
+  // the sort path only
+  uint8_t* flags = nullptr;
+  uint32_t *ghead = nullptr, *gex = nullptr, *sgid = nullptr;
+  bool ensure_front() {
     if (sb.val) return true;
     khi = ws_alloc<uint64_t>(ctx, n);
     klo = ws_alloc<uint64_t>(ctx, n);
@@ -2368,11 +2312,8 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
     sb.lo2 = klo;
     sb.val2 = nullptr;
     return sb.val && effend;
-  };
-  // per-record arrays of the sort path only (the window path never touches them: allocated when the tile takes the sort path)
-  uint8_t* flags = nullptr;
-  uint32_t *ghead = nullptr, *gex = nullptr, *sgid = nullptr;
-  auto sort_path_arrays = [&]() -> bool {
+  }
+  bool ensure_sort() {
     if (sgid) return true;
     sb.val2 = ws_alloc<uint32_t>(ctx, n);
     flags = ws_alloc<uint8_t>(ctx, n);
@@ -2380,73 +2321,335 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
     gex = ws_alloc<uint32_t>(ctx, n);
     sgid = ws_alloc<uint32_t>(ctx, n);
     return sgid != nullptr;
-  };
-  uint32_t* head_off = ws_alloc<uint32_t>(ctx, (size_t)in->n_files + 1);
-  uint32_t* run_off = ws_alloc<uint32_t>(ctx, (size_t)in->n_files + 1);
-  if (!head_off || !run_off) return TBK_ENOMEM;
-  // ceil(log2(files)) merge rounds + one local pass against ~12 radix passes.  Measured on MI355X: 2 files x 1 M
-  // 0.17 ms vs 0.47 ms; 16 files x 0.5 M: whole step 3.90 vs 4.13 ms; 64 files x 0.25 M (6 rounds): 8.58 vs 8.67 ms —
-  // level there, so more files than that take the radix sort.
-  bool use_runs = in->n_files <= 64;
-  uint32_t runs_min = 32768;          // below this the tile is launch-bound either way; keep the one code path
-  if (ctx->dbg.sort) {  // test hook: sort=radix / runs force one path whatever the shape
-    use_runs = ctx->dbg.sort != 1 && (use_runs || ctx->dbg.sort == 2);
-    if (ctx->dbg.sort == 2) runs_min = 0;
   }
+};
 
-  // The window path (wgroup.hip) goes from the runs to the groups without sorting the records; it covers plain BAM inputs
-  // with integral YC (the ordered / carried-tag cases keep the sort path, which has the per-record order they need).
-  // Small tiles of a few files are launch-bound either way and the lean run-sort path needs no read-back: it keeps them.
-  bool use_win = tbk_window_supported(in->n_files) && !O.store_frac && !O.collapse_same && (n >= (8u << 20) || (in->n_files > 64 && n >= 65536));
-  if (in->tbmerged)
-    for (uint32_t f = 0; f < in->n_files; ++f) use_win = use_win && in->tbmerged[f] == 0;
-  if (ctx->dbg.path) {  // test hook: path=sort keeps the sort path, path=window takes the window path whatever the size
-    if (ctx->dbg.path == 1) use_win = false;
-    if (ctx->dbg.path == 2)
-      use_win = tbk_window_supported(in->n_files) && !O.store_frac && !O.collapse_same && [&] {
-        bool ok = true;
-        if (in->tbmerged)
-          for (uint32_t f = 0; f < in->n_files; ++f) ok = ok && in->tbmerged[f] == 0;
-        return ok;
-      }();
-  }
-  // Group partials of other ranks (multi-GPU owner side): every "file" is the run of one source rank, all flagged
-  // TieBrush-merged, with explicit priorities — the window path in its PART form (wgroup.hip) is the reduce-by-key.  Small tiles
-  // and anything that form cannot hold (TBK_DERR_FRACTIONAL) keep the sort path, which treats them as TieBrush-merged inputs.
-  bool part = false;
-  if (in->tbmerged && in->prio_hi && in->prio_lo && in->yc_in && in->yx_in && in->yd_in && in->n_files <= 64 && !O.store_frac &&
-      !O.collapse_same && O.strategy != TBK_STRAT_FULL) {
-    part = true;
-    for (uint32_t f = 0; f < in->n_files; ++f) part = part && in->tbmerged[f] != 0;
-    if (ctx->dbg.path == 1) part = false;
-    if (part && (n >= 65536 || ctx->dbg.path == 2)) use_win = true;
-    else part = false;
-  }
-  // Raw window path: plain tiles without an explicit merge priority go from the input records straight to the groups — the key
-  // pass, the effective-end scan and the compaction are folded into the window kernels (TBK_RAW=0: test hook, keeps them apart)
-  bool use_raw = use_win;
-  if (ctx->dbg.raw == 0) use_raw = false;
-  if (part) use_raw = true;  // (the PART form exists in raw mode only)
-  if (n >= (1u << 30) || in->n_cigar_ops >= (1u << 30)) {  // the raw window kernels address a record's fields by 32-bit byte offsets
-    use_raw = false;
-    if (part) part = false, use_win = false;
-  }
-  WgOut win_out;
-  bool win_done = false;
+// What the route that finished the tile leaves for the YD stage.
+struct ColResult {
+  int form = TBK_ROUTE_NONE;  // (NONE with no error bit: nothing passed the filter)
   uint32_t m = 0, ng = 0;
   GroupAcc G{};
   int32_t* g_yd = nullptr;
-  uint32_t* gperm = nullptr;
-  uint32_t* ginv = nullptr;
-  bool any_tbm = false;
-  if (in->tbmerged)
-    for (uint32_t f = 0; f < in->n_files; ++f) any_tbm |= in->tbmerged[f] != 0;
-  // Every kernel reads the record / group counts from the device scalars (sc[0] = passing records, sc[1] = groups), so
-  // the host only needs them where it must size something by them.  "Lean" tiles — plain BAM inputs on the run-sort
-  // path, integral YC — need that nowhere: grids and arrays take the upper bound n, nothing is read back until the
-  // single synchronisation at the end, and the rare events that want a different path (a bucket too long for the
-  // local sort, a key-hash collision) simply restart the tile.
-  bool lean = use_runs && !O.store_frac && !any_tbm && n >= runs_min;
+  uint32_t *gperm = nullptr, *ginv = nullptr;
+  WgOut win;          // the window routes' groups
+  SortBufs sorted{};  // the sort route's records
+};
+
+int col_inputs(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_in* in, ColIn* I, ColOpt* O) {
+  uint32_t* d_fo = ws_alloc<uint32_t>(ctx, in->n_files + 1);
+  uint8_t* d_tb = ws_alloc<uint8_t>(ctx, in->n_files);
+  if (!d_fo || !d_tb) return TBK_ENOMEM;
+  const TbkHostTable tables[2] = {{d_fo, in->file_off, (size_t)(in->n_files + 1) * 4}, {d_tb, in->tbmerged, in->n_files}};
+  TBK_TRY(tbk_stage_upload(ctx, tables, 2));
+  I->n = in->n_records;
+  I->k = in->n_files;
+  I->file_off = d_fo;
+  I->tbm = d_tb;
+  I->tid = in->tid;
+  I->pos = in->pos;
+  I->flag = in->flag;
+  I->mapq = in->mapq;
+  I->strand = in->strand;
+  I->nh = in->nh;
+  I->cig_off = in->cig_off;
+  I->cig = in->cig;
+  I->yc_in = in->yc_in;
+  I->yx_in = in->yx_in;
+  I->yd_in = in->yd_in;
+  I->md_off = in->md_off;
+  I->md = in->md;
+  I->md_has = in->md_has;
+  I->qh = in->qname_hash;
+  I->qn_off = in->qname_off;
+  I->qn = in->qname;
+  I->qh_mask = ctx->dbg.qhash_mask;
+  I->prio_hi = in->prio_hi;
+  I->prio_lo = in->prio_lo;
+  O->strategy = o->strategy;
+  O->max_nh = o->max_nh;
+  O->min_qual = o->min_qual;
+  O->keep_supp = o->keep_supplementary;
+  O->keep_sec = o->keep_secondary;
+  O->collapse_same = o->collapse_same;
+  O->store_frac = o->store_frac;
+  O->hash_mask = ctx->dbg.hash_mask;
+  return 0;
+}
+
+// The general front end: keys, the filter, the effective ends and the compaction of the passing records into s2, as kernels of their
+// own (the raw window route has them inside its window kernels).  ceff: the compacted effective ends, for the window path.
+int col_front_end(tbk_ctx* ctx, const ColIn& I, const ColOpt& O, ColArrays& A, const SortBufs& s2, uint32_t* ceff, bool runs) {
+  const uint32_t B = 256, n = I.n;
+  uint64_t* sc = ctx->d_scalars;
+  TBK_LAUNCH(ctx, "col_keys", col_keys_k, cdiv(n, B), B, 0, I, O, A.khi, A.klo, A.kend, A.kflags, A.fidx, ctx->d_err);
+  EffLoad ld{A.khi, A.kend, A.kflags};
+  EffStore st{A.khi, A.klo, A.kflags, A.effend, s2.hi, s2.lo, s2.val, sc + 0, n, ctx->d_err, A.fidx, A.head_off, ceff, I.prio_hi};
+  EffKey ident{0u, 0u, INT32_MIN, 0u};
+  TBK_TRY((scan_op_run<EffKey, EffOp, EffLoad, EffStore>(ctx, "col_effkey_scan", n, ld, st, EffOp{}, ident, true)));
+  if (runs) TBK_LAUNCH(ctx, "col_runs", col_runs_k, cdiv(I.k + 1, B), B, 0, I.k, I.file_off, A.head_off, sc + 0, A.run_off);
+  return 0;
+}
+
+// What follows tbk_window_groups on both window forms: the output order with its tie sets, the caller's results, the record -> group
+// map; then the read-back.  form: the raw form's groups come with their order (wo.gperm / ginv) and, unless wg_back=split, with the
+// tie sets done and the results written (direct_on: into the caller's arrays, by the compaction); the compacted form's order is made
+// here.  effend == nullptr: the effective end of the representative — or the low word of its explicit priority — rides in the high
+// word of G.rep.  *eb: TBK_DERR_COLLISION (the verification: the compaction's waves, wg_finish_raw_k or wg_finish_k) asks for a reseed.
+int window_epilogue(tbk_ctx* ctx, const ColIn& I, const ColOpt& O, tbk_groups_out* out, WgOut wo, int form, uint32_t m, bool direct_on,
+                    const int32_t* effend, ColResult* R, uint32_t* eb) {
+  const uint32_t B = 256, n = I.n, ng = wo.ng;
+  if (ng > out->cap_groups) {
+    out->n_groups = ng;
+    return TBK_E2BIG;
+  }
+  GroupAcc G{};
+  G.yc = wo.yc;
+  G.ns = wo.ns;
+  G.yxin = wo.yxin;
+  G.ydin = wo.ydin;
+  G.rep = wo.rep;
+  G.first = wo.first;
+  G.tie = wo.tie;
+  G.orep = out->rep;
+  int32_t* g_yd = ws_alloc<int32_t>(ctx, ng);
+  if (form != TBK_ROUTE_RAW_WINDOW) {
+    wo.gperm = ws_alloc<uint32_t>(ctx, ng);
+    wo.ginv = wo.has_ginv ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
+  }
+  if (!wo.gperm || (wo.has_ginv && !wo.ginv)) return TBK_ENOMEM;
+  // (items placed by list leave their distances with the items, yd_lgather_k: nothing accumulates in g_yd then)
+  if (!wo.yd_by_list) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
+  const uint64_t* png = ctx->d_scalars + 1;  // (tbk_window_groups left the group count there)
+  if (!wo.ties_done) TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng, B), B, 0, I, O.strategy, png, wo.gmem, G, wo.gperm, wo.ginv);
+  if (!direct_on)  // (nothing was written in key order: every group is written here)
+    TBK_LAUNCH(ctx, "col_write", col_write_k<false>, cdiv(ng, B), B, 0, png, wo.gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,
+               out->yx, out->g_start, out->g_end, effend, out->rep_effend, out->g_key, O.strategy);
+  else if (!wo.ties_done)  // (wg_back=split: the members of tie sets are rewritten here)
+    TBK_LAUNCH(ctx, "col_write", col_write_k<true>, cdiv(ng, B), B, 0, png, wo.gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,
+               out->yx, out->g_start, out->g_end, effend, out->rep_effend, out->g_key, O.strategy);
+  if (out->rec_group) TBK_LAUNCH(ctx, "col_recgroup", col_recgroup_w_k, cdiv(n, B), B, 0, n, wo.rec_sg, wo.ginv, out->rec_group);
+  TBK_TRY(tbk_sync_err(ctx, eb));
+  if (*eb) return (*eb & TBK_DERR_COLLISION) ? 0 : tbk_derr_to_status(ctx, *eb);  // (these kernels hand nothing on: any other bit is an error)
+  R->form = form;
+  R->m = m;
+  R->ng = ng;
+  R->G = G;
+  R->g_yd = g_yd;
+  R->gperm = wo.gperm;
+  R->ginv = wo.ginv;
+  R->win = wo;
+  return 0;
+}
+
+// ---- raw window form: plain tiles without an explicit merge priority (and group partials, `part`) go from the input records straight
+// to the groups (wgroup.hip) ----
+int route_raw_window(tbk_ctx* ctx, const ColIn& I, const ColOpt& O, bool part, tbk_groups_out* out, ColResult* R, uint32_t* eb) {
+  WgRawIn raw;
+  raw.O = O;
+  raw.part = part;
+  // (the compaction pass writes the results at their key-order places; only the members of tie sets are rewritten behind it)
+  WgDirectOut& direct = raw.direct;
+  direct.cap = out->cap_groups;
+  direct.rep = out->rep, direct.yc = out->yc, direct.yx = out->yx;
+  direct.g_start = out->g_start, direct.g_end = out->g_end, direct.rep_effend = out->rep_effend, direct.g_key = out->g_key;
+  direct.strategy = O.strategy;
+  const bool direct_on = out->rep && out->yc && out->yx;
+  if (!direct_on) direct.rep = nullptr;  // (the caller's arrays are not all there)
+  WgCall call{I, O.strategy, O.seed, out->rec_group != nullptr};
+  call.raw = &raw;
+  WgOut wo;
+  TBK_TRY(tbk_window_groups(ctx, call, &wo, eb));
+  if (*eb) return 0;
+  const uint32_t m = (uint32_t)ctx->h_scalars[0];
+  out->n_passed = m;
+  if (m == 0) return 0;
+  return window_epilogue(ctx, I, O, out, wo, TBK_ROUTE_RAW_WINDOW, m, direct_on, nullptr, R, eb);
+}
+
+// ---- compacted window form: the general front end, then the groups straight from the position-sorted runs of the passing records,
+// no record sort (wgroup.hip) ----
+int route_compacted_window(tbk_ctx* ctx, const ColIn& I, const ColOpt& O, ColArrays& A, tbk_groups_out* out, ColResult* R, uint32_t* eb) {
+  if (!A.ensure_front()) return TBK_ENOMEM;
+  if (!A.ceff && !(A.ceff = ws_alloc<uint32_t>(ctx, I.n))) return TBK_ENOMEM;
+  const SortBufs s2 = A.sb;
+  TBK_TRY(col_front_end(ctx, I, O, A, s2, A.ceff, true));
+  TBK_TRY(tbk_sync_err(ctx, eb));
+  if (*eb) return tbk_derr_to_status(ctx, *eb);
+  const uint32_t m = (uint32_t)ctx->h_scalars[0];
+  out->n_passed = m;
+  if (m == 0) return 0;
+  const WgCompactedIn compacted{s2.hi, s2.lo, s2.val, A.ceff, m, A.run_off, A.khi, A.klo};
+  WgCall call{I, O.strategy, O.seed, out->rec_group != nullptr};
+  call.compacted = &compacted;
+  WgOut wo;
+  TBK_TRY(tbk_window_groups(ctx, call, &wo, eb));
+  if (*eb) return 0;
+  return window_epilogue(ctx, I, O, out, wo, TBK_ROUTE_COMPACTED_WINDOW, m, false, A.effend, R, eb);
+}
+
+// ---- sort path: the general front end, the passing records ordered by key, groups from the heads of the sorted order ----
+int route_sort(tbk_ctx* ctx, const ColIn& I, const ColOpt& O, const CollapsePlan& plan, bool any_tbm, ColArrays& A, tbk_groups_out* out,
+               ColResult* R, uint32_t* eb) {
+  const uint32_t B = 256, n = I.n;
+  uint64_t* sc = ctx->d_scalars;
+  const bool lean = plan.lean;
+  if (!A.ensure_front() || !A.ensure_sort()) return TBK_ENOMEM;
+  SortBufs s2 = A.sb;
+  TBK_TRY(col_front_end(ctx, I, O, A, s2, nullptr, plan.use_runs));
+  uint32_t m = 0, ng = 0;
+  uint32_t m_hi = n, ng_hi = n;  // what sizes grids and arrays: the counts themselves, or their upper bound
+  if (!lean) {
+    TBK_TRY(tbk_sync_err(ctx, eb));
+    if (*eb) return tbk_derr_to_status(ctx, *eb);
+    m = (uint32_t)ctx->h_scalars[0];
+    out->n_passed = m;
+    if (m == 0) return 0;
+    m_hi = m;
+  }
+  // The files are position-sorted runs (verified by the scan above): merge them and order each (tid,start) bucket
+  // locally (msort.hip).  Many files, a small tile, or a bucket longer than the local window take the radix sort.
+  bool runs_now = plan.use_runs && (lean || m >= plan.runs_min);
+  for (;;) {
+    if (runs_now)
+      TBK_TRY(tbk_sort_runs(ctx, &s2, m_hi, A.run_off, I.k, ctx->d_err, (uint32_t*)(sc + 12)));  // sc[12]: zeroed with the counters by the driver
+    else
+      TBK_TRY(tbk_radix_sort128(ctx, &s2, m));
+    TBK_LAUNCH(ctx, "col_heads", col_heads_k, cdiv(m_hi, B), B, 0, I, O.strategy, sc + 0, m_hi, s2.hi, s2.lo, s2.val, A.fidx, A.flags,
+               A.ghead, ctx->d_err);
+    TBK_TRY(tbk_exscan_u32(ctx, A.ghead, A.gex, m_hi, sc + 1));
+    if (lean) break;
+    TBK_TRY(tbk_sync_err(ctx, eb));
+    if (runs_now && (*eb & TBK_DERR_BIGBUCKET)) {  // redo on the merged (phase-A) order, which the *2 side still holds
+      std::swap(s2.hi, s2.hi2);
+      std::swap(s2.lo, s2.lo2);
+      std::swap(s2.val, s2.val2);
+      TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
+      runs_now = false;
+      continue;
+    }
+    break;
+  }
+  if (!lean) {
+    if (*eb) return 0;  // (a collision: the driver reseeds)
+    ng = (uint32_t)ctx->h_scalars[1];
+    if (ng > out->cap_groups) {
+      out->n_groups = ng;
+      return TBK_E2BIG;
+    }
+    ng_hi = ng;
+  }
+  const uint64_t *pm = sc + 0, *png = sc + 1;
+  GroupAcc G{};
+  G.yc = ws_alloc<double>(ctx, ng_hi);
+  G.ns = ws_alloc<uint32_t>(ctx, ng_hi);
+  G.yxin = ws_alloc<long long>(ctx, ng_hi);
+  G.ydin = ws_alloc<long long>(ctx, ng_hi);
+  G.rep = ws_alloc<unsigned long long>(ctx, ng_hi);
+  G.first = ws_alloc<uint32_t>(ctx, ng_hi);
+  G.tie = ws_alloc<uint8_t>(ctx, ng_hi);
+  int32_t* g_yd = ws_alloc<int32_t>(ctx, ng_hi);
+  uint32_t* gperm = ws_alloc<uint32_t>(ctx, ng_hi);
+  uint32_t* ginv = ws_alloc<uint32_t>(ctx, ng_hi);
+  if (!ginv) return TBK_ENOMEM;
+  TBK_LAUNCH(ctx, "col_init_groups", col_init_groups_k, cdiv(ng_hi, B), B, 0, png, G, g_yd);
+  TBK_LAUNCH(ctx, "col_reduce", col_reduce_k, cdiv(m_hi, B), B, 0, I, O, pm, s2.val, A.flags, A.gex, A.fidx, A.effend, G, A.sgid, ctx->d_err);
+  if (I.prio_hi && I.prio_lo) TBK_LAUNCH(ctx, "col_rep_prio", col_rep_prio_k, cdiv(ng_hi, B), B, 0, I, png, pm, s2.val, G);
+  if (O.collapse_same) TBK_LAUNCH(ctx, "col_same", col_same_k, cdiv(m_hi, B), B, 0, I, O, pm, s2.val, A.flags, A.sgid, A.fidx, G);
+  TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng_hi, B), B, 0, I, O.strategy, png, s2.val, G, gperm, ginv);
+
+  // ---- ordered YC when a fractional term can occur (only --store-frac and TieBrush-merged inputs can bring one;
+  // such tiles are never lean, so m and ng are known here) ----
+  if (O.store_frac || any_tbm) {
+    TBK_TRY(tbk_sync_err(ctx, eb));
+    const bool need_ordered = O.store_frac || (*eb & TBK_DERR_FRACTIONAL);
+    *eb &= ~TBK_DERR_FRACTIONAL;
+    if (*eb) return tbk_derr_to_status(ctx, *eb);
+    if (need_ordered) {
+      TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
+      SortBufs ob;
+      ob.hi = ws_alloc<uint64_t>(ctx, m);
+      ob.lo = ws_alloc<uint64_t>(ctx, m);
+      ob.val = ws_alloc<uint32_t>(ctx, m);
+      ob.hi2 = ws_alloc<uint64_t>(ctx, m);
+      ob.lo2 = ws_alloc<uint64_t>(ctx, m);
+      ob.val2 = ws_alloc<uint32_t>(ctx, m);
+      uint8_t* fh_by_rec = ws_alloc<uint8_t>(ctx, n);
+      if (!ob.val2 || !fh_by_rec) return TBK_ENOMEM;
+      TBK_LAUNCH(ctx, "ord_fill", ord_fill_k, cdiv(m, B), B, 0, m, s2.val, A.sgid, A.effend, I.prio_hi, A.flags, ob.hi, ob.lo, ob.val, fh_by_rec);
+      TBK_TRY(tbk_radix_sort128(ctx, &ob, m));
+      TBK_LAUNCH(ctx, "ord_sum", ord_sum_k, cdiv(ng, 64), 64, 0, I, O, ng, m, ob.val, A.fidx, fh_by_rec, G);
+    }
+  }
+  TBK_LAUNCH(ctx, "col_write", col_write_k<false>, cdiv(ng_hi, B), B, 0, png, gperm, G, s2.hi, s2.lo, out->cap_groups, out->rep, out->yc,
+             out->yx, out->g_start, out->g_end, A.effend, out->rep_effend, out->g_key, O.strategy);
+  if (out->rec_group) TBK_LAUNCH(ctx, "col_recgroup", col_recgroup_k, cdiv(m_hi, B), B, 0, pm, s2.val, A.sgid, ginv, out->rec_group);
+  TBK_TRY(tbk_sync_err(ctx, eb));
+  *eb &= ~TBK_DERR_FRACTIONAL;  // (no error here: the ordered sum above has answered it)
+  // (lean: the counts arrive with this read-back — unless the tile goes round again, on the radix path or with the next seed)
+  if (lean && !(*eb & (TBK_DERR_BIGBUCKET | TBK_DERR_COLLISION))) {
+    m = (uint32_t)ctx->h_scalars[0];
+    ng = (uint32_t)ctx->h_scalars[1];
+    out->n_passed = m;
+  }
+  if (*eb) return 0;
+  R->form = TBK_ROUTE_SORT;
+  R->m = m;
+  R->ng = ng;
+  R->G = G;
+  R->g_yd = g_yd;
+  R->gperm = gperm;
+  R->ginv = ginv;
+  R->sorted = s2;
+  return 0;
+}
+
+// The YD stage's job, from the result of the route that finished the tile.
+YdJob* yd_job_of(const ColIn& I, const ColArrays& A, const ColResult& R, const tbk_groups_out* out) {
+  YdJob* job = new YdJob();
+  job->I = I;
+  job->m = R.m;
+  job->ng = R.ng;
+  job->cap = out->cap_groups;
+  job->win = R.form != TBK_ROUTE_SORT;
+  if (job->win) {
+    job->by_list = R.win.yd_by_list;
+    job->np = R.win.np;
+    job->pfile = R.win.pfile;
+    job->pgrp = R.win.pgrp;
+    job->gpoff = R.win.gpoff;
+    job->gfmask = R.win.gfmask;
+  }
+  job->val = job->win ? A.sb.val : R.sorted.val;  // (the window path's stage reads neither this nor the next three)
+  job->flags = A.flags;
+  job->fidx = A.fidx;
+  job->sgid = A.sgid;
+  job->ginv = R.ginv;
+  job->gperm = R.gperm;
+  job->G = R.G;
+  job->shi = job->win ? R.win.ghi : R.sorted.hi;
+  job->slo = job->win ? R.win.glo : R.sorted.lo;
+  job->g_yd = R.g_yd;
+  job->out_yd = out->yd;
+  return job;
+}
+}  // namespace
+
+int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_in* in, const CollapsePlanIn& plan_in, tbk_groups_out* out) {
+  const uint32_t n = in->n_records;
+  out->n_groups = 0;
+  out->n_passed = 0;
+  ctx->route = tbk_collapse_route{};
+  if (out->rec_group) TBK_HIP(hipMemsetAsync(out->rec_group, 0xFF, (size_t)n * 4, ctx->stream));
+  if (n == 0) return 0;
+  uint64_t* sc = ctx->d_scalars;  // [0]=n_pass [1]=n_groups [2]=n_items [3]=n_chains [4]=n_nodes
+  ColIn I;
+  ColOpt O;
+  TBK_TRY(col_inputs(ctx, o, in, &I, &O));
+  ColArrays A{ctx, n};
+  A.head_off = ws_alloc<uint32_t>(ctx, (size_t)in->n_files + 1);
+  A.run_off = ws_alloc<uint32_t>(ctx, (size_t)in->n_files + 1);
+  if (!A.head_off || !A.run_off) return TBK_ENOMEM;
+  CollapsePlan plan = collapse_plan(plan_in);
   const uint64_t seeds[4] = {TBK_KEY_SEED0, 0xA5A5F00DCAFE1234ull, 0x0123456789ABCDEFull, 0xDEADBEEF0BADF00Dull};
   int attempt = 0;
   // the route of this call for tbk_last_route: host bookkeeping, written back on every way out of the loop
@@ -2462,313 +2665,40 @@ int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_
       c->route.big_bucket = big;
     }
   } route{ctx, &attempt};
+  ColResult R;
   for (;;) {
     if (attempt == 4) return TBK_ECOLLISION;
     O.seed = seeds[attempt];
+    // (the counters and, in scalar 15, the device's error word: whatever bits sent the tile round again are cleared here)
     TBK_HIP(hipMemsetAsync(sc, 0, 16 * sizeof(uint64_t), ctx->stream));
-    if (use_raw && use_win) {
-      uint32_t eb = 0;
-      WgOut wo;
-      // (the compaction pass writes the results at their key-order places; only the members of tie sets are rewritten behind it)
-      WgDirectOut direct;
-      direct.cap = out->cap_groups;
-      direct.rep = out->rep, direct.yc = out->yc, direct.yx = out->yx;
-      direct.g_start = out->g_start, direct.g_end = out->g_end, direct.rep_effend = out->rep_effend, direct.g_key = out->g_key;
-      direct.strategy = O.strategy;
-      const bool direct_on = out->rep && out->yc && out->yx;
-      if (!direct_on) direct.rep = nullptr;
-      TBK_TRY(tbk_window_groups(ctx, I, O.strategy, nullptr, nullptr, nullptr, nullptr, n, I.file_off, nullptr, nullptr, out->rec_group != nullptr,
-                                O.seed, &wo, &eb, &O, part, &direct));
-      if (eb & (TBK_DERR_RAWORDER | TBK_DERR_BIGBUCKET | TBK_DERR_FRACTIONAL)) {  // not this path's kind of input (the general front end
-        TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));     // decides what is an error), or a pile-up beyond the
-        use_raw = false;                                                            // group table
-        route.handed_back |= (eb & TBK_DERR_RAWORDER) != 0;
-        route.big |= (eb & TBK_DERR_BIGBUCKET) != 0;
-        if ((eb & (TBK_DERR_BIGBUCKET | TBK_DERR_FRACTIONAL)) || part) use_win = false;
-        part = false;
-        continue;
-      }
-      if (eb & TBK_DERR_COLLISION) {  // reseed
-        ++attempt;
-        continue;
-      }
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      m = (uint32_t)ctx->h_scalars[0];
-      out->n_passed = m;
-      if (m == 0) return 0;
-      ng = wo.ng;
-      if (ng > out->cap_groups) {
-        out->n_groups = ng;
-        return TBK_E2BIG;
-      }
-      G.yc = wo.yc;
-      G.ns = wo.ns;
-      G.yxin = wo.yxin;
-      G.ydin = wo.ydin;
-      G.rep = wo.rep;
-      G.first = wo.first;
-      G.tie = wo.tie;
-      G.orep = out->rep;
-      g_yd = ws_alloc<int32_t>(ctx, ng);
-      // the output order and its inverse (made where col_recgroup_w_k or yd_fill_w_k, items NOT placed by list, will read it) come with
-      // the groups: the compaction wrote the identity and wg_tie_k permuted the tie sets of several groups and rewrote their members'
-      // results (wo.ties_done; wg_back=split: col_tie_sort_k and col_write_k<tied only> do both here, a pass over every group each)
-      gperm = wo.gperm;
-      ginv = wo.ginv;
-      // (items placed by list leave their distances with the items, yd_lgather_k: nothing accumulates in g_yd then)
-      const bool yd_by_list = !wo.pgrp || tbk_yd_by_list(ctx, I.k);
-      if (!gperm || ((out->rec_group || !yd_by_list) && !ginv)) return TBK_ENOMEM;
-      if (!yd_by_list) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
-      const uint64_t* png = sc + 1;  // (tbk_window_groups left the group count there)
-      if (!wo.ties_done) TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng, B), B, 0, I, O.strategy, png, wo.gmem, G, gperm, ginv);
-      // (effend == nullptr: the effective end of the representative — or the low word of its explicit priority — rides in the
-      // high word of G.rep)
-      if (direct_on && !wo.ties_done)
-        TBK_LAUNCH(ctx, "col_write", col_write_k<true>, cdiv(ng, B), B, 0, png, gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,
-                   out->yx, out->g_start, out->g_end, (const int32_t*)nullptr, out->rep_effend, out->g_key, O.strategy);
-      else if (!direct_on)  // (the caller's arrays are not all there: nothing was written in key order, every group is written here)
-        TBK_LAUNCH(ctx, "col_write", col_write_k<false>, cdiv(ng, B), B, 0, png, gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,
-                   out->yx, out->g_start, out->g_end, (const int32_t*)nullptr, out->rep_effend, out->g_key, O.strategy);
-      if (out->rec_group) TBK_LAUNCH(ctx, "col_recgroup", col_recgroup_w_k, cdiv(n, B), B, 0, n, wo.rec_sg, ginv, out->rec_group);
-      TBK_TRY(tbk_sync_err(ctx, &eb));
-      if (eb & TBK_DERR_COLLISION) {  // (the verification: the compaction's waves, or wg_finish_raw_k): reseed
-        ++attempt;
-        continue;
-      }
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      win_out = wo;
-      win_done = true;
-      route.form = TBK_ROUTE_RAW_WINDOW;
-      if (attempt > 0) {
-        char b[96];
-        snprintf(b, sizeof(b), "info: key-hash collision, reseeded %d time(s)", attempt);
-        ctx->last_error = b;
-      }
-      break;
-    }
-    if (!front_arrays()) return TBK_ENOMEM;
-    if (use_win && !ceff) {
-      ceff = ws_alloc<uint32_t>(ctx, n);
-      if (!ceff) return TBK_ENOMEM;
-    }
-    SortBufs s2 = sb;
-    TBK_LAUNCH(ctx, "col_keys", col_keys_k, cdiv(n, B), B, 0, I, O, khi, klo, kend, kflags, fidx, ctx->d_err);
-    {
-      EffLoad ld{khi, kend, kflags};
-      EffStore st{khi, klo, kflags, effend, s2.hi, s2.lo, s2.val, sc + 0, n, ctx->d_err, fidx, head_off, use_win ? ceff : nullptr, I.prio_hi};
-      EffKey ident{0u, 0u, INT32_MIN, 0u};
-      TBK_TRY((scan_op_run<EffKey, EffOp, EffLoad, EffStore>(ctx, "col_effkey_scan", n, ld, st, EffOp{}, ident, true)));
-    }
-    if (use_runs || use_win) TBK_LAUNCH(ctx, "col_runs", col_runs_k, cdiv(I.k + 1, B), B, 0, I.k, I.file_off, head_off, sc + 0, run_off);
     uint32_t eb = 0;
-    if (use_win) {
-      // ---- window path (wgroup.hip): groups straight from the position-sorted runs, no record sort ----
-      TBK_TRY(tbk_sync_err(ctx, &eb));
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      m = (uint32_t)ctx->h_scalars[0];
-      out->n_passed = m;
-      if (m == 0) return 0;
-      WgOut wo;
-      TBK_TRY(tbk_window_groups(ctx, I, O.strategy, s2.hi, s2.lo, s2.val, ceff, m, run_off, khi, klo, out->rec_group != nullptr, O.seed, &wo, &eb));
-      if (eb & TBK_DERR_BIGBUCKET) {  // a pile-up with more distinct alignments than the LDS table holds: sort path
-        TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-        use_win = false;
-        route.big = true;
-        continue;
-      }
-      if (eb & TBK_DERR_COLLISION) {  // reseed
-        ++attempt;
-        continue;
-      }
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      ng = wo.ng;
-      if (ng > out->cap_groups) {
-        out->n_groups = ng;
-        return TBK_E2BIG;
-      }
-      G.yc = wo.yc;
-      G.ns = wo.ns;
-      G.yxin = wo.yxin;
-      G.ydin = wo.ydin;
-      G.rep = wo.rep;
-      G.first = wo.first;
-      G.tie = wo.tie;
-      g_yd = ws_alloc<int32_t>(ctx, ng);
-      gperm = ws_alloc<uint32_t>(ctx, ng);
-      // (items placed by list leave their distances with the items, yd_lgather_k: nothing accumulates in g_yd then)
-      const bool yd_by_list = !wo.pgrp || tbk_yd_by_list(ctx, I.k);
-      // the inverse permutation has two readers on this path, col_recgroup_w_k and yd_fill_w_k (items NOT placed by list): not made
-      // when neither will run
-      ginv = (out->rec_group || !yd_by_list) ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
-      if (!gperm || ((out->rec_group || !yd_by_list) && !ginv)) return TBK_ENOMEM;
-      if (!yd_by_list) TBK_HIP(hipMemsetAsync(g_yd, 0, (size_t)ng * 4, ctx->stream));
-      const uint64_t* png = sc + 1;  // (tbk_window_groups left the group count there)
-      TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng, B), B, 0, I, O.strategy, png, wo.gmem, G, gperm, ginv);
-      TBK_LAUNCH(ctx, "col_write", col_write_k<false>, cdiv(ng, B), B, 0, png, gperm, G, wo.ghi, wo.glo, out->cap_groups, out->rep, out->yc,
-                 out->yx, out->g_start, out->g_end, effend, out->rep_effend, out->g_key, O.strategy);
-      if (out->rec_group) TBK_LAUNCH(ctx, "col_recgroup", col_recgroup_w_k, cdiv(n, B), B, 0, n, wo.rec_sg, ginv, out->rec_group);
-      TBK_TRY(tbk_sync_err(ctx, &eb));
-      if (eb & TBK_DERR_COLLISION) {  // (the verification pass of the window path, wg_finish_k): reseed
-        ++attempt;
-        continue;
-      }
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      win_out = wo;
-      win_done = true;
-      route.form = TBK_ROUTE_COMPACTED_WINDOW;
-      if (attempt > 0) {
-        char b[96];
-        snprintf(b, sizeof(b), "info: key-hash collision, reseeded %d time(s)", attempt);
-        ctx->last_error = b;
-      }
-      break;
-    }
-    if (!sort_path_arrays()) return TBK_ENOMEM;
-    s2.val2 = sb.val2;
-    uint32_t m_hi = n, ng_hi = n;  // what sizes grids and arrays: the counts themselves, or their upper bound
-    if (!lean) {
-      TBK_TRY(tbk_sync_err(ctx, &eb));
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      m = (uint32_t)ctx->h_scalars[0];
-      out->n_passed = m;
-      if (m == 0) return 0;
-      m_hi = m;
-    }
-    // The files are position-sorted runs (verified by the scan above): merge them and order each (tid,start) bucket
-    // locally (msort.hip).  Many files, a small tile, or a bucket longer than the local window take the radix sort.
-    bool runs_now = use_runs && (lean || m >= runs_min);
-    for (;;) {
-      if (runs_now)
-        TBK_TRY(tbk_sort_runs(ctx, &s2, m_hi, run_off, I.k, ctx->d_err, (uint32_t*)(sc + 12)));  // sc[12]: zeroed with the counters above
-      else
-        TBK_TRY(tbk_radix_sort128(ctx, &s2, m));
-      TBK_LAUNCH(ctx, "col_heads", col_heads_k, cdiv(m_hi, B), B, 0, I, O.strategy, sc + 0, m_hi, s2.hi, s2.lo, s2.val, fidx, flags,
-                 ghead, ctx->d_err);
-      TBK_TRY(tbk_exscan_u32(ctx, ghead, gex, m_hi, sc + 1));
-      if (lean) break;
-      TBK_TRY(tbk_sync_err(ctx, &eb));
-      if (runs_now && (eb & TBK_DERR_BIGBUCKET)) {  // redo on the merged (phase-A) order, which the *2 side still holds
-        std::swap(s2.hi, s2.hi2);
-        std::swap(s2.lo, s2.lo2);
-        std::swap(s2.val, s2.val2);
-        TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-        runs_now = false;
-        continue;
-      }
-      break;
-    }
-    if (!lean) {
-      if (eb & TBK_DERR_COLLISION) {  // reseed
-        ++attempt;
-        continue;
-      }
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      ng = (uint32_t)ctx->h_scalars[1];
-      if (ng > out->cap_groups) {
-        out->n_groups = ng;
-        return TBK_E2BIG;
-      }
-      ng_hi = ng;
-    }
-    const uint64_t *pm = sc + 0, *png = sc + 1;
-    G.yc = ws_alloc<double>(ctx, ng_hi);
-    G.ns = ws_alloc<uint32_t>(ctx, ng_hi);
-    G.yxin = ws_alloc<long long>(ctx, ng_hi);
-    G.ydin = ws_alloc<long long>(ctx, ng_hi);
-    G.rep = ws_alloc<unsigned long long>(ctx, ng_hi);
-    G.first = ws_alloc<uint32_t>(ctx, ng_hi);
-    G.tie = ws_alloc<uint8_t>(ctx, ng_hi);
-    g_yd = ws_alloc<int32_t>(ctx, ng_hi);
-    gperm = ws_alloc<uint32_t>(ctx, ng_hi);
-    ginv = ws_alloc<uint32_t>(ctx, ng_hi);
-    if (!ginv) return TBK_ENOMEM;
-    TBK_LAUNCH(ctx, "col_init_groups", col_init_groups_k, cdiv(ng_hi, B), B, 0, png, G, g_yd);
-    TBK_LAUNCH(ctx, "col_reduce", col_reduce_k, cdiv(m_hi, B), B, 0, I, O, pm, s2.val, flags, gex, fidx, effend, G, sgid, ctx->d_err);
-    if (I.prio_hi && I.prio_lo) TBK_LAUNCH(ctx, "col_rep_prio", col_rep_prio_k, cdiv(ng_hi, B), B, 0, I, png, pm, s2.val, G);
-    if (O.collapse_same) TBK_LAUNCH(ctx, "col_same", col_same_k, cdiv(m_hi, B), B, 0, I, O, pm, s2.val, flags, sgid, fidx, G);
-    TBK_LAUNCH(ctx, "col_tie_sort", col_tie_sort_k, cdiv(ng_hi, B), B, 0, I, O.strategy, png, s2.val, G, gperm, ginv);
-
-    // ---- ordered YC when a fractional term can occur (only --store-frac and TieBrush-merged inputs can bring one;
-    // such tiles are never lean, so m and ng are known here) ----
-    if (O.store_frac || any_tbm) {
-      TBK_TRY(tbk_sync_err(ctx, &eb));
-      const bool need_ordered = O.store_frac || (eb & TBK_DERR_FRACTIONAL);
-      eb &= ~TBK_DERR_FRACTIONAL;
-      if (eb) return tbk_derr_to_status(ctx, eb);
-      if (need_ordered) {
-        TBK_HIP(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-        SortBufs ob;
-        ob.hi = ws_alloc<uint64_t>(ctx, m);
-        ob.lo = ws_alloc<uint64_t>(ctx, m);
-        ob.val = ws_alloc<uint32_t>(ctx, m);
-        ob.hi2 = ws_alloc<uint64_t>(ctx, m);
-        ob.lo2 = ws_alloc<uint64_t>(ctx, m);
-        ob.val2 = ws_alloc<uint32_t>(ctx, m);
-        uint8_t* fh_by_rec = ws_alloc<uint8_t>(ctx, n);
-        if (!ob.val2 || !fh_by_rec) return TBK_ENOMEM;
-        TBK_LAUNCH(ctx, "ord_fill", ord_fill_k, cdiv(m, B), B, 0, m, s2.val, sgid, effend, I.prio_hi, flags, ob.hi, ob.lo, ob.val, fh_by_rec);
-        TBK_TRY(tbk_radix_sort128(ctx, &ob, m));
-        TBK_LAUNCH(ctx, "ord_sum", ord_sum_k, cdiv(ng, 64), 64, 0, I, O, ng, m, ob.val, fidx, fh_by_rec, G);
-      }
-    }
-    TBK_LAUNCH(ctx, "col_write", col_write_k<false>, cdiv(ng_hi, B), B, 0, png, gperm, G, s2.hi, s2.lo, out->cap_groups, out->rep, out->yc,
-               out->yx, out->g_start, out->g_end, effend, out->rep_effend, out->g_key, O.strategy);
-    if (out->rec_group) TBK_LAUNCH(ctx, "col_recgroup", col_recgroup_k, cdiv(m_hi, B), B, 0, pm, s2.val, sgid, ginv, out->rec_group);
-    TBK_TRY(tbk_sync_err(ctx, &eb));
-    if (lean) {
-      if (eb & TBK_DERR_BIGBUCKET) {  // same keys again, on the radix path (the counts are read back there)
-        use_runs = false;
-        lean = false;
-        continue;
-      }
-      if (eb & TBK_DERR_COLLISION) {  // reseed
-        ++attempt;
-        continue;
-      }
-      m = (uint32_t)ctx->h_scalars[0];
-      ng = (uint32_t)ctx->h_scalars[1];
-      out->n_passed = m;
-    }
-    if (eb & ~TBK_DERR_FRACTIONAL) return tbk_derr_to_status(ctx, eb);
-    sb = s2;
-    route.form = TBK_ROUTE_SORT;
-    if (attempt > 0) {
-      char b[96];
-      snprintf(b, sizeof(b), "info: key-hash collision, reseeded %d time(s)", attempt);
-      ctx->last_error = b;
-    }
-    break;
+    if (plan.route == COLP_ROUTE_RAW_WINDOW)
+      TBK_TRY(route_raw_window(ctx, I, O, plan.part, out, &R, &eb));
+    else if (plan.route == COLP_ROUTE_COMPACTED_WINDOW)
+      TBK_TRY(route_compacted_window(ctx, I, O, A, out, &R, &eb));
+    else
+      TBK_TRY(route_sort(ctx, I, O, plan, plan_in.tbm_any, A, out, &R, &eb));
+    const CollapseNext next = collapse_plan_after(plan, eb);
+    route.handed_back |= next.raw_handed_back;
+    route.big |= next.big_bucket;
+    if (next.action == COLP_ERROR) return tbk_derr_to_status(ctx, eb);
+    if (next.action == COLP_DONE) break;
+    if (next.action == COLP_RESEED) ++attempt;
+    plan = next.plan;
   }
-  out->n_groups = ng;
-  if (m == 0) return 0;
-  if (ng > out->cap_groups) return TBK_E2BIG;
+  if (R.form == TBK_ROUTE_NONE) return 0;  // nothing passed
+  route.form = R.form;
+  if (attempt > 0) {
+    char b[96];
+    snprintf(b, sizeof(b), "info: key-hash collision, reseeded %d time(s)", attempt);
+    ctx->last_error = b;
+  }
+  out->n_groups = R.ng;
+  if (R.m == 0) return 0;
+  if (R.ng > out->cap_groups) return TBK_E2BIG;
   TBK_TRY(tbk_check_launch(ctx, "collapse"));
   // ---- YD stage: handed to the caller (tbk_api) as a job — run inline or deferred on the side context ----
-  YdJob* job = new YdJob();
-  job->I = I;
-  job->m = m;
-  job->ng = ng;
-  job->cap = out->cap_groups;
-  if (win_done) {
-    job->win = true;
-    job->np = win_out.np;
-    job->pfile = win_out.pfile;
-    job->pgrp = win_out.pgrp;
-    job->gpoff = win_out.gpoff;
-    job->gfmask = win_out.gfmask;
-  }
-  job->val = sb.val;
-  job->flags = flags;
-  job->fidx = fidx;
-  job->sgid = sgid;
-  job->ginv = ginv;
-  job->gperm = gperm;
-  job->G = G;
-  job->shi = win_done ? win_out.ghi : sb.hi;
-  job->slo = win_done ? win_out.glo : sb.lo;
-  job->g_yd = g_yd;
-  job->out_yd = out->yd;
-  ctx->yd_job = job;
+  ctx->yd_job = yd_job_of(I, A, R, out);
   return 0;
 }
 

@@ -9,6 +9,7 @@
 #include <vector>
 #include <new>
 
+#include "collapse_plan.hpp"
 #include "tbk_internal.h"
 
 // ---- workspace arena ------------------------------------------------------------------------------
@@ -195,6 +196,25 @@ void tbk_stage_release(tbk_ctx* ctx) {
     return;
   }
   (void)hipEventRecord(ctx->stage_ev, ctx->stream);
+}
+int tbk_stage_upload(tbk_ctx* ctx, const TbkHostTable* tables, int n_tables) {
+  size_t total = 0;
+  for (int i = 0; i < n_tables; ++i) total += tables[i].bytes;
+  const bool staged = total <= 4096 * sizeof(uint64_t);
+  char* stage = staged ? (char*)tbk_stage_acquire(ctx) : nullptr;
+  for (int i = 0; i < n_tables; ++i) {
+    const TbkHostTable& t = tables[i];
+    const void* src = t.src;
+    if (!src) {
+      TBK_HIP(hipMemsetAsync(t.dst, 0, t.bytes, ctx->stream));
+      continue;
+    }
+    if (staged) src = memcpy(stage, src, t.bytes), stage += t.bytes;
+    TBK_HIP(hipMemcpyAsync(t.dst, src, t.bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (staged) tbk_stage_release(ctx);
+  else TBK_HIP(hipStreamSynchronize(ctx->stream));
+  return 0;
 }
 
 int tbk_check_launch(tbk_ctx* ctx, const char* what) {
@@ -803,10 +823,18 @@ int tbk_collapse_tile(tbk_ctx* ctx, const tbk_collapse_opts* opts, const tbk_soa
   if (opts->strategy == TBK_STRAT_FULL && in->n_records && (!in->md_off || !in->md_has)) return TBK_EINVAL;
   if (opts->collapse_same && (!in->qname_hash || !in->qname_off || (in->n_records && !in->qname))) return TBK_EINVAL;  // -A compares names
   if ((in->prio_hi == nullptr) != (in->prio_lo == nullptr)) return TBK_EINVAL;
-  bool any_tb = false;
+  // what the route decision reads of the call (collapse_plan.hpp): filled in here, once, for the arena hints and for the driver
+  CollapsePlanIn pin;
+  pin.n_records = in->n_records, pin.n_cigar_ops = in->n_cigar_ops, pin.n_files = in->n_files;
+  uint32_t n_tb = 0;
   if (in->tbmerged)
-    for (uint32_t f = 0; f < in->n_files; ++f) any_tb |= in->tbmerged[f] != 0;
-  if (in->n_records && any_tb && (!in->yc_in || !in->yx_in || !in->yd_in)) return TBK_EINVAL;
+    for (uint32_t f = 0; f < in->n_files; ++f) n_tb += in->tbmerged[f] != 0;
+  pin.tbm_none = n_tb == 0, pin.tbm_any = n_tb != 0, pin.tbm_all = n_tb == in->n_files;
+  pin.has_prio = in->prio_hi && in->prio_lo;
+  pin.has_carried = in->yc_in && in->yx_in && in->yd_in;
+  pin.strategy = opts->strategy, pin.store_frac = opts->store_frac, pin.collapse_same = opts->collapse_same;
+  pin.path = ctx->dbg.path, pin.raw = ctx->dbg.raw, pin.sort = ctx->dbg.sort;
+  if (in->n_records && pin.tbm_any && !pin.has_carried) return TBK_EINVAL;
   // a device-resident tile (e.g. tbk_bam_decode) may deliver its groups to host arrays; host input needs host output
   if (in->mem != out->mem && !(in->mem == TBK_MEM_DEVICE && out->mem == TBK_MEM_HOST)) return TBK_EINVAL;
   if (opts->defer_yd && (in->mem != TBK_MEM_DEVICE || out->mem != TBK_MEM_DEVICE)) return TBK_EINVAL;
@@ -814,14 +842,11 @@ int tbk_collapse_tile(tbk_ctx* ctx, const tbk_collapse_opts* opts, const tbk_soa
   TBK_HIP(hipSetDevice(ctx->device));
   tbk_prof_begin_call(ctx);
   // Arena hints.  The sort path keeps keys, sort buffers and per-record scratch (160 B per record); the window path in its raw form —
-  // large plain tiles, the predicate of tbk_collapse_device restated — works on the input where it lies and needs half of that
+  // the route of large plain tiles on the device (collapse_arena_lean) — works on the input where it lies and needs half of that
   // (config 3: 25 GB for 320 M records — scratch at the far end of the arena, the group arrays at the bottom — and 9.6 GB for its
   // YD stage, which borrows the range behind the group arrays when it is deferred).  A hint that proves too small costs one call with overflow
   // chunks, after which the arena has learnt its size.
-  bool lean = in->mem == TBK_MEM_DEVICE && !opts->store_frac && !opts->collapse_same && !in->prio_hi && ctx->dbg.path == 0 && ctx->dbg.raw < 0 &&
-              (in->n_records >= (8u << 20) || (in->n_files > 64 && in->n_records >= 65536));
-  if (lean && in->tbmerged)
-    for (uint32_t f = 0; f < in->n_files; ++f) lean = lean && in->tbmerged[f] == 0;
+  const bool lean = collapse_arena_lean(pin, collapse_plan(pin), in->mem == TBK_MEM_DEVICE);
   size_t hint = (size_t)in->n_records * (lean ? 84 : 160) + (size_t)in->n_cigar_ops * 8 + ((size_t)8 << 20);
   const auto pa = std::chrono::steady_clock::now();
   TBK_TRY(ws_begin_call(ctx, hint));
@@ -846,7 +871,7 @@ int tbk_collapse_tile(tbk_ctx* ctx, const tbk_collapse_opts* opts, const tbk_soa
     const size_t cap = out->cap_groups, n = in->n_records;
     TBK_TRY(out_dalloc(ctx, out, cap, n, opts->keep_results != 0, &dout));
     p_in = mark();
-    rc = tbk_collapse_device(ctx, opts, in, &dout);
+    rc = tbk_collapse_device(ctx, opts, in, pin, &dout);
     p_grp = mark();
     if (rc == 0 && ctx->yd_job) {
       void* job = ctx->yd_job;
@@ -859,7 +884,7 @@ int tbk_collapse_tile(tbk_ctx* ctx, const tbk_collapse_opts* opts, const tbk_soa
     if (rc == 0 && opts->keep_results) rc = keep_results(ctx, &dout);
     if (rc == 0) rc = out_d2h(ctx, out, &dout, n);
   } else if (in->mem == TBK_MEM_DEVICE) {
-    rc = tbk_collapse_device(ctx, opts, in, out);
+    rc = tbk_collapse_device(ctx, opts, in, pin, out);
     if (rc == 0 && ctx->yd_job) {
       void* job = ctx->yd_job;
       ctx->yd_job = nullptr;
@@ -922,7 +947,7 @@ int tbk_collapse_tile(tbk_ctx* ctx, const tbk_collapse_opts* opts, const tbk_soa
     size_t cap = out->cap_groups;
     TBK_TRY(out_dalloc(ctx, out, cap, n, opts->keep_results != 0, &dout));
     p_in = mark();
-    rc = tbk_collapse_device(ctx, opts, &din, &dout);
+    rc = tbk_collapse_device(ctx, opts, &din, pin, &dout);
     p_grp = mark();
     if (rc == 0 && ctx->yd_job) {
       void* job = ctx->yd_job;

@@ -286,6 +286,14 @@ extern "C" void tbk_bam_release(tbk_ctx* ctx);
 // upload out of it has run (a no-op almost always) and returns the block, tbk_stage_release marks the upload just queued
 void* tbk_stage_acquire(tbk_ctx* ctx);
 void tbk_stage_release(tbk_ctx* ctx);
+// Host tables of a call -> device.  The caller's arrays may be transient: small tables are staged through that block together, so the
+// upload is a true asynchronous copy and needs no wait; larger ones go straight from the caller's memory and are waited for.
+struct TbkHostTable {
+  void* dst;        // device
+  const void* src;  // host; nullptr: the device array is zeroed
+  size_t bytes;
+};
+int tbk_stage_upload(tbk_ctx* ctx, const TbkHostTable* tables, int n_tables);
 int tbk_sync_err(tbk_ctx* ctx, uint32_t* err_bits);    // d_scalars[0..15] -> h_scalars, stream sync, error bits
 int tbk_derr_to_status(tbk_ctx* ctx, uint32_t bits);
 
@@ -319,7 +327,8 @@ int tbk_sort_runs(tbk_ctx* ctx, SortBufs* b, uint32_t n_hi, const uint32_t* d_ru
                   uint32_t* nbig_zeroed);
 
 // ---- pipelines --------------------------------------------------------------------
-int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_in* in, tbk_groups_out* out);
+struct CollapsePlanIn;  // collapse_plan.hpp: what the route decision reads of the call (tbk_collapse_tile fills it in once)
+int tbk_collapse_device(tbk_ctx* ctx, const tbk_collapse_opts* o, const tbk_soa_in* in, const CollapsePlanIn& plan_in, tbk_groups_out* out);
 int tbk_collapse_warm(tbk_ctx* ctx);  // tbk_warmup: the first-use costs of the YD stage's machines
 int tbk_collapse_yd_run(tbk_ctx* run_on, void* job);  // consumes ctx->yd_job (prepared by tbk_collapse_device)
 int tbk_coverage_device(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_out* out);

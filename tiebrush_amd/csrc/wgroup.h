@@ -2,6 +2,7 @@
 #pragma once
 #include <stdlib.h>
 
+#include "collapse_plan.hpp"
 #include "strategy.hpp"
 #include "tbk_internal.h"
 
@@ -23,11 +24,15 @@ struct WgOut {
   unsigned long long* rep = nullptr;
   uint32_t* first = nullptr;        // == identity: the "sorted arrays" of the later stages are the group arrays
   uint8_t* tie = nullptr;
-  // RAW: output order -> group and (want_ginv) its inverse, written by the compaction (identity) and wg_tie_k (the tie sets of several
+  // RAW: output order -> group and (has_ginv) its inverse, written by the compaction (identity) and wg_tie_k (the tie sets of several
   // groups, whose members' results it also rewrites through the permutation).  ties_done == false (wg_back=split, or the compacted
   // form): the arrays are allocated, col_tie_sort_k and col_write_k fill them and place the results.
   uint32_t *gperm = nullptr, *ginv = nullptr;
   bool ties_done = false;
+  // Decided here once, for the caller's epilogue and the YD stage.  yd_by_list: the YD stage places its items by list (tbk_yd_by_list,
+  // or no incidence has a group array).  has_ginv: the inverse of the output order has a reader — col_recgroup_w_k (want_rec_sg) or
+  // yd_fill_w_k (items NOT placed by list) — and is made: by the raw form here, by the caller beside its gperm otherwise
+  bool yd_by_list = false, has_ginv = false;
 };
 
 // The caller's result arrays (tbk_groups_out), for the compaction pass to fill in key order — which IS the output order except inside
@@ -44,24 +49,41 @@ struct WgDirectOut {
   int strategy = 0;
 };
 
-// chi / clo / cval: the compacted passing records (k runs, run f = [run_off[f], run_off[f+1]), device offsets), m of them (host
-// value); ceff: the effective end of the k-way merge of every compacted record (or, for cross-rank tiles, the low word of the
-// explicit merge priority); scratch_hi / scratch_lo: two dead 8-byte-per-record arrays (>= m) to work in.
+// The two input forms of tbk_window_groups: a call carries exactly one.
+// COMPACTED: the passing records, compacted by the general front end of collapse.hip
+struct WgCompactedIn {
+  const uint64_t *chi, *clo;  // [m] the compacted passing records' keys: k runs, run f = [run_off[f], run_off[f+1])
+  const uint32_t* cval;       // [m] ... and their record numbers
+  const uint32_t* ceff;       // [m] the effective end of the k-way merge of every compacted record (or, for cross-rank tiles, the low
+                              // word of the explicit merge priority)
+  uint32_t m;                 // compacted records (host value)
+  const uint32_t* run_off;    // [k + 1] the runs' offsets, on the device
+  uint64_t *scratch_hi, *scratch_lo;  // two dead 8-byte-per-record arrays (>= m) to work in
+};
+// RAW: the windows are cut on the input records themselves (I.n of them, the runs are I.file_off on the device); keys, the filter and
+// the effective ends are computed inside the window kernels, the number of passing records is added to ctx->d_scalars[0] (zeroed by
+// the caller).  TBK_DERR_RAWORDER in *err_bits: the input is not of the shape this form takes — run the general path.
+struct WgRawIn {
+  tbkd::ColOpt O;      // the filter and the options of the key (the seed is the call's)
+  // part (k <= 64, every file TieBrush-merged, explicit priorities): the records are group partials of other ranks —
+  // WgOut::yc is the sum of the carried integral YC, yxin / ydin the sum / maximum of the carried YX / YD, no incidences (np = 0);
+  // TBK_DERR_FRACTIONAL in *err_bits: a carried value this form cannot hold — run the sort path.
+  bool part = false;
+  WgDirectOut direct;  // the caller's result arrays (rep == nullptr: the caller writes its results itself)
+};
+struct WgCall {
+  const tbkd::ColIn& I;
+  int strategy;
+  uint64_t seed;
+  bool want_rec_sg;  // WgOut::rec_sg is wanted
+  const WgCompactedIn* compacted = nullptr;
+  const WgRawIn* raw = nullptr;
+};
 // Returns 0 and fills *out (arrays from ctx's workspace), or a TBK status; TBK_DERR_BIGBUCKET / _COLLISION come back in *err_bits
 // (the counts in *out are then meaningless).  The kernels queued last (wg_compact's verification of the listed records, or wg_finish)
 // may still raise TBK_DERR_COLLISION in ctx->d_err: the caller's next read-back must treat it as a reseed request.
-int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const uint64_t* chi, const uint64_t* clo, const uint32_t* cval,
-                      const uint32_t* ceff, uint32_t m, const uint32_t* d_run_off, uint64_t* scratch_hi, uint64_t* scratch_lo,
-                      bool want_rec_sg, uint64_t seed, WgOut* out, uint32_t* err_bits, const tbkd::ColOpt* raw_opt = nullptr, bool part = false,
-                      const WgDirectOut* direct = nullptr /* RAW only */);
-// raw_opt != nullptr — RAW mode: the windows are cut on the input records themselves (chi .. ceff and the scratch arrays are
-// unused and may be null, m = I.n, d_run_off = I.file_off on the device); keys, the filter and the effective ends are computed
-// inside the window kernels, the number of passing records is added to ctx->d_scalars[0] (zeroed by the caller).
-// TBK_DERR_RAWORDER in *err_bits: the input is not of the shape this mode takes — run the general path.
-// part (RAW only, k <= 64, every file TieBrush-merged, explicit priorities): the records are group partials of other ranks
-//  — WgOut::yc is the sum of the carried integral YC, yxin / ydin the sum / maximum of the carried YX / YD, no
-// incidences (np = 0); TBK_DERR_FRACTIONAL in *err_bits: a carried value this form cannot hold — run the sort path.
-bool tbk_window_supported(uint32_t k);
+int tbk_window_groups(tbk_ctx* ctx, const WgCall& call, WgOut* out, uint32_t* err_bits);
+inline bool tbk_window_supported(uint32_t k) { return collapse_window_supported(k); }
 // The raw form's offsets pass on its own (test infrastructure: tests/support/offsets_probe.hip): the reference ids per chunk, then what
 // tbk_window_groups runs between its splitters and its window kernels — the stream or wave kernel (TbkDebug::wg_offsets_block, wg_og),
 // the edges, the transpose.  tid / pos: n records in k runs (d_run_off [k + 1], device), W: nW sorted bounds (any values).

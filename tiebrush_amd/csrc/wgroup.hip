@@ -2586,8 +2586,6 @@ __global__ __launch_bounds__(64) void wg_spread_sum_k(const unsigned long long* 
 
 }  // namespace
 
-bool tbk_window_supported(uint32_t k) { return k >= 1 && k <= 1024; }
-
 // the offsets matrix of k runs against nW bounds, bound-major in `off` ([nrows * k], nrows = nW + 2)
 static int wg_offsets_build(tbk_ctx* ctx, bool raw, const uint64_t* chi, const int32_t* rtid, const int32_t* rpos, const int32_t* ctid,
                             const uint32_t* d_run_off, uint32_t k,
@@ -2636,12 +2634,8 @@ int tbk_partial_reduce_device(tbk_ctx* ctx, int strategy, const int32_t* rows, u
   TBK_HIP(hipMemsetAsync(sc, 0, 16 * sizeof(uint64_t), ctx->stream));
   uint32_t* d_run_off = ws_alloc<uint32_t>(ctx, (size_t)k + 1);
   if (!d_run_off) return TBK_ENOMEM;
-  {
-    void* stage = tbk_stage_acquire(ctx);
-    memcpy(stage, run_off_host, (size_t)(k + 1) * 4);
-    TBK_HIP(hipMemcpyAsync(d_run_off, stage, (size_t)(k + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    tbk_stage_release(ctx);
-  }
+  const TbkHostTable run_off_table{d_run_off, run_off_host, (size_t)(k + 1) * 4};
+  TBK_TRY(tbk_stage_upload(ctx, &run_off_table, 1));
   uint64_t* chi = ws_alloc<uint64_t>(ctx, m);
   int32_t* r_tid = ws_alloc<int32_t>(ctx, m);
   int32_t* r_pos = ws_alloc<int32_t>(ctx, m);
@@ -2714,14 +2708,24 @@ int tbk_partial_reduce_device(tbk_ctx* ctx, int strategy, const int32_t* rows, u
 }
 
 
-int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const uint64_t* chi, const uint64_t* clo, const uint32_t* cval,
-                      const uint32_t* ceff, uint32_t m, const uint32_t* d_run_off, uint64_t* scratch_hi, uint64_t* scratch_lo,
-                      bool want_rec_sg, uint64_t seed, WgOut* out, uint32_t* err_bits, const tbkd::ColOpt* raw_opt, bool part,
-                      const WgDirectOut* direct) {
+int tbk_window_groups(tbk_ctx* ctx, const WgCall& call, WgOut* out, uint32_t* err_bits) {
+  const tbkd::ColIn& I = call.I;
+  const int strategy = call.strategy;
+  const uint64_t seed = call.seed;
+  const bool want_rec_sg = call.want_rec_sg;
   const uint32_t k = I.k;
   const uint32_t B = 256;
   *err_bits = 0;
-  const bool raw = raw_opt != nullptr;  // the records themselves are the runs: m = I.n, d_run_off = I.file_off, chi .. ceff unused
+  if ((call.raw != nullptr) == (call.compacted != nullptr)) return TBK_EINVAL;
+  const bool raw = call.raw != nullptr;  // the records themselves are the runs
+  const WgCompactedIn C = raw ? WgCompactedIn{nullptr, nullptr, nullptr, nullptr, I.n, I.file_off, nullptr, nullptr} : *call.compacted;
+  const uint64_t *chi = C.chi, *clo = C.clo;
+  const uint32_t *cval = C.cval, *ceff = C.ceff, *d_run_off = C.run_off;
+  const uint32_t m = C.m;
+  uint64_t *scratch_hi = C.scratch_hi, *scratch_lo = C.scratch_lo;
+  const tbkd::ColOpt* raw_opt = raw ? &call.raw->O : nullptr;
+  const bool part = raw && call.raw->part;
+  const WgDirectOut* direct = raw ? &call.raw->direct : nullptr;
   if (!tbk_window_supported(k) || m == 0) return TBK_EINVAL;
   if (part && (!raw || k > 64 || !I.prio_hi || !I.yc_in || !I.yx_in || !I.yd_in)) return TBK_EINVAL;
   // Everything allocated from here to the group arrays (`out`) is this stage's scratch — 80 bytes per record on the raw path — and
@@ -2971,6 +2975,8 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   if (T.fmask && !out->gfmask) return TBK_ENOMEM;
   out->pfile = ws_alloc<uint16_t>(ctx, np);
   out->pgrp = tbk_yd_by_list(ctx, k) ? nullptr : ws_alloc<uint32_t>(ctx, np);
+  out->yd_by_list = !out->pgrp;  // (no per-incidence group array: by list)
+  out->has_ginv = want_rec_sg || !out->yd_by_list;
   out->yc = lean ? nullptr : ws_alloc<double>(ctx, ng);
   out->ns = lean ? nullptr : ws_alloc<uint32_t>(ctx, ng);
   out->yxin = part ? ws_alloc<long long>(ctx, ng) : nullptr;
@@ -2982,12 +2988,11 @@ int tbk_window_groups(tbk_ctx* ctx, const tbkd::ColIn& I, int strategy, const ui
   out->rec_sg = want_rec_sg ? ws_alloc<uint32_t>(ctx, I.n) : nullptr;
   // (raw) the output order and its inverse.  The inverse has two readers, col_recgroup_w_k and yd_fill_w_k (items NOT placed by list):
   // not made when neither will run
-  const bool want_ginv = want_rec_sg || (out->pgrp && !tbk_yd_by_list(ctx, k));
   const bool back_split = ctx->dbg.wg_back_split;
   if (raw) {
     out->gperm = ws_alloc<uint32_t>(ctx, ng);
-    out->ginv = want_ginv ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
-    if (ng && (!out->gperm || (want_ginv && !out->ginv))) return TBK_ENOMEM;
+    out->ginv = out->has_ginv ? ws_alloc<uint32_t>(ctx, ng) : nullptr;
+    if (ng && (!out->gperm || (out->has_ginv && !out->ginv))) return TBK_ENOMEM;
     out->ties_done = !back_split;
   }
   ctx->ws_top_mode = true;
