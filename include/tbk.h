@@ -650,6 +650,52 @@ int tbk_sample_clip_regions(tbk_ctx* ctx, tbk_sample_out* rows, const tbk_region
  * tile is consumed; lifetimes, file_off_out and the TBK_EINVAL-before-anything-changes rule are tbk_tile_region's. */
 int tbk_tile_regions(tbk_ctx* ctx, const tbk_soa_in* tile, const tbk_regions* regions, tbk_soa_in* out, uint32_t* file_off_out, uint32_t* n_kept);
 
+/* ---- The bigWig's sections on the device (ABI version 9, appended) -----------------------------------------------------
+ * What `tiecov -W --bigwig-writer device` / `tiebrush --bigwig --bigwig-writer device` run.  The reference hands its intervals to
+ * libBigWig (tiecov.cpp:243-275); the contract here is the host writer's (host/bigwig.cpp): the same levels, reductions, sections and
+ * payload bytes, only compressed by the device's deflater. */
+
+/* tbk_bgzf_deflate, argument for argument, with zlib framing (RFC 1950) instead of BGZF members: every piece of the run (`cuts`, or
+ * pieces of 0xff00 bytes) becomes one zlib stream — 78 9C, one deflate block, the big-endian Adler-32 of the piece — and the streams
+ * lie back to back in HOST `out`.  stream_bytes (HOST, one entry per piece, required) receives their sizes; a piece of no bytes is the
+ * 8-byte stream of nothing.  TBK_E2BIG as there: *out_bytes (and stream_bytes) say what is needed, `out` is not touched. */
+int tbk_zlib_deflate(tbk_ctx* ctx, const uint8_t* src, uint64_t n, int src_mem, const uint64_t* cuts, uint32_t n_members, uint8_t* out,
+                     uint64_t out_cap, uint64_t* out_bytes, uint32_t* stream_bytes);
+
+typedef struct tbk_bw_section {
+  uint32_t chrom, start, end; /* the R-tree key of the section: its chromosome, first start, last end                   */
+  uint32_t reserved;
+  uint64_t offset;            /* of its zlib stream within the level's bytes                                            */
+  uint64_t size;              /* of that stream                                                                         */
+} tbk_bw_section;
+typedef struct tbk_bw_level {
+  uint32_t reduction;         /* bases per zoom record; 0: the data level                                               */
+  uint32_t max_payload;       /* the largest uncompressed section of the level                                          */
+  uint64_t n_items;           /* data: rows; zoom: records                                                              */
+  uint64_t n_sections;
+  uint64_t bytes;             /* of the level's streams                                                                 */
+  const tbk_bw_section* sections; /* HOST, context-owned: valid until the next tbk_bigwig_build on ctx or tbk_destroy  */
+} tbk_bw_level;
+#define TBK_BW_MAX_ZOOM 10
+typedef struct tbk_bw_out {
+  uint32_t n_levels;          /* 1 + nz: level[0] is the data, level[1 ..] the zoom levels, finest first                */
+  uint32_t reserved;
+  tbk_bw_level level[1 + TBK_BW_MAX_ZOOM];
+} tbk_bw_out;
+/* receives the streams of `level` in order, in slices of whole sections (valid during the call); nonzero stops the build (TBK_EINVAL) */
+typedef int (*tbk_bw_sink)(void* user, uint32_t level, const uint8_t* bytes, uint64_t n);
+/* rows: kind TBK_TRACK_COV, HOST or DEVICE, sorted by (tid, start), disjoint, end > start >= 0, tid in [0, n_ref); the value is
+ * (float)val.  ref_len[n_ref] (HOST) = the chromosome lengths.  Data sections end at a chromosome change or after 1024 rows: a 24-byte
+ * header (chrom, start, end, 0, 0, type 1, 0, count) and 12 bytes a row.  Zoom levels as BigWigWriter::close plans them: reduction
+ * max(32, 4 (covered / n + 1)), times 4 a level, while below 2^31 and at most TBK_BW_MAX_ZOOM; a level with more than half the
+ * records of the one before is dropped and ends the plan, one with fewer than 1000 is kept and ends it.  A zoom record is 32 bytes
+ * {chrom, start, end, valid, min, max, sum, sum of squares}; sum and squares add val * w (float) row by row in row order, as the host
+ * does, so the floats are the host's bit for bit.  Zoom sections: up to 1024 records of one chromosome, no header.
+ * Order of events: every row is validated (TBK_EINVAL for a row outside the rules above: nothing faults, no sink call, the context
+ * takes the next call); out->n_levels and every level's reduction and n_items are set; then per level its remaining fields and table,
+ * then its bytes to `sink`.  No rows: one empty data level, no sink call, status 0.  TBK_EUNSUPPORTED: a level of 2^31 records. */
+int tbk_bigwig_build(tbk_ctx* ctx, const tbk_track_rows* rows, uint32_t n_ref, const uint32_t* ref_len, tbk_bw_sink sink, void* user, tbk_bw_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1054,6 +1054,73 @@ class Context:
         assert len(text) == total.value
         return text
 
+    def zlib_deflate(self, payload, cuts=None, out_cap=None):
+        """tbk_zlib_deflate: a byte run (bytes, or a uint8 device tensor) -> the list of its pieces' zlib streams; cuts = payload
+        offsets of the piece boundaries ([0, ..., len(payload)]), default one piece per 0xff00 bytes.  out_cap: the room offered for
+        the streams (default: enough); when they do not fit, TbkError(TBK_E2BIG) with .needed (bytes) and .sizes (per stream)."""
+        keep = []
+        dev = _is_torch(payload)
+        n = _numel(payload) if dev else len(payload)
+        src = _addr(payload, np.uint8, keep, n) if dev else np.frombuffer(payload, dtype=np.uint8)
+        cp, nm = None, 0
+        if cuts is not None:
+            cuts = np.ascontiguousarray(cuts, dtype=np.uint64)
+            cp, nm = cuts.ctypes.data, len(cuts) - 1
+        pieces = nm if cuts is not None else (n + 0xff00 - 1) // 0xff00
+        sizes = np.zeros(max(pieces, 1), dtype=np.uint32)
+        cap = int(out_cap) if out_cap is not None else n + pieces * 64 + 4096
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        need = C.c_uint64(0)
+        self._order_after_torch(dev)
+        sp = src if dev else (src.ctypes.data if n else None)
+        rc = self.L.tbk_zlib_deflate(self.h, sp, n, _lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, cp, nm, out.ctypes.data, cap, C.byref(need),
+                                     sizes.ctypes.data)
+        if rc == -4:
+            e = TbkError(rc, "tbk_zlib_deflate: %d bytes needed" % int(need.value))
+            e.needed, e.sizes = int(need.value), sizes[:pieces].copy()
+            raise e
+        self._check(rc, "tbk_zlib_deflate")
+        if n == 0:
+            return []
+        assert int(sizes[:pieces].sum()) == int(need.value)
+        ends = np.cumsum(sizes[:pieces].astype(np.uint64))
+        return [out[int(e) - int(s):int(e)].tobytes() for s, e in zip(sizes[:pieces], ends)]
+
+    def bigwig_build(self, tid, start, end, val, ref_len):
+        """tbk_bigwig_build: the compressed sections of a bigWig file from coverage rows (numpy arrays or device tensors; the value is
+        taken as float32) and the chromosome lengths.  Returns the levels, data first: dicts of reduction (0: the data), n_items,
+        max_payload, bytes (the level's zlib streams back to back) and sections [(chrom, start, end, offset, size)]."""
+        keep = []
+        dev = _is_torch(tid)
+        n = _numel(tid)
+        rows = _lib.TrackRows(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, _lib.TRACK["cov"], n, 0, _addr(tid, np.int32, keep, n),
+                              _addr(start, np.int32, keep, n), _addr(end, np.int32, keep, n), _addr(val, np.float64, keep, n), None, None, None, 0)
+        lens = np.ascontiguousarray(ref_len, dtype=np.uint32)
+        self._order_after_torch(dev)
+        out = _lib.BwOut()
+        parts = {}
+        tables = {}
+
+        def sink(_user, level, p, nb):
+            if level not in tables:   # (the level's table is complete before its first byte)
+                lv = out.level[level]
+                tables[level] = [(int(s.chrom), int(s.start), int(s.end), int(s.offset), int(s.size))
+                                 for s in lv.sections[:int(lv.n_sections)]]
+            parts.setdefault(level, []).append(C.string_at(p, nb))
+            return 0
+
+        cb = _lib.BW_SINK(sink)
+        self._check(self.L.tbk_bigwig_build(self.h, C.byref(rows), len(lens), lens.ctypes.data if len(lens) else None, cb, None, C.byref(out)),
+                    "tbk_bigwig_build")
+        levels = []
+        for k in range(int(out.n_levels)):
+            lv = out.level[k]
+            data = b"".join(parts.get(k, []))
+            assert len(data) == int(lv.bytes) and len(tables.get(k, [])) == int(lv.n_sections)
+            levels.append(dict(reduction=int(lv.reduction), n_items=int(lv.n_items), max_payload=int(lv.max_payload), bytes=data,
+                               sections=tables.get(k, [])))
+        return levels
+
 
 def index_query(bam_path, tid, beg, end, index_path=None):
     """tbh_index_query: the chunks [(vbeg, vend)] a reader of [beg, end) on reference tid has to read, through the file's index

@@ -17,6 +17,8 @@
 //                        zero-advance matrices), minimum-redundancy code lengths (deflate_codes.h, one lane), the dynamic block header,
 //                        and the token bits OR-ed into LDS at their prefix-summed bit offsets; one coalesced copy to the member's slot
 //     bgz_gather_k       the members' slots -> one contiguous run (sizes prefix-summed on the device)
+//   tbk_zlib_deflate   the same pieces as zlib streams (RFC 1950), what a bigWig section is (bigwig.hip: tbk_zlib_sections)
+//     zl_size_k / zl_gather_k   in the place of bgz_gather_k: 78 9C, the slot's deflate bytes, the payload's Adler-32
 //
 // Byte work: no MFMA.  The deflate kernel is bound by LDS round trips of dependent byte compares, not by HBM (it reads a payload byte
 // once and writes a quarter of one).
@@ -617,6 +619,79 @@ __global__ __launch_bounds__(256) void bgz_gather_k(uint32_t nmem, const uint8_t
   if (threadIdx.x < sz - tail0) d[tail0 + threadIdx.x] = s[tail0 + threadIdx.x];
 }
 
+// ---- zlib framing (tbk_zlib_deflate, the bigWig sections): a pass of its own behind bgz_deflate_k, which stays what it is --------------
+// A member's slot holds 18 header bytes, the raw deflate bytes and 8 trailer bytes: the zlib stream of the same payload is the two
+// bytes 78 9C, those deflate bytes and the payload's Adler-32, big-endian.  msize[m] -> the stream's size, in place (a piece of no
+// bytes, which bgz_deflate_k skips, becomes the 8-byte stream of one empty fixed block).
+__global__ __launch_bounds__(256) void zl_size_k(uint32_t nmem, uint32_t* __restrict__ msize) {
+  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= nmem) return;
+  const uint32_t sz = msize[m];
+  msize[m] = sz ? sz - 26u + 6u : 8u;
+}
+// the streams packed back to back; a block per member.  Adler-32 of the payload (RFC 1950): a = 1 + sum d_i, b = n + sum (n - i) d_i,
+// both mod 65521.  The b sum passes 2^32 inside 0xff00 bytes of large values, so both sums are 64-bit integers (any order gives the
+// same integer) and the remainder is taken once.
+__global__ __launch_bounds__(256) void zl_gather_k(uint32_t nmem, const DfMember* __restrict__ mem, const uint8_t* __restrict__ src,
+                                                   const uint8_t* __restrict__ slots, const uint32_t* __restrict__ zsize,
+                                                   const uint64_t* __restrict__ zoff, uint8_t* __restrict__ out) {
+  __shared__ unsigned long long red_a[4], red_b[4];
+  const uint32_t m = blockIdx.x;
+  if (m >= nmem) return;
+  const DfMember M = mem[m];
+  const uint32_t n = M.n, sz = zsize[m];
+  uint8_t* d = out + zoff[m];
+  if (n == 0) {
+    const uint8_t empty[8] = {0x78, 0x9c, 0x03, 0x00, 0x00, 0x00, 0x00, 0x01};
+    if (threadIdx.x < 8) d[threadIdx.x] = empty[threadIdx.x];
+    return;
+  }
+  const uint8_t* p = src + M.src;
+  unsigned long long sa = 0, sb = 0;
+  const uint32_t nw = n >> 2;
+  for (uint32_t w = threadIdx.x; w < nw; w += 256) {
+    uint32_t v;
+    __builtin_memcpy(&v, p + 4 * (size_t)w, 4);
+    const uint32_t i = 4 * w, d0 = v & 0xFFu, d1 = (v >> 8) & 0xFFu, d2 = (v >> 16) & 0xFFu, d3 = v >> 24;
+    sa += d0 + d1 + d2 + d3;
+    sb += (unsigned long long)(n - i) * d0 + (unsigned long long)(n - i - 1) * d1 + (unsigned long long)(n - i - 2) * d2 +
+          (unsigned long long)(n - i - 3) * d3;
+  }
+  if (threadIdx.x < (n & 3u)) {
+    const uint32_t i = nw * 4 + threadIdx.x;
+    sa += p[i];
+    sb += (unsigned long long)(n - i) * p[i];
+  }
+#pragma unroll
+  for (int k = 32; k > 0; k >>= 1) {
+    sa += (unsigned long long)__shfl_xor((long long)sa, k);
+    sb += (unsigned long long)__shfl_xor((long long)sb, k);
+  }
+  if ((threadIdx.x & 63u) == 0) red_a[threadIdx.x >> 6] = sa, red_b[threadIdx.x >> 6] = sb;
+  // the deflate bytes meanwhile: the destination starts at any byte, the slot's deflate bytes at byte 18
+  const uint8_t* s = slots + (size_t)m * DF_SLOT + 18;
+  const uint32_t len = sz - 6u;
+  uint8_t* q = d + 2;
+  const uint32_t head = min(len, (uint32_t)((4u - ((uintptr_t)q & 3u)) & 3u));
+  if (threadIdx.x < head) q[threadIdx.x] = s[threadIdx.x];
+  const uint32_t cw = (len - head) >> 2;
+  for (uint32_t i = threadIdx.x; i < cw; i += 256) {
+    uint32_t v;
+    __builtin_memcpy(&v, s + head + 4 * (size_t)i, 4);
+    *(uint32_t*)(q + head + 4 * (size_t)i) = v;
+  }
+  const uint32_t tail0 = head + cw * 4;
+  if (threadIdx.x < len - tail0) q[tail0 + threadIdx.x] = s[tail0 + threadIdx.x];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t a = (uint32_t)((1ull + red_a[0] + red_a[1] + red_a[2] + red_a[3]) % 65521ull);
+    const uint32_t b = (uint32_t)(((unsigned long long)n + red_b[0] + red_b[1] + red_b[2] + red_b[3]) % 65521ull);
+    d[0] = 0x78, d[1] = 0x9c;
+    uint8_t* t = d + 2 + len;
+    t[0] = (uint8_t)(b >> 8), t[1] = (uint8_t)b, t[2] = (uint8_t)(a >> 8), t[3] = (uint8_t)a;
+  }
+}
+
 // ---- records: plan, emit, cut --------------------------------------------------------------------------------------------------
 
 __device__ __forceinline__ uint32_t rd32(const uint8_t* p) {
@@ -969,8 +1044,9 @@ int deflate_grid(tbk_ctx* ctx) {
 }
 
 // payload run (device) + member table (device) -> packed members in *d_out (device, EB_PACKED) and their total size
+// (zlib: the same members as zlib streams — zl_size_k / zl_gather_k in the place of bgz_gather_k; *d_moff then holds the streams' offsets)
 int deflate_members(tbk_ctx* ctx, const uint8_t* d_src, const DfMember* d_mem, uint32_t nmem, uint8_t** d_out, uint64_t* total,
-                    const uint64_t** d_moff = nullptr) {
+                    const uint64_t** d_moff = nullptr, bool zlib = false) {
   *total = 0;
   *d_out = nullptr;
   if (nmem == 0) return 0;
@@ -987,6 +1063,7 @@ int deflate_members(tbk_ctx* ctx, const uint8_t* d_src, const DfMember* d_mem, u
   TBK_HIP(hipMemsetAsync(ctx->d_scalars, 0, 16 * sizeof(uint64_t), ctx->stream));
   TBK_HIP(hipMemsetAsync(msize + nmem, 0, 4, ctx->stream));
   TBK_LAUNCH(ctx, "bgz_deflate", bgz_deflate_k, grid, DF_NT, L_END, nmem, d_mem, d_src, slots, msize, tok, counter, ctx->d_err);
+  if (zlib) TBK_LAUNCH(ctx, "zl_size", zl_size_k, cdiv(nmem, 256), 256, 0, nmem, msize);
   TBK_TRY(tbk_exscan_u32_u64(ctx, msize, moff, nmem + 1, ctx->d_scalars + 1));
   uint32_t eb = 0;
   TBK_TRY(tbk_sync_err(ctx, &eb));
@@ -997,7 +1074,8 @@ int deflate_members(tbk_ctx* ctx, const uint8_t* d_src, const DfMember* d_mem, u
   *total = ctx->h_scalars[1];
   uint8_t* packed;
   TBK_TRY(enc_buf(ctx, EB_PACKED, (size_t)*total + 16, (void**)&packed));
-  TBK_LAUNCH(ctx, "bgz_gather", bgz_gather_k, nmem, 256, 0, nmem, slots, msize, moff, packed);
+  if (zlib) TBK_LAUNCH(ctx, "zl_gather", zl_gather_k, nmem, 256, 0, nmem, d_mem, d_src, slots, msize, moff, packed);
+  else TBK_LAUNCH(ctx, "bgz_gather", bgz_gather_k, nmem, 256, 0, nmem, slots, msize, moff, packed);
   *d_out = packed;
   if (d_moff) *d_moff = moff;
   return 0;
@@ -1025,8 +1103,11 @@ void tbk_enc_free(tbk_ctx* ctx) {
   ctx->enc = nullptr;
 }
 
-extern "C" int tbk_bgzf_deflate(tbk_ctx* ctx, const uint8_t* src, uint64_t n, int src_mem, const uint64_t* cuts, uint32_t n_members, uint8_t* out,
-                                uint64_t out_cap, uint64_t* out_bytes) {
+namespace {
+// tbk_bgzf_deflate, and tbk_zlib_deflate (stream_bytes: the HOST array of the streams' sizes) — nothing else differs
+int deflate_run(tbk_ctx* ctx, const uint8_t* src, uint64_t n, int src_mem, const uint64_t* cuts, uint32_t n_members, uint8_t* out, uint64_t out_cap,
+                uint64_t* out_bytes, uint32_t* stream_bytes) {
+  const bool zlib = stream_bytes != nullptr;
   if (!ctx || !out_bytes || (n && !src)) return TBK_EINVAL;
   *out_bytes = 0;
   if (n == 0) return 0;
@@ -1063,12 +1144,41 @@ extern "C" int tbk_bgzf_deflate(tbk_ctx* ctx, const uint8_t* src, uint64_t n, in
   TBK_HIP(hipStreamSynchronize(ctx->stream));  // (mt is a local)
   uint8_t* packed;
   uint64_t total;
-  TBK_TRY(deflate_members(ctx, d_src, d_mem, nmem, &packed, &total));
+  const uint64_t* d_moff = nullptr;
+  TBK_TRY(deflate_members(ctx, d_src, d_mem, nmem, &packed, &total, &d_moff, zlib));
   *out_bytes = total;
+  if (zlib) {  // (the sizes are known whether or not the bytes fit)
+    std::vector<uint64_t> off((size_t)nmem + 1);
+    TBK_HIP(hipMemcpyAsync(off.data(), d_moff, off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    for (uint32_t m = 0; m < nmem; ++m) stream_bytes[m] = (uint32_t)(off[m + 1] - off[m]);
+  }
   if (total > out_cap || (total && !out)) return TBK_E2BIG;
   TBK_HIP(hipMemcpyAsync(out, packed, total, hipMemcpyDeviceToHost, ctx->stream));
   TBK_HIP(hipStreamSynchronize(ctx->stream));
-  return tbk_check_launch(ctx, "bgzf_deflate");
+  return tbk_check_launch(ctx, zlib ? "zlib_deflate" : "bgzf_deflate");
+}
+}  // namespace
+
+extern "C" int tbk_bgzf_deflate(tbk_ctx* ctx, const uint8_t* src, uint64_t n, int src_mem, const uint64_t* cuts, uint32_t n_members, uint8_t* out,
+                                uint64_t out_cap, uint64_t* out_bytes) {
+  return deflate_run(ctx, src, n, src_mem, cuts, n_members, out, out_cap, out_bytes, nullptr);
+}
+extern "C" int tbk_zlib_deflate(tbk_ctx* ctx, const uint8_t* src, uint64_t n, int src_mem, const uint64_t* cuts, uint32_t n_members, uint8_t* out,
+                                uint64_t out_cap, uint64_t* out_bytes, uint32_t* stream_bytes) {
+  if (!stream_bytes) return TBK_EINVAL;
+  return deflate_run(ctx, src, n, src_mem, cuts, n_members, out, out_cap, out_bytes, stream_bytes);
+}
+
+// bigwig.hip's sections: a payload run and its cut table, both on the device, -> zlib streams packed back to back (*d_out) and their
+// offsets (*d_zoff, [nmem + 1]), in the encoder's buffers until its next call
+int tbk_zlib_sections(tbk_ctx* ctx, const uint8_t* d_src, const uint64_t* d_cut, uint32_t nmem, uint8_t** d_out, uint64_t* total, const uint64_t** d_zoff) {
+  *total = 0, *d_out = nullptr, *d_zoff = nullptr;
+  if (nmem == 0) return 0;
+  DfMember* d_mem;
+  TBK_TRY(enc_buf(ctx, EB_MISC, (size_t)nmem * sizeof(DfMember), (void**)&d_mem));
+  TBK_LAUNCH(ctx, "enc_members", enc_members_k, cdiv(nmem, 256), 256, 0, nmem, d_cut, d_mem);
+  return deflate_members(ctx, d_src, d_mem, nmem, d_out, total, d_zoff, true);
 }
 
 namespace {

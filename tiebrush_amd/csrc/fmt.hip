@@ -194,6 +194,22 @@ __global__ void fmt_cuts_k(const uint64_t* off, uint32_t n, uint32_t rows, uint3
 
 }  // namespace
 
+int tbk_pin_slices(tbk_ctx* ctx, size_t bytes) {
+  if (ctx->fmt_pin_cap >= bytes) return 0;
+  for (auto& p : ctx->fmt_pin)
+    if (p) (void)hipHostFree(p), p = nullptr;
+  ctx->fmt_pin_cap = 0;
+  for (auto& p : ctx->fmt_pin)
+    if (hipHostMalloc((void**)&p, bytes, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      p = nullptr;
+      ctx->last_error = "pinned staging allocation failed";
+      return TBK_ENOMEM;
+    }
+  ctx->fmt_pin_cap = bytes;
+  return 0;
+}
+
 int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes) {
   Rows R;
   R.kind = rows->kind;
@@ -243,19 +259,7 @@ int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink s
   for (uint32_t s = 0; s < ns; ++s) slice_max = std::max(slice_max, cut[s + 1] - cut[s]);
   char* dbuf[2] = {ws_alloc<char>(ctx, slice_max + 16), ns > 1 ? ws_alloc<char>(ctx, slice_max + 16) : nullptr};
   if (!dbuf[0] || (ns > 1 && !dbuf[1])) return TBK_ENOMEM;
-  if (ctx->fmt_pin_cap < slice_max) {
-    for (auto& p : ctx->fmt_pin)
-      if (p) (void)hipHostFree(p), p = nullptr;
-    ctx->fmt_pin_cap = 0;
-    for (auto& p : ctx->fmt_pin)
-      if (hipHostMalloc((void**)&p, slice_max, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        p = nullptr;
-        ctx->last_error = "tbk_format_track: pinned staging allocation failed";
-        return TBK_ENOMEM;
-      }
-    ctx->fmt_pin_cap = slice_max;
-  }
+  TBK_TRY(tbk_pin_slices(ctx, slice_max));
   hipEvent_t ev[2] = {tbk_event(ctx), tbk_event(ctx)};
   if (!ev[0] || !ev[1]) return TBK_EHIP;
   int rc = 0;

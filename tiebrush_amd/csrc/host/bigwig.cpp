@@ -171,70 +171,60 @@ bool BigWigWriter::write_index(const std::vector<Block>& blocks, uint64_t* index
   return true;
 }
 
-bool BigWigWriter::close(std::string& err) {
-  auto fail = [&](const char* what) {
-    err = std::string(what) + " (" + path_ + ")";
-    if (f_) fclose(f_);
-    f_ = nullptr;
+
+bool BigWigWriter::fail(std::string& err, const char* what) {
+  err = std::string(what) + " (" + path_ + ")";
+  if (f_) fclose(f_);
+  f_ = nullptr;
+  return false;
+}
+
+bool BigWigWriter::restart(std::string& err) {
+  if (f_) fclose(f_);
+  f_ = fopen(path_.c_str(), "wb");
+  max_uncompressed_ = 0;
+  if (!f_) {
+    err = "cannot create " + path_;
     return false;
-  };
-  if (!f_) return fail("bigWig file is not open");
-  // ---- zoom plan: reductions of 4x from a first level a few times the mean interval, while a level still has many records
-  uint64_t covered = 0;
-  double vmin = 0, vmax = 0, vsum = 0, vsq = 0;
+  }
+  return true;
+}
+
+// the 40-byte total summary: one pass over the rows, double sums in row order
+BigWigWriter::Summary BigWigWriter::summarise() const {
+  Summary s;
   for (size_t i = 0; i < items_.size(); ++i) {
     const Item& it = items_[i];
     const double w = (double)(it.end - it.start), v = (double)it.val;
-    covered += it.end - it.start;
-    if (i == 0 || v < vmin) vmin = v;
-    if (i == 0 || v > vmax) vmax = v;
-    vsum += v * w;
-    vsq += v * v * w;
+    s.covered += it.end - it.start;
+    if (i == 0 || v < s.vmin) s.vmin = v;
+    if (i == 0 || v > s.vmax) s.vmax = v;
+    s.vsum += v * w;
+    s.vsq += v * v * w;
   }
-  struct ZRec {
-    uint32_t chrom, start, end, valid;
-    float mn, mx, sum, sq;
-  };
-  std::vector<uint32_t> reductions;
-  std::vector<std::vector<ZRec>> zoom;
-  if (!items_.empty()) {
-    uint64_t red = std::max<uint64_t>(32, 4 * (covered / items_.size() + 1));
-    for (int z = 0; z < MAX_ZOOM && red < (1ull << 31); ++z, red *= 4) {
-      std::vector<ZRec> recs;
-      for (const Item& it : items_) {  // bins aligned to multiples of the reduction; an interval feeds every bin it overlaps
-        for (uint64_t b = it.start / red; b * red < it.end; ++b) {
-          const uint32_t bs = (uint32_t)(b * red), be = (uint32_t)std::min<uint64_t>((b + 1) * red, UINT32_MAX);
-          const uint32_t lo = std::max(bs, it.start), hi = std::min(be, it.end);
-          if (recs.empty() || recs.back().chrom != it.chrom || recs.back().start != bs) {
-            const uint32_t clen = it.chrom < lens_.size() ? lens_[it.chrom] : be;
-            recs.push_back(ZRec{it.chrom, bs, std::min(be, std::max(clen, hi)), 0, it.val, it.val, 0.f, 0.f});
-          }
-          ZRec& r = recs.back();
-          const float w = (float)(hi - lo);
-          r.valid += hi - lo;
-          r.mn = std::min(r.mn, it.val);
-          r.mx = std::max(r.mx, it.val);
-          r.sum += it.val * w;
-          r.sq += it.val * it.val * w;
-        }
-      }
-      if (z > 0 && recs.size() * 2 > zoom.back().size()) break;  // no longer shrinking
-      reductions.push_back((uint32_t)red);
-      zoom.push_back(std::move(recs));
-      if (zoom.back().size() < 1000) break;
+  return s;
+}
+
+// ---- the layout: everything of the file but the sections' bytes.  begin(nz), then per level begin_level / the sections / end_level,
+// then finish.  Both section producers write through it, so the two kinds of file differ in their compressed bytes alone.
+class BigWigWriter::Layout {
+ public:
+  explicit Layout(BigWigWriter& w) : w_(w), f_(w.f_) {}
+  // fixed part (rewritten by finish with the offsets) and the chromosome tree
+  bool begin(uint32_t nz) {
+    nz_ = nz;
+    zdata_.assign(nz, 0);
+    zindex_.assign(nz, 0);
+    summary_off_ = 64 + 24ull * nz;
+    tree_off_ = summary_off_ + 40;
+    {
+      std::vector<uint8_t> zero((size_t)tree_off_, 0);
+      if (!put(f_, zero)) return false;
     }
-  }
-  const uint32_t nz = (uint32_t)zoom.size();
-  // ---- fixed part (rewritten at the end with the offsets), chromosome tree
-  const uint64_t summary_off = 64 + 24ull * nz;
-  const uint64_t tree_off = summary_off + 40;
-  {
-    std::vector<uint8_t> zero((size_t)tree_off, 0);
-    if (!put(f_, zero)) return fail("write failed");
-  }
-  uint32_t key = 1;
-  for (auto& n : names_) key = std::max<uint32_t>(key, (uint32_t)n.size());
-  {
+    const std::vector<std::string>& names_ = w_.names_;
+    const std::vector<uint32_t>& lens_ = w_.lens_;
+    uint32_t key = 1;
+    for (auto& n : names_) key = std::max<uint32_t>(key, (uint32_t)n.size());
     // leaves of up to BLOCK chromosomes (sorted by name, as a B+ tree needs), parents of up to BLOCK children; every node is
     // padded to BLOCK items so that the offsets are known before anything is written
     std::vector<uint32_t> order(names_.size());
@@ -249,7 +239,7 @@ bool BigWigWriter::close(std::string& err) {
     }
     const uint64_t node_bytes = 4 + (uint64_t)BLOCK * (key + 8);
     std::vector<uint64_t> level_off(level_nodes.size());
-    uint64_t off = tree_off + 32;
+    uint64_t off = tree_off_ + 32;
     for (size_t L = level_nodes.size(); L-- > 0;) {
       level_off[L] = off;
       off += level_nodes[L] * node_bytes;
@@ -292,15 +282,119 @@ bool BigWigWriter::close(std::string& err) {
         }
       }
     }
-    if (!put(f_, b.d)) return fail("write failed");
+    return put(f_, b.d);
   }
-  // ---- data sections
-  const uint64_t data_off = (uint64_t)ftello(f_);
-  std::vector<Block> blocks;
-  {
+  // level 0: the data's section count (patched by finish); a zoom level: its record count.  The sections follow.
+  bool begin_level(uint32_t L, uint64_t n_items) {
+    blocks.clear();
     Buf c;
-    c.u64(0);  // section count, patched below
-    if (!put(f_, c.d)) return fail("write failed");
+    if (L == 0) {
+      data_off_ = (uint64_t)ftello(f_);
+      c.u64(0);
+    } else {
+      zdata_[L - 1] = (uint64_t)ftello(f_);
+      c.u32((uint32_t)n_items);
+    }
+    return put(f_, c.d);
+  }
+  // the R-tree over the level's sections
+  bool end_level(uint32_t L) {
+    if (L == 0) {
+      n_data_sections_ = blocks.size();
+      return w_.write_index(blocks, &index_off_);
+    }
+    return w_.write_index(blocks, &zindex_[L - 1]);
+  }
+  // trailer; header, zoom headers, summary, section count
+  bool finish(const std::vector<uint32_t>& reductions, const Summary& sm) {
+    {
+      Buf m;
+      m.u32(BW_MAGIC);  // the file ends with the magic again
+      if (!put(f_, m.d)) return false;
+    }
+    Buf h;
+    h.u32(BW_MAGIC);
+    h.u16(4);
+    h.u16(nz_);
+    h.u64(tree_off_);
+    h.u64(data_off_);
+    h.u64(index_off_);
+    h.u16(0);
+    h.u16(0);
+    h.u64(0);
+    h.u64(summary_off_);
+    h.u32(w_.max_uncompressed_);
+    h.u64(0);
+    for (uint32_t z = 0; z < nz_; ++z) {
+      h.u32(reductions[z]);
+      h.u32(0);
+      h.u64(zdata_[z]);
+      h.u64(zindex_[z]);
+    }
+    h.u64(sm.covered);
+    h.f64(sm.vmin);
+    h.f64(sm.vmax);
+    h.f64(sm.vsum);
+    h.f64(sm.vsq);
+    if (fseeko(f_, 0, SEEK_SET) != 0 || !put(f_, h.d)) return false;
+    Buf c;
+    c.u64(n_data_sections_);
+    return fseeko(f_, (off_t)data_off_, SEEK_SET) == 0 && put(f_, c.d);
+  }
+  std::vector<Block> blocks;  // of the level being written
+
+ private:
+  BigWigWriter& w_;
+  FILE* f_;
+  uint32_t nz_ = 0;
+  uint64_t summary_off_ = 0, tree_off_ = 0, data_off_ = 0, index_off_ = 0, n_data_sections_ = 0;
+  std::vector<uint64_t> zdata_, zindex_;
+};
+
+// the writer's own section producer: zoom plan and records on this core, one compress2 call per section
+bool BigWigWriter::close(std::string& err) {
+  if (!f_) return fail(err, "bigWig file is not open");
+  const Summary sm = summarise();
+  // ---- zoom plan: reductions of 4x from a first level a few times the mean interval, while a level still has many records
+  struct ZRec {
+    uint32_t chrom, start, end, valid;
+    float mn, mx, sum, sq;
+  };
+  std::vector<uint32_t> reductions;
+  std::vector<std::vector<ZRec>> zoom;
+  if (!items_.empty()) {
+    uint64_t red = std::max<uint64_t>(32, 4 * (sm.covered / items_.size() + 1));
+    for (int z = 0; z < MAX_ZOOM && red < (1ull << 31); ++z, red *= 4) {
+      std::vector<ZRec> recs;
+      for (const Item& it : items_) {  // bins aligned to multiples of the reduction; an interval feeds every bin it overlaps
+        for (uint64_t b = it.start / red; b * red < it.end; ++b) {
+          const uint32_t bs = (uint32_t)(b * red), be = (uint32_t)std::min<uint64_t>((b + 1) * red, UINT32_MAX);
+          const uint32_t lo = std::max(bs, it.start), hi = std::min(be, it.end);
+          if (recs.empty() || recs.back().chrom != it.chrom || recs.back().start != bs) {
+            const uint32_t clen = it.chrom < lens_.size() ? lens_[it.chrom] : be;
+            recs.push_back(ZRec{it.chrom, bs, std::min(be, std::max(clen, hi)), 0, it.val, it.val, 0.f, 0.f});
+          }
+          ZRec& r = recs.back();
+          const float w = (float)(hi - lo);
+          r.valid += hi - lo;
+          r.mn = std::min(r.mn, it.val);
+          r.mx = std::max(r.mx, it.val);
+          r.sum += it.val * w;
+          r.sq += it.val * it.val * w;
+        }
+      }
+      if (z > 0 && recs.size() * 2 > zoom.back().size()) break;  // no longer shrinking
+      reductions.push_back((uint32_t)red);
+      zoom.push_back(std::move(recs));
+      if (zoom.back().size() < 1000) break;
+    }
+  }
+  const uint32_t nz = (uint32_t)zoom.size();
+  Layout lay(*this);
+  if (!lay.begin(nz)) return fail(err, "write failed");
+  // ---- data sections
+  if (!lay.begin_level(0, items_.size())) return fail(err, "write failed");
+  {
     size_t i = 0;
     while (i < items_.size()) {
       size_t j = i;
@@ -319,20 +413,14 @@ bool BigWigWriter::close(std::string& err) {
         s.u32(items_[q].end);
         s.f32(items_[q].val);
       }
-      if (!write_sections(s.d, items_[i].chrom, items_[i].start, items_[j - 1].end, blocks)) return fail("write failed");
+      if (!write_sections(s.d, items_[i].chrom, items_[i].start, items_[j - 1].end, lay.blocks)) return fail(err, "write failed");
       i = j;
     }
   }
-  uint64_t index_off = 0;
-  if (!write_index(blocks, &index_off)) return fail("write failed");
+  if (!lay.end_level(0)) return fail(err, "write failed");
   // ---- zoom levels
-  std::vector<uint64_t> zdata(nz), zindex(nz);
   for (uint32_t z = 0; z < nz; ++z) {
-    zdata[z] = (uint64_t)ftello(f_);
-    Buf c;
-    c.u32((uint32_t)zoom[z].size());
-    if (!put(f_, c.d)) return fail("write failed");
-    std::vector<Block> zb;
+    if (!lay.begin_level(1 + z, zoom[z].size())) return fail(err, "write failed");
     size_t i = 0;
     while (i < zoom[z].size()) {
       size_t j = i;
@@ -349,48 +437,65 @@ bool BigWigWriter::close(std::string& err) {
         s.f32(r.sum);
         s.f32(r.sq);
       }
-      if (!write_sections(s.d, zoom[z][i].chrom, zoom[z][i].start, zoom[z][j - 1].end, zb)) return fail("write failed");
+      if (!write_sections(s.d, zoom[z][i].chrom, zoom[z][i].start, zoom[z][j - 1].end, lay.blocks)) return fail(err, "write failed");
       i = j;
     }
-    if (!write_index(zb, &zindex[z])) return fail("write failed");
+    if (!lay.end_level(1 + z)) return fail(err, "write failed");
   }
-  {
-    Buf m;
-    m.u32(BW_MAGIC);  // the file ends with the magic again
-    if (!put(f_, m.d)) return fail("write failed");
-  }
-  // ---- header, zoom headers, summary, section count
-  Buf h;
-  h.u32(BW_MAGIC);
-  h.u16(4);
-  h.u16(nz);
-  h.u64(tree_off);
-  h.u64(data_off);
-  h.u64(index_off);
-  h.u16(0);
-  h.u16(0);
-  h.u64(0);
-  h.u64(summary_off);
-  h.u32(max_uncompressed_);
-  h.u64(0);
-  for (uint32_t z = 0; z < nz; ++z) {
-    h.u32(reductions[z]);
-    h.u32(0);
-    h.u64(zdata[z]);
-    h.u64(zindex[z]);
-  }
-  h.u64(covered);
-  h.f64(vmin);
-  h.f64(vmax);
-  h.f64(vsum);
-  h.f64(vsq);
-  if (fseeko(f_, 0, SEEK_SET) != 0 || !put(f_, h.d)) return fail("write failed");
-  Buf c;
-  c.u64(blocks.size());
-  if (fseeko(f_, (off_t)data_off, SEEK_SET) != 0 || !put(f_, c.d)) return fail("write failed");
+  if (!lay.finish(reductions, sm)) return fail(err, "write failed");
   if (fclose(f_) != 0) {
     f_ = nullptr;
-    return fail("write failed");
+    return fail(err, "write failed");
+  }
+  f_ = nullptr;
+  return true;
+}
+
+// sections from a feed: the same layout calls, driven by the producer's
+bool BigWigWriter::close_with(const std::function<bool(BigWigFeed&)>& produce, std::string& err) {
+  if (!f_) return fail(err, "bigWig file is not open");
+  const Summary sm = summarise();
+  struct Feed : BigWigFeed {
+    BigWigWriter& w;
+    Layout lay;
+    std::vector<uint32_t> reductions;
+    std::vector<uint64_t> n_items;
+    bool planned = false, io_ok = true;
+    int open_level = -1;
+    explicit Feed(BigWigWriter& w_) : w(w_), lay(w_) {}
+    bool io(bool ok) {
+      if (!ok) io_ok = false;
+      return ok;
+    }
+    bool plan(const uint32_t* red, const uint64_t* items, uint32_t nz) override {
+      if (planned) return false;
+      planned = true;
+      reductions.assign(red, red + nz);
+      n_items.assign(items, items + 1 + nz);
+      return io(lay.begin(nz));
+    }
+    bool level(uint32_t L, const BigWigSection* s, size_t n, uint32_t max_payload) override {
+      if (!planned || (int)L != open_level + 1 || L >= n_items.size()) return false;
+      if (open_level >= 0 && !io(lay.end_level((uint32_t)open_level))) return false;
+      if (!io(lay.begin_level(L, n_items[L]))) return false;
+      open_level = (int)L;
+      const uint64_t base = (uint64_t)ftello(w.f_);
+      for (size_t i = 0; i < n; ++i) lay.blocks.push_back(Block{s[i].chrom, s[i].start, s[i].end, base + s[i].off, s[i].size});
+      if (max_payload > w.max_uncompressed_) w.max_uncompressed_ = max_payload;
+      return true;
+    }
+    bool bytes(const void* p, size_t n) override { return open_level >= 0 && io(n == 0 || fwrite(p, 1, n, w.f_) == n); }
+  } feed(*this);
+  if (!produce(feed)) {
+    err = feed.io_ok ? "the section producer gave up" : "write failed";
+    err += " (" + path_ + ")";
+    return false;  // (the file stays open: restart() and close() can still write it)
+  }
+  if (!feed.planned || feed.open_level + 1 != (int)feed.n_items.size()) return fail(err, "the section producer left levels out");
+  if (!feed.lay.end_level((uint32_t)feed.open_level) || !feed.lay.finish(feed.reductions, sm)) return fail(err, "write failed");
+  if (fclose(f_) != 0) {
+    f_ = nullptr;
+    return fail(err, "write failed");
   }
   f_ = nullptr;
   return true;

@@ -86,6 +86,8 @@ static const char* USAGE =
     "  --junc PREFIX        also write tiecov's junction track of the output (as tiecov -j)\n"
     "  --samp PREFIX        also write tiecov's sample-count track of the output (as tiecov -s; needs @CO SAMPLE: header lines)\n"
     "  --bigwig             write the coverage track as PREFIX.bigwig (as tiecov -W; needs --cov)\n"
+    "  --bigwig-writer host|device   with --bigwig: the file's sections and zoom levels by this core with zlib (host, the default)\n"
+    "                       or by the GPU (device: the same payloads, compressed by the device's deflater)\n"
     "                       (the tracks are what tiecov writes when it reads OUT.bam; not with --ranks)\n"
     "  --index              also write the output's BAM index OUT.bam.bai (what samtools index makes of OUT.bam; not with --ranks,\n"
     "                       not when the output goes to standard output)\n"
@@ -610,7 +612,7 @@ static int fwrite_sink(void* user, const char* p, uint64_t n) { return fwrite(p,
 // The tracks of the whole output, as tiecov_main.cpp computes them from its decode of the file: coverage and junctions in one
 // tbk_coverage_tile, the sample counts in tbk_sample_tile, the text by tbk_format_track (the host formatter when the device
 // formatter refuses a value, or with TBK_TRACK_HOST_FMT).
-static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, TrackRecs& T, const std::vector<std::string>& names, int num_samples) {
+static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, TrackRecs& T, const std::vector<std::string>& names, int num_samples, bool bw_device) {
   TbkApi& api = dev.api;
   tbk_ctx* ctx = dev.ctx;
   auto t0 = tnow();
@@ -672,8 +674,10 @@ static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, Track
       ms_text += tms(a, tnow());
     }
     if (tf.cov_bw) {
-      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
-      tf.close_bigwig();
+      if (bw_device && !api.bigwig_build) GError("Error: --bigwig-writer device: libtbk.so lacks tbk_bigwig_build\n");
+      tbh::BigWigDevice bd;
+      bd.ctx = ctx, bd.build = api.bigwig_build, bd.strerror_ = api.strerror_, bd.last_error = api.last_error;
+      tf.write_bigwig(o.n_intervals, it.data(), is.data(), ie.data(), iv.data(), bw_device ? &bd : nullptr);
     }
     if (tf.junc) {
       tbk_track_rows r = rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
@@ -1407,9 +1411,9 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
 
 // the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
-  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", nullptr};
+  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", "bigwig-writer", nullptr};
   const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQFR");
-  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", nullptr};
+  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", nullptr};
   const int region_files = count_value_option(argc, argv, "regions-file", 'R', value_longs_R, "oNQFr");
   bool ranks = false, tracks = false, index = false, csi = false;
   for (int i = 1; i < argc; ++i) {
@@ -1437,7 +1441,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;index;csi;region=;regions-file=;SMLPEDVho:N:Q:F:r:R:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;index;csi;region=;regions-file=;SMLPEDVho:N:Q:F:r:R:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1497,6 +1501,8 @@ int main(int argc, char* argv[]) {
                     samp_prefix = args.getOpt("samp") ? args.getOpt("samp") : "";
   const bool bigwig = args.getOpt("bigwig") != nullptr;
   if (bigwig && cov_prefix.empty()) GError("Error: --bigwig needs --cov\n");
+  if (args.getOpt("bigwig-writer") && !bigwig) GError("Error: --bigwig-writer needs --bigwig\n");
+  const bool bw_device = args.getOpt("bigwig-writer") && tbh::parse_bigwig_writer(args.getOpt("bigwig-writer"));
   const bool want_index = args.getOpt("index") != nullptr;
   if (want_index && strcmp(outfname, "-") == 0)
     GError("Error: --index needs an output file (-o FILE): an index addresses file offsets, standard output has none\n");
@@ -1567,7 +1573,7 @@ int main(int argc, char* argv[]) {
   out.close();
   if (trecs) {
     dev.wait();
-    write_tracks(dev, env, tfiles, *trecs, inRecords.header()->target_name, num_samples);
+    write_tracks(dev, env, tfiles, *trecs, inRecords.header()->target_name, num_samples, bw_device);
   }
   auto t_closed = tnow();
   if (env.timing) fprintf(stderr, "writer closed at %.1f ms\n", tms(dev.t_start, t_closed));

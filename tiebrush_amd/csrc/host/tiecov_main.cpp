@@ -34,6 +34,8 @@ static const char* USAGE =
     "  -j PREFIX    splice junctions as BED\n"
     "  -s PREFIX    estimated number of samples per position as bedGraph (needs @CO SAMPLE: header lines)\n"
     "  -W           write the coverage (-c) as a bigWig file (PREFIX.bigwig) instead of a bedGraph\n"
+    "  --bigwig-writer host|device   with -W: who builds the file's sections and zoom levels — this core with zlib (host, the\n"
+    "               default) or the GPU (device: the same payloads, compressed by the device's deflater)\n"
     "  -r,--region REGION   only the tracks of REGION: NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive, commas allowed), read\n"
     "               through the file's index (input.bam.csi, input.bam.bai or input.bai; `tiebrush --index` / `--csi` write one)\n"
     "  -R,--regions-file FILE   the tracks of several regions in one run: FILE is BED (chrom start end, 0-based half-open; further\n"
@@ -44,11 +46,11 @@ static const char* USAGE =
 // ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
 // how often -r / --region is given (Args keeps the last value of a repeated option)
 static int count_region_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "regions-file", nullptr};
+  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", nullptr};
   return count_value_option(argc, argv, "region", 'r', value_longs, "csjR");
 }
 static int count_regions_file_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "region", nullptr};
+  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", nullptr};
   return count_value_option(argc, argv, "regions-file", 'R', value_longs, "csjr");
 }
 
@@ -73,7 +75,7 @@ struct TrackClip {
 
 // The rows of tbk_coverage_tile / tbk_sample_tile for `in` (host arrays, or a device view), cut to *clip where one is given, into the
 // open files of tf.  An input of no records goes the same way: the calls give no rows and status 0.
-static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int num_samples, tbh::TrackFiles& tf, const TrackClip* clip) {
+static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int num_samples, tbh::TrackFiles& tf, const TrackClip* clip, bool bw_device) {
   const size_t n = in.n_records, co = in.n_cigar_ops;
   const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
   FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
@@ -108,8 +110,9 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
     }
     if (coutf) tbh::emit_cov_lines(coutf, hdr->target_name, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());  // flushCoverage, tiecov.cpp:237
     if (cov_bw) {  // flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the same intervals, the value as a float
-      for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
-      tf.close_bigwig();
+      tbh::BigWigDevice bd;
+      bd.ctx = ctx, bd.build = tbk_bigwig_build, bd.strerror_ = tbk_strerror, bd.last_error = tbk_last_error;
+      tf.write_bigwig(o.n_intervals, it.data(), is.data(), ie.data(), iv.data(), bw_device ? &bd : nullptr);
     }
     if (joutf)  // CJunc::write, tiecov.cpp:91-95 (numbered from 1)
       tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
@@ -156,7 +159,7 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
 // normalised table of the BED file, through the table entries): every other statement is shared.
 static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::RegionTable& U, bool one, const std::string& index_file,
                         const std::string& covfname, const std::string& jfname, const std::string& sfname, bool bigwig,
-                        const std::chrono::steady_clock::time_point t0) {
+                        bool bw_device, const std::chrono::steady_clock::time_point t0) {
   const bool timing = getenv("TBK_TIMING") != nullptr;
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   // every refusal comes before an output file exists
@@ -207,7 +210,7 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
   tbh::TrackFiles tf;
   open_tracks(tf, hdr, covfname, jfname, sfname, bigwig);
   const TrackClip clip{&regs, one};
-  write_tracks(ctx, hdr, in, num_samples, tf, &clip);
+  write_tracks(ctx, hdr, in, num_samples, tf, &clip, bw_device);
   tf.close();
   if (timing)
     fprintf(stderr, "tiecov %s phases ms: %u regions | index %.1f | chunk reads %.1f (%llu bytes in %u chunks) | context up at %.1f | decode + filter %.1f (%u of %u records) | tracks %.1f\n",
@@ -217,7 +220,7 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
 }
 
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;DVWhc:s:j:r:R:");
+  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;DVWhc:s:j:r:R:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -236,6 +239,8 @@ int main(int argc, char* argv[]) {
     return 1;
   }
   const bool bigwig = args.getOpt('W') != nullptr;
+  if (args.getOpt("bigwig-writer") && !(bigwig && args.getOpt('c'))) GError("Error: --bigwig-writer needs -W (and -c)\n");
+  const bool bw_device = args.getOpt("bigwig-writer") && tbh::parse_bigwig_writer(args.getOpt("bigwig-writer"));
   if (args.getOpt("verbose") || args.getOpt('V')) {
     fprintf(stderr, "Running TieCov " VERSION ". Command line:\n");
     args.printCmdLine(stderr);
@@ -270,7 +275,7 @@ int main(int argc, char* argv[]) {
       if (!tbh::parse_region(*hdr, r, &rtid, &beg, &end, err)) GError("Error: %s\n", err.c_str());
       U.add(rtid, beg, end);
     }
-    return regions_main(hdr, infname, U, rf == nullptr, index_file, covfname, jfname, sfname, bigwig, t0);
+    return regions_main(hdr, infname, U, rf == nullptr, index_file, covfname, jfname, sfname, bigwig, bw_device, t0);
   }
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;
@@ -353,7 +358,7 @@ int main(int argc, char* argv[]) {
   in.yc = yc.data();
   in.strand = strand.data();
   in.yx = yx.data();
-  write_tracks(ctx, hdr, in, num_samples, tf, nullptr);
+  write_tracks(ctx, hdr, in, num_samples, tf, nullptr, bw_device);
   tf.close();
   tbk_destroy(ctx);
   return 0;

@@ -3,7 +3,10 @@
 
 #include <string.h>
 
+#include <stdlib.h>
+
 #include <algorithm>
+#include <chrono>
 
 #include "GSam.h"
 
@@ -24,6 +27,7 @@ void TrackFiles::open(std::string cov_prefix, std::string junc_prefix, std::stri
       std::string err;
       if (!bw.open(cov_prefix, names, lens, err)) GError("Error creating file %s\n", cov_prefix.c_str());
       cov_bw = true;
+      bw_lens = lens;
     } else {
       if (!ends_with(cov_prefix, ".bedgraph")) cov_prefix += ".bedgraph";
       cov = fopen(cov_prefix.c_str(), "w");
@@ -53,6 +57,90 @@ void TrackFiles::close_bigwig() {
   std::string err;
   if (!bw.close(err)) GError("Error: writing %s failed (%s)\n", cov_name.c_str(), err.c_str());
   cov_bw = false;
+}
+
+bool parse_bigwig_writer(const char* value) {
+  const std::string v = value ? value : "";
+  if (v == "device") return true;
+  if (v != "host") GError("Error: --bigwig-writer takes host or device (got '%s')\n", v.c_str());
+  return false;
+}
+
+namespace {
+// tbk_bigwig_build's events -> the writer's feed: the plan at the first event, a level's table before its first byte
+struct BwBridge {
+  BigWigFeed* feed;
+  const tbk_bw_out* out;
+  bool planned = false, failed = false;
+  int level = -1;
+  bool advance(uint32_t to) {  // plan, and the tables of every level up to `to`
+    if (!planned) {
+      uint32_t red[TBK_BW_MAX_ZOOM];
+      uint64_t items[1 + TBK_BW_MAX_ZOOM];
+      const uint32_t nz = out->n_levels - 1;
+      for (uint32_t L = 0; L <= nz; ++L) items[L] = out->level[L].n_items;
+      for (uint32_t z = 0; z < nz; ++z) red[z] = out->level[1 + z].reduction;
+      planned = true;
+      if (!feed->plan(red, items, nz)) return false;
+    }
+    while (level < (int)to) {
+      const tbk_bw_level& lv = out->level[++level];
+      std::vector<BigWigSection> sec((size_t)lv.n_sections);
+      for (size_t i = 0; i < sec.size(); ++i) {
+        const tbk_bw_section& s = lv.sections[i];
+        sec[i] = BigWigSection{s.chrom, s.start, s.end, s.offset, s.size};
+      }
+      if (!feed->level((uint32_t)level, sec.data(), sec.size(), lv.max_payload)) return false;
+    }
+    return true;
+  }
+  static int sink(void* user, uint32_t level, const uint8_t* bytes, uint64_t n) {
+    BwBridge* b = (BwBridge*)user;
+    if (b->advance(level) && b->feed->bytes(bytes, (size_t)n)) return 0;
+    b->failed = true;
+    return 1;
+  }
+};
+}  // namespace
+
+void TrackFiles::write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const BigWigDevice* dev) {
+  if (!cov_bw) return;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (uint32_t i = 0; i < n; ++i) bw.add((uint32_t)tid[i], (uint32_t)start[i], (uint32_t)end[i], (float)val[i]);
+  const char* writer = "host";
+  std::string err;
+  bool done = false;
+  if (dev) {
+    tbk_track_rows r;
+    memset(&r, 0, sizeof(r));
+    r.mem = TBK_MEM_HOST, r.kind = TBK_TRACK_COV, r.n = n, r.tid = tid, r.start = start, r.end = end, r.val = val;
+    tbk_bw_out out;
+    memset(&out, 0, sizeof(out));
+    int rc = 0;
+    bool write_failed = false;
+    done = bw.close_with(
+        [&](BigWigFeed& feed) {
+          BwBridge b{&feed, &out};
+          rc = dev->build(dev->ctx, &r, (uint32_t)bw_lens.size(), bw_lens.data(), BwBridge::sink, &b, &out);
+          if (rc == 0 && !b.advance(out.n_levels - 1)) b.failed = true;  // (levels without a byte: an empty data level)
+          write_failed = b.failed;
+          return rc == 0 && !b.failed;
+        },
+        err);
+    if (done) {
+      writer = "device";
+    } else {
+      if (write_failed || rc == 0) GError("Error: writing %s failed (%s)\n", cov_name.c_str(), err.c_str());
+      fprintf(stderr, "Warning: the device bigWig writer refused %s (%s: %s); the host writer takes it\n", cov_name.c_str(), dev->strerror_(rc),
+              dev->last_error(dev->ctx));
+      if (!bw.restart(err)) GError("Error: writing %s failed (%s)\n", cov_name.c_str(), err.c_str());
+    }
+  }
+  if (!done && !bw.close(err)) GError("Error: writing %s failed (%s)\n", cov_name.c_str(), err.c_str());
+  cov_bw = false;
+  if (getenv("TBK_TIMING"))
+    fprintf(stderr, "bigwig phase ms: writer %s | %u rows | %.1f\n", writer, n,
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
 void TrackFiles::close() {

@@ -10,6 +10,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../../include/tbk.h"
 #include "bigwig.h"
 #include "bgzf.h"
 
@@ -17,14 +18,30 @@ namespace tbh {
 
 // The open track files.  An empty prefix: that track is not written.  Coverage goes to stdout for "-" / "stdout", to PREFIX.bigwig
 // with `bigwig`, else to PREFIX.bedgraph; junctions to PREFIX.bed; the sample counts to PREFIX.bedgraph.  Errors are fatal (GError).
+// The device section producer of the bigWig (--bigwig-writer device) as a command line has it: tiecov links libtbk.so, tiebrush binds it
+// at run time, so the entry points travel as pointers.
+struct BigWigDevice {
+  tbk_ctx* ctx = nullptr;
+  decltype(&tbk_bigwig_build) build = nullptr;
+  decltype(&tbk_strerror) strerror_ = nullptr;
+  decltype(&tbk_last_error) last_error = nullptr;
+};
+// "host" / "device" -> false / true; anything else is fatal (GError)
+bool parse_bigwig_writer(const char* value);
+
 struct TrackFiles {
   FILE *cov = nullptr, *junc = nullptr, *samp = nullptr;
   BigWigWriter bw;
   bool cov_bw = false;
+  std::vector<uint32_t> bw_lens;  // the chromosome lengths the bigWig was opened with
   std::string cov_name;
   void open(std::string cov_prefix, std::string junc_prefix, std::string samp_prefix, bool bigwig, const std::vector<std::string>& names,
             const std::vector<uint32_t>& lens);
   void close_bigwig();  // (after every interval went to bw)
+  // The coverage rows into the bigWig and the file closed (flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the value as a float).
+  // dev == nullptr: the host producer.  Else the sections are tbk_bigwig_build's; a refusal of that call other than a failed write
+  // hands the file to the host producer (a line on stderr says so).  TBK_TIMING: a "bigwig phase" line on stderr for either.
+  void write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const BigWigDevice* dev);
   void close();
 };
 

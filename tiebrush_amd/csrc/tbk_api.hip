@@ -644,6 +644,7 @@ void tbk_destroy(tbk_ctx* ctx) {
   if (ctx->bounce) (void)hipHostFree(ctx->bounce);
   tbk_enc_free(ctx);
   tbk_ix_free(ctx);
+  tbk_bw_free(ctx);
   tbk_stager_free(ctx);
   if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
   if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);
@@ -1091,6 +1092,36 @@ int tbk_format_track(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink si
   const int rc = tbk_format_device(ctx, &d, sink, user, out_bytes);
   tbk_prof_end_call(ctx);
   return rc;
+}
+
+int tbk_bigwig_build(tbk_ctx* ctx, const tbk_track_rows* rows, uint32_t n_ref, const uint32_t* ref_len, tbk_bw_sink sink, void* user, tbk_bw_out* out) {
+  if (!ctx || !rows || !sink || !out || rows->n == UINT32_MAX) return TBK_EINVAL;
+  memset(out, 0, sizeof(*out));
+  out->n_levels = 1;
+  if (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE) return TBK_EINVAL;
+  if (rows->kind != TBK_TRACK_COV) return TBK_EINVAL;
+  const size_t n = rows->n;
+  if (n && (!rows->tid || !rows->start || !rows->end || !rows->val)) return TBK_EINVAL;
+  if (n_ref && !ref_len) return TBK_EINVAL;
+  if (n == 0) return 0;
+  TBK_HIP(hipSetDevice(ctx->device));
+  tbk_prof_begin_call(ctx);
+  struct ProfEnd {
+    tbk_ctx* c;
+    ~ProfEnd() { tbk_prof_end_call(c); }
+  } prof_end{ctx};
+  // (rows, the data payload at 12 bytes a row, per-row counts and offsets of a zoom level, the first zoom level's records)
+  TBK_TRY(ws_begin_call(ctx, n * 64 + (size_t)n_ref * 16 + ((size_t)16 << 20)));
+  RegGuard reg_guard{ctx};
+  tbk_track_rows d = *rows;
+  if (rows->mem == TBK_MEM_HOST) {
+    d.mem = TBK_MEM_DEVICE;
+    TBK_TRY(h2d(ctx, rows->tid, n, &d.tid));
+    TBK_TRY(h2d(ctx, rows->start, n, &d.start));
+    TBK_TRY(h2d(ctx, rows->end, n, &d.end));
+    TBK_TRY(h2d(ctx, rows->val, n, &d.val));
+  }
+  return tbk_bigwig_device(ctx, &d, n_ref, ref_len, sink, user, out);
 }
 
 }  // extern "C"

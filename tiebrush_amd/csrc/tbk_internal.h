@@ -198,10 +198,12 @@ struct tbk_ctx {
   uint32_t n_names = 0;
   void* fmt_pin[2] = {nullptr, nullptr};
   size_t fmt_pin_cap = 0;
+  void* bw = nullptr;            // the host section tables of the last tbk_bigwig_build (bigwig.hip)
 };
 void tbk_stager_free(tbk_ctx* ctx);
 void tbk_enc_free(tbk_ctx* ctx);
 void tbk_ix_free(tbk_ctx* ctx);
+void tbk_bw_free(tbk_ctx* ctx);
 // baix.hip: the index part of a run the encoder has just packed.  All pointers are device memory of the encoder, alive until its next call.
 struct TbkIxIn {
   uint32_t n;             // records
@@ -340,3 +342,9 @@ int tbk_sample_device(tbk_ctx* ctx, const tbk_cov_in* in, int32_t num_samples, t
 // fmt.hip: tbk_format_track's body (rows in device memory; the arena must be reserved by the caller) and tbk_track_names'
 int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes);
 int tbk_names_upload(tbk_ctx* ctx, uint32_t n_names, const uint64_t* off, const char* bytes);
+// the two pinned slice buffers of tbk_format_track / tbk_bigwig_build, at least `bytes` each
+int tbk_pin_slices(tbk_ctx* ctx, size_t bytes);
+// bgzdef.hip: a device payload run cut at d_cut[0 .. nmem] -> zlib streams back to back (*d_out) and their offsets (*d_zoff, [nmem + 1])
+int tbk_zlib_sections(tbk_ctx* ctx, const uint8_t* d_src, const uint64_t* d_cut, uint32_t nmem, uint8_t** d_out, uint64_t* total, const uint64_t** d_zoff);
+// bigwig.hip: tbk_bigwig_build's body (rows in device memory, n > 0; the arena must be reserved by the caller)
+int tbk_bigwig_device(tbk_ctx* ctx, const tbk_track_rows* rows, uint32_t n_ref, const uint32_t* ref_len, tbk_bw_sink sink, void* user, tbk_bw_out* out);
