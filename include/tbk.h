@@ -696,6 +696,27 @@ typedef int (*tbk_bw_sink)(void* user, uint32_t level, const uint8_t* bytes, uin
  * then its bytes to `sink`.  No rows: one empty data level, no sink call, status 0.  TBK_EUNSUPPORTED: a level of 2^31 records. */
 int tbk_bigwig_build(tbk_ctx* ctx, const tbk_track_rows* rows, uint32_t n_ref, const uint32_t* ref_len, tbk_bw_sink sink, void* user, tbk_bw_out* out);
 
+/* ---- A text track as BGZF members with its tabix index part (ABI version 9, appended) ----------------------------------
+ * What `tiecov --tabix` / `tiebrush --tabix` run: the text of tbk_format_track never leaves the device — every slice of whole lines is
+ * deflated there into a run of whole BGZF members (cut every 0xff00 payload bytes as bgzip cuts them, the last member of a run short,
+ * no EOF member) and indexed there, the lines taking the place of tbk_bam_encode_indexed's records.  The contract per row: beg = start,
+ * end = max(end, start + 1), bin = reg2bin(beg, end) (ix->reserved selects the bins as there), vbeg = member offset << 16 | offset in
+ * the member's payload of the line's first byte, vend = the next line's vbeg, the run's last vend = run bytes << 16.
+ * The sink receives the runs in file order, each with its part (offsets relative to the run's first byte; NULL when ix is NULL: the
+ * rows are then only compressed).  The bytes and the part are valid only during the sink call; nonzero stops the call (TBK_EINVAL).
+ * The sink may be called from another thread of the library's, never two calls at once: slice k + 1 is formatted and deflated while
+ * the sink takes slice k. */
+typedef int (*tbk_tbx_sink)(void* user, const uint8_t* members, uint64_t n_bytes, const tbk_ix_part* part);
+/* rows as for tbk_format_track (HOST or DEVICE; names from tbk_track_names); head / head_len: an optional header that goes before row
+ * 0, in the first run (rows->n == 0 with a header: one run that holds the header, and an empty part).  Slices as tbk_format_track cuts
+ * them (TBK_DEBUG fmt_slice=BYTES).  ix->rec_vbeg is not used.  *text_bytes / *out_bytes (optional): the text's size, header included,
+ * and the runs'.  TBK_EUNSUPPORTED, before the first sink call, for a value outside the formatter's range.  TBK_EINVAL (nothing faults,
+ * the context takes the next call) for a tid without a name or outside [0, ix->n_ref), a negative start, an end beyond what the format
+ * addresses or beyond its reference's last window, a tid that decreases, a start that decreases within a tid (tabix refuses unsorted
+ * input, and the window table's rule needs the order), and what tbk_bam_encode_indexed refuses of ix. */
+int tbk_track_bgzf(tbk_ctx* ctx, const tbk_track_rows* rows, const char* head, uint32_t head_len, const tbk_ix_opts* ix, tbk_tbx_sink sink, void* user,
+                   uint64_t* text_bytes, uint64_t* out_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,7 +29,7 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
            "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route",
-           "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build"]
+           "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build", "tbk_track_bgzf"]
 
 
 class CollapseOpts(C.Structure):
@@ -118,6 +118,8 @@ class TrackRows(C.Structure):
 
 
 TRACK_SINK = C.CFUNCTYPE(C.c_int, _P, _P, C.c_uint64)
+
+TBX_SINK = C.CFUNCTYPE(C.c_int, _P, _P, C.c_uint64, C.POINTER(IxPart))
 
 BW_MAX_ZOOM = 10                              # TBK_BW_MAX_ZOOM
 
@@ -232,6 +234,8 @@ def load():
     L.tbk_zlib_deflate.restype = C.c_int
     L.tbk_bigwig_build.argtypes = [_P, C.POINTER(TrackRows), C.c_uint32, _P, BW_SINK, _P, C.POINTER(BwOut)]
     L.tbk_bigwig_build.restype = C.c_int
+    L.tbk_track_bgzf.argtypes = [_P, C.POINTER(TrackRows), _P, C.c_uint32, C.POINTER(IxOpts), TBX_SINK, _P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.tbk_track_bgzf.restype = C.c_int
     L.tbk_bam_decode_spans.argtypes = [_P, C.c_uint32, _P, _P, _P, _P, C.c_int32, C.POINTER(SoaIn), _P, C.POINTER(_P)]
     L.tbk_bam_decode_spans.restype = C.c_int
     L.tbk_region_view.argtypes = [_P, C.POINTER(SoaIn), _P, C.c_int32, C.c_int64, C.c_int64, C.POINTER(CovIn), C.POINTER(C.c_uint32)]

@@ -1054,6 +1054,60 @@ class Context:
         assert len(text) == total.value
         return text
 
+    def track_bgzf(self, kind, tid, start, end, val=None, strand=None, count=None, heat=None, first_junc=1, head=b"", ref_len=None, csi_depth=None, on_run=None):
+        """tbk_track_bgzf: format_track's rows as a list of (run of whole BGZF members, index part) — the text is formatted, deflated and
+        indexed on the device, slice by slice; `head` goes before row 0.  The part is a dict as bam_encode_indexed
+        returns it (chunks, lin, lin_first, refs; virtual offsets relative to the run's first byte), or None when ref_len is None
+        (the rows are only compressed).  csi_depth as there.  on_run(run, part): called from the sink; a true return stops the call
+        (TBK_EINVAL).  A TbkError carries .n_runs, the runs the sink had taken.  The last call's text and run sizes are left in
+        self.last_track_bytes."""
+        if csi_depth is not None and not 0 <= int(csi_depth) < 2 ** 32 - 1:
+            raise ValueError("csi_depth must be None or a non-negative integer")
+        keep = []
+        dev = _is_torch(tid)
+        n = _numel(tid)
+        s = _lib.TrackRows(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, _lib.TRACK[kind], n, 0, _addr(tid, np.int32, keep, n),
+                           _addr(start, np.int32, keep, n), _addr(end, np.int32, keep, n), _addr(val, np.float64, keep, n),
+                           _addr(strand, np.uint8, keep, n), _addr(count, np.int64, keep, n), _addr(heat, np.float32, keep, n), int(first_junc))
+        self._order_after_torch(dev)
+        io = None
+        if ref_len is not None:
+            ref_len = np.ascontiguousarray(ref_len, dtype=np.uint32)
+            io = _lib.IxOpts()
+            io.n_ref, io.reserved, io.ref_len, io.rec_vbeg = len(ref_len), 0 if csi_depth is None else int(csi_depth) + 1, ref_len.ctypes.data, None
+        chunk_dt = np.dtype([("tid", "<i4"), ("bin", "<u4"), ("beg", "<u8"), ("end", "<u8")])
+        ref_dt = np.dtype([("tid", "<i4"), ("reserved", "<u4"), ("n_records", "<u8"), ("first", "<u8"), ("last", "<u8")])
+        runs = []
+
+        def arr(ptr, count, dt):  # (the run and its part are valid only during the sink call: copied out here)
+            if not count:
+                return np.zeros(0, dtype=dt)
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dt).itemsize), dtype=dt).copy()
+
+        def sink(_user, p, nb, part):
+            d = None
+            if part:
+                q = part.contents
+                d = {"chunks": arr(q.chunks, q.n_chunks, chunk_dt), "lin": arr(q.lin, q.n_lin, np.dtype("<u8")), "lin_first": int(q.lin_first),
+                     "refs": arr(q.refs, q.n_refs, ref_dt)}
+            runs.append((C.string_at(p, nb), d))
+            return 1 if on_run is not None and on_run(*runs[-1]) else 0
+
+        cb = _lib.TBX_SINK(sink)
+        head = bytes(head)
+        text, out = C.c_uint64(0), C.c_uint64(0)
+        rc = self.L.tbk_track_bgzf(self.h, C.byref(s), head if head else None, len(head), C.byref(io) if io is not None else None, cb, None,
+                                   C.byref(text), C.byref(out))
+        try:
+            self._check(rc, "tbk_track_bgzf")
+        except TbkError as e:
+            e.n_runs = len(runs)
+            raise
+        del keep
+        assert sum(len(r) for r, _ in runs) == out.value
+        self.last_track_bytes = (int(text.value), int(out.value))
+        return runs
+
     def zlib_deflate(self, payload, cuts=None, out_cap=None):
         """tbk_zlib_deflate: a byte run (bytes, or a uint8 device tensor) -> the list of its pieces' zlib streams; cuts = payload
         offsets of the piece boundaries ([0, ..., len(payload)]), default one piece per 0xff00 bytes.  out_cap: the room offered for

@@ -6,6 +6,7 @@
 //   ix_rec_k      16 lanes per record: refID / pos / l_read_name / n_cigar_op out of the record's first dwords in the payload stream (the
 //                 records lie back to back there, whatever their source was: the lanes' loads coalesce), the CIGAR's reference length
 //                 summed over the lanes; lane 0 bisects the cuts for the record's member -> (tid, bin), (tid, end), vbeg
+//   tx_rec_k      the other front end (tbk_track_bgzf): one thread per row of a text track, the row's line in the place of the record
 //   ix_head_k     run heads: a record whose (tid, bin) differs from its predecessor's; refIDs must not decrease
 //   ix_runs_k     the runs compacted (tbk_exscan_u32 of the heads): sort key (tid, bin | beg), the run's end = the vbeg behind its last record
 //   tbk_radix_sort128 of the runs by (tid, bin, beg); ix_mhead_k / ix_chunks_k merge neighbours of one bin that meet in one member
@@ -103,6 +104,52 @@ __global__ __launch_bounds__(256) void ix_rec_k(uint32_t n, const uint8_t* __res
     tend[g] = (uint64_t)(uint32_t)tid << 32 | end;
   }
   // the record's member: the last m < nmem with cut[m] <= o (an empty member shares its cut with the next one, which wins)
+  uint32_t lo = 0, hi = nmem;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (cut[mid] <= o) lo = mid + 1;
+    else hi = mid;
+  }
+  const uint32_t m = lo ? lo - 1 : 0;  // (cut[0] == 0: lo >= 1)
+  vbeg[g] = moff[m] << 16 | ((o - cut[m]) & 0xffffull);
+}
+
+// The front end of a track's index (tbk_track_bgzf): one thread per row of the run, the row in the place of ix_rec_k's
+// record — beg = start, end = max(end, start + 1), the same bins; the line's offset in the run's text (its offset in the track's text,
+// less the run's first line's, plus the header bytes before it) bisects the member cuts for its vbeg.  A row is compared with the row
+// before it in the TRACK (not only in the run): tids must not decrease, starts must not decrease within a tid.
+__global__ __launch_bounds__(256) void tx_rec_k(uint32_t n, uint32_t first, const int32_t* __restrict__ r_tid, const int32_t* __restrict__ r_start,
+                                                const int32_t* __restrict__ r_end, const uint64_t* __restrict__ off, uint64_t text0, uint32_t nmem,
+                                                const uint64_t* __restrict__ cut, const uint64_t* __restrict__ moff, uint64_t ztotal, uint32_t n_ref,
+                                                const uint64_t* __restrict__ base, uint32_t fmt, uint64_t* __restrict__ key, uint64_t* __restrict__ tend,
+                                                uint64_t* __restrict__ vbeg, uint32_t* __restrict__ err) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g > n) return;
+  if (g == n) {
+    vbeg[n] = ztotal << 16;
+    return;
+  }
+  const uint32_t i = first + g;
+  const int32_t tid = r_tid[i], beg = r_start[i];
+  const int64_t e = max((int64_t)r_end[i], (int64_t)beg + 1);
+  const uint64_t max_end = fmt ? 1ull << (14 + 3 * (fmt - 1)) : IX_MAX_END;  // fmt: tbk_ix_opts.reserved (0 BAI, k CSI of depth k - 1)
+  uint32_t bad = 0;
+  if (tid < 0 || (uint32_t)tid >= n_ref || beg < 0 || (uint64_t)e > max_end) bad |= IX_E_RANGE;
+  const uint64_t end = (uint64_t)e;
+  if (!bad && ((end - 1) >> 14) >= base[tid + 1] - base[tid]) bad |= IX_E_RANGE;  // (ends behind its reference's last window)
+  if (i) {
+    const int32_t tp = r_tid[i - 1];
+    if (tp > tid || (tp == tid && r_start[i - 1] > beg)) bad |= IX_E_UNSORTED;
+  }
+  if (bad) {
+    atomicOr(err, bad);
+    key[g] = 0, tend[g] = 0;
+  } else {
+    key[g] = (uint64_t)(uint32_t)tid << 32 | (fmt ? ix_reg2bin_depth((uint64_t)(uint32_t)beg, end, fmt - 1) : ix_reg2bin((uint32_t)beg, (uint32_t)end));
+    tend[g] = (uint64_t)(uint32_t)tid << 32 | end;
+  }
+  // the line's member: the last m < nmem with cut[m] <= o (row 0 lies behind the header)
+  const uint64_t o = off[i] - off[first] + text0;
   uint32_t lo = 0, hi = nmem;
   while (lo < hi) {
     const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -276,35 +323,60 @@ int tbk_ix_check_opts(tbk_ctx* ctx, const tbk_ix_opts* ix) {
   return 0;
 }
 
-int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_part* part) {
-  memset(part, 0, sizeof(*part));
-  const uint32_t n = I.n, n_ref = ix->n_ref;
-  if (n == 0) return 0;
+namespace {
+// what a front end (ix_rec_k for records, tx_rec_k for track rows) fills and the back half reads
+struct IxFront {
+  uint32_t n = 0;
+  std::vector<uint64_t> base;  // [n_ref + 1] flat window of every reference's window 0
+  size_t base_bytes = 0;
+  uint64_t *d_base = nullptr, *key = nullptr, *tend = nullptr, *M = nullptr, *vbeg = nullptr, *rend = nullptr;
+  uint32_t *head = nullptr, *ex = nullptr;
+  SortBufs sb;
+};
+
+// the front half up to the launch of the front end's kernel.  fresh_arena: the arena starts over (the encoder's path); else the arrays
+// go behind what the arena holds
+int ix_front(tbk_ctx* ctx, uint32_t n, const tbk_ix_opts* ix, bool fresh_arena, IxFront& F) {
+  const uint32_t n_ref = ix->n_ref;
   hipStream_t st = ctx->stream;
-  std::vector<uint64_t> base((size_t)n_ref + 1, 0);
+  F.n = n;
+  std::vector<uint64_t>& base = F.base;
+  base.assign((size_t)n_ref + 1, 0);
   for (uint32_t t = 0; t < n_ref; ++t) base[t + 1] = base[t] + (((uint64_t)ix->ref_len[t] + 16383) >> 14);
-  const size_t base_bytes = (((size_t)n_ref + 1) * 8 + 255) & ~(size_t)255;
+  const size_t base_bytes = F.base_bytes = (((size_t)n_ref + 1) * 8 + 255) & ~(size_t)255;
   // (the encoder's kernels have run and its scans' partial sums are dead: the arena starts over)
-  TBK_TRY(tbk_ws_reserve(ctx, (size_t)n * 140 + base[n_ref] * 8 + (size_t)n_ref * 48 + tbk_radix_ws_bytes(n) + ((size_t)2 << 20)));
+  if (fresh_arena) TBK_TRY(tbk_ws_reserve(ctx, (size_t)n * 140 + base[n_ref] * 8 + (size_t)n_ref * 48 + tbk_radix_ws_bytes(n) + ((size_t)2 << 20)));
   uint8_t* hp;
   TBK_TRY(ix_host(ctx, base_bytes, &hp));
   memcpy(hp, base.data(), ((size_t)n_ref + 1) * 8);
-  uint64_t* d_base = ws_alloc<uint64_t>(ctx, (size_t)n_ref + 1);
-  uint64_t* key = ws_alloc<uint64_t>(ctx, n);
-  uint64_t* tend = ws_alloc<uint64_t>(ctx, n);
-  uint64_t* M = ws_alloc<uint64_t>(ctx, n);
-  uint64_t* vbeg = ws_alloc<uint64_t>(ctx, (size_t)n + 1);
-  uint32_t* head = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint32_t* ex = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  SortBufs sb;
+  uint64_t* d_base = F.d_base = ws_alloc<uint64_t>(ctx, (size_t)n_ref + 1);
+  uint64_t* key = F.key = ws_alloc<uint64_t>(ctx, n);
+  uint64_t* tend = F.tend = ws_alloc<uint64_t>(ctx, n);
+  uint64_t* M = F.M = ws_alloc<uint64_t>(ctx, n);
+  uint64_t* vbeg = F.vbeg = ws_alloc<uint64_t>(ctx, (size_t)n + 1);
+  uint32_t* head = F.head = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  uint32_t* ex = F.ex = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
+  SortBufs& sb = F.sb;
   sb.hi = ws_alloc<uint64_t>(ctx, n), sb.lo = ws_alloc<uint64_t>(ctx, n), sb.val = ws_alloc<uint32_t>(ctx, n);
-  uint64_t* rend = ws_alloc<uint64_t>(ctx, n);
+  uint64_t* rend = F.rend = ws_alloc<uint64_t>(ctx, n);
   if (!d_base || !key || !tend || !M || !vbeg || !head || !ex || !sb.hi || !sb.lo || !sb.val || !rend) return TBK_ENOMEM;
   TBK_HIP(hipMemcpyAsync(d_base, hp, ((size_t)n_ref + 1) * 8, hipMemcpyHostToDevice, st));
   uint64_t* sc = ctx->d_scalars;
   TBK_HIP(hipMemsetAsync(sc, 0, 16 * sizeof(uint64_t), st));
-  TBK_LAUNCH(ctx, "ix_rec", ix_rec_k, cdiv(((uint64_t)n + 1) * 16, 256), 256, 0, n, I.pay, I.ooff, I.nmem, I.cut, I.moff, I.ztotal, n_ref, d_base, ix->reserved, key, tend,
-             vbeg, ctx->d_err);
+  return 0;
+}
+
+// the back half: everything from ix_head_k on.  track: the rows of tbk_track_bgzf stand in the records' place (the messages say so)
+int ix_back(tbk_ctx* ctx, IxFront& F, const tbk_ix_opts* ix, uint64_t ztotal, bool track, tbk_ix_part* part) {
+  const uint32_t n = F.n, n_ref = ix->n_ref;
+  hipStream_t st = ctx->stream;
+  const std::vector<uint64_t>& base = F.base;
+  const size_t base_bytes = F.base_bytes;
+  uint64_t *d_base = F.d_base, *key = F.key, *tend = F.tend, *M = F.M, *vbeg = F.vbeg, *rend = F.rend;
+  uint32_t *head = F.head, *ex = F.ex;
+  SortBufs& sb = F.sb;
+  uint64_t* sc = ctx->d_scalars;
+  uint8_t* hp;
   TBK_LAUNCH(ctx, "ix_head", ix_head_k, cdiv((uint64_t)n + 1, 256), 256, 0, n, key, head, ctx->d_err);
   TBK_TRY(tbk_exscan_u32(ctx, head, ex, n + 1, sc + 4));
   TBK_TRY((scan_op_run<IxMax, IxMaxOp, IxMaxLoad, IxMaxStore>(ctx, "ix_max_scan", n, IxMaxLoad{tend}, IxMaxStore{M}, IxMaxOp{}, IxMax{0u, 0u})));
@@ -312,6 +384,13 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
   uint32_t eb = 0;
   TBK_TRY(tbk_sync_err(ctx, &eb));  // (the run count sizes the sort, the reference range the two tables)
   if (eb) {
+    if (track) {
+      ctx->last_error = (eb & IX_E_RANGE) ? "track_bgzf: a row outside what the index addresses (tid not below n_ref, negative start, or an end beyond the "
+                                            "format's reach or its reference's last window)"
+                        : (eb & IX_E_UNSORTED) ? "track_bgzf: the rows are not sorted (a tid decreases, or a start decreases within a tid)"
+                                               : "track_bgzf: device error";
+      return (eb & (IX_E_RANGE | IX_E_UNSORTED)) ? TBK_EINVAL : TBK_EHIP;
+    }
     ctx->last_error = (eb & IX_E_MALFORMED)  ? "bam_encode_indexed: a malformed record"
                       : (eb & IX_E_RANGE)    ? (ix->reserved ? "bam_encode_indexed: a record outside what the CSI addresses (refID not in the header, negative pos, or an end "
                                                                "beyond 2^(14 + 3 * depth) or its reference)"
@@ -325,7 +404,7 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
   const uint32_t tid_first = (uint32_t)ctx->h_scalars[5], tid_last = (uint32_t)(ctx->h_scalars[6] >> 32);
   const uint64_t max_end = ctx->h_scalars[6] & 0xffffffffull;
   if (R == 0 || R > n || tid_last >= n_ref || tid_first > tid_last || max_end == 0) {
-    ctx->last_error = "bam_encode_indexed: inconsistent run table";
+    ctx->last_error = track ? "track_bgzf: inconsistent run table" : "bam_encode_indexed: inconsistent run table";
     return TBK_EHIP;
   }
   const uint32_t n_t = tid_last - tid_first + 1;
@@ -346,7 +425,7 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
     return m;
   };
   const uint64_t n_bins = ix->reserved ? ((1ull << (3 * ix->reserved)) - 1) / 7 : 37449;
-  TBK_TRY(tbk_radix_sort128(ctx, &sb, R, bits_below(n_ref) << 32 | bits_below(n_bins) | 0xffffull, bits_below(I.ztotal) << 16 | 0xffffull, true));
+  TBK_TRY(tbk_radix_sort128(ctx, &sb, R, bits_below(n_ref) << 32 | bits_below(n_bins) | 0xffffull, bits_below(ztotal) << 16 | 0xffffull, true));
   TBK_LAUNCH(ctx, "ix_mhead", ix_mhead_k, cdiv((uint64_t)R + 1, 256), 256, 0, R, sb.hi, sb.lo, sb.val, rend, esorted, mh);
   TBK_TRY(tbk_exscan_u32(ctx, mh, mex, R + 1, sc + 7));
   TBK_LAUNCH(ctx, "ix_chunks", ix_chunks_k, cdiv(R, 256), 256, 0, R, sb.hi, sb.lo, esorted, mh, mex, d_chunks);
@@ -364,7 +443,7 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
   if (ix->rec_vbeg) TBK_HIP(hipMemcpyAsync(ix->rec_vbeg, vbeg, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
   TBK_TRY(tbk_sync_err(ctx, &eb));
   if (eb) {
-    ctx->last_error = "bam_encode_indexed: device error in the index kernels";
+    ctx->last_error = track ? "track_bgzf: device error in the index kernels" : "bam_encode_indexed: device error in the index kernels";
     return TBK_EHIP;
   }
   uint32_t nr = 0;
@@ -375,5 +454,34 @@ int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_p
   part->n_lin = n_lin;
   part->lin_first = lin_first;
   part->chunks = h_chunks, part->lin = h_lin, part->refs = h_refs;
-  return tbk_check_launch(ctx, "bam_encode_indexed");
+  return tbk_check_launch(ctx, track ? "track_bgzf" : "bam_encode_indexed");
+}
+}  // namespace
+
+size_t tbk_ix_ws_bytes(uint32_t n, const tbk_ix_opts* ix) {
+  uint64_t windows = 0;
+  for (uint32_t t = 0; t < ix->n_ref; ++t) windows += ((uint64_t)ix->ref_len[t] + 16383) >> 14;
+  return (size_t)n * 140 + windows * 8 + (size_t)ix->n_ref * 48 + tbk_radix_ws_bytes(n) + ((size_t)2 << 20);
+}
+
+int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& I, const tbk_ix_opts* ix, tbk_ix_part* part) {
+  memset(part, 0, sizeof(*part));
+  const uint32_t n = I.n, n_ref = ix->n_ref;
+  if (n == 0) return 0;
+  IxFront F;
+  TBK_TRY(ix_front(ctx, n, ix, true, F));
+  TBK_LAUNCH(ctx, "ix_rec", ix_rec_k, cdiv(((uint64_t)n + 1) * 16, 256), 256, 0, n, I.pay, I.ooff, I.nmem, I.cut, I.moff, I.ztotal, n_ref, F.d_base, ix->reserved, F.key, F.tend,
+             F.vbeg, ctx->d_err);
+  return ix_back(ctx, F, ix, I.ztotal, false, part);
+}
+
+int tbk_tx_build(tbk_ctx* ctx, const TbkTxIn& I, const tbk_ix_opts* ix, tbk_ix_part* part) {
+  memset(part, 0, sizeof(*part));
+  const uint32_t n = I.n, n_ref = ix->n_ref;
+  if (n == 0) return 0;
+  IxFront F;
+  TBK_TRY(ix_front(ctx, n, ix, false, F));
+  TBK_LAUNCH(ctx, "tx_rec", tx_rec_k, cdiv((uint64_t)n + 1, 256), 256, 0, n, I.first, I.tid, I.start, I.end, I.off, I.text0, I.nmem, I.cut, I.moff, I.ztotal, n_ref, F.d_base,
+             ix->reserved, F.key, F.tend, F.vbeg, ctx->d_err);
+  return ix_back(ctx, F, ix, I.ztotal, true, part);
 }

@@ -1182,6 +1182,41 @@ int tbk_zlib_sections(tbk_ctx* ctx, const uint8_t* d_src, const uint64_t* d_cut,
 }
 
 namespace {
+// members of 0xff00 payload bytes as bgzip cuts them, the last one short: cut[m] = the member's first payload byte, cut[nmem] = n
+__global__ __launch_bounds__(256) void run_members_k(uint32_t nmem, uint64_t n, uint64_t* __restrict__ cut, DfMember* __restrict__ mem) {
+  const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m > nmem) return;
+  const uint64_t a = min((uint64_t)m * DF_MAXPAY, n);
+  cut[m] = a;
+  if (m == nmem) return;
+  DfMember M;
+  M.src = a;
+  M.n = (uint32_t)(min(a + DF_MAXPAY, n) - a);
+  M.pad = 0;
+  mem[m] = M;
+}
+}  // namespace
+
+// fmt.hip's track runs (tbk_track_bgzf): a device byte run -> BGZF members of 0xff00 payload bytes packed back to back (*d_out), with the
+// cut table and the members' offsets the index's front end bisects, in the encoder's buffers until its next call
+int tbk_bgzf_run(tbk_ctx* ctx, const uint8_t* d_src, uint64_t n, uint8_t** d_out, uint64_t* total, uint32_t* nmem_out, const uint64_t** d_cut_out,
+                 const uint64_t** d_moff) {
+  *total = 0, *d_out = nullptr, *nmem_out = 0, *d_cut_out = nullptr, *d_moff = nullptr;
+  if (n == 0) return 0;
+  const uint64_t nmem64 = (n + DF_MAXPAY - 1) / DF_MAXPAY;
+  if (nmem64 >= (1ull << 31)) return TBK_E2BIG;
+  const uint32_t nmem = (uint32_t)nmem64;
+  const size_t cut_bytes = (((size_t)nmem + 1) * 8 + 255) & ~(size_t)255;
+  uint8_t* misc;
+  TBK_TRY(enc_buf(ctx, EB_MISC, cut_bytes + (size_t)nmem * sizeof(DfMember), (void**)&misc));
+  uint64_t* d_cut = (uint64_t*)misc;
+  DfMember* d_mem = (DfMember*)(misc + cut_bytes);
+  TBK_LAUNCH(ctx, "run_members", run_members_k, cdiv((uint64_t)nmem + 1, 256), 256, 0, nmem, n, d_cut, d_mem);
+  *nmem_out = nmem, *d_cut_out = d_cut;
+  return deflate_members(ctx, d_src, d_mem, nmem, d_out, total, d_moff);
+}
+
+namespace {
 // tbk_bam_encode; with `ix`, the run's index part too (tbk_bam_encode_indexed: baix.hip) — nothing else differs
 int bam_encode_run(tbk_ctx* ctx, const tbk_enc_in* in, uint8_t* out, uint64_t out_cap, uint64_t* out_bytes, uint64_t* payload_bytes, const tbk_ix_opts* ix,
                    tbk_ix_part* part) {

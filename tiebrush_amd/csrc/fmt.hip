@@ -6,7 +6,8 @@
 //   sample    "%s\t%d\t%d\t%ld\t%f\n"          (the float heat promoted to double)
 // Three passes: the length of every line (and a range check of its values), an exclusive scan of the lengths, then the bytes.  The
 // bytes go out in slices of bounded size through two device buffers and two pinned host buffers: the device formats slice k + 1 while
-// the caller's sink takes slice k.
+// the caller's sink takes slice k.  tbk_track_bgzf cuts the same slices and keeps the text on the device: what leaves is BGZF members and
+// their tabix index parts.
 //
 // %.3f / %f: the printed digits are those of the EXACT binary value rounded half to even, as glibc prints them.  No floating-point
 // arithmetic is involved: v = m * 2^e with m < 2^53; the integer part is m >> -e (or m << e), the fraction's digits are
@@ -210,8 +211,19 @@ int tbk_pin_slices(tbk_ctx* ctx, size_t bytes) {
   return 0;
 }
 
-int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes) {
-  Rows R;
+namespace {
+// What tbk_format_track and tbk_track_bgzf share: the lines' lengths and offsets, the range check, and the slices of whole lines.
+struct FmtPlan {
+  Rows R = {};
+  uint64_t* off = nullptr;    // device [n + 1]: every line's offset in the track's text
+  uint64_t total = 0;         // bytes of the text
+  uint32_t per = 0, ns = 0;   // rows per slice, slices
+  std::vector<uint64_t> cut;  // [ns + 1] the slices' first bytes
+  uint64_t slice_max = 0;
+};
+
+int fmt_plan(tbk_ctx* ctx, const tbk_track_rows* rows, FmtPlan& P) {
+  Rows& R = P.R;
   R.kind = rows->kind;
   R.n = rows->n;
   R.tid = rows->tid, R.start = rows->start, R.end = rows->end;
@@ -219,10 +231,8 @@ int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink s
   R.first_junc = rows->first_junc;
   R.name_off = ctx->d_name_off, R.names = ctx->d_names, R.n_names = ctx->n_names;
   const uint32_t n = R.n;
-  if (out_bytes) *out_bytes = 0;
-  if (n == 0) return 0;
   uint32_t* lens = ws_alloc<uint32_t>(ctx, (size_t)n + 1);
-  uint64_t* off = ws_alloc<uint64_t>(ctx, (size_t)n + 1);
+  uint64_t* off = P.off = ws_alloc<uint64_t>(ctx, (size_t)n + 1);
   uint32_t* stat = ws_alloc<uint32_t>(ctx, 4);
   uint64_t* d_total = ws_alloc<uint64_t>(ctx, 1);
   if (!lens || !off || !stat || !d_total) return TBK_ENOMEM;
@@ -235,7 +245,7 @@ int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink s
   TBK_HIP(hipMemcpyAsync(&hs[1], d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   const uint32_t maxlen = (uint32_t)hs[0], errb = (uint32_t)(hs[0] >> 32);
-  const uint64_t total = hs[1];
+  P.total = hs[1];
   if (errb & FMT_ERR_TID) {
     ctx->last_error = "a row's reference index has no name in the table (tbk_track_names)";
     return TBK_EINVAL;
@@ -246,17 +256,33 @@ int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink s
   }
   // slices of whole lines, at most `cap` bytes each (a single line longer than that is a slice of its own)
   const uint64_t cap = std::max<uint64_t>(ctx->dbg.fmt_slice ? ctx->dbg.fmt_slice : ((uint64_t)32 << 20), maxlen);
-  const uint32_t per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, cap / std::max<uint32_t>(maxlen, 1)));
-  const uint32_t ns = cdiv(n, per);
+  const uint32_t per = P.per = (uint32_t)std::min<uint64_t>(n, std::max<uint64_t>(1, cap / std::max<uint32_t>(maxlen, 1)));
+  const uint32_t ns = P.ns = cdiv(n, per);
   uint64_t* d_cut = ws_alloc<uint64_t>(ctx, (size_t)ns + 1);
   if (!d_cut) return TBK_ENOMEM;
   TBK_LAUNCH(ctx, "fmt_cuts_k", fmt_cuts_k, cdiv((uint64_t)ns + 1, 256), 256, 0, off, n, per, ns + 1, d_cut);
   TBK_TRY(tbk_check_launch(ctx, "fmt_cuts_k"));
-  std::vector<uint64_t> cut((size_t)ns + 1);
+  std::vector<uint64_t>& cut = P.cut;
+  cut.assign((size_t)ns + 1, 0);
   TBK_HIP(hipMemcpyAsync(cut.data(), d_cut, cut.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   TBK_HIP(hipStreamSynchronize(ctx->stream));
-  uint64_t slice_max = 0;
-  for (uint32_t s = 0; s < ns; ++s) slice_max = std::max(slice_max, cut[s + 1] - cut[s]);
+  P.slice_max = 0;
+  for (uint32_t s = 0; s < ns; ++s) P.slice_max = std::max(P.slice_max, cut[s + 1] - cut[s]);
+  return 0;
+}
+}  // namespace
+
+int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes) {
+  const uint32_t n = rows->n;
+  if (out_bytes) *out_bytes = 0;
+  if (n == 0) return 0;
+  FmtPlan P;
+  TBK_TRY(fmt_plan(ctx, rows, P));
+  const Rows& R = P.R;
+  const uint64_t* off = P.off;
+  const uint64_t total = P.total, slice_max = P.slice_max;
+  const uint32_t per = P.per, ns = P.ns;
+  const std::vector<uint64_t>& cut = P.cut;
   char* dbuf[2] = {ws_alloc<char>(ctx, slice_max + 16), ns > 1 ? ws_alloc<char>(ctx, slice_max + 16) : nullptr};
   if (!dbuf[0] || (ns > 1 && !dbuf[1])) return TBK_ENOMEM;
   TBK_TRY(tbk_pin_slices(ctx, slice_max));
@@ -283,6 +309,88 @@ int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink s
   TBK_HIP(hipStreamSynchronize(ctx->stream));
   if (out_bytes) *out_bytes = total;
   return rc;
+}
+
+// tbk_track_bgzf: the slices of tbk_format_track, but the text stays on the device — slice k is formatted into the text
+// buffer (the header in front of row 0), deflated into a run of whole members (tbk_bgzf_run), indexed (tbk_tx_build: tx_rec_k and the
+// BAM index's back half) and copied into one of two pinned buffers with its part; the context's sink thread takes it while the
+// device works on slice k + 1.
+int tbk_track_bgzf_device(tbk_ctx* ctx, const tbk_track_rows* rows, const char* head, uint32_t head_len, const tbk_ix_opts* ix, tbk_tbx_sink sink, void* user,
+                          uint64_t* text_bytes, uint64_t* out_bytes) {
+  const uint32_t n = rows->n;
+  if (text_bytes) *text_bytes = 0;
+  if (out_bytes) *out_bytes = 0;
+  if (n == 0 && head_len == 0) return 0;
+  FmtPlan P;
+  if (n) TBK_TRY(fmt_plan(ctx, rows, P));  // (the range refusal comes from here: before any run)
+  else P.ns = 1, P.cut.assign(2, 0);      // the header alone: one run
+  const Rows& R = P.R;
+  tbk_ix_opts ixo = {};
+  if (ix) ixo = *ix, ixo.rec_vbeg = nullptr;
+  const uint64_t text_max = P.slice_max + head_len;
+  char* dtext = ws_alloc<char>(ctx, text_max + 64);
+  if (!dtext) return TBK_ENOMEM;
+  if (head_len) TBK_HIP(hipMemcpyAsync(dtext, head, head_len, hipMemcpyHostToDevice, ctx->stream));
+  // a member that does not compress is stored: its payload and a few dozen bytes of framing
+  TBK_TRY(tbk_pin_slices(ctx, text_max + (text_max / 0xff00 + 2) * 64));
+  struct Slot {  // what the sink of a slice reads while the next slice is made
+    tbk_ix_part part;
+    std::vector<tbk_ix_chunk> chunks;
+    std::vector<uint64_t> lin;
+    std::vector<tbk_ix_ref> refs;
+    uint64_t zbytes = 0;
+  } slot[2];
+  int sink_rc = 0;
+  uint64_t zsum = 0;
+  TbkWorker worker;  // (declared last: it is joined before the slots go)
+  for (uint32_t s = 0; s < P.ns; ++s) {
+    const size_t mark = ctx->ws_off;  // the slice's temporaries (deflater's scans, index arrays) go when the slice is done
+    const uint32_t lo = s * P.per, hi = (uint32_t)std::min<uint64_t>(n, (uint64_t)lo + P.per);
+    const uint64_t text0 = s == 0 ? head_len : 0, len = text0 + P.cut[s + 1] - P.cut[s];
+    if (hi > lo) {
+      TBK_LAUNCH(ctx, "fmt_write_k", fmt_write_k, cdiv(hi - lo, FMT_NT), FMT_NT, 0, R, P.off, lo, hi, dtext + text0);
+      TBK_TRY(tbk_check_launch(ctx, "fmt_write_k"));
+    }
+    uint8_t* packed;
+    uint64_t ztotal;
+    uint32_t nmem;
+    const uint64_t *d_cut, *d_moff;
+    TBK_TRY(tbk_bgzf_run(ctx, (const uint8_t*)dtext, len, &packed, &ztotal, &nmem, &d_cut, &d_moff));
+    if (ztotal > ctx->fmt_pin_cap) {
+      ctx->last_error = "track_bgzf: a run larger than its text allows for";
+      return TBK_EHIP;
+    }
+    Slot& S = slot[s & 1];  // (its last sink call, of slice s - 2, has returned: slice s - 1 was posted behind it)
+    TBK_HIP(hipMemcpyAsync(ctx->fmt_pin[s & 1], packed, ztotal, hipMemcpyDeviceToHost, ctx->stream));
+    S.zbytes = ztotal;
+    if (ix) {  // (the index kernels run under the members' download; the build ends with a synchronisation)
+      const TbkTxIn I{hi - lo, lo, R.tid, R.start, R.end, P.off, text0, nmem, d_cut, d_moff, ztotal};
+      tbk_ix_part part;
+      TBK_TRY(tbk_tx_build(ctx, I, &ixo, &part));
+      S.chunks.assign(part.chunks, part.chunks + part.n_chunks);
+      S.lin.assign(part.lin, part.lin + part.n_lin);
+      S.refs.assign(part.refs, part.refs + part.n_refs);
+      S.part = part;
+      S.part.chunks = S.chunks.data(), S.part.lin = S.lin.data(), S.part.refs = S.refs.data();
+    }
+    TBK_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->ws_off = mark;
+    zsum += ztotal;
+    worker.wait();  // slice s - 1 is with the sink since the device began this one
+    if (sink_rc != 0) break;
+    const uint8_t* zb = (const uint8_t*)ctx->fmt_pin[s & 1];
+    const tbk_ix_part* pp = ix ? &S.part : nullptr;
+    const uint64_t zn = S.zbytes;
+    worker.post([=, &sink_rc]() { sink_rc = sink(user, zb, zn, pp); });
+  }
+  worker.wait();
+  if (sink_rc != 0) {
+    ctx->last_error = "tbk_track_bgzf: the sink refused a run";
+    return TBK_EINVAL;
+  }
+  if (text_bytes) *text_bytes = P.total + head_len;
+  if (out_bytes) *out_bytes = zsum;
+  return 0;
 }
 
 int tbk_names_upload(tbk_ctx* ctx, uint32_t n_names, const uint64_t* off, const char* bytes) {

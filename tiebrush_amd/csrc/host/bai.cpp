@@ -221,31 +221,45 @@ void BaiIndex::add(uint64_t file_base, const BaiChunk* chunks, size_t n_chunks, 
 
 // CSIv1 before compression: a bin's loff is the linear table's entry of the bin's first 16 kb window (a record of the bin ends behind the
 // bin's start, so the entry exists); the table itself is not written
+void BaiIndex::put_ref_csi(std::vector<uint8_t>& o, const Ref& r) const {
+  std::vector<uint32_t> first((size_t)depth_ + 2, 0);  // first[l]: the first bin of level l; first[depth + 1] + 1: the meta bin
+  for (int l = 0; l <= depth_; ++l) first[(size_t)l + 1] = first[(size_t)l] + (1u << (3 * l));
+  put32(o, (uint32_t)r.bins.size() + 1);
+  for (const auto& b : r.bins) {
+    int l = depth_;
+    while (b.first < first[(size_t)l]) --l;
+    const uint64_t w = (uint64_t)(b.first - first[(size_t)l]) << (3 * (depth_ - l));
+    put32(o, b.first);
+    put64(o, w < r.lin.size() && r.lin[w] != ~0ull ? r.lin[w] : 0);
+    put32(o, (uint32_t)b.second.size());
+    for (const auto& c : b.second) put64(o, c.first), put64(o, c.second);
+  }
+  put32(o, first[(size_t)depth_ + 1] + 1), put64(o, 0), put32(o, 2);  // the meta bin: what the BAI's pseudo-bin holds
+  put64(o, r.first), put64(o, r.last), put64(o, r.n), put64(o, 0);
+}
+
 void BaiIndex::serialize_csi(std::vector<uint8_t>& o) const {
   o.insert(o.end(), {'C', 'S', 'I', 1});
   put32(o, 14), put32(o, (uint32_t)depth_), put32(o, 0);
   put32(o, (uint32_t)ref_.size());
-  std::vector<uint32_t> first((size_t)depth_ + 2, 0);  // first[l]: the first bin of level l; first[depth + 1] + 1: the meta bin
-  for (int l = 0; l <= depth_; ++l) first[(size_t)l + 1] = first[(size_t)l] + (1u << (3 * l));
   for (const Ref& r : ref_) {
-    if (r.n == 0) {
-      put32(o, 0);
-      continue;
-    }
-    put32(o, (uint32_t)r.bins.size() + 1);
-    for (const auto& b : r.bins) {
-      int l = depth_;
-      while (b.first < first[(size_t)l]) --l;
-      const uint64_t w = (uint64_t)(b.first - first[(size_t)l]) << (3 * (depth_ - l));
-      put32(o, b.first);
-      put64(o, w < r.lin.size() && r.lin[w] != ~0ull ? r.lin[w] : 0);
-      put32(o, (uint32_t)b.second.size());
-      for (const auto& c : b.second) put64(o, c.first), put64(o, c.second);
-    }
-    put32(o, first[(size_t)depth_ + 1] + 1), put64(o, 0), put32(o, 2);  // the meta bin: what the BAI's pseudo-bin holds
-    put64(o, r.first), put64(o, r.last), put64(o, r.n), put64(o, 0);
+    if (r.n == 0) put32(o, 0);
+    else put_ref_csi(o, r);
   }
   put64(o, 0);  // n_no_coor
+}
+
+void BaiIndex::put_ref_bai(std::vector<uint8_t>& o, const Ref& r) const {
+  put32(o, (uint32_t)r.bins.size() + 1);
+  for (const auto& b : r.bins) {  // (a map: ascending bin numbers)
+    put32(o, b.first);
+    put32(o, (uint32_t)b.second.size());
+    for (const auto& c : b.second) put64(o, c.first), put64(o, c.second);
+  }
+  put32(o, 37450), put32(o, 2);  // the pseudo-bin: the reference's range in the file, mapped / unmapped counts
+  put64(o, r.first), put64(o, r.last), put64(o, r.n), put64(o, 0);
+  put32(o, (uint32_t)r.lin.size());
+  for (uint64_t v : r.lin) put64(o, v);
 }
 
 void BaiIndex::serialize(std::vector<uint8_t>& o) const {
@@ -254,38 +268,67 @@ void BaiIndex::serialize(std::vector<uint8_t>& o) const {
   o.insert(o.end(), {'B', 'A', 'I', 1});
   put32(o, (uint32_t)ref_.size());
   for (const Ref& r : ref_) {
-    if (r.n == 0) {
-      put32(o, 0), put32(o, 0);
-      continue;
-    }
-    put32(o, (uint32_t)r.bins.size() + 1);
-    for (const auto& b : r.bins) {  // (a map: ascending bin numbers)
-      put32(o, b.first);
-      put32(o, (uint32_t)b.second.size());
-      for (const auto& c : b.second) put64(o, c.first), put64(o, c.second);
-    }
-    put32(o, 37450), put32(o, 2);  // the pseudo-bin: the reference's range in the file, mapped / unmapped counts
-    put64(o, r.first), put64(o, r.last), put64(o, r.n), put64(o, 0);
-    put32(o, (uint32_t)r.lin.size());
-    for (uint64_t v : r.lin) put64(o, v);
+    if (r.n == 0) put32(o, 0), put32(o, 0);
+    else put_ref_bai(o, r);
   }
   put64(o, 0);  // n_no_coor: the output holds no unplaced reads
+}
+
+void BaiIndex::serialize_tabix(std::vector<uint8_t>& o, const std::vector<std::string>& names, int32_t skip) const {
+  o.clear();
+  std::vector<uint8_t> hb;  // the header block (htslib: the index's `meta`)
+  uint32_t n_live = 0, l_nm = 0;
+  for (size_t t = 0; t < ref_.size(); ++t)
+    if (ref_[t].n) ++n_live, l_nm += (uint32_t)(t < names.size() ? names[t].size() : 0) + 1;
+  put32(hb, 0x10000), put32(hb, 1), put32(hb, 2), put32(hb, 3), put32(hb, '#'), put32(hb, (uint32_t)skip), put32(hb, l_nm);
+  for (size_t t = 0; t < ref_.size(); ++t)
+    if (ref_[t].n) {
+      if (t < names.size()) hb.insert(hb.end(), names[t].begin(), names[t].end());
+      hb.push_back(0);
+    }
+  if (csi_) {
+    o.insert(o.end(), {'C', 'S', 'I', 1});
+    put32(o, 14), put32(o, (uint32_t)depth_), put32(o, (uint32_t)hb.size());
+    o.insert(o.end(), hb.begin(), hb.end());
+    put32(o, n_live);
+  } else {
+    o.insert(o.end(), {'T', 'B', 'I', 1});
+    put32(o, n_live);
+    o.insert(o.end(), hb.begin(), hb.end());
+  }
+  for (const Ref& r : ref_) {
+    if (r.n == 0) continue;
+    if (csi_) put_ref_csi(o, r);
+    else put_ref_bai(o, r);
+  }
+  put64(o, 0);  // n_no_coor
+}
+
+namespace {
+bool write_bgzf_renamed(const std::vector<uint8_t>& o, const std::string& path, std::string& err) {
+  const std::string tmp = path + ".tmp";
+  BgzfWriter w;
+  const bool ok = w.open(tmp, 6, 1) && w.write(o.data(), o.size());
+  if (!(w.close() && ok) || rename(tmp.c_str(), path.c_str()) != 0) {
+    (void)unlink(tmp.c_str());
+    err = "cannot write " + path;
+    return false;
+  }
+  return true;
+}
+}  // namespace
+
+bool BaiIndex::write_tabix(const std::string& path, const std::vector<std::string>& names, int32_t skip, std::string& err) const {
+  std::vector<uint8_t> o;
+  serialize_tabix(o, names, skip);
+  return write_bgzf_renamed(o, path, err);
 }
 
 bool BaiIndex::write(const std::string& path, std::string& err) const {
   std::vector<uint8_t> o;
   serialize(o);
   const std::string tmp = path + ".tmp";
-  if (csi_) {  // BGZF members and the EOF member, by the host codec
-    BgzfWriter w;
-    const bool ok = w.open(tmp, 6, 1) && w.write(o.data(), o.size());
-    if (!(w.close() && ok) || rename(tmp.c_str(), path.c_str()) != 0) {
-      (void)unlink(tmp.c_str());
-      err = "cannot write " + path;
-      return false;
-    }
-    return true;
-  }
+  if (csi_) return write_bgzf_renamed(o, path, err);  // BGZF members and the EOF member, by the host codec
   FILE* f = fopen(tmp.c_str(), "wb");
   if (!f) {
     err = "cannot create " + tmp;

@@ -75,6 +75,13 @@ class BaiIndex {
   void serialize(std::vector<uint8_t>& out) const;  // BAI, or the CSI's bytes before BGZF compression
   // written beside its final name and renamed when complete: no half-written index is left behind (a CSI: BGZF members and the EOF member)
   bool write(const std::string& path, std::string& err) const;
+  // The index of a BGZF text track (tabix): the same bins, chunks, windows and pseudo / meta bins behind tabix's header
+  // block {format 0x10000 (UCSC: 0-based, half-open), col_seq 1, col_beg 2, col_end 3, meta '#', skip, l_nm, names}.  The references
+  // are renumbered to those that have rows, in file order (what `tabix -l` lists).  "TBI\1" n_ref header bodies n_no_coor, or in CSI
+  // mode the CSI with the header block as its aux field (l_aux = 28 + l_nm).  The bytes before BGZF compression.
+  void serialize_tabix(std::vector<uint8_t>& out, const std::vector<std::string>& names, int32_t skip) const;
+  // BGZF members and the EOF member by the host codec, written beside the final name and renamed when complete
+  bool write_tabix(const std::string& path, const std::vector<std::string>& names, int32_t skip, std::string& err) const;
 
  private:
   struct Ref {
@@ -84,6 +91,8 @@ class BaiIndex {
   };
   void set_refs(const std::vector<uint32_t>& lens);
   void serialize_csi(std::vector<uint8_t>& out) const;
+  void put_ref_bai(std::vector<uint8_t>& out, const Ref& r) const;  // a reference's body with records: bins, pseudo-bin, windows
+  void put_ref_csi(std::vector<uint8_t>& out, const Ref& r) const;  // the same for a CSI: a loff per bin, the meta bin
   bool active_ = false, csi_ = false;
   int depth_ = kBaiDepth;
   std::vector<uint32_t> len_;

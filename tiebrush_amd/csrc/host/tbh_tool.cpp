@@ -5,6 +5,9 @@
 //   tags IN.bam OUT.bam SPEC...   apply tag edits to every record: YC=f:2.5  YX=i:255  YD=i:0  YD=del
 //   bai IN.bam                    write IN.bam.bai with the host index builder alone (bai.h: what `tiebrush --index` builds as it writes)
 //   csi IN.bam                    write IN.bam.csi the same way (what `tiebrush --csi` builds: references beyond 2^29 included)
+//   tabix IN.bam IN.bed OUT.gz    a bedGraph / BED track (a first line that begins with "track" is its header) as BGZF OUT.gz with its
+//                                 tabix index OUT.gz.tbi / .csi by the host path alone (tabix.h: what `tiecov --tabix` writes; IN.bam
+//                                 gives the reference names and lengths); rows out of order are refused with their line number
 //   query IN.bam REGION [INDEX]   the chunks the index names for REGION (bai_read.h), one line "vbeg vend" in hex each, then the number of
 //                                 records in the chunks and of those overlapping the region, by the host codec ("hit vbeg" per overlap)
 //   rquery IN.bam REGIONS.bed [INDEX]   the same for the region table of a BED file: "regions R", a "region tid beg end"
@@ -13,9 +16,11 @@
 //   mkbam SOADIR PREFIX [LEVEL [THREADS]]   encode the raw SoA arrays of a synthetic tile (file_off, tid, pos, flag, mapq, strand,
 //                                 nh, cig_off, cig as little-endian files + header.txt) as PREFIX<f>.bam, one per input file: the
 //                                 records tiebrush_amd.synth.write_bams writes (SEQ '*', QNAME r<f>_<i>, NH:C / XS:A), files in parallel
+#include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <atomic>
 #include <string>
 #include <thread>
@@ -28,6 +33,7 @@
 #include "fastload.h"
 #include "tmerge.h"
 #include "bigwig.h"
+#include "tabix.h"
 
 template <class T>
 static bool slurp(const std::string& dir, const char* name, std::vector<T>& v) {
@@ -378,6 +384,92 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
+  if (cmd == "tabix" && argc == 5) {  // <alignment file: names and lengths> <in.bedgraph|in.bed> <out.gz>
+    GSamReader rd(argv[2]);
+    sam_hdr_t* hdr = rd.header();
+    std::vector<std::string> names;
+    std::vector<uint32_t> lens;
+    for (int t = 0; t < hdr->n_targets; ++t) {
+      names.push_back(hdr->target_name[t]);
+      lens.push_back(hdr->target_len[t]);
+    }
+    FILE* f = fopen(argv[3], "r");
+    if (!f) {
+      fprintf(stderr, "tbh_tool tabix: cannot open %s\n", argv[3]);
+      return 1;
+    }
+    std::string text, head, err;
+    {
+      char buf[1 << 16];
+      size_t got;
+      while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got);
+      fclose(f);
+    }
+    size_t p = 0;
+    if (text.compare(0, 5, "track") == 0) {
+      p = text.find('\n');
+      p = p == std::string::npos ? text.size() : p + 1;
+      head = text.substr(0, p);
+    }
+    tbh::TabixWriter w;
+    if (!w.open(argv[4], names, lens, head, err)) {
+      fprintf(stderr, "tbh_tool tabix: %s\n", err.c_str());
+      return 1;
+    }
+    // slices of whole lines as the command lines' host path cuts them; the header rides with the first
+    const size_t slice_rows = (size_t)1 << 19;
+    std::vector<tbh::BaiRec> recs;
+    size_t s0 = 0, line = head.empty() ? 0 : 1;
+    int32_t last_tid = -1, last_beg = 0;
+    auto flush = [&](size_t upto) {
+      if (upto == s0) return true;
+      for (tbh::BaiRec& r : recs) r.vbeg -= s0;
+      const bool ok = w.add_text(text.data() + s0, upto - s0, recs, err);
+      recs.clear(), s0 = upto;
+      return ok;
+    };
+    bool ok = true;
+    while (ok && p < text.size()) {
+      size_t e = text.find('\n', p);
+      e = e == std::string::npos ? text.size() : e + 1;
+      ++line;
+      const size_t t1 = text.find('\t', p);
+      char* q = nullptr;
+      long long a = 0, b = 0;
+      bool good = t1 != std::string::npos && t1 < e;
+      if (good) {
+        a = strtoll(text.c_str() + t1 + 1, &q, 10);
+        good = q != text.c_str() + t1 + 1 && *q == '\t';
+      }
+      if (good) {
+        const char* q0 = q + 1;
+        b = strtoll(q0, &q, 10);
+        good = q != q0;
+      }
+      const int tid = good ? hdr->name2tid(text.substr(p, t1 - p).c_str()) : -1;
+      if (!good || tid < 0 || a < 0 || a > INT32_MAX) {
+        fprintf(stderr, "tbh_tool tabix: %s line %zu: not a row of a reference in %s\n", argv[3], line, argv[2]);
+        w.discard();
+        return 1;
+      }
+      if (tid < last_tid || (tid == last_tid && (int32_t)a < last_beg)) {
+        fprintf(stderr, "tbh_tool tabix: %s line %zu is out of order (the rows must be sorted by reference, then start)\n", argv[3], line);
+        w.discard();
+        return 1;
+      }
+      last_tid = tid, last_beg = (int32_t)a;
+      recs.push_back(tbh::BaiRec{tid, (int32_t)a, std::max<int64_t>(b, a + 1), (uint64_t)p});
+      p = e;
+      if (recs.size() == slice_rows) ok = flush(p);
+    }
+    ok = ok && flush(text.size());
+    if (!ok || !w.close(err)) {
+      fprintf(stderr, "tbh_tool tabix: %s\n", err.c_str());
+      w.discard();
+      return 1;
+    }
+    return 0;
+  }
   if (cmd == "bai" && argc == 3) {
     std::string err;
     if (!tbh::bai_index_file(argv[2], std::string(argv[2]) + ".bai", err)) {
@@ -489,6 +581,6 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|query|rquery|mquery|mrquery ...\n");
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery ...\n");
   return 2;
 }

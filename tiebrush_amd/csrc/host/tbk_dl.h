@@ -41,6 +41,7 @@ struct TbkApi {
   decltype(&tbk_track_names) track_names = nullptr;
   decltype(&tbk_format_track) format_track = nullptr;
   decltype(&tbk_bigwig_build) bigwig_build = nullptr;  // optional: --bigwig-writer device
+  decltype(&tbk_track_bgzf) track_bgzf = nullptr;      // optional: --tabix
   std::string error;
   bool has_tracks() const { return coverage_tile && sample_tile && track_names && format_track; }
 
@@ -93,6 +94,7 @@ struct TbkApi {
     track_names = (decltype(track_names))dlsym(h, "tbk_track_names");
     format_track = (decltype(format_track))dlsym(h, "tbk_format_track");
     bigwig_build = (decltype(bigwig_build))dlsym(h, "tbk_bigwig_build");
+    track_bgzf = (decltype(track_bgzf))dlsym(h, "tbk_track_bgzf");
     if (abi_version() != TBK_ABI_VERSION) {
       error = "libtbk.so has another ABI version";
       return false;

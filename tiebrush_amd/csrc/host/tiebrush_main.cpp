@@ -88,6 +88,9 @@ static const char* USAGE =
     "  --bigwig             write the coverage track as PREFIX.bigwig (as tiecov -W; needs --cov)\n"
     "  --bigwig-writer host|device   with --bigwig: the file's sections and zoom levels by this core with zlib (host, the default)\n"
     "                       or by the GPU (device: the same payloads, compressed by the device's deflater)\n"
+    "  --tabix              write every text track BGZF-compressed with its tabix index (PREFIX.bedgraph.gz / PREFIX.bed.gz and\n"
+    "                       FILE.gz.tbi, or FILE.gz.csi for references longer than 2^29), as tiecov --tabix; with --bigwig the\n"
+    "                       coverage stays the bigWig; needs one of --cov / --junc / --samp, not --cov - and not --ranks\n"
     "                       (the tracks are what tiecov writes when it reads OUT.bam; not with --ranks)\n"
     "  --index              also write the output's BAM index OUT.bam.bai (what samtools index makes of OUT.bam; not with --ranks,\n"
     "                       not when the output goes to standard output)\n"
@@ -649,8 +652,14 @@ static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, Track
     return r;
   };
   double ms_cov = 0, ms_samp = 0;
-  if (tf.cov || tf.cov_bw || tf.junc) {
-    size_t ci = (tf.cov || tf.cov_bw) ? 2 * co + 2 * n + 16 : 0, cj = tf.junc ? co + 16 : 0;
+  // --tabix: a track's writer is open in the place of its FILE* (tabix.h)
+  const bool cov_tx = tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
+  tbh::TabixDevice txd;
+  txd.ctx = ctx, txd.track_bgzf = api.track_bgzf, txd.track_names = api.track_names, txd.strerror_ = api.strerror_, txd.last_error = api.last_error;
+  txd.names_set = !env.track_host_fmt;
+  if ((cov_tx || junc_tx || samp_tx) && !env.track_host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
+  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx) {
+    size_t ci = (tf.cov || tf.cov_bw || cov_tx) ? 2 * co + 2 * n + 16 : 0, cj = (tf.junc || junc_tx) ? co + 16 : 0;
     std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
     std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
     std::vector<uint8_t> jstr(cj ? cj : 1);
@@ -686,8 +695,22 @@ static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, Track
       if (!device_text(tf.junc, r)) tbh::emit_junc_lines(tf.junc, names, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
       ms_text += tms(a, tnow());
     }
+    if (cov_tx) {
+      tbk_track_rows r = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
+      r.val = iv.data();
+      auto a = tnow();
+      tbh::write_tabix_track(tf.cov_tx, r, names, &txd);
+      ms_text += tms(a, tnow());
+    }
+    if (junc_tx) {
+      tbk_track_rows r = rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
+      r.val = jv.data(), r.strand = jstr.data();
+      auto a = tnow();
+      tbh::write_tabix_track(tf.junc_tx, r, names, &txd);
+      ms_text += tms(a, tnow());
+    }
   }
-  if (tf.samp) {  // (sized and retried as tiecov_main.cpp does)
+  if (tf.samp || samp_tx) {  // (sized and retried as tiecov_main.cpp does)
     size_t cs = 2 * co + 2 * n + 16;
     std::vector<int32_t> st, ss, se;
     std::vector<int64_t> sc;
@@ -711,7 +734,8 @@ static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, Track
     tbk_track_rows r = rows(TBK_TRACK_SAMPLE, so.n_intervals, st.data(), ss.data(), se.data());
     r.count = sc.data(), r.heat = sh.data();
     auto b = tnow();
-    if (!device_text(tf.samp, r)) tbh::emit_samp_lines(tf.samp, names, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());
+    if (samp_tx) tbh::write_tabix_track(tf.samp_tx, r, names, &txd);
+    else if (!device_text(tf.samp, r)) tbh::emit_samp_lines(tf.samp, names, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());
     ms_text += tms(b, tnow());
   }
   tf.close();
@@ -1415,9 +1439,10 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
   const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQFR");
   static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", nullptr};
   const int region_files = count_value_option(argc, argv, "regions-file", 'R', value_longs_R, "oNQFr");
-  bool ranks = false, tracks = false, index = false, csi = false;
+  bool ranks = false, tracks = false, index = false, csi = false, tabix = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
+    tabix = tabix || strcmp(argv[i], "--tabix") == 0;
     index = index || strcmp(argv[i], "--index") == 0;
     csi = csi || strcmp(argv[i], "--csi") == 0;
     for (const char* o : {"--cov", "--junc", "--samp", "--bigwig"}) {
@@ -1425,6 +1450,7 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
       tracks = tracks || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
     }
   }
+  if (ranks && tabix) GError("Error: --tabix is not available with --ranks (run tiecov --tabix on the output)\n");
   if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
   if (ranks && index) GError("Error: --index is not available with --ranks (index the output afterwards)\n");
   if (ranks && csi) GError("Error: --csi is not available with --ranks (index the output afterwards)\n");
@@ -1441,7 +1467,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;index;csi;region=;regions-file=;SMLPEDVho:N:Q:F:r:R:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;tabix;index;csi;region=;regions-file=;SMLPEDVho:N:Q:F:r:R:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1511,6 +1537,10 @@ int main(int argc, char* argv[]) {
   if (want_csi && strcmp(outfname, "-") == 0)
     GError("Error: --csi needs an output file (-o FILE, not -o -): an index addresses file offsets, standard output has none\n");
   const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty();
+  const bool tabix = args.getOpt("tabix") != nullptr;
+  if (tabix && !tracks) GError("Error: --tabix needs at least one of --cov / --junc / --samp (it applies to their tracks)\n");
+  if (tabix && !bigwig && (cov_prefix == "-" || cov_prefix == "stdout"))
+    GError("Error: --tabix needs a coverage file (--cov PREFIX, not --cov %s): an index addresses file offsets, standard output has none\n", cov_prefix.c_str());
   const char* region = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");
   const char* regions_file = args.getOpt('R') ? args.getOpt('R') : args.getOpt("regions-file");
   const bool regional = region || regions_file;
@@ -1545,7 +1575,7 @@ int main(int argc, char* argv[]) {
       num_samples = (int)h->co_samples().size();
       if (num_samples == 0) GError("Error: no sample lines found in header");
     }
-    tfiles.open(cov_prefix, junc_prefix, samp_prefix, bigwig, h->target_name, h->target_len);
+    tfiles.open(cov_prefix, junc_prefix, samp_prefix, bigwig, h->target_name, h->target_len, tabix);
     trecs.reset(new TrackRecs());
   }
   // the index: a reference a BAI cannot address is refused before the output is created; an older index of the same name goes now

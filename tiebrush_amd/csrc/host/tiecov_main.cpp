@@ -36,6 +36,10 @@ static const char* USAGE =
     "  -W           write the coverage (-c) as a bigWig file (PREFIX.bigwig) instead of a bedGraph\n"
     "  --bigwig-writer host|device   with -W: who builds the file's sections and zoom levels — this core with zlib (host, the\n"
     "               default) or the GPU (device: the same payloads, compressed by the device's deflater)\n"
+    "  --tabix      write every text track BGZF-compressed with its tabix index: PREFIX.bedgraph.gz / PREFIX.bed.gz and FILE.gz.tbi\n"
+    "               beside each (FILE.gz.csi when a reference is longer than 2^29), what bgzip and tabix -p bed -S 1 make of the\n"
+    "               plain tracks; compressed and indexed on the GPU (TBK_TRACK_HOST_FMT=1: on the cores).  With -W the coverage\n"
+    "               stays the bigWig.  Not with -c - / stdout\n"
     "  -r,--region REGION   only the tracks of REGION: NAME, NAME:BEG or NAME:BEG-END (1-based, inclusive, commas allowed), read\n"
     "               through the file's index (input.bam.csi, input.bam.bai or input.bai; `tiebrush --index` / `--csi` write one)\n"
     "  -R,--regions-file FILE   the tracks of several regions in one run: FILE is BED (chrom start end, 0-based half-open; further\n"
@@ -56,14 +60,15 @@ static int count_regions_file_opts(int argc, char** argv) {
 
 // ---- what every run does with its records: the tracks -----------------------------------------------------------------------------
 // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
-static void open_tracks(tbh::TrackFiles& tf, sam_hdr_t* hdr, const std::string& covfname, const std::string& jfname, const std::string& sfname, bool bigwig) {
+static void open_tracks(tbh::TrackFiles& tf, sam_hdr_t* hdr, const std::string& covfname, const std::string& jfname, const std::string& sfname, bool bigwig,
+                        bool tabix) {
   std::vector<std::string> names;
   std::vector<uint32_t> lens;
   for (int t = 0; t < hdr->n_targets; ++t) {
     names.push_back(hdr->target_name[t]);
     lens.push_back(hdr->target_len[t]);
   }
-  tf.open(covfname, jfname, sfname, bigwig, names, lens);
+  tf.open(covfname, jfname, sfname, bigwig, names, lens, tabix);
 }
 
 // the cut of a region run: the table, through the one-region entries (one: the table is the region itself, which may be empty) or the
@@ -80,9 +85,19 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
   const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
   FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
   const bool cov_bw = tf.cov_bw;
+  // --tabix: a track's writer is open in the place of its FILE*
+  const bool cov_tx = tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
+  tbh::TabixDevice txd;
+  txd.ctx = ctx, txd.track_bgzf = tbk_track_bgzf, txd.track_names = tbk_track_names, txd.strerror_ = tbk_strerror, txd.last_error = tbk_last_error;
+  auto tabix_rows = [](int kind, uint32_t nr, const int32_t* t, const int32_t* s, const int32_t* e) {
+    tbk_track_rows r;
+    memset(&r, 0, sizeof(r));
+    r.mem = TBK_MEM_HOST, r.kind = kind, r.n = nr, r.tid = t, r.start = s, r.end = e, r.first_junc = 1;
+    return r;
+  };
   int rc = 0;
-  if (coutf || cov_bw || joutf) {
-    const size_t ci = (coutf || cov_bw) ? 2 * co + 2 * n + 16 + extra : 0, cj = joutf ? co + 16 : 0;
+  if (coutf || cov_bw || joutf || cov_tx || junc_tx) {
+    const size_t ci = (coutf || cov_bw || cov_tx) ? 2 * co + 2 * n + 16 + extra : 0, cj = (joutf || junc_tx) ? co + 16 : 0;
     std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
     std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
     std::vector<uint8_t> jstr(cj ? cj : 1);
@@ -116,8 +131,18 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
     }
     if (joutf)  // CJunc::write, tiecov.cpp:91-95 (numbered from 1)
       tbh::emit_junc_lines(joutf, hdr->target_name, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
+    if (cov_tx) {
+      tbk_track_rows r = tabix_rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
+      r.val = iv.data();
+      tbh::write_tabix_track(tf.cov_tx, r, hdr->target_name, &txd);
+    }
+    if (junc_tx) {
+      tbk_track_rows r = tabix_rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
+      r.val = jv.data(), r.strand = jstr.data();
+      tbh::write_tabix_track(tf.junc_tx, r, hdr->target_name, &txd);
+    }
   }
-  if (soutf) {
+  if (soutf || samp_tx) {
     // the value of the track changes only where an M segment starts or ends: at most 2 intervals per CIGAR operation + 2 per
     // record, as for the coverage track (not one per covered base); if a call still reports TBK_E2BIG it also reports the
     // count it needs, and the call is repeated with that
@@ -151,7 +176,12 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
       rc = clip->one ? tbk_sample_clip(ctx, &so, U->tid[0], U->beg[0], U->end[0]) : tbk_sample_clip_regions(ctx, &so, U);
       if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
     }
-    tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
+    if (soutf) tbh::emit_samp_lines(soutf, hdr->target_name, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
+    if (samp_tx) {
+      tbk_track_rows r = tabix_rows(TBK_TRACK_SAMPLE, so.n_intervals, st.data(), ss.data(), se.data());
+      r.count = sc.data(), r.heat = sh.data();
+      tbh::write_tabix_track(tf.samp_tx, r, hdr->target_name, &txd);
+    }
   }
 }
 
@@ -159,7 +189,7 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
 // normalised table of the BED file, through the table entries): every other statement is shared.
 static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::RegionTable& U, bool one, const std::string& index_file,
                         const std::string& covfname, const std::string& jfname, const std::string& sfname, bool bigwig,
-                        bool bw_device, const std::chrono::steady_clock::time_point t0) {
+                        bool bw_device, bool tabix, const std::chrono::steady_clock::time_point t0) {
   const bool timing = getenv("TBK_TIMING") != nullptr;
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   // every refusal comes before an output file exists
@@ -208,7 +238,7 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
   const double ms_decode = ms();
   // file names and header lines as without -r
   tbh::TrackFiles tf;
-  open_tracks(tf, hdr, covfname, jfname, sfname, bigwig);
+  open_tracks(tf, hdr, covfname, jfname, sfname, bigwig, tabix);
   const TrackClip clip{&regs, one};
   write_tracks(ctx, hdr, in, num_samples, tf, &clip, bw_device);
   tf.close();
@@ -220,7 +250,7 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
 }
 
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;DVWhc:s:j:r:R:");
+  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;tabix;DVWhc:s:j:r:R:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -233,12 +263,16 @@ int main(int argc, char* argv[]) {
     fprintf(stdout, "%s\n", VERSION);
     return 0;
   }
+  const bool tabix = args.getOpt("tabix") != nullptr;
+  if (tabix && !args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j')) GError("Error: --tabix needs at least one of -c / -j / -s (it applies to their tracks)\n");
   if (!args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j')) {
     GMessage("%s", USAGE);
     GMessage("\nError: at least one of -c/-j/-s arguments required!\n");
     return 1;
   }
   const bool bigwig = args.getOpt('W') != nullptr;
+  if (tabix && !bigwig && args.getOpt('c') && (strcmp(args.getOpt('c'), "-") == 0 || strcmp(args.getOpt('c'), "stdout") == 0))
+    GError("Error: --tabix needs a coverage file (-c PREFIX, not -c %s): an index addresses file offsets, standard output has none\n", args.getOpt('c'));
   if (args.getOpt("bigwig-writer") && !(bigwig && args.getOpt('c'))) GError("Error: --bigwig-writer needs -W (and -c)\n");
   const bool bw_device = args.getOpt("bigwig-writer") && tbh::parse_bigwig_writer(args.getOpt("bigwig-writer"));
   if (args.getOpt("verbose") || args.getOpt('V')) {
@@ -275,13 +309,13 @@ int main(int argc, char* argv[]) {
       if (!tbh::parse_region(*hdr, r, &rtid, &beg, &end, err)) GError("Error: %s\n", err.c_str());
       U.add(rtid, beg, end);
     }
-    return regions_main(hdr, infname, U, rf == nullptr, index_file, covfname, jfname, sfname, bigwig, bw_device, t0);
+    return regions_main(hdr, infname, U, rf == nullptr, index_file, covfname, jfname, sfname, bigwig, bw_device, tabix, t0);
   }
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;
-  open_tracks(tf, hdr, covfname, jfname, sfname, bigwig);
+  open_tracks(tf, hdr, covfname, jfname, sfname, bigwig, tabix);
   int num_samples = 0;
-  if (tf.samp) {  // load_sample_info (commons.h:47-71)
+  if (tf.samp || tf.samp_tx.is_open()) {  // load_sample_info (commons.h:47-71)
     num_samples = (int)hdr->co_samples().size();
     if (num_samples == 0) GError("Error: no sample lines found in header");
   }

@@ -17,8 +17,29 @@ static bool ends_with(const std::string& s, const char* suf) {
   return s.size() >= n && s.compare(s.size() - n, n, suf) == 0;
 }
 
+static const char* const kCovHead = "track type=bedGraph\n";
+static const char* const kJuncHead = "track name=junctions\n";
+static const char* const kSampHead =
+    "track type=bedGraph name=\"Sample Count Heatmap\" description=\"Sample Count Heatmap\" visibility=full "
+    "graphType=\"heatmap\" color=200,100,0 altColor=0,100,200\n";
+
+// --tabix: PREFIX<ext>.gz, opened with the track's header line
+static void open_tabix(TabixWriter& w, std::string prefix, const char* ext, const char* head, const std::vector<std::string>& names,
+                       const std::vector<uint32_t>& lens) {
+  if (ends_with(prefix, (std::string(ext) + ".gz").c_str())) prefix.resize(prefix.size() - 3);
+  if (!ends_with(prefix, ext)) prefix += ext;
+  prefix += ".gz";
+  std::string err;
+  if (!w.open(prefix, names, lens, head, err)) GError("Error creating file %s (%s)\n", prefix.c_str(), err.c_str());
+}
+
 void TrackFiles::open(std::string cov_prefix, std::string junc_prefix, std::string samp_prefix, bool bigwig, const std::vector<std::string>& names,
-                      const std::vector<uint32_t>& lens) {
+                      const std::vector<uint32_t>& lens, bool tabix) {
+  if (tabix) {  // every text track; the coverage as a bigWig stays what it is below
+    if (!cov_prefix.empty() && !bigwig && cov_prefix != "-" && cov_prefix != "stdout") open_tabix(cov_tx, cov_prefix, ".bedgraph", kCovHead, names, lens), cov_name = cov_tx.path(), cov_prefix.clear();
+    if (!junc_prefix.empty()) open_tabix(junc_tx, junc_prefix, ".bed", kJuncHead, names, lens), junc_prefix.clear();
+    if (!samp_prefix.empty()) open_tabix(samp_tx, samp_prefix, ".bedgraph", kSampHead, names, lens), samp_prefix.clear();
+  }
   if (!cov_prefix.empty()) {
     if (cov_prefix == "-" || cov_prefix == "stdout") {
       cov = stdout;
@@ -32,7 +53,7 @@ void TrackFiles::open(std::string cov_prefix, std::string junc_prefix, std::stri
       if (!ends_with(cov_prefix, ".bedgraph")) cov_prefix += ".bedgraph";
       cov = fopen(cov_prefix.c_str(), "w");
       if (!cov) GError("Error creating file %s\n", cov_prefix.c_str());
-      fprintf(cov, "track type=bedGraph\n");
+      fprintf(cov, "%s", kCovHead);
     }
     cov_name = cov_prefix;
   }
@@ -40,15 +61,13 @@ void TrackFiles::open(std::string cov_prefix, std::string junc_prefix, std::stri
     if (!ends_with(junc_prefix, ".bed")) junc_prefix += ".bed";
     junc = fopen(junc_prefix.c_str(), "w");
     if (!junc) GError("Error creating file %s\n", junc_prefix.c_str());
-    fprintf(junc, "track name=junctions\n");
+    fprintf(junc, "%s", kJuncHead);
   }
   if (!samp_prefix.empty()) {
     if (!ends_with(samp_prefix, ".bedgraph")) samp_prefix += ".bedgraph";
     samp = fopen(samp_prefix.c_str(), "w");
     if (!samp) GError("Error creating file %s\n", samp_prefix.c_str());
-    fprintf(samp,
-            "track type=bedGraph name=\"Sample Count Heatmap\" description=\"Sample Count Heatmap\" visibility=full "
-            "graphType=\"heatmap\" color=200,100,0 altColor=0,100,200\n");
+    fprintf(samp, "%s", kSampHead);
   }
 }
 
@@ -150,6 +169,13 @@ void TrackFiles::close() {
   if (junc) fclose(junc);
   if (samp) fclose(samp);
   cov = junc = samp = nullptr;
+  for (TabixWriter* w : {&cov_tx, &junc_tx, &samp_tx}) {  // (a track nobody wrote rows to: its header, the EOF member, an empty index)
+    std::string err;
+    if (!w->is_open()) continue;
+    std::vector<BaiRec> none;
+    if ((!w->head().empty() && !w->add_text(w->head().data(), w->head().size(), none, err)) || !w->close(err))
+      GError("Error: writing %s failed (%s)\n", w->path().c_str(), err.c_str());
+  }
 }
 
 void GErrorWrite() { GError("Error: failed to write an output line\n"); }

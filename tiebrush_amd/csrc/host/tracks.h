@@ -13,11 +13,14 @@
 #include "../../../include/tbk.h"
 #include "bigwig.h"
 #include "bgzf.h"
+#include "tabix.h"
 
 namespace tbh {
 
 // The open track files.  An empty prefix: that track is not written.  Coverage goes to stdout for "-" / "stdout", to PREFIX.bigwig
 // with `bigwig`, else to PREFIX.bedgraph; junctions to PREFIX.bed; the sample counts to PREFIX.bedgraph.  Errors are fatal (GError).
+// With `tabix` every text track is PREFIX.bedgraph.gz / PREFIX.bed.gz (BGZF) with its tabix index beside it (tabix.h): the track's
+// TabixWriter is open in the place of its FILE*, and takes the header line with its first rows.
 // The device section producer of the bigWig (--bigwig-writer device) as a command line has it: tiecov links libtbk.so, tiebrush binds it
 // at run time, so the entry points travel as pointers.
 struct BigWigDevice {
@@ -35,8 +38,9 @@ struct TrackFiles {
   bool cov_bw = false;
   std::vector<uint32_t> bw_lens;  // the chromosome lengths the bigWig was opened with
   std::string cov_name;
+  TabixWriter cov_tx, junc_tx, samp_tx;  // --tabix
   void open(std::string cov_prefix, std::string junc_prefix, std::string samp_prefix, bool bigwig, const std::vector<std::string>& names,
-            const std::vector<uint32_t>& lens);
+            const std::vector<uint32_t>& lens, bool tabix = false);
   void close_bigwig();  // (after every interval went to bw)
   // The coverage rows into the bigWig and the file closed (flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the value as a float).
   // dev == nullptr: the host producer.  Else the sections are tbk_bigwig_build's; a refusal of that call other than a failed write

@@ -1094,6 +1094,44 @@ int tbk_format_track(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink si
   return rc;
 }
 
+int tbk_track_bgzf(tbk_ctx* ctx, const tbk_track_rows* rows, const char* head, uint32_t head_len, const tbk_ix_opts* ix, tbk_tbx_sink sink, void* user,
+                   uint64_t* text_bytes, uint64_t* out_bytes) {
+  if (!ctx || !rows || !sink || rows->n == UINT32_MAX || (head_len && !head)) return TBK_EINVAL;
+  if (rows->mem != TBK_MEM_HOST && rows->mem != TBK_MEM_DEVICE) return TBK_EINVAL;
+  const bool cov = rows->kind == TBK_TRACK_COV, junc = rows->kind == TBK_TRACK_JUNC, samp = rows->kind == TBK_TRACK_SAMPLE;
+  if (!cov && !junc && !samp) return TBK_EINVAL;
+  const size_t n = rows->n;
+  if (n && (!rows->tid || !rows->start || !rows->end || ((cov || junc) && !rows->val) || (junc && !rows->strand) ||
+            (samp && (!rows->count || !rows->heat))))
+    return TBK_EINVAL;
+  if (n && !ctx->d_name_off) {
+    ctx->last_error = "tbk_track_bgzf: no reference names (tbk_track_names)";
+    return TBK_EINVAL;
+  }
+  if (ix) TBK_TRY(tbk_ix_check_opts(ctx, ix));
+  TBK_HIP(hipSetDevice(ctx->device));
+  tbk_prof_begin_call(ctx);
+  struct ProfEnd {
+    tbk_ctx* c;
+    ~ProfEnd() { tbk_prof_end_call(c); }
+  } prof_end{ctx};
+  // (rows, lengths and offsets, one slice of text of at most 32 MiB by default, the index arrays of a slice)
+  TBK_TRY(ws_begin_call(ctx, n * 64 + head_len + ((size_t)48 << 20) + (ix ? tbk_ix_ws_bytes((uint32_t)n, ix) : 0)));
+  RegGuard reg_guard{ctx};
+  tbk_track_rows d = *rows;
+  if (rows->mem == TBK_MEM_HOST) {
+    d.mem = TBK_MEM_DEVICE;
+    TBK_TRY(h2d(ctx, rows->tid, n, &d.tid));
+    TBK_TRY(h2d(ctx, rows->start, n, &d.start));
+    TBK_TRY(h2d(ctx, rows->end, n, &d.end));
+    if (!samp) TBK_TRY(h2d(ctx, rows->val, n, &d.val));
+    if (junc) TBK_TRY(h2d(ctx, rows->strand, n, &d.strand));
+    if (samp) TBK_TRY(h2d(ctx, rows->count, n, &d.count));
+    if (samp) TBK_TRY(h2d(ctx, rows->heat, n, &d.heat));
+  }
+  return tbk_track_bgzf_device(ctx, &d, head, head_len, ix, sink, user, text_bytes, out_bytes);
+}
+
 int tbk_bigwig_build(tbk_ctx* ctx, const tbk_track_rows* rows, uint32_t n_ref, const uint32_t* ref_len, tbk_bw_sink sink, void* user, tbk_bw_out* out) {
   if (!ctx || !rows || !sink || !out || rows->n == UINT32_MAX) return TBK_EINVAL;
   memset(out, 0, sizeof(*out));

@@ -216,6 +216,22 @@ struct TbkIxIn {
 };
 int tbk_ix_check_opts(tbk_ctx* ctx, const tbk_ix_opts* ix);  // TBK_EINVAL for a reference the format (tbk_ix_opts.reserved) cannot address
 int tbk_ix_build(tbk_ctx* ctx, const TbkIxIn& in, const tbk_ix_opts* ix, tbk_ix_part* part);
+// baix.hip: the index part of a run of track lines (tbk_track_bgzf): the same builder behind another front end (tx_rec_k), the rows in
+// the place of the records.  Unlike tbk_ix_build it allocates behind what the arena holds (the caller's rows and text stay) and leaves the
+// arena's mark to the caller.  All pointers are device memory.
+struct TbkTxIn {
+  uint32_t n;             // rows of the run: [first, first + n) of the arrays below
+  uint32_t first;
+  const int32_t *tid, *start, *end;
+  const uint64_t* off;    // [rows + 1] the lines' offsets in the track's text
+  uint64_t text0;         // the run's text starts at off[first] - text0 (text0: the bytes of a header before row `first`)
+  uint32_t nmem;          // members
+  const uint64_t* cut;    // [nmem + 1] the members' first payload bytes
+  const uint64_t* moff;   // [nmem + 1] the members' offsets in the packed run
+  uint64_t ztotal;        // bytes of the packed run
+};
+int tbk_tx_build(tbk_ctx* ctx, const TbkTxIn& in, const tbk_ix_opts* ix, tbk_ix_part* part);
+size_t tbk_ix_ws_bytes(uint32_t n, const tbk_ix_opts* ix);  // arena bytes of one build over n records / rows
 // the tile tbk_bam_decode left on the context: inflated streams, record offsets, record count (false: there is none)
 bool tbk_bam_dev_records(tbk_ctx* ctx, const uint8_t** inf, const uint64_t** rec, uint32_t* n);
 // tbk_tile_region's hold on that tile: whether `tile` is the one the last decode returned (not a joined one, not another context's: told
@@ -342,9 +358,15 @@ int tbk_sample_device(tbk_ctx* ctx, const tbk_cov_in* in, int32_t num_samples, t
 // fmt.hip: tbk_format_track's body (rows in device memory; the arena must be reserved by the caller) and tbk_track_names'
 int tbk_format_device(tbk_ctx* ctx, const tbk_track_rows* rows, tbk_track_sink sink, void* user, uint64_t* out_bytes);
 int tbk_names_upload(tbk_ctx* ctx, uint32_t n_names, const uint64_t* off, const char* bytes);
+// fmt.hip: tbk_track_bgzf's body (rows in device memory; the arena must be reserved by the caller)
+int tbk_track_bgzf_device(tbk_ctx* ctx, const tbk_track_rows* rows, const char* head, uint32_t head_len, const tbk_ix_opts* ix, tbk_tbx_sink sink, void* user,
+                          uint64_t* text_bytes, uint64_t* out_bytes);
 // the two pinned slice buffers of tbk_format_track / tbk_bigwig_build, at least `bytes` each
 int tbk_pin_slices(tbk_ctx* ctx, size_t bytes);
 // bgzdef.hip: a device payload run cut at d_cut[0 .. nmem] -> zlib streams back to back (*d_out) and their offsets (*d_zoff, [nmem + 1])
 int tbk_zlib_sections(tbk_ctx* ctx, const uint8_t* d_src, const uint64_t* d_cut, uint32_t nmem, uint8_t** d_out, uint64_t* total, const uint64_t** d_zoff);
+// bgzdef.hip: a device byte run cut every 0xff00 bytes -> BGZF members packed back to back (*d_out), the cuts (*d_cut, [*nmem + 1]) and
+// the members' offsets in the run (*d_moff, [*nmem + 1]), in the encoder's buffers until its next call
+int tbk_bgzf_run(tbk_ctx* ctx, const uint8_t* d_src, uint64_t n, uint8_t** d_out, uint64_t* total, uint32_t* nmem, const uint64_t** d_cut, const uint64_t** d_moff);
 // bigwig.hip: tbk_bigwig_build's body (rows in device memory, n > 0; the arena must be reserved by the caller)
 int tbk_bigwig_device(tbk_ctx* ctx, const tbk_track_rows* rows, uint32_t n_ref, const uint32_t* ref_len, tbk_bw_sink sink, void* user, tbk_bw_out* out);
