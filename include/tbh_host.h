@@ -83,6 +83,26 @@ int64_t tbh_regions_from_bed(const char* bam_path, const char* bed_path, int32_t
 int64_t tbh_index_query_regions(const char* bam_path, const char* index_path, uint32_t n, const int32_t* tid, const int64_t* beg, const int64_t* end,
                                 uint64_t* chunk_beg, uint64_t* chunk_end, uint64_t cap);
 
+/* ---- The features of `--features BED --summary OUT` (appended; tbh_abi_version stays 1) ----
+ * The BED file at bed_path against the header of bam_path, ONE feature per line in the file's order: nothing is merged, sorted or
+ * dropped.  Columns 1-3 as tbh_regions_from_bed reads them (and the same lines skipped), 4 the name (default "."), 5 ignored, 6 the
+ * strand '+', '-' or '.' (default '.'); an end beyond the reference is cut to its length.  line[i] is the feature's line in the file,
+ * counted from 1.  Returns the number n >= 1 of features; tid / beg / end / strand / line are written when n <= cap, and the names,
+ * each closed by a NUL byte, to `names` when they fit names_cap; *names_bytes (optional) = the bytes the names need.  Otherwise nothing
+ * of that part is written: call again with room.  -1 on failure (tbh_last_error names the line): what tbh_regions_from_bed refuses, a
+ * strand other than + - ., a feature that is empty after the cut, a file without any feature. */
+int64_t tbh_features_from_bed(const char* bam_path, const char* bed_path, int32_t* tid, int64_t* beg, int64_t* end, uint8_t* strand, uint64_t* line,
+                              uint64_t cap, char* names, uint64_t names_cap, uint64_t* names_bytes);
+
+/* The host summariser behind TBK_SUMMARY_HOST=1 and `tbh_tool summary`: tbk_cov_summary's outputs (include/tbk.h) by plain loops over
+ * HOST rows, a feature's products added in row order.  Rows as there: n_intervals interval rows sorted by (tid, start) and disjoint,
+ * n_junctions junction rows sorted by (tid, start, end, strand); want_cov / want_junc 0: that part is not computed, its rows are not
+ * read and its outputs may be NULL.  strand NULL = all '.'.  Returns 0, or -1 for a null argument or n == 0. */
+int tbh_cov_summary_host(uint32_t n, const int32_t* tid, const int64_t* beg, const int64_t* end, const uint8_t* strand, int want_cov, uint32_t n_intervals,
+                         const int32_t* iv_tid, const int32_t* iv_start, const int32_t* iv_end, const double* iv_val, int want_junc, uint32_t n_junctions,
+                         const int32_t* j_tid, const int32_t* j_start, const int32_t* j_end, const uint8_t* j_strand, const double* j_val,
+                         uint64_t* covered, double* sum, double* max, double* junc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -717,6 +717,36 @@ typedef int (*tbk_tbx_sink)(void* user, const uint8_t* members, uint64_t n_bytes
 int tbk_track_bgzf(tbk_ctx* ctx, const tbk_track_rows* rows, const char* head, uint32_t head_len, const tbk_ix_opts* ix, tbk_tbx_sink sink, void* user,
                    uint64_t* text_bytes, uint64_t* out_bytes);
 
+/* ---- The rows of a coverage call against a list of features (ABI version 9, appended) -----------------------------------
+ * What `tiecov --features BED --summary OUT` / `tiebrush --features BED --summary OUT` run.  The reference has no such option, so this
+ * replaces no interface of it; the contract is stated against the rows themselves. */
+typedef struct tbk_features {
+  uint32_t n;
+  const int32_t* tid;
+  const int64_t* beg;     /* 0-based, half-open [beg, end)                                                              */
+  const int64_t* end;
+  const uint8_t* strand;  /* '+', '-', '.'; NULL = all '.'                                                              */
+} tbk_features;            /* HOST arrays, any order, overlaps allowed                                                   */
+
+typedef struct tbk_feat_out {
+  int32_t mem;             /* HOST or DEVICE, each array [n]                                                             */
+  uint64_t* covered;       /* bases of the feature under an interval row                                                 */
+  double* sum;             /* sum over those bases of the row's value                                                    */
+  double* max;             /* largest value of a row on the feature, 0 when there is none                                */
+  double* junc;            /* summed value of the junction rows with the feature's tid, start, end and strand ('.': every strand) */
+} tbk_feat_out;
+
+/* rows: what tbk_coverage_tile wrote (mem HOST: uploaded by the call; or DEVICE), not changed.  cap_intervals == 0: covered / sum / max
+ * are not computed and their pointers may be NULL; cap_junctions == 0: the same for junc.  n_intervals == 0 / n_junctions == 0 give
+ * zeros, status 0.  covered and max are exact; junc adds its rows (at most three from tbk_coverage_tile) in row order; sum adds one
+ * rounded product val * bases per row of the feature in an order fixed by the inputs — two calls on the same inputs give the same bits —
+ * so |sum - S| <= gamma(m + 1) * SUM |val * bases| for m rows, and sum is exact where every row value is a multiple of 2^-3 and the sum
+ * is below 2^50 (integral YC: every default run).
+ * TBK_EINVAL, before anything is launched: n == 0, a tid < 0, a beg < 0, an end <= beg, a strand byte other than + - .  TBK_EINVAL, found on
+ * the device as tbk_cov_clip finds it: interval rows that are not sorted by (tid, start) and disjoint, junction rows that are not sorted
+ * by (tid, start, end, strand).  Nothing faults and the context takes the next call. */
+int tbk_cov_summary(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_features* features, tbk_feat_out* out);
+
 #ifdef __cplusplus
 }
 #endif

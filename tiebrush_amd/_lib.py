@@ -29,7 +29,7 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
            "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route",
-           "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build", "tbk_track_bgzf"]
+           "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build", "tbk_track_bgzf", "tbk_cov_summary"]
 
 
 class CollapseOpts(C.Structure):
@@ -107,6 +107,14 @@ class IxPart(C.Structure):
 
 class Regions(C.Structure):
     _fields_ = [("n", C.c_uint32), ("tid", _P), ("beg", _P), ("end", _P)]
+
+
+class Features(C.Structure):
+    _fields_ = [("n", C.c_uint32), ("tid", _P), ("beg", _P), ("end", _P), ("strand", _P)]
+
+
+class FeatOut(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("covered", _P), ("sum", _P), ("max", _P), ("junc", _P)]
 
 
 TRACK = {"cov": 0, "junc": 1, "sample": 2}
@@ -256,6 +264,8 @@ def load():
     L.tbk_sample_clip_regions.restype = C.c_int
     L.tbk_tile_regions.argtypes = [_P, C.POINTER(SoaIn), C.POINTER(Regions), C.POINTER(SoaIn), _P, C.POINTER(C.c_uint32)]
     L.tbk_tile_regions.restype = C.c_int
+    L.tbk_cov_summary.argtypes = [_P, C.POINTER(CovOut), C.POINTER(Features), C.POINTER(FeatOut)]
+    L.tbk_cov_summary.restype = C.c_int
     _lib = L
     return L
 
@@ -264,7 +274,7 @@ def load():
 HOST_LIB_PATH = os.environ.get("TBK_HOST_LIB") or os.path.join(_HERE, "_build", "libtbh.so")
 HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin",
                 "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin", "tbh_index_query",
-                "tbh_regions_from_bed", "tbh_index_query_regions"]   # include/tbh_host.h
+                "tbh_regions_from_bed", "tbh_index_query_regions", "tbh_features_from_bed", "tbh_cov_summary_host"]   # include/tbh_host.h
 _host = None
 
 
@@ -301,6 +311,10 @@ def load_host():
     H.tbh_regions_from_bed.restype = C.c_int64
     H.tbh_index_query_regions.argtypes = [C.c_char_p, C.c_char_p, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint64]
     H.tbh_index_query_regions.restype = C.c_int64
+    H.tbh_features_from_bed.argtypes = [C.c_char_p, C.c_char_p, _P, _P, _P, _P, _P, C.c_uint64, _P, C.c_uint64, C.POINTER(C.c_uint64)]
+    H.tbh_features_from_bed.restype = C.c_int64
+    H.tbh_cov_summary_host.argtypes = [C.c_uint32, _P, _P, _P, _P, C.c_int, C.c_uint32, _P, _P, _P, _P, C.c_int, C.c_uint32, _P, _P, _P, _P, _P, _P, _P, _P, _P]
+    H.tbh_cov_summary_host.restype = C.c_int
     _host = H
     return H
 

@@ -994,6 +994,44 @@ class Context:
             res.update(j_tid=jv[0][:b], j_start=jv[1][:b], j_end=jv[2][:b], j_strand=jv[3][:b], j_val=jv[4][:b])
         return res
 
+    def cov_summary(self, rows, features):
+        """tbk_cov_summary: the result dict of coverage() (numpy rows or device tensors; a dict without iv_* / j_* rows leaves those
+        columns out) read against features: [(tid, beg, end)] or [(tid, beg, end, strand)] with strand one of '+', '-', '.', or a dict
+        of arrays tid / beg / end (/ strand).  Returns numpy arrays, one element per feature: covered (uint64), sum, max, junc."""
+        keep = []
+        if isinstance(features, dict):
+            ft, fb, fe = (np.ascontiguousarray(features[k], dtype=d) for k, d in (("tid", np.int32), ("beg", np.int64), ("end", np.int64)))
+            fs = np.ascontiguousarray(features["strand"], dtype=np.uint8) if features.get("strand") is not None else None
+        else:
+            fl = [tuple(f) for f in features]
+            ft = np.array([f[0] for f in fl], dtype=np.int32)
+            fb = np.array([f[1] for f in fl], dtype=np.int64)
+            fe = np.array([f[2] for f in fl], dtype=np.int64)
+            fs = None
+            if any(len(f) > 3 for f in fl):
+                fs = np.array([(f[3] if isinstance(f[3], int) else ord(f[3])) if len(f) > 3 else ord(".") for f in fl], dtype=np.uint8)
+        n = len(ft)
+        want_cov, want_junc = "iv_tid" in rows, "j_tid" in rows
+        dev = any(_is_torch(rows.get(k)) for k in ("iv_tid", "j_tid"))
+        a, b = (len(rows["iv_tid"]) if want_cov else 0), (len(rows["j_tid"]) if want_junc else 0)
+
+        def ptr(name, dt, cnt):
+            return _addr(rows[name], dt, keep, cnt) if cnt else None
+        # (a capacity of zero says "not computed": rows of a wanted but empty track keep a capacity of one)
+        o = _lib.CovOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, max(a, 1) if want_cov else 0, ptr("iv_tid", np.int32, a), ptr("iv_start", np.int32, a),
+                        ptr("iv_end", np.int32, a), ptr("iv_val", np.float64, a), max(b, 1) if want_junc else 0, ptr("j_tid", np.int32, b),
+                        ptr("j_start", np.int32, b), ptr("j_end", np.int32, b), ptr("j_strand", np.uint8, b), ptr("j_val", np.float64, b), a, b, 0, 0)
+        f = _lib.Features(n, ft.ctypes.data, fb.ctypes.data, fe.ctypes.data, fs.ctypes.data if fs is not None else None)
+        res = dict(covered=np.zeros(n, dtype=np.uint64), sum=np.zeros(n), max=np.zeros(n), junc=np.zeros(n))
+        fo = _lib.FeatOut(_lib.TBK_MEM_HOST, *(res[k].ctypes.data if n else None for k in ("covered", "sum", "max", "junc")))
+        self._order_after_torch(dev)
+        self._check(self.L.tbk_cov_summary(self.h, C.byref(o), C.byref(f), C.byref(fo)), "tbk_cov_summary")
+        if not want_cov:
+            del res["covered"], res["sum"], res["max"]
+        if not want_junc:
+            del res["junc"]
+        return res
+
     def sample(self, cin: CovInput, num_samples: int, cap_intervals=None):
         keep = []
         if isinstance(cin, DeviceCovView):                      # (region_view / groups_to_cov_in: the view carries yx)
@@ -1228,6 +1266,50 @@ def regions_from_bed(bam_path, bed_path):
         if n <= cap:
             return [(int(t[i]), int(b[i]), int(e[i])) for i in range(n)]
         cap = int(n)
+
+
+def features_from_bed(bam_path, bed_path):
+    """tbh_features_from_bed: the BED file's lines against the header of bam_path as features, one per line in the file's order (nothing
+    merged, sorted or dropped): a dict of numpy arrays tid (int32), beg, end (int64, the end cut to the reference), strand (uint8: '+',
+    '-', '.') and line (uint64, the line in the file from 1) and the list name.  RuntimeError (with the line number) for a malformed
+    line, an unknown chrom, a strand other than + - ., a feature that is empty after the cut.  Host only."""
+    H = _lib.load_host()
+    cap, ncap = 64, 1024
+    while True:
+        t, b, e = np.zeros(cap, dtype=np.int32), np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int64)
+        s, ln = np.zeros(cap, dtype=np.uint8), np.zeros(cap, dtype=np.uint64)
+        names, nb = C.create_string_buffer(ncap), C.c_uint64(0)
+        n = H.tbh_features_from_bed(os.fsencode(bam_path), os.fsencode(bed_path), t.ctypes.data, b.ctypes.data, e.ctypes.data, s.ctypes.data, ln.ctypes.data,
+                                    cap, C.cast(names, C.c_void_p), ncap, C.byref(nb))
+        if n < 0:
+            raise RuntimeError((H.tbh_last_error() or b"").decode())
+        if n <= cap and nb.value <= ncap:
+            return dict(tid=t[:n].copy(), beg=b[:n].copy(), end=e[:n].copy(), strand=s[:n].copy(), line=ln[:n].copy(),
+                        name=[x.decode() for x in names.raw[:nb.value].split(b"\0")[:n]])
+        cap, ncap = max(cap, int(n)), max(ncap, int(nb.value))
+
+
+def cov_summary_host(rows, features):
+    """tbh_cov_summary_host: Context.cov_summary's columns by the host summariser (plain loops, a feature's rows added in row order)
+    from numpy rows and a dict of feature arrays tid / beg / end (/ strand).  Host only."""
+    H = _lib.load_host()
+    keep = []
+    ft, fb, fe = (np.ascontiguousarray(features[k], dtype=d) for k, d in (("tid", np.int32), ("beg", np.int64), ("end", np.int64)))
+    fs = np.ascontiguousarray(features["strand"], dtype=np.uint8) if features.get("strand") is not None else None
+    n = len(ft)
+    want_cov, want_junc = "iv_tid" in rows, "j_tid" in rows
+    a, b = (len(rows["iv_tid"]) if want_cov else 0), (len(rows["j_tid"]) if want_junc else 0)
+
+    def ptr(name, dt, cnt):
+        return _addr(rows[name], dt, keep, cnt) if cnt else None
+    res = dict(covered=np.zeros(n, dtype=np.uint64), sum=np.zeros(n), max=np.zeros(n), junc=np.zeros(n))
+    rc = H.tbh_cov_summary_host(n, ft.ctypes.data, fb.ctypes.data, fe.ctypes.data, fs.ctypes.data if fs is not None else None, int(want_cov), a,
+                                ptr("iv_tid", np.int32, a), ptr("iv_start", np.int32, a), ptr("iv_end", np.int32, a), ptr("iv_val", np.float64, a), int(want_junc), b,
+                                ptr("j_tid", np.int32, b), ptr("j_start", np.int32, b), ptr("j_end", np.int32, b), ptr("j_strand", np.uint8, b), ptr("j_val", np.float64, b),
+                                *(res[k].ctypes.data for k in ("covered", "sum", "max", "junc")))
+    if rc != 0:
+        raise RuntimeError((H.tbh_last_error() or b"").decode())
+    return res
 
 
 def index_query_regions(bam_path, table, index_path=None):

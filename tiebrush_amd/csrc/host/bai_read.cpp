@@ -378,6 +378,71 @@ bool regions_from_bed_file(const BamHeader& hdr, const std::string& bed_path, Re
   return regions_from_bed(hdr, std::string(b.begin(), b.end()), bed_path, U, err);
 }
 
+bool features_from_bed(const BamHeader& hdr, const std::string& text, const std::string& what, FeatureTable& F, std::string& err) {
+  F = FeatureTable();
+  size_t lineno = 0;
+  for (size_t p = 0; p < text.size();) {
+    size_t nl = text.find('\n', p);
+    if (nl == std::string::npos) nl = text.size();
+    std::string line = text.substr(p, nl - p);
+    p = nl + 1;
+    ++lineno;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    const std::string at = what + " line " + std::to_string(lineno) + ": ";
+    std::vector<std::string> f;
+    for (size_t q = 0; q < line.size() && f.size() < 6;) {
+      while (q < line.size() && (line[q] == '\t' || line[q] == ' ')) ++q;
+      size_t e = q;
+      while (e < line.size() && line[e] != '\t' && line[e] != ' ') ++e;
+      if (e > q) f.push_back(line.substr(q, e - q));
+      q = e;
+    }
+    if (f.empty() || f[0][0] == '#' || f[0] == "track" || f[0] == "browser") continue;
+    if (f.size() < 3) return err = at + "fewer than three fields (expected chrom start end [name [score [strand]]])", false;
+    int64_t b = 0, e = 0;
+    if (!bed_coord(f[1], &b)) return err = at + "the start '" + f[1] + "' is not a non-negative integer", false;
+    if (!bed_coord(f[2], &e)) return err = at + "the end '" + f[2] + "' is not a non-negative integer", false;
+    if (b > e) return err = at + "start > end", false;
+    const int t = hdr.name2tid(f[0]);
+    if (t < 0) return err = at + "unknown reference name '" + f[0] + "'", false;
+    uint8_t strand = '.';
+    if (f.size() >= 6) {
+      if (f[5] != "+" && f[5] != "-" && f[5] != ".") return err = at + "the strand '" + f[5] + "' is not one of + - .", false;
+      strand = (uint8_t)f[5][0];
+    }
+    e = std::min<int64_t>(e, hdr.target_len[(size_t)t]);
+    if (b >= e) return err = at + "the feature is empty on its reference", false;
+    F.tid.push_back((int32_t)t), F.beg.push_back(b), F.end.push_back(e), F.strand.push_back(strand);
+    F.name.push_back(f.size() >= 4 ? f[3] : std::string("."));
+    F.line.push_back(lineno);
+  }
+  if (F.n() == 0) return err = what + ": no feature in it", false;
+  return true;
+}
+
+bool features_from_bed_file(const BamHeader& hdr, const std::string& bed_path, FeatureTable& F, std::string& err) {
+  std::vector<uint8_t> b;
+  if (!slurp(bed_path, b)) return err = "cannot read the features file " + bed_path, false;
+  return features_from_bed(hdr, std::string(b.begin(), b.end()), bed_path, F, err);
+}
+
+bool features_inside(const FeatureTable& F, const RegionTable& U, const std::string& what, std::string& err) {
+  for (size_t i = 0; i < F.n(); ++i) {
+    // the last interval that begins at or before the feature's begin on its reference
+    size_t lo = 0, hi = U.n();
+    while (lo < hi) {
+      const size_t m = lo + (hi - lo) / 2;
+      if (U.tid[m] < F.tid[i] || (U.tid[m] == F.tid[i] && U.beg[m] <= F.beg[i]))
+        lo = m + 1;
+      else
+        hi = m;
+    }
+    if (lo == 0 || U.tid[lo - 1] != F.tid[i] || U.end[lo - 1] < F.end[i])
+      return err = what + " line " + std::to_string(F.line[i]) + ": the feature is not wholly inside one interval of the region", false;
+  }
+  return true;
+}
+
 bool read_spans(const std::string& bam_path, const std::vector<IdxChunk>& chunks, std::vector<RegionSpan>& spans, uint64_t* bytes_read, std::string& err) {
   spans.clear();
   if (bytes_read) *bytes_read = 0;

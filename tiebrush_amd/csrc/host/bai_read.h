@@ -82,6 +82,24 @@ bool parse_region(const BamHeader& hdr, const std::string& region, int32_t* tid,
 bool regions_from_bed(const BamHeader& hdr, const std::string& text, const std::string& what, RegionTable& U, std::string& err);
 bool regions_from_bed_file(const BamHeader& hdr, const std::string& bed_path, RegionTable& U, std::string& err);
 
+// The features of `--features BED --summary OUT`: one per BED line, in the file's order — nothing is merged, sorted or
+// dropped, so features may overlap, nest and repeat.  line[i] is the feature's line in the text (1-based).
+struct FeatureTable {
+  std::vector<int32_t> tid;
+  std::vector<int64_t> beg, end;
+  std::vector<uint8_t> strand;  // '+', '-', '.'
+  std::vector<std::string> name;
+  std::vector<uint64_t> line;
+  size_t n() const { return tid.size(); }
+};
+// BED text as regions_from_bed reads it (separators, skipped lines, '\r'), columns 1-3 required, 4 the name (default "."), 5 ignored, 6 the
+// strand (default '.').  An end beyond the reference is cut to its length.  false, with the line number in err: what regions_from_bed
+// refuses, a strand other than + - ., a feature that is empty after the cut; (without a line number) a text without a feature.
+bool features_from_bed(const BamHeader& hdr, const std::string& text, const std::string& what, FeatureTable& F, std::string& err);
+bool features_from_bed_file(const BamHeader& hdr, const std::string& bed_path, FeatureTable& F, std::string& err);
+// true when every feature lies wholly inside one interval of the normalised table U; false: err names the first one's line that does not
+bool features_inside(const FeatureTable& F, const RegionTable& U, const std::string& what, std::string& err);
+
 // One merged chunk's bytes: the whole BGZF members from the chunk's first member on; the records are the inflated bytes from first_uoff
 // in the first member up to last_uoff in the last one (0: the last member read is whole, the chunk ends where it ends).
 struct RegionSpan {

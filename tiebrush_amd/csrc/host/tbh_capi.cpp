@@ -14,6 +14,7 @@
 #include "bgzf.h"
 #include "tagwrite.h"
 #include "tmerge.h"
+#include "tracks.h"
 
 namespace {
 thread_local std::string g_err;
@@ -154,6 +155,44 @@ int64_t tbh_index_query_regions(const char* bam_path, const char* index_path, ui
   if (ch.size() <= cap)
     for (size_t i = 0; i < ch.size(); ++i) chunk_beg[i] = ch[i].beg, chunk_end[i] = ch[i].end;
   return (int64_t)ch.size();
+}
+
+int64_t tbh_features_from_bed(const char* bam_path, const char* bed_path, int32_t* tid, int64_t* beg, int64_t* end, uint8_t* strand, uint64_t* line,
+                              uint64_t cap, char* names, uint64_t names_cap, uint64_t* names_bytes) {
+  if (!bam_path || !bed_path || (cap && (!tid || !beg || !end || !strand || !line)) || (names_cap && !names)) return fail("tbh_features_from_bed: null argument");
+  std::string err;
+  tbh::BamFile bf;
+  if (!bf.open(bam_path, err, 1)) return fail("tbh_features_from_bed: " + err);
+  tbh::FeatureTable F;
+  if (!tbh::features_from_bed_file(bf.hdr, bed_path, F, err)) return fail("tbh_features_from_bed: " + err);
+  if (F.n() <= cap)
+    for (size_t i = 0; i < F.n(); ++i) tid[i] = F.tid[i], beg[i] = F.beg[i], end[i] = F.end[i], strand[i] = F.strand[i], line[i] = F.line[i];
+  uint64_t nb = 0;
+  for (const std::string& s : F.name) nb += s.size() + 1;
+  if (names_bytes) *names_bytes = nb;
+  if (nb <= names_cap) {
+    char* p = names;
+    for (const std::string& s : F.name) memcpy(p, s.c_str(), s.size() + 1), p += s.size() + 1;
+  }
+  return (int64_t)F.n();
+}
+
+int tbh_cov_summary_host(uint32_t n, const int32_t* tid, const int64_t* beg, const int64_t* end, const uint8_t* strand, int want_cov, uint32_t n_intervals,
+                         const int32_t* iv_tid, const int32_t* iv_start, const int32_t* iv_end, const double* iv_val, int want_junc, uint32_t n_junctions,
+                         const int32_t* j_tid, const int32_t* j_start, const int32_t* j_end, const uint8_t* j_strand, const double* j_val,
+                         uint64_t* covered, double* sum, double* max, double* junc) {
+  if (!n || !tid || !beg || !end || (want_cov && (!covered || !sum || !max)) || (want_junc && !junc)) return fail("tbh_cov_summary_host: null argument or no feature");
+  if ((want_cov && n_intervals && (!iv_tid || !iv_start || !iv_end || !iv_val)) || (want_junc && n_junctions && (!j_tid || !j_start || !j_end || !j_strand || !j_val)))
+    return fail("tbh_cov_summary_host: null rows");
+  tbh::FeatureTable F;
+  F.tid.assign(tid, tid + n), F.beg.assign(beg, beg + n), F.end.assign(end, end + n);
+  if (strand) F.strand.assign(strand, strand + n);
+  else F.strand.assign(n, (uint8_t)'.');
+  tbh::FeatSummary S;
+  tbh::summarise_features(F, want_cov != 0, n_intervals, iv_tid, iv_start, iv_end, iv_val, want_junc != 0, n_junctions, j_tid, j_start, j_end, j_strand, j_val, S);
+  if (want_cov) memcpy(covered, S.covered.data(), (size_t)n * 8), memcpy(sum, S.sum.data(), (size_t)n * 8), memcpy(max, S.max.data(), (size_t)n * 8);
+  if (want_junc) memcpy(junc, S.junc.data(), (size_t)n * 8);
+  return 0;
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@
 //   rquery IN.bam REGIONS.bed [INDEX]   the same for the region table of a BED file: "regions R", a "region tid beg end"
 //                                 line per interval of the normalised table, the chunks merged over the whole table, records, hits
 //   mquery REGION THREADS IN1.bam ... / mrquery REGIONS.bed THREADS IN1.bam ...   the host plumbing of `tiebrush -r` / `-R`, per input
+//   summary IN.bam COV.bedgraph JUNC.bed FEATURES.bed OUT.tsv   the per-feature summary of `tiecov --features --summary` from our own
+//                                 plain tracks, by the host summariser alone ("-" for a track that is not there)
 //   mkbam SOADIR PREFIX [LEVEL [THREADS]]   encode the raw SoA arrays of a synthetic tile (file_off, tid, pos, flag, mapq, strand,
 //                                 nh, cig_off, cig as little-endian files + header.txt) as PREFIX<f>.bam, one per input file: the
 //                                 records tiebrush_amd.synth.write_bams writes (SEQ '*', QNAME r<f>_<i>, NH:C / XS:A), files in parallel
@@ -34,6 +36,7 @@
 #include "tmerge.h"
 #include "bigwig.h"
 #include "tabix.h"
+#include "tracks.h"
 
 template <class T>
 static bool slurp(const std::string& dir, const char* name, std::vector<T>& v) {
@@ -581,6 +584,57 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery ...\n");
+  // the host-only form of `tiecov --features FEATURES.bed --summary OUT.tsv`: our own plain tracks read back (a first line
+  // that begins with "track" is the header; "-" in the place of a track: that part of the summary stays zero), the host summariser, the
+  // TSV writer.  The tracks' values are what "%.3f" printed.
+  if (cmd == "summary" && argc == 7) {
+    std::string err;
+    tbh::BamFile bf;
+    tbh::FeatureTable F;
+    if (!bf.open(argv[2], err, 1) || !tbh::features_from_bed_file(bf.hdr, argv[5], F, err)) {
+      fprintf(stderr, "tbh_tool summary: %s\n", err.c_str());
+      return 1;
+    }
+    std::vector<int32_t> tid[2], start[2], end[2];
+    std::vector<double> val[2];
+    std::vector<uint8_t> jstrand;
+    bool have[2] = {false, false};
+    for (int k = 0; k < 2; ++k) {
+      const std::string path = argv[3 + k];
+      if (path == "-") continue;
+      have[k] = true;
+      FILE* f = fopen(path.c_str(), "r");
+      if (!f) {
+        fprintf(stderr, "tbh_tool summary: cannot read %s\n", path.c_str());
+        return 1;
+      }
+      char line[4096], name[2048], jname[64], strand = '.';
+      for (size_t lineno = 1; fgets(line, sizeof(line), f); ++lineno) {
+        if (lineno == 1 && strncmp(line, "track", 5) == 0) continue;
+        long long s = 0, e = 0;
+        double v = 0;
+        const bool ok = k == 0 ? sscanf(line, "%2047s %lld %lld %lf", name, &s, &e, &v) == 4
+                               : sscanf(line, "%2047s %lld %lld %63s %lf %c", name, &s, &e, jname, &v, &strand) == 6;
+        const int t = ok ? bf.hdr.name2tid(name) : -1;
+        if (t < 0) {
+          fprintf(stderr, "tbh_tool summary: %s line %zu: not a row of the track\n", path.c_str(), lineno);
+          fclose(f);
+          return 1;
+        }
+        tid[k].push_back(t), start[k].push_back((int32_t)s), end[k].push_back((int32_t)e), val[k].push_back(v);
+        if (k == 1) jstrand.push_back((uint8_t)strand);
+      }
+      fclose(f);
+    }
+    tbh::FeatSummary S;
+    tbh::summarise_features(F, have[0], (uint32_t)tid[0].size(), tid[0].data(), start[0].data(), end[0].data(), val[0].data(), have[1], (uint32_t)tid[1].size(),
+                            tid[1].data(), start[1].data(), end[1].data(), jstrand.data(), val[1].data(), S);
+    if (!tbh::write_summary_tsv(argv[6], bf.hdr.target_name, F, S, err)) {
+      fprintf(stderr, "tbh_tool summary: %s\n", err.c_str());
+      return 1;
+    }
+    return 0;
+  }
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery|summary ...\n");
   return 2;
 }

@@ -42,6 +42,7 @@ struct TbkApi {
   decltype(&tbk_format_track) format_track = nullptr;
   decltype(&tbk_bigwig_build) bigwig_build = nullptr;  // optional: --bigwig-writer device
   decltype(&tbk_track_bgzf) track_bgzf = nullptr;      // optional: --tabix
+  decltype(&tbk_cov_summary) cov_summary = nullptr;    // optional: --features / --summary
   std::string error;
   bool has_tracks() const { return coverage_tile && sample_tile && track_names && format_track; }
 
@@ -95,6 +96,7 @@ struct TbkApi {
     format_track = (decltype(format_track))dlsym(h, "tbk_format_track");
     bigwig_build = (decltype(bigwig_build))dlsym(h, "tbk_bigwig_build");
     track_bgzf = (decltype(track_bgzf))dlsym(h, "tbk_track_bgzf");
+    cov_summary = (decltype(cov_summary))dlsym(h, "tbk_cov_summary");
     if (abi_version() != TBK_ABI_VERSION) {
       error = "libtbk.so has another ABI version";
       return false;

@@ -92,6 +92,10 @@ static const char* USAGE =
     "                       FILE.gz.tbi, or FILE.gz.csi for references longer than 2^29), as tiecov --tabix; with --bigwig the\n"
     "                       coverage stays the bigWig; needs one of --cov / --junc / --samp, not --cov - and not --ranks\n"
     "                       (the tracks are what tiecov writes when it reads OUT.bam; not with --ranks)\n"
+    "  --features BED --summary OUT.tsv   also write tiecov's per-feature summary of the output (as tiecov --features --summary: one\n"
+    "                       line per line of BED with size, covered bases, sum, mean0, mean and max of the coverage and the junction\n"
+    "                       support of the feature taken as an intron); goes with any of the tracks or alone; with -r / -R every\n"
+    "                       feature must lie inside one interval of the region; not with --ranks\n"
     "  --index              also write the output's BAM index OUT.bam.bai (what samtools index makes of OUT.bam; not with --ranks,\n"
     "                       not when the output goes to standard output)\n"
     "  --csi                also write the output's CSI index OUT.bam.csi (what samtools index -c makes of OUT.bam: for references\n"
@@ -615,7 +619,9 @@ static int fwrite_sink(void* user, const char* p, uint64_t n) { return fwrite(p,
 // The tracks of the whole output, as tiecov_main.cpp computes them from its decode of the file: coverage and junctions in one
 // tbk_coverage_tile, the sample counts in tbk_sample_tile, the text by tbk_format_track (the host formatter when the device
 // formatter refuses a value, or with TBK_TRACK_HOST_FMT).
-static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, TrackRecs& T, const std::vector<std::string>& names, int num_samples, bool bw_device) {
+// With a summary job the coverage and junction rows are computed whatever tracks are open, and summarised.
+static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, TrackRecs& T, const std::vector<std::string>& names, int num_samples, bool bw_device,
+                         const tbh::SummaryJob& sj) {
   TbkApi& api = dev.api;
   tbk_ctx* ctx = dev.ctx;
   auto t0 = tnow();
@@ -658,8 +664,8 @@ static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, Track
   txd.ctx = ctx, txd.track_bgzf = api.track_bgzf, txd.track_names = api.track_names, txd.strerror_ = api.strerror_, txd.last_error = api.last_error;
   txd.names_set = !env.track_host_fmt;
   if ((cov_tx || junc_tx || samp_tx) && !env.track_host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
-  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx) {
-    size_t ci = (tf.cov || tf.cov_bw || cov_tx) ? 2 * co + 2 * n + 16 : 0, cj = (tf.junc || junc_tx) ? co + 16 : 0;
+  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx || sj.on()) {
+    size_t ci = (tf.cov || tf.cov_bw || cov_tx || sj.on()) ? 2 * co + 2 * n + 16 : 0, cj = (tf.junc || junc_tx || sj.on()) ? co + 16 : 0;
     std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
     std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
     std::vector<uint8_t> jstr(cj ? cj : 1);
@@ -675,6 +681,11 @@ static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, Track
     ms_cov = tms(a, tnow());
     if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
     if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    if (sj.on()) {
+      tbh::SummaryDevice sd;
+      sd.ctx = ctx, sd.summary = api.cov_summary, sd.strerror_ = api.strerror_, sd.last_error = api.last_error;
+      tbh::write_summary(sj, names, o, sd);
+    }
     if (tf.cov) {
       tbk_track_rows r = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
       r.val = iv.data();
@@ -1435,16 +1446,20 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
 
 // the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
-  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", "bigwig-writer", nullptr};
+  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", "bigwig-writer", "features", "summary", nullptr};
   const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQFR");
-  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", nullptr};
+  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", "features", "summary", nullptr};
   const int region_files = count_value_option(argc, argv, "regions-file", 'R', value_longs_R, "oNQFr");
-  bool ranks = false, tracks = false, index = false, csi = false, tabix = false;
+  bool ranks = false, tracks = false, index = false, csi = false, tabix = false, summary = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
     tabix = tabix || strcmp(argv[i], "--tabix") == 0;
     index = index || strcmp(argv[i], "--index") == 0;
     csi = csi || strcmp(argv[i], "--csi") == 0;
+    for (const char* o : {"--features", "--summary"}) {
+      const size_t k = strlen(o);
+      summary = summary || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
+    }
     for (const char* o : {"--cov", "--junc", "--samp", "--bigwig"}) {
       const size_t k = strlen(o);
       tracks = tracks || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
@@ -1452,6 +1467,7 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
   }
   if (ranks && tabix) GError("Error: --tabix is not available with --ranks (run tiecov --tabix on the output)\n");
   if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
+  if (ranks && summary) GError("Error: --features / --summary are not available with --ranks (run tiecov --features --summary on the output)\n");
   if (ranks && index) GError("Error: --index is not available with --ranks (index the output afterwards)\n");
   if (ranks && csi) GError("Error: --csi is not available with --ranks (index the output afterwards)\n");
   if (regions > 1) GError("Error: -r / --region given more than once (one region per run)\n");
@@ -1467,7 +1483,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;tabix;index;csi;region=;regions-file=;SMLPEDVho:N:Q:F:r:R:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;tabix;index;csi;region=;regions-file=;features=;summary=;SMLPEDVho:N:Q:F:r:R:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1541,6 +1557,9 @@ int main(int argc, char* argv[]) {
   if (tabix && !tracks) GError("Error: --tabix needs at least one of --cov / --junc / --samp (it applies to their tracks)\n");
   if (tabix && !bigwig && (cov_prefix == "-" || cov_prefix == "stdout"))
     GError("Error: --tabix needs a coverage file (--cov PREFIX, not --cov %s): an index addresses file offsets, standard output has none\n", cov_prefix.c_str());
+  if ((args.getOpt("summary") != nullptr) != (args.getOpt("features") != nullptr))
+    GError("Error: --features BED and --summary OUT.tsv go together (%s is missing)\n", args.getOpt("summary") ? "--features" : "--summary");
+  const bool summary = args.getOpt("summary") != nullptr;
   const char* region = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");
   const char* regions_file = args.getOpt('R') ? args.getOpt('R') : args.getOpt("regions-file");
   const bool regional = region || regions_file;
@@ -1561,8 +1580,16 @@ int main(int argc, char* argv[]) {
     refuse_region_inputs(inRecords, false, ropt);
     rplan.reset(new RegionPlan(plan_region(inRecords, region, regions_file)));
   }
-  Device dev(env, opt, dev_writer, tracks, regional ? t_begin : tnow());
-  if (!regional) inRecords.start();
+  // --features / --summary: the BED file is read (and refused) against the output's header before any output file exists — and before
+  // the device's helper thread does: a refusal leaves through exit(), which must not run beside a thread that is bringing the runtime up
+  // (so a summary run opens its inputs ahead of the device, as a region run does)
+  tbh::SummaryJob sjob;
+  if (summary) {
+    if (!regional) inRecords.start();
+    sjob.setup(args.getOpt("features"), args.getOpt("summary"), *inRecords.header(), rplan ? &rplan->U : nullptr);
+  }
+  Device dev(env, opt, dev_writer, tracks || summary, regional || summary ? t_begin : tnow());
+  if (!regional && !summary) inRecords.start();
   auto t_ctx = tnow();
   Totals tot;
   // the tracks: the output header's sample lines (load_sample_info, commons.h:47-71) are checked before any work, the files opened
@@ -1576,8 +1603,8 @@ int main(int argc, char* argv[]) {
       if (num_samples == 0) GError("Error: no sample lines found in header");
     }
     tfiles.open(cov_prefix, junc_prefix, samp_prefix, bigwig, h->target_name, h->target_len, tabix);
-    trecs.reset(new TrackRecs());
   }
+  if (tracks || summary) trecs.reset(new TrackRecs());
   // the index: a reference a BAI cannot address is refused before the output is created; an older index of the same name goes now
   tbh::BaiIndex bai;
   if (want_index) {
@@ -1603,7 +1630,7 @@ int main(int argc, char* argv[]) {
   out.close();
   if (trecs) {
     dev.wait();
-    write_tracks(dev, env, tfiles, *trecs, inRecords.header()->target_name, num_samples, bw_device);
+    write_tracks(dev, env, tfiles, *trecs, inRecords.header()->target_name, num_samples, bw_device, sjob);
   }
   auto t_closed = tnow();
   if (env.timing) fprintf(stderr, "writer closed at %.1f ms\n", tms(dev.t_start, t_closed));

@@ -26,7 +26,7 @@ static const char* USAGE =
     "TieCov v" VERSION " (MI355X build)\n"
     "Summarises a (TieBrush-collapsed) BAM file as BED-like tracks.\n"
     "\n"
-    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [-r REGION | -R FILE] input.bam\n"
+    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [--features BED --summary OUT.tsv] [-r REGION | -R FILE] input.bam\n"
     "\n"
     "  -h,--help    print this text and exit\n"
     "  --version    print the version and exit\n"
@@ -45,16 +45,21 @@ static const char* USAGE =
     "  -R,--regions-file FILE   the tracks of several regions in one run: FILE is BED (chrom start end, 0-based half-open; further\n"
     "               columns ignored), its intervals sorted and merged where they overlap or abut; read through the index like -r\n"
     "  --index-file PATH    the index to use with -r / -R\n"
-    " At least one of -c / -j / -s is required.\n";
+    "  --features BED --summary OUT.tsv   per-feature coverage and junction support: one line of OUT.tsv per line of BED (chrom start\n"
+    "               end [name [score [strand]]]; features may overlap, nest and repeat, nothing is merged): size, covered bases, sum,\n"
+    "               mean0 = sum / size, mean = sum / covered, max of the coverage, and junc = the junction track's value for the feature\n"
+    "               taken as an intron (same start and end; strand + - or, for '.', every strand).  Computed on the GPU from the rows of\n"
+    "               -c / -j (TBK_SUMMARY_HOST=1: on this core).  With -r / -R every feature must lie inside one interval of the region\n"
+    " At least one of -c / -j / -s / --summary is required.\n";
 
 // ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
 // how often -r / --region is given (Args keeps the last value of a repeated option)
 static int count_region_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", nullptr};
+  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", "features", "summary", nullptr};
   return count_value_option(argc, argv, "region", 'r', value_longs, "csjR");
 }
 static int count_regions_file_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", nullptr};
+  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", "features", "summary", nullptr};
   return count_value_option(argc, argv, "regions-file", 'R', value_longs, "csjr");
 }
 
@@ -79,8 +84,10 @@ struct TrackClip {
 };
 
 // The rows of tbk_coverage_tile / tbk_sample_tile for `in` (host arrays, or a device view), cut to *clip where one is given, into the
-// open files of tf.  An input of no records goes the same way: the calls give no rows and status 0.
-static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int num_samples, tbh::TrackFiles& tf, const TrackClip* clip, bool bw_device) {
+// open files of tf.  An input of no records goes the same way: the calls give no rows and status 0.  With a summary job the coverage
+// and junction rows are computed whatever tracks are open, and summarised before the cut.
+static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int num_samples, tbh::TrackFiles& tf, const TrackClip* clip, bool bw_device,
+                         const tbh::SummaryJob& sj) {
   const size_t n = in.n_records, co = in.n_cigar_ops;
   const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
   FILE *coutf = tf.cov, *joutf = tf.junc, *soutf = tf.samp;
@@ -96,8 +103,8 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
     return r;
   };
   int rc = 0;
-  if (coutf || cov_bw || joutf || cov_tx || junc_tx) {
-    const size_t ci = (coutf || cov_bw || cov_tx) ? 2 * co + 2 * n + 16 + extra : 0, cj = (joutf || junc_tx) ? co + 16 : 0;
+  if (coutf || cov_bw || joutf || cov_tx || junc_tx || sj.on()) {
+    const size_t ci = (coutf || cov_bw || cov_tx || sj.on()) ? 2 * co + 2 * n + 16 + extra : 0, cj = (joutf || junc_tx || sj.on()) ? co + 16 : 0;
     std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
     std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
     std::vector<uint8_t> jstr(cj ? cj : 1);
@@ -118,6 +125,11 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
     rc = tbk_coverage_tile(ctx, &in, &o);
     if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
     if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", tbk_strerror(rc), tbk_last_error(ctx));
+    if (sj.on()) {
+      tbh::SummaryDevice sd;
+      sd.ctx = ctx, sd.summary = tbk_cov_summary, sd.strerror_ = tbk_strerror, sd.last_error = tbk_last_error;
+      tbh::write_summary(sj, hdr->target_name, o, sd);
+    }
     if (clip) {
       const tbk_regions* U = clip->U;
       rc = clip->one ? tbk_cov_clip(ctx, &o, U->tid[0], U->beg[0], U->end[0]) : tbk_cov_clip_regions(ctx, &o, U);
@@ -189,7 +201,7 @@ static void write_tracks(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int
 // normalised table of the BED file, through the table entries): every other statement is shared.
 static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::RegionTable& U, bool one, const std::string& index_file,
                         const std::string& covfname, const std::string& jfname, const std::string& sfname, bool bigwig,
-                        bool bw_device, bool tabix, const std::chrono::steady_clock::time_point t0) {
+                        bool bw_device, bool tabix, const tbh::SummaryJob& sj, const std::chrono::steady_clock::time_point t0) {
   const bool timing = getenv("TBK_TIMING") != nullptr;
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   // every refusal comes before an output file exists
@@ -240,7 +252,7 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
   tbh::TrackFiles tf;
   open_tracks(tf, hdr, covfname, jfname, sfname, bigwig, tabix);
   const TrackClip clip{&regs, one};
-  write_tracks(ctx, hdr, in, num_samples, tf, &clip, bw_device);
+  write_tracks(ctx, hdr, in, num_samples, tf, &clip, bw_device, sj);
   tf.close();
   if (timing)
     fprintf(stderr, "tiecov %s phases ms: %u regions | index %.1f | chunk reads %.1f (%llu bytes in %u chunks) | context up at %.1f | decode + filter %.1f (%u of %u records) | tracks %.1f\n",
@@ -250,7 +262,7 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
 }
 
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;tabix;DVWhc:s:j:r:R:");
+  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;features=;summary=;tabix;DVWhc:s:j:r:R:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -265,7 +277,9 @@ int main(int argc, char* argv[]) {
   }
   const bool tabix = args.getOpt("tabix") != nullptr;
   if (tabix && !args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j')) GError("Error: --tabix needs at least one of -c / -j / -s (it applies to their tracks)\n");
-  if (!args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j')) {
+  if ((args.getOpt("summary") != nullptr) != (args.getOpt("features") != nullptr))
+    GError("Error: --features BED and --summary OUT.tsv go together (%s is missing)\n", args.getOpt("summary") ? "--features" : "--summary");
+  if (!args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j') && !args.getOpt("summary")) {
     GMessage("%s", USAGE);
     GMessage("\nError: at least one of -c/-j/-s arguments required!\n");
     return 1;
@@ -290,6 +304,7 @@ int main(int argc, char* argv[]) {
   std::string infname = args.nextNonOpt();
   GSamReader samreader(infname.c_str(), SAM_QNAME | SAM_FLAG | SAM_RNAME | SAM_POS | SAM_CIGAR | SAM_AUX);
   sam_hdr_t* hdr = samreader.header();
+  tbh::SummaryJob sj;  // (--features / --summary: refused, where they are, before any output file exists)
   if (args.getOpt('r') || args.getOpt("region") || args.getOpt('R') || args.getOpt("regions-file") || args.getOpt("index-file")) {
     const auto t0 = std::chrono::steady_clock::now();
     if (count_region_opts(argc, argv) > 1) GError("Error: -r / --region given more than once (one region per run)\n");
@@ -309,8 +324,10 @@ int main(int argc, char* argv[]) {
       if (!tbh::parse_region(*hdr, r, &rtid, &beg, &end, err)) GError("Error: %s\n", err.c_str());
       U.add(rtid, beg, end);
     }
-    return regions_main(hdr, infname, U, rf == nullptr, index_file, covfname, jfname, sfname, bigwig, bw_device, tabix, t0);
+    sj.setup(args.getOpt("features"), args.getOpt("summary"), *hdr, &U);
+    return regions_main(hdr, infname, U, rf == nullptr, index_file, covfname, jfname, sfname, bigwig, bw_device, tabix, sj, t0);
   }
+  sj.setup(args.getOpt("features"), args.getOpt("summary"), *hdr, nullptr);
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;
   open_tracks(tf, hdr, covfname, jfname, sfname, bigwig, tabix);
@@ -392,7 +409,7 @@ int main(int argc, char* argv[]) {
   in.yc = yc.data();
   in.strand = strand.data();
   in.yx = yx.data();
-  write_tracks(ctx, hdr, in, num_samples, tf, nullptr, bw_device);
+  write_tracks(ctx, hdr, in, num_samples, tf, nullptr, bw_device, sj);
   tf.close();
   tbk_destroy(ctx);
   return 0;

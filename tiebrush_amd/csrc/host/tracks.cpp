@@ -205,4 +205,100 @@ void emit_samp_lines(FILE* f, const std::vector<std::string>& names, uint32_t n,
   emit_lines(f, n, [&](uint32_t i, char* b, size_t cap) { return fmt_samp_line(b, cap, names[tid[i]].c_str(), start[i], end[i], count[i], heat[i]); });
 }
 
+void summarise_features(const FeatureTable& F, bool want_cov, uint32_t ni, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val,
+                        bool want_junc, uint32_t nj, const int32_t* jtid, const int32_t* jstart, const int32_t* jend, const uint8_t* jstrand, const double* jval,
+                        FeatSummary& S) {
+  S.resize(F.n());
+  for (size_t f = 0; f < F.n(); ++f) {
+    const int32_t ft = F.tid[f];
+    const int64_t fb = F.beg[f], fe = F.end[f];
+    if (want_cov && ni) {
+      uint32_t lo = 0, hi = ni;  // the first row that ends behind the feature's begin on its reference, or lies on a later one
+      while (lo < hi) {
+        const uint32_t m = lo + (hi - lo) / 2;
+        if (tid[m] > ft || (tid[m] == ft && (int64_t)end[m] > fb))
+          hi = m;
+        else
+          lo = m + 1;
+      }
+      double s = 0.0, mx = 0.0;
+      uint64_t c = 0;
+      for (uint32_t i = lo; i < ni && tid[i] == ft && (int64_t)start[i] < fe; ++i) {
+        const int64_t len = std::min<int64_t>(end[i], fe) - std::max<int64_t>(start[i], fb);
+        s += val[i] * (double)len;
+        c += (uint64_t)len;
+        mx = (i == lo || val[i] > mx) ? val[i] : mx;
+      }
+      S.covered[f] = c, S.sum[f] = s, S.max[f] = c ? mx : 0.0;
+    }
+    if (want_junc && nj) {
+      uint32_t lo = 0, hi = nj;  // the first junction row at or behind (tid, start, end)
+      while (lo < hi) {
+        const uint32_t m = lo + (hi - lo) / 2;
+        const bool ge = jtid[m] != ft ? jtid[m] > ft : ((int64_t)jstart[m] != fb ? (int64_t)jstart[m] > fb : (int64_t)jend[m] >= fe);
+        if (ge)
+          hi = m;
+        else
+          lo = m + 1;
+      }
+      double j = 0.0;
+      for (uint32_t i = lo; i < nj && jtid[i] == ft && (int64_t)jstart[i] == fb && (int64_t)jend[i] == fe; ++i)
+        if (F.strand[f] == '.' || jstrand[i] == F.strand[f]) j += jval[i];
+      S.junc[f] = j;
+    }
+  }
+}
+
+bool write_summary_tsv(const std::string& path, const std::vector<std::string>& names, const FeatureTable& F, const FeatSummary& S, std::string& err) {
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) return err = "cannot create " + path, false;
+  bool ok = fputs("#chrom\tstart\tend\tname\tstrand\tsize\tcovered\tsum\tmean0\tmean\tmax\tjunc\n", f) >= 0;
+  for (size_t i = 0; ok && i < F.n(); ++i) {
+    const int64_t size = F.end[i] - F.beg[i];
+    const double mean0 = S.sum[i] / (double)size, mean = S.covered[i] ? S.sum[i] / (double)S.covered[i] : 0.0;
+    ok = fprintf(f, "%s\t%lld\t%lld\t%s\t%c\t%lld\t%llu\t%.3f\t%.3f\t%.3f\t%.3f\t%.3f\n", names[(size_t)F.tid[i]].c_str(), (long long)F.beg[i], (long long)F.end[i],
+                 F.name[i].c_str(), (char)F.strand[i], (long long)size, (unsigned long long)S.covered[i], S.sum[i], mean0, mean, S.max[i], S.junc[i]) > 0;
+  }
+  if (fclose(f) != 0) ok = false;
+  if (!ok) err = "writing " + path + " failed";
+  return ok;
+}
+
+void SummaryJob::setup(const char* features_opt, const char* summary_opt, const BamHeader& hdr, const RegionTable* U) {
+  if (summary_opt && !features_opt) GError("Error: --summary needs --features BED (the features to summarise)\n");
+  if (features_opt && !summary_opt) GError("Error: --features needs --summary OUT.tsv (the file to write)\n");
+  if (!summary_opt) return;
+  if (!*summary_opt || !*features_opt) GError("Error: --features / --summary need a file name\n");
+  bed = features_opt, out = summary_opt;
+  std::string err;
+  if (!features_from_bed_file(hdr, bed, F, err)) GError("Error: --features: %s\n", err.c_str());
+  // (outside the region's intervals the rows are incomplete; inside them they are the whole file's)
+  if (U && !features_inside(F, *U, bed, err)) GError("Error: --features: %s\n", err.c_str());
+}
+
+void write_summary(const SummaryJob& job, const std::vector<std::string>& names, const tbk_cov_out& rows, const SummaryDevice& dev) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const FeatureTable& F = job.F;
+  const bool host = getenv("TBK_SUMMARY_HOST") && strcmp(getenv("TBK_SUMMARY_HOST"), "0") != 0;
+  FeatSummary S;
+  if (host) {
+    summarise_features(F, true, rows.n_intervals, rows.iv_tid, rows.iv_start, rows.iv_end, rows.iv_val, true, rows.n_junctions, rows.j_tid, rows.j_start,
+                       rows.j_end, rows.j_strand, rows.j_val, S);
+  } else {
+    if (!dev.summary) GError("Error: --summary: the loaded libtbk.so has no tbk_cov_summary (an older build?)\n");
+    S.resize(F.n());
+    tbk_features f;
+    f.n = (uint32_t)F.n(), f.tid = F.tid.data(), f.beg = F.beg.data(), f.end = F.end.data(), f.strand = F.strand.data();
+    tbk_feat_out o;
+    o.mem = TBK_MEM_HOST, o.covered = S.covered.data(), o.sum = S.sum.data(), o.max = S.max.data(), o.junc = S.junc.data();
+    const int rc = dev.summary(dev.ctx, &rows, &f, &o);
+    if (rc != 0) GError("Error: GPU feature summary failed: %s (%s)\n", dev.strerror_(rc), dev.last_error(dev.ctx));
+  }
+  std::string err;
+  if (!write_summary_tsv(job.out, names, F, S, err)) GError("Error: --summary: %s\n", err.c_str());
+  if (getenv("TBK_TIMING"))
+    fprintf(stderr, "summary phase ms: %s | %zu features | %u interval rows | %u junction rows | %.1f\n", host ? "host" : "device", F.n(), rows.n_intervals,
+            rows.n_junctions, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+}
+
 }  // namespace tbh

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../../include/tbk.h"
+#include "bai_read.h"
 #include "bigwig.h"
 #include "bgzf.h"
 #include "tabix.h"
@@ -68,6 +69,43 @@ void emit_samp_lines(FILE* f, const std::vector<std::string>& names, uint32_t n,
                      const int64_t* count, const float* heat);
 
 void GErrorWrite();  // [[noreturn]]: "failed to write an output line"
+
+// ---- `--features BED --summary OUT`: the rows of a coverage call read against features --------------------------------
+// what tbk_cov_summary computes, one element per feature
+struct FeatSummary {
+  std::vector<uint64_t> covered;
+  std::vector<double> sum, max, junc;
+  void resize(size_t n) { covered.assign(n, 0), sum.assign(n, 0.0), max.assign(n, 0.0), junc.assign(n, 0.0); }
+};
+// The host summariser (TBK_SUMMARY_HOST=1, `tbh_tool summary`): plain loops over host rows, tbk_cov_summary's contract — interval rows
+// sorted by (tid, start) and disjoint, junction rows sorted by (tid, start, end, strand); a feature's products are added in row order.
+// want_cov / want_junc false: those columns stay zero.
+void summarise_features(const FeatureTable& F, bool want_cov, uint32_t ni, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val,
+                        bool want_junc, uint32_t nj, const int32_t* jtid, const int32_t* jstart, const int32_t* jend, const uint8_t* jstrand, const double* jval,
+                        FeatSummary& S);
+// the summary file: the header line, then one line per feature in the table's order; mean0 = sum / size, mean = sum / covered (0 when
+// nothing is covered), in double.  false: the file cannot be created or written
+bool write_summary_tsv(const std::string& path, const std::vector<std::string>& names, const FeatureTable& F, const FeatSummary& S, std::string& err);
+
+// The device summariser as a command line has it (see BigWigDevice).  summary == nullptr: the library in use has no tbk_cov_summary.
+struct SummaryDevice {
+  tbk_ctx* ctx = nullptr;
+  decltype(&tbk_cov_summary) summary = nullptr;
+  decltype(&tbk_strerror) strerror_ = nullptr;
+  decltype(&tbk_last_error) last_error = nullptr;
+};
+// `--features BED --summary OUT` of a run: parsed (and refused) before any output file exists, written by write_summary
+struct SummaryJob {
+  std::string bed, out;
+  FeatureTable F;
+  bool on() const { return !out.empty(); }
+  // The two options' rules and the BED file against the header (and, in a region run, against its normalised table U: every feature
+  // wholly inside one interval).  Errors are fatal (GError) and name the line.
+  void setup(const char* features_opt, const char* summary_opt, const BamHeader& hdr, const RegionTable* U);
+};
+// The summary of HOST rows (what tbk_coverage_tile wrote, before any clip) into job.out: tbk_cov_summary through dev, or the host
+// summariser with TBK_SUMMARY_HOST=1.  Errors are fatal; a missing tbk_cov_summary is one.  TBK_TIMING: a "summary phase ms" line.
+void write_summary(const SummaryJob& job, const std::vector<std::string>& names, const tbk_cov_out& rows, const SummaryDevice& dev);
 
 template <class F>
 void emit_lines(FILE* f, uint32_t n, F fmt) {
