@@ -62,7 +62,7 @@ def test_tiecov_device_writer_equals_default(tmp_path, name):
 
 @pytest.mark.parametrize("name", ["t1", "t2"])
 def test_tiecov_region_device_writer(tmp_path, name):
-    """-r: the writer takes the clipped rows (the same write_tracks)"""
+    """-r: the writer takes the clipped rows (the same run_tracks)"""
     rows = _golden_rows(name)
     a, b = rows[len(rows) // 3], rows[len(rows) // 2]
     chrom = a[0]

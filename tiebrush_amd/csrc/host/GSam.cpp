@@ -83,17 +83,7 @@ void GSamRecord::setupCoordinates() {
   end = ex.end;
 }
 
-char GSamRecord::spliceStrand() {
-  char c = tag_char1("XS");
-  if (c == 0) {
-    char m = tag_char1("ts");
-    if (m == '+' || m == '-') {
-      if (flags() & 0x10) c = (m == '+') ? '-' : '+';
-      else c = m;
-    }
-  }
-  return (c == '+' || c == '-') ? c : '.';
-}
+char GSamRecord::spliceStrand() { return tbh::splice_strand(view()); }
 
 std::string GSamRecord::cigar() {
   tbh::RecView v = view();

@@ -264,6 +264,20 @@ double aux2f(const uint8_t* s) {
 char aux2A(const uint8_t* s) { return *s == 'A' ? (char)s[1] : 0; }
 const char* aux2Z(const uint8_t* s) { return (*s == 'Z' || *s == 'H') ? (const char*)(s + 1) : nullptr; }
 
+char splice_strand(const RecView& v) {
+  const uint8_t *a = v.aux_begin(), *e = v.aux_end();
+  auto char1 = [&](const char tag[2]) -> char {  // GSam.cpp:436-444 (tag_char1)
+    const uint8_t* s = aux_get(a, e, tag);
+    return s && (*s == 'A' || *s == 'Z') ? (char)s[1] : 0;
+  };
+  char c = char1("XS");
+  if (c == 0) {
+    const char m = char1("ts");
+    if (m == '+' || m == '-') c = (v.flag() & 0x10) ? (m == '+' ? '-' : '+') : m;
+  }
+  return (c == '+' || c == '-') ? c : '.';
+}
+
 int BamRec::update_int(const char tag[2], int64_t val) {
   if (val < INT32_MIN || val > (int64_t)UINT32_MAX) return -1;
   uint8_t type;

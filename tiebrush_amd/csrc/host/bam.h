@@ -57,6 +57,9 @@ int64_t aux2i(const uint8_t* s);  // bam_aux2i: integer types, else 0
 double aux2f(const uint8_t* s);   // bam_aux2f: d, f, integers, else 0
 char aux2A(const uint8_t* s);     // bam_aux2A: 'A' else 0
 const char* aux2Z(const uint8_t* s);  // bam_aux2Z: Z/H else NULL
+// GSamRecord::spliceStrand (GSam.cpp:464-475): the first character of XS (type A or Z); without one, that of ts, turned over for a record
+// on the reverse strand (flag 0x10); '+', '-' or '.'
+char splice_strand(const RecView& v);
 
 // An owned, editable record (the bam1_t the reference mutates before sam_write1)
 struct BamRec {

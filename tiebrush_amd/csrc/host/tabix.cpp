@@ -204,34 +204,35 @@ uint32_t host_slice_rows() {
 }
 }  // namespace
 
-void write_tabix_track(TabixWriter& w, const tbk_track_rows& r, const std::vector<std::string>& names, TabixDevice* dev) {
+void set_track_names(const TrackApi& api, const std::vector<std::string>& names) {
+  std::vector<uint64_t> off(names.size() + 1, 0);
+  std::string blob;
+  for (size_t t = 0; t < names.size(); ++t) blob += names[t], off[t + 1] = blob.size();
+  const int rc = api.track_names(api.ctx, (uint32_t)names.size(), off.data(), blob.data());
+  if (rc != 0) GError("Error: GPU track names failed: %s (%s)\n", api.strerror_(rc), api.last_error(api.ctx));
+}
+
+void write_tabix_track(TabixWriter& w, const tbk_track_rows& r, const std::vector<std::string>& names, const TrackApi& api, bool* names_set) {
   const auto t0 = std::chrono::steady_clock::now();
   const char* kinds[3] = {"coverage", "junctions", "samples"};
   const char* writer = "host";
   uint64_t text_bytes = 0;
   bool done = false;
   std::string err;
-  if (dev && !getenv("TBK_TRACK_HOST_FMT")) {
-    if (!dev->names_set) {
-      std::vector<uint64_t> off(names.size() + 1, 0);
-      std::string blob;
-      for (size_t t = 0; t < names.size(); ++t) blob += names[t], off[t + 1] = blob.size();
-      const int rc = dev->track_names(dev->ctx, (uint32_t)names.size(), off.data(), blob.data());
-      if (rc != 0) GError("Error: GPU track names failed: %s (%s)\n", dev->strerror_(rc), dev->last_error(dev->ctx));
-      dev->names_set = true;
-    }
+  if (!getenv("TBK_TRACK_HOST_FMT")) {
+    if (!*names_set) set_track_names(api, names), *names_set = true;
     tbk_ix_opts ix;
     memset(&ix, 0, sizeof(ix));
     ix.n_ref = (uint32_t)w.index().ref_len().size(), ix.reserved = w.index().ix_format(), ix.ref_len = w.index().ref_len().data();
     TbxBridge b{&w};
     uint64_t out_bytes = 0;
-    const int rc = dev->track_bgzf(dev->ctx, &r, w.head().data(), (uint32_t)w.head().size(), &ix, TbxBridge::sink, &b, &text_bytes, &out_bytes);
+    const int rc = api.track_bgzf(api.ctx, &r, w.head().data(), (uint32_t)w.head().size(), &ix, TbxBridge::sink, &b, &text_bytes, &out_bytes);
     if (rc == 0) {
       done = true, writer = "device";
     } else {
-      if (b.failed || w.runs()) GError("Error: writing %s failed (%s: %s)\n", w.path().c_str(), dev->strerror_(rc), dev->last_error(dev->ctx));
-      fprintf(stderr, "Warning: the device track writer refused %s (%s: %s); the host writer takes it\n", w.path().c_str(), dev->strerror_(rc),
-              dev->last_error(dev->ctx));
+      if (b.failed || w.runs()) GError("Error: writing %s failed (%s: %s)\n", w.path().c_str(), api.strerror_(rc), api.last_error(api.ctx));
+      fprintf(stderr, "Warning: the device track writer refused %s (%s: %s); the host writer takes it\n", w.path().c_str(), api.strerror_(rc),
+              api.last_error(api.ctx));
     }
   }
   if (!done) {

@@ -57,18 +57,13 @@ class TabixWriter {
 bool tabix_host_track(TabixWriter& w, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end,
                       const std::function<int(uint32_t, char*, size_t)>& fmt, uint32_t slice_rows, int threads, std::string& err);
 
-// The device producer as a command line has it (tiecov links libtbk.so, tiebrush binds it at run time).
-struct TabixDevice {
-  tbk_ctx* ctx = nullptr;
-  decltype(&tbk_track_bgzf) track_bgzf = nullptr;
-  decltype(&tbk_track_names) track_names = nullptr;
-  decltype(&tbk_strerror) strerror_ = nullptr;
-  decltype(&tbk_last_error) last_error = nullptr;
-  bool names_set = false;  // the reference names are on the context (tbk_track_names)
-};
-// One track from HOST rows into an open writer, and the writer closed.  dev == nullptr or TBK_TRACK_HOST_FMT: the host path.  Else the
-// runs are tbk_track_bgzf's; a refusal of that call before its first run hands the track to the host path (a line on stderr says so).
+struct TrackApi;  // tracks.h: the device entry points as a command line has them
+// The reference names onto the context, for tbk_format_track and tbk_track_bgzf.  Errors are fatal (GError).
+void set_track_names(const TrackApi& api, const std::vector<std::string>& names);
+// One track from HOST rows into an open writer, and the writer closed.  TBK_TRACK_HOST_FMT: the host path.  Else the runs are
+// api.track_bgzf's, after set_track_names unless *names_set says the run has called it (it does afterwards); a refusal of that call
+// before its first run hands the track to the host path (a line on stderr says so).
 // Errors are fatal (GError).  TBK_TIMING: a "tabix phase ms" line on stderr.
-void write_tabix_track(TabixWriter& w, const tbk_track_rows& rows, const std::vector<std::string>& names, TabixDevice* dev);
+void write_tabix_track(TabixWriter& w, const tbk_track_rows& rows, const std::vector<std::string>& names, const TrackApi& api, bool* names_set);
 
 }  // namespace tbh

@@ -249,89 +249,35 @@ static void spawn_ranks_launcher_if_asked(int argc, char* argv[], const Env& env
 }
 
 // ---- tracks (--cov / --junc / --samp): what tiecov would read back from the output BAM.  Every group that goes into the file adds its
-// record here as tiecov decodes it (tiecov_main.cpp: tid, pos, flag, CIGAR, spliceStrand from XS / ts) with the YC / YX values the writer
-// put into that record.  Those are (float)yc and yx for a record that carried none of the three tags, and otherwise whatever the tag
-// update left: an integer YC of an old TieBrush input is not replaced by bam_aux_update_float (bam.cpp: update_float), and tiecov reads
-// that stale value.  The one source of the written bytes is the writer's own tagging (tagwrite.cpp), so such records are tagged again
-// here and their tags read back.  Once the routes are done the whole file's records go through tbk_coverage_tile / tbk_sample_tile in one
-// call each, as in tiecov, so the JUNC numbering and the bundles run over the whole file whatever tiles the collapse used.
-struct TrackRecs {
-  std::vector<int32_t> tid, pos;
-  std::vector<uint16_t> flag;
-  std::vector<uint32_t> cig_off{0}, cig;
-  std::vector<double> yc;
-  std::vector<int64_t> yx;
-  std::vector<uint8_t> strand;
-
-  static void written_values(const tbh::RecView& v, double gyc, int64_t gyx, int32_t gyd, double* wyc, int64_t* wyx) {
-    bool fresh = gyx >= 0 && gyx <= (int64_t)UINT32_MAX;  // (tagwrite.cpp: the tags are appended as they are)
-    for (const uint8_t* a = v.aux_begin(); fresh && a + 3 <= v.aux_end();) {
-      const size_t sz = tbh::aux_field_size(a, v.aux_end());
-      if (!sz) break;
-      if (a[0] == 'Y' && (a[1] == 'C' || a[1] == 'X' || a[1] == 'D')) fresh = false;
-      a += sz;
-    }
-    if (fresh) {
-      *wyc = (double)(float)gyc, *wyx = gyx;
-      return;
-    }
-    thread_local std::vector<uint8_t> o;
-    thread_local tbh::BamRec rr;
-    o.clear();
-    tbh::append_tagged(v, gyc, gyx, gyd, o, rr);
-    tbh::RecView w;
-    w.p = o.data() + 4;
-    w.len = (uint32_t)(o.size() - 4);
-    *wyc = 1.0, *wyx = 1;  // (tiecov.cpp:482-485 defaults)
-    if (const uint8_t* t = tbh::aux_get(w.aux_begin(), w.aux_end(), "YC")) *wyc = tbh::aux2f(t);
-    if (const uint8_t* t = tbh::aux_get(w.aux_begin(), w.aux_end(), "YX")) *wyx = tbh::aux2i(t);
+// record to a tbh::CovRecs as tiecov decodes it (tracks.h: tid, pos, flag, CIGAR, splice strand) with the YC / YX values the writer
+// put into that record: written_values.  Those are (float)yc and yx for a record that carried none of the three tags, and otherwise
+// whatever the tag update left: an integer YC of an old TieBrush input is not replaced by bam_aux_update_float (bam.cpp: update_float),
+// and tiecov reads that stale value.  The one source of the written bytes is the writer's own tagging (tagwrite.cpp), so such records
+// are tagged again here and their tags read back.  Once the routes are done the whole file's records go through tbh::run_tracks, as in
+// tiecov, so the JUNC numbering and the bundles run over the whole file whatever tiles the collapse used.
+static void written_values(const tbh::RecView& v, double gyc, int64_t gyx, int32_t gyd, double* wyc, int64_t* wyx) {
+  bool fresh = gyx >= 0 && gyx <= (int64_t)UINT32_MAX;  // (tagwrite.cpp: the tags are appended as they are)
+  for (const uint8_t* a = v.aux_begin(); fresh && a + 3 <= v.aux_end();) {
+    const size_t sz = tbh::aux_field_size(a, v.aux_end());
+    if (!sz) break;
+    if (a[0] == 'Y' && (a[1] == 'C' || a[1] == 'X' || a[1] == 'D')) fresh = false;
+    a += sz;
   }
-
-  // groups [0, ng) of one write, in file order: rec(g) their records, gyc / gyx / gyd the collapse's values
-  void add(uint32_t ng, const RecFn& rec, const double* gyc, const int64_t* gyx, const int32_t* gyd, int threads) {
-    const size_t b = tid.size();
-    tid.resize(b + ng), pos.resize(b + ng), flag.resize(b + ng), yc.resize(b + ng), yx.resize(b + ng), strand.resize(b + ng);
-    cig_off.resize(b + ng + 1);
-    const int T = ng < 16384 ? 1 : std::max(1, threads);
-    auto par = [&](const std::function<void(uint32_t, uint32_t)>& f) {
-      std::vector<std::thread> th;
-      for (int t = 1; t < T; ++t) th.emplace_back(f, (uint32_t)((uint64_t)ng * t / T), (uint32_t)((uint64_t)ng * (t + 1) / T));
-      f(0, (uint32_t)((uint64_t)ng / T));
-      for (auto& x : th) x.join();
-    };
-    par([&](uint32_t lo, uint32_t hi) {
-      for (uint32_t g = lo; g < hi; ++g) {
-        const tbh::RecView v = rec(g);
-        const size_t i = b + g;
-        tid[i] = v.tid(), pos[i] = v.pos(), flag[i] = v.flag();
-        cig_off[i + 1] = v.n_cigar();
-        written_values(v, gyc[g], gyx[g], gyd[g], &yc[i], &yx[i]);
-        const uint8_t *a = v.aux_begin(), *e = v.aux_end();  // spliceStrand as tiecov_main.cpp reads it
-        char xs = 0, ts = 0;
-        if (const uint8_t* t = tbh::aux_get(a, e, "XS")) xs = (*t == 'A' || *t == 'Z') ? (char)t[1] : 0;
-        if (!xs)
-          if (const uint8_t* t = tbh::aux_get(a, e, "ts")) ts = (*t == 'A' || *t == 'Z') ? (char)t[1] : 0;
-        char c = xs;
-        if (c == 0 && (ts == '+' || ts == '-')) c = (flag[i] & 0x10) ? (ts == '+' ? '-' : '+') : ts;
-        strand[i] = (uint8_t)((c == '+' || c == '-') ? c : '.');
-      }
-    });
-    uint64_t ops = cig_off[b];
-    for (size_t i = b; i < b + ng; ++i) {
-      const uint32_t k = cig_off[i + 1];
-      cig_off[i + 1] = (uint32_t)(ops += k);
-      if (ops >= (1ull << 32)) GError("Error: the output is too large for one coverage tile (--cov / --junc / --samp)\n");
-    }
-    cig.resize(ops);
-    par([&](uint32_t lo, uint32_t hi) {
-      for (uint32_t g = lo; g < hi; ++g) {
-        const tbh::RecView v = rec(g);
-        uint32_t* o = cig.data() + cig_off[b + g];
-        for (uint32_t c = 0; c < v.n_cigar(); ++c) o[c] = v.cigar(c);
-      }
-    });
+  if (fresh) {
+    *wyc = (double)(float)gyc, *wyx = gyx;
+    return;
   }
-};
+  thread_local std::vector<uint8_t> o;
+  thread_local tbh::BamRec rr;
+  o.clear();
+  tbh::append_tagged(v, gyc, gyx, gyd, o, rr);
+  tbh::RecView w;
+  w.p = o.data() + 4;
+  w.len = (uint32_t)(o.size() - 4);
+  *wyc = 1.0, *wyx = 1;  // (tiecov.cpp:482-485 defaults)
+  if (const uint8_t* t = tbh::aux_get(w.aux_begin(), w.aux_end(), "YC")) *wyc = tbh::aux2f(t);
+  if (const uint8_t* t = tbh::aux_get(w.aux_begin(), w.aux_end(), "YX")) *wyx = tbh::aux2i(t);
+}
 
 // The inputs as the routes see them.
 struct Inputs {
@@ -516,7 +462,7 @@ class Output {
   double ms_dev_write = 0;              // the device writer's time, its bytes of tagged records and of BGZF members
   uint64_t dev_payload = 0, dev_z = 0;
 
-  Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env, TrackRecs* tracks, tbh::BaiIndex* bai = nullptr)
+  Output(const char* fname, sam_hdr_t* hdr, Device& dev, const Env& env, tbh::CovRecs* tracks, tbh::BaiIndex* bai = nullptr)
       : file_(new GSamWriter(fname, hdr, GSamFile_BAM)), dev_(dev), env_(env), tracks_(tracks), bai_(bai), bai_path_(std::string(fname) + (bai && bai->csi() ? ".csi" : ".bai")) {}
   // (the end of the file: the EOF member; the index goes out once that is on disk)
   void close() {
@@ -594,7 +540,7 @@ class Output {
   std::unique_ptr<GSamWriter> file_;
   Device& dev_;
   const Env& env_;
-  TrackRecs* tracks_;
+  tbh::CovRecs* tracks_;
   tbh::BaiIndex* bai_;  // --index / --csi: the parts of everything that goes into the file, in file order
   std::string bai_path_;
 
@@ -608,151 +554,22 @@ class Output {
       if (frc != 0) GError("Error: fetching the collapse's results failed: %s (%s)\n", dev_.api.strerror_(frc), dev_.api.last_error(c));
       ycp = yc.data(), yxp = yx.data(), ydp = yd.data();
     }
-    tracks_->add(ng, rec, ycp, yxp, ydp, env_.threads);
+    auto values = [&](uint32_t g, const tbh::RecView& v, double* wyc, int64_t* wyx) { written_values(v, ycp[g], yxp[g], ydp[g], wyc, wyx); };
+    if (!tracks_->append(ng, rec, values, ng < 16384 ? 1 : env_.threads)) GError("Error: the output is too large for one coverage tile (--cov / --junc / --samp)\n");
     if (env_.timing) fprintf(stderr, "tracks: %u records added in %.1f ms\n", ng, tms(a, tnow()));
     return true;
   }
 };
 
-static int fwrite_sink(void* user, const char* p, uint64_t n) { return fwrite(p, 1, n, (FILE*)user) == n ? 0 : 1; }
-
-// The tracks of the whole output, as tiecov_main.cpp computes them from its decode of the file: coverage and junctions in one
-// tbk_coverage_tile, the sample counts in tbk_sample_tile, the text by tbk_format_track (the host formatter when the device
-// formatter refuses a value, or with TBK_TRACK_HOST_FMT).
-// With a summary job the coverage and junction rows are computed whatever tracks are open, and summarised.
-static void write_tracks(Device& dev, const Env& env, tbh::TrackFiles& tf, TrackRecs& T, const std::vector<std::string>& names, int num_samples, bool bw_device,
-                         const tbh::SummaryJob& sj) {
-  TbkApi& api = dev.api;
-  tbk_ctx* ctx = dev.ctx;
-  auto t0 = tnow();
-  const size_t n = T.tid.size(), co = T.cig.size();
-  tbk_cov_in in;
-  memset(&in, 0, sizeof(in));
-  in.mem = TBK_MEM_HOST;
-  in.n_records = (uint32_t)n;
-  in.n_cigar_ops = (uint32_t)co;
-  in.tid = T.tid.data(), in.pos = T.pos.data(), in.flag = T.flag.data(), in.cig_off = T.cig_off.data(), in.cig = T.cig.data();
-  in.yc = T.yc.data(), in.strand = T.strand.data(), in.yx = T.yx.data();
-  if (!env.track_host_fmt) {
-    std::vector<uint64_t> off(names.size() + 1, 0);
-    std::string blob;
-    for (size_t t = 0; t < names.size(); ++t) blob += names[t], off[t + 1] = blob.size();
-    const int rc = api.track_names(ctx, (uint32_t)names.size(), off.data(), blob.data());
-    if (rc != 0) GError("Error: GPU track names failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-  }
-  double ms_text = 0;
-  int host_tracks = 0;
-  // the text of one track: the device formatter, or false (then the caller's host formatter)
-  auto device_text = [&](FILE* f, tbk_track_rows r) {
-    if (env.track_host_fmt) return ++host_tracks, false;
-    const int rc = api.format_track(ctx, &r, fwrite_sink, f, nullptr);
-    if (rc == TBK_EUNSUPPORTED) return ++host_tracks, false;
-    if (rc == TBK_EINVAL && std::string(api.last_error(ctx)).find("sink") != std::string::npos) GError("Error: failed to write an output line\n");
-    if (rc != 0) GError("Error: GPU track text failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-    return true;
-  };
-  auto rows = [](int kind, uint32_t nr, const int32_t* tid, const int32_t* st, const int32_t* en) {
-    tbk_track_rows r;
-    memset(&r, 0, sizeof(r));
-    r.mem = TBK_MEM_HOST, r.kind = kind, r.n = nr, r.tid = tid, r.start = st, r.end = en, r.first_junc = 1;
-    return r;
-  };
-  double ms_cov = 0, ms_samp = 0;
-  // --tabix: a track's writer is open in the place of its FILE* (tabix.h)
-  const bool cov_tx = tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
-  tbh::TabixDevice txd;
-  txd.ctx = ctx, txd.track_bgzf = api.track_bgzf, txd.track_names = api.track_names, txd.strerror_ = api.strerror_, txd.last_error = api.last_error;
-  txd.names_set = !env.track_host_fmt;
-  if ((cov_tx || junc_tx || samp_tx) && !env.track_host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
-  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx || sj.on()) {
-    size_t ci = (tf.cov || tf.cov_bw || cov_tx || sj.on()) ? 2 * co + 2 * n + 16 : 0, cj = (tf.junc || junc_tx || sj.on()) ? co + 16 : 0;
-    std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
-    std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
-    std::vector<uint8_t> jstr(cj ? cj : 1);
-    tbk_cov_out o;
-    memset(&o, 0, sizeof(o));
-    o.mem = TBK_MEM_HOST;
-    o.cap_intervals = (uint32_t)ci;
-    o.iv_tid = it.data(), o.iv_start = is.data(), o.iv_end = ie.data(), o.iv_val = iv.data();
-    o.cap_junctions = (uint32_t)cj;
-    o.j_tid = jt.data(), o.j_start = js.data(), o.j_end = je.data(), o.j_strand = jstr.data(), o.j_val = jv.data();
-    auto a = tnow();
-    const int rc = api.coverage_tile(ctx, &in, &o);
-    ms_cov = tms(a, tnow());
-    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
-    if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-    if (sj.on()) {
-      tbh::SummaryDevice sd;
-      sd.ctx = ctx, sd.summary = api.cov_summary, sd.strerror_ = api.strerror_, sd.last_error = api.last_error;
-      tbh::write_summary(sj, names, o, sd);
-    }
-    if (tf.cov) {
-      tbk_track_rows r = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
-      r.val = iv.data();
-      auto a = tnow();
-      if (!device_text(tf.cov, r)) tbh::emit_cov_lines(tf.cov, names, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
-      ms_text += tms(a, tnow());
-    }
-    if (tf.cov_bw) {
-      if (bw_device && !api.bigwig_build) GError("Error: --bigwig-writer device: libtbk.so lacks tbk_bigwig_build\n");
-      tbh::BigWigDevice bd;
-      bd.ctx = ctx, bd.build = api.bigwig_build, bd.strerror_ = api.strerror_, bd.last_error = api.last_error;
-      tf.write_bigwig(o.n_intervals, it.data(), is.data(), ie.data(), iv.data(), bw_device ? &bd : nullptr);
-    }
-    if (tf.junc) {
-      tbk_track_rows r = rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
-      r.val = jv.data(), r.strand = jstr.data();
-      auto a = tnow();
-      if (!device_text(tf.junc, r)) tbh::emit_junc_lines(tf.junc, names, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
-      ms_text += tms(a, tnow());
-    }
-    if (cov_tx) {
-      tbk_track_rows r = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
-      r.val = iv.data();
-      auto a = tnow();
-      tbh::write_tabix_track(tf.cov_tx, r, names, &txd);
-      ms_text += tms(a, tnow());
-    }
-    if (junc_tx) {
-      tbk_track_rows r = rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
-      r.val = jv.data(), r.strand = jstr.data();
-      auto a = tnow();
-      tbh::write_tabix_track(tf.junc_tx, r, names, &txd);
-      ms_text += tms(a, tnow());
-    }
-  }
-  if (tf.samp || samp_tx) {  // (sized and retried as tiecov_main.cpp does)
-    size_t cs = 2 * co + 2 * n + 16;
-    std::vector<int32_t> st, ss, se;
-    std::vector<int64_t> sc;
-    std::vector<float> sh;
-    tbk_sample_out so;
-    int rc = 0;
-    auto a = tnow();
-    for (int attempt = 0; attempt < 2; ++attempt) {
-      st.resize(cs), ss.resize(cs), se.resize(cs), sc.resize(cs), sh.resize(cs);
-      memset(&so, 0, sizeof(so));
-      so.mem = TBK_MEM_HOST;
-      so.cap_intervals = (uint32_t)cs;
-      so.iv_tid = st.data(), so.iv_start = ss.data(), so.iv_end = se.data(), so.iv_count = sc.data(), so.iv_heat = sh.data();
-      rc = api.sample_tile(ctx, &in, num_samples, &so);
-      if (rc != TBK_E2BIG) break;
-      cs = (size_t)so.n_intervals + 16;
-    }
-    ms_samp = tms(a, tnow());
-    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
-    if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
-    tbk_track_rows r = rows(TBK_TRACK_SAMPLE, so.n_intervals, st.data(), ss.data(), se.data());
-    r.count = sc.data(), r.heat = sh.data();
-    auto b = tnow();
-    if (samp_tx) tbh::write_tabix_track(tf.samp_tx, r, names, &txd);
-    else if (!device_text(tf.samp, r)) tbh::emit_samp_lines(tf.samp, names, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());
-    ms_text += tms(b, tnow());
-  }
-  tf.close();
-  if (env.timing)
-    fprintf(stderr, "tracks ms: %zu records | coverage call %.1f | sample call %.1f | text + write %.1f (%d of the tracks by the host formatter) | total %.1f\n", n, ms_cov,
-            ms_samp, ms_text, host_tracks, tms(t0, tnow()));
+// the device entry points for tbh::run_tracks (tiebrush cuts the records of a region run, not the rows: no clip entries)
+static tbh::TrackApi track_api(const Device& dev) {
+  const TbkApi& d = dev.api;
+  tbh::TrackApi a;
+  a.ctx = dev.ctx;
+  a.coverage_tile = d.coverage_tile, a.sample_tile = d.sample_tile;
+  a.track_names = d.track_names, a.format_track = d.format_track, a.track_bgzf = d.track_bgzf, a.bigwig_build = d.bigwig_build, a.cov_summary = d.cov_summary;
+  a.strerror_ = d.strerror_, a.last_error = d.last_error;
+  return a;
 }
 
 // What the summary lines count.
@@ -1593,7 +1410,7 @@ int main(int argc, char* argv[]) {
   auto t_ctx = tnow();
   Totals tot;
   // the tracks: the output header's sample lines (load_sample_info, commons.h:47-71) are checked before any work, the files opened
-  std::unique_ptr<TrackRecs> trecs;
+  std::unique_ptr<tbh::CovRecs> trecs;
   tbh::TrackFiles tfiles;
   int num_samples = 0;
   if (tracks) {
@@ -1602,9 +1419,11 @@ int main(int argc, char* argv[]) {
       num_samples = (int)h->co_samples().size();
       if (num_samples == 0) GError("Error: no sample lines found in header");
     }
-    tfiles.open(cov_prefix, junc_prefix, samp_prefix, bigwig, h->target_name, h->target_len, tabix);
+    tbh::TrackOptions topt;
+    topt.cov = cov_prefix, topt.junc = junc_prefix, topt.samp = samp_prefix, topt.bigwig = bigwig, topt.bw_device = bw_device, topt.tabix = tabix;
+    tfiles.open(topt, h->target_name, h->target_len);
   }
-  if (tracks || summary) trecs.reset(new TrackRecs());
+  if (tracks || summary) trecs.reset(new tbh::CovRecs());
   // the index: a reference a BAI cannot address is refused before the output is created; an older index of the same name goes now
   tbh::BaiIndex bai;
   if (want_index) {
@@ -1630,7 +1449,16 @@ int main(int argc, char* argv[]) {
   out.close();
   if (trecs) {
     dev.wait();
-    write_tracks(dev, env, tfiles, *trecs, inRecords.header()->target_name, num_samples, bw_device, sjob);
+    // the tracks of the whole output, as tiecov computes them from its decode of the file; the text by tbk_format_track (the host
+    // formatter when the device formatter refuses a value, or with TBK_TRACK_HOST_FMT)
+    const auto t0 = tnow();
+    tbh::TrackTimes tt;
+    tbh::TrackRun run;
+    run.num_samples = num_samples, run.bw_device = bw_device, run.summary = &sjob, run.device_text = !env.track_host_fmt, run.times = &tt;
+    tbh::run_tracks(track_api(dev), trecs->as_cov_in(), inRecords.header()->target_name, tfiles, run);
+    if (env.timing)
+      fprintf(stderr, "tracks ms: %zu records | coverage call %.1f | sample call %.1f | text + write %.1f (%d of the tracks by the host formatter) | total %.1f\n",
+              trecs->tid.size(), tt.ms_cov, tt.ms_samp, tt.ms_text, tt.host_tracks, tms(t0, tnow()));
   }
   auto t_closed = tnow();
   if (env.timing) fprintf(stderr, "writer closed at %.1f ms\n", tms(dev.t_start, t_closed));

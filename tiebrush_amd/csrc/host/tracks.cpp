@@ -33,9 +33,10 @@ static void open_tabix(TabixWriter& w, std::string prefix, const char* ext, cons
   if (!w.open(prefix, names, lens, head, err)) GError("Error creating file %s (%s)\n", prefix.c_str(), err.c_str());
 }
 
-void TrackFiles::open(std::string cov_prefix, std::string junc_prefix, std::string samp_prefix, bool bigwig, const std::vector<std::string>& names,
-                      const std::vector<uint32_t>& lens, bool tabix) {
-  if (tabix) {  // every text track; the coverage as a bigWig stays what it is below
+void TrackFiles::open(const TrackOptions& o, const std::vector<std::string>& names, const std::vector<uint32_t>& lens) {
+  std::string cov_prefix = o.cov, junc_prefix = o.junc, samp_prefix = o.samp;
+  const bool bigwig = o.bigwig;
+  if (o.tabix) {  // every text track; the coverage as a bigWig stays what it is below
     if (!cov_prefix.empty() && !bigwig && cov_prefix != "-" && cov_prefix != "stdout") open_tabix(cov_tx, cov_prefix, ".bedgraph", kCovHead, names, lens), cov_name = cov_tx.path(), cov_prefix.clear();
     if (!junc_prefix.empty()) open_tabix(junc_tx, junc_prefix, ".bed", kJuncHead, names, lens), junc_prefix.clear();
     if (!samp_prefix.empty()) open_tabix(samp_tx, samp_prefix, ".bedgraph", kSampHead, names, lens), samp_prefix.clear();
@@ -122,7 +123,7 @@ struct BwBridge {
 };
 }  // namespace
 
-void TrackFiles::write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const BigWigDevice* dev) {
+void TrackFiles::write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev) {
   if (!cov_bw) return;
   const auto t0 = std::chrono::steady_clock::now();
   for (uint32_t i = 0; i < n; ++i) bw.add((uint32_t)tid[i], (uint32_t)start[i], (uint32_t)end[i], (float)val[i]);
@@ -140,7 +141,7 @@ void TrackFiles::write_bigwig(uint32_t n, const int32_t* tid, const int32_t* sta
     done = bw.close_with(
         [&](BigWigFeed& feed) {
           BwBridge b{&feed, &out};
-          rc = dev->build(dev->ctx, &r, (uint32_t)bw_lens.size(), bw_lens.data(), BwBridge::sink, &b, &out);
+          rc = dev->bigwig_build(dev->ctx, &r, (uint32_t)bw_lens.size(), bw_lens.data(), BwBridge::sink, &b, &out);
           if (rc == 0 && !b.advance(out.n_levels - 1)) b.failed = true;  // (levels without a byte: an empty data level)
           write_failed = b.failed;
           return rc == 0 && !b.failed;
@@ -276,7 +277,7 @@ void SummaryJob::setup(const char* features_opt, const char* summary_opt, const 
   if (U && !features_inside(F, *U, bed, err)) GError("Error: --features: %s\n", err.c_str());
 }
 
-void write_summary(const SummaryJob& job, const std::vector<std::string>& names, const tbk_cov_out& rows, const SummaryDevice& dev) {
+void write_summary(const SummaryJob& job, const std::vector<std::string>& names, const tbk_cov_out& rows, const TrackApi& api) {
   const auto t0 = std::chrono::steady_clock::now();
   const FeatureTable& F = job.F;
   const bool host = getenv("TBK_SUMMARY_HOST") && strcmp(getenv("TBK_SUMMARY_HOST"), "0") != 0;
@@ -285,20 +286,188 @@ void write_summary(const SummaryJob& job, const std::vector<std::string>& names,
     summarise_features(F, true, rows.n_intervals, rows.iv_tid, rows.iv_start, rows.iv_end, rows.iv_val, true, rows.n_junctions, rows.j_tid, rows.j_start,
                        rows.j_end, rows.j_strand, rows.j_val, S);
   } else {
-    if (!dev.summary) GError("Error: --summary: the loaded libtbk.so has no tbk_cov_summary (an older build?)\n");
+    if (!api.cov_summary) GError("Error: --summary: the loaded libtbk.so has no tbk_cov_summary (an older build?)\n");
     S.resize(F.n());
     tbk_features f;
     f.n = (uint32_t)F.n(), f.tid = F.tid.data(), f.beg = F.beg.data(), f.end = F.end.data(), f.strand = F.strand.data();
     tbk_feat_out o;
     o.mem = TBK_MEM_HOST, o.covered = S.covered.data(), o.sum = S.sum.data(), o.max = S.max.data(), o.junc = S.junc.data();
-    const int rc = dev.summary(dev.ctx, &rows, &f, &o);
-    if (rc != 0) GError("Error: GPU feature summary failed: %s (%s)\n", dev.strerror_(rc), dev.last_error(dev.ctx));
+    const int rc = api.cov_summary(api.ctx, &rows, &f, &o);
+    if (rc != 0) GError("Error: GPU feature summary failed: %s (%s)\n", api.strerror_(rc), api.last_error(api.ctx));
   }
   std::string err;
   if (!write_summary_tsv(job.out, names, F, S, err)) GError("Error: --summary: %s\n", err.c_str());
   if (getenv("TBK_TIMING"))
     fprintf(stderr, "summary phase ms: %s | %zu features | %u interval rows | %u junction rows | %.1f\n", host ? "host" : "device", F.n(), rows.n_intervals,
             rows.n_junctions, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+}
+
+tbk_cov_in CovRecs::as_cov_in() const {
+  tbk_cov_in in;
+  memset(&in, 0, sizeof(in));
+  in.mem = TBK_MEM_HOST;
+  in.n_records = (uint32_t)tid.size();
+  in.n_cigar_ops = (uint32_t)cig.size();
+  in.tid = tid.data(), in.pos = pos.data(), in.flag = flag.data(), in.cig_off = cig_off.data(), in.cig = cig.data();
+  in.yc = yc.data(), in.strand = strand.data(), in.yx = yx.data();
+  return in;
+}
+
+bool CovRecs::append(uint32_t ng, const std::function<RecView(uint32_t)>& rec, const std::function<void(uint32_t, const RecView&, double*, int64_t*)>& values,
+                     int threads) {
+  const size_t b = tid.size();
+  tid.resize(b + ng), pos.resize(b + ng), flag.resize(b + ng), yc.resize(b + ng), yx.resize(b + ng), strand.resize(b + ng);
+  cig_off.resize(b + ng + 1);
+  const int T = std::max(1, threads);
+  auto par = [&](const std::function<void(uint32_t, uint32_t)>& f) {
+    std::vector<std::thread> th;
+    for (int t = 1; t < T; ++t) th.emplace_back(f, (uint32_t)((uint64_t)ng * t / T), (uint32_t)((uint64_t)ng * (t + 1) / T));
+    f(0, (uint32_t)((uint64_t)ng / T));
+    for (auto& x : th) x.join();
+  };
+  par([&](uint32_t lo, uint32_t hi) {
+    for (uint32_t g = lo; g < hi; ++g) {
+      const RecView v = rec(g);
+      const size_t i = b + g;
+      tid[i] = v.tid(), pos[i] = v.pos(), flag[i] = v.flag();
+      cig_off[i + 1] = v.n_cigar();
+      values(g, v, &yc[i], &yx[i]);
+      strand[i] = (uint8_t)splice_strand(v);
+    }
+  });
+  uint64_t ops = cig_off[b];
+  for (size_t i = b; i < b + ng; ++i) {
+    ops += cig_off[i + 1];
+    if (ops >= (1ull << 32)) return false;
+    cig_off[i + 1] = (uint32_t)ops;
+  }
+  cig.resize(ops);
+  par([&](uint32_t lo, uint32_t hi) {
+    for (uint32_t g = lo; g < hi; ++g) {
+      const RecView v = rec(g);
+      uint32_t* o = cig.data() + cig_off[b + g];
+      for (uint32_t c = 0; c < v.n_cigar(); ++c) o[c] = v.cigar(c);
+    }
+  });
+  return true;
+}
+
+static int fwrite_sink(void* user, const char* p, uint64_t n) { return fwrite(p, 1, n, (FILE*)user) == n ? 0 : 1; }
+
+void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run) {
+  using clock = std::chrono::steady_clock;
+  auto ms_since = [](clock::time_point a) { return std::chrono::duration<double, std::milli>(clock::now() - a).count(); };
+  tbk_ctx* ctx = api.ctx;
+  const size_t n = in.n_records, co = in.n_cigar_ops;
+  const TrackClip* clip = run.clip;
+  const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
+  const bool summary = run.summary && run.summary->on();
+  // --tabix: a track's writer is open in the place of its FILE* (tabix.h)
+  const bool cov_tx = tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
+  const bool host_fmt = getenv("TBK_TRACK_HOST_FMT") != nullptr;
+  if ((cov_tx || junc_tx || samp_tx) && !host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
+  bool names_set = false;  // the reference names are on the context
+  if (run.device_text) set_track_names(api, names), names_set = true;
+  TrackTimes times;
+  // the text of one plain track: the device formatter, or false (then the caller's host formatter)
+  auto device_text = [&](FILE* f, const tbk_track_rows& r) {
+    if (!run.device_text) return ++times.host_tracks, false;
+    const int rc = api.format_track(ctx, &r, fwrite_sink, f, nullptr);
+    if (rc == TBK_EUNSUPPORTED) return ++times.host_tracks, false;
+    if (rc == TBK_EINVAL && std::string(api.last_error(ctx)).find("sink") != std::string::npos) GErrorWrite();
+    if (rc != 0) GError("Error: GPU track text failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    return true;
+  };
+  auto rows = [](int kind, uint32_t nr, const int32_t* t, const int32_t* s, const int32_t* e) {
+    tbk_track_rows r;
+    memset(&r, 0, sizeof(r));
+    r.mem = TBK_MEM_HOST, r.kind = kind, r.n = nr, r.tid = t, r.start = s, r.end = e, r.first_junc = 1;
+    return r;
+  };
+  int rc = 0;
+  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx || summary) {
+    const size_t ci = (tf.cov || tf.cov_bw || cov_tx || summary) ? 2 * co + 2 * n + 16 + extra : 0, cj = (tf.junc || junc_tx || summary) ? co + 16 : 0;
+    std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
+    std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
+    std::vector<uint8_t> jstr(cj ? cj : 1);
+    tbk_cov_out o;
+    memset(&o, 0, sizeof(o));
+    o.mem = TBK_MEM_HOST;
+    o.cap_intervals = (uint32_t)ci;
+    o.iv_tid = it.data(), o.iv_start = is.data(), o.iv_end = ie.data(), o.iv_val = iv.data();
+    o.cap_junctions = (uint32_t)cj;
+    o.j_tid = jt.data(), o.j_start = js.data(), o.j_end = je.data(), o.j_strand = jstr.data(), o.j_val = jv.data();
+    auto a = clock::now();
+    rc = api.coverage_tile(ctx, &in, &o);
+    times.ms_cov = ms_since(a);
+    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+    if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    if (summary) write_summary(*run.summary, names, o, api);
+    if (clip) {
+      const tbk_regions* U = clip->U;
+      rc = clip->one ? api.cov_clip(ctx, &o, U->tid[0], U->beg[0], U->end[0]) : api.cov_clip_regions(ctx, &o, U);
+      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    }
+    tbk_track_rows rcov = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
+    rcov.val = iv.data();
+    tbk_track_rows rjunc = rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
+    rjunc.val = jv.data(), rjunc.strand = jstr.data();
+    if (tf.cov) {  // flushCoverage, tiecov.cpp:237
+      a = clock::now();
+      if (!device_text(tf.cov, rcov)) emit_cov_lines(tf.cov, names, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
+      times.ms_text += ms_since(a);
+    }
+    if (tf.cov_bw) {  // flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the same intervals, the value as a float
+      if (run.bw_device && !api.bigwig_build) GError("Error: --bigwig-writer device: libtbk.so lacks tbk_bigwig_build\n");
+      tf.write_bigwig(o.n_intervals, it.data(), is.data(), ie.data(), iv.data(), run.bw_device ? &api : nullptr);
+    }
+    if (tf.junc) {  // CJunc::write, tiecov.cpp:91-95 (numbered from 1)
+      a = clock::now();
+      if (!device_text(tf.junc, rjunc)) emit_junc_lines(tf.junc, names, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
+      times.ms_text += ms_since(a);
+    }
+    a = clock::now();
+    if (cov_tx) write_tabix_track(tf.cov_tx, rcov, names, api, &names_set);
+    if (junc_tx) write_tabix_track(tf.junc_tx, rjunc, names, api, &names_set);
+    times.ms_text += ms_since(a);
+  }
+  if (tf.samp || samp_tx) {
+    // the value of the track changes only where an M segment starts or ends: at most 2 intervals per CIGAR operation + 2 per
+    // record, as for the coverage track (not one per covered base); if a call still reports TBK_E2BIG it also reports the
+    // count it needs, and the call is repeated with that
+    size_t cs = 2 * co + 2 * n + 16 + extra;
+    std::vector<int32_t> st, ss, se;
+    std::vector<int64_t> sc;
+    std::vector<float> sh;
+    tbk_sample_out so;
+    auto a = clock::now();
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      st.resize(cs), ss.resize(cs), se.resize(cs), sc.resize(cs), sh.resize(cs);
+      memset(&so, 0, sizeof(so));
+      so.mem = TBK_MEM_HOST;
+      so.cap_intervals = (uint32_t)cs;
+      so.iv_tid = st.data(), so.iv_start = ss.data(), so.iv_end = se.data(), so.iv_count = sc.data(), so.iv_heat = sh.data();
+      rc = api.sample_tile(ctx, &in, run.num_samples, &so);
+      if (rc != TBK_E2BIG) break;
+      cs = (size_t)so.n_intervals + 16 + extra;
+    }
+    times.ms_samp = ms_since(a);
+    if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+    if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    if (clip) {
+      const tbk_regions* U = clip->U;
+      rc = clip->one ? api.sample_clip(ctx, &so, U->tid[0], U->beg[0], U->end[0]) : api.sample_clip_regions(ctx, &so, U);
+      if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    }
+    tbk_track_rows r = rows(TBK_TRACK_SAMPLE, so.n_intervals, st.data(), ss.data(), se.data());
+    r.count = sc.data(), r.heat = sh.data();
+    a = clock::now();
+    if (samp_tx) write_tabix_track(tf.samp_tx, r, names, api, &names_set);
+    else if (!device_text(tf.samp, r)) emit_samp_lines(tf.samp, names, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
+    times.ms_text += ms_since(a);
+  }
+  tf.close();
+  if (run.times) *run.times = times;
 }
 
 }  // namespace tbh

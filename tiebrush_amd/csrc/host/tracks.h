@@ -1,11 +1,13 @@
 // tracks.h — tiecov's three track files, shared by the tiecov command line and by `tiebrush --cov / --junc / --samp`: file names and
 // header lines (tiecov.cpp:365-402 and the openings around them), and the host formatter of the lines (flushCoverage :237,
 // CJunc::write :91-95, flushCoverage(pair) :289).  The host formatter is what tiecov prints with, the reference the device formatter
-// (tbk_format_track) is tested against, and the command line's fallback when the device formatter refuses a track.
+// (tbk_format_track) is tested against, and the command line's fallback when the device formatter refuses a track.  And what both do
+// with their records: the record table (CovRecs) and the one run from it to the closed files (run_tracks).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -18,21 +20,38 @@
 
 namespace tbh {
 
-// The open track files.  An empty prefix: that track is not written.  Coverage goes to stdout for "-" / "stdout", to PREFIX.bigwig
-// with `bigwig`, else to PREFIX.bedgraph; junctions to PREFIX.bed; the sample counts to PREFIX.bedgraph.  Errors are fatal (GError).
-// With `tabix` every text track is PREFIX.bedgraph.gz / PREFIX.bed.gz (BGZF) with its tabix index beside it (tabix.h): the track's
-// TabixWriter is open in the place of its FILE*, and takes the header line with its first rows.
-// The device section producer of the bigWig (--bigwig-writer device) as a command line has it: tiecov links libtbk.so, tiebrush binds it
-// at run time, so the entry points travel as pointers.
-struct BigWigDevice {
+// The device entry points of a track run, as a command line has them: tracks.cpp and tabix.cpp are linked without libtbk.so (tbh_tool,
+// libtbh.so), tiecov links the library and tiebrush binds it at run time, so the calls travel as pointers.  An entry the library in use
+// lacks is null (tiebrush: track_bgzf, bigwig_build, cov_summary may be; it never clips, and leaves the four clip entries null).
+struct TrackApi {
   tbk_ctx* ctx = nullptr;
-  decltype(&tbk_bigwig_build) build = nullptr;
+  decltype(&tbk_coverage_tile) coverage_tile = nullptr;
+  decltype(&tbk_sample_tile) sample_tile = nullptr;
+  decltype(&tbk_cov_clip) cov_clip = nullptr;
+  decltype(&tbk_cov_clip_regions) cov_clip_regions = nullptr;
+  decltype(&tbk_sample_clip) sample_clip = nullptr;
+  decltype(&tbk_sample_clip_regions) sample_clip_regions = nullptr;
+  decltype(&tbk_track_names) track_names = nullptr;
+  decltype(&tbk_format_track) format_track = nullptr;
+  decltype(&tbk_track_bgzf) track_bgzf = nullptr;
+  decltype(&tbk_bigwig_build) bigwig_build = nullptr;
+  decltype(&tbk_cov_summary) cov_summary = nullptr;
   decltype(&tbk_strerror) strerror_ = nullptr;
   decltype(&tbk_last_error) last_error = nullptr;
+};
+
+// The track options of a command line (tiecov -c / -j / -s / -W / --bigwig-writer / --tabix and tiebrush's long spellings of them; each
+// main checks their rules in its own words).  An empty prefix: that track is not written.
+struct TrackOptions {
+  std::string cov, junc, samp;
+  bool bigwig = false, bw_device = false, tabix = false;
 };
 // "host" / "device" -> false / true; anything else is fatal (GError)
 bool parse_bigwig_writer(const char* value);
 
+// The open track files.  Coverage goes to stdout for "-" / "stdout", to PREFIX.bigwig with `bigwig`, else to PREFIX.bedgraph; junctions to PREFIX.bed; the sample counts to PREFIX.bedgraph.  Errors are fatal (GError).
+// With `tabix` every text track is PREFIX.bedgraph.gz / PREFIX.bed.gz (BGZF) with its tabix index beside it (tabix.h): the track's
+// TabixWriter is open in the place of its FILE*, and takes the header line with its first rows.
 struct TrackFiles {
   FILE *cov = nullptr, *junc = nullptr, *samp = nullptr;
   BigWigWriter bw;
@@ -40,13 +59,12 @@ struct TrackFiles {
   std::vector<uint32_t> bw_lens;  // the chromosome lengths the bigWig was opened with
   std::string cov_name;
   TabixWriter cov_tx, junc_tx, samp_tx;  // --tabix
-  void open(std::string cov_prefix, std::string junc_prefix, std::string samp_prefix, bool bigwig, const std::vector<std::string>& names,
-            const std::vector<uint32_t>& lens, bool tabix = false);
+  void open(const TrackOptions& o, const std::vector<std::string>& names, const std::vector<uint32_t>& lens);
   void close_bigwig();  // (after every interval went to bw)
   // The coverage rows into the bigWig and the file closed (flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the value as a float).
-  // dev == nullptr: the host producer.  Else the sections are tbk_bigwig_build's; a refusal of that call other than a failed write
+  // dev == nullptr: the host producer.  Else the sections are dev->bigwig_build's; a refusal of that call other than a failed write
   // hands the file to the host producer (a line on stderr says so).  TBK_TIMING: a "bigwig phase" line on stderr for either.
-  void write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const BigWigDevice* dev);
+  void write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev);
   void close();
 };
 
@@ -87,13 +105,6 @@ void summarise_features(const FeatureTable& F, bool want_cov, uint32_t ni, const
 // nothing is covered), in double.  false: the file cannot be created or written
 bool write_summary_tsv(const std::string& path, const std::vector<std::string>& names, const FeatureTable& F, const FeatSummary& S, std::string& err);
 
-// The device summariser as a command line has it (see BigWigDevice).  summary == nullptr: the library in use has no tbk_cov_summary.
-struct SummaryDevice {
-  tbk_ctx* ctx = nullptr;
-  decltype(&tbk_cov_summary) summary = nullptr;
-  decltype(&tbk_strerror) strerror_ = nullptr;
-  decltype(&tbk_last_error) last_error = nullptr;
-};
 // `--features BED --summary OUT` of a run: parsed (and refused) before any output file exists, written by write_summary
 struct SummaryJob {
   std::string bed, out;
@@ -103,9 +114,53 @@ struct SummaryJob {
   // wholly inside one interval).  Errors are fatal (GError) and name the line.
   void setup(const char* features_opt, const char* summary_opt, const BamHeader& hdr, const RegionTable* U);
 };
-// The summary of HOST rows (what tbk_coverage_tile wrote, before any clip) into job.out: tbk_cov_summary through dev, or the host
-// summariser with TBK_SUMMARY_HOST=1.  Errors are fatal; a missing tbk_cov_summary is one.  TBK_TIMING: a "summary phase ms" line.
-void write_summary(const SummaryJob& job, const std::vector<std::string>& names, const tbk_cov_out& rows, const SummaryDevice& dev);
+// The summary of HOST rows (what tbk_coverage_tile wrote, before any clip) into job.out: api.cov_summary, or the host summariser with
+// TBK_SUMMARY_HOST=1.  Errors are fatal; a missing tbk_cov_summary is one.  TBK_TIMING: a "summary phase ms" line.
+void write_summary(const SummaryJob& job, const std::vector<std::string>& names, const tbk_cov_out& rows, const TrackApi& api);
+
+// ---- what every run does with its records: the tracks -----------------------------------------------------------------------------
+// The records of a run as tbk_coverage_tile / tbk_sample_tile read them (host arrays): tiecov's decode of its input, tiebrush's groups
+// as they go into the output.
+struct CovRecs {
+  std::vector<int32_t> tid, pos;
+  std::vector<uint16_t> flag;
+  std::vector<uint32_t> cig_off{0}, cig;
+  std::vector<double> yc;
+  std::vector<int64_t> yx;
+  std::vector<uint8_t> strand;
+  tbk_cov_in as_cov_in() const;
+  // ng further records, rec(g) in file order: tid, pos, flag and the splice strand (bam.h) on `threads` workers, the CIGAR offsets by
+  // one serial pass over the counts, then the operations on the workers again.  values(g, view, &yc, &yx) gives a record's weights.
+  // false: the CIGAR operations of all records no longer fit 32 bits (the message is the caller's)
+  bool append(uint32_t ng, const std::function<RecView(uint32_t)>& rec, const std::function<void(uint32_t, const RecView&, double*, int64_t*)>& values,
+              int threads);
+};
+
+// the cut of a region run: the table, through the one-region entries (one: the table is the region itself, which may be empty) or the
+// table entries
+struct TrackClip {
+  const tbk_regions* U;
+  bool one;
+};
+// the figures of tiebrush's "tracks ms:" line
+struct TrackTimes {
+  double ms_cov = 0, ms_samp = 0, ms_text = 0;  // the coverage call, the sample call, text + write of every track
+  int host_tracks = 0;                           // plain-text tracks that the host formatter wrote
+};
+struct TrackRun {
+  const TrackClip* clip = nullptr;
+  int num_samples = 0;
+  bool bw_device = false;                // the bigWig's sections by api.bigwig_build
+  const SummaryJob* summary = nullptr;   // (null, or a job that is not on: no summary)
+  bool device_text = false;              // plain text by api.format_track (the names set up front), the host formatter where it refuses a track
+  TrackTimes* times = nullptr;
+};
+// The rows of coverage_tile / sample_tile for `in` (host arrays, or a device view), cut to *run.clip where one is given, into the open
+// files of tf, and the files closed.  An input of no records goes the same way: the calls give no rows and status 0.  With a summary
+// job the coverage and junction rows are computed whatever tracks are open, and summarised before the cut.  The
+// reference names go to the context (track_names) at most once: up front with device_text, else before the first tabix track the
+// device writes.  Errors are fatal (GError).
+void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run);
 
 template <class F>
 void emit_lines(FILE* f, uint32_t n, F fmt) {
