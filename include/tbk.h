@@ -747,6 +747,42 @@ typedef struct tbk_feat_out {
  * by (tid, start, end, strand).  Nothing faults and the context takes the next call. */
 int tbk_cov_summary(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_features* features, tbk_feat_out* out);
 
+/* ---- tiecov over a record stream that arrives in tiles (ABI version 9: entries appended) ----
+ * tiecov flushes its coverage, sample rows and junctions per bundle, so a stream cut at a bundle head gives rows that concatenate to the
+ * rows of the uncut stream.  The context keeps a CARRY in device memory: the records of the bundle that was still open when the last
+ * tile ended.  tbk_cov_stream_push takes the next tile (TBK_MEM_DEVICE; tid, pos, flag, strand, cig_off, cig, and yc_in / yx_in where
+ * they exist), drops its unmapped records (flag 0x4), computes the ends of the others by the coverage path's own rule and finds the LAST
+ * bundle head of carry ++ tile: the first record of a tid run, or a start beyond the running maximum of end over the run (tiecov.cpp:443).
+ *   *view  = carry ++ the tile's mapped records before that head, as tiecov's input; yc / yx as in tbk_region_view (the tag where
+ *            tag_seen — NULL: everywhere — says it is present, 1.0 / 1 where not).  The records from the head on are the new carry.
+ *   No head in the tile (the open bundle goes on): the view is empty and everything is carried; the carry grows over such pushes.
+ *   final != 0: nothing is held back, the carry empties.
+ * info: n_view = view->n_records, n_carry = the records now carried, n_taken = the tile's mapped records that went to the view, cut =
+ * the head's index among the tile's records (tile->n_records with `final`, 0 when the tile brought no head).
+ * The view lives in context-owned device memory, valid until the next tbk_cov_stream_push / tbk_cov_stream_reset on ctx; it survives
+ * tbk_coverage_tile and tbk_sample_tile.  The carry is double-buffered: the new one is written while the old one is read.
+ * TBK_EINVAL for a HOST tile.  TBK_E2BIG when carry + tile exceed 2^32 - 2 records or CIGAR words (or the debug key stream_cap=RECORDS),
+ * TBK_ENOMEM when the device has no room: after either the carry is unchanged (the previous view is not), nothing faults and the context
+ * takes the next call.  tbk_cov_stream_reset empties the carry (a new stream); the buffers stay. */
+/* tbk_bam_decode_spans for ONE span — a batch of whole BGZF members whose record stream starts at first_uoff of the first member's payload —
+ * that may END INSIDE A RECORD: fewer than 4 bytes left, or a block_size that runs past the batch's end, is where the records stop, not
+ * TBK_EINVAL.  *tail_off = the inflated offset, counted from the first member's payload start, of the first byte that no whole record
+ * consumed (the inflated size when the batch ends on a record boundary): the caller's next batch starts there.  A batch that holds no
+ * whole record: an empty tile, status 0, *tail_off == first_uoff.  Both record-index routes (a lane per member; the chain) give the same
+ * records and the same tail.  Everything else is tbk_bam_decode_spans': the tile in context-owned device memory until tbk_bam_release or
+ * the next decode, YC / YX read for every record, *tag_seen_out; TBK_EINVAL for a block_size below 32, a refID outside [-1, n_ref), an
+ * offset outside its member, a corrupt member. */
+int tbk_bam_decode_open(tbk_ctx* ctx, const uint8_t* comp, uint64_t comp_bytes, uint32_t first_uoff, int32_t n_ref, tbk_soa_in* tile,
+                        const uint8_t** tag_seen_out, uint64_t* tail_off);
+
+typedef struct tbk_cov_stream_info {
+  uint32_t n_view, n_carry, n_taken, cut;
+  int32_t first_tid, first_pos; /* the first record (refID, 0-based pos) of the bundle that is open after the call; first_tid = -2: none is.
+                                   After TBK_E2BIG: of the bundle that did not fit (the carry's first record; without a carry, the tile's) */
+} tbk_cov_stream_info;
+int tbk_cov_stream_push(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, int final, tbk_cov_in* view, tbk_cov_stream_info* info);
+int tbk_cov_stream_reset(tbk_ctx* ctx);
+
 #ifdef __cplusplus
 }
 #endif

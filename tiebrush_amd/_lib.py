@@ -29,7 +29,8 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_shard_pack", "tbk_shard_unpack", "tbk_partial_keys", "tbk_partial_pack", "tbk_partial_unpack", "tbk_partial_reduce", "tbk_unpack_tile", "tbk_tile_join", "tbk_reserve_tile", "tbk_bgzf_deflate", "tbk_bam_encode", "tbk_kept_results", "tbk_warmup", "tbk_partial_stage_keys", "tbk_partial_stage_cands", "tbk_partial_stage_pack",
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
            "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route",
-           "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build", "tbk_track_bgzf", "tbk_cov_summary"]
+           "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build", "tbk_track_bgzf", "tbk_cov_summary",
+           "tbk_cov_stream_push", "tbk_cov_stream_reset", "tbk_bam_decode_open"]
 
 
 class CollapseOpts(C.Structure):
@@ -149,6 +150,10 @@ class BwOut(C.Structure):
 BW_SINK = C.CFUNCTYPE(C.c_int, _P, C.c_uint32, _P, C.c_uint64)
 
 
+class CovStreamInfo(C.Structure):
+    _fields_ = [("n_view", C.c_uint32), ("n_carry", C.c_uint32), ("n_taken", C.c_uint32), ("cut", C.c_uint32), ("first_tid", C.c_int32), ("first_pos", C.c_int32)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("ms", C.c_float), ("launches", C.c_uint32)]
 
@@ -266,6 +271,12 @@ def load():
     L.tbk_tile_regions.restype = C.c_int
     L.tbk_cov_summary.argtypes = [_P, C.POINTER(CovOut), C.POINTER(Features), C.POINTER(FeatOut)]
     L.tbk_cov_summary.restype = C.c_int
+    L.tbk_cov_stream_push.argtypes = [_P, C.POINTER(SoaIn), _P, C.c_int, C.POINTER(CovIn), C.POINTER(CovStreamInfo)]
+    L.tbk_cov_stream_push.restype = C.c_int
+    L.tbk_cov_stream_reset.argtypes = [_P]
+    L.tbk_cov_stream_reset.restype = C.c_int
+    L.tbk_bam_decode_open.argtypes = [_P, _P, C.c_uint64, C.c_uint32, C.c_int32, C.POINTER(SoaIn), C.POINTER(_P), C.POINTER(C.c_uint64)]
+    L.tbk_bam_decode_open.restype = C.c_int
     _lib = L
     return L
 

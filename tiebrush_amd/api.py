@@ -504,6 +504,35 @@ class Context:
         u, _keep = _regions(table)
         return self._region_view("tbk_regions_view", tile_struct, tag_seen, (C.byref(u),))
 
+    # ---- a record stream in tiles ----
+    def bam_decode_open(self, comp, first_uoff, n_ref):
+        """tbk_bam_decode_open: bytes of whole BGZF members whose record stream starts at first_uoff of the first member's payload and
+        may end inside a record -> (SoaIn struct of the device-resident tile of the whole records, tag_seen: device pointer or None,
+        tail_off: the inflated offset of the first byte no whole record consumed).  The arrays live in the context until bam_release()
+        or the next decode."""
+        buf = np.frombuffer(comp, dtype=np.uint8)
+        s, seen, tail = _lib.SoaIn(), C.c_void_p(), C.c_uint64(0)
+        self._check(self.L.tbk_bam_decode_open(self.h, buf.ctypes.data if len(buf) else None, len(buf), int(first_uoff), int(n_ref), C.byref(s), C.byref(seen),
+                                               C.byref(tail)), "tbk_bam_decode_open")
+        self._bam_keep = (buf,)
+        return s, seen.value, int(tail.value)
+
+    def cov_stream_push(self, tile_struct, tag_seen, final):
+        """tbk_cov_stream_push: the next tile of a record stream (a SoaIn struct of a device tile: bam_decode_open / bam_decode_spans) -> (DeviceCovView of the carried records and the tile's mapped records before its last bundle head, info
+        dict n_view / n_carry / n_taken / cut).  The records from that head on wait in the context for the next push; final: nothing
+        waits.  The view is valid until the next push or cov_stream_reset()."""
+        v, info = _lib.CovIn(), _lib.CovStreamInfo()
+        self._order_after_torch(True)
+        rc = self.L.tbk_cov_stream_push(self.h, C.byref(tile_struct), tag_seen, int(bool(final)), C.byref(v), C.byref(info))
+        # (tid, pos) of the first record of the bundle that is open after the call — after TBK_E2BIG: of the one that did not fit —, or None
+        self.cov_stream_first = (int(info.first_tid), int(info.first_pos)) if rc in (0, -4) and info.first_tid != -2 else None
+        self._check(rc, "tbk_cov_stream_push")
+        return DeviceCovView(v, int(v.n_records), int(v.n_cigar_ops)), {k: int(getattr(info, k)) for k in ("n_view", "n_carry", "n_taken", "cut")}
+
+    def cov_stream_reset(self):
+        """tbk_cov_stream_reset: forget the carried records (a new stream begins)"""
+        self._check(self.L.tbk_cov_stream_reset(self.h), "tbk_cov_stream_reset")
+
     def bam_decode_file_spans(self, file_spans, n_ref, tbmerged=None, want_md=False, want_names=False):
         """tbk_bam_decode_file_spans: file_spans = per input file the list of its spans [(bytes of whole BGZF members, first_uoff,
         last_uoff)] (a file may have none) -> (SoaIn struct of the device-resident tile, file_off [n_files + 1]).  The arrays live in the

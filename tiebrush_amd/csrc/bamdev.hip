@@ -617,12 +617,14 @@ constexpr uint32_t IDX_CH = 48 * 1024;
 __global__ __launch_bounds__(IDX_NT) void bam_index_k(const uint8_t* __restrict__ inf, const uint64_t* __restrict__ fbase,
                                                       const uint64_t* __restrict__ fbytes, const uint64_t* __restrict__ first,
                                                       const uint64_t* __restrict__ cap_off, uint64_t* __restrict__ rec, uint32_t* __restrict__ cnt,
-                                                      uint32_t* __restrict__ err) {
+                                                      uint32_t* __restrict__ err, uint64_t* __restrict__ tail) {
+  // tail (tbk_bam_decode_open; NULL otherwise): the stream may end inside a record — fewer than 4 bytes left, or a block_size that runs
+  // past the end, is where the walk stops, not an error; tail[f] = the offset in the file of the first byte no whole record consumed
   __shared__ __align__(16) uint8_t buf[IDX_CH + 16];
   __shared__ uint32_t list[IDX_CH / 36 + 2];
   __shared__ uint32_t s_n;
   __shared__ unsigned long long s_next;
-  __shared__ uint32_t s_bad;
+  __shared__ uint32_t s_bad, s_done;
   const uint32_t f = blockIdx.x;
   const uint8_t* base = inf + fbase[f];
   const uint64_t n = fbytes[f];
@@ -644,19 +646,32 @@ __global__ __launch_bounds__(IDX_NT) void bam_index_k(const uint8_t* __restrict_
     __syncthreads();
     if (threadIdx.x == 0) {
       uint32_t q = (uint32_t)(p - c0), m = 0;
-      bool bad = false;
+      bool bad = false, done = false;
       while (q + 4 <= cl) {
         const uint32_t bs = (uint32_t)buf[q] | ((uint32_t)buf[q + 1] << 8) | ((uint32_t)buf[q + 2] << 16) | ((uint32_t)buf[q + 3] << 24);
-        if (bs < 32 || c0 + q + 4 + (uint64_t)bs > n) {
+        if (bs < 32) {
           bad = true;
+          break;
+        }
+        if (c0 + q + 4 + (uint64_t)bs > n) {  // a record that runs past the end
+          if (tail)
+            done = true;
+          else
+            bad = true;
           break;
         }
         list[m++] = q;
         q += 4 + bs;
       }
-      if (!bad && q < cl && c0 + cl == n) bad = true;  // fewer than 4 bytes left at the end of the file: a truncated record
+      if (!bad && !done && q < cl && c0 + cl == n) {  // fewer than 4 bytes left at the end of the file: a truncated record
+        if (tail)
+          done = true;
+        else
+          bad = true;
+      }
       s_n = m;
       s_next = c0 + q;
+      s_done = done ? 1u : 0u;
       if (bad) s_bad = 1;
     }
     __syncthreads();
@@ -664,15 +679,22 @@ __global__ __launch_bounds__(IDX_NT) void bam_index_k(const uint8_t* __restrict_
     for (uint32_t i = threadIdx.x; i < m; i += IDX_NT) out[total + i] = fbase[f] + c0 + list[i];
     total += m;
     const uint64_t np = s_next;
-    const bool bad = s_bad != 0;
+    const bool bad = s_bad != 0, done = s_done != 0;
     __syncthreads();
+    if (done) {  // (an open stream's incomplete last record begins at np)
+      p = np;
+      break;
+    }
     if (bad || np <= p) {  // (no progress cannot happen: a chunk is longer than a block_size field plus the alignment slack)
       if (threadIdx.x == 0) atomicOr(err, 4u);
       break;
     }
     p = np;
   }
-  if (threadIdx.x == 0) cnt[f] = (uint32_t)(total < 0xFFFFFFFFull ? total : 0xFFFFFFFFull);
+  if (threadIdx.x == 0) {
+    cnt[f] = (uint32_t)(total < 0xFFFFFFFFull ? total : 0xFFFFFFFFull);
+    if (tail) tail[f] = p;
+  }
 }
 
 // The record index without the chain.  htslib starts a new BGZF block when the next record does not fit into the current one
@@ -1122,6 +1144,7 @@ struct SpanArgs {
   int32_t n_ref;             // the header's: what bam_header_k reads from a file
   const uint8_t** seen_out;  // device [n_records]: BamSoA::seen (NULL: not wanted)
   const uint8_t* span_tbm;   // host [n_spans]: the tbmerged flag of the file that owns the span (NULL: YC / YX / YD read for every record)
+  uint64_t* tail_off;        // tbk_bam_decode_open (one span; NULL otherwise): the stream may end inside a record; where the whole records end
 };
 }  // namespace
 
@@ -1224,6 +1247,7 @@ static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const*
     tile->file_off = file_off_out;
     for (uint32_t f = 0; f <= k; ++f) file_off_out[f] = 0;
     if (sp->seen_out) *sp->seen_out = nullptr;
+    if (sp->tail_off) *sp->tail_off = first[0];
     return 0;
   }
   if (mt.empty()) {
@@ -1245,7 +1269,9 @@ static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const*
   uint32_t* d_cnt = ws_alloc<uint32_t>(ctx, k);
   uint64_t* d_rec0 = ws_alloc<uint64_t>(ctx, cap_off[k]);
   uint8_t* d_tbm = ws_alloc<uint8_t>(ctx, k);
-  if (!B->inf || !d_comp || !d_mt || !d_tab || !d_rec0 || !d_tbm) return TBK_ENOMEM;
+  const bool open = sp && sp->tail_off;
+  uint64_t* d_tail = open ? ws_alloc<uint64_t>(ctx, k) : nullptr;
+  if (!B->inf || !d_comp || !d_mt || !d_tab || !d_rec0 || !d_tbm || (open && !d_tail)) return TBK_ENOMEM;
   TBK_HIP(hipMemcpyAsync(d_mt, mt.data(), mt.size() * sizeof(BgzMember), hipMemcpyHostToDevice, ctx->stream));
   TBK_HIP(hipMemcpyAsync(d_tab, fbase.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
   TBK_HIP(hipMemcpyAsync(d_tab + k, fbytes.data(), k * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1308,11 +1334,16 @@ static int bam_decode_impl(tbk_ctx* ctx, uint32_t n_files, const uint8_t* const*
     TBK_TRY(tbk_sync_err(ctx, &eb));
     for (uint32_t f = 0; f < k; ++f) chain = chain || fflag[f] != 0;  // (one file that needs the chain: every file takes it — the kernel is a block per file)
   }
+  // (an open stream whose members all end on record boundaries ends on one: the walks took everything)
+  std::vector<uint64_t> tail(k, 0);
+  for (uint32_t f = 0; f < k; ++f) tail[f] = fbytes[f];
   if (chain && !eb) {
-    TBK_LAUNCH(ctx, "bam_index_chain", bam_index_k, k, IDX_NT, 0, B->inf, d_tab, d_tab + k, d_tab + 2 * k, d_tab + 3 * k, d_rec0, d_cnt, ctx->d_err);
+    TBK_LAUNCH(ctx, "bam_index_chain", bam_index_k, k, IDX_NT, 0, B->inf, d_tab, d_tab + k, d_tab + 2 * k, d_tab + 3 * k, d_rec0, d_cnt, ctx->d_err, d_tail);
     TBK_HIP(hipMemcpyAsync(cnt.data(), d_cnt, k * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (open) TBK_HIP(hipMemcpyAsync(tail.data(), d_tail, k * 8, hipMemcpyDeviceToHost, ctx->stream));
     TBK_TRY(tbk_sync_err(ctx, &eb));
   }
+  if (open && !eb) *sp->tail_off = tail[0];
   if (eb) {
     ctx->last_error = (eb & 1u) ? "corrupt BGZF member (deflate stream, ISIZE or CRC32)" : (eb & 2u) ? "not a BAM stream / truncated header" : "corrupt BAM record chain";
     bamdev_free(ctx);
@@ -1462,8 +1493,21 @@ extern "C" int tbk_bam_decode_spans(tbk_ctx* ctx, uint32_t n_spans, const uint8_
     return 0;
   }
   if (!first_uoff || !last_uoff) return TBK_EINVAL;
-  SpanArgs sp{first_uoff, last_uoff, n_ref, tag_seen_out, nullptr};
+  SpanArgs sp{first_uoff, last_uoff, n_ref, tag_seen_out, nullptr, nullptr};
   return bam_decode_impl(ctx, n_spans, comp, comp_bytes, nullptr, 0, 0, tile, span_off_out, &sp);
+}
+
+// tbk_bam_decode_spans for ONE span whose record stream may end inside a record (include/tbk.h): the chain kernel stops at the incomplete
+// record instead of refusing it and says where; the per-member walks flag such a stream for the chain, as they flag every member that does
+// not end with a record, so both routes give the same count and the same tail.
+extern "C" int tbk_bam_decode_open(tbk_ctx* ctx, const uint8_t* comp, uint64_t comp_bytes, uint32_t first_uoff, int32_t n_ref, tbk_soa_in* tile,
+                                   const uint8_t** tag_seen_out, uint64_t* tail_off) {
+  if (!ctx || !tile || !tag_seen_out || !tail_off || n_ref < 0 || (!comp && comp_bytes)) return TBK_EINVAL;
+  const uint32_t last_uoff = 0;
+  const uint8_t* const comps[1] = {comp ? comp : (const uint8_t*)""};
+  SpanArgs sp{&first_uoff, &last_uoff, n_ref, tag_seen_out, nullptr, tail_off};
+  *tail_off = first_uoff;
+  return bam_decode_impl(ctx, 1, comps, &comp_bytes, nullptr, 0, 0, tile, ctx->bam_open_off, &sp);
 }
 
 // files given as runs of spans (include/tbk.h): the spans are decoded as tbk_bam_decode_spans decodes them, each under the tbmerged flag of
@@ -1495,7 +1539,7 @@ extern "C" int tbk_bam_decode_file_spans(tbk_ctx* ctx, uint32_t n_files, const u
   for (uint32_t f = 0; f < n_files; ++f)
     for (uint32_t s = span_first[f]; s < span_first[f + 1]; ++s) span_tbm[s] = tbmerged && tbmerged[f] ? 1 : 0;
   std::vector<uint32_t> span_off((size_t)n_spans + 1, 0);
-  SpanArgs sp{first_uoff, last_uoff, n_ref, nullptr, span_tbm.data()};
+  SpanArgs sp{first_uoff, last_uoff, n_ref, nullptr, span_tbm.data(), nullptr};
   const int rc = bam_decode_impl(ctx, n_spans, comp, comp_bytes, nullptr, want_md, want_names, tile, span_off.data(), &sp);
   for (uint32_t f = 0; f <= n_files; ++f) file_off_out[f] = rc == 0 ? span_off[span_first[f]] : 0;
   if (rc != 0) return rc;

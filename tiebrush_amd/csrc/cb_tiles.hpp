@@ -23,7 +23,23 @@ struct CbOp {
     return r;
   }
 };
+// Whether a record on `tid` that starts at `start` (1-based) opens a bundle, given the aggregate of the records before it: the first
+// record of a tid run, or a start beyond the running maximum of end over the run so far (tiecov.cpp:443).  The one statement of the
+// rule for every walk that looks for heads (cov.hip: cb_heads_k, cl_heads_k; stream.hip: st_heads_k).
+__device__ __forceinline__ bool cb_is_head(const CbAgg& before, int32_t tid, int32_t start) {
+  return before.last_tid == INT32_MIN || tid != before.last_tid || start > before.mx;
+}
 constexpr uint32_t CB_NT = 256, CB_ROWS = 4, CB_TILE = CB_NT * 4 * CB_ROWS;
+// four consecutive records of a thread from a column of m: one 16-byte load inside the column, element by element (`fill` behind it) at its end
+__device__ __forceinline__ void cb_load4(const int32_t* __restrict__ a, uint64_t i, uint32_t m, int32_t fill, int32_t v[4]) {
+  if (i + 3 < m) {
+    const int4 q = *reinterpret_cast<const int4*>(a + i);  // (i is a multiple of 4, the arrays 256-byte aligned)
+    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = i + e < m ? a[i + e] : fill;
+  }
+}
 template <class T, class Op>
 __device__ __forceinline__ T wave_incl_scan_op(T v, Op op) {
 #pragma unroll

@@ -191,15 +191,6 @@ struct BundleStore {
 //   (2) with the aggregate of the records before it, every record knows whether it opens a bundle: heads counted per tile, scanned;
 //   (3) the same walk again, now numbering: bundle of every record, head flags, the bundle table.
 // 32 bytes read and 8 written per record instead of the look-back kernel's waits: 0.53 -> 0.3 ms on config 3.
-__device__ __forceinline__ void cb_load4(const int32_t* __restrict__ a, uint64_t i, uint32_t m, int32_t fill, int32_t v[4]) {
-  if (i + 3 < m) {
-    const int4 q = *reinterpret_cast<const int4*>(a + i);  // (i is a multiple of 4, the arrays 256-byte aligned)
-    v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = i + e < m ? a[i + e] : fill;
-  }
-}
 __global__ __launch_bounds__(CB_NT) void cb_agg_k(uint32_t m, const int32_t* __restrict__ tid, const int32_t* __restrict__ end, uint4* __restrict__ part,
                                                   uint32_t* __restrict__ done) {
   // (the four rows' loads are issued together and their wave scans run side by side: one barrier per block, not two per row)
@@ -275,8 +266,7 @@ __global__ __launch_bounds__(CB_NT) void cb_heads_k(uint32_t m, CovArrays A, con
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       if (i + e < m) {
-        const bool run_head = w.last_tid == INT32_MIN || t4[e] != w.last_tid;
-        const bool head = run_head || s4[e] > w.mx;  // tiecov.cpp:443
+        const bool head = cb_is_head(w, t4[e], s4[e]);
         hd |= (head ? 1u : 0u) << e;
         nh += head ? 1u : 0u;
         w = op(w, CbAgg{t4[e], t4[e], e4[e], 1u});
@@ -889,7 +879,7 @@ __global__ __launch_bounds__(CB_NT) void cl_heads_k(uint32_t m, CovArrays A, con
     for (int e = 0; e < 4; ++e) {
       if (i + e < m) {
         const bool first = w.last_tid == INT32_MIN;
-        const bool head = first || t4[r][e] != w.last_tid || s4[r][e] > w.mx;  // tiecov.cpp:443
+        const bool head = cb_is_head(w, t4[r][e], s4[r][e]);
         if (head) {
           xs[r] += (long long)s4[r][e] - 1ll - (first ? 0ll : (long long)w.mx);
           hd |= 1u << e;

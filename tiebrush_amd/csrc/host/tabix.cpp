@@ -127,12 +127,12 @@ void TabixWriter::discard() {
 }
 
 bool tabix_host_track(TabixWriter& w, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end,
-                      const std::function<int(uint32_t, char*, size_t)>& fmt, uint32_t slice_rows, int threads, std::string& err) {
+                      const std::function<int(uint32_t, char*, size_t)>& fmt, uint32_t slice_rows, int threads, std::string& err, bool with_head) {
   if (!slice_rows) slice_rows = 1u << 19;
   std::string text;
   std::vector<BaiRec> recs;
   bool first = true;
-  for (uint32_t lo = 0; lo < n || first; first = false) {
+  for (uint32_t lo = 0; lo < n || (first && with_head); first = false) {
     const uint32_t hi = (uint32_t)std::min<uint64_t>(n, (uint64_t)lo + slice_rows), m = hi - lo;
     const size_t nt = m < 50000 ? 1 : (size_t)std::max(1, std::min(threads, 32));
     std::vector<std::string> parts(nt);
@@ -164,7 +164,7 @@ bool tabix_host_track(TabixWriter& w, uint32_t n, const int32_t* tid, const int3
       for (auto& x : th) x.join();
     }
     text.clear();
-    if (first) text = w.head();
+    if (first && with_head) text = w.head();
     recs.clear();
     recs.reserve(m);
     uint32_t i = lo;
@@ -212,13 +212,14 @@ void set_track_names(const TrackApi& api, const std::vector<std::string>& names)
   if (rc != 0) GError("Error: GPU track names failed: %s (%s)\n", api.strerror_(rc), api.last_error(api.ctx));
 }
 
-void write_tabix_track(TabixWriter& w, const tbk_track_rows& r, const std::vector<std::string>& names, const TrackApi& api, bool* names_set) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const char* kinds[3] = {"coverage", "junctions", "samples"};
-  const char* writer = "host";
+bool feed_tabix_track(TabixWriter& w, const tbk_track_rows& r, const std::vector<std::string>& names, const TrackApi& api, bool* names_set, bool with_head,
+                      uint64_t* device_text_bytes) {
   uint64_t text_bytes = 0;
   bool done = false;
   std::string err;
+  const std::string none;
+  const std::string& head = with_head ? w.head() : none;
+  const uint64_t runs_before = w.runs();
   if (!getenv("TBK_TRACK_HOST_FMT")) {
     if (!*names_set) set_track_names(api, names), *names_set = true;
     tbk_ix_opts ix;
@@ -226,11 +227,11 @@ void write_tabix_track(TabixWriter& w, const tbk_track_rows& r, const std::vecto
     ix.n_ref = (uint32_t)w.index().ref_len().size(), ix.reserved = w.index().ix_format(), ix.ref_len = w.index().ref_len().data();
     TbxBridge b{&w};
     uint64_t out_bytes = 0;
-    const int rc = api.track_bgzf(api.ctx, &r, w.head().data(), (uint32_t)w.head().size(), &ix, TbxBridge::sink, &b, &text_bytes, &out_bytes);
+    const int rc = api.track_bgzf(api.ctx, &r, head.data(), (uint32_t)head.size(), &ix, TbxBridge::sink, &b, &text_bytes, &out_bytes);
     if (rc == 0) {
-      done = true, writer = "device";
-    } else {
-      if (b.failed || w.runs()) GError("Error: writing %s failed (%s: %s)\n", w.path().c_str(), api.strerror_(rc), api.last_error(api.ctx));
+      done = true;
+    } else {  // (a refusal before the call's first run hands these rows to the host path; behind one the file is broken)
+      if (b.failed || w.runs() != runs_before) GError("Error: writing %s failed (%s: %s)\n", w.path().c_str(), api.strerror_(rc), api.last_error(api.ctx));
       fprintf(stderr, "Warning: the device track writer refused %s (%s: %s); the host writer takes it\n", w.path().c_str(), api.strerror_(rc),
               api.last_error(api.ctx));
     }
@@ -245,8 +246,20 @@ void write_tabix_track(TabixWriter& w, const tbk_track_rows& r, const std::vecto
       };
     else
       fmt = [&](uint32_t i, char* b, size_t cap) { return fmt_samp_line(b, cap, names[r.tid[i]].c_str(), r.start[i], r.end[i], r.count[i], r.heat[i]); };
-    if (!tabix_host_track(w, r.n, r.tid, r.start, r.end, fmt, host_slice_rows(), worker_count(), err)) GError("Error: writing %s failed (%s)\n", w.path().c_str(), err.c_str());
+    if (!tabix_host_track(w, r.n, r.tid, r.start, r.end, fmt, host_slice_rows(), worker_count(), err, with_head))
+      GError("Error: writing %s failed (%s)\n", w.path().c_str(), err.c_str());
   }
+  if (device_text_bytes) *device_text_bytes = text_bytes;
+  return done;
+}
+
+void write_tabix_track(TabixWriter& w, const tbk_track_rows& r, const std::vector<std::string>& names, const TrackApi& api, bool* names_set) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const char* kinds[3] = {"coverage", "junctions", "samples"};
+  uint64_t text_bytes = 0;
+  const bool done = feed_tabix_track(w, r, names, api, names_set, true, &text_bytes);
+  const char* writer = done ? "device" : "host";
+  std::string err;
   if (!w.close(err)) GError("Error: writing %s failed (%s)\n", w.path().c_str(), err.c_str());
   if (getenv("TBK_TIMING"))
     fprintf(stderr, "tabix phase ms: writer %s | %s | %u rows | %llu text bytes | %llu gz bytes | %.1f\n", writer, kinds[r.kind], r.n,

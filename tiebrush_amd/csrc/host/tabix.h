@@ -55,7 +55,7 @@ class TabixWriter {
 // The host path of a whole track: fmt(i, buf, cap) is snprintf-like (tracks.h).  Slices of `slice_rows` rows (0: 2^19; the first
 // carries the writer's header line), formatted and deflated on `threads` workers.
 bool tabix_host_track(TabixWriter& w, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end,
-                      const std::function<int(uint32_t, char*, size_t)>& fmt, uint32_t slice_rows, int threads, std::string& err);
+                      const std::function<int(uint32_t, char*, size_t)>& fmt, uint32_t slice_rows, int threads, std::string& err, bool with_head = true);
 
 struct TrackApi;  // tracks.h: the device entry points as a command line has them
 // The reference names onto the context, for tbk_format_track and tbk_track_bgzf.  Errors are fatal (GError).
@@ -65,5 +65,11 @@ void set_track_names(const TrackApi& api, const std::vector<std::string>& names)
 // before its first run hands the track to the host path (a line on stderr says so).
 // Errors are fatal (GError).  TBK_TIMING: a "tabix phase ms" line on stderr.
 void write_tabix_track(TabixWriter& w, const tbk_track_rows& rows, const std::vector<std::string>& names, const TrackApi& api, bool* names_set);
+// The same without the close, for a track that arrives in several pieces (TrackStream, tracks.h): the rows of one piece as further runs
+// (device) or slices (host) behind what the writer has.  with_head: the writer's header line goes in front of these rows — the first
+// piece.  true: the device wrote them (*device_text_bytes: their text).  A device refusal before the call's first run hands the piece to
+// the host path.  The caller closes the writer.
+bool feed_tabix_track(TabixWriter& w, const tbk_track_rows& rows, const std::vector<std::string>& names, const TrackApi& api, bool* names_set, bool with_head,
+                      uint64_t* device_text_bytes);
 
 }  // namespace tbh

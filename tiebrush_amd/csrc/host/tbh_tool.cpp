@@ -15,6 +15,8 @@
 //   mquery REGION THREADS IN1.bam ... / mrquery REGIONS.bed THREADS IN1.bam ...   the host plumbing of `tiebrush -r` / `-R`, per input
 //   summary IN.bam COV.bedgraph JUNC.bed FEATURES.bed OUT.tsv   the per-feature summary of `tiecov --features --summary` from our own
 //                                 plain tracks, by the host summariser alone ("-" for a track that is not there)
+//   batches IN.bam BYTES          the batches of whole BGZF members a streamed decode reads (stream_read.h): per batch its
+//                                 member range, first_uoff, the range of whole records in it and the tail, both by the host codec
 //   mkbam SOADIR PREFIX [LEVEL [THREADS]]   encode the raw SoA arrays of a synthetic tile (file_off, tid, pos, flag, mapq, strand,
 //                                 nh, cig_off, cig as little-endian files + header.txt) as PREFIX<f>.bam, one per input file: the
 //                                 records tiebrush_amd.synth.write_bams writes (SEQ '*', QNAME r<f>_<i>, NH:C / XS:A), files in parallel
@@ -35,6 +37,7 @@
 #include "fastload.h"
 #include "tmerge.h"
 #include "bigwig.h"
+#include "stream_read.h"
 #include "tabix.h"
 #include "tracks.h"
 
@@ -635,6 +638,39 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery|summary ...\n");
+  if (cmd == "batches" && argc == 4) {  // batches FILE.bam BYTES
+    tbh::StreamReader rd;
+    std::string err;
+    if (!rd.open(argv[2], strtoull(argv[3], nullptr, 10), err)) {
+      fprintf(stderr, "tbh_tool batches: %s\n", err.c_str());
+      return 1;
+    }
+    printf("header n_targets=%d\n", rd.header().n_targets);
+    tbh::StreamBatch b;
+    uint64_t rec = 0, k = 0;
+    while (rd.next(b, err)) {
+      uint64_t n = 0, tail = 0;
+      if (!tbh::stream_host_tail(b, &n, &tail, err)) {
+        fprintf(stderr, "tbh_tool batches: %s: %s\n", argv[2], err.c_str());
+        return 1;
+      }
+      printf("batch %llu members=%llu..%llu first_uoff=%u records=%llu..%llu tail=%llu last=%d\n", (unsigned long long)k++, (unsigned long long)b.first_member,
+             (unsigned long long)(b.first_member + b.csize.size()), b.first_uoff, (unsigned long long)rec, (unsigned long long)(rec + n), (unsigned long long)tail,
+             (int)b.last);
+      rec += n;
+      if (!rd.advance(b, tail, err)) {
+        fprintf(stderr, "tbh_tool batches: %s\n", err.c_str());
+        return 1;
+      }
+    }
+    if (!err.empty()) {
+      fprintf(stderr, "tbh_tool batches: %s\n", err.c_str());
+      return 1;
+    }
+    printf("end records=%llu members=%llu bytes_read=%llu reinflated=%llu\n", (unsigned long long)rec, (unsigned long long)rd.members(),
+           (unsigned long long)rd.bytes_read(), (unsigned long long)rd.reinflated());
+    return 0;
+  }
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery|summary|batches ...\n");
   return 2;
 }

@@ -4,6 +4,8 @@
 // With -r REGION (no counterpart in the reference) only the chunks the file's index names for the region are read, and
 // they are inflated, decoded, filtered, summarised and cut to the region on the device (regions_main below).
 // With -R FILE the same for the region table of a BED file, in one run: the chunks are merged over the whole table.
+// With --stream the file is read in batches of whole BGZF members, decoded on the device and cut at bundle heads
+// (stream_main below): host and device memory are bounded by the batch and the largest bundle, not by the file.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -18,6 +20,8 @@
 #include "GSam.h"
 #include "args.h"
 #include "bai_read.h"
+#include "bgzf.h"
+#include "stream_read.h"
 #include "tracks.h"
 
 #define VERSION "0.0.7"
@@ -26,7 +30,7 @@ static const char* USAGE =
     "TieCov v" VERSION " (MI355X build)\n"
     "Summarises a (TieBrush-collapsed) BAM file as BED-like tracks.\n"
     "\n"
-    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [--features BED --summary OUT.tsv] [-r REGION | -R FILE] input.bam\n"
+    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [--features BED --summary OUT.tsv] [-r REGION | -R FILE] [--stream] input.bam\n"
     "\n"
     "  -h,--help    print this text and exit\n"
     "  --version    print the version and exit\n"
@@ -50,16 +54,20 @@ static const char* USAGE =
     "               mean0 = sum / size, mean = sum / covered, max of the coverage, and junc = the junction track's value for the feature\n"
     "               taken as an intron (same start and end; strand + - or, for '.', every strand).  Computed on the GPU from the rows of\n"
     "               -c / -j (TBK_SUMMARY_HOST=1: on this core).  With -r / -R every feature must lie inside one interval of the region\n"
+    "  --stream [--tile-bytes N]   read input.bam in batches of whole BGZF members of about N compressed bytes (plain bytes, or K / M / G;\n"
+    "               default 64M; --tile-bytes alone implies --stream), decode them on the GPU and write the tracks bundle by bundle: the same\n"
+    "               bytes as without it, with memory bounded by a batch and the largest bundle.  With -c (also - / stdout), -j, -s, -W,\n"
+    "               --tabix; not with -r / -R / --index-file, --features / --summary, --bigwig-writer device, or SAM text input\n"
     " At least one of -c / -j / -s / --summary is required.\n";
 
 // ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
 // how often -r / --region is given (Args keeps the last value of a repeated option)
 static int count_region_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", "features", "summary", nullptr};
+  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", "features", "summary", "tile-bytes", nullptr};
   return count_value_option(argc, argv, "region", 'r', value_longs, "csjR");
 }
 static int count_regions_file_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", "features", "summary", nullptr};
+  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", "features", "summary", "tile-bytes", nullptr};
   return count_value_option(argc, argv, "regions-file", 'R', value_longs, "csjr");
 }
 
@@ -149,8 +157,109 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
   return 0;
 }
 
+// ---- tiecov --stream -----------------------------------------------------------------------------------------------
+// "N", "NK", "NM", "NG" -> bytes; false: not a size
+static bool parse_size(const char* v, uint64_t* out) {
+  char* e = nullptr;
+  const unsigned long long n = strtoull(v, &e, 10);
+  if (e == v || *v == '-') return false;
+  uint64_t mul = 1;
+  if (*e == 'K' || *e == 'k') mul = 1ull << 10, ++e;
+  else if (*e == 'M' || *e == 'm') mul = 1ull << 20, ++e;
+  else if (*e == 'G' || *e == 'g') mul = 1ull << 30, ++e;
+  if (*e) return false;
+  *out = (uint64_t)n * mul;
+  return true;
+}
+
+// The whole file in batches: reader -> tbk_bam_decode_open -> tbk_cov_stream_push -> the rows of the view into the open files.  Every
+// refusal of the option rules came before this; from the first file on, a failure removes what was written (standard output is what it is).
+static int stream_main(sam_hdr_t* hdr, const std::string& infname, uint64_t tile_bytes, const tbh::TrackOptions& topt) {
+  using clock = std::chrono::steady_clock;
+  const auto t0 = clock::now();
+  auto ms_since = [](clock::time_point a) { return std::chrono::duration<double, std::milli>(clock::now() - a).count(); };
+  int num_samples = 0;
+  if (!topt.samp.empty()) {
+    num_samples = (int)hdr->co_samples().size();
+    if (num_samples == 0) GError("Error: no sample lines found in header");
+  }
+  tbk_ctx* ctx = nullptr;
+  const int dev = getenv("TBK_DEVICE") ? atoi(getenv("TBK_DEVICE")) : 0;
+  int rc = 0;
+  std::thread ctx_thread([&]() { rc = tbk_create(dev, &ctx); });
+  tbh::StreamReader rd;
+  std::string err;
+  const bool opened = rd.open(infname, tile_bytes, err);
+  ctx_thread.join();
+  if (!opened) GError("Error: %s\n", err.c_str());
+  if (rc != 0) GError("Error: cannot use GPU %d (%s); this build has no CPU coverage path\n", dev, tbk_strerror(rc));
+  tbh::TrackFiles tf;
+  open_tracks(tf, hdr, topt);
+  auto fail = [&](const std::string& msg) {
+    tf.discard();
+    GError("Error: %s\n", msg.c_str());
+  };
+  tbh::TrackRun run;
+  run.num_samples = num_samples;
+  const tbh::TrackApi api = linked_track_api(ctx);
+  tbh::TrackStream ts(api, hdr->target_name, tf, run);
+  double ms_decode = 0, ms_push = 0, ms_tracks = 0;
+  uint32_t largest_carry = 0;
+  uint64_t n_batches = 0;
+  bool ended = false;
+  auto push = [&](const tbk_soa_in& tile, const uint8_t* seen, bool last) {
+    tbk_cov_in view;
+    tbk_cov_stream_info info;
+    auto a = clock::now();
+    const int prc = tbk_cov_stream_push(ctx, &tile, seen, last ? 1 : 0, &view, &info);
+    ms_push += ms_since(a);
+    if (prc == TBK_E2BIG) {  // (info names the first record of the bundle that did not fit)
+      const bool known = info.first_tid >= 0 && info.first_tid < hdr->n_targets;
+      fail("bundle too large for one tile: the bundle of " + infname + " that begins at " +
+           (known ? hdr->target_name[(size_t)info.first_tid] + ":" + std::to_string((long long)info.first_pos + 1) : std::string("an unplaced record")) +
+           " and the next batch exceed what one call can take");
+    }
+    if (prc != 0) fail(std::string("GPU stream cut failed: ") + tbk_strerror(prc) + " (" + tbk_last_error(ctx) + ")");
+    largest_carry = std::max(largest_carry, info.n_carry);
+    if (view.n_records == 0 && !last) return;  // (the open bundle goes on: nothing to write yet)
+    if (view.n_records == 0) memset(&view, 0, sizeof(view)), view.mem = TBK_MEM_HOST;  // (no record at all: the empty input of a whole-file run)
+    a = clock::now();
+    ts.tile(view, last);
+    ms_tracks += ms_since(a);
+    ended = last;
+  };
+  tbh::StreamBatch b;
+  while (rd.next(b, err)) {
+    ++n_batches;
+    tbk_soa_in tile;
+    const uint8_t* seen = nullptr;
+    uint64_t tail = 0;
+    auto a = clock::now();
+    rc = tbk_bam_decode_open(ctx, b.z.data(), b.z.size(), b.first_uoff, hdr->n_targets, &tile, &seen, &tail);
+    ms_decode += ms_since(a);
+    if (rc == TBK_E2BIG) fail("input too large for one tile (a batch of " + infname + " holds 2^32 records: use a smaller --tile-bytes)");
+    if (rc != 0) fail("could not decode " + infname + " (" + tbk_strerror(rc) + " " + tbk_last_error(ctx) + ")");
+    if (!rd.advance(b, tail, err)) fail(err);
+    push(tile, seen, b.last);
+  }
+  if (!err.empty()) fail(err);
+  if (!ended) {  // (the file ended on a batch's edge, or holds no record: what is still open goes out now)
+    tbk_soa_in none;
+    memset(&none, 0, sizeof(none));
+    none.mem = TBK_MEM_DEVICE;
+    push(none, nullptr, true);
+  }
+  ts.end();
+  if (getenv("TBK_TIMING"))
+    fprintf(stderr, "tiecov --stream phases ms: %llu batches of about %llu bytes (%llu tiles written) | %llu bytes read | %llu bytes inflated twice | largest carry %u records | decode %.1f | push %.1f | tracks %.1f | total %.1f\n",
+            (unsigned long long)n_batches, (unsigned long long)tile_bytes, (unsigned long long)ts.tiles(), (unsigned long long)rd.bytes_read(),
+            (unsigned long long)rd.reinflated(), largest_carry, ms_decode, ms_push, ms_tracks, ms_since(t0));
+  tbk_destroy(ctx);
+  return 0;
+}
+
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;features=;summary=;tabix;DVWhc:s:j:r:R:");
+  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;features=;summary=;tabix;stream;tile-bytes=;DVWhc:s:j:r:R:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -192,6 +301,19 @@ int main(int argc, char* argv[]) {
     return 1;
   }
   std::string infname = args.nextNonOpt();
+  // --stream: what it does not go with is refused here, before the input is opened and any file exists
+  const bool stream = args.getOpt("stream") || args.getOpt("tile-bytes");
+  uint64_t tile_bytes = (uint64_t)64 << 20;  // (the default is not measured yet: DESIGN.md 4k)
+  if (stream) {
+    if (args.getOpt("tile-bytes") && !parse_size(args.getOpt("tile-bytes"), &tile_bytes))
+      GError("Error: --tile-bytes takes a size in bytes, or with a K / M / G suffix (got '%s')\n", args.getOpt("tile-bytes"));
+    if (args.getOpt('r') || args.getOpt("region") || args.getOpt('R') || args.getOpt("regions-file") || args.getOpt("index-file"))
+      GError("Error: --stream and -r / -R / --index-file do not go together (a region run reads only the region's chunks)\n");
+    if (args.getOpt("features") || args.getOpt("summary"))
+      GError("Error: --stream and --features / --summary do not go together (a feature across two tiles needs a carried partial sum)\n");
+    if (topt.bw_device) GError("Error: --stream and --bigwig-writer device do not go together (the device writer takes all rows at once)\n");
+    if (!tbh::bgzf_probe(infname)) GError("Error: --stream needs a BAM file (BGZF); %s is SAM text or cannot be read\n", infname.c_str());
+  }
   GSamReader samreader(infname.c_str(), SAM_QNAME | SAM_FLAG | SAM_RNAME | SAM_POS | SAM_CIGAR | SAM_AUX);
   sam_hdr_t* hdr = samreader.header();
   tbh::SummaryJob sj;  // (--features / --summary: refused, where they are, before any output file exists)
@@ -217,6 +339,7 @@ int main(int argc, char* argv[]) {
     sj.setup(args.getOpt("features"), args.getOpt("summary"), *hdr, &U);
     return regions_main(hdr, infname, U, rf == nullptr, index_file, topt, sj, t0);
   }
+  if (stream) return stream_main(hdr, infname, tile_bytes, topt);
   sj.setup(args.getOpt("features"), args.getOpt("summary"), *hdr, nullptr);
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;

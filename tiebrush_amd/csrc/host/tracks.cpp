@@ -2,6 +2,7 @@
 #include "tracks.h"
 
 #include <string.h>
+#include <unistd.h>
 
 #include <stdlib.h>
 
@@ -62,12 +63,14 @@ void TrackFiles::open(const TrackOptions& o, const std::vector<std::string>& nam
     if (!ends_with(junc_prefix, ".bed")) junc_prefix += ".bed";
     junc = fopen(junc_prefix.c_str(), "w");
     if (!junc) GError("Error creating file %s\n", junc_prefix.c_str());
+    junc_name = junc_prefix;
     fprintf(junc, "%s", kJuncHead);
   }
   if (!samp_prefix.empty()) {
     if (!ends_with(samp_prefix, ".bedgraph")) samp_prefix += ".bedgraph";
     samp = fopen(samp_prefix.c_str(), "w");
     if (!samp) GError("Error creating file %s\n", samp_prefix.c_str());
+    samp_name = samp_prefix;
     fprintf(samp, "%s", kSampHead);
   }
 }
@@ -354,21 +357,41 @@ bool CovRecs::append(uint32_t ng, const std::function<RecView(uint32_t)>& rec, c
 
 static int fwrite_sink(void* user, const char* p, uint64_t n) { return fwrite(p, 1, n, (FILE*)user) == n ? 0 : 1; }
 
-void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run) {
+TrackStream::TrackStream(const TrackApi& api, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run)
+    : api_(api), names_(names), tf_(tf), run_(run) {
+  // --tabix: a track's writer is open in the place of its FILE* (tabix.h)
+  const bool host_fmt = getenv("TBK_TRACK_HOST_FMT") != nullptr;
+  if ((tf.cov_tx.is_open() || tf.junc_tx.is_open() || tf.samp_tx.is_open()) && !host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
+  if (run.device_text) set_track_names(api, names), names_set_ = true;
+}
+
+void TrackStream::tile(const tbk_cov_in& in, bool last) {
   using clock = std::chrono::steady_clock;
   auto ms_since = [](clock::time_point a) { return std::chrono::duration<double, std::milli>(clock::now() - a).count(); };
+  const TrackApi& api = api_;
+  const std::vector<std::string>& names = names_;
+  TrackFiles& tf = tf_;
+  const TrackRun& run = run_;
+  TrackTimes& times = times_;
+  bool& names_set = names_set_;
   tbk_ctx* ctx = api.ctx;
   const size_t n = in.n_records, co = in.n_cigar_ops;
   const TrackClip* clip = run.clip;
   const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
   const bool summary = run.summary && run.summary->on();
-  // --tabix: a track's writer is open in the place of its FILE* (tabix.h)
   const bool cov_tx = tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
-  const bool host_fmt = getenv("TBK_TRACK_HOST_FMT") != nullptr;
-  if ((cov_tx || junc_tx || samp_tx) && !host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
-  bool names_set = false;  // the reference names are on the context
-  if (run.device_text) set_track_names(api, names), names_set = true;
-  TrackTimes times;
+  const bool only = last && tiles_ == 0;  // the run's one tile: run_tracks
+  // (the summary and a clip take every row of a track in one call: a run of several tiles does not have them)
+  if (!only && (summary || clip)) GError("Error: a summary and a region clip take the rows of one tile\n");
+  ++tiles_;
+  // a tabix track: the run's one tile as before (written and closed); a tile of several as further runs behind the writer's, the header
+  // line with the first rows, the writer closed by end().  A tile without rows for a track writes nothing to it.
+  auto tabix = [&](TabixWriter& w, const tbk_track_rows& r, int k) {
+    if (only) return write_tabix_track(w, r, names, api, &names_set);
+    if (!r.n) return;
+    (void)feed_tabix_track(w, r, names, api, &names_set, !tx_started_[k], nullptr);
+    tx_started_[k] = true;
+  };
   // the text of one plain track: the device formatter, or false (then the caller's host formatter)
   auto device_text = [&](FILE* f, const tbk_track_rows& r) {
     if (!run.device_text) return ++times.host_tracks, false;
@@ -399,7 +422,8 @@ void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std
     o.j_tid = jt.data(), o.j_start = js.data(), o.j_end = je.data(), o.j_strand = jstr.data(), o.j_val = jv.data();
     auto a = clock::now();
     rc = api.coverage_tile(ctx, &in, &o);
-    times.ms_cov = ms_since(a);
+    times.ms_cov += ms_since(a);
+    n_bases_ += o.n_bases, span_bases_ += o.span_bases;
     if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
     if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
     if (summary) write_summary(*run.summary, names, o, api);
@@ -411,7 +435,7 @@ void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std
     tbk_track_rows rcov = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
     rcov.val = iv.data();
     tbk_track_rows rjunc = rows(TBK_TRACK_JUNC, o.n_junctions, jt.data(), js.data(), je.data());
-    rjunc.val = jv.data(), rjunc.strand = jstr.data();
+    rjunc.val = jv.data(), rjunc.strand = jstr.data(), rjunc.first_junc = first_junc_;  // (JUNC%08d runs on over the tiles)
     if (tf.cov) {  // flushCoverage, tiecov.cpp:237
       a = clock::now();
       if (!device_text(tf.cov, rcov)) emit_cov_lines(tf.cov, names, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
@@ -419,16 +443,22 @@ void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std
     }
     if (tf.cov_bw) {  // flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the same intervals, the value as a float
       if (run.bw_device && !api.bigwig_build) GError("Error: --bigwig-writer device: libtbk.so lacks tbk_bigwig_build\n");
-      tf.write_bigwig(o.n_intervals, it.data(), is.data(), ie.data(), iv.data(), run.bw_device ? &api : nullptr);
+      if (only) {
+        tf.write_bigwig(o.n_intervals, it.data(), is.data(), ie.data(), iv.data(), run.bw_device ? &api : nullptr);
+      } else {  // the host writer keeps its items: the file is closed by end()
+        if (run.bw_device) GError("Error: --bigwig-writer device takes the rows of one tile\n");
+        for (uint32_t i = 0; i < o.n_intervals; ++i) tf.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
+      }
     }
     if (tf.junc) {  // CJunc::write, tiecov.cpp:91-95 (numbered from 1)
       a = clock::now();
-      if (!device_text(tf.junc, rjunc)) emit_junc_lines(tf.junc, names, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), 1);
+      if (!device_text(tf.junc, rjunc)) emit_junc_lines(tf.junc, names, o.n_junctions, jt.data(), js.data(), je.data(), jv.data(), jstr.data(), first_junc_);
       times.ms_text += ms_since(a);
     }
+    first_junc_ += o.n_junctions;
     a = clock::now();
-    if (cov_tx) write_tabix_track(tf.cov_tx, rcov, names, api, &names_set);
-    if (junc_tx) write_tabix_track(tf.junc_tx, rjunc, names, api, &names_set);
+    if (cov_tx) tabix(tf.cov_tx, rcov, 0);
+    if (junc_tx) tabix(tf.junc_tx, rjunc, 1);
     times.ms_text += ms_since(a);
   }
   if (tf.samp || samp_tx) {
@@ -451,7 +481,7 @@ void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std
       if (rc != TBK_E2BIG) break;
       cs = (size_t)so.n_intervals + 16 + extra;
     }
-    times.ms_samp = ms_since(a);
+    times.ms_samp += ms_since(a);
     if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
     if (rc != 0) GError("Error: GPU sample track failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
     if (clip) {
@@ -462,12 +492,39 @@ void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std
     tbk_track_rows r = rows(TBK_TRACK_SAMPLE, so.n_intervals, st.data(), ss.data(), se.data());
     r.count = sc.data(), r.heat = sh.data();
     a = clock::now();
-    if (samp_tx) write_tabix_track(tf.samp_tx, r, names, api, &names_set);
+    if (samp_tx) tabix(tf.samp_tx, r, 2);
     else if (!device_text(tf.samp, r)) emit_samp_lines(tf.samp, names, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
     times.ms_text += ms_since(a);
   }
-  tf.close();
-  if (run.times) *run.times = times;
+}
+
+void TrackStream::end() {
+  TabixWriter* const tx[3] = {&tf_.cov_tx, &tf_.junc_tx, &tf_.samp_tx};
+  for (int k = 0; k < 3; ++k) {  // (a writer that got rows tile by tile; one that got none is TrackFiles::close's: header, EOF member, empty index)
+    std::string err;
+    if (tx_started_[k] && !tx[k]->close(err)) GError("Error: writing %s failed (%s)\n", tx[k]->path().c_str(), err.c_str());
+  }
+  tf_.close();
+  if (run_.times) *run_.times = times_;
+}
+
+void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run) {
+  TrackStream s(api, names, tf, run);
+  s.tile(in, true);
+  s.end();
+}
+
+void TrackFiles::discard() {
+  std::string err;
+  if (cov_bw) (void)bw.close(err), cov_bw = false;
+  if (cov && cov != stdout) fclose(cov);
+  if (junc) fclose(junc);
+  if (samp) fclose(samp);
+  cov = junc = samp = nullptr;
+  for (TabixWriter* w : {&cov_tx, &junc_tx, &samp_tx})
+    if (w->is_open()) w->discard();
+  for (const std::string* p : {&cov_name, &junc_name, &samp_name})
+    if (!p->empty() && *p != "-" && *p != "stdout") (void)unlink(p->c_str());
 }
 
 }  // namespace tbh

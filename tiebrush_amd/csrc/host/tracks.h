@@ -57,7 +57,7 @@ struct TrackFiles {
   BigWigWriter bw;
   bool cov_bw = false;
   std::vector<uint32_t> bw_lens;  // the chromosome lengths the bigWig was opened with
-  std::string cov_name;
+  std::string cov_name, junc_name, samp_name;  // (junc / samp: the plain files; a tabix track's name is its writer's)
   TabixWriter cov_tx, junc_tx, samp_tx;  // --tabix
   void open(const TrackOptions& o, const std::vector<std::string>& names, const std::vector<uint32_t>& lens);
   void close_bigwig();  // (after every interval went to bw)
@@ -66,6 +66,7 @@ struct TrackFiles {
   // hands the file to the host producer (a line on stderr says so).  TBK_TIMING: a "bigwig phase" line on stderr for either.
   void write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev);
   void close();
+  void discard();  // a run that failed: every file closed and removed (standard output is what it is)
 };
 
 // Text output: the lines are independent, so slices of them are formatted by worker threads and written in order.
@@ -161,6 +162,33 @@ struct TrackRun {
 // reference names go to the context (track_names) at most once: up front with device_text, else before the first tabix track the
 // device writes.  Errors are fatal (GError).
 void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run);
+
+// run_tracks in three steps, for a record stream that arrives in tiles cut at bundle heads: the rows of the tiles, one
+// after the other, are the rows of the uncut stream, so every tile's lines are appended to the open files — the junction numbers run on,
+// the bigWig's host writer collects the rows of every tile — and end() closes the files.  run_tracks is begin, ONE tile, end: the same
+// calls in the same order, the same bytes.  A tabix track takes a tile's rows as further runs (feed_tabix_track: the header line with
+// the first rows, one close in end()).  The summary, a clip and the device bigWig writer take the rows of one tile and are refused
+// (GError) in a run of several.
+class TrackStream {
+ public:
+  TrackStream(const TrackApi& api, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run);
+  void tile(const tbk_cov_in& in, bool last);  // last: no tile follows
+  void end();
+  uint64_t n_bases() const { return n_bases_; }
+  uint64_t span_bases() const { return span_bases_; }
+  uint64_t tiles() const { return tiles_; }
+
+ private:
+  const TrackApi& api_;
+  const std::vector<std::string>& names_;
+  TrackFiles& tf_;
+  const TrackRun& run_;
+  int64_t first_junc_ = 1;
+  uint64_t n_bases_ = 0, span_bases_ = 0, tiles_ = 0;
+  bool names_set_ = false;  // the reference names are on the context
+  bool tx_started_[3] = {false, false, false};  // --tabix in a run of several tiles: the track's writer has its header line and first rows
+  TrackTimes times_;
+};
 
 template <class F>
 void emit_lines(FILE* f, uint32_t n, F fmt) {

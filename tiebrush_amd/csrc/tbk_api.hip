@@ -551,6 +551,7 @@ void tbk_debug_parse(const char* spec, TbkDebug* out) {
     else if (k == "phases") out->phases = on;
     else if (k == "no_bounce") out->no_bounce = on;
     else if (k == "fmt_slice") out->fmt_slice = u;
+    else if (k == "stream_cap") out->stream_cap = u;
   }
 }
 
@@ -645,6 +646,7 @@ void tbk_destroy(tbk_ctx* ctx) {
   tbk_enc_free(ctx);
   tbk_ix_free(ctx);
   tbk_bw_free(ctx);
+  tbk_cov_stream_free(ctx);
   tbk_stager_free(ctx);
   if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
   if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);

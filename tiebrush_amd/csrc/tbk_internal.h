@@ -114,6 +114,7 @@ struct TbkDebug {
   bool no_bounce = false;     // no_bounce=1: results of moderate size are copied straight into the caller's (registered) arrays
   bool phases = false;        // phases=1: tbk_collapse_tile prints where its wall time went (copies in, grouping, YD stage, results) to stderr
   uint64_t fmt_slice = 0;     // fmt_slice=N: bytes of a tbk_format_track slice (0: 32 MiB)
+  uint64_t stream_cap = 0;    // stream_cap=N: records the open bundle and a tile of tbk_cov_stream_push may hold together (0: 2^32 - 2)
 };
 void tbk_debug_parse(const char* spec, TbkDebug* out);
 
@@ -179,6 +180,7 @@ struct tbk_ctx {
   char* d_unpack = nullptr;      // the tile tbk_unpack_tile rebuilt from its packed wire form (pack.hip)
   size_t d_unpack_cap = 0;
   std::vector<uint8_t> unpack_tbm;
+  uint32_t bam_open_off[2] = {0, 0};  // tbk_bam_decode_open: what its tile's file_off points to
   void* bam_dev = nullptr;       // device-decoded BAM input (bamdev.hip): inflated streams + record index + the SoA tile's arrays
   void* enc = nullptr;           // the encoder's device buffers (bgzdef.hip)
   void* ix = nullptr;            // the pinned host arrays of the last tbk_bam_encode_indexed's index part (baix.hip)
@@ -199,11 +201,13 @@ struct tbk_ctx {
   void* fmt_pin[2] = {nullptr, nullptr};
   size_t fmt_pin_cap = 0;
   void* bw = nullptr;            // the host section tables of the last tbk_bigwig_build (bigwig.hip)
+  void* cov_stream = nullptr;    // the carry (double-buffered) and the view of tbk_cov_stream_push (stream.hip)
 };
 void tbk_stager_free(tbk_ctx* ctx);
 void tbk_enc_free(tbk_ctx* ctx);
 void tbk_ix_free(tbk_ctx* ctx);
 void tbk_bw_free(tbk_ctx* ctx);
+void tbk_cov_stream_free(tbk_ctx* ctx);
 // baix.hip: the index part of a run the encoder has just packed.  All pointers are device memory of the encoder, alive until its next call.
 struct TbkIxIn {
   uint32_t n;             // records
