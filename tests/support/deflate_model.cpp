@@ -6,7 +6,19 @@
 // zlib's levels reach on the same members, which is how the parse was chosen.
 //
 //   deflate_model selftest
-//   deflate_model <file> [hbits=11] [lazy=1] [tables=2] [min4_far] [good=16] [member=65280] [h8bits=10]   (defaults = the kernel's)
+//   deflate_model <file> [hbits=11] [lazy=1] [tables=2] [min4_far] [good=16] [member=65280] [h8bits=10] [shortcap=0] [tie8=1]
+//       the EXPLORATORY parse the kernel's was chosen with (parse()); its defaults are NOT the kernel's: 11 hash bits where the kernel
+//       has 10, candidates compared over 258 bytes where the kernel compares 16, the 8-byte candidate preferred on a tie, a lazy look
+//       that crosses the kernel's round seams, a stored block only beyond 8 n + 40 bits.  tools/deflate_bench.py and
+//       tests/test_deflate_model.py use it for sizes.
+//   deflate_model tokens <payload file> <cuts file: u64 offsets, members + 1 of them> <out file>
+//       the KERNEL's parse (parse_kernel(), restated from bgz_deflate_k line by line) and the kernel's choice of block: per member the
+//       token list, the block type and the deflate bytes, which the device's must equal to the byte (tests/test_deflate_scenes_cpu.py,
+//       tests/test_gpu_deflate_edges.py).  Out file, little-endian u32: 'DFTK', members; per member n, BTYPE, tokens, deflate bytes,
+//       the bits the choice of block was made on; then the tokens (u32 each, as below) and the bytes.
+//   deflate_model candidates <payload file> <cuts file> <out file>
+//       the same, and behind every member's bytes four u16 per position: the 4-byte table's candidate and the 8-byte table's (0xFFFF:
+//       none) and their compared lengths — what a scene relies on where its tokens alone would not show it.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -103,18 +115,87 @@ static void parse(const uint8_t* s, uint32_t n, const Params& P, std::vector<uin
   }
 }
 
+// bgz_deflate_k's parse (tiebrush_amd/csrc/bgzdef.hip), serial.  Rounds of 512 positions (DF_ROUND), both tables 1 << 10 entries.
+//   inserting wave: positions ascending; p + 4 <= n: the 4-byte table's entry is read and set to p (a candidate counts at distance <=
+//     32768); p + 8 <= n: likewise the 8-byte table (its candidate is dropped when it is the 4-byte table's entry, or beyond 32768).
+//     Every position is inserted, inside matches too.
+//   matching waves: common prefix with the candidate capped at min(16, n - p), 0 when the first four bytes differ; the 4-byte candidate
+//     first, the 8-byte one replaces it only when strictly longer; below 4: no match.
+//   parsing wave: L >= 4 at p: when L < 16, p + 1 lies in the same round and has a longer compared length, p goes out as a literal;
+//     otherwise the match is taken, a compared length of 16 extended to the true length capped at min(258, n - p).
+static void parse_kernel(const uint8_t* s, uint32_t n, std::vector<uint32_t>& tok, std::vector<uint16_t>* cand = nullptr) {
+  const uint32_t ROUND = 512, GOOD = 16, HB = 10;
+  std::vector<uint32_t> t4((size_t)1 << HB, 0), t8((size_t)1 << HB, 0);  // position + 1, 0 = none
+  std::vector<uint8_t> mlen(n, 0);
+  std::vector<uint32_t> mdist(n, 0);
+  auto compared = [&](uint32_t p, uint32_t q) -> uint32_t {
+    if (ld32(s + p) != ld32(s + q)) return 0;
+    const uint32_t lim = std::min<uint32_t>(GOOD, n - p);
+    uint32_t l = 4;
+    while (l < lim && s[q + l] == s[p + l]) ++l;
+    return std::min(l, lim);
+  };
+  for (uint32_t p = 0; p + 4 <= n; ++p) {
+    const uint32_t w0 = ld32(s + p);
+    uint32_t k4 = 0xFFFFFFFFu, k8 = 0xFFFFFFFFu;
+    uint32_t& e4 = t4[(w0 * 0x9E3779B1u) >> (32 - HB)];
+    const uint32_t c4 = e4;
+    e4 = p + 1;
+    if (c4 != 0 && p + 1 - c4 <= 32768u) k4 = c4 - 1;
+    if (p + 8 <= n) {
+      uint32_t& e8 = t8[(w0 * 0x9E3779B1u + ld32(s + p + 4) * 0x85EBCA77u) >> (32 - HB)];
+      const uint32_t c8 = e8;
+      e8 = p + 1;
+      if (c8 != 0 && c8 != c4 && p + 1 - c8 <= 32768u) k8 = c8 - 1;
+    }
+    uint32_t best = 0, bestd = 0, l4 = 0, l8 = 0;
+    if (k4 != 0xFFFFFFFFu) best = l4 = compared(p, k4), bestd = p - k4;
+    if (k8 != 0xFFFFFFFFu) {
+      const uint32_t l = l8 = compared(p, k8);
+      if (l > best) best = l, bestd = p - k8;
+    }
+    if (cand) (*cand)[4 * p] = (uint16_t)k4, (*cand)[4 * p + 1] = (uint16_t)k8, (*cand)[4 * p + 2] = (uint16_t)l4, (*cand)[4 * p + 3] = (uint16_t)l8;
+    if (best < 4) best = 0, bestd = 0;
+    mlen[p] = (uint8_t)best, mdist[p] = bestd;
+  }
+  for (uint32_t p = 0; p < n;) {
+    const uint32_t L = mlen[p];
+    if (L < 4) {
+      tok.push_back(s[p]);
+      ++p;
+      continue;
+    }
+    const uint32_t next = (p + 1 < n && (p + 1) / ROUND == p / ROUND) ? mlen[p + 1] : 0u;  // (no look beyond the round)
+    if (L < GOOD && next > L) {
+      tok.push_back(s[p]);
+      ++p;
+      continue;
+    }
+    uint32_t full = L;
+    if (L >= GOOD) {
+      const uint32_t lim = std::min<uint32_t>(258, n - p), q = p - mdist[p];
+      while (full < lim && s[q + full] == s[p + full]) ++full;
+    }
+    tok.push_back(0x80000000u | (full << 16) | (mdist[p] - 1));
+    p += full;
+  }
+}
+
 struct Codes {
   uint8_t len[DFL_NLIT + 2];
   uint16_t code[DFL_NLIT + 2];
 };
 
 // lengths (<= maxbits) of the n symbols with frequencies f[]; at least two symbols get a code, as zlib arranges it
-static void build(const uint32_t* f_in, int n, int maxbits, uint8_t* len, uint16_t* code) {
+// (forced: the kernel's df_build_code raises the frequencies themselves, so a symbol that only completes a code counts once in the
+// bits the kernel chooses the block on — the exact mode does the same)
+static void build(uint32_t* f_in, int n, int maxbits, uint8_t* len, uint16_t* code, bool forced = false) {
   std::vector<uint32_t> f(f_in, f_in + n);
   int nz = 0;
   for (int s = 0; s < n; ++s) nz += f[s] != 0;
   for (int s = 0; nz < 2 && s < n; ++s)
     if (f[s] == 0) f[s] = 1, ++nz;
+  if (forced) std::copy(f.begin(), f.end(), f_in);
   std::vector<uint32_t> key;
   for (int s = 0; s < n; ++s)
     if (f[s]) key.push_back(f[s] << 9 | (uint32_t)s);   // (f < 2^17 in a 64 KiB member)
@@ -128,7 +209,8 @@ static void build(const uint32_t* f_in, int n, int maxbits, uint8_t* len, uint16
   dfl_canonical_codes(len, n, maxbits, code, blc);
 }
 
-static void encode(const std::vector<uint32_t>& tok, const uint8_t* s, uint32_t n, BitOut& o) {
+// kernel: the kernel's choice of block (stored when the dynamic block's bits reach 8 n + 32) -> BTYPE; *bits_out: those bits
+static int encode(const std::vector<uint32_t>& tok, const uint8_t* s, uint32_t n, BitOut& o, bool kernel = false, uint64_t* bits_out = nullptr) {
   uint32_t lf[DFL_NLIT + 2] = {0}, df[DFL_NDIST + 2] = {0};
   uint64_t extra = 0;
   for (uint32_t t : tok) {
@@ -146,8 +228,8 @@ static void encode(const std::vector<uint32_t>& tok, const uint8_t* s, uint32_t 
   }
   ++lf[256];
   Codes L, D, C;
-  build(lf, DFL_NLIT, 15, L.len, L.code);
-  build(df, DFL_NDIST, 15, D.len, D.code);
+  build(lf, DFL_NLIT, 15, L.len, L.code, kernel);
+  build(df, DFL_NDIST, 15, D.len, D.code, kernel);
   int hlit = DFL_NLIT, hdist = DFL_NDIST;
   while (hlit > 257 && L.len[hlit - 1] == 0) --hlit;
   while (hdist > 1 && D.len[hdist - 1] == 0) --hdist;
@@ -167,14 +249,15 @@ static void encode(const std::vector<uint32_t>& tok, const uint8_t* s, uint32_t 
   }
   for (int sy = 0; sy < DFL_NLIT; ++sy) dyn_bits += (uint64_t)lf[sy] * L.len[sy];
   for (int sy = 0; sy < DFL_NDIST; ++sy) dyn_bits += (uint64_t)df[sy] * D.len[sy];
-  if (dyn_bits > (uint64_t)n * 8 + 40) {  // stored
+  if (bits_out) *bits_out = dyn_bits;
+  if (kernel ? dyn_bits >= (uint64_t)n * 8 + 32 : dyn_bits > (uint64_t)n * 8 + 40) {  // stored
     o.put(1, 1);
     o.put(0, 2);
     o.flush();
     o.put(n & 0xFFFF, 16);
     o.put(~n & 0xFFFF, 16);
     for (uint32_t i = 0; i < n; ++i) o.put(s[i], 8);
-    return;
+    return 0;
   }
   o.put(1, 1);
   o.put(2, 2);
@@ -202,6 +285,67 @@ static void encode(const std::vector<uint32_t>& tok, const uint8_t* s, uint32_t 
   }
   o.put(L.code[256], L.len[256]);
   o.flush();
+  return 2;
+}
+
+static bool inflates_to(const std::vector<uint8_t>& z_in, const uint8_t* s, uint32_t n) {
+  std::vector<uint8_t> back(n + 16);
+  z_stream z;
+  memset(&z, 0, sizeof(z));
+  inflateInit2(&z, -15);
+  z.next_in = const_cast<uint8_t*>(z_in.data()), z.avail_in = (uInt)z_in.size(), z.next_out = back.data(), z.avail_out = (uInt)back.size();
+  const int rc = inflate(&z, Z_FINISH);
+  const bool ok = rc == Z_STREAM_END && z.total_out == n && z.avail_in == 0 && memcmp(back.data(), s, n) == 0;
+  inflateEnd(&z);
+  return ok;
+}
+
+static bool read_file(const char* path, std::vector<uint8_t>& d) {
+  FILE* f = fopen(path, "rb");
+  if (!f) return false;
+  uint8_t buf[1 << 16];
+  size_t r;
+  while ((r = fread(buf, 1, sizeof(buf), f)) > 0) d.insert(d.end(), buf, buf + r);
+  fclose(f);
+  return true;
+}
+
+// the exact mode: see the header
+static int tokens_mode(const char* payload_path, const char* cuts_path, const char* out_path, bool with_candidates) {
+  std::vector<uint8_t> d, cb;
+  if (!read_file(payload_path, d) || !read_file(cuts_path, cb) || cb.size() < 16 || cb.size() % 8) return 2;
+  const size_t nmem = cb.size() / 8 - 1;
+  std::vector<uint64_t> cuts(nmem + 1);
+  memcpy(cuts.data(), cb.data(), cb.size());
+  FILE* f = fopen(out_path, "wb");
+  if (!f) return 2;
+  auto w32 = [&](uint32_t v) { fwrite(&v, 4, 1, f); };
+  fwrite("DFTK", 1, 4, f);
+  w32((uint32_t)nmem);
+  for (size_t m = 0; m < nmem; ++m) {
+    if (cuts[m + 1] < cuts[m] || cuts[m + 1] > d.size() || cuts[m + 1] - cuts[m] > 0xff00) return fprintf(stderr, "member %zu: bad cuts\n", m), fclose(f), 2;
+    const uint32_t n = (uint32_t)(cuts[m + 1] - cuts[m]);
+    const uint8_t* s = d.data() + cuts[m];
+    std::vector<uint32_t> tok;
+    std::vector<uint16_t> cand;
+    if (with_candidates) {
+      cand.assign((size_t)4 * n, 0);
+      for (uint32_t p = 0; p < n; ++p) cand[4 * p] = cand[4 * p + 1] = 0xFFFF;
+    }
+    BitOut o;
+    int btype = 0;
+    uint64_t bits = 0;
+    if (n) {  // (a member of no bytes: the kernel writes nothing)
+      parse_kernel(s, n, tok, with_candidates ? &cand : nullptr);
+      btype = encode(tok, s, n, o, true, &bits);
+      if (!inflates_to(o.b, s, n)) return fprintf(stderr, "member %zu: zlib does not give the payload back\n", m), fclose(f), 1;
+    }
+    w32(n), w32((uint32_t)btype), w32((uint32_t)tok.size()), w32((uint32_t)o.b.size()), w32((uint32_t)bits);
+    if (!tok.empty()) fwrite(tok.data(), 4, tok.size(), f);
+    if (!o.b.empty()) fwrite(o.b.data(), 1, o.b.size(), f);
+    if (!cand.empty()) fwrite(cand.data(), 2, cand.size(), f);
+  }
+  return fclose(f) == 0 ? 0 : 2;
 }
 
 static size_t zsize(const uint8_t* s, uint32_t n, int level) {
@@ -299,6 +443,8 @@ static int selftest() {
 
 int main(int argc, char** argv) {
   if (argc >= 2 && strcmp(argv[1], "selftest") == 0) return selftest();
+  if (argc == 5 && strcmp(argv[1], "tokens") == 0) return tokens_mode(argv[2], argv[3], argv[4], false);
+  if (argc == 5 && strcmp(argv[1], "candidates") == 0) return tokens_mode(argv[2], argv[3], argv[4], true);
   if (argc < 2) return 2;
   Params P;
   if (argc > 2) P.hbits = atoi(argv[2]);
