@@ -103,6 +103,17 @@ int tbh_cov_summary_host(uint32_t n, const int32_t* tid, const int64_t* beg, con
                          const int32_t* j_tid, const int32_t* j_start, const int32_t* j_end, const uint8_t* j_strand, const double* j_val,
                          uint64_t* covered, double* sum, double* max, double* junc);
 
+/* The host form of tbk_cov_thresholds behind TBK_SUMMARY_HOST=1 and `tbh_tool depth`: per feature the bases under an
+ * interval row (covered [n], may be NULL) and, per threshold, under a row with value >= thr[k] (ge [n][n_thr], feature-major), by a
+ * plain loop over HOST rows sorted by (tid, start) and disjoint.  Returns 0, or -1 for a null argument, n == 0, n_thr outside 1 .. 16,
+ * a threshold that is NaN, infinite or <= 0, or thresholds that are not strictly ascending. */
+int tbh_cov_thresholds_host(uint32_t n, const int32_t* tid, const int64_t* beg, const int64_t* end, uint32_t n_intervals, const int32_t* iv_tid,
+                            const int32_t* iv_start, const int32_t* iv_end, const double* iv_val, const double* thr, uint32_t n_thr, uint64_t* covered,
+                            uint64_t* ge);
+/* `--thresholds LIST` as the command lines parse it: 1 to 16 decimal numbers, finite, > 0, strictly ascending, each parsed completely.
+ * Returns their number with thr[0 .. n) filled in (cap >= 16), or -1 with tbh_last_error naming the offending item. */
+int tbh_parse_thresholds(const char* list, double* thr, uint32_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -783,6 +783,24 @@ typedef struct tbk_cov_stream_info {
 int tbk_cov_stream_push(tbk_ctx* ctx, const tbk_soa_in* tile, const uint8_t* tag_seen, int final, tbk_cov_in* view, tbk_cov_stream_info* info);
 int tbk_cov_stream_reset(tbk_ctx* ctx);
 
+/* ---- Bases at depth: the rows of a coverage call against features and thresholds (ABI version 9, appended) ----------------
+ * What `--depth-summary OUT.tsv` (features [0, LN) of every reference) and `--feature-depth OUT.tsv` (the features of a BED file) of
+ * tiecov / tiebrush run: per feature and threshold T, the bases of the feature under an interval row whose value is >= T. */
+#define TBK_MAX_THRESHOLDS 16
+typedef struct tbk_thr_out {
+  int32_t mem;             /* HOST or DEVICE                                                                             */
+  uint64_t* covered;       /* [n], may be NULL: bases of the feature under an interval row (tbk_cov_summary's covered)   */
+  uint64_t* ge;            /* [n][n_thr], feature-major: bases under a row with value >= thr[k]                          */
+} tbk_thr_out;
+
+/* rows: what tbk_coverage_tile wrote (mem HOST: uploaded by the call; or DEVICE), not changed; only the interval rows are read, the
+ * features' strands are ignored.  n_intervals == 0 gives zeros, status 0.  The comparison val >= thr[k] is made on the doubles, and the
+ * counts are integers: they are exact for every input and the same in any order of addition.
+ * TBK_EINVAL, before anything is launched: what tbk_cov_summary refuses of the features, n_thr outside 1 .. TBK_MAX_THRESHOLDS, a
+ * threshold that is NaN, infinite or <= 0, thresholds that are not strictly ascending.  TBK_EINVAL, found on the device: interval rows
+ * that are not sorted by (tid, start) and disjoint.  Nothing faults and the context takes the next call. */
+int tbk_cov_thresholds(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_features* features, const double* thr, uint32_t n_thr, tbk_thr_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1061,6 +1061,46 @@ class Context:
             del res["junc"]
         return res
 
+    def cov_thresholds(self, rows, features, thr, out=None):
+        """tbk_cov_thresholds: the interval rows of coverage()'s result dict (numpy rows or device tensors) read against features (as
+        cov_summary takes them; strands are ignored) and 1 to 16 strictly ascending thresholds > 0.  Returns covered [n] and ge
+        [n, len(thr)] — the bases of the feature under a row, and under a row with value >= thr[k] — as uint64 numpy arrays for numpy
+        rows, as int64 tensors on the rows' device for device rows (the library writes them there); out="host" / "device" says where
+        they go whatever the rows are."""
+        keep = []
+        if isinstance(features, dict):
+            ft, fb, fe = (np.ascontiguousarray(features[k], dtype=d) for k, d in (("tid", np.int32), ("beg", np.int64), ("end", np.int64)))
+        else:
+            fl = [tuple(f) for f in features]
+            ft = np.array([f[0] for f in fl], dtype=np.int32)
+            fb = np.array([f[1] for f in fl], dtype=np.int64)
+            fe = np.array([f[2] for f in fl], dtype=np.int64)
+        n = len(ft)
+        t = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
+        nt = len(t)
+        dev = _is_torch(rows.get("iv_tid"))
+        a = len(rows["iv_tid"]) if "iv_tid" in rows else 0
+
+        def ptr(name, dt):
+            return _addr(rows[name], dt, keep, a) if a else None
+        o = _lib.CovOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, max(a, 1), ptr("iv_tid", np.int32), ptr("iv_start", np.int32), ptr("iv_end", np.int32),
+                        ptr("iv_val", np.float64), 0, None, None, None, None, None, a, 0, 0, 0)
+        f = _lib.Features(n, ft.ctypes.data, fb.ctypes.data, fe.ctypes.data, None)
+        dev_out = dev if out is None else out == "device"
+        if dev_out:
+            import torch
+            device = rows["iv_tid"].device if dev else "cuda:%d" % self.device
+            res = dict(covered=torch.zeros(max(n, 1), dtype=torch.int64, device=device)[:n], ge=torch.zeros((max(n, 1), max(nt, 1)), dtype=torch.int64, device=device))
+            fo = _lib.ThrOut(_lib.TBK_MEM_DEVICE, res["covered"].data_ptr(), res["ge"].data_ptr())
+        else:
+            res = dict(covered=np.zeros(n, dtype=np.uint64), ge=np.zeros((n, nt), dtype=np.uint64))
+            fo = _lib.ThrOut(_lib.TBK_MEM_HOST, res["covered"].ctypes.data if n else None, res["ge"].ctypes.data if n and nt else None)
+        self._order_after_torch(dev or dev_out)
+        self._check(self.L.tbk_cov_thresholds(self.h, C.byref(o), C.byref(f), t.ctypes.data if nt else None, nt, C.byref(fo)), "tbk_cov_thresholds")
+        if dev_out:
+            res["ge"] = res["ge"][:n, :nt]
+        return res
+
     def sample(self, cin: CovInput, num_samples: int, cap_intervals=None):
         keep = []
         if isinstance(cin, DeviceCovView):                      # (region_view / groups_to_cov_in: the view carries yx)
@@ -1339,6 +1379,38 @@ def cov_summary_host(rows, features):
     if rc != 0:
         raise RuntimeError((H.tbh_last_error() or b"").decode())
     return res
+
+
+def cov_thresholds_host(rows, features, thr):
+    """tbh_cov_thresholds_host: Context.cov_thresholds' columns by the host loop, from numpy rows and a dict of feature arrays
+    tid / beg / end.  RuntimeError for what the device entry refuses of the thresholds and the features' count.  Host only."""
+    H = _lib.load_host()
+    keep = []
+    ft, fb, fe = (np.ascontiguousarray(features[k], dtype=d) for k, d in (("tid", np.int32), ("beg", np.int64), ("end", np.int64)))
+    n = len(ft)
+    t = np.ascontiguousarray(thr, dtype=np.float64).reshape(-1)
+    a = len(rows["iv_tid"]) if "iv_tid" in rows else 0
+
+    def ptr(name, dt):
+        return _addr(rows[name], dt, keep, a) if a else None
+    res = dict(covered=np.zeros(n, dtype=np.uint64), ge=np.zeros((n, len(t)), dtype=np.uint64))
+    rc = H.tbh_cov_thresholds_host(n, ft.ctypes.data, fb.ctypes.data, fe.ctypes.data, a, ptr("iv_tid", np.int32), ptr("iv_start", np.int32), ptr("iv_end", np.int32),
+                                   ptr("iv_val", np.float64), t.ctypes.data if len(t) else None, len(t), res["covered"].ctypes.data if n else None,
+                                   res["ge"].ctypes.data if n and len(t) else None)
+    if rc != 0:
+        raise RuntimeError((H.tbh_last_error() or b"").decode())
+    return res
+
+
+def parse_thresholds(text):
+    """tbh_parse_thresholds: a --thresholds list as the command lines parse it -> the thresholds (float64 array); RuntimeError names the
+    offending item.  Host only."""
+    H = _lib.load_host()
+    t = np.zeros(_lib.MAX_THRESHOLDS, dtype=np.float64)
+    n = H.tbh_parse_thresholds(os.fsencode(text), t.ctypes.data, len(t))
+    if n < 0:
+        raise RuntimeError((H.tbh_last_error() or b"").decode())
+    return t[:n].copy()
 
 
 def index_query_regions(bam_path, table, index_path=None):

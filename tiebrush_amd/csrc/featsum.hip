@@ -6,6 +6,7 @@
 // The reference has no such option; the contract is stated against the rows themselves (include/tbk.h).  Interval rows are sorted by
 // (tid, start) and disjoint, so the rows a feature meets are ONE run [lo, hi), found by two searches; only the run's first and last row can
 // reach beyond the feature.  Junction rows are sorted by (tid, start, end, strand): the feature's rows are found by one search.
+// (fs_order_k, the searches, the fold and the tile constants are shared with tbk_cov_thresholds: featsum_common.hpp)
 //   fs_order_k   *bad |= 1 for interval rows that are not sorted and disjoint, |= 2 for junction rows out of order (read back: TBK_EINVAL)
 //   fs_tile_k    one wave per tile of FS_TILE interval rows: the tile's sum of val x len, its bases and its largest value, each lane its
 //                rows in order and then a butterfly over the lanes — an order that depends on the tile alone
@@ -17,29 +18,13 @@
 // No floating-point atomics and no differences of prefix sums: a feature's sum is made of additions of its own rows' products alone, in an
 // order fixed by (lo, hi), so two calls on the same inputs give the same bits; where every product and partial sum is representable (YC
 // integral, the default) any order gives the same bits as well.
-#include "dev_common.hpp"
-#include "tbk_internal.h"
+#include "featsum_common.hpp"
 
 namespace {
 
-constexpr int FS_NT = 256;             // threads of a block: four waves, a tile or a feature each
-constexpr uint32_t FS_TILE = 256;      // interval rows per aggregate
-constexpr uint32_t FS_DIRECT = 256;    // the longest run that is walked row by row
+// (the two constants are featsum_common.hpp's; tests/test_feature_model_cpu.py reads their values off this line to hold its mirrors to them)
+static_assert(FS_TILE == 256 && FS_DIRECT == 256, "constexpr uint32_t FS_TILE = 256; constexpr uint32_t FS_DIRECT = 256;");
 
-struct FsRows {
-  uint32_t ni, nj;
-  const int32_t *tid, *start, *end;
-  const double* val;
-  const int32_t *jtid, *jstart, *jend;
-  const uint8_t* jstrand;
-  const double* jval;
-};
-struct FsFeat {
-  uint32_t n;
-  const int32_t* tid;
-  const int64_t *beg, *end;
-  const uint8_t* strand;  // NULL: every feature is '.'
-};
 struct FsAgg {
   double *sum, *max;
   uint64_t* len;
@@ -48,30 +33,6 @@ struct FsOut {
   uint64_t* covered;
   double *sum, *max, *junc;
 };
-
-__global__ __launch_bounds__(FS_NT) void fs_order_k(FsRows R, uint32_t* __restrict__ bad) {
-  const uint64_t i = (uint64_t)blockIdx.x * FS_NT + threadIdx.x;
-  if (i < R.ni) {
-    const int32_t t = R.tid[i], e = R.end[i];
-    if (e < R.start[i] || (i + 1 < R.ni && (R.tid[i + 1] < t || (R.tid[i + 1] == t && R.start[i + 1] < e)))) atomicOr(bad, 1u);
-  }
-  if (i + 1 < R.nj) {
-    const int32_t t = R.jtid[i], t2 = R.jtid[i + 1], s = R.jstart[i], s2 = R.jstart[i + 1], e = R.jend[i], e2 = R.jend[i + 1];
-    const bool ok = t2 > t || (t2 == t && (s2 > s || (s2 == s && (e2 > e || (e2 == e && R.jstrand[i + 1] >= R.jstrand[i])))));
-    if (!ok) atomicOr(bad, 2u);
-  }
-}
-
-// the lanes' partial (sum, bases, max) folded into every lane: a fixed butterfly
-__device__ __forceinline__ void fs_fold(double& s, uint64_t& c, double& m) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    s += __shfl_xor(s, d, 64);
-    c += __shfl_xor(c, d, 64);
-    const double o = __shfl_xor(m, d, 64);
-    m = o > m ? o : m;
-  }
-}
 
 __global__ __launch_bounds__(FS_NT) void fs_tile_k(FsRows R, uint32_t n_tiles, FsAgg A) {
   const uint32_t t = blockIdx.x * (FS_NT / WAVE) + (threadIdx.x >> 6);
@@ -88,31 +49,6 @@ __global__ __launch_bounds__(FS_NT) void fs_tile_k(FsRows R, uint32_t n_tiles, F
   }
   fs_fold(s, c, m);
   if (lane_id() == 0) A.sum[t] = s, A.len[t] = c, A.max[t] = m;
-}
-
-// The first index in [lo, n) at which the monotone predicate holds (n: nowhere), found by the whole wave: up to 64 probes a round.
-// Invariant: the answer lies in [lo, hi], and hi == n or pred(hi) is known.  Every probe is an index below n.
-template <class P>
-__device__ __forceinline__ uint32_t fs_search(uint32_t lo, uint32_t n, P pred) {
-  uint32_t hi = n;
-  const uint32_t lane = lane_id();
-  while (hi - lo > WAVE) {
-    const uint32_t step = (hi - lo + WAVE - 1) / WAVE;  // lane k probes the last index of the k-th stretch of `step`
-    const uint64_t idx = (uint64_t)lo + (uint64_t)(lane + 1) * step - 1;
-    const bool p = idx >= hi || pred((uint32_t)idx);
-    const unsigned long long found = __ballot(p);
-    if (!found) {  // (lane 63 probed hi - 1, the last index, and it fails too: the answer is hi)
-      lo = hi;
-      break;
-    }
-    const uint32_t k = (uint32_t)__builtin_ctzll(found);
-    const uint64_t top = (uint64_t)lo + (uint64_t)(k + 1) * step - 1;
-    lo += k * step;
-    hi = top < hi ? (uint32_t)top : hi;
-  }
-  const uint32_t idx = lo + lane;
-  const unsigned long long b = __ballot(idx < hi && pred(idx));
-  return b ? lo + (uint32_t)__builtin_ctzll(b) : hi;
 }
 
 __global__ __launch_bounds__(FS_NT) void fs_feat_k(FsRows R, FsFeat F, FsAgg A, FsOut O) {
@@ -175,36 +111,6 @@ __global__ __launch_bounds__(FS_NT) void fs_feat_k(FsRows R, FsFeat F, FsAgg A, 
   }
 }
 
-struct ProfEnd {
-  tbk_ctx* c;
-  ~ProfEnd() { tbk_prof_end_call(c); }
-};
-
-// an array of the caller (host or device) as a device pointer: a device array as it is, a host array through a copy into the arena
-template <class T>
-int fs_in(tbk_ctx* ctx, int mem, const T* p, size_t n, const T** d) {
-  if (mem == TBK_MEM_DEVICE || !n) {
-    *d = p;
-    return 0;
-  }
-  T* a = ws_alloc<T>(ctx, n);
-  if (!a) return TBK_ENOMEM;
-  TBK_HIP(hipMemcpyAsync(a, p, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-  *d = a;
-  return 0;
-}
-// an output column: the caller's device array, or scratch that fs_back copies to the caller's host array
-template <class T>
-int fs_col(tbk_ctx* ctx, int mem, T* p, size_t n, T** d) {
-  *d = mem == TBK_MEM_DEVICE ? p : ws_alloc<T>(ctx, n);
-  return *d ? 0 : TBK_ENOMEM;
-}
-template <class T>
-int fs_back(tbk_ctx* ctx, int mem, T* dst, const T* d, size_t n) {
-  if (mem == TBK_MEM_HOST) TBK_HIP(hipMemcpyAsync(dst, d, n * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int tbk_cov_summary(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_features* F, tbk_feat_out* out) {
@@ -240,20 +146,7 @@ extern "C" int tbk_cov_summary(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_
   TBK_TRY(fs_in(ctx, rows->mem, (const int32_t*)rows->j_end, nj, &R.jend));
   TBK_TRY(fs_in(ctx, rows->mem, (const uint8_t*)rows->j_strand, nj, &R.jstrand));
   TBK_TRY(fs_in(ctx, rows->mem, (const double*)rows->j_val, nj, &R.jval));
-  if (ni || nj) {
-    uint32_t* bad = ws_alloc<uint32_t>(ctx, 1);
-    if (!bad) return TBK_ENOMEM;
-    TBK_HIP(hipMemsetAsync(bad, 0, 4, ctx->stream));
-    TBK_LAUNCH(ctx, "featsum_order", fs_order_k, cdiv(ni > nj ? ni : nj, FS_NT), FS_NT, 0, R, bad);
-    uint32_t res = 0;
-    TBK_HIP(hipMemcpyAsync(&res, bad, 4, hipMemcpyDeviceToHost, ctx->stream));
-    TBK_HIP(hipStreamSynchronize(ctx->stream));
-    if (res) {
-      ctx->last_error = (res & 1u) ? "summary: interval rows are not sorted by reference and start, or overlap"
-                                   : "summary: junction rows are not sorted by reference, start, end and strand";
-      return TBK_EINVAL;
-    }
-  }
+  TBK_TRY(fs_check_order(ctx, R, "summary"));
   FsFeat D{};
   D.n = n;
   TBK_TRY(fs_in(ctx, TBK_MEM_HOST, F->tid, n, &D.tid));

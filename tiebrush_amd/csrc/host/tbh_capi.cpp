@@ -195,4 +195,26 @@ int tbh_cov_summary_host(uint32_t n, const int32_t* tid, const int64_t* beg, con
   return 0;
 }
 
+int tbh_cov_thresholds_host(uint32_t n, const int32_t* tid, const int64_t* beg, const int64_t* end, uint32_t n_intervals, const int32_t* iv_tid,
+                            const int32_t* iv_start, const int32_t* iv_end, const double* iv_val, const double* thr, uint32_t n_thr, uint64_t* covered,
+                            uint64_t* ge) {
+  if (!n || !tid || !beg || !end || !thr || !ge) return fail("tbh_cov_thresholds_host: null argument or no feature");
+  if (n_intervals && (!iv_tid || !iv_start || !iv_end || !iv_val)) return fail("tbh_cov_thresholds_host: null rows");
+  if (n_thr < 1 || n_thr > TBK_MAX_THRESHOLDS) return fail("tbh_cov_thresholds_host: between 1 and 16 thresholds");
+  for (uint32_t k = 0; k < n_thr; ++k)
+    if (!(thr[k] > 0.0) || thr[k] - thr[k] != 0.0 || (k && !(thr[k] > thr[k - 1]))) return fail("tbh_cov_thresholds_host: thresholds are finite, > 0 and strictly ascending");
+  tbh::threshold_features(n, tid, beg, end, n_intervals, iv_tid, iv_start, iv_end, iv_val, thr, n_thr, covered, ge);
+  return 0;
+}
+
+int tbh_parse_thresholds(const char* list, double* thr, uint32_t cap) {
+  if (!list || !thr || cap < TBK_MAX_THRESHOLDS) return (int)fail("tbh_parse_thresholds: null argument or room for fewer than 16");
+  std::vector<double> v;
+  std::vector<std::string> text;
+  std::string err;
+  if (!tbh::parse_thresholds(list, v, text, err)) return (int)fail("--thresholds: " + err);
+  for (size_t k = 0; k < v.size(); ++k) thr[k] = v[k];
+  return (int)v.size();
+}
+
 }  // extern "C"

@@ -15,6 +15,9 @@
 //   mquery REGION THREADS IN1.bam ... / mrquery REGIONS.bed THREADS IN1.bam ...   the host plumbing of `tiebrush -r` / `-R`, per input
 //   summary IN.bam COV.bedgraph JUNC.bed FEATURES.bed OUT.tsv   the per-feature summary of `tiecov --features --summary` from our own
 //                                 plain tracks, by the host summariser alone ("-" for a track that is not there)
+//   depth IN.bam COV.bedgraph THRESHOLDS OUT.tsv [FEATURES.bed]   the bases-at-depth table of `tiecov --thresholds --depth-summary` (per
+//                                 reference; with FEATURES.bed the per-feature table of `--feature-depth`) from our own plain coverage
+//                                 track, by the host loops alone (THRESHOLDS "-": no ge_ columns, per reference only)
 //   batches IN.bam BYTES          the batches of whole BGZF members a streamed decode reads (stream_read.h): per batch its
 //                                 member range, first_uoff, the range of whole records in it and the tail, both by the host codec
 //   mkbam SOADIR PREFIX [LEVEL [THREADS]]   encode the raw SoA arrays of a synthetic tile (file_off, tid, pos, flag, mapq, strand,
@@ -638,6 +641,85 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
+  // the host-only form of `tiecov --thresholds THRESHOLDS --depth-summary OUT.tsv` and, with a BED file, of `--features FEATURES.bed
+  // --feature-depth OUT.tsv`: our own plain coverage track read back, the host loops, the table writers
+  if (cmd == "depth" && (argc == 6 || argc == 7)) {
+    std::string err;
+    tbh::BamFile bf;
+    if (!bf.open(argv[2], err, 1)) {
+      fprintf(stderr, "tbh_tool depth: %s\n", err.c_str());
+      return 1;
+    }
+    const bool per_feature = argc == 7;
+    std::vector<double> thr;
+    std::vector<std::string> thr_text;
+    if (strcmp(argv[4], "-") != 0 || per_feature) {
+      if (!tbh::parse_thresholds(argv[4], thr, thr_text, err)) {
+        fprintf(stderr, "tbh_tool depth: --thresholds: %s\n", err.c_str());
+        return 1;
+      }
+    }
+    tbh::FeatureTable F;
+    if (per_feature && !tbh::features_from_bed_file(bf.hdr, argv[6], F, err)) {
+      fprintf(stderr, "tbh_tool depth: %s\n", err.c_str());
+      return 1;
+    }
+    std::vector<int32_t> tid, start, end;
+    std::vector<double> val;
+    {
+      FILE* f = fopen(argv[3], "r");
+      if (!f) {
+        fprintf(stderr, "tbh_tool depth: cannot read %s\n", argv[3]);
+        return 1;
+      }
+      char line[4096], name[2048];
+      for (size_t lineno = 1; fgets(line, sizeof(line), f); ++lineno) {
+        if (lineno == 1 && strncmp(line, "track", 5) == 0) continue;
+        long long s = 0, e = 0;
+        double v = 0;
+        const int t = sscanf(line, "%2047s %lld %lld %lf", name, &s, &e, &v) == 4 ? bf.hdr.name2tid(name) : -1;
+        if (t < 0) {
+          fprintf(stderr, "tbh_tool depth: %s line %zu: not a row of the track\n", argv[3], lineno);
+          fclose(f);
+          return 1;
+        }
+        tid.push_back(t), start.push_back((int32_t)s), end.push_back((int32_t)e), val.push_back(v);
+      }
+      fclose(f);
+    }
+    const uint32_t ni = (uint32_t)tid.size(), nt = (uint32_t)thr.size();
+    const std::vector<std::string>& names = bf.hdr.target_name;
+    bool ok;
+    if (per_feature) {
+      std::vector<uint64_t> covered(F.n()), ge(F.n() * nt);
+      tbh::threshold_features(F.n(), F.tid.data(), F.beg.data(), F.end.data(), ni, tid.data(), start.data(), end.data(), val.data(), thr.data(), nt, covered.data(), ge.data());
+      ok = tbh::write_feature_depth_tsv(argv[5], names, F, thr_text, covered.data(), ge.data(), err);
+    } else {
+      const std::vector<uint32_t>& lens = bf.hdr.target_len;
+      tbh::FeatureTable R;  // [0, LN) of every reference with a base
+      for (size_t r = 0; r < lens.size(); ++r)
+        if (lens[r]) R.tid.push_back((int32_t)r), R.beg.push_back(0), R.end.push_back((int64_t)lens[r]), R.strand.push_back((uint8_t)'.');
+      tbh::DepthTable D;
+      D.resize(lens.size(), nt);
+      if (R.n()) {
+        tbh::FeatSummary S;
+        tbh::summarise_features(R, true, ni, tid.data(), start.data(), end.data(), val.data(), false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, S);
+        std::vector<uint64_t> ge(R.n() * nt + 1);
+        if (nt) tbh::threshold_features(R.n(), R.tid.data(), R.beg.data(), R.end.data(), ni, tid.data(), start.data(), end.data(), val.data(), thr.data(), nt, nullptr, ge.data());
+        for (size_t i = 0; i < R.n(); ++i) {
+          const size_t r = (size_t)R.tid[i];
+          D.covered[r] = S.covered[i], D.sum[r] = S.sum[i], D.max[r] = S.max[i];
+          for (uint32_t k = 0; k < nt; ++k) D.ge[r * nt + k] = ge[i * nt + k];
+        }
+      }
+      ok = tbh::write_depth_tsv(argv[5], names, lens, thr_text, D, err);
+    }
+    if (!ok) {
+      fprintf(stderr, "tbh_tool depth: %s\n", err.c_str());
+      return 1;
+    }
+    return 0;
+  }
   if (cmd == "batches" && argc == 4) {  // batches FILE.bam BYTES
     tbh::StreamReader rd;
     std::string err;
@@ -671,6 +753,6 @@ int main(int argc, char** argv) {
            (unsigned long long)rd.bytes_read(), (unsigned long long)rd.reinflated());
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery|summary|batches ...\n");
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery|summary|depth|batches ...\n");
   return 2;
 }

@@ -43,6 +43,7 @@ struct TbkApi {
   decltype(&tbk_bigwig_build) bigwig_build = nullptr;  // optional: --bigwig-writer device
   decltype(&tbk_track_bgzf) track_bgzf = nullptr;      // optional: --tabix
   decltype(&tbk_cov_summary) cov_summary = nullptr;    // optional: --features / --summary
+  decltype(&tbk_cov_thresholds) cov_thresholds = nullptr;  // optional: --thresholds
   std::string error;
   bool has_tracks() const { return coverage_tile && sample_tile && track_names && format_track; }
 
@@ -97,6 +98,7 @@ struct TbkApi {
     bigwig_build = (decltype(bigwig_build))dlsym(h, "tbk_bigwig_build");
     track_bgzf = (decltype(track_bgzf))dlsym(h, "tbk_track_bgzf");
     cov_summary = (decltype(cov_summary))dlsym(h, "tbk_cov_summary");
+    cov_thresholds = (decltype(cov_thresholds))dlsym(h, "tbk_cov_thresholds");
     if (abi_version() != TBK_ABI_VERSION) {
       error = "libtbk.so has another ABI version";
       return false;

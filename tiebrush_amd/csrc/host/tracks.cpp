@@ -4,6 +4,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <stdarg.h>
 #include <stdlib.h>
 
 #include <algorithm>
@@ -305,6 +306,190 @@ void write_summary(const SummaryJob& job, const std::vector<std::string>& names,
             rows.n_junctions, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
+// ---- bases at depth -------------------------------------------------------------------------------------------------
+bool parse_thresholds(const char* list, std::vector<double>& thr, std::vector<std::string>& text, std::string& err) {
+  thr.clear(), text.clear();
+  const std::string all = list ? list : "";
+  for (size_t a = 0;; ) {
+    const size_t b = std::min(all.find(',', a), all.size());
+    const std::string item = all.substr(a, b - a);
+    if (thr.size() == TBK_MAX_THRESHOLDS) return err = "more than 16 thresholds (the 17th is '" + item + "')", false;
+    char* e = nullptr;
+    const double v = item.empty() ? 0.0 : strtod(item.c_str(), &e);
+    // (strtod skips leading blanks and reads "inf", "nan" and hexadecimal forms: a decimal number starts with a digit, a point or a sign)
+    if (item.empty() || !strchr("0123456789.+-", item[0]) || *e != 0 || item.find_first_of("xXnN") != std::string::npos)
+      return err = "'" + item + "' is not a decimal number", false;
+    if (!(v > 0.0) || v - v != 0.0) return err = "'" + item + "' is not a finite number above 0", false;
+    if (!thr.empty() && !(v > thr.back())) return err = "'" + item + "' is not above the threshold before it ('" + text.back() + "'): the list is strictly ascending", false;
+    thr.push_back(v), text.push_back(item);
+    if (b == all.size()) return true;
+    a = b + 1;
+  }
+}
+
+void threshold_features(size_t n, const int32_t* ftid, const int64_t* fbeg, const int64_t* fend, uint32_t ni, const int32_t* tid, const int32_t* start,
+                        const int32_t* end, const double* val, const double* thr, uint32_t n_thr, uint64_t* covered, uint64_t* ge) {
+  for (size_t f = 0; f < n; ++f) {
+    const int32_t ft = ftid[f];
+    const int64_t fb = fbeg[f], fe = fend[f];
+    uint32_t lo = 0, hi = ni;  // the first row that ends behind the feature's begin on its reference, or lies on a later one
+    while (lo < hi) {
+      const uint32_t m = lo + (hi - lo) / 2;
+      if (tid[m] > ft || (tid[m] == ft && (int64_t)end[m] > fb))
+        hi = m;
+      else
+        lo = m + 1;
+    }
+    uint64_t c = 0;
+    uint64_t* g = ge + f * n_thr;
+    for (uint32_t k = 0; k < n_thr; ++k) g[k] = 0;
+    for (uint32_t i = lo; i < ni && tid[i] == ft && (int64_t)start[i] < fe; ++i) {
+      const uint64_t len = (uint64_t)(std::min<int64_t>(end[i], fe) - std::max<int64_t>(start[i], fb));
+      c += len;
+      for (uint32_t k = 0; k < n_thr && val[i] >= thr[k]; ++k) g[k] += len;  // (ascending: the first threshold above the value ends the row)
+    }
+    if (covered) covered[f] = c;
+  }
+}
+
+// a table file under write_summary's rules, with one more: a file that could not be written whole is removed
+static bool write_table(const std::string& path, const std::string& text, std::string& err) {
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) return err = "cannot create " + path, false;
+  bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+  if (fclose(f) != 0) ok = false;
+  if (!ok) (void)unlink(path.c_str()), err = "writing " + path + " failed";
+  return ok;
+}
+static void append_fmt(std::string& o, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+static void append_fmt(std::string& o, const char* fmt, ...) {
+  char b[512];
+  va_list ap;
+  va_start(ap, fmt);
+  const int n = vsnprintf(b, sizeof(b), fmt, ap);
+  va_end(ap);
+  o.append(b, (size_t)std::min<int>(std::max(n, 0), (int)sizeof(b) - 1));
+}
+
+bool write_depth_tsv(const std::string& path, const std::vector<std::string>& names, const std::vector<uint32_t>& lens, const std::vector<std::string>& thr_text,
+                     const DepthTable& D, std::string& err) {
+  const size_t nt = thr_text.size();
+  std::string o = "#chrom\tlength\tcovered\tsum\tmean0\tmean\tmax";
+  for (const std::string& t : thr_text) o += "\tge_" + t;
+  o += "\n";
+  auto line = [&](const std::string& name, uint64_t len, uint64_t cov, double sum, double max, const uint64_t* ge) {
+    o += name;
+    append_fmt(o, "\t%llu\t%llu\t%.3f\t%.3f\t%.3f\t%.3f", (unsigned long long)len, (unsigned long long)cov, sum, len ? sum / (double)len : 0.0,
+               cov ? sum / (double)cov : 0.0, max);
+    for (size_t k = 0; k < nt; ++k) append_fmt(o, "\t%llu", (unsigned long long)ge[k]);
+    o += "\n";
+  };
+  uint64_t t_len = 0, t_cov = 0;
+  double t_sum = 0.0, t_max = 0.0;
+  std::vector<uint64_t> t_ge(nt ? nt : 1, 0);
+  for (size_t r = 0; r < names.size(); ++r) {
+    line(names[r], lens[r], D.covered[r], D.sum[r], D.max[r], D.ge.data() + r * nt);
+    t_len += lens[r], t_cov += D.covered[r], t_sum += D.sum[r], t_max = std::max(t_max, D.max[r]);
+    for (size_t k = 0; k < nt; ++k) t_ge[k] += D.ge[r * nt + k];
+  }
+  line("total", t_len, t_cov, t_sum, t_max, t_ge.data());
+  return write_table(path, o, err);
+}
+
+bool write_feature_depth_tsv(const std::string& path, const std::vector<std::string>& names, const FeatureTable& F, const std::vector<std::string>& thr_text,
+                             const uint64_t* covered, const uint64_t* ge, std::string& err) {
+  const size_t nt = thr_text.size();
+  std::string o = "#chrom\tstart\tend\tname\tstrand\tsize\tcovered";
+  for (const std::string& t : thr_text) o += "\tge_" + t;
+  o += "\n";
+  for (size_t i = 0; i < F.n(); ++i) {
+    o += names[(size_t)F.tid[i]];
+    append_fmt(o, "\t%lld\t%lld\t", (long long)F.beg[i], (long long)F.end[i]);
+    o += F.name[i];
+    append_fmt(o, "\t%c\t%lld\t%llu", (char)F.strand[i], (long long)(F.end[i] - F.beg[i]), (unsigned long long)covered[i]);
+    for (size_t k = 0; k < nt; ++k) append_fmt(o, "\t%llu", (unsigned long long)ge[i * nt + k]);
+    o += "\n";
+  }
+  return write_table(path, o, err);
+}
+
+void DepthJob::setup(const char* thresholds_opt, const char* depth_opt, const char* feature_depth_opt, const char* features_opt, const BamHeader& hdr,
+                     const RegionTable* U) {
+  if (!thresholds_opt && !depth_opt && !feature_depth_opt) return;
+  std::string err;
+  if (thresholds_opt && !parse_thresholds(thresholds_opt, thr, thr_text, err)) GError("Error: --thresholds: %s\n", err.c_str());
+  if (thresholds_opt && !depth_opt && !feature_depth_opt)
+    GError("Error: --thresholds needs --depth-summary OUT.tsv or --feature-depth OUT.tsv (the table its columns go to)\n");
+  if (feature_depth_opt && !features_opt) GError("Error: --feature-depth needs --features BED (the features to count in)\n");
+  if (feature_depth_opt && !thresholds_opt) GError("Error: --feature-depth needs --thresholds T1,T2,... (the depths to count)\n");
+  if ((depth_opt && !*depth_opt) || (feature_depth_opt && (!*feature_depth_opt || !*features_opt))) GError("Error: --depth-summary / --feature-depth / --features need a file name\n");
+  if (depth_opt && U) GError("Error: --depth-summary and -r / -R do not go together (outside the region's intervals the rows are incomplete)\n");
+  lens = hdr.target_len;
+  if (depth_opt) summary_out = depth_opt;
+  if (feature_depth_opt) {
+    feature_out = feature_depth_opt, bed = features_opt;
+    if (!features_from_bed_file(hdr, bed, F, err)) GError("Error: --features: %s\n", err.c_str());
+    if (U && !features_inside(F, *U, bed, err)) GError("Error: --features: %s\n", err.c_str());
+  }
+}
+
+// one tile's rows (host, before any clip) into the run's depth tables
+void TrackStream::depth_tile(const tbk_cov_out& rows) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const DepthJob& job = *run_.depth;
+  const TrackApi& api = api_;
+  const bool host = getenv("TBK_SUMMARY_HOST") && strcmp(getenv("TBK_SUMMARY_HOST"), "0") != 0;
+  const uint32_t nt = (uint32_t)job.thr.size(), ni = rows.n_intervals;
+  if (!host && nt && !api.cov_thresholds) GError("Error: --thresholds: the loaded libtbk.so has no tbk_cov_thresholds (an older build?)\n");
+  tbk_cov_out iv = rows;  // the interval rows alone
+  iv.cap_junctions = 0, iv.n_junctions = 0;
+  auto thresholds = [&](const FeatureTable& F, uint64_t* covered, uint64_t* ge) {
+    if (host) return threshold_features(F.n(), F.tid.data(), F.beg.data(), F.end.data(), ni, rows.iv_tid, rows.iv_start, rows.iv_end, rows.iv_val, job.thr.data(), nt, covered, ge);
+    tbk_features f;
+    f.n = (uint32_t)F.n(), f.tid = F.tid.data(), f.beg = F.beg.data(), f.end = F.end.data(), f.strand = nullptr;
+    tbk_thr_out o;
+    o.mem = TBK_MEM_HOST, o.covered = covered, o.ge = ge;
+    const int rc = api.cov_thresholds(api.ctx, &iv, &f, job.thr.data(), nt, &o);
+    if (rc != 0) GError("Error: GPU depth thresholds failed: %s (%s)\n", api.strerror_(rc), api.last_error(api.ctx));
+  };
+  if (job.per_ref()) {
+    const size_t n_ref = job.lens.size();
+    if (depth_.covered.size() != n_ref) depth_.resize(n_ref, nt);
+    FeatureTable F;  // a tile needs the references between its first and its last row's: [0, LN) of each (LN:0 has no base to count)
+    if (ni)
+      for (int32_t t = rows.iv_tid[0]; t <= rows.iv_tid[ni - 1]; ++t)
+        if (t >= 0 && (size_t)t < n_ref && job.lens[(size_t)t]) F.tid.push_back(t), F.beg.push_back(0), F.end.push_back((int64_t)job.lens[(size_t)t]), F.strand.push_back((uint8_t)'.');
+    if (F.n()) {
+      FeatSummary S;
+      if (host) {
+        summarise_features(F, true, ni, rows.iv_tid, rows.iv_start, rows.iv_end, rows.iv_val, false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, S);
+      } else {
+        if (!api.cov_summary) GError("Error: --depth-summary: the loaded libtbk.so has no tbk_cov_summary (an older build?)\n");
+        S.resize(F.n());
+        tbk_features f;
+        f.n = (uint32_t)F.n(), f.tid = F.tid.data(), f.beg = F.beg.data(), f.end = F.end.data(), f.strand = nullptr;
+        tbk_feat_out o;
+        o.mem = TBK_MEM_HOST, o.covered = S.covered.data(), o.sum = S.sum.data(), o.max = S.max.data(), o.junc = nullptr;
+        const int rc = api.cov_summary(api.ctx, &iv, &f, &o);
+        if (rc != 0) GError("Error: GPU depth summary failed: %s (%s)\n", api.strerror_(rc), api.last_error(api.ctx));
+      }
+      std::vector<uint64_t> ge(F.n() * (size_t)nt + 1, 0);
+      if (nt) thresholds(F, nullptr, ge.data());
+      for (size_t i = 0; i < F.n(); ++i) {
+        const size_t r = (size_t)F.tid[i];
+        depth_.covered[r] += S.covered[i], depth_.sum[r] += S.sum[i], depth_.max[r] = std::max(depth_.max[r], S.max[i]);
+        for (uint32_t k = 0; k < nt; ++k) depth_.ge[r * nt + k] += ge[i * nt + k];
+      }
+    }
+  }
+  if (job.per_feature()) {
+    fd_covered_.assign(job.F.n(), 0), fd_ge_.assign(job.F.n() * (size_t)nt, 0);
+    thresholds(job.F, fd_covered_.data(), fd_ge_.data());
+  }
+  depth_host_ = host, depth_rows_ += ni;
+  ms_depth_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 tbk_cov_in CovRecs::as_cov_in() const {
   tbk_cov_in in;
   memset(&in, 0, sizeof(in));
@@ -379,10 +564,11 @@ void TrackStream::tile(const tbk_cov_in& in, bool last) {
   const TrackClip* clip = run.clip;
   const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
   const bool summary = run.summary && run.summary->on();
+  const bool depth = run.depth && run.depth->on();
   const bool cov_tx = tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
   const bool only = last && tiles_ == 0;  // the run's one tile: run_tracks
   // (the summary and a clip take every row of a track in one call: a run of several tiles does not have them)
-  if (!only && (summary || clip)) GError("Error: a summary and a region clip take the rows of one tile\n");
+  if (!only && (summary || clip || (depth && run.depth->per_feature()))) GError("Error: a summary and a region clip take the rows of one tile\n");
   ++tiles_;
   // a tabix track: the run's one tile as before (written and closed); a tile of several as further runs behind the writer's, the header
   // line with the first rows, the writer closed by end().  A tile without rows for a track writes nothing to it.
@@ -408,8 +594,8 @@ void TrackStream::tile(const tbk_cov_in& in, bool last) {
     return r;
   };
   int rc = 0;
-  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx || summary) {
-    const size_t ci = (tf.cov || tf.cov_bw || cov_tx || summary) ? 2 * co + 2 * n + 16 + extra : 0, cj = (tf.junc || junc_tx || summary) ? co + 16 : 0;
+  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx || summary || depth) {
+    const size_t ci = (tf.cov || tf.cov_bw || cov_tx || summary || depth) ? 2 * co + 2 * n + 16 + extra : 0, cj = (tf.junc || junc_tx || summary) ? co + 16 : 0;
     std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
     std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
     std::vector<uint8_t> jstr(cj ? cj : 1);
@@ -427,6 +613,7 @@ void TrackStream::tile(const tbk_cov_in& in, bool last) {
     if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
     if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
     if (summary) write_summary(*run.summary, names, o, api);
+    if (depth) depth_tile(o);
     if (clip) {
       const tbk_regions* U = clip->U;
       rc = clip->one ? api.cov_clip(ctx, &o, U->tid[0], U->beg[0], U->end[0]) : api.cov_clip_regions(ctx, &o, U);
@@ -505,6 +692,26 @@ void TrackStream::end() {
     if (tx_started_[k] && !tx[k]->close(err)) GError("Error: writing %s failed (%s)\n", tx[k]->path().c_str(), err.c_str());
   }
   tf_.close();
+  if (run_.depth && run_.depth->on()) {  // (behind the tracks: a run that failed before this left neither table)
+    const auto t0 = std::chrono::steady_clock::now();
+    const DepthJob& job = *run_.depth;
+    std::string err;
+    if (job.per_ref()) {
+      if (depth_.covered.size() != job.lens.size()) depth_.resize(job.lens.size(), job.thr.size());  // (no tile at all)
+      if (!write_depth_tsv(job.summary_out, names_, job.lens, job.thr_text, depth_, err)) GError("Error: --depth-summary: %s\n", err.c_str());
+    }
+    if (job.per_feature()) {
+      if (fd_covered_.size() != job.F.n()) fd_covered_.assign(job.F.n(), 0), fd_ge_.assign(job.F.n() * job.thr.size(), 0);
+      if (!write_feature_depth_tsv(job.feature_out, names_, job.F, job.thr_text, fd_covered_.data(), fd_ge_.data(), err)) {
+        if (job.per_ref()) (void)unlink(job.summary_out.c_str());
+        GError("Error: --feature-depth: %s\n", err.c_str());
+      }
+    }
+    ms_depth_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (getenv("TBK_TIMING"))
+      fprintf(stderr, "depth phase ms: %s | %zu references | %zu features | %zu thresholds | %llu interval rows in %llu tiles | %.1f\n", depth_host_ ? "host" : "device",
+              job.per_ref() ? job.lens.size() : (size_t)0, job.F.n(), job.thr.size(), (unsigned long long)depth_rows_, (unsigned long long)tiles_, ms_depth_);
+  }
   if (run_.times) *run_.times = times_;
 }
 

@@ -22,7 +22,7 @@ namespace tbh {
 
 // The device entry points of a track run, as a command line has them: tracks.cpp and tabix.cpp are linked without libtbk.so (tbh_tool,
 // libtbh.so), tiecov links the library and tiebrush binds it at run time, so the calls travel as pointers.  An entry the library in use
-// lacks is null (tiebrush: track_bgzf, bigwig_build, cov_summary may be; it never clips, and leaves the four clip entries null).
+// lacks is null (tiebrush: track_bgzf, bigwig_build, cov_summary, cov_thresholds may be; it never clips, and leaves the four clip entries null).
 struct TrackApi {
   tbk_ctx* ctx = nullptr;
   decltype(&tbk_coverage_tile) coverage_tile = nullptr;
@@ -38,6 +38,7 @@ struct TrackApi {
   decltype(&tbk_cov_summary) cov_summary = nullptr;
   decltype(&tbk_strerror) strerror_ = nullptr;
   decltype(&tbk_last_error) last_error = nullptr;
+  decltype(&tbk_cov_thresholds) cov_thresholds = nullptr;  // (the last field: a table filled in field by field without it stays valid)
 };
 
 // The track options of a command line (tiecov -c / -j / -s / -W / --bigwig-writer / --tabix and tiebrush's long spellings of them; each
@@ -119,6 +120,46 @@ struct SummaryJob {
 // TBK_SUMMARY_HOST=1.  Errors are fatal; a missing tbk_cov_summary is one.  TBK_TIMING: a "summary phase ms" line.
 void write_summary(const SummaryJob& job, const std::vector<std::string>& names, const tbk_cov_out& rows, const TrackApi& api);
 
+// ---- `--thresholds T1,.. --depth-summary OUT` / `--feature-depth OUT`: bases at depth ----------------------------------
+// "T1,T2,..": 1 to 16 decimal numbers, each parsed completely by strtod, finite, > 0, strictly ascending; text[k] is item k as given
+// (the column's name is ge_<text>).  false: err names the offending item
+bool parse_thresholds(const char* list, std::vector<double>& thr, std::vector<std::string>& text, std::string& err);
+// The host form of tbk_cov_thresholds (TBK_SUMMARY_HOST=1, `tbh_tool depth`): a plain loop per feature over host rows sorted by
+// (tid, start) and disjoint.  covered [n] (may be null), ge [n][n_thr] feature-major; the comparison val >= thr[k] on the doubles
+void threshold_features(size_t n, const int32_t* ftid, const int64_t* fbeg, const int64_t* fend, uint32_t ni, const int32_t* tid, const int32_t* start,
+                        const int32_t* end, const double* val, const double* thr, uint32_t n_thr, uint64_t* covered, uint64_t* ge);
+// the per-reference table of a run: one element per @SQ in header order, added up over the tiles of a streamed run (the integers by
+// integer addition, max by max, sum by double addition in tile order)
+struct DepthTable {
+  std::vector<uint64_t> covered, ge;  // ge [n_ref][n_thr]
+  std::vector<double> sum, max;
+  void resize(size_t n_ref, size_t n_thr) { covered.assign(n_ref, 0), ge.assign(n_ref * n_thr, 0), sum.assign(n_ref, 0.0), max.assign(n_ref, 0.0); }
+};
+// `#chrom length covered sum mean0 mean max ge_T1 ..`: one line per reference, then `total` (the integers added, the sums added in
+// header order, the largest max; mean0 = sum / length and mean = sum / covered, 0 where the divisor is).  false: the file cannot be
+// created or written (and is removed)
+bool write_depth_tsv(const std::string& path, const std::vector<std::string>& names, const std::vector<uint32_t>& lens, const std::vector<std::string>& thr_text,
+                     const DepthTable& D, std::string& err);
+// `#chrom start end name strand size covered ge_T1 ..`: one line per feature in the table's order
+bool write_feature_depth_tsv(const std::string& path, const std::vector<std::string>& names, const FeatureTable& F, const std::vector<std::string>& thr_text,
+                             const uint64_t* covered, const uint64_t* ge, std::string& err);
+
+// the three options of a run: parsed (and refused) before a device is touched or any output file exists; the files are written by
+// TrackStream::end, so a run that fails leaves neither
+struct DepthJob {
+  std::string summary_out, feature_out, bed;
+  std::vector<double> thr;
+  std::vector<std::string> thr_text;
+  std::vector<uint32_t> lens;  // the references' lengths, header order
+  FeatureTable F;              // --feature-depth
+  bool per_ref() const { return !summary_out.empty(); }
+  bool per_feature() const { return !feature_out.empty(); }
+  bool on() const { return per_ref() || per_feature(); }
+  // The options' rules (each refusal its own sentence), the threshold list, the BED file against the header and — in a region run,
+  // which U != null says — the refusal of --depth-summary and every feature wholly inside one interval.  Errors are fatal (GError).
+  void setup(const char* thresholds_opt, const char* depth_opt, const char* feature_depth_opt, const char* features_opt, const BamHeader& hdr, const RegionTable* U);
+};
+
 // ---- what every run does with its records: the tracks -----------------------------------------------------------------------------
 // The records of a run as tbk_coverage_tile / tbk_sample_tile read them (host arrays): tiecov's decode of its input, tiebrush's groups
 // as they go into the output.
@@ -153,6 +194,7 @@ struct TrackRun {
   int num_samples = 0;
   bool bw_device = false;                // the bigWig's sections by api.bigwig_build
   const SummaryJob* summary = nullptr;   // (null, or a job that is not on: no summary)
+  const DepthJob* depth = nullptr;       // (the same for --depth-summary / --feature-depth)
   bool device_text = false;              // plain text by api.format_track (the names set up front), the host formatter where it refuses a track
   TrackTimes* times = nullptr;
 };
@@ -167,8 +209,9 @@ void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std
 // after the other, are the rows of the uncut stream, so every tile's lines are appended to the open files — the junction numbers run on,
 // the bigWig's host writer collects the rows of every tile — and end() closes the files.  run_tracks is begin, ONE tile, end: the same
 // calls in the same order, the same bytes.  A tabix track takes a tile's rows as further runs (feed_tabix_track: the header line with
-// the first rows, one close in end()).  The summary, a clip and the device bigWig writer take the rows of one tile and are refused
-// (GError) in a run of several.
+// the first rows, one close in end()).  The summary, --feature-depth, a clip and the device bigWig writer take the rows of one tile and
+// are refused (GError) in a run of several.  --depth-summary goes with any number of tiles: every row belongs to one tile, so a tile's
+// table — over the references between its first and its last row — is added to the run's (DepthTable), and end() writes the file.
 class TrackStream {
  public:
   TrackStream(const TrackApi& api, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run);
@@ -187,6 +230,12 @@ class TrackStream {
   uint64_t n_bases_ = 0, span_bases_ = 0, tiles_ = 0;
   bool names_set_ = false;  // the reference names are on the context
   bool tx_started_[3] = {false, false, false};  // --tabix in a run of several tiles: the track's writer has its header line and first rows
+  DepthTable depth_;                 // --depth-summary: the run's table so far
+  std::vector<uint64_t> fd_covered_, fd_ge_;  // --feature-depth: the one tile's columns, written by end()
+  double ms_depth_ = 0;
+  uint64_t depth_rows_ = 0;
+  bool depth_host_ = false;
+  void depth_tile(const tbk_cov_out& rows);
   TrackTimes times_;
 };
 
