@@ -114,6 +114,29 @@ int tbh_cov_thresholds_host(uint32_t n, const int32_t* tid, const int64_t* beg, 
  * Returns their number with thr[0 .. n) filled in (cap >= 16), or -1 with tbh_last_error naming the offending item. */
 int tbh_parse_thresholds(const char* list, double* thr, uint32_t cap);
 
+/* ---- The annotation of `--gtf FILE --transcripts OUT` (appended; tbh_abi_version stays 1) ----
+ * The GTF file at gtf_path against the header of bam_path: only lines whose third column is `exon` are read (columns 4 and 5 1-based
+ * inclusive, 7 the strand, 9 the attributes: transcript_id required, gene_id optional, default "."); transcripts are numbered by the
+ * first appearance of their transcript_id, a transcript's exons sorted by start.  Returns the number n_tx >= 1 of transcripts and writes
+ * *n_exon; tx_off [n_tx + 1] (CSR into the exon arrays), tid, strand, line (the line of the transcript's first exon line, from 1) are
+ * written when n_tx <= tx_cap, ex_beg / ex_end (0-based half-open) when *n_exon <= ex_cap, the names — per transcript its id and its
+ * gene, each closed by a NUL byte — when they fit names_cap; *names_bytes (optional) = the bytes they need.  Otherwise nothing of that
+ * part is written: call again with room.  -1 on failure (tbh_last_error names the line): an exon line with fewer than nine columns, a
+ * coordinate that is not a number, start < 1, end < start, an end beyond the reference, an unknown chrom, a strand other than + - ., no
+ * transcript_id, a transcript on two chroms or strands, exons of a transcript that overlap or abut, a file without an exon line. */
+int64_t tbh_transcripts_from_gtf(const char* bam_path, const char* gtf_path, uint32_t* tx_off, int32_t* tid, uint8_t* strand, uint64_t* line, uint64_t tx_cap,
+                                 int64_t* ex_beg, int64_t* ex_end, uint64_t ex_cap, uint64_t* n_exon, char* names, uint64_t names_cap, uint64_t* names_bytes);
+
+/* The host summariser behind TBK_SUMMARY_HOST=1 and `tbh_tool transcripts`: tbk_tx_summary's outputs (include/tbk.h) by plain loops over
+ * HOST rows — tbh_cov_summary_host over the exons and the introns, a transcript's parts added in exon order.  The table and the rows as
+ * there; want_cov / want_junc 0: that half is not computed, its rows are not read and its outputs may be NULL.  The four per-exon
+ * arrays are optional.  Returns 0, or -1 for a null argument or a table tbk_tx_summary refuses. */
+int tbh_tx_summary_host(uint32_t n_tx, uint32_t n_exon, const uint32_t* tx_off, const int32_t* tid, const uint8_t* strand, const int64_t* ex_beg,
+                        const int64_t* ex_end, int want_cov, uint32_t n_intervals, const int32_t* iv_tid, const int32_t* iv_start, const int32_t* iv_end,
+                        const double* iv_val, int want_junc, uint32_t n_junctions, const int32_t* j_tid, const int32_t* j_start, const int32_t* j_end,
+                        const uint8_t* j_strand, const double* j_val, uint64_t* covered, double* sum, double* max, uint32_t* exons_hit, uint32_t* introns_hit,
+                        double* junc_min, double* junc_sum, uint64_t* ex_covered, double* ex_sum, double* ex_max, double* in_junc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -801,6 +801,42 @@ typedef struct tbk_thr_out {
  * that are not sorted by (tid, start) and disjoint.  Nothing faults and the context takes the next call. */
 int tbk_cov_thresholds(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_features* features, const double* thr, uint32_t n_thr, tbk_thr_out* out);
 
+/* ---- Per-transcript support: the rows of a coverage call against an annotation (ABI version 9, appended) -----------------
+ * What `--gtf FILE --transcripts OUT.tsv` of tiecov / tiebrush run.  A transcript is a run of exons; the introns are implied between
+ * them: [ex_end[e], ex_beg[e + 1]) behind every exon but the transcript's last. */
+typedef struct tbk_transcripts {        /* HOST arrays */
+  uint32_t n_tx, n_exon;
+  const uint32_t* tx_off;               /* [n_tx + 1], tx_off[0] == 0, strictly ascending, tx_off[n_tx] == n_exon */
+  const int32_t* tid;                   /* [n_tx] */
+  const uint8_t* strand;                /* [n_tx] '+', '-', '.'; NULL = all '.' */
+  const int64_t *ex_beg, *ex_end;       /* [n_exon] 0-based half-open; within a transcript ascending, ex_beg[e+1] > ex_end[e] */
+} tbk_transcripts;
+typedef struct tbk_tx_out {
+  int32_t mem;                          /* HOST or DEVICE */
+  uint64_t* covered; double *sum, *max; uint32_t* exons_hit;         /* [n_tx], from the interval rows */
+  uint32_t* introns_hit; double *junc_min, *junc_sum;                /* [n_tx], from the junction rows */
+  uint64_t* ex_covered; double *ex_sum, *ex_max;                     /* [n_exon], optional (all three or none) */
+  double* in_junc;                      /* [n_exon], optional: the intron BEHIND exon e; 0 for a transcript's last exon */
+} tbk_tx_out;
+
+/* rows: as tbk_cov_summary takes them (HOST: uploaded by the call; or DEVICE; not changed; cap_intervals == 0 leaves the columns of the
+ * interval rows out — covered, sum, max, exons_hit, ex_* — and their pointers may be NULL; cap_junctions == 0 the same for introns_hit,
+ * junc_min, junc_sum, in_junc; no rows give zeros, status 0).
+ * Per exon: tbk_cov_summary's covered, sum, max of [ex_beg, ex_end) on the transcript's tid.  Per intron: tbk_cov_summary's junc of the
+ * intron under the transcript's strand ('.' takes every strand).  Per transcript: covered and sum add its exons', max is the largest of
+ * its covered exons' max (0 when nothing is covered), exons_hit counts the exons with covered > 0, introns_hit the introns with
+ * junc > 0, junc_min is the smallest junc over its introns (0 for a single-exon transcript), junc_sum their sum.
+ * covered, max, exons_hit, introns_hit, in_junc and junc_min are exact.  sum adds one rounded product per row piece in an order fixed by
+ * the inputs (the parts of a transcript in an order that depends on its exon count alone): |sum - S| <= gamma(m + 1) * SUM |val * bases|
+ * for m row pieces, junc_sum the same over its at most 3 * introns rows; both are exact where every row value is a multiple of 2^-3 and
+ * the sums stay below 2^50 (integral YC: every default run).  Two calls on the same inputs give the same bits.  The optional per-exon
+ * columns are, bit for bit, tbk_cov_summary's columns for the exons given as features, in_junc its junc for the introns.
+ * TBK_EINVAL, before anything is launched: n_tx == 0; tx_off[0] != 0, a transcript without an exon, tx_off[n_tx] != n_exon; a tid < 0, an
+ * ex_beg < 0, an ex_end <= ex_beg; exons of a transcript that are out of order, overlap or abut; a strand byte other than + - .; only
+ * some of ex_covered / ex_sum / ex_max.  TBK_EINVAL, found on the device: what tbk_cov_summary refuses of the rows.  Nothing faults and
+ * the context takes the next call. */
+int tbk_tx_summary(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_transcripts* transcripts, tbk_tx_out* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
            "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route",
            "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build", "tbk_track_bgzf", "tbk_cov_summary",
-           "tbk_cov_stream_push", "tbk_cov_stream_reset", "tbk_bam_decode_open", "tbk_cov_thresholds"]
+           "tbk_cov_stream_push", "tbk_cov_stream_reset", "tbk_bam_decode_open", "tbk_cov_thresholds", "tbk_tx_summary"]
 
 
 class CollapseOpts(C.Structure):
@@ -120,6 +120,15 @@ class FeatOut(C.Structure):
 
 class ThrOut(C.Structure):
     _fields_ = [("mem", C.c_int32), ("covered", _P), ("ge", _P)]
+
+
+class Transcripts(C.Structure):
+    _fields_ = [("n_tx", C.c_uint32), ("n_exon", C.c_uint32), ("tx_off", _P), ("tid", _P), ("strand", _P), ("ex_beg", _P), ("ex_end", _P)]
+
+
+class TxOut(C.Structure):
+    _fields_ = [("mem", C.c_int32), ("covered", _P), ("sum", _P), ("max", _P), ("exons_hit", _P), ("introns_hit", _P), ("junc_min", _P), ("junc_sum", _P),
+                ("ex_covered", _P), ("ex_sum", _P), ("ex_max", _P), ("in_junc", _P)]
 
 
 MAX_THRESHOLDS = 16   # TBK_MAX_THRESHOLDS
@@ -278,6 +287,8 @@ def load():
     L.tbk_cov_summary.restype = C.c_int
     L.tbk_cov_thresholds.argtypes = [_P, C.POINTER(CovOut), C.POINTER(Features), _P, C.c_uint32, C.POINTER(ThrOut)]
     L.tbk_cov_thresholds.restype = C.c_int
+    L.tbk_tx_summary.argtypes = [_P, C.POINTER(CovOut), C.POINTER(Transcripts), C.POINTER(TxOut)]
+    L.tbk_tx_summary.restype = C.c_int
     L.tbk_cov_stream_push.argtypes = [_P, C.POINTER(SoaIn), _P, C.c_int, C.POINTER(CovIn), C.POINTER(CovStreamInfo)]
     L.tbk_cov_stream_push.restype = C.c_int
     L.tbk_cov_stream_reset.argtypes = [_P]
@@ -293,7 +304,7 @@ HOST_LIB_PATH = os.environ.get("TBK_HOST_LIB") or os.path.join(_HERE, "_build", 
 HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin",
                 "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin", "tbh_index_query",
                 "tbh_regions_from_bed", "tbh_index_query_regions", "tbh_features_from_bed", "tbh_cov_summary_host",
-                "tbh_cov_thresholds_host", "tbh_parse_thresholds"]   # include/tbh_host.h
+                "tbh_cov_thresholds_host", "tbh_parse_thresholds", "tbh_transcripts_from_gtf", "tbh_tx_summary_host"]   # include/tbh_host.h
 _host = None
 
 
@@ -338,6 +349,10 @@ def load_host():
     H.tbh_cov_thresholds_host.restype = C.c_int
     H.tbh_parse_thresholds.argtypes = [C.c_char_p, _P, C.c_uint32]
     H.tbh_parse_thresholds.restype = C.c_int
+    H.tbh_transcripts_from_gtf.argtypes = [C.c_char_p, C.c_char_p, _P, _P, _P, _P, C.c_uint64, _P, _P, C.c_uint64, C.POINTER(C.c_uint64), _P, C.c_uint64, C.POINTER(C.c_uint64)]
+    H.tbh_transcripts_from_gtf.restype = C.c_int64
+    H.tbh_tx_summary_host.argtypes = [C.c_uint32, C.c_uint32] + [_P] * 5 + [C.c_int, C.c_uint32] + [_P] * 4 + [C.c_int, C.c_uint32] + [_P] * 5 + [_P] * 11
+    H.tbh_tx_summary_host.restype = C.c_int
     _host = H
     return H
 

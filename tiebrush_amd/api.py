@@ -1101,6 +1101,44 @@ class Context:
             res["ge"] = res["ge"][:n, :nt]
         return res
 
+    def tx_summary(self, rows, tx, parts=False):
+        """tbk_tx_summary: the result dict of coverage() (numpy rows or device tensors; a dict without iv_* / j_* rows leaves those
+        columns out) read against transcripts: a dict of arrays tx_off [n_tx + 1] (CSR into the exons), tid [n_tx], ex_beg / ex_end
+        [n_exon] and optionally strand [n_tx] ('+', '-', '.'), as transcripts_from_gtf returns it.  Returns numpy arrays, one element
+        per transcript: covered (uint64), sum, max, exons_hit (uint32), introns_hit (uint32), junc_min, junc_sum.  parts=True adds the
+        per-exon ex_covered, ex_sum, ex_max and in_junc (the intron behind the exon; 0 for a transcript's last); a tuple of those
+        names asks for just them."""
+        keep = []
+        off = np.ascontiguousarray(tx["tx_off"], dtype=np.uint32)
+        tt = np.ascontiguousarray(tx["tid"], dtype=np.int32)
+        eb, ee = np.ascontiguousarray(tx["ex_beg"], dtype=np.int64), np.ascontiguousarray(tx["ex_end"], dtype=np.int64)
+        ts = np.ascontiguousarray(tx["strand"], dtype=np.uint8) if tx.get("strand") is not None else None
+        n_tx, n_ex = len(tt), len(eb)
+        want_cov, want_junc = "iv_tid" in rows, "j_tid" in rows
+        dev = any(_is_torch(rows.get(k)) for k in ("iv_tid", "j_tid"))
+        a, b = (len(rows["iv_tid"]) if want_cov else 0), (len(rows["j_tid"]) if want_junc else 0)
+
+        def ptr(name, dt, cnt):
+            return _addr(rows[name], dt, keep, cnt) if cnt else None
+        # (a capacity of zero says "not computed": rows of a wanted but empty track keep a capacity of one)
+        o = _lib.CovOut(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, max(a, 1) if want_cov else 0, ptr("iv_tid", np.int32, a), ptr("iv_start", np.int32, a),
+                        ptr("iv_end", np.int32, a), ptr("iv_val", np.float64, a), max(b, 1) if want_junc else 0, ptr("j_tid", np.int32, b),
+                        ptr("j_start", np.int32, b), ptr("j_end", np.int32, b), ptr("j_strand", np.uint8, b), ptr("j_val", np.float64, b), a, b, 0, 0)
+        x = _lib.Transcripts(n_tx, n_ex, off.ctypes.data if len(off) else None, tt.ctypes.data if n_tx else None, ts.ctypes.data if ts is not None else None,
+                             eb.ctypes.data if n_ex else None, ee.ctypes.data if n_ex else None)
+        cov_cols, junc_cols = ("covered", "sum", "max", "exons_hit"), ("introns_hit", "junc_min", "junc_sum")
+        ex_cols = ("ex_covered", "ex_sum", "ex_max", "in_junc")
+        asked = ex_cols if parts is True else tuple(parts or ())
+        dts = dict(covered=np.uint64, exons_hit=np.uint32, introns_hit=np.uint32, ex_covered=np.uint64)
+        res = {k: np.zeros(n_tx, dtype=dts.get(k, np.float64)) for k in cov_cols + junc_cols}
+        res.update({k: np.zeros(n_ex, dtype=dts.get(k, np.float64)) for k in asked})
+        xo = _lib.TxOut(_lib.TBK_MEM_HOST, *((res[k].ctypes.data if k in res and len(res[k]) else None) for k in cov_cols + junc_cols + ex_cols))
+        self._order_after_torch(dev)
+        self._check(self.L.tbk_tx_summary(self.h, C.byref(o), C.byref(x), C.byref(xo)), "tbk_tx_summary")
+        for k in (() if want_cov else cov_cols + ex_cols[:3]) + (() if want_junc else junc_cols + ex_cols[3:]):
+            res.pop(k, None)
+        return res
+
     def sample(self, cin: CovInput, num_samples: int, cap_intervals=None):
         keep = []
         if isinstance(cin, DeviceCovView):                      # (region_view / groups_to_cov_in: the view carries yx)
@@ -1411,6 +1449,61 @@ def parse_thresholds(text):
     if n < 0:
         raise RuntimeError((H.tbh_last_error() or b"").decode())
     return t[:n].copy()
+
+
+def transcripts_from_gtf(bam_path, gtf_path):
+    """tbh_transcripts_from_gtf: the exon lines of the GTF file against the header of bam_path as a transcript table: a dict of numpy
+    arrays tx_off (uint32, [n_tx + 1], CSR into the exons), tid (int32), strand (uint8), line (uint64: the line of the transcript's
+    first exon line, from 1), ex_beg / ex_end (int64, 0-based half-open, ascending within a transcript) and the lists id and gene.
+    Transcripts come in the order of their first appearance.  RuntimeError (with the line number) for what the parser refuses.  Host
+    only."""
+    H = _lib.load_host()
+    tcap, ecap, ncap = 64, 256, 4096
+    while True:
+        off, t = np.zeros(tcap + 1, dtype=np.uint32), np.zeros(tcap, dtype=np.int32)
+        s, ln = np.zeros(tcap, dtype=np.uint8), np.zeros(tcap, dtype=np.uint64)
+        eb, ee = np.zeros(ecap, dtype=np.int64), np.zeros(ecap, dtype=np.int64)
+        names, nb, ne = C.create_string_buffer(ncap), C.c_uint64(0), C.c_uint64(0)
+        n = H.tbh_transcripts_from_gtf(os.fsencode(bam_path), os.fsencode(gtf_path), off.ctypes.data, t.ctypes.data, s.ctypes.data, ln.ctypes.data, tcap,
+                                       eb.ctypes.data, ee.ctypes.data, ecap, C.byref(ne), C.cast(names, C.c_void_p), ncap, C.byref(nb))
+        if n < 0:
+            raise RuntimeError((H.tbh_last_error() or b"").decode())
+        if n <= tcap and ne.value <= ecap and nb.value <= ncap:
+            both = [x.decode() for x in names.raw[:nb.value].split(b"\0")[:2 * n]]
+            m = int(ne.value)
+            return dict(tx_off=off[:n + 1].copy(), tid=t[:n].copy(), strand=s[:n].copy(), line=ln[:n].copy(), ex_beg=eb[:m].copy(), ex_end=ee[:m].copy(),
+                        id=both[0::2], gene=both[1::2])
+        tcap, ecap, ncap = max(tcap, int(n)), max(ecap, int(ne.value)), max(ncap, int(nb.value))
+
+
+def tx_summary_host(rows, tx):
+    """tbh_tx_summary_host: Context.tx_summary's columns (the per-exon ones included) by the host summariser (plain loops, a
+    transcript's parts added in exon order) from numpy rows and a transcript table as Context.tx_summary takes it.  Host only."""
+    H = _lib.load_host()
+    keep = []
+    off = np.ascontiguousarray(tx["tx_off"], dtype=np.uint32)
+    tt = np.ascontiguousarray(tx["tid"], dtype=np.int32)
+    eb, ee = np.ascontiguousarray(tx["ex_beg"], dtype=np.int64), np.ascontiguousarray(tx["ex_end"], dtype=np.int64)
+    ts = np.ascontiguousarray(tx["strand"], dtype=np.uint8) if tx.get("strand") is not None else None
+    n_tx, n_ex = len(tt), len(eb)
+    want_cov, want_junc = "iv_tid" in rows, "j_tid" in rows
+    a, b = (len(rows["iv_tid"]) if want_cov else 0), (len(rows["j_tid"]) if want_junc else 0)
+
+    def ptr(name, dt, cnt):
+        return _addr(rows[name], dt, keep, cnt) if cnt else None
+    cols = ("covered", "sum", "max", "exons_hit", "introns_hit", "junc_min", "junc_sum", "ex_covered", "ex_sum", "ex_max", "in_junc")
+    dts = dict(covered=np.uint64, exons_hit=np.uint32, introns_hit=np.uint32, ex_covered=np.uint64)
+    res = {k: np.zeros(n_ex if k in cols[7:] else n_tx, dtype=dts.get(k, np.float64)) for k in cols}
+    rc = H.tbh_tx_summary_host(n_tx, n_ex, off.ctypes.data if len(off) else None, tt.ctypes.data if n_tx else None, ts.ctypes.data if ts is not None else None,
+                               eb.ctypes.data if n_ex else None, ee.ctypes.data if n_ex else None, int(want_cov), a, ptr("iv_tid", np.int32, a),
+                               ptr("iv_start", np.int32, a), ptr("iv_end", np.int32, a), ptr("iv_val", np.float64, a), int(want_junc), b, ptr("j_tid", np.int32, b),
+                               ptr("j_start", np.int32, b), ptr("j_end", np.int32, b), ptr("j_strand", np.uint8, b), ptr("j_val", np.float64, b),
+                               *(res[k].ctypes.data if len(res[k]) else None for k in cols))
+    if rc != 0:
+        raise RuntimeError((H.tbh_last_error() or b"").decode())
+    for k in (() if want_cov else cols[:4] + cols[7:10]) + (() if want_junc else cols[4:7] + cols[10:]):
+        del res[k]
+    return res
 
 
 def index_query_regions(bam_path, table, index_path=None):

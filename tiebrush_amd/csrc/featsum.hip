@@ -6,7 +6,8 @@
 // The reference has no such option; the contract is stated against the rows themselves (include/tbk.h).  Interval rows are sorted by
 // (tid, start) and disjoint, so the rows a feature meets are ONE run [lo, hi), found by two searches; only the run's first and last row can
 // reach beyond the feature.  Junction rows are sorted by (tid, start, end, strand): the feature's rows are found by one search.
-// (fs_order_k, the searches, the fold and the tile constants are shared with tbk_cov_thresholds: featsum_common.hpp)
+// (fs_order_k, the searches, the fold and the tile constants are shared with tbk_cov_thresholds, the run walk and the junction lookup of
+// fs_feat_k with tbk_tx_summary: featsum_common.hpp)
 //   fs_order_k   *bad |= 1 for interval rows that are not sorted and disjoint, |= 2 for junction rows out of order (read back: TBK_EINVAL)
 //   fs_tile_k    one wave per tile of FS_TILE interval rows: the tile's sum of val x len, its bases and its largest value, each lane its
 //                rows in order and then a butterfly over the lanes — an order that depends on the tile alone
@@ -25,31 +26,10 @@ namespace {
 // (the two constants are featsum_common.hpp's; tests/test_feature_model_cpu.py reads their values off this line to hold its mirrors to them)
 static_assert(FS_TILE == 256 && FS_DIRECT == 256, "constexpr uint32_t FS_TILE = 256; constexpr uint32_t FS_DIRECT = 256;");
 
-struct FsAgg {
-  double *sum, *max;
-  uint64_t* len;
-};
 struct FsOut {
   uint64_t* covered;
   double *sum, *max, *junc;
 };
-
-__global__ __launch_bounds__(FS_NT) void fs_tile_k(FsRows R, uint32_t n_tiles, FsAgg A) {
-  const uint32_t t = blockIdx.x * (FS_NT / WAVE) + (threadIdx.x >> 6);
-  if (t >= n_tiles) return;  // (a whole wave leaves: the shuffles below run in full waves)
-  const uint64_t r0 = (uint64_t)t * FS_TILE, r1 = r0 + FS_TILE < R.ni ? r0 + FS_TILE : R.ni;
-  double s = 0.0, m = -__builtin_inf();
-  uint64_t c = 0;
-  for (uint64_t i = r0 + lane_id(); i < r1; i += WAVE) {
-    const int64_t len = (int64_t)R.end[i] - (int64_t)R.start[i];
-    const double v = R.val[i];
-    s += v * (double)len;
-    c += (uint64_t)len;
-    m = v > m ? v : m;
-  }
-  fs_fold(s, c, m);
-  if (lane_id() == 0) A.sum[t] = s, A.len[t] = c, A.max[t] = m;
-}
 
 __global__ __launch_bounds__(FS_NT) void fs_feat_k(FsRows R, FsFeat F, FsAgg A, FsOut O) {
   const uint32_t f = blockIdx.x * (FS_NT / WAVE) + (threadIdx.x >> 6);
@@ -58,55 +38,13 @@ __global__ __launch_bounds__(FS_NT) void fs_feat_k(FsRows R, FsFeat F, FsAgg A, 
   const int32_t ft = F.tid[f];
   const int64_t fb = F.beg[f], fe = F.end[f];
   if (O.covered) {
-    double s = 0.0, m = -__builtin_inf();
+    double s = 0.0, m = 0.0;
     uint64_t c = 0;
-    if (R.ni) {
-      // lo: the first row that ends behind the feature's begin on its reference (or lies on a later one); hi: the first one from there
-      // that starts at or behind its end
-      const uint32_t lo = fs_search(0, R.ni, [&](uint32_t i) { const int32_t t = R.tid[i]; return t > ft || (t == ft && (int64_t)R.end[i] > fb); });
-      const uint32_t hi = fs_search(lo, R.ni, [&](uint32_t i) { const int32_t t = R.tid[i]; return t > ft || (t == ft && (int64_t)R.start[i] >= fe); });
-      auto rows = [&](uint32_t a, uint32_t b) {  // rows [a, b) cut to the feature
-        for (uint32_t i = a + lane; i < b; i += WAVE) {
-          const int64_t rs = R.start[i], re = R.end[i];
-          const int64_t len = (re < fe ? re : fe) - (rs > fb ? rs : fb);
-          const double v = R.val[i];
-          s += v * (double)len;
-          c += (uint64_t)len;
-          m = v > m ? v : m;
-        }
-      };
-      if (hi - lo <= FS_DIRECT) {
-        rows(lo, hi);
-      } else {
-        // whole tiles never hold the run's first or last row, the two that may reach beyond the feature
-        const uint32_t t0 = lo / FS_TILE + 1, t1 = (hi - 1) / FS_TILE;
-        rows(lo, t0 * FS_TILE);
-        for (uint32_t t = t0 + lane; t < t1; t += WAVE) {
-          s += A.sum[t];
-          c += A.len[t];
-          const double v = A.max[t];
-          m = v > m ? v : m;
-        }
-        rows(t1 * FS_TILE, hi);
-      }
-      fs_fold(s, c, m);
-    }
+    if (R.ni) fs_cov_part(R, A, ft, fb, fe, s, c, m);
     if (lane == 0) O.covered[f] = c, O.sum[f] = s, O.max[f] = c ? m : 0.0;
   }
   if (O.junc) {
-    double j = 0.0;
-    if (R.nj) {
-      uint32_t i = fs_search(0, R.nj, [&](uint32_t k) {
-        const int32_t t = R.jtid[k];
-        if (t != ft) return t > ft;
-        const int64_t js = R.jstart[k];
-        return js > fb || (js == fb && (int64_t)R.jend[k] >= fe);
-      });
-      const uint8_t want = F.strand ? F.strand[f] : (uint8_t)'.';
-      if (lane == 0)
-        for (; i < R.nj && R.jtid[i] == ft && (int64_t)R.jstart[i] == fb && (int64_t)R.jend[i] == fe; ++i)
-          if (want == '.' || R.jstrand[i] == want) j += R.jval[i];
-    }
+    const double j = R.nj ? fs_junc_part(R, ft, fb, fe, F.strand ? F.strand[f] : (uint8_t)'.') : 0.0;
     if (lane == 0) O.junc[f] = j;
   }
 }

@@ -7,13 +7,18 @@
 
 #include <stdarg.h>
 #include <string.h>
+#include <unistd.h>
 
 void GError(const char* fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vfprintf(stderr, fmt, ap);
   va_end(ap);
-  exit(1);
+  // Not exit(): tiebrush brings the HIP runtime up on a helper thread while main opens the inputs, and exit() would run the handlers and
+  // static destructors of libraries that thread is still loading and initialising (seen as a glibc heap abort behind the message of a
+  // refused input).  Every open stream is flushed, as exit() would; nothing in these programs registers an exit handler of its own.
+  fflush(nullptr);
+  _exit(1);
 }
 void GMessage(const char* fmt, ...) {
   va_list ap;

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <thread>
+#include <unordered_map>
 
 #include "bgzf.h"
 
@@ -441,6 +442,122 @@ bool features_inside(const FeatureTable& F, const RegionTable& U, const std::str
       return err = what + " line " + std::to_string(F.line[i]) + ": the feature is not wholly inside one interval of the region", false;
   }
   return true;
+}
+
+// the value of `key` among the `key value;` pairs of a GTF line's ninth column: quoted (a ';' inside the quotes belongs to it) or bare
+static bool gtf_attr(const std::string& a, const char* key, std::string* value) {
+  const size_t klen = strlen(key);
+  for (size_t p = 0; p < a.size();) {
+    while (p < a.size() && (a[p] == ' ' || a[p] == '\t' || a[p] == ';')) ++p;
+    size_t k = p;
+    while (k < a.size() && a[k] != ' ' && a[k] != '\t' && a[k] != ';' && a[k] != '"') ++k;
+    const bool hit = k - p == klen && a.compare(p, klen, key) == 0;
+    p = k;
+    while (p < a.size() && (a[p] == ' ' || a[p] == '\t')) ++p;
+    std::string v;
+    if (p < a.size() && a[p] == '"') {
+      const size_t q = a.find('"', p + 1);
+      v = a.substr(p + 1, (q == std::string::npos ? a.size() : q) - p - 1);
+      p = q == std::string::npos ? a.size() : q + 1;
+      while (p < a.size() && a[p] != ';') ++p;  // (whatever stands between the closing quote and the ';')
+    } else {
+      size_t q = p;
+      while (q < a.size() && a[q] != ';') ++q;
+      v = a.substr(p, q - p);
+      while (!v.empty() && (v.back() == ' ' || v.back() == '\t')) v.pop_back();
+      p = q;
+    }
+    if (hit) return *value = v, true;
+  }
+  return false;
+}
+
+bool transcripts_from_gtf(const BamHeader& hdr, const std::string& text, const std::string& what, TranscriptTable& X, std::string& err) {
+  struct Exon {
+    int64_t beg, end;
+    uint64_t line;
+  };
+  struct Tx {
+    int32_t tid;
+    uint8_t strand;
+    uint64_t line;
+    std::string id, gene;
+    std::vector<Exon> ex;
+  };
+  std::vector<Tx> txs;
+  std::unordered_map<std::string, size_t> by_id;
+  size_t lineno = 0;
+  for (size_t p = 0; p < text.size();) {
+    size_t nl = text.find('\n', p);
+    if (nl == std::string::npos) nl = text.size();
+    std::string line = text.substr(p, nl - p);
+    p = nl + 1;
+    ++lineno;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    const size_t first = line.find_first_not_of(" \t");
+    if (first == std::string::npos || line[first] == '#') continue;
+    const std::string at = what + " line " + std::to_string(lineno) + ": ";
+    std::vector<std::string> f;  // eight columns and the rest
+    for (size_t q = 0; f.size() < 9;) {
+      const size_t e = f.size() == 8 ? std::string::npos : line.find('\t', q);
+      f.push_back(line.substr(q, e == std::string::npos ? std::string::npos : e - q));
+      if (e == std::string::npos) break;
+      q = e + 1;
+    }
+    if (f.size() < 3 || f[2] != "exon") continue;
+    if (f.size() < 9) return err = at + "fewer than nine columns on an exon line", false;
+    int64_t b1 = 0, e1 = 0;
+    if (!bed_coord(f[3], &b1)) return err = at + "the start '" + f[3] + "' is not a non-negative integer", false;
+    if (!bed_coord(f[4], &e1)) return err = at + "the end '" + f[4] + "' is not a non-negative integer", false;
+    if (b1 < 1) return err = at + "start < 1 (GTF coordinates are 1-based)", false;
+    if (e1 < b1) return err = at + "end < start", false;
+    const int t = hdr.name2tid(f[0]);
+    if (t < 0) return err = at + "unknown reference name '" + f[0] + "'", false;
+    if (e1 > (int64_t)hdr.target_len[(size_t)t]) return err = at + "the exon ends beyond its reference (" + f[0] + " has " + std::to_string(hdr.target_len[(size_t)t]) + " bases)", false;
+    if (f[6] != "+" && f[6] != "-" && f[6] != ".") return err = at + "the strand '" + f[6] + "' is not one of + - .", false;
+    std::string id, gene = ".";
+    if (!gtf_attr(f[8], "transcript_id", &id) || id.empty()) return err = at + "an exon line without transcript_id", false;
+    (void)gtf_attr(f[8], "gene_id", &gene);
+    if (gene.empty()) gene = ".";
+    auto it = by_id.find(id);
+    if (it == by_id.end()) {
+      it = by_id.emplace(id, txs.size()).first;
+      txs.push_back(Tx{(int32_t)t, (uint8_t)f[6][0], lineno, id, gene, {}});
+    }
+    Tx& x = txs[it->second];
+    if (x.tid != t) return err = at + "transcript " + id + " is on two references (" + hdr.target_name[(size_t)x.tid] + " on line " + std::to_string(x.line) + ")", false;
+    if (x.strand != (uint8_t)f[6][0]) return err = at + "transcript " + id + " is on two strands (" + std::string(1, (char)x.strand) + " on line " + std::to_string(x.line) + ")", false;
+    x.ex.push_back(Exon{b1 - 1, e1, lineno});
+  }
+  if (txs.empty()) return err = what + ": no exon line in it", false;
+  X = TranscriptTable();
+  for (Tx& x : txs) {
+    std::stable_sort(x.ex.begin(), x.ex.end(), [](const Exon& a, const Exon& c) { return a.beg < c.beg; });
+    for (size_t e = 1; e < x.ex.size(); ++e)
+      if (x.ex[e].beg <= x.ex[e - 1].end)
+        return err = what + " line " + std::to_string(std::max(x.ex[e].line, x.ex[e - 1].line)) + ": two exons of transcript " + x.id + " overlap or abut (the other is on line " +
+                     std::to_string(std::min(x.ex[e].line, x.ex[e - 1].line)) + "; an intron has at least one base)",
+               false;
+    X.tid.push_back(x.tid), X.strand.push_back(x.strand), X.line.push_back(x.line), X.id.push_back(x.id), X.gene.push_back(x.gene);
+    for (const Exon& e : x.ex) X.ex_beg.push_back(e.beg), X.ex_end.push_back(e.end);
+    X.tx_off.push_back((uint32_t)X.ex_beg.size());
+  }
+  return true;
+}
+
+bool transcripts_from_gtf_file(const BamHeader& hdr, const std::string& gtf_path, TranscriptTable& X, std::string& err) {
+  std::vector<uint8_t> b;
+  if (!slurp(gtf_path, b)) return err = "cannot read the annotation file " + gtf_path, false;
+  return transcripts_from_gtf(hdr, std::string(b.begin(), b.end()), gtf_path, X, err);
+}
+
+FeatureTable transcript_spans(const TranscriptTable& X) {
+  FeatureTable F;
+  for (size_t t = 0; t < X.n_tx(); ++t) {
+    F.tid.push_back(X.tid[t]), F.beg.push_back(X.ex_beg[X.tx_off[t]]), F.end.push_back(X.ex_end[X.tx_off[t + 1] - 1]);
+    F.strand.push_back(X.strand[t]), F.name.push_back(X.id[t]), F.line.push_back(X.line[t]);
+  }
+  return F;
 }
 
 bool read_spans(const std::string& bam_path, const std::vector<IdxChunk>& chunks, std::vector<RegionSpan>& spans, uint64_t* bytes_read, std::string& err) {

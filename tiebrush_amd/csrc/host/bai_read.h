@@ -100,6 +100,32 @@ bool features_from_bed_file(const BamHeader& hdr, const std::string& bed_path, F
 // true when every feature lies wholly inside one interval of the normalised table U; false: err names the first one's line that does not
 bool features_inside(const FeatureTable& F, const RegionTable& U, const std::string& what, std::string& err);
 
+// The annotation of `--gtf FILE --transcripts OUT`: transcripts as runs of exons, the introns implied between them.
+// Transcripts are numbered by the first appearance of their transcript_id among the file's exon lines; a transcript's exons are sorted
+// by start whatever their order in the file.  tx_off is CSR into ex_beg / ex_end (0-based half-open); line[t] is the line of the
+// transcript's first exon line in the text (1-based).
+struct TranscriptTable {
+  std::vector<uint32_t> tx_off{0};
+  std::vector<int32_t> tid;
+  std::vector<uint8_t> strand;  // '+', '-', '.'
+  std::vector<uint64_t> line;
+  std::vector<std::string> id, gene;  // transcript_id, gene_id (default ".")
+  std::vector<int64_t> ex_beg, ex_end;
+  size_t n_tx() const { return tid.size(); }
+  size_t n_exon() const { return ex_beg.size(); }
+};
+// GTF text: nine tab-separated columns; a line whose first non-blank character is '#' and a blank line are skipped, a trailing '\r' is
+// dropped.  Only lines whose column 3 is exactly `exon` are read (the others without a look at their other columns): columns 4 and 5 are
+// 1-based inclusive, column 7 the strand, column 9 `key value;` pairs with the value quoted (a ';' inside the quotes belongs to it) or
+// bare; transcript_id is required, gene_id optional.  false, with the line number in err: fewer than nine columns, a coordinate that is
+// not a number, start < 1, end < start, an end beyond the reference (an exon is not cut), an unknown chrom, a strand other than + - .,
+// no transcript_id, a transcript on two chroms or two strands, two exons of a transcript that overlap or abut; (without a line number)
+// a text without an exon line.  GFF3 is not read.
+bool transcripts_from_gtf(const BamHeader& hdr, const std::string& text, const std::string& what, TranscriptTable& X, std::string& err);
+bool transcripts_from_gtf_file(const BamHeader& hdr, const std::string& gtf_path, TranscriptTable& X, std::string& err);
+// the transcripts' spans [first exon's begin, last exon's end) as features (name: the transcript's id, line: its first exon line's)
+FeatureTable transcript_spans(const TranscriptTable& X);
+
 // One merged chunk's bytes: the whole BGZF members from the chunk's first member on; the records are the inflated bytes from first_uoff
 // in the first member up to last_uoff in the last one (0: the last member read is whole, the chunk ends where it ends).
 struct RegionSpan {

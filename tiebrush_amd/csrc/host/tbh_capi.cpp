@@ -217,4 +217,68 @@ int tbh_parse_thresholds(const char* list, double* thr, uint32_t cap) {
   return (int)v.size();
 }
 
+int64_t tbh_transcripts_from_gtf(const char* bam_path, const char* gtf_path, uint32_t* tx_off, int32_t* tid, uint8_t* strand, uint64_t* line, uint64_t tx_cap,
+                                 int64_t* ex_beg, int64_t* ex_end, uint64_t ex_cap, uint64_t* n_exon, char* names, uint64_t names_cap, uint64_t* names_bytes) {
+  if (!bam_path || !gtf_path || !n_exon || (tx_cap && (!tx_off || !tid || !strand || !line)) || (ex_cap && (!ex_beg || !ex_end)) || (names_cap && !names))
+    return fail("tbh_transcripts_from_gtf: null argument");
+  std::string err;
+  tbh::BamFile bf;
+  if (!bf.open(bam_path, err, 1)) return fail("tbh_transcripts_from_gtf: " + err);
+  tbh::TranscriptTable X;
+  if (!tbh::transcripts_from_gtf_file(bf.hdr, gtf_path, X, err)) return fail("tbh_transcripts_from_gtf: " + err);
+  *n_exon = X.n_exon();
+  if (X.n_tx() <= tx_cap) {
+    memcpy(tx_off, X.tx_off.data(), (X.n_tx() + 1) * 4);
+    for (size_t t = 0; t < X.n_tx(); ++t) tid[t] = X.tid[t], strand[t] = X.strand[t], line[t] = X.line[t];
+  }
+  if (X.n_exon() <= ex_cap) memcpy(ex_beg, X.ex_beg.data(), X.n_exon() * 8), memcpy(ex_end, X.ex_end.data(), X.n_exon() * 8);
+  uint64_t nb = 0;
+  for (size_t t = 0; t < X.n_tx(); ++t) nb += X.id[t].size() + X.gene[t].size() + 2;
+  if (names_bytes) *names_bytes = nb;
+  if (nb <= names_cap) {
+    char* p = names;
+    for (size_t t = 0; t < X.n_tx(); ++t)
+      for (const std::string* s : {&X.id[t], &X.gene[t]}) memcpy(p, s->c_str(), s->size() + 1), p += s->size() + 1;
+  }
+  return (int64_t)X.n_tx();
+}
+
+int tbh_tx_summary_host(uint32_t n_tx, uint32_t n_exon, const uint32_t* tx_off, const int32_t* tid, const uint8_t* strand, const int64_t* ex_beg,
+                        const int64_t* ex_end, int want_cov, uint32_t n_intervals, const int32_t* iv_tid, const int32_t* iv_start, const int32_t* iv_end,
+                        const double* iv_val, int want_junc, uint32_t n_junctions, const int32_t* j_tid, const int32_t* j_start, const int32_t* j_end,
+                        const uint8_t* j_strand, const double* j_val, uint64_t* covered, double* sum, double* max, uint32_t* exons_hit, uint32_t* introns_hit,
+                        double* junc_min, double* junc_sum, uint64_t* ex_covered, double* ex_sum, double* ex_max, double* in_junc) {
+  if (!n_tx || !n_exon || !tx_off || !tid || !ex_beg || !ex_end || (want_cov && (!covered || !sum || !max || !exons_hit)) ||
+      (want_junc && (!introns_hit || !junc_min || !junc_sum)))
+    return fail("tbh_tx_summary_host: null argument or no transcript");
+  if ((want_cov && n_intervals && (!iv_tid || !iv_start || !iv_end || !iv_val)) || (want_junc && n_junctions && (!j_tid || !j_start || !j_end || !j_strand || !j_val)))
+    return fail("tbh_tx_summary_host: null rows");
+  if (tx_off[0] != 0 || tx_off[n_tx] != n_exon) return fail("tbh_tx_summary_host: tx_off does not run from 0 to n_exon");
+  for (uint32_t t = 0; t < n_tx; ++t) {
+    if (tx_off[t + 1] <= tx_off[t] || tx_off[t + 1] > n_exon || tid[t] < 0 || (strand && strand[t] != '+' && strand[t] != '-' && strand[t] != '.'))
+      return fail("tbh_tx_summary_host: a transcript without an exon, a tid < 0 or a strand other than + - .");
+    for (uint32_t e = tx_off[t]; e < tx_off[t + 1]; ++e)
+      if (ex_beg[e] < 0 || ex_end[e] <= ex_beg[e] || (e > tx_off[t] && ex_beg[e] <= ex_end[e - 1]))
+        return fail("tbh_tx_summary_host: the exons of a transcript are not empty, ascending and apart");
+  }
+  tbh::TranscriptTable X;
+  X.tx_off.assign(tx_off, tx_off + n_tx + 1), X.tid.assign(tid, tid + n_tx), X.ex_beg.assign(ex_beg, ex_beg + n_exon), X.ex_end.assign(ex_end, ex_end + n_exon);
+  if (strand) X.strand.assign(strand, strand + n_tx);
+  else X.strand.assign(n_tx, (uint8_t)'.');
+  tbh::TxSummary S;
+  tbh::summarise_transcripts(X, want_cov != 0, n_intervals, iv_tid, iv_start, iv_end, iv_val, want_junc != 0, n_junctions, j_tid, j_start, j_end, j_strand, j_val, S);
+  if (want_cov) {
+    memcpy(covered, S.covered.data(), (size_t)n_tx * 8), memcpy(sum, S.sum.data(), (size_t)n_tx * 8), memcpy(max, S.max.data(), (size_t)n_tx * 8);
+    memcpy(exons_hit, S.exons_hit.data(), (size_t)n_tx * 4);
+    if (ex_covered) memcpy(ex_covered, S.ex_covered.data(), (size_t)n_exon * 8);
+    if (ex_sum) memcpy(ex_sum, S.ex_sum.data(), (size_t)n_exon * 8);
+    if (ex_max) memcpy(ex_max, S.ex_max.data(), (size_t)n_exon * 8);
+  }
+  if (want_junc) {
+    memcpy(introns_hit, S.introns_hit.data(), (size_t)n_tx * 4), memcpy(junc_min, S.junc_min.data(), (size_t)n_tx * 8), memcpy(junc_sum, S.junc_sum.data(), (size_t)n_tx * 8);
+    if (in_junc) memcpy(in_junc, S.in_junc.data(), (size_t)n_exon * 8);
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -720,6 +720,56 @@ int main(int argc, char** argv) {
     }
     return 0;
   }
+  // the host-only form of `tiecov --gtf ANNOT.gtf --transcripts OUT.tsv`: transcripts IN.bam COV.bedgraph JUNC.bed
+  // ANNOT.gtf OUT.tsv — our own plain tracks read back as `summary` reads them, the host summariser, the TSV writer
+  if (cmd == "transcripts" && argc == 7) {
+    std::string err;
+    tbh::BamFile bf;
+    tbh::TranscriptTable X;
+    if (!bf.open(argv[2], err, 1) || !tbh::transcripts_from_gtf_file(bf.hdr, argv[5], X, err)) {
+      fprintf(stderr, "tbh_tool transcripts: %s\n", err.c_str());
+      return 1;
+    }
+    std::vector<int32_t> tid[2], start[2], end[2];
+    std::vector<double> val[2];
+    std::vector<uint8_t> jstrand;
+    bool have[2] = {false, false};
+    for (int k = 0; k < 2; ++k) {
+      const std::string path = argv[3 + k];
+      if (path == "-") continue;
+      have[k] = true;
+      FILE* f = fopen(path.c_str(), "r");
+      if (!f) {
+        fprintf(stderr, "tbh_tool transcripts: cannot read %s\n", path.c_str());
+        return 1;
+      }
+      char line[4096], name[2048], jname[64], strand = '.';
+      for (size_t lineno = 1; fgets(line, sizeof(line), f); ++lineno) {
+        if (lineno == 1 && strncmp(line, "track", 5) == 0) continue;
+        long long s = 0, e = 0;
+        double v = 0;
+        const bool ok = k == 0 ? sscanf(line, "%2047s %lld %lld %lf", name, &s, &e, &v) == 4
+                               : sscanf(line, "%2047s %lld %lld %63s %lf %c", name, &s, &e, jname, &v, &strand) == 6;
+        const int t = ok ? bf.hdr.name2tid(name) : -1;
+        if (t < 0) {
+          fprintf(stderr, "tbh_tool transcripts: %s line %zu: not a row of the track\n", path.c_str(), lineno);
+          fclose(f);
+          return 1;
+        }
+        tid[k].push_back(t), start[k].push_back((int32_t)s), end[k].push_back((int32_t)e), val[k].push_back(v);
+        if (k == 1) jstrand.push_back((uint8_t)strand);
+      }
+      fclose(f);
+    }
+    tbh::TxSummary S;
+    tbh::summarise_transcripts(X, have[0], (uint32_t)tid[0].size(), tid[0].data(), start[0].data(), end[0].data(), val[0].data(), have[1], (uint32_t)tid[1].size(),
+                               tid[1].data(), start[1].data(), end[1].data(), jstrand.data(), val[1].data(), S);
+    if (!tbh::write_transcripts_tsv(argv[6], bf.hdr.target_name, X, S, err)) {
+      fprintf(stderr, "tbh_tool transcripts: %s\n", err.c_str());
+      return 1;
+    }
+    return 0;
+  }
   if (cmd == "batches" && argc == 4) {  // batches FILE.bam BYTES
     tbh::StreamReader rd;
     std::string err;
@@ -753,6 +803,6 @@ int main(int argc, char** argv) {
            (unsigned long long)rd.bytes_read(), (unsigned long long)rd.reinflated());
     return 0;
   }
-  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery|summary|depth|batches ...\n");
+  fprintf(stderr, "usage: tbh_tool cat|mergeorder|soa|fastsoa|mkbam|tiles|tags|bedgraph2bw|bai|csi|tabix|query|rquery|mquery|mrquery|summary|depth|transcripts|batches ...\n");
   return 2;
 }

@@ -44,6 +44,7 @@ struct TbkApi {
   decltype(&tbk_track_bgzf) track_bgzf = nullptr;      // optional: --tabix
   decltype(&tbk_cov_summary) cov_summary = nullptr;    // optional: --features / --summary
   decltype(&tbk_cov_thresholds) cov_thresholds = nullptr;  // optional: --thresholds
+  decltype(&tbk_tx_summary) tx_summary = nullptr;      // optional: --gtf / --transcripts
   std::string error;
   bool has_tracks() const { return coverage_tile && sample_tile && track_names && format_track; }
 
@@ -99,6 +100,7 @@ struct TbkApi {
     track_bgzf = (decltype(track_bgzf))dlsym(h, "tbk_track_bgzf");
     cov_summary = (decltype(cov_summary))dlsym(h, "tbk_cov_summary");
     cov_thresholds = (decltype(cov_thresholds))dlsym(h, "tbk_cov_thresholds");
+    tx_summary = (decltype(tx_summary))dlsym(h, "tbk_tx_summary");
     if (abi_version() != TBK_ABI_VERSION) {
       error = "libtbk.so has another ABI version";
       return false;

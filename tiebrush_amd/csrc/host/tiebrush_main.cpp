@@ -102,6 +102,10 @@ static const char* USAGE =
     "                       with -r / -R or --ranks\n"
     "  --feature-depth OUT.tsv   with --features BED and --thresholds: per line of BED its size, covered bases and the bases at depth\n"
     "                       >= T (as tiecov --feature-depth); with -r / -R as --summary; not with --ranks\n"
+    "  --gtf FILE --transcripts OUT.tsv   also write tiecov's per-transcript support of the output (as tiecov --gtf --transcripts: per\n"
+    "                       transcript of the GTF's exon lines its exons' coverage and how many of its introns are junctions of the\n"
+    "                       output); goes with any of the tracks or alone; with -r / -R every transcript's span must lie inside one\n"
+    "                       interval of the region; not with --ranks\n"
     "  --index             also write the output's BAM index OUT.bam.bai (what samtools index makes of OUT.bam; not with --ranks,\n"
     "                       not when the output goes to standard output)\n"
     "  --csi                also write the output's CSI index OUT.bam.csi (what samtools index -c makes of OUT.bam: for references\n"
@@ -573,7 +577,7 @@ static tbh::TrackApi track_api(const Device& dev) {
   tbh::TrackApi a;
   a.ctx = dev.ctx;
   a.coverage_tile = d.coverage_tile, a.sample_tile = d.sample_tile;
-  a.track_names = d.track_names, a.format_track = d.format_track, a.track_bgzf = d.track_bgzf, a.bigwig_build = d.bigwig_build, a.cov_summary = d.cov_summary, a.cov_thresholds = d.cov_thresholds;
+  a.track_names = d.track_names, a.format_track = d.format_track, a.track_bgzf = d.track_bgzf, a.bigwig_build = d.bigwig_build, a.cov_summary = d.cov_summary, a.cov_thresholds = d.cov_thresholds, a.tx_summary = d.tx_summary;
   a.strerror_ = d.strerror_, a.last_error = d.last_error;
   return a;
 }
@@ -1269,11 +1273,11 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
 
 // the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
-  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", nullptr};
+  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
   const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQFR");
-  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", nullptr};
+  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
   const int region_files = count_value_option(argc, argv, "regions-file", 'R', value_longs_R, "oNQFr");
-  bool ranks = false, tracks = false, index = false, csi = false, tabix = false, summary = false, depth = false;
+  bool ranks = false, tracks = false, index = false, csi = false, tabix = false, summary = false, depth = false, transcripts = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
     tabix = tabix || strcmp(argv[i], "--tabix") == 0;
@@ -1287,6 +1291,10 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
       const size_t k = strlen(o);
       depth = depth || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
     }
+    for (const char* o : {"--gtf", "--transcripts"}) {
+      const size_t k = strlen(o);
+      transcripts = transcripts || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
+    }
     for (const char* o : {"--cov", "--junc", "--samp", "--bigwig"}) {
       const size_t k = strlen(o);
       tracks = tracks || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
@@ -1296,6 +1304,7 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
   if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
   if (ranks && depth) GError("Error: --thresholds / --depth-summary / --feature-depth are not available with --ranks (run tiecov --depth-summary on the output)\n");
   if (ranks && summary) GError("Error: --features / --summary are not available with --ranks (run tiecov --features --summary on the output)\n");
+  if (ranks && transcripts) GError("Error: --gtf / --transcripts are not available with --ranks (run tiecov --gtf --transcripts on the output)\n");
   if (ranks && index) GError("Error: --index is not available with --ranks (index the output afterwards)\n");
   if (ranks && csi) GError("Error: --csi is not available with --ranks (index the output afterwards)\n");
   if (regions > 1) GError("Error: -r / --region given more than once (one region per run)\n");
@@ -1311,7 +1320,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;tabix;index;csi;region=;regions-file=;features=;summary=;thresholds=;depth-summary=;feature-depth=;SMLPEDVho:N:Q:F:r:R:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;tabix;index;csi;region=;regions-file=;features=;summary=;thresholds=;depth-summary=;feature-depth=;gtf=;transcripts=;SMLPEDVho:N:Q:F:r:R:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1388,8 +1397,10 @@ int main(int argc, char* argv[]) {
   // (--features serves --summary and --feature-depth: with neither, today's sentence)
   if (args.getOpt("summary") ? !args.getOpt("features") : (args.getOpt("features") && !args.getOpt("feature-depth")))
     GError("Error: --features BED and --summary OUT.tsv go together (%s is missing)\n", args.getOpt("summary") ? "--features" : "--summary");
+  if (args.getOpt("transcripts") ? !args.getOpt("gtf") : args.getOpt("gtf") != nullptr)
+    GError("Error: --gtf FILE and --transcripts OUT.tsv go together (%s is missing)\n", args.getOpt("transcripts") ? "--gtf" : "--transcripts");
   const bool depth = args.getOpt("thresholds") || args.getOpt("depth-summary") || args.getOpt("feature-depth");
-  const bool summary = args.getOpt("summary") != nullptr || depth;  // (what needs the output's rows and its header up front)
+  const bool summary = args.getOpt("summary") != nullptr || depth || args.getOpt("transcripts") != nullptr;  // (what needs the output's rows and its header up front)
   const char* region = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");
   const char* regions_file = args.getOpt('R') ? args.getOpt('R') : args.getOpt("regions-file");
   const bool regional = region || regions_file;
@@ -1415,10 +1426,12 @@ int main(int argc, char* argv[]) {
   // (so a summary run opens its inputs ahead of the device, as a region run does)
   tbh::SummaryJob sjob;
   tbh::DepthJob djob;
+  tbh::TxJob xjob;
   if (summary) {
     if (!regional) inRecords.start();
     sjob.setup(args.getOpt("summary") ? args.getOpt("features") : nullptr, args.getOpt("summary"), *inRecords.header(), rplan ? &rplan->U : nullptr);
     djob.setup(args.getOpt("thresholds"), args.getOpt("depth-summary"), args.getOpt("feature-depth"), args.getOpt("features"), *inRecords.header(), rplan ? &rplan->U : nullptr);
+    xjob.setup(args.getOpt("gtf"), args.getOpt("transcripts"), *inRecords.header(), rplan ? &rplan->U : nullptr);
   }
   Device dev(env, opt, dev_writer, tracks || summary, regional || summary ? t_begin : tnow());
   if (!regional && !summary) inRecords.start();
@@ -1469,7 +1482,7 @@ int main(int argc, char* argv[]) {
     const auto t0 = tnow();
     tbh::TrackTimes tt;
     tbh::TrackRun run;
-    run.num_samples = num_samples, run.bw_device = bw_device, run.summary = &sjob, run.depth = &djob, run.device_text = !env.track_host_fmt, run.times = &tt;
+    run.num_samples = num_samples, run.bw_device = bw_device, run.summary = &sjob, run.depth = &djob, run.transcripts = &xjob, run.device_text = !env.track_host_fmt, run.times = &tt;
     tbh::run_tracks(track_api(dev), trecs->as_cov_in(), inRecords.header()->target_name, tfiles, run);
     if (env.timing)
       fprintf(stderr, "tracks ms: %zu records | coverage call %.1f | sample call %.1f | text + write %.1f (%d of the tracks by the host formatter) | total %.1f\n",

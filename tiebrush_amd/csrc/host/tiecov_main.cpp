@@ -30,7 +30,7 @@ static const char* USAGE =
     "TieCov v" VERSION " (MI355X build)\n"
     "Summarises a (TieBrush-collapsed) BAM file as BED-like tracks.\n"
     "\n"
-    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [--features BED --summary OUT.tsv] [--thresholds T1,T2,.. --depth-summary OUT.tsv] [-r REGION | -R FILE] [--stream] input.bam\n"
+    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [--features BED --summary OUT.tsv] [--thresholds T1,T2,.. --depth-summary OUT.tsv] [--gtf FILE --transcripts OUT.tsv] [-r REGION | -R FILE] [--stream] input.bam\n"
     "\n"
     "  -h,--help    print this text and exit\n"
     "  --version    print the version and exit\n"
@@ -61,21 +61,29 @@ static const char* USAGE =
     "               Computed on the GPU from the rows of -c (TBK_SUMMARY_HOST=1: on this core); goes with --stream; not with -r / -R\n"
     "  --feature-depth OUT.tsv   with --features BED and --thresholds: one line per line of BED with size, covered bases and the ge_T\n"
     "               columns.  With -r / -R every feature must lie inside one interval of the region; not with --stream\n"
+    "  --gtf FILE --transcripts OUT.tsv   per-transcript support: FILE is GTF (only its `exon` lines are read; transcript_id required,\n"
+    "               gene_id optional; GFF3 is not read), one line of OUT.tsv per transcript in the order of first appearance: its span, id,\n"
+    "               gene, strand, exons, length (exonic bases), covered, sum, mean0 = sum / length, mean = sum / covered and max of the\n"
+    "               coverage over its exons, exons_hit (exons with a covered base), introns, introns_hit (introns that are a junction of\n"
+    "               the track on the transcript's strand; '.' takes every strand), junc_min and junc_sum over its introns' junction values.\n"
+    "               Computed on the GPU from the rows of -c / -j (TBK_SUMMARY_HOST=1: on this core).  With -r / -R every transcript's\n"
+    "               span must lie inside one interval of the region; not with --stream\n"
     "  --stream [--tile-bytes N]   read input.bam in batches of whole BGZF members of about N compressed bytes (plain bytes, or K / M / G;\n"
     "               default 64M; --tile-bytes alone implies --stream), decode them on the GPU and write the tracks bundle by bundle: the same\n"
     "               bytes as without it, with memory bounded by a batch and the largest bundle.  With -c (also - / stdout), -j, -s, -W,\n"
-    "               --tabix, --depth-summary; not with -r / -R / --index-file, --features / --summary / --feature-depth, --bigwig-writer device,\n"
+    "               --tabix, --depth-summary; not with -r / -R / --index-file, --features / --summary / --feature-depth, --gtf / --transcripts,\n"
+    "               --bigwig-writer device,\n"
     "               or SAM text input\n"
-    " At least one of -c / -j / -s / --summary / --depth-summary / --feature-depth is required.\n";
+    " At least one of -c / -j / -s / --summary / --depth-summary / --feature-depth / --transcripts is required.\n";
 
 // ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
 // how often -r / --region is given (Args keeps the last value of a repeated option)
 static int count_region_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", nullptr};
+  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
   return count_value_option(argc, argv, "region", 'r', value_longs, "csjR");
 }
 static int count_regions_file_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", nullptr};
+  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
   return count_value_option(argc, argv, "regions-file", 'R', value_longs, "csjr");
 }
 
@@ -90,23 +98,23 @@ static tbh::TrackApi linked_track_api(tbk_ctx* ctx) {
   a.coverage_tile = tbk_coverage_tile, a.sample_tile = tbk_sample_tile;
   a.cov_clip = tbk_cov_clip, a.cov_clip_regions = tbk_cov_clip_regions, a.sample_clip = tbk_sample_clip, a.sample_clip_regions = tbk_sample_clip_regions;
   a.track_names = tbk_track_names, a.format_track = tbk_format_track, a.track_bgzf = tbk_track_bgzf, a.bigwig_build = tbk_bigwig_build;
-  a.cov_summary = tbk_cov_summary, a.cov_thresholds = tbk_cov_thresholds;
+  a.cov_summary = tbk_cov_summary, a.cov_thresholds = tbk_cov_thresholds, a.tx_summary = tbk_tx_summary;
   a.strerror_ = tbk_strerror, a.last_error = tbk_last_error;
   return a;
 }
 
 // The tracks of `in` into the open files of tf, and the files closed; the plain text stays on the host formatter.
 static void write_run(tbk_ctx* ctx, sam_hdr_t* hdr, const tbk_cov_in& in, int num_samples, tbh::TrackFiles& tf, const tbh::TrackClip* clip, bool bw_device,
-                      const tbh::SummaryJob& sj, const tbh::DepthJob& dj) {
+                      const tbh::SummaryJob& sj, const tbh::DepthJob& dj, const tbh::TxJob& xj) {
   tbh::TrackRun run;
-  run.clip = clip, run.num_samples = num_samples, run.bw_device = bw_device, run.summary = &sj, run.depth = &dj;
+  run.clip = clip, run.num_samples = num_samples, run.bw_device = bw_device, run.summary = &sj, run.depth = &dj, run.transcripts = &xj;
   tbh::run_tracks(linked_track_api(ctx), in, hdr->target_name, tf, run);
 }
 
 // The run of -r (one: U is the region itself, which may be empty, and goes through the one-region entries) and of -R (U is the
 // normalised table of the BED file, through the table entries): every other statement is shared.
 static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::RegionTable& U, bool one, const std::string& index_file,
-                        const tbh::TrackOptions& topt, const tbh::SummaryJob& sj, const tbh::DepthJob& dj, const std::chrono::steady_clock::time_point t0) {
+                        const tbh::TrackOptions& topt, const tbh::SummaryJob& sj, const tbh::DepthJob& dj, const tbh::TxJob& xj, const std::chrono::steady_clock::time_point t0) {
   const bool timing = getenv("TBK_TIMING") != nullptr;
   auto ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
   // every refusal comes before an output file exists
@@ -157,7 +165,7 @@ static int regions_main(sam_hdr_t* hdr, const std::string& infname, const tbh::R
   tbh::TrackFiles tf;
   open_tracks(tf, hdr, topt);
   const tbh::TrackClip clip{&regs, one};
-  write_run(ctx, hdr, in, num_samples, tf, &clip, topt.bw_device, sj, dj);
+  write_run(ctx, hdr, in, num_samples, tf, &clip, topt.bw_device, sj, dj, xj);
   if (timing)
     fprintf(stderr, "tiecov %s phases ms: %u regions | index %.1f | chunk reads %.1f (%llu bytes in %u chunks) | context up at %.1f | decode + filter %.1f (%u of %u records) | tracks %.1f\n",
             one ? "-r" : "-R", R, ms_index, ms_read - ms_index, (unsigned long long)bytes_read, k, ms_ctx, ms_decode - ms_ctx, n_kept, tile.n_records, ms() - ms_decode);
@@ -267,7 +275,7 @@ static int stream_main(sam_hdr_t* hdr, const std::string& infname, uint64_t tile
 }
 
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;features=;summary=;thresholds=;depth-summary=;feature-depth=;tabix;stream;tile-bytes=;DVWhc:s:j:r:R:");
+  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;features=;summary=;thresholds=;depth-summary=;feature-depth=;gtf=;transcripts=;tabix;stream;tile-bytes=;DVWhc:s:j:r:R:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -285,7 +293,10 @@ int main(int argc, char* argv[]) {
   // (--features serves --summary and --feature-depth: with neither, today's sentence)
   if (args.getOpt("summary") ? !args.getOpt("features") : (args.getOpt("features") && !args.getOpt("feature-depth")))
     GError("Error: --features BED and --summary OUT.tsv go together (%s is missing)\n", args.getOpt("summary") ? "--features" : "--summary");
-  if (!args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j') && !args.getOpt("summary") && !args.getOpt("depth-summary") && !args.getOpt("feature-depth")) {
+  if (args.getOpt("transcripts") ? !args.getOpt("gtf") : args.getOpt("gtf") != nullptr)
+    GError("Error: --gtf FILE and --transcripts OUT.tsv go together (%s is missing)\n", args.getOpt("transcripts") ? "--gtf" : "--transcripts");
+  if (!args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j') && !args.getOpt("summary") && !args.getOpt("depth-summary") && !args.getOpt("feature-depth") &&
+      !args.getOpt("transcripts")) {
     GMessage("%s", USAGE);
     GMessage("\nError: at least one of -c/-j/-s arguments required!\n");
     return 1;
@@ -320,6 +331,8 @@ int main(int argc, char* argv[]) {
       GError("Error: --stream and -r / -R / --index-file do not go together (a region run reads only the region's chunks)\n");
     if (args.getOpt("features") || args.getOpt("summary"))
       GError("Error: --stream and --features / --summary do not go together (a feature across two tiles needs a carried partial sum)\n");
+    if (args.getOpt("gtf") || args.getOpt("transcripts"))
+      GError("Error: --stream and --gtf / --transcripts do not go together (a transcript can lie across the seam of two tiles)\n");
     if (topt.bw_device) GError("Error: --stream and --bigwig-writer device do not go together (the device writer takes all rows at once)\n");
     if (!tbh::bgzf_probe(infname)) GError("Error: --stream needs a BAM file (BGZF); %s is SAM text or cannot be read\n", infname.c_str());
   }
@@ -327,6 +340,7 @@ int main(int argc, char* argv[]) {
   sam_hdr_t* hdr = samreader.header();
   tbh::SummaryJob sj;  // (--features / --summary: refused, where they are, before any output file exists)
   tbh::DepthJob dj;    // (--thresholds / --depth-summary / --feature-depth: the same)
+  tbh::TxJob xj;       // (--gtf / --transcripts: the same)
   const char* sum_features = args.getOpt("summary") ? args.getOpt("features") : nullptr;
   if (args.getOpt('r') || args.getOpt("region") || args.getOpt('R') || args.getOpt("regions-file") || args.getOpt("index-file")) {
     const auto t0 = std::chrono::steady_clock::now();
@@ -349,11 +363,13 @@ int main(int argc, char* argv[]) {
     }
     sj.setup(sum_features, args.getOpt("summary"), *hdr, &U);
     dj.setup(args.getOpt("thresholds"), args.getOpt("depth-summary"), args.getOpt("feature-depth"), args.getOpt("features"), *hdr, &U);
-    return regions_main(hdr, infname, U, rf == nullptr, index_file, topt, sj, dj, t0);
+    xj.setup(args.getOpt("gtf"), args.getOpt("transcripts"), *hdr, &U);
+    return regions_main(hdr, infname, U, rf == nullptr, index_file, topt, sj, dj, xj, t0);
   }
   dj.setup(args.getOpt("thresholds"), args.getOpt("depth-summary"), args.getOpt("feature-depth"), args.getOpt("features"), *hdr, nullptr);
   if (stream) return stream_main(hdr, infname, tile_bytes, topt, dj);
   sj.setup(sum_features, args.getOpt("summary"), *hdr, nullptr);
+  xj.setup(args.getOpt("gtf"), args.getOpt("transcripts"), *hdr, nullptr);
   // file names and header lines: tracks.cpp (tiecov.cpp:365-402)
   tbh::TrackFiles tf;
   open_tracks(tf, hdr, topt);
@@ -391,7 +407,7 @@ int main(int argc, char* argv[]) {
 
   ctx_thread.join();
   if (rc != 0) GError("Error: cannot use GPU %d (%s); this build has no CPU coverage path\n", dev, tbk_strerror(rc));
-  write_run(ctx, hdr, recs.as_cov_in(), num_samples, tf, nullptr, topt.bw_device, sj, dj);
+  write_run(ctx, hdr, recs.as_cov_in(), num_samples, tf, nullptr, topt.bw_device, sj, dj, xj);
   tbk_destroy(ctx);
   return 0;
 }

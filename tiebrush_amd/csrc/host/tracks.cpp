@@ -433,6 +433,99 @@ void DepthJob::setup(const char* thresholds_opt, const char* depth_opt, const ch
   }
 }
 
+// ---- per-transcript support -------------------------------------------------------------------------------------------
+void summarise_transcripts(const TranscriptTable& X, bool want_cov, uint32_t ni, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val,
+                           bool want_junc, uint32_t nj, const int32_t* jtid, const int32_t* jstart, const int32_t* jend, const uint8_t* jstrand, const double* jval,
+                           TxSummary& S) {
+  const size_t n_tx = X.n_tx(), n_ex = X.n_exon();
+  S.resize(n_tx, n_ex);
+  if (want_cov) {  // the exons as features
+    FeatureTable F;
+    for (size_t t = 0; t < n_tx; ++t)
+      for (uint32_t e = X.tx_off[t]; e < X.tx_off[t + 1]; ++e) F.tid.push_back(X.tid[t]), F.beg.push_back(X.ex_beg[e]), F.end.push_back(X.ex_end[e]), F.strand.push_back((uint8_t)'.');
+    FeatSummary E;
+    summarise_features(F, true, ni, tid, start, end, val, false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, E);
+    S.ex_covered = E.covered, S.ex_sum = E.sum, S.ex_max = E.max;
+  }
+  if (want_junc && n_ex > n_tx) {  // the introns as features
+    FeatureTable F;
+    std::vector<uint32_t> at;
+    for (size_t t = 0; t < n_tx; ++t)
+      for (uint32_t e = X.tx_off[t]; e + 1 < X.tx_off[t + 1]; ++e)
+        F.tid.push_back(X.tid[t]), F.beg.push_back(X.ex_end[e]), F.end.push_back(X.ex_beg[e + 1]), F.strand.push_back(X.strand[t]), at.push_back(e);
+    FeatSummary I;
+    summarise_features(F, false, 0, nullptr, nullptr, nullptr, nullptr, true, nj, jtid, jstart, jend, jstrand, jval, I);
+    for (size_t k = 0; k < at.size(); ++k) S.in_junc[at[k]] = I.junc[k];
+  }
+  for (size_t t = 0; t < n_tx; ++t) {
+    const uint32_t e0 = X.tx_off[t], e1 = X.tx_off[t + 1];
+    for (uint32_t e = e0; e < e1 && want_cov; ++e) {
+      S.covered[t] += S.ex_covered[e], S.sum[t] += S.ex_sum[e];
+      if (S.ex_covered[e]) S.max[t] = (S.exons_hit[t] == 0 || S.ex_max[e] > S.max[t]) ? S.ex_max[e] : S.max[t], ++S.exons_hit[t];
+    }
+    for (uint32_t e = e0; e + 1 < e1 && want_junc; ++e) {
+      const double j = S.in_junc[e];
+      S.junc_sum[t] += j, S.introns_hit[t] += j > 0.0;
+      S.junc_min[t] = (e == e0 || j < S.junc_min[t]) ? j : S.junc_min[t];
+    }
+  }
+}
+
+bool write_transcripts_tsv(const std::string& path, const std::vector<std::string>& names, const TranscriptTable& X, const TxSummary& S, std::string& err) {
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) return err = "cannot create " + path, false;
+  bool ok = fputs("#chrom\tstart\tend\ttranscript\tgene\tstrand\texons\tlength\tcovered\tsum\tmean0\tmean\tmax\texons_hit\tintrons\tintrons_hit\tjunc_min\tjunc_sum\n", f) >= 0;
+  for (size_t t = 0; ok && t < X.n_tx(); ++t) {
+    const uint32_t e0 = X.tx_off[t], e1 = X.tx_off[t + 1];
+    int64_t length = 0;
+    for (uint32_t e = e0; e < e1; ++e) length += X.ex_end[e] - X.ex_beg[e];
+    const double mean0 = S.sum[t] / (double)length, mean = S.covered[t] ? S.sum[t] / (double)S.covered[t] : 0.0;
+    ok = fprintf(f, "%s\t%lld\t%lld\t%s\t%s\t%c\t%u\t%lld\t%llu\t%.3f\t%.3f\t%.3f\t%.3f\t%u\t%u\t%u\t%.3f\t%.3f\n", names[(size_t)X.tid[t]].c_str(), (long long)X.ex_beg[e0],
+                 (long long)X.ex_end[e1 - 1], X.id[t].c_str(), X.gene[t].c_str(), (char)X.strand[t], e1 - e0, (long long)length, (unsigned long long)S.covered[t], S.sum[t],
+                 mean0, mean, S.max[t], S.exons_hit[t], e1 - e0 - 1, S.introns_hit[t], S.junc_min[t], S.junc_sum[t]) > 0;
+  }
+  if (fclose(f) != 0) ok = false;
+  if (!ok) (void)unlink(path.c_str()), err = "writing " + path + " failed";
+  return ok;
+}
+
+void TxJob::setup(const char* gtf_opt, const char* transcripts_opt, const BamHeader& hdr, const RegionTable* U) {
+  if (transcripts_opt && !gtf_opt) GError("Error: --transcripts needs --gtf FILE (the annotation to summarise)\n");
+  if (gtf_opt && !transcripts_opt) GError("Error: --gtf needs --transcripts OUT.tsv (the file to write)\n");
+  if (!transcripts_opt) return;
+  if (!*transcripts_opt || !*gtf_opt) GError("Error: --gtf / --transcripts need a file name\n");
+  gtf = gtf_opt, out = transcripts_opt;
+  std::string err;
+  if (!transcripts_from_gtf_file(hdr, gtf, X, err)) GError("Error: --gtf: %s\n", err.c_str());
+  // (outside the region's intervals the rows are incomplete, and a transcript's introns lie between its exons: the whole span)
+  if (U && !features_inside(transcript_spans(X), *U, gtf, err)) GError("Error: --gtf: %s (a transcript's span, from its first exon to its last)\n", err.c_str());
+}
+
+// the one tile's rows (host, before any clip) into the run's transcript columns; the file is end()'s
+void TrackStream::tx_tile(const tbk_cov_out& rows) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const TranscriptTable& X = run_.transcripts->X;
+  const TrackApi& api = api_;
+  tx_host_ = getenv("TBK_SUMMARY_HOST") && strcmp(getenv("TBK_SUMMARY_HOST"), "0") != 0;
+  if (tx_host_) {
+    summarise_transcripts(X, true, rows.n_intervals, rows.iv_tid, rows.iv_start, rows.iv_end, rows.iv_val, true, rows.n_junctions, rows.j_tid, rows.j_start, rows.j_end,
+                          rows.j_strand, rows.j_val, tx_);
+  } else {
+    if (!api.tx_summary) GError("Error: --transcripts: the loaded libtbk.so has no tbk_tx_summary (an older build?)\n");
+    tx_.resize(X.n_tx(), X.n_exon());
+    tbk_transcripts x;
+    x.n_tx = (uint32_t)X.n_tx(), x.n_exon = (uint32_t)X.n_exon(), x.tx_off = X.tx_off.data(), x.tid = X.tid.data(), x.strand = X.strand.data();
+    x.ex_beg = X.ex_beg.data(), x.ex_end = X.ex_end.data();
+    tbk_tx_out o;
+    memset(&o, 0, sizeof(o));
+    o.mem = TBK_MEM_HOST, o.covered = tx_.covered.data(), o.sum = tx_.sum.data(), o.max = tx_.max.data(), o.exons_hit = tx_.exons_hit.data();
+    o.introns_hit = tx_.introns_hit.data(), o.junc_min = tx_.junc_min.data(), o.junc_sum = tx_.junc_sum.data();
+    const int rc = api.tx_summary(api.ctx, &rows, &x, &o);
+    if (rc != 0) GError("Error: GPU transcript summary failed: %s (%s)\n", api.strerror_(rc), api.last_error(api.ctx));
+  }
+  ms_tx_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 // one tile's rows (host, before any clip) into the run's depth tables
 void TrackStream::depth_tile(const tbk_cov_out& rows) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -565,10 +658,11 @@ void TrackStream::tile(const tbk_cov_in& in, bool last) {
   const size_t extra = clip ? clip->U->n : 0;  // (a clip over a table of R intervals can grow the interval rows by R - 1: the arrays are sized with R added)
   const bool summary = run.summary && run.summary->on();
   const bool depth = run.depth && run.depth->on();
-  const bool cov_tx = tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
+  const bool txjob = run.transcripts && run.transcripts->on();
+  const bool cov_tx =tf.cov_tx.is_open(), junc_tx = tf.junc_tx.is_open(), samp_tx = tf.samp_tx.is_open();
   const bool only = last && tiles_ == 0;  // the run's one tile: run_tracks
   // (the summary and a clip take every row of a track in one call: a run of several tiles does not have them)
-  if (!only && (summary || clip || (depth && run.depth->per_feature()))) GError("Error: a summary and a region clip take the rows of one tile\n");
+  if (!only && (summary || txjob || clip || (depth && run.depth->per_feature()))) GError("Error: a summary and a region clip take the rows of one tile\n");
   ++tiles_;
   // a tabix track: the run's one tile as before (written and closed); a tile of several as further runs behind the writer's, the header
   // line with the first rows, the writer closed by end().  A tile without rows for a track writes nothing to it.
@@ -594,8 +688,8 @@ void TrackStream::tile(const tbk_cov_in& in, bool last) {
     return r;
   };
   int rc = 0;
-  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx || summary || depth) {
-    const size_t ci = (tf.cov || tf.cov_bw || cov_tx || summary || depth) ? 2 * co + 2 * n + 16 + extra : 0, cj = (tf.junc || junc_tx || summary) ? co + 16 : 0;
+  if (tf.cov || tf.cov_bw || tf.junc || cov_tx || junc_tx || summary || depth || txjob) {
+    const size_t ci = (tf.cov || tf.cov_bw || cov_tx || summary || depth || txjob) ? 2 * co + 2 * n + 16 + extra : 0, cj = (tf.junc || junc_tx || summary || txjob) ? co + 16 : 0;
     std::vector<int32_t> it(ci ? ci : 1), is(ci ? ci : 1), ie(ci ? ci : 1), jt(cj ? cj : 1), js(cj ? cj : 1), je(cj ? cj : 1);
     std::vector<double> iv(ci ? ci : 1), jv(cj ? cj : 1);
     std::vector<uint8_t> jstr(cj ? cj : 1);
@@ -614,6 +708,7 @@ void TrackStream::tile(const tbk_cov_in& in, bool last) {
     if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
     if (summary) write_summary(*run.summary, names, o, api);
     if (depth) depth_tile(o);
+    if (txjob) tx_tile(o);
     if (clip) {
       const tbk_regions* U = clip->U;
       rc = clip->one ? api.cov_clip(ctx, &o, U->tid[0], U->beg[0], U->end[0]) : api.cov_clip_regions(ctx, &o, U);
@@ -711,6 +806,20 @@ void TrackStream::end() {
     if (getenv("TBK_TIMING"))
       fprintf(stderr, "depth phase ms: %s | %zu references | %zu features | %zu thresholds | %llu interval rows in %llu tiles | %.1f\n", depth_host_ ? "host" : "device",
               job.per_ref() ? job.lens.size() : (size_t)0, job.F.n(), job.thr.size(), (unsigned long long)depth_rows_, (unsigned long long)tiles_, ms_depth_);
+  }
+  if (run_.transcripts && run_.transcripts->on()) {  // (behind the tracks and the depth tables: a run that failed before this left no file)
+    const auto t0 = std::chrono::steady_clock::now();
+    const TxJob& job = *run_.transcripts;
+    if (tx_.covered.size() != job.X.n_tx()) tx_.resize(job.X.n_tx(), job.X.n_exon());  // (no tile at all)
+    std::string err;
+    if (!write_transcripts_tsv(job.out, names_, job.X, tx_, err)) {
+      if (run_.depth && run_.depth->per_ref()) (void)unlink(run_.depth->summary_out.c_str());
+      if (run_.depth && run_.depth->per_feature()) (void)unlink(run_.depth->feature_out.c_str());
+      GError("Error: --transcripts: %s\n", err.c_str());
+    }
+    ms_tx_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (getenv("TBK_TIMING"))
+      fprintf(stderr, "transcripts phase ms: %s | %zu transcripts, %zu exons | %.1f\n", tx_host_ ? "host" : "device", job.X.n_tx(), job.X.n_exon(), ms_tx_);
   }
   if (run_.times) *run_.times = times_;
 }

@@ -22,7 +22,7 @@ namespace tbh {
 
 // The device entry points of a track run, as a command line has them: tracks.cpp and tabix.cpp are linked without libtbk.so (tbh_tool,
 // libtbh.so), tiecov links the library and tiebrush binds it at run time, so the calls travel as pointers.  An entry the library in use
-// lacks is null (tiebrush: track_bgzf, bigwig_build, cov_summary, cov_thresholds may be; it never clips, and leaves the four clip entries null).
+// lacks is null (tiebrush: track_bgzf, bigwig_build, cov_summary, cov_thresholds, tx_summary may be; it never clips, and leaves the four clip entries null).
 struct TrackApi {
   tbk_ctx* ctx = nullptr;
   decltype(&tbk_coverage_tile) coverage_tile = nullptr;
@@ -38,7 +38,8 @@ struct TrackApi {
   decltype(&tbk_cov_summary) cov_summary = nullptr;
   decltype(&tbk_strerror) strerror_ = nullptr;
   decltype(&tbk_last_error) last_error = nullptr;
-  decltype(&tbk_cov_thresholds) cov_thresholds = nullptr;  // (the last field: a table filled in field by field without it stays valid)
+  decltype(&tbk_cov_thresholds) cov_thresholds = nullptr;
+  decltype(&tbk_tx_summary) tx_summary = nullptr;  // (the last field: a table filled in field by field without it stays valid)
 };
 
 // The track options of a command line (tiecov -c / -j / -s / -W / --bigwig-writer / --tabix and tiebrush's long spellings of them; each
@@ -160,6 +161,40 @@ struct DepthJob {
   void setup(const char* thresholds_opt, const char* depth_opt, const char* feature_depth_opt, const char* features_opt, const BamHeader& hdr, const RegionTable* U);
 };
 
+// ---- `--gtf FILE --transcripts OUT`: per-transcript support -----------------------------------------------------------
+// what tbk_tx_summary computes: one element per transcript, and the parts per exon (in_junc: the intron BEHIND the exon, 0 for a last one)
+struct TxSummary {
+  std::vector<uint64_t> covered, ex_covered;
+  std::vector<double> sum, max, junc_min, junc_sum, ex_sum, ex_max, in_junc;
+  std::vector<uint32_t> exons_hit, introns_hit;
+  void resize(size_t n_tx, size_t n_exon) {
+    covered.assign(n_tx, 0), sum.assign(n_tx, 0.0), max.assign(n_tx, 0.0), junc_min.assign(n_tx, 0.0), junc_sum.assign(n_tx, 0.0);
+    exons_hit.assign(n_tx, 0), introns_hit.assign(n_tx, 0);
+    ex_covered.assign(n_exon, 0), ex_sum.assign(n_exon, 0.0), ex_max.assign(n_exon, 0.0), in_junc.assign(n_exon, 0.0);
+  }
+};
+// The host summariser (TBK_SUMMARY_HOST=1, `tbh_tool transcripts`): tbk_tx_summary's contract by plain loops — summarise_features over
+// the exons and over the introns, then a transcript's parts added in exon order.  want_cov / want_junc false: those columns stay zero.
+void summarise_transcripts(const TranscriptTable& X, bool want_cov, uint32_t ni, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val,
+                           bool want_junc, uint32_t nj, const int32_t* jtid, const int32_t* jstart, const int32_t* jend, const uint8_t* jstrand, const double* jval,
+                           TxSummary& S);
+// `#chrom start end transcript gene strand exons length covered sum mean0 mean max exons_hit introns introns_hit junc_min junc_sum`: one
+// line per transcript in the table's order; start / end are the first exon's begin and the last exon's end, length the exonic bases,
+// mean0 = sum / length, mean = sum / covered (0 when nothing is covered), in double.  false: the file cannot be created or written (and
+// is removed)
+bool write_transcripts_tsv(const std::string& path, const std::vector<std::string>& names, const TranscriptTable& X, const TxSummary& S, std::string& err);
+
+// the two options of a run: parsed (and refused) before a device is touched or any output file exists; the file is written by
+// TrackStream::end behind the closed tracks, so a run that fails leaves none
+struct TxJob {
+  std::string gtf, out;
+  TranscriptTable X;
+  bool on() const { return !out.empty(); }
+  // The two options' rules and the GTF file against the header (and, in a region run, against its normalised table U: every
+  // transcript's span wholly inside one interval).  Errors are fatal (GError) and name the line.
+  void setup(const char* gtf_opt, const char* transcripts_opt, const BamHeader& hdr, const RegionTable* U);
+};
+
 // ---- what every run does with its records: the tracks -----------------------------------------------------------------------------
 // The records of a run as tbk_coverage_tile / tbk_sample_tile read them (host arrays): tiecov's decode of its input, tiebrush's groups
 // as they go into the output.
@@ -195,12 +230,14 @@ struct TrackRun {
   bool bw_device = false;                // the bigWig's sections by api.bigwig_build
   const SummaryJob* summary = nullptr;   // (null, or a job that is not on: no summary)
   const DepthJob* depth = nullptr;       // (the same for --depth-summary / --feature-depth)
+  const TxJob* transcripts = nullptr;    // (the same for --gtf / --transcripts)
   bool device_text = false;              // plain text by api.format_track (the names set up front), the host formatter where it refuses a track
   TrackTimes* times = nullptr;
 };
 // The rows of coverage_tile / sample_tile for `in` (host arrays, or a device view), cut to *run.clip where one is given, into the open
 // files of tf, and the files closed.  An input of no records goes the same way: the calls give no rows and status 0.  With a summary
-// job the coverage and junction rows are computed whatever tracks are open, and summarised before the cut.  The
+// or a transcripts job the coverage and junction rows are computed whatever tracks are open, and summarised before the cut (DESIGN.md
+// 4j, 4m).  The
 // reference names go to the context (track_names) at most once: up front with device_text, else before the first tabix track the
 // device writes.  Errors are fatal (GError).
 void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std::string>& names, TrackFiles& tf, const TrackRun& run);
@@ -209,8 +246,8 @@ void run_tracks(const TrackApi& api, const tbk_cov_in& in, const std::vector<std
 // after the other, are the rows of the uncut stream, so every tile's lines are appended to the open files — the junction numbers run on,
 // the bigWig's host writer collects the rows of every tile — and end() closes the files.  run_tracks is begin, ONE tile, end: the same
 // calls in the same order, the same bytes.  A tabix track takes a tile's rows as further runs (feed_tabix_track: the header line with
-// the first rows, one close in end()).  The summary, --feature-depth, a clip and the device bigWig writer take the rows of one tile and
-// are refused (GError) in a run of several.  --depth-summary goes with any number of tiles: every row belongs to one tile, so a tile's
+// the first rows, one close in end()).  The summary, --feature-depth, --transcripts, a clip and the device bigWig writer take the rows
+// of one tile and are refused (GError) in a run of several.  --depth-summary goes with any number of tiles: every row belongs to one tile, so a tile's
 // table — over the references between its first and its last row — is added to the run's (DepthTable), and end() writes the file.
 class TrackStream {
  public:
@@ -236,6 +273,10 @@ class TrackStream {
   uint64_t depth_rows_ = 0;
   bool depth_host_ = false;
   void depth_tile(const tbk_cov_out& rows);
+  TxSummary tx_;                     // --transcripts: the one tile's columns, written by end()
+  double ms_tx_ = 0;
+  bool tx_host_ = false;
+  void tx_tile(const tbk_cov_out& rows);
   TrackTimes times_;
 };
 
