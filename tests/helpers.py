@@ -1,4 +1,5 @@
 """Shared helpers of the parity tests (golden normaliser of SURVEY.md §4.4)."""
+import gzip
 import os
 
 import numpy as np
@@ -100,3 +101,23 @@ def tbk_debug(monkeypatch, **kw):
         else:
             cur[k] = str(v)
     monkeypatch.setenv("TBK_DEBUG", ",".join("%s=%s" % kv for kv in cur.items()))
+
+
+def host_tagged_stream(records, yc, yx, yd, tmp_path):
+    """the host writer's record stream: records (bytes without block_size) tagged by tbh_tag_deflate_part, inflated again"""
+    from tiebrush_amd import _lib
+    H = _lib.load_host()
+    n = len(records)
+    off = np.zeros(n + 1, dtype=np.uint64)
+    ln = np.array([len(r) for r in records], dtype=np.uint32)
+    off[1:] = np.cumsum(ln.astype(np.uint64))
+    blob = np.frombuffer(b"".join(records) + b"\0", dtype=np.uint8)
+    ycv = np.ascontiguousarray(yc, np.float64)
+    yxv = np.ascontiguousarray(yx, np.int64)
+    ydv = np.ascontiguousarray(yd, np.int32)
+    path = str(tmp_path / "host_part.bgzf")
+    rc = H.tbh_tag_deflate_part(blob.ctypes.data, off.ctypes.data, ln.ctypes.data, n, ycv.ctypes.data, yxv.ctypes.data, ydv.ctypes.data, 6, 2,
+                                path.encode())
+    assert rc == 0, H.tbh_last_error()
+    data = open(path, "rb").read()
+    return gzip.decompress(data) if data else b""

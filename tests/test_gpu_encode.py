@@ -10,7 +10,7 @@ import struct
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, sample_paths
+from helpers import GOLDEN, host_tagged_stream, sample_paths
 from test_gpu_deflate import check_run
 
 pytestmark = pytest.mark.gpu
@@ -22,26 +22,6 @@ def ctx():
     c = api.Context(0)
     yield c
     c.close()
-
-
-def host_tagged_stream(records, yc, yx, yd, tmp_path):
-    """the host writer's record stream: records (bytes without block_size) tagged by tbh_tag_deflate_part, inflated again"""
-    from tiebrush_amd import _lib
-    H = _lib.load_host()
-    n = len(records)
-    off = np.zeros(n + 1, dtype=np.uint64)
-    ln = np.array([len(r) for r in records], dtype=np.uint32)
-    off[1:] = np.cumsum(ln.astype(np.uint64))
-    blob = np.frombuffer(b"".join(records) + b"\0", dtype=np.uint8)
-    ycv = np.ascontiguousarray(yc, np.float64)
-    yxv = np.ascontiguousarray(yx, np.int64)
-    ydv = np.ascontiguousarray(yd, np.int32)
-    path = str(tmp_path / "host_part.bgzf")
-    rc = H.tbh_tag_deflate_part(blob.ctypes.data, off.ctypes.data, ln.ctypes.data, n, ycv.ctypes.data, yxv.ctypes.data, ydv.ctypes.data, 6, 2,
-                                path.encode())
-    assert rc == 0, H.tbh_last_error()
-    data = open(path, "rb").read()
-    return gzip.decompress(data) if data else b""
 
 
 def members_begin_with_records(run: bytes):
