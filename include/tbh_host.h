@@ -137,6 +137,17 @@ int tbh_tx_summary_host(uint32_t n_tx, uint32_t n_exon, const uint32_t* tx_off, 
                         const uint8_t* j_strand, const double* j_val, uint64_t* covered, double* sum, double* max, uint32_t* exons_hit, uint32_t* introns_hit,
                         double* junc_min, double* junc_sum, uint64_t* ex_covered, double* ex_sum, double* ex_max, double* in_junc);
 
+/* ---- `--strand-cov PREFIX` (appended; tbh_abi_version stays 1) ----
+ * The host form of tbk_cov_split_strand behind TBK_SPLIT_HOST=1: tiecov's input (HOST arrays; flag, yc, yx may be NULL) divided by
+ * splice strand by a plain loop.  Class 0 holds the mapped records (flag bit 0x4 clear; flag NULL: all) with strand '+', class 1 '-',
+ * class 2 every other byte.  n_rec[3] / n_cig[3] receive the classes' records and CIGAR words.  The output columns hold the classes one
+ * after the other, each in the input's order: o_tid, o_pos, o_strand, o_yc, o_yx [n] (class s from n_rec[0] + .. + n_rec[s - 1] on; o_yc /
+ * o_yx are written where the input has the column), o_cig [n_cigar_ops] likewise by n_cig, and o_cig_off [n + 3]: class s's n_rec[s] + 1
+ * offsets, counted from 0, from element n_rec[0] + .. + n_rec[s - 1] + s on.  Returns 0, or -1 for a null argument. */
+int tbh_split_strand_host(uint32_t n, uint32_t n_cigar_ops, const int32_t* tid, const int32_t* pos, const uint16_t* flag, const uint32_t* cig_off,
+                          const uint32_t* cig, const double* yc, const uint8_t* strand, const int64_t* yx, uint32_t* n_rec, uint32_t* n_cig, int32_t* o_tid,
+                          int32_t* o_pos, uint32_t* o_cig_off, uint32_t* o_cig, double* o_yc, uint8_t* o_strand, int64_t* o_yx);
+
 #ifdef __cplusplus
 }
 #endif

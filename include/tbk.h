@@ -837,6 +837,27 @@ typedef struct tbk_tx_out {
  * the context takes the next call. */
 int tbk_tx_summary(tbk_ctx* ctx, const tbk_cov_out* rows, const tbk_transcripts* transcripts, tbk_tx_out* out);
 
+/* ---- Tiecov's input divided by splice strand (ABI version 9, appended) -----------------------------------------------------
+ * What `--strand-cov PREFIX` of tiecov / tiebrush runs between a view and the coverage chain.  The reference's tiecov adds every strand
+ * into one track (tiecov.cpp:435-499), so this replaces no interface of it; the contract is that tbk_coverage_tile on view[s] gives the
+ * rows of a file that holds only that strand's mapped records.
+ * Tiecov's input divided by splice strand: view[0] the records with strand '+', view[1] '-', view[2] every other byte ('.'),
+ * each in the input's order, each a complete tbk_cov_in (CIGAR CSR rebuilt from 0, closing offset written).
+ * in->mem HOST (uploaded by the call) or DEVICE; `in` is not changed.  in->flag == NULL: every record is mapped; records with flag bit
+ * 0x4 go to no view, and the views carry flag = NULL.  tid, pos, yc, yx, strand and the CIGAR words are copied bit for bit (yc as raw
+ * 64 bits); in->yc == NULL / in->yx == NULL give views without that column.  view[s].n_records / n_cigar_ops add up to the mapped
+ * records and their words.  n_records == 0: three empty views (NULL columns), status 0; a class without records is an empty view that
+ * tbk_coverage_tile accepts.
+ * The views are DEVICE memory of the context's own, apart from the arena and from every other view: valid until the next
+ * tbk_cov_split_strand on ctx or tbk_destroy, through tbk_coverage_tile, tbk_sample_tile, the clips, tbk_format_track, tbk_track_bgzf and
+ * tbk_bigwig_build; the views of tbk_region_view(s), tbk_groups_to_cov_in and tbk_cov_stream_push and the stream's carry stay valid.
+ * TBK_EINVAL before anything is launched: in->strand == NULL with n_records > 0 (an input without records gives the three empty views
+ * whatever its pointers are: a zeroed view is one), what tbk_coverage_tile refuses of the input, and an input that is itself a view of the
+ * previous split on ctx (its memory is what the call is about to write; the views given out before the refusal stay valid).  TBK_EINVAL, found on the
+ * device before anything is written: a cig_off that does not ascend or runs past n_cigar_ops.  TBK_E2BIG: 2^32 - 1 records.  TBK_ENOMEM:
+ * the device has no room for the views.  After each the previous views are invalid, nothing faults and the context takes the next call. */
+int tbk_cov_split_strand(tbk_ctx* ctx, const tbk_cov_in* in, tbk_cov_in view[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,7 +30,7 @@ SYMBOLS = ["tbk_abi_version", "tbk_create", "tbk_destroy", "tbk_strerror", "tbk_
            "tbk_partial_pack_md", "tbk_partial_unpack_md", "tbk_partial_reduce_md", "tbk_track_names", "tbk_format_track", "tbk_bam_encode_indexed",
            "tbk_bam_decode_spans", "tbk_region_view", "tbk_cov_clip", "tbk_sample_clip", "tbk_bam_decode_file_spans", "tbk_tile_region", "tbk_last_route",
            "tbk_regions_view", "tbk_cov_clip_regions", "tbk_sample_clip_regions", "tbk_tile_regions", "tbk_zlib_deflate", "tbk_bigwig_build", "tbk_track_bgzf", "tbk_cov_summary",
-           "tbk_cov_stream_push", "tbk_cov_stream_reset", "tbk_bam_decode_open", "tbk_cov_thresholds", "tbk_tx_summary"]
+           "tbk_cov_stream_push", "tbk_cov_stream_reset", "tbk_bam_decode_open", "tbk_cov_thresholds", "tbk_tx_summary", "tbk_cov_split_strand"]
 
 
 class CollapseOpts(C.Structure):
@@ -295,6 +295,8 @@ def load():
     L.tbk_cov_stream_reset.restype = C.c_int
     L.tbk_bam_decode_open.argtypes = [_P, _P, C.c_uint64, C.c_uint32, C.c_int32, C.POINTER(SoaIn), C.POINTER(_P), C.POINTER(C.c_uint64)]
     L.tbk_bam_decode_open.restype = C.c_int
+    L.tbk_cov_split_strand.argtypes = [_P, C.POINTER(CovIn), C.POINTER(CovIn)]
+    L.tbk_cov_split_strand.restype = C.c_int
     _lib = L
     return L
 
@@ -304,7 +306,8 @@ HOST_LIB_PATH = os.environ.get("TBK_HOST_LIB") or os.path.join(_HERE, "_build", 
 HOST_SYMBOLS = ["tbh_abi_version", "tbh_last_error", "tbh_tag_deflate_part", "tbh_write_bam_parts", "tbh_is_tiebrush", "tbh_bai_index_file", "tbh_bai_reg2bin",
                 "tbh_csi_index_file", "tbh_csi_depth", "tbh_csi_reg2bin", "tbh_index_query",
                 "tbh_regions_from_bed", "tbh_index_query_regions", "tbh_features_from_bed", "tbh_cov_summary_host",
-                "tbh_cov_thresholds_host", "tbh_parse_thresholds", "tbh_transcripts_from_gtf", "tbh_tx_summary_host"]   # include/tbh_host.h
+                "tbh_cov_thresholds_host", "tbh_parse_thresholds", "tbh_transcripts_from_gtf", "tbh_tx_summary_host",
+                "tbh_split_strand_host"]   # include/tbh_host.h
 _host = None
 
 
@@ -353,6 +356,8 @@ def load_host():
     H.tbh_transcripts_from_gtf.restype = C.c_int64
     H.tbh_tx_summary_host.argtypes = [C.c_uint32, C.c_uint32] + [_P] * 5 + [C.c_int, C.c_uint32] + [_P] * 4 + [C.c_int, C.c_uint32] + [_P] * 5 + [_P] * 11
     H.tbh_tx_summary_host.restype = C.c_int
+    H.tbh_split_strand_host.argtypes = [C.c_uint32, C.c_uint32] + [_P] * 17
+    H.tbh_split_strand_host.restype = C.c_int
     _host = H
     return H
 

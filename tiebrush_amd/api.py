@@ -1023,6 +1023,27 @@ class Context:
             res.update(j_tid=jv[0][:b], j_start=jv[1][:b], j_end=jv[2][:b], j_strand=jv[3][:b], j_val=jv[4][:b])
         return res
 
+    def cov_split_strand(self, cin):
+        """tbk_cov_split_strand: a CovInput (numpy arrays: uploaded by the call; or device tensors) or a DeviceCovView divided by splice
+        strand -> [view of '+', view of '-', view of every other strand byte], each a DeviceCovView in the input's order without the
+        unmapped records (flag 0x4), in memory of the context's own: valid until the next cov_split_strand, through coverage(), sample(),
+        the clips and the track writers."""
+        keep = []
+        if isinstance(cin, DeviceCovView):
+            s, dev = cin.struct, True
+        else:
+            dev = _is_torch(cin.tid)
+            n = _numel(cin.tid)
+            nc = _numel(cin.cig)
+            s = _lib.CovIn(_lib.TBK_MEM_DEVICE if dev else _lib.TBK_MEM_HOST, n, nc, _addr(cin.tid, np.int32, keep, n),
+                           _addr(cin.pos, np.int32, keep, n), _addr(cin.flag, np.uint16, keep, n),
+                           _addr(cin.cig_off, np.uint32, keep, n + 1), _addr(cin.cig, np.uint32, keep, nc),
+                           _addr(cin.yc, np.float64, keep, n), _addr(cin.strand, np.uint8, keep, n), _addr(cin.yx, np.int64, keep, n))
+        self._order_after_torch(dev)
+        v = (_lib.CovIn * 3)()
+        self._check(self.L.tbk_cov_split_strand(self.h, C.byref(s), v), "tbk_cov_split_strand")
+        return [DeviceCovView(v[k], int(v[k].n_records), int(v[k].n_cigar_ops)) for k in range(3)]
+
     def cov_summary(self, rows, features):
         """tbk_cov_summary: the result dict of coverage() (numpy rows or device tensors; a dict without iv_* / j_* rows leaves those
         columns out) read against features: [(tid, beg, end)] or [(tid, beg, end, strand)] with strand one of '+', '-', '.', or a dict
@@ -1521,6 +1542,89 @@ def index_query_regions(bam_path, table, index_path=None):
         if n <= cap:
             return [(int(cb[i]), int(ce[i])) for i in range(n)]
         cap = int(n)
+
+
+STRAND_CLASSES = ("plus", "minus", "none")   # the views of cov_split_strand, in order
+
+
+def cov_view_to_numpy(view) -> CovInput:
+    """The arrays of a DeviceCovView copied back to the host as a CovInput (tests and tools): a column the view lacks is None (flag, and
+    yc / yx where the input had none); an empty view gives empty arrays and cig_off == [0]."""
+    s, n, nc = view.struct, int(view.n_records), int(view.n_cigar_ops)
+    hip = C.CDLL("libamdhip64.so")
+
+    def col(name, dt, cnt):
+        ptr = getattr(s, name)
+        if not ptr and name in ("flag", "yc", "yx"):
+            return None
+        a = np.zeros(cnt, dtype=dt)
+        if cnt and ptr and n:
+            rc = hip.hipMemcpy(C.c_void_p(a.ctypes.data), C.c_void_p(ptr), C.c_size_t(a.nbytes), 2)
+            if rc != 0:
+                raise RuntimeError("hipMemcpy failed (%d)" % rc)
+        return a
+
+    return CovInput(tid=col("tid", np.int32, n), pos=col("pos", np.int32, n), flag=col("flag", np.uint16, n),
+                    cig_off=col("cig_off", np.uint32, n + 1), cig=col("cig", np.uint32, nc), yc=col("yc", np.float64, n),
+                    strand=col("strand", np.uint8, n), yx=col("yx", np.int64, n))
+
+
+def split_strand_host(cin: CovInput):
+    """The rule of tbk_cov_split_strand in numpy: [the records with strand '+', with '-', with any other byte], each a CovInput in the
+    input's order without the unmapped records (flag bit 0x4; flag None: every record is mapped), CIGAR CSR rebuilt from 0, flag None,
+    every other column copied bit for bit."""
+    if cin.strand is None:
+        raise ValueError("split_strand_host: the input carries no strand column")
+    n = int(np.asarray(cin.tid).shape[0])
+    strand = np.asarray(cin.strand, dtype=np.uint8)
+    mapped = np.ones(n, dtype=bool) if cin.flag is None else (np.asarray(cin.flag, dtype=np.uint16) & 0x4) == 0
+    cls = np.where(strand == ord("+"), 0, np.where(strand == ord("-"), 1, 2))
+    off = np.asarray(cin.cig_off, dtype=np.uint32).astype(np.int64)
+    cig = np.asarray(cin.cig, dtype=np.uint32)
+    out = []
+    for k in range(3):
+        idx = np.flatnonzero(mapped & (cls == k))
+        cnt = off[idx + 1] - off[idx]
+        noff = np.zeros(len(idx) + 1, dtype=np.int64)
+        np.cumsum(cnt, out=noff[1:])
+        # word j of the part comes from off[record] + (j - the record's new offset)
+        src = np.repeat(off[idx] - noff[:-1], cnt) + np.arange(int(noff[-1]), dtype=np.int64)
+        out.append(CovInput(tid=np.asarray(cin.tid, dtype=np.int32)[idx], pos=np.asarray(cin.pos, dtype=np.int32)[idx], flag=None,
+                            cig_off=noff.astype(np.uint32), cig=cig[src], yc=None if cin.yc is None else np.asarray(cin.yc, dtype=np.float64)[idx],
+                            strand=strand[idx], yx=None if cin.yx is None else np.asarray(cin.yx, dtype=np.int64)[idx]))
+    return out
+
+
+def _split_strand_libtbh(cin: CovInput):
+    """tbh_split_strand_host: the same rule by the command lines' host loop (libtbh.so; TBK_SPLIT_HOST=1), as three CovInput"""
+    H = _lib.load_host()
+    n, nc = int(np.asarray(cin.tid).shape[0]), int(np.asarray(cin.cig).shape[0])
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        b = np.ascontiguousarray(a, dtype=dt)
+        keep.append(b)
+        return b.ctypes.data
+    n_rec, n_cig = np.zeros(3, np.uint32), np.zeros(3, np.uint32)
+    o_tid, o_pos, o_strand = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+    o_off, o_cig = np.zeros(n + 3, np.uint32), np.zeros(nc, np.uint32)
+    o_yc = np.zeros(n, np.float64) if cin.yc is not None else None
+    o_yx = np.zeros(n, np.int64) if cin.yx is not None else None
+    rc = H.tbh_split_strand_host(n, nc, ptr(cin.tid, np.int32), ptr(cin.pos, np.int32), ptr(cin.flag, np.uint16), ptr(cin.cig_off, np.uint32), ptr(cin.cig, np.uint32),
+                                 ptr(cin.yc, np.float64), ptr(cin.strand, np.uint8), ptr(cin.yx, np.int64), n_rec.ctypes.data, n_cig.ctypes.data, o_tid.ctypes.data,
+                                 o_pos.ctypes.data, o_off.ctypes.data, o_cig.ctypes.data, None if o_yc is None else o_yc.ctypes.data, o_strand.ctypes.data,
+                                 None if o_yx is None else o_yx.ctypes.data)
+    if rc != 0:
+        raise RuntimeError((H.tbh_last_error() or b"").decode())
+    out, r, w = [], 0, 0
+    for s in range(3):
+        m, c = int(n_rec[s]), int(n_cig[s])
+        out.append(CovInput(tid=o_tid[r:r + m].copy(), pos=o_pos[r:r + m].copy(), flag=None, cig_off=o_off[r + s:r + s + m + 1].copy(), cig=o_cig[w:w + c].copy(),
+                            yc=None if o_yc is None else o_yc[r:r + m].copy(), strand=o_strand[r:r + m].copy(), yx=None if o_yx is None else o_yx[r:r + m].copy()))
+        r, w = r + m, w + c
+    return out
 
 
 def to_numpy(d):

@@ -281,4 +281,33 @@ int tbh_tx_summary_host(uint32_t n_tx, uint32_t n_exon, const uint32_t* tx_off, 
   return 0;
 }
 
+int tbh_split_strand_host(uint32_t n, uint32_t n_cigar_ops, const int32_t* tid, const int32_t* pos, const uint16_t* flag, const uint32_t* cig_off,
+                          const uint32_t* cig, const double* yc, const uint8_t* strand, const int64_t* yx, uint32_t* n_rec, uint32_t* n_cig, int32_t* o_tid,
+                          int32_t* o_pos, uint32_t* o_cig_off, uint32_t* o_cig, double* o_yc, uint8_t* o_strand, int64_t* o_yx) {
+  if (!strand || !n_rec || !n_cig || !o_cig_off || (n && (!tid || !pos || !cig_off || !o_tid || !o_pos || !o_strand)) || (n_cigar_ops && (!cig || !o_cig)) ||
+      (n && yc && !o_yc) || (n && yx && !o_yx))
+    return fail("tbh_split_strand_host: null argument");
+  tbk_cov_in in;
+  memset(&in, 0, sizeof(in));
+  in.mem = TBK_MEM_HOST, in.n_records = n, in.n_cigar_ops = n_cigar_ops;
+  in.tid = tid, in.pos = pos, in.flag = flag, in.cig_off = cig_off, in.cig = cig, in.yc = yc, in.strand = strand, in.yx = yx;
+  tbh::CovRecs out[3];
+  tbh::split_strand_host(in, out);
+  size_t r = 0, w = 0;
+  for (int s = 0; s < 3; ++s) {
+    const tbh::CovRecs& o = out[s];
+    const size_t m = o.tid.size(), c = o.cig.size();
+    n_rec[s] = (uint32_t)m, n_cig[s] = (uint32_t)c;
+    if (m) {
+      memcpy(o_tid + r, o.tid.data(), m * 4), memcpy(o_pos + r, o.pos.data(), m * 4), memcpy(o_strand + r, o.strand.data(), m);
+      if (yc) memcpy(o_yc + r, o.yc.data(), m * 8);
+      if (yx) memcpy(o_yx + r, o.yx.data(), m * 8);
+    }
+    memcpy(o_cig_off + r + s, o.cig_off.data(), (m + 1) * 4);
+    if (c) memcpy(o_cig + w, o.cig.data(), c * 4);
+    r += m, w += c;
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -45,6 +45,7 @@ struct TbkApi {
   decltype(&tbk_cov_summary) cov_summary = nullptr;    // optional: --features / --summary
   decltype(&tbk_cov_thresholds) cov_thresholds = nullptr;  // optional: --thresholds
   decltype(&tbk_tx_summary) tx_summary = nullptr;      // optional: --gtf / --transcripts
+  decltype(&tbk_cov_split_strand) cov_split_strand = nullptr;  // optional: --strand-cov
   std::string error;
   bool has_tracks() const { return coverage_tile && sample_tile && track_names && format_track; }
 
@@ -101,6 +102,7 @@ struct TbkApi {
     cov_summary = (decltype(cov_summary))dlsym(h, "tbk_cov_summary");
     cov_thresholds = (decltype(cov_thresholds))dlsym(h, "tbk_cov_thresholds");
     tx_summary = (decltype(tx_summary))dlsym(h, "tbk_tx_summary");
+    cov_split_strand = (decltype(cov_split_strand))dlsym(h, "tbk_cov_split_strand");
     if (abi_version() != TBK_ABI_VERSION) {
       error = "libtbk.so has another ABI version";
       return false;

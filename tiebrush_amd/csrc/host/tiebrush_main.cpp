@@ -85,6 +85,8 @@ static const char* USAGE =
     "  --cov PREFIX         also write tiecov's coverage track of the output (as tiecov -c; - or stdout: standard output)\n"
     "  --junc PREFIX        also write tiecov's junction track of the output (as tiecov -j)\n"
     "  --samp PREFIX        also write tiecov's sample-count track of the output (as tiecov -s; needs @CO SAMPLE: header lines)\n"
+    "  --strand-cov PREFIX  also write the output's coverage per splice strand (as tiecov --strand-cov): PREFIX.plus.bedgraph,\n"
+    "                       PREFIX.minus.bedgraph, PREFIX.none.bedgraph; with --bigwig .bigwig, with --tabix .bedgraph.gz and an index each\n"
     "  --bigwig             write the coverage track as PREFIX.bigwig (as tiecov -W; needs --cov)\n"
     "  --bigwig-writer host|device   with --bigwig: the file's sections and zoom levels by this core with zlib (host, the default)\n"
     "                       or by the GPU (device: the same payloads, compressed by the device's deflater)\n"
@@ -577,7 +579,7 @@ static tbh::TrackApi track_api(const Device& dev) {
   tbh::TrackApi a;
   a.ctx = dev.ctx;
   a.coverage_tile = d.coverage_tile, a.sample_tile = d.sample_tile;
-  a.track_names = d.track_names, a.format_track = d.format_track, a.track_bgzf = d.track_bgzf, a.bigwig_build = d.bigwig_build, a.cov_summary = d.cov_summary, a.cov_thresholds = d.cov_thresholds, a.tx_summary = d.tx_summary;
+  a.track_names = d.track_names, a.format_track = d.format_track, a.track_bgzf = d.track_bgzf, a.bigwig_build = d.bigwig_build, a.cov_summary = d.cov_summary, a.cov_thresholds = d.cov_thresholds, a.tx_summary = d.tx_summary, a.cov_split_strand = d.cov_split_strand;
   a.strerror_ = d.strerror_, a.last_error = d.last_error;
   return a;
 }
@@ -1273,10 +1275,17 @@ static void run_streaming(Device& dev, Output& out, const tbk_collapse_opts& opt
 
 // the track options and --index with --ranks: refused before the launcher starts (the multi-rank tracks and index are not built)
 static void refuse_tracks_with_ranks(int argc, char* argv[]) {
-  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
+  static const char* const value_longs[] = {"writer", "cov", "junc", "samp", "ranks", "regions-file", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", "strand-cov", nullptr};
   const int regions = count_value_option(argc, argv, "region", 'r', value_longs, "oNQFR");
-  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
+  static const char* const value_longs_R[] = {"writer", "cov", "junc", "samp", "ranks", "region", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", "strand-cov", nullptr};
   const int region_files = count_value_option(argc, argv, "regions-file", 'R', value_longs_R, "oNQFr");
+  static const char* const value_longs_S[] = {"writer", "cov", "junc", "samp", "ranks", "region", "regions-file", "bigwig-writer", "features", "summary", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
+  const int strand_covs = count_value_option(argc, argv, "strand-cov", 0, value_longs_S, "oNQFrR");
+  const char* strand_prefix = nullptr;  // (the value as given, for the refusals that come before the launcher and before Args)
+  for (int i = 1; i < argc; ++i) {
+    if (strcmp(argv[i], "--strand-cov") == 0 && i + 1 < argc) strand_prefix = argv[i + 1];
+    else if (strncmp(argv[i], "--strand-cov=", 13) == 0) strand_prefix = argv[i] + 13;
+  }
   bool ranks = false, tracks = false, index = false, csi = false, tabix = false, summary = false, depth = false, transcripts = false;
   for (int i = 1; i < argc; ++i) {
     ranks = ranks || strcmp(argv[i], "--ranks") == 0 || strncmp(argv[i], "--ranks=", 8) == 0;
@@ -1300,6 +1309,7 @@ static void refuse_tracks_with_ranks(int argc, char* argv[]) {
       tracks = tracks || (strncmp(argv[i], o, k) == 0 && (argv[i][k] == 0 || argv[i][k] == '='));
     }
   }
+  if (strand_covs) tbh::check_strand_cov(strand_prefix ? strand_prefix : "", strand_covs, ranks ? 2 : 1);
   if (ranks && tabix) GError("Error: --tabix is not available with --ranks (run tiecov --tabix on the output)\n");
   if (ranks && tracks) GError("Error: --cov / --junc / --samp / --bigwig are not available with --ranks (run tiecov on the output)\n");
   if (ranks && depth) GError("Error: --thresholds / --depth-summary / --feature-depth are not available with --ranks (run tiecov --depth-summary on the output)\n");
@@ -1320,7 +1330,7 @@ int main(int argc, char* argv[]) {
   spawn_ranks_launcher_if_asked(argc, argv, env);
   TInputFiles inRecords;
   inRecords.setup(VERSION, argc, argv);
-  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;tabix;index;csi;region=;regions-file=;features=;summary=;thresholds=;depth-summary=;feature-depth=;gtf=;transcripts=;SMLPEDVho:N:Q:F:r:R:A");
+  Args args(argc, argv, "help;debug;verbose;version;full;clip;exon;keep-supp;keep-secondary;keep-unmap;collapse-same;store-frac;writer=;cov=;junc=;samp=;bigwig;bigwig-writer=;tabix;index;csi;region=;regions-file=;features=;summary=;thresholds=;depth-summary=;feature-depth=;gtf=;transcripts=;strand-cov=;SMLPEDVho:N:Q:F:r:R:A");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -1379,7 +1389,8 @@ int main(int argc, char* argv[]) {
   const std::string cov_prefix = args.getOpt("cov") ? args.getOpt("cov") : "", junc_prefix = args.getOpt("junc") ? args.getOpt("junc") : "",
                     samp_prefix = args.getOpt("samp") ? args.getOpt("samp") : "";
   const bool bigwig = args.getOpt("bigwig") != nullptr;
-  if (bigwig && cov_prefix.empty()) GError("Error: --bigwig needs --cov\n");
+  const std::string strand_prefix = args.getOpt("strand-cov") ? args.getOpt("strand-cov") : "";
+  if (bigwig && cov_prefix.empty() && strand_prefix.empty()) GError("Error: --bigwig needs --cov\n");
   if (args.getOpt("bigwig-writer") && !bigwig) GError("Error: --bigwig-writer needs --bigwig\n");
   const bool bw_device = args.getOpt("bigwig-writer") && tbh::parse_bigwig_writer(args.getOpt("bigwig-writer"));
   const bool want_index = args.getOpt("index") != nullptr;
@@ -1389,7 +1400,7 @@ int main(int argc, char* argv[]) {
   if (want_csi && want_index) GError("Error: --csi and --index do not go together (their bins differ: one run builds one index)\n");
   if (want_csi && strcmp(outfname, "-") == 0)
     GError("Error: --csi needs an output file (-o FILE, not -o -): an index addresses file offsets, standard output has none\n");
-  const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty();
+  const bool tracks = !cov_prefix.empty() || !junc_prefix.empty() || !samp_prefix.empty() || !strand_prefix.empty();
   const bool tabix = args.getOpt("tabix") != nullptr;
   if (tabix && !tracks) GError("Error: --tabix needs at least one of --cov / --junc / --samp (it applies to their tracks)\n");
   if (tabix && !bigwig && (cov_prefix == "-" || cov_prefix == "stdout"))
@@ -1449,6 +1460,7 @@ int main(int argc, char* argv[]) {
     }
     tbh::TrackOptions topt;
     topt.cov = cov_prefix, topt.junc = junc_prefix, topt.samp = samp_prefix, topt.bigwig = bigwig, topt.bw_device = bw_device, topt.tabix = tabix;
+    topt.strand_cov = strand_prefix;
     tfiles.open(topt, h->target_name, h->target_len);
   }
   if (tracks || summary) trecs.reset(new tbh::CovRecs());

@@ -30,7 +30,7 @@ static const char* USAGE =
     "TieCov v" VERSION " (MI355X build)\n"
     "Summarises a (TieBrush-collapsed) BAM file as BED-like tracks.\n"
     "\n"
-    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [--features BED --summary OUT.tsv] [--thresholds T1,T2,.. --depth-summary OUT.tsv] [--gtf FILE --transcripts OUT.tsv] [-r REGION | -R FILE] [--stream] input.bam\n"
+    " usage: tiecov [-s out.sample] [-c out.coverage] [-j out.junctions] [--features BED --summary OUT.tsv] [--thresholds T1,T2,.. --depth-summary OUT.tsv] [--gtf FILE --transcripts OUT.tsv] [--strand-cov PREFIX] [-r REGION | -R FILE] [--stream] input.bam\n"
     "\n"
     "  -h,--help    print this text and exit\n"
     "  --version    print the version and exit\n"
@@ -68,23 +68,32 @@ static const char* USAGE =
     "               the track on the transcript's strand; '.' takes every strand), junc_min and junc_sum over its introns' junction values.\n"
     "               Computed on the GPU from the rows of -c / -j (TBK_SUMMARY_HOST=1: on this core).  With -r / -R every transcript's\n"
     "               span must lie inside one interval of the region; not with --stream\n"
+    "  --strand-cov PREFIX   the coverage of each splice strand (the XS tag, else minimap2's ts turned round on a reverse read) in a file\n"
+    "               of its own: PREFIX.plus.bedgraph, PREFIX.minus.bedgraph and PREFIX.none.bedgraph (every other record), each the file -c\n"
+    "               writes for a BAM of that strand's mapped records alone.  The records are divided on the GPU (TBK_SPLIT_HOST=1: on this\n"
+    "               core).  -W makes them .bigwig, --tabix .bedgraph.gz with an index each; goes with every other output, -r / -R and\n"
+    "               --stream; PREFIX cannot be - / stdout\n"
     "  --stream [--tile-bytes N]   read input.bam in batches of whole BGZF members of about N compressed bytes (plain bytes, or K / M / G;\n"
     "               default 64M; --tile-bytes alone implies --stream), decode them on the GPU and write the tracks bundle by bundle: the same\n"
     "               bytes as without it, with memory bounded by a batch and the largest bundle.  With -c (also - / stdout), -j, -s, -W,\n"
     "               --tabix, --depth-summary; not with -r / -R / --index-file, --features / --summary / --feature-depth, --gtf / --transcripts,\n"
     "               --bigwig-writer device,\n"
     "               or SAM text input\n"
-    " At least one of -c / -j / -s / --summary / --depth-summary / --feature-depth / --transcripts is required.\n";
+    " At least one of -c / -j / -s / --summary / --depth-summary / --feature-depth / --transcripts / --strand-cov is required.\n";
 
 // ---- tiecov -r --------------------------------------------------------------------------------------------------------------------
 // how often -r / --region is given (Args keeps the last value of a repeated option)
 static int count_region_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
+  static const char* const value_longs[] = {"index-file", "regions-file", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", "strand-cov", nullptr};
   return count_value_option(argc, argv, "region", 'r', value_longs, "csjR");
 }
 static int count_regions_file_opts(int argc, char** argv) {
-  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
+  static const char* const value_longs[] = {"index-file", "region", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", "strand-cov", nullptr};
   return count_value_option(argc, argv, "regions-file", 'R', value_longs, "csjr");
+}
+static int count_strand_cov_opts(int argc, char** argv) {
+  static const char* const value_longs[] = {"index-file", "region", "regions-file", "bigwig-writer", "features", "summary", "tile-bytes", "thresholds", "depth-summary", "feature-depth", "gtf", "transcripts", nullptr};
+  return count_value_option(argc, argv, "strand-cov", 0, value_longs, "csjrR");
 }
 
 // ---- what every run does with its records: the tracks (tracks.cpp: run_tracks) ----------------------------------------------------
@@ -98,7 +107,7 @@ static tbh::TrackApi linked_track_api(tbk_ctx* ctx) {
   a.coverage_tile = tbk_coverage_tile, a.sample_tile = tbk_sample_tile;
   a.cov_clip = tbk_cov_clip, a.cov_clip_regions = tbk_cov_clip_regions, a.sample_clip = tbk_sample_clip, a.sample_clip_regions = tbk_sample_clip_regions;
   a.track_names = tbk_track_names, a.format_track = tbk_format_track, a.track_bgzf = tbk_track_bgzf, a.bigwig_build = tbk_bigwig_build;
-  a.cov_summary = tbk_cov_summary, a.cov_thresholds = tbk_cov_thresholds, a.tx_summary = tbk_tx_summary;
+  a.cov_summary = tbk_cov_summary, a.cov_thresholds = tbk_cov_thresholds, a.tx_summary = tbk_tx_summary, a.cov_split_strand = tbk_cov_split_strand;
   a.strerror_ = tbk_strerror, a.last_error = tbk_last_error;
   return a;
 }
@@ -275,7 +284,7 @@ static int stream_main(sam_hdr_t* hdr, const std::string& infname, uint64_t tile
 }
 
 int main(int argc, char* argv[]) {
-  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;features=;summary=;thresholds=;depth-summary=;feature-depth=;gtf=;transcripts=;tabix;stream;tile-bytes=;DVWhc:s:j:r:R:");
+  Args args(argc, argv, "help;verbose;version;region=;regions-file=;index-file=;bigwig-writer=;features=;summary=;thresholds=;depth-summary=;feature-depth=;gtf=;transcripts=;strand-cov=;tabix;stream;tile-bytes=;DVWhc:s:j:r:R:");
   if (!args.error().empty()) {
     GMessage("%s\n%s\n", USAGE, args.error().c_str());
     return 1;
@@ -289,14 +298,16 @@ int main(int argc, char* argv[]) {
     return 0;
   }
   const bool tabix = args.getOpt("tabix") != nullptr;
-  if (tabix && !args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j')) GError("Error: --tabix needs at least one of -c / -j / -s (it applies to their tracks)\n");
+  const char* strand_cov = args.getOpt("strand-cov");
+  tbh::check_strand_cov(strand_cov, count_strand_cov_opts(argc, argv), 1);
+  if (tabix && !args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j') && !strand_cov) GError("Error: --tabix needs at least one of -c / -j / -s (it applies to their tracks)\n");
   // (--features serves --summary and --feature-depth: with neither, today's sentence)
   if (args.getOpt("summary") ? !args.getOpt("features") : (args.getOpt("features") && !args.getOpt("feature-depth")))
     GError("Error: --features BED and --summary OUT.tsv go together (%s is missing)\n", args.getOpt("summary") ? "--features" : "--summary");
   if (args.getOpt("transcripts") ? !args.getOpt("gtf") : args.getOpt("gtf") != nullptr)
     GError("Error: --gtf FILE and --transcripts OUT.tsv go together (%s is missing)\n", args.getOpt("transcripts") ? "--gtf" : "--transcripts");
   if (!args.getOpt('c') && !args.getOpt('s') && !args.getOpt('j') && !args.getOpt("summary") && !args.getOpt("depth-summary") && !args.getOpt("feature-depth") &&
-      !args.getOpt("transcripts")) {
+      !args.getOpt("transcripts") && !strand_cov) {
     GMessage("%s", USAGE);
     GMessage("\nError: at least one of -c/-j/-s arguments required!\n");
     return 1;
@@ -304,7 +315,7 @@ int main(int argc, char* argv[]) {
   const bool bigwig = args.getOpt('W') != nullptr;
   if (tabix && !bigwig && args.getOpt('c') && (strcmp(args.getOpt('c'), "-") == 0 || strcmp(args.getOpt('c'), "stdout") == 0))
     GError("Error: --tabix needs a coverage file (-c PREFIX, not -c %s): an index addresses file offsets, standard output has none\n", args.getOpt('c'));
-  if (args.getOpt("bigwig-writer") && !(bigwig && args.getOpt('c'))) GError("Error: --bigwig-writer needs -W (and -c)\n");
+  if (args.getOpt("bigwig-writer") && !(bigwig && (args.getOpt('c') || strand_cov))) GError("Error: --bigwig-writer needs -W (and -c)\n");
   tbh::TrackOptions topt;
   topt.bigwig = bigwig, topt.tabix = tabix;
   topt.bw_device = args.getOpt("bigwig-writer") && tbh::parse_bigwig_writer(args.getOpt("bigwig-writer"));
@@ -315,6 +326,7 @@ int main(int argc, char* argv[]) {
   topt.cov = args.getOpt('c') ? args.getOpt('c') : "";
   topt.junc = args.getOpt('j') ? args.getOpt('j') : "";
   topt.samp = args.getOpt('s') ? args.getOpt('s') : "";
+  topt.strand_cov = strand_cov ? strand_cov : "";
   if (args.startNonOpt() == 0) {
     GMessage("%s", USAGE);
     GMessage("\nError: no input file provided!\n");
@@ -334,6 +346,7 @@ int main(int argc, char* argv[]) {
     if (args.getOpt("gtf") || args.getOpt("transcripts"))
       GError("Error: --stream and --gtf / --transcripts do not go together (a transcript can lie across the seam of two tiles)\n");
     if (topt.bw_device) GError("Error: --stream and --bigwig-writer device do not go together (the device writer takes all rows at once)\n");
+    tbh::refuse_split_host_on_device(strand_cov, "--stream");
     if (!tbh::bgzf_probe(infname)) GError("Error: --stream needs a BAM file (BGZF); %s is SAM text or cannot be read\n", infname.c_str());
   }
   GSamReader samreader(infname.c_str(), SAM_QNAME | SAM_FLAG | SAM_RNAME | SAM_POS | SAM_CIGAR | SAM_AUX);
@@ -344,6 +357,7 @@ int main(int argc, char* argv[]) {
   const char* sum_features = args.getOpt("summary") ? args.getOpt("features") : nullptr;
   if (args.getOpt('r') || args.getOpt("region") || args.getOpt('R') || args.getOpt("regions-file") || args.getOpt("index-file")) {
     const auto t0 = std::chrono::steady_clock::now();
+    tbh::refuse_split_host_on_device(strand_cov, "-r / -R");
     if (count_region_opts(argc, argv) > 1) GError("Error: -r / --region given more than once (one region per run)\n");
     if (count_regions_file_opts(argc, argv) > 1) GError("Error: -R / --regions-file given more than once (one file of regions per run)\n");
     const char* r = args.getOpt('r') ? args.getOpt('r') : args.getOpt("region");

@@ -35,9 +35,47 @@ static void open_tabix(TabixWriter& w, std::string prefix, const char* ext, cons
   if (!w.open(prefix, names, lens, head, err)) GError("Error creating file %s (%s)\n", prefix.c_str(), err.c_str());
 }
 
+const char* const kStrandSuffix[3] = {".plus", ".minus", ".none"};
+
+bool split_host_asked() { return getenv("TBK_SPLIT_HOST") && strcmp(getenv("TBK_SPLIT_HOST"), "0") != 0; }
+
+void refuse_split_host_on_device(const char* prefix, const char* what) {
+  if (prefix && split_host_asked())
+    GError("Error: TBK_SPLIT_HOST=1 divides host records; the records of a %s run are on the device (unset it, or run without %s)\n", what, what);
+}
+
+void check_strand_cov(const char* prefix, int times, int ranks) {
+  if (!prefix) return;
+  if (times > 1) GError("Error: --strand-cov given more than once (one prefix per run)\n");
+  if (!*prefix || strcmp(prefix, "-") == 0 || strcmp(prefix, "stdout") == 0)
+    GError("Error: --strand-cov needs a file prefix (not '%s'): its three tracks cannot share standard output\n", prefix);
+  if (ranks > 1) GError("Error: --strand-cov and --ranks do not go together (the per-strand tracks are written by a single-rank run)\n");
+}
+
 void TrackFiles::open(const TrackOptions& o, const std::vector<std::string>& names, const std::vector<uint32_t>& lens) {
   std::string cov_prefix = o.cov, junc_prefix = o.junc, samp_prefix = o.samp;
   const bool bigwig = o.bigwig;
+  for (int s = 0; s < 3 && !o.strand_cov.empty(); ++s) {  // --strand-cov: each file by the rules of -c below
+    CovSink& k = strand[s];
+    std::string prefix = o.strand_cov + kStrandSuffix[s];
+    if (o.tabix && !bigwig) {
+      open_tabix(k.tx, prefix, ".bedgraph", kCovHead, names, lens);
+      k.name = k.tx.path();
+    } else if (bigwig) {
+      prefix += ".bigwig";
+      std::string err;
+      if (!k.bw.open(prefix, names, lens, err)) GError("Error creating file %s\n", prefix.c_str());
+      k.is_bw = true;
+      bw_lens = lens;
+      k.name = prefix;
+    } else {
+      prefix += ".bedgraph";
+      k.f = fopen(prefix.c_str(), "w");
+      if (!k.f) GError("Error creating file %s\n", prefix.c_str());
+      fprintf(k.f, "%s", kCovHead);
+      k.name = prefix;
+    }
+  }
   if (o.tabix) {  // every text track; the coverage as a bigWig stays what it is below
     if (!cov_prefix.empty() && !bigwig && cov_prefix != "-" && cov_prefix != "stdout") open_tabix(cov_tx, cov_prefix, ".bedgraph", kCovHead, names, lens), cov_name = cov_tx.path(), cov_prefix.clear();
     if (!junc_prefix.empty()) open_tabix(junc_tx, junc_prefix, ".bed", kJuncHead, names, lens), junc_prefix.clear();
@@ -81,6 +119,16 @@ void TrackFiles::close_bigwig() {
   std::string err;
   if (!bw.close(err)) GError("Error: writing %s failed (%s)\n", cov_name.c_str(), err.c_str());
   cov_bw = false;
+}
+
+// (a per-strand bigWig whose items are all in: --strand-cov -W over several tiles)
+static void close_strand_bigwigs(TrackFiles& tf) {
+  for (CovSink& k : tf.strand) {
+    if (!k.is_bw) continue;
+    std::string err;
+    if (!k.bw.close(err)) GError("Error: writing %s failed (%s)\n", k.name.c_str(), err.c_str());
+    k.is_bw = false;
+  }
 }
 
 bool parse_bigwig_writer(const char* value) {
@@ -127,7 +175,9 @@ struct BwBridge {
 };
 }  // namespace
 
-void TrackFiles::write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev) {
+// one bigWig file: the rows into `bw` and the file closed (TrackFiles::write_bigwig for the coverage track and for a strand's)
+static void write_bigwig_file(BigWigWriter& bw, bool& cov_bw, const std::string& cov_name, const std::vector<uint32_t>& bw_lens, uint32_t n, const int32_t* tid,
+                              const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev) {
   if (!cov_bw) return;
   const auto t0 = std::chrono::steady_clock::now();
   for (uint32_t i = 0; i < n; ++i) bw.add((uint32_t)tid[i], (uint32_t)start[i], (uint32_t)end[i], (float)val[i]);
@@ -167,14 +217,26 @@ void TrackFiles::write_bigwig(uint32_t n, const int32_t* tid, const int32_t* sta
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
+void TrackFiles::write_bigwig(uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev) {
+  write_bigwig_file(bw, cov_bw, cov_name, bw_lens, n, tid, start, end, val, dev);
+}
+void TrackFiles::write_strand_bigwig(int s, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev) {
+  write_bigwig_file(strand[s].bw, strand[s].is_bw, strand[s].name, bw_lens, n, tid, start, end, val, dev);
+}
+
 void TrackFiles::close() {
   close_bigwig();
+  close_strand_bigwigs(*this);
+  for (CovSink& k : strand) {
+    if (k.f) fclose(k.f);
+    k.f = nullptr;
+  }
   if (cov && cov != stdout) fclose(cov);
   if (cov == stdout) fflush(stdout);
   if (junc) fclose(junc);
   if (samp) fclose(samp);
   cov = junc = samp = nullptr;
-  for (TabixWriter* w : {&cov_tx, &junc_tx, &samp_tx}) {  // (a track nobody wrote rows to: its header, the EOF member, an empty index)
+  for (TabixWriter* w : {&cov_tx, &junc_tx, &samp_tx, &strand[0].tx, &strand[1].tx, &strand[2].tx}) {  // (a track nobody wrote rows to: its header, the EOF member, an empty index)
     std::string err;
     if (!w->is_open()) continue;
     std::vector<BaiRec> none;
@@ -589,9 +651,27 @@ tbk_cov_in CovRecs::as_cov_in() const {
   in.mem = TBK_MEM_HOST;
   in.n_records = (uint32_t)tid.size();
   in.n_cigar_ops = (uint32_t)cig.size();
-  in.tid = tid.data(), in.pos = pos.data(), in.flag = flag.data(), in.cig_off = cig_off.data(), in.cig = cig.data();
-  in.yc = yc.data(), in.strand = strand.data(), in.yx = yx.data();
+  // A column without elements travels as NULL, said here and not left to what vector::data() gives for an empty vector: no records at
+  // all (every column), or a part of split_strand_host, which has no flag column ("every record counts") and no yc / yx where its
+  // input had none.  A table that append() filled has every column as long as tid, so nothing changes for it.
+  auto col = [](const auto& v) { return v.empty() ? nullptr : v.data(); };
+  in.tid = col(tid), in.pos = col(pos), in.flag = col(flag), in.cig_off = cig_off.data(), in.cig = col(cig);
+  in.yc = col(yc), in.strand = col(strand), in.yx = col(yx);
   return in;
+}
+
+void split_strand_host(const tbk_cov_in& in, CovRecs out[3]) {
+  for (int s = 0; s < 3; ++s) out[s] = CovRecs();
+  for (size_t i = 0; i < in.n_records; ++i) {
+    if (in.flag && (in.flag[i] & 0x4)) continue;
+    const uint8_t st = in.strand[i];
+    CovRecs& o = out[st == '+' ? 0 : (st == '-' ? 1 : 2)];
+    o.tid.push_back(in.tid[i]), o.pos.push_back(in.pos[i]), o.strand.push_back(st);
+    if (in.yc) o.yc.push_back(in.yc[i]);
+    if (in.yx) o.yx.push_back(in.yx[i]);
+    o.cig.insert(o.cig.end(), in.cig + in.cig_off[i], in.cig + in.cig_off[i + 1]);
+    o.cig_off.push_back((uint32_t)o.cig.size());
+  }
 }
 
 bool CovRecs::append(uint32_t ng, const std::function<RecView(uint32_t)>& rec, const std::function<void(uint32_t, const RecView&, double*, int64_t*)>& values,
@@ -639,7 +719,7 @@ TrackStream::TrackStream(const TrackApi& api, const std::vector<std::string>& na
     : api_(api), names_(names), tf_(tf), run_(run) {
   // --tabix: a track's writer is open in the place of its FILE* (tabix.h)
   const bool host_fmt = getenv("TBK_TRACK_HOST_FMT") != nullptr;
-  if ((tf.cov_tx.is_open() || tf.junc_tx.is_open() || tf.samp_tx.is_open()) && !host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
+  if ((tf.cov_tx.is_open() || tf.junc_tx.is_open() || tf.samp_tx.is_open() || tf.strand[0].tx.is_open()) && !host_fmt && !api.track_bgzf) GError("Error: --tabix: libtbk.so lacks tbk_track_bgzf\n");
   if (run.device_text) set_track_names(api, names), names_set_ = true;
 }
 
@@ -778,15 +858,83 @@ void TrackStream::tile(const tbk_cov_in& in, bool last) {
     else if (!device_text(tf.samp, r)) emit_samp_lines(tf.samp, names, so.n_intervals, st.data(), ss.data(), se.data(), sc.data(), sh.data());  // flushCoverage(pair), tiecov.cpp:289
     times.ms_text += ms_since(a);
   }
+  if (tf.strand_on()) {
+    // --strand-cov: the tile divided by splice strand, the coverage chain on each part (intervals only), the rows cut by
+    // the run's clip and written as the coverage rows are.  A tile cut at a bundle head of the whole stream is cut at a bundle head of
+    // each part, so a part's rows over the tiles are its rows over the uncut stream.  (n_bases_ / span_bases_ stay the whole tile's.)
+    const bool host = split_host_asked();
+    tbk_cov_in part[3];
+    CovRecs hrec[3];
+    auto a = clock::now();
+    if (host) {
+      // (the command lines refuse this before a file exists, refuse_split_host_on_device; a caller that did not: the files go with the run)
+      if (in.mem != TBK_MEM_HOST && in.n_records) {
+        tf.discard();
+        GError("Error: TBK_SPLIT_HOST=1 divides host records; the records of this run are on the device\n");
+      }
+      split_strand_host(in, hrec);
+      for (int s = 0; s < 3; ++s) part[s] = hrec[s].as_cov_in();
+    } else {
+      if (!api.cov_split_strand) GError("Error: --strand-cov: the loaded libtbk.so has no tbk_cov_split_strand (an older build?)\n");
+      rc = api.cov_split_strand(ctx, &in, part);
+      if (rc == TBK_E2BIG) GError("Error: input too large for one tile\n");
+      if (rc != 0) GError("Error: GPU strand split failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+    }
+    ms_split_ += ms_since(a);
+    strand_host_ = host;
+    for (int s = 0; s < 3; ++s) {
+      CovSink& k = tf.strand[s];
+      const size_t pn = part[s].n_records, pco = part[s].n_cigar_ops;
+      strand_records_[s] += pn;
+      const size_t ci = 2 * pco + 2 * pn + 16 + extra;
+      std::vector<int32_t> it(ci), is(ci), ie(ci);
+      std::vector<double> iv(ci);
+      tbk_cov_out o;
+      memset(&o, 0, sizeof(o));
+      o.mem = TBK_MEM_HOST;
+      o.cap_intervals = (uint32_t)ci;
+      o.iv_tid = it.data(), o.iv_start = is.data(), o.iv_end = ie.data(), o.iv_val = iv.data();
+      a = clock::now();
+      rc = api.coverage_tile(ctx, &part[s], &o);
+      if (rc == TBK_EFATALOP) GError("ERROR: unknown opcode in a CIGAR string (tiecov accepts M, I, D, N, S only)\n");
+      if (rc != 0) GError("Error: GPU coverage failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+      if (clip) {
+        const tbk_regions* U = clip->U;
+        rc = clip->one ? api.cov_clip(ctx, &o, U->tid[0], U->beg[0], U->end[0]) : api.cov_clip_regions(ctx, &o, U);
+        if (rc != 0) GError("Error: GPU clip failed: %s (%s)\n", api.strerror_(rc), api.last_error(ctx));
+      }
+      ms_strand_cov_ += ms_since(a);
+      tbk_track_rows rcov = rows(TBK_TRACK_COV, o.n_intervals, it.data(), is.data(), ie.data());
+      rcov.val = iv.data();
+      a = clock::now();
+      if (k.f && !device_text(k.f, rcov)) emit_cov_lines(k.f, names, o.n_intervals, it.data(), is.data(), ie.data(), iv.data());
+      if (k.is_bw) {
+        if (run.bw_device && !api.bigwig_build) GError("Error: --bigwig-writer device: libtbk.so lacks tbk_bigwig_build\n");
+        if (only) {
+          tf.write_strand_bigwig(s, o.n_intervals, it.data(), is.data(), ie.data(), iv.data(), run.bw_device ? &api : nullptr);
+        } else {
+          if (run.bw_device) GError("Error: --bigwig-writer device takes the rows of one tile\n");
+          for (uint32_t i = 0; i < o.n_intervals; ++i) k.bw.add((uint32_t)it[i], (uint32_t)is[i], (uint32_t)ie[i], (float)iv[i]);
+        }
+      }
+      if (k.tx.is_open()) tabix(k.tx, rcov, 3 + s);
+      ms_strand_text_ += ms_since(a);
+    }
+  }
 }
 
 void TrackStream::end() {
-  TabixWriter* const tx[3] = {&tf_.cov_tx, &tf_.junc_tx, &tf_.samp_tx};
-  for (int k = 0; k < 3; ++k) {  // (a writer that got rows tile by tile; one that got none is TrackFiles::close's: header, EOF member, empty index)
+  TabixWriter* const tx[6] = {&tf_.cov_tx, &tf_.junc_tx, &tf_.samp_tx, &tf_.strand[0].tx, &tf_.strand[1].tx, &tf_.strand[2].tx};
+  for (int k = 0; k < 6; ++k) {  // (a writer that got rows tile by tile; one that got none is TrackFiles::close's: header, EOF member, empty index)
     std::string err;
     if (tx_started_[k] && !tx[k]->close(err)) GError("Error: writing %s failed (%s)\n", tx[k]->path().c_str(), err.c_str());
   }
+  const bool strand_on = tf_.strand_on();
   tf_.close();
+  if (strand_on && getenv("TBK_TIMING"))
+    fprintf(stderr, "strand phase ms: %s | %llu+ %llu- %llu. records | %.1f | %.1f | %.1f\n", strand_host_ ? "host" : "device",
+            (unsigned long long)strand_records_[0], (unsigned long long)strand_records_[1], (unsigned long long)strand_records_[2], ms_split_, ms_strand_cov_,
+            ms_strand_text_);
   if (run_.depth && run_.depth->on()) {  // (behind the tracks: a run that failed before this left neither table)
     const auto t0 = std::chrono::steady_clock::now();
     const DepthJob& job = *run_.depth;
@@ -837,9 +985,14 @@ void TrackFiles::discard() {
   if (junc) fclose(junc);
   if (samp) fclose(samp);
   cov = junc = samp = nullptr;
-  for (TabixWriter* w : {&cov_tx, &junc_tx, &samp_tx})
+  for (CovSink& k : strand) {
+    if (k.is_bw) (void)k.bw.close(err), k.is_bw = false;
+    if (k.f) fclose(k.f);
+    k.f = nullptr;
+  }
+  for (TabixWriter* w : {&cov_tx, &junc_tx, &samp_tx, &strand[0].tx, &strand[1].tx, &strand[2].tx})
     if (w->is_open()) w->discard();
-  for (const std::string* p : {&cov_name, &junc_name, &samp_name})
+  for (const std::string* p : {&cov_name, &junc_name, &samp_name, &strand[0].name, &strand[1].name, &strand[2].name})
     if (!p->empty() && *p != "-" && *p != "stdout") (void)unlink(p->c_str());
 }
 

@@ -39,17 +39,37 @@ struct TrackApi {
   decltype(&tbk_strerror) strerror_ = nullptr;
   decltype(&tbk_last_error) last_error = nullptr;
   decltype(&tbk_cov_thresholds) cov_thresholds = nullptr;
-  decltype(&tbk_tx_summary) tx_summary = nullptr;  // (the last field: a table filled in field by field without it stays valid)
+  decltype(&tbk_tx_summary) tx_summary = nullptr;
+  decltype(&tbk_cov_split_strand) cov_split_strand = nullptr;  // (the last field: a table filled in field by field without it stays valid)
 };
 
 // The track options of a command line (tiecov -c / -j / -s / -W / --bigwig-writer / --tabix and tiebrush's long spellings of them; each
 // main checks their rules in its own words).  An empty prefix: that track is not written.
 struct TrackOptions {
   std::string cov, junc, samp;
+  std::string strand_cov;  // --strand-cov PREFIX: the coverage of each splice strand in a file of its own
   bool bigwig = false, bw_device = false, tabix = false;
 };
+// `--strand-cov PREFIX` as both command lines refuse it, before any file exists: a prefix of - / stdout (three tracks do not share one
+// standard output), the option given twice (`times`: how often the command line holds it), --ranks (`ranks` > 1).  Errors are fatal.
+void check_strand_cov(const char* prefix, int times, int ranks);
+// TBK_SPLIT_HOST=1 (anything but "0"): the records are divided by split_strand_host.  That loop reads host arrays, so a run whose records
+// stay on the device (`what`: "-r / -R", "--stream") refuses the variable with --strand-cov — here, before any file exists (GError)
+bool split_host_asked();
+void refuse_split_host_on_device(const char* prefix, const char* what);
 // "host" / "device" -> false / true; anything else is fatal (GError)
 bool parse_bigwig_writer(const char* value);
+
+// one coverage sink of --strand-cov: what the coverage track itself has
+struct CovSink {
+  FILE* f = nullptr;
+  BigWigWriter bw;
+  bool is_bw = false;
+  TabixWriter tx;
+  std::string name;
+  bool on() const { return f || is_bw || tx.is_open(); }
+};
+extern const char* const kStrandSuffix[3];  // ".plus", ".minus", ".none": PREFIX<suffix>.bedgraph / .bigwig / .bedgraph.gz
 
 // The open track files.  Coverage goes to stdout for "-" / "stdout", to PREFIX.bigwig with `bigwig`, else to PREFIX.bedgraph; junctions to PREFIX.bed; the sample counts to PREFIX.bedgraph.  Errors are fatal (GError).
 // With `tabix` every text track is PREFIX.bedgraph.gz / PREFIX.bed.gz (BGZF) with its tabix index beside it (tabix.h): the track's
@@ -61,6 +81,10 @@ struct TrackFiles {
   std::vector<uint32_t> bw_lens;  // the chromosome lengths the bigWig was opened with
   std::string cov_name, junc_name, samp_name;  // (junc / samp: the plain files; a tabix track's name is its writer's)
   TabixWriter cov_tx, junc_tx, samp_tx;  // --tabix
+  CovSink strand[3];  // --strand-cov: the records with splice strand '+', '-', and every other, each a coverage track under -c's rules
+  bool strand_on() const { return strand[0].on() || strand[1].on() || strand[2].on(); }
+  // write_bigwig for the sink of class s
+  void write_strand_bigwig(int s, uint32_t n, const int32_t* tid, const int32_t* start, const int32_t* end, const double* val, const TrackApi* dev);
   void open(const TrackOptions& o, const std::vector<std::string>& names, const std::vector<uint32_t>& lens);
   void close_bigwig();  // (after every interval went to bw)
   // The coverage rows into the bigWig and the file closed (flushCoverage(bigWigFile_t*), tiecov.cpp:243-275: the value as a float).
@@ -205,13 +229,18 @@ struct CovRecs {
   std::vector<double> yc;
   std::vector<int64_t> yx;
   std::vector<uint8_t> strand;
-  tbk_cov_in as_cov_in() const;
+  tbk_cov_in as_cov_in() const;  // (an empty flag column travels as NULL: every record counts)
   // ng further records, rec(g) in file order: tid, pos, flag and the splice strand (bam.h) on `threads` workers, the CIGAR offsets by
   // one serial pass over the counts, then the operations on the workers again.  values(g, view, &yc, &yx) gives a record's weights.
   // false: the CIGAR operations of all records no longer fit 32 bits (the message is the caller's)
   bool append(uint32_t ng, const std::function<RecView(uint32_t)>& rec, const std::function<void(uint32_t, const RecView&, double*, int64_t*)>& values,
               int threads);
 };
+
+// tbk_cov_split_strand's rule by a plain loop over HOST arrays (TBK_SPLIT_HOST=1, libtbh's tbh_split_strand_host): out[0] the mapped
+// records (flag bit 0x4 clear; no flag column: all) with strand '+', out[1] '-', out[2] every other byte, each in the input's order with
+// its CIGAR CSR rebuilt from 0 and no flag column; yc / yx are copied where the input has them
+void split_strand_host(const tbk_cov_in& in, CovRecs out[3]);
 
 // the cut of a region run: the table, through the one-region entries (one: the table is the region itself, which may be empty) or the
 // table entries
@@ -266,7 +295,11 @@ class TrackStream {
   int64_t first_junc_ = 1;
   uint64_t n_bases_ = 0, span_bases_ = 0, tiles_ = 0;
   bool names_set_ = false;  // the reference names are on the context
-  bool tx_started_[3] = {false, false, false};  // --tabix in a run of several tiles: the track's writer has its header line and first rows
+  bool tx_started_[6] = {false, false, false, false, false, false};  // --tabix in a run of several tiles: the track's writer (cov, junc, samp, the three strands) has its header line and first rows
+  // --strand-cov: the figures of the "strand phase ms" line (TBK_TIMING), added up over the tiles
+  double ms_split_ = 0, ms_strand_cov_ = 0, ms_strand_text_ = 0;
+  uint64_t strand_records_[3] = {0, 0, 0};
+  bool strand_host_ = false;
   DepthTable depth_;                 // --depth-summary: the run's table so far
   std::vector<uint64_t> fd_covered_, fd_ge_;  // --feature-depth: the one tile's columns, written by end()
   double ms_depth_ = 0;

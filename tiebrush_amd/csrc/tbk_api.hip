@@ -647,6 +647,7 @@ void tbk_destroy(tbk_ctx* ctx) {
   tbk_ix_free(ctx);
   tbk_bw_free(ctx);
   tbk_cov_stream_free(ctx);
+  tbk_strand_split_free(ctx);
   tbk_stager_free(ctx);
   if (ctx->d_scalars) (void)hipFree(ctx->d_scalars);
   if (ctx->h_scalars) (void)hipHostFree(ctx->h_scalars);

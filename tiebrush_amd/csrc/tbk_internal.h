@@ -202,12 +202,14 @@ struct tbk_ctx {
   size_t fmt_pin_cap = 0;
   void* bw = nullptr;            // the host section tables of the last tbk_bigwig_build (bigwig.hip)
   void* cov_stream = nullptr;    // the carry (double-buffered) and the view of tbk_cov_stream_push (stream.hip)
+  void* strand_split = nullptr;  // the three views of the last tbk_cov_split_strand (strandsplit.hip)
 };
 void tbk_stager_free(tbk_ctx* ctx);
 void tbk_enc_free(tbk_ctx* ctx);
 void tbk_ix_free(tbk_ctx* ctx);
 void tbk_bw_free(tbk_ctx* ctx);
 void tbk_cov_stream_free(tbk_ctx* ctx);
+void tbk_strand_split_free(tbk_ctx* ctx);
 // baix.hip: the index part of a run the encoder has just packed.  All pointers are device memory of the encoder, alive until its next call.
 struct TbkIxIn {
   uint32_t n;             // records
